@@ -196,9 +196,9 @@ def parse():
                     help="order of the tracks of a stream: raster (the synthetic grid, default) or shuffled (what goodFeaturesToTrack's sort by corner "
                          "response gives on real footage: neighbouring workgroups read unrelated windows)")
     ap.add_argument("--ring", type=int, default=60, help="distinct synthetic frames kept in HBM (one motion period)")
-    ap.add_argument("--min-seconds", type=float, default=2.0,
+    ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="keep timing further blocks of --steps steps until the timed region is at least this long (an external sampler can "
-                         "then corroborate the run); 0 = exactly --steps steps")
+                         "then corroborate the run); 0 (default) = exactly --steps steps")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of each cpu_baseline leg (0 disables)")
     ap.add_argument("--exchange-every", type=int, default=30)
     ap.add_argument("--fine-max-count", type=int, default=0, help="calibration aid (tools/pmc_lk_calib.sh): cap the Newton iterations of the fine LK stage")
@@ -221,6 +221,9 @@ def parse():
     ap.add_argument("--verbose", action="store_true", help="wall-clock stamps of the legs on stderr")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
                     help="file that receives the FULL record (roofline_detail, every extras / BA leg); stdout carries only the compact contract line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the packed track state of every resident stream of rank 0) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB: two builds run with the same arguments can be compared output for output")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST ONLY: allow more ranks than visible GPUs (ranks share devices round-robin; needs --backend gloo, RCCL refuses duplicate devices)")
     return ap.parse_args()
@@ -311,6 +314,44 @@ def ba_cpu_baseline(out, first, cpu_seconds):
                                sample=f"{done} LM iterations of the same C5 window, structured (Schur) NumPy restatement, {dt:.1f} s; the dense "
                                       "reference path (utils/NLS.py:228-235) is infeasible at this size")
     out["gpu_over_cpu"] = round(out["iters_per_s"] / out["cpu_baseline"]["value"], 1)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(wl, path):
+    """--dump-outputs: the state the timed path hands its caller after the last timed step, one .npy per array (float32 where the library computes
+    float32, float64 otherwise), axis 0 = resident stream.  From the packed per-stream record (vh_session_pack_state, the record the multi-GPU
+    exchange carries): p [S, N, 2] positions of the live tracks (NaN past n_cur), ids [S, N] their track ids (-1 past n_cur), t [S, 3] camera
+    position, n_cur / n_pose / frame_i / klt_flags [S]; res [S] the rms reprojection residual in float64.  The inputs are fixed by the arguments (seeded
+    frames and tracks, exactly --steps timed steps), so two runs with the same arguments differ only where the builds do.  Past DUMP_MAX_BYTES a fixed,
+    seeded sample of the streams is written; `streams` names the ones written."""
+    from velocity_amd import _lib as L
+
+    S, N, SG = wl.S, wl.N, wl.SG
+    per_stream = 4 * 2 * N + 8 * N + 4 * 3 + 8 * 6  # p, ids, t, and six float64 scalars
+    budget = DUMP_MAX_BYTES - 16 * 1024  # room for the .npy headers
+    keep = np.arange(S)
+    if S * per_stream > budget:
+        keep = np.sort(np.random.default_rng(0).choice(S, size=budget // per_stream, replace=False))
+    torch.cuda.synchronize()
+    rec = torch.empty((S, 8 + 3 * N), dtype=torch.float32, device=wl.frames.device)
+    for g, ses in enumerate(wl.sessions):
+        L.check(ses.lib.vh_session_pack_state(ses.handle, L.dptr(rec[g * SG:(g + 1) * SG]), L.stream_ptr()), "vh_session_pack_state")
+    torch.cuda.synchronize()
+    rec = rec.cpu().numpy()[keep]
+    n_cur = rec[:, 0].astype(np.int64)
+    live = np.arange(N)[None, :] < n_cur[:, None]
+    p = rec[:, 8:8 + 2 * N].reshape(-1, N, 2).copy()
+    p[~live] = np.nan
+    ids = np.where(live, rec[:, 8 + 2 * N:].view(np.int32), -1).astype(np.float64)
+    res = np.array([wl.sessions[b // SG]._rd(wl.sessions[b // SG].view(b % SG).res, 1, np.float64)[0] for b in keep])
+    arrays = dict(streams=keep.astype(np.float64), p=p, ids=ids, t=rec[:, 4:7].copy(), res=res, n_cur=rec[:, 0].astype(np.float64),
+                  n_pose=rec[:, 1].astype(np.float64), frame_i=rec[:, 2].astype(np.float64), klt_flags=rec[:, 3].astype(np.float64))
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return dict(dir=path, streams=int(len(keep)), of_streams=S, bytes=int(sum(x.nbytes for x in arrays.values())), files=sorted(arrays))
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -582,6 +623,7 @@ def main():
     m = wl.measure(a.steps, a.warmup, a.min_seconds, barrier, reduce_max, ex)
     st = m["st"]
     stamp("headline measured")
+    dumped = dump_outputs(wl, a.dump_outputs) if a.dump_outputs and rank == 0 else None  # before verify(), which steps the sessions further
 
     if rank == 0:
         elapsed, timed = m["elapsed"], m["timed_steps"]
@@ -609,6 +651,8 @@ def main():
         out["headline_hbm"] = headline_hbm(cfg, value / world)
         out["build"] = L.build_info()  # which binary ran: vh_build_id() of the loaded library vs the hash of the tree's sources
         out["build_id"] = out["build"]["build_id"]
+        if dumped:
+            out["dump_outputs"] = dumped
         cpu_args = (cfg, wl.K, wl.frames[: a.ring], wl.p0, wl.p3, wl.vp, wl.lkc, wl.lkf)
         if a.verify_frames > 0:
             out["verified"] = verify(wl, wl.done_steps + 1, nframes=a.verify_frames)

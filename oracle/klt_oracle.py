@@ -16,25 +16,45 @@ LK_COARSE = dict(win=15, max_level=4, max_count=10, eps=0.1)  # utils/KLT.py:106
 LK_FINE = dict(win=51, max_level=0, max_count=30, eps=0.001)  # utils/KLT.py:107
 
 
+def _user_build_dir():
+    """Where this user builds the library when oracle/_build is not writable (a checkout owned by another user, or read-only): a directory of
+    its own under the system temp directory."""
+    import tempfile
+
+    d = os.path.join(tempfile.gettempdir(), f"velocity_oracle_{os.getuid()}")
+    os.makedirs(d, mode=0o700, exist_ok=True)
+    if os.stat(d).st_uid != os.getuid():
+        raise RuntimeError(f"{d} belongs to another user: cannot build the oracle there")
+    return d
+
+
 def build(native=False, force=False):
-    """Compile klt_oracle.c with gcc (oracle/Makefile)."""
+    """Compile klt_oracle.c with gcc (oracle/Makefile) into oracle/_build, or -- when this user cannot write there -- into _user_build_dir().
+    An up-to-date library in either place is used as it is."""
     name = "libklt_oracle_native.so" if native else "libklt_oracle.so"
-    path = os.path.join(_HERE, "_build", name)
     src = os.path.join(_HERE, "klt_oracle.c")
-    stamp = path + ".host"
-    if native:
-        # -march=native code must not travel to another machine (the build tree is copied to the GPU box as it is)
-        host = _host_signature()
-        if not os.path.exists(stamp) or open(stamp).read() != host:
-            force = True
-    if force or not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src):
-        cmd = ["make", "-C", _HERE, "-s"] + (["NATIVE=1"] if native else [])
-        if force:
+    # -march=native code must not travel to another machine (the build tree is copied to the GPU box as it is): a stamp names the host it was built on
+    host = _host_signature() if native else None
+
+    def current(path):
+        if not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src):
+            return False
+        return not native or (os.path.exists(path + ".host") and open(path + ".host").read() == host)
+
+    tree = os.path.join(_HERE, "_build")
+    writable = os.access(tree, os.W_OK | os.X_OK) if os.path.isdir(tree) else os.access(_HERE, os.W_OK | os.X_OK)
+    if not force and current(os.path.join(tree, name)):
+        return os.path.join(tree, name)
+    out = tree if writable else _user_build_dir()
+    path = os.path.join(out, name)
+    if force or not current(path):
+        cmd = ["make", "-C", _HERE, "-s", f"BUILD={out}"] + (["NATIVE=1"] if native else [])
+        if force or (native and os.path.exists(path)):  # built for another host (stale stamp): make's mtime check cannot see that
             cmd.insert(3, "-B")
         subprocess.run(cmd, check=True)
         if native:
-            with open(stamp, "w") as f:
-                f.write(_host_signature())
+            with open(path + ".host", "w") as f:
+                f.write(host)
     return path
 
 

@@ -181,3 +181,16 @@ def test_compact_line_with_multi_gpu_summary_and_oversized_extras_still_fits():
     d = json.loads(text)
     assert len(text.encode()) <= 4096
     assert d["multi_gpu"]["ranks_seen_in_last_gather"] == 8 and d["roofline"]["frac"] and d["cpu_baseline"]["value"] > 0 and "sample" not in d["cpu_baseline"]
+
+
+def test_steps_set_the_timed_steps_and_outputs_can_be_dumped(monkeypatch):
+    """By default --steps is the number of timed steps (no further blocks up to a minimum duration), and --dump-outputs takes a directory."""
+    import sys
+
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "3"])
+    a = b.parse()
+    assert a.steps == 7 and a.warmup == 3 and a.min_seconds == 0 and a.dump_outputs == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "/tmp/out"])
+    assert b.parse().dump_outputs == "/tmp/out"
+    assert b.DUMP_MAX_BYTES == 64 << 20

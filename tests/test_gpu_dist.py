@@ -1,7 +1,8 @@
-"""N > 1 on ONE MI355X: two ranks share cuda:0 and talk over gloo (which stages device tensors through the host), so every
+"""N > 1 on ONE MI355X: two or three ranks share cuda:0 and talk over gloo (which stages device tensors through the host), so every
 multi-rank code path -- the point-sharded BA with its two all-reduces per iteration and the ragged point gather, the
 track-state all-gather of real tracker sessions, and bench.py's own rank launcher -- executes before an 8-GPU node ever
-sees it.  RCCL itself refuses two ranks on one device; its one-rank path is covered in test_gpu_nls.py / test_gpu_driver.py."""
+sees it.  The eight-rank tests run one rank per device and skip on a node with fewer than eight GPUs.  RCCL itself refuses two
+ranks on one device; its one-rank path is covered in test_gpu_nls.py / test_gpu_driver.py."""
 import json
 import os
 import subprocess
@@ -21,6 +22,16 @@ _COMMON = (
     "torch.cuda.set_device(0)\n"
     "dist.init_process_group('gloo', rank=rank, world_size=world)\n"
 )
+
+
+def _need_gpus(n):
+    """The eight-rank topologies run one rank per device, as on the 8-GPU node of config 4 (eight ranks on one device would be nine processes
+    holding it, the test process included).  Decided before any rank starts."""
+    import torch
+
+    have = torch.cuda.device_count()
+    if have < n:
+        pytest.skip(f"needs {n} GPUs (one per rank), found {have}")
 
 
 def _run_ranks(tmp_path, body, world=2, timeout=600, extra_env=None):
@@ -164,11 +175,13 @@ def test_bench_refuses_more_ranks_than_gpus():
 
 
 def test_c4_topology_eight_ranks_one_stream_each_exchange_with_live_state(tmp_path):
-    """BASELINE config 4 as specified, as far as one device allows: world = 8 (gloo, all ranks on cuda:0), ONE 1080p-shaped stream per rank
+    """BASELINE config 4 as specified: world = 8 (gloo, one rank per device), ONE 1080p-shaped stream per rank
     (16:9 at reduced size), 31 tracked frames with the all-gather of the packed track state every 30 frames, so a real exchange fires on
     live state (frame 30).  Every rank checks ALL EIGHT gathered records bit for bit against per-stream SessionOracles (CPU, the checker),
-    and the exchange's own record must say world_size 8 with eight device entries."""
+    and the exchange's own record must say world_size 8 with eight device entries.  Rank r runs on cuda:r (_need_gpus)."""
+    _need_gpus(8)
     body = (
+        "torch.cuda.set_device(rank)\n"
         "from velocity_amd import synth, _lib as L, dist as vd\n"
         "from velocity_amd.driver import TrackerSession\n"
         "from oracle.session_oracle import SessionOracle\n"
@@ -262,9 +275,10 @@ def test_c4_full_size_two_ranks_exchange_at_frame_30(tmp_path):
 
 
 def test_bench_eight_ranks_oversubscribed_prints_n_gpus_8(tmp_path):
-    """`python bench.py --gpus 8 --oversubscribe --backend gloo`: the driver's 8-GPU launch shape (8 ranks, weak scaling, exchange every 30
-    frames) on one device; the line says n_gpus 8 and its dist record shows 8 ranks seen in the last gather."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--oversubscribe", "--streams", "1", "--steps", "32",
+    """`python bench.py --gpus 8 --backend gloo`: the driver's 8-GPU launch shape (8 ranks, weak scaling, exchange every 30
+    frames); the line says n_gpus 8 and its dist record shows 8 ranks seen in the last gather.  One rank per device (_need_gpus)."""
+    _need_gpus(8)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--streams", "1", "--steps", "32",
            "--warmup", "2", "--no-ba", "--cpu-seconds", "0", "--exchange-every", "30", "--min-seconds", "0", "--no-extras", "--verify-frames", "2",
            "--detail", str(tmp_path / "detail.json")]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}

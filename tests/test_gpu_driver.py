@@ -182,3 +182,48 @@ def test_bench_prints_exactly_one_compact_contract_line(tmp_path):
     assert d["verified"]["bit_exact"] is True and d["verified"]["pose_within_1e5"] is True
     full = json.load(open(detail))
     assert full["value"] == d["value"] and "roofline_detail" in full and full["roofline_detail"]["kernels"]
+
+
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat_exactly(tmp_path):
+    """`bench.py --dump-outputs DIR`: exactly --steps timed steps, then the packed state of every stream after the last of them as float32 / float64 .npy
+    files of at most 64 MB.  Two runs with the same arguments write the same arrays; stream 0's entries agree with the run's own record; and the four
+    streams (each at its own phase of the ring, so no two alike) come out in the same order whether they run as two sessions of two or as one session
+    of four, i.e. the dump's row b is stream b across session groups."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    steps, warmup, S = 9, 3, 4
+    runs = []
+    for k, groups in enumerate((2, 2, 1)):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--streams", str(S), "--groups", str(groups), "--steps", str(steps), "--warmup",
+                            str(warmup), "--no-extras", "--no-ba", "--cpu-seconds", "0", "--dump-outputs", str(d),
+                            "--detail", str(tmp_path / f"detail{k}.json")], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        line = json.loads(r.stdout.splitlines()[-1])
+        assert line["steps"] == steps and line["timed_steps"] == steps and line["ms_per_step"] > 0 and line["config"]["stream_groups"] == groups
+        got = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert {"p", "ids", "t", "res", "n_cur", "frame_i", "streams"} <= set(got)
+        assert all(v.dtype in (np.float32, np.float64) for v in got.values()) and sum(v.nbytes for v in got.values()) <= 64 << 20
+        runs.append((line, got))
+    (line, a), (_, b), (_, c) = runs
+    full = json.load(open(tmp_path / "detail0.json"))
+    assert full["dump_outputs"]["streams"] == S and full["dump_outputs"]["bytes"] <= 64 << 20
+    assert set(a) == set(b) == set(c)
+    for name in a:
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    assert np.array_equal(a["streams"], np.arange(S)) and a["p"].shape == (S, 2000, 2) and a["t"].dtype == np.float32
+    assert np.all(a["frame_i"] == warmup + steps)  # the state after the last TIMED step (the parity replay runs after the dump)
+    n0 = int(a["n_cur"][0])
+    assert n0 / 2000 == pytest.approx(line["tracks_alive_frac"], abs=1e-4) and np.isfinite(a["p"][0, :n0]).all() and np.isnan(a["p"][0, n0:]).all()
+    assert np.allclose(a["t"][0], full["pose_t"], atol=1e-5) and a["res"][0] == pytest.approx(full["rms_residual_px"], abs=1e-5)
+    # stream order across session groups: the tracks are bit-exact per stream (the oracle contract), so one session of four gives the same rows
+    assert all(not np.array_equal(a["p"][i], a["p"][j], equal_nan=True) for i in range(S) for j in range(i))
+    for name in ("p", "ids", "n_cur", "n_pose", "frame_i"):
+        np.testing.assert_array_equal(c[name], a[name], err_msg=name)
+    np.testing.assert_allclose(c["t"], a["t"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(c["res"], a["res"], rtol=1e-5)

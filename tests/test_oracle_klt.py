@@ -254,3 +254,31 @@ def test_hard_scene_fires_the_gates_and_is_periodic():
     s2, s3 = c["stage2_roi_translation_lk_fb1"], c["stage3_affine_warp_lk_fb03"]
     assert s3["fwd_status"] + s2["fwd_status"] > 0 and s3["fb"] > 5 and s2["fb"] > 5
     assert 0.8 < c["survive"] / c["tracks"] < 0.995 and not c["coarse_affine_failure"]
+
+
+def test_native_build_goes_to_a_user_directory_when_the_tree_is_not_writable(tmp_path, monkeypatch):
+    """bench.py's CPU baseline compiles the -march=native oracle where it runs; in a checkout this user cannot write (oracle/_build owned by whoever
+    built the tree) the library goes to a directory of the user's own, and a current library there is reused.  Runs on a private copy of oracle/
+    (sources only), so what the real oracle/_build holds plays no part."""
+    import ctypes
+    import os
+    import shutil
+    import tempfile
+
+    here = tmp_path / "oracle"
+    here.mkdir()
+    for f in ("Makefile", "klt_oracle.c"):
+        shutil.copy2(os.path.join(os.path.dirname(KO.__file__), f), here / f)
+    monkeypatch.setattr(KO, "_HERE", str(here))
+    ro = (str(here), str(here / "_build"))
+    real_access = os.access
+    monkeypatch.setattr(os, "access", lambda p, mode, **kw: False if os.path.abspath(p) in ro else real_access(p, mode, **kw))
+    monkeypatch.setattr(tempfile, "gettempdir", lambda: str(tmp_path / "tmp"))
+    (tmp_path / "tmp").mkdir()
+    path = KO.build(native=True)
+    assert path == os.path.join(str(tmp_path / "tmp"), f"velocity_oracle_{os.getuid()}", "libklt_oracle_native.so")
+    assert not (here / "_build").exists()
+    assert open(path + ".host").read() == KO._host_signature()
+    mtime = os.path.getmtime(path)
+    assert KO.build(native=True) == path and os.path.getmtime(path) == mtime
+    assert KO.set_threads(ctypes.CDLL(path), 1) == 1
