@@ -99,7 +99,9 @@ VH_API int vh_bounding_rect(vh_ctx* ctx, const float* p, int n, int imw, int imh
 VH_API int vh_pyr_lk(vh_ctx* ctx, const uint8_t* im1, const uint8_t* im2, int w, int h, int stride1, int stride2, const float* p1,
                      int n, const vh_lk_params* lk_host, float fbt, float* p2, uint8_t* v, float* err, float* fbe, void* stream);
 /* cv2.estimateAffine2D(from[valid], to[valid], method=RANSAC), utils/KLT.py:116,127 (deterministic stand-in, see
- * DESIGN.md).  valid may be NULL (all).  Outputs: M device double[6] (2x3), inl device uint8[n], status device int[1]. */
+ * DESIGN.md).  valid may be NULL (all).  Outputs: M device double[6] (2x3), inl device uint8[n], status device int[1]: 1 = model found,
+ * 0 = none, -1 = the inliers' refit is out of the representable range (|coordinate| >= 2^31, or a centred coordinate >= sqrt(2^42 / inliers): no
+ * inliers, no model). */
 VH_API int vh_ransac_affine(vh_ctx* ctx, const float* from, const float* to, const uint8_t* valid, int n, double* M, uint8_t* inl,
                             int* status, void* stream);
 /* KLTmain(im, im0, im0_small, p0), utils/KLT.py:99-134, for stream slot `slot` of the workspace.

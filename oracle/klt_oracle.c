@@ -637,6 +637,25 @@ static int hypothesis(const float *from, const float *to, int m, uint32_t hyp, d
 
 static int64_t fixq(double v, int bits) { return (int64_t)llrint(ldexp(v, bits)); }
 
+/* The refit's sums (the device's refit_sums computes the same doubles).  Means: a coordinate's v = round(x 2^32) is summed as hi = v >> 32 and
+ * lo = v mod 2^32; both int64 sums stay exact for any count below 2^31, however far from the origin the points lie.  mean_total rounds hi 2^32 + lo to
+ * double once: (double) of the plain int64 sum wherever that did not overflow.  Moments: plain int64 sums of round(p 2^20), p = a product of two
+ * centred coordinates, each below lim2 = 2^42 / count in square, so every sum of |p| stays below 2^42.  Out of range the refit is unrepresentable. */
+#define MEAN_LIM 2147483648.0
+static inline int mean_add(int64_t hl[2], float x)
+{
+    if (!(fabsf(x) < (float)MEAN_LIM)) return 1;
+    int64_t q = fixq(x, 32);
+    hl[0] += q >> 32;
+    hl[1] += q & 0xFFFFFFFFll;
+    return 0;
+}
+static inline double mean_total(const int64_t hl[2])
+{
+    int64_t hi = hl[0] + (hl[1] >> 32), lo = hl[1] & 0xFFFFFFFFll; /* carry: |hi| < 2^53, lo < 2^32, both exact in double */
+    return ldexp(ldexp((double)hi, 32) + (double)lo, -32);
+}
+
 /* ---- OpenCV-style refinement of the RANSAC model (sensitivity mode, g_refine_mode == 1) ---------------------------------------- */
 /* Affine2DRefineCallback: residuals (M x - u, per inlier, 2 rows) and their Jacobian w.r.t. the 6 entries of M (linear). */
 static double lm_affine_residual(const float *from, const float *to, const uint8_t *inl, int m, const double h[6], double JtJ[36], double Jtr[6])
@@ -726,7 +745,8 @@ static void lm_refine_affine(const float *from, const float *to, const uint8_t *
     }
 }
 
-/* from/to: m compacted pairs.  Out: M (2x3 row-major, float64), inl (m bytes).  Returns 1 on success. */
+/* from/to: m compacted pairs.  Out: M (2x3 row-major, float64), inl (m bytes).  Returns 1 on success, 0 when no model is found, -1 when the
+ * inliers' refit is out of the representable range (see below). */
 KO_API int ko_ransac_affine(const float *from, const float *to, int m, double Mout[6], uint8_t *inl, int *iters_used)
 {
     for (int i = 0; i < m; i++) inl[i] = 0;
@@ -757,24 +777,29 @@ KO_API int ko_ransac_affine(const float *from, const float *to, int m, double Mo
     hypothesis(from, to, m, (uint32_t)best, M);
     for (int i = 0; i < m; i++) inl[i] = (uint8_t)is_inlier(M, from[2 * i], from[2 * i + 1], to[2 * i], to[2 * i + 1]);
 
-    /* least-squares refit on the inliers; every sum is an exact int64 fixed-point sum (order independent) */
-    int64_t sx = 0, sy = 0, su = 0, sv = 0;
+    /* least-squares refit on the inliers; every sum is exact (order independent).  Input whose terms do not fit (a coordinate >= 2^31, a centred
+     * coordinate beyond sqrt(2^42 / count): 14 800 px at 20 000 inliers) has no representable refit: -1, no inliers, no model. */
+    int64_t s1[4][2] = {{0}}, q[7] = {0};
+    int bad = 0;
     for (int i = 0; i < m; i++)
-        if (inl[i]) {
-            sx += fixq(from[2 * i], 32); sy += fixq(from[2 * i + 1], 32);
-            su += fixq(to[2 * i], 32);   sv += fixq(to[2 * i + 1], 32);
-        }
+        if (inl[i])
+            bad |= mean_add(s1[0], from[2 * i]) | mean_add(s1[1], from[2 * i + 1]) | mean_add(s1[2], to[2 * i]) | mean_add(s1[3], to[2 * i + 1]);
     double cnt = (double)best_count;
-    double mx = ldexp((double)sx, -32) / cnt, my = ldexp((double)sy, -32) / cnt;
-    double mu = ldexp((double)su, -32) / cnt, mv = ldexp((double)sv, -32) / cnt;
-    int64_t q[9] = {0};
-    for (int i = 0; i < m; i++)
+    double mx = mean_total(s1[0]) / cnt, my = mean_total(s1[1]) / cnt;
+    double mu = mean_total(s1[2]) / cnt, mv = mean_total(s1[3]) / cnt;
+    double lim2 = 4398046511104.0 / cnt; /* 2^42 / count */
+    for (int i = 0; i < m && !bad; i++)
         if (inl[i]) {
             double x = from[2 * i] - mx, y = from[2 * i + 1] - my, u = to[2 * i] - mu, v = to[2 * i + 1] - mv;
+            if (!(x * x < lim2 && y * y < lim2 && u * u < lim2 && v * v < lim2)) { bad = 1; break; }
             q[0] += fixq(x * x, 20); q[1] += fixq(x * y, 20); q[2] += fixq(y * y, 20);
             q[3] += fixq(x * u, 20); q[4] += fixq(y * u, 20);
             q[5] += fixq(x * v, 20); q[6] += fixq(y * v, 20);
         }
+    if (bad) {
+        for (int i = 0; i < m; i++) inl[i] = 0;
+        return -1;
+    }
     double Sxx = ldexp((double)q[0], -20), Sxy = ldexp((double)q[1], -20), Syy = ldexp((double)q[2], -20);
     double Sxu = ldexp((double)q[3], -20), Syu = ldexp((double)q[4], -20), Sxv = ldexp((double)q[5], -20), Syv = ldexp((double)q[6], -20);
     double det = Sxx * Syy - Sxy * Sxy;
@@ -793,6 +818,9 @@ KO_API int ko_ransac_affine(const float *from, const float *to, int m, double Mo
 }
 
 /* mean of (p - p0) over valid points, float32 differences summed exactly in 2^-32 fixed point (KLT.py:121-123) */
+/* No overflow here, unlike the refit's coordinate sums: the terms are displacements, not coordinates.  A track is valid only if the coarse LK kept
+ * it, and LK keeps a point only while both ends lie within a window of the frame.  So |dx| < w + 4 win; the int64 sum needs n (w + 4 win) >= 2^31
+ * to overflow, e.g. 250 000 tracks on an 8K frame. */
 static void mean_translation(const float *p0, const float *p, const uint8_t *v, int n, double out[2], int *count)
 {
     int64_t sx = 0, sy = 0;
@@ -907,7 +935,7 @@ KO_API int ko_klt_main(const uint8_t *im, const uint8_t *im0, const uint8_t *im0
     for (int i = 0; i < 2 * n; i++) p[i] = p[i] / 0.25f;
     double M[6];
     int m = compact_pairs(p0, p, v, n, ca, cb, idx);
-    if (ko_ransac_affine(ca, cb, m, M, inl, NULL)) {
+    if (ko_ransac_affine(ca, cb, m, M, inl, NULL) > 0) {
         for (int k = 0; k < m; k++) v[idx[k]] = inl[k];
     } else {
         for (int i = 0; i < n; i++) v[i] = 0;
@@ -933,7 +961,7 @@ KO_API int ko_klt_main(const uint8_t *im, const uint8_t *im0, const uint8_t *im0
     int ok = 0;
     if (nv > 10) {
         m = compact_pairs(p0, p, v, n, ca, cb, idx);
-        ok = ko_ransac_affine(ca, cb, m, M, inl, NULL);
+        ok = ko_ransac_affine(ca, cb, m, M, inl, NULL) > 0;
     }
     if (!ok) {
         flags |= 1;
@@ -961,6 +989,12 @@ KO_API void ko_klt_regional(const uint8_t *im0, const uint8_t *im, int w, int h,
 }
 
 KO_API double ko_det_log(double x) { return det_log(x); }
+/* the adaptive iteration count of the selection rule (cv::RANSACUpdateNumIters for 3-point models), for tests */
+KO_API int ko_ransac_update_iters(double conf, double ep, int max_iters) { return ransac_update_iters(conf, ep, max_iters); }
+KO_API void ko_ransac_update_iters_n(double conf, const double *ep, int n, int max_iters, int *out)
+{
+    for (int i = 0; i < n; i++) out[i] = ransac_update_iters(conf, ep[i], max_iters);
+}
 
 /* cv2.cvtColor(BGR2GRAY) for 8-bit images (vidExample.py:91): OpenCV 4.x fixed point, 15 fractional bits (unpinned like the
  * rest of the OpenCV half) */

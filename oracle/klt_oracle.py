@@ -77,6 +77,8 @@ def lib(native=False):
         L = C.CDLL(path)
         L.ko_det_log.restype = C.c_double
         L.ko_det_log.argtypes = [C.c_double]
+        L.ko_ransac_update_iters.restype = C.c_int
+        L.ko_ransac_update_iters.argtypes = [C.c_double, C.c_double, C.c_int]
         if native:
             return L
         _LIB = L
@@ -232,7 +234,19 @@ def ransac_affine(src, dst, L=None):
     inl = np.zeros(max(m, 1), np.uint8)
     it = C.c_int()
     ok = L.ko_ransac_affine(ps, pd, m, M.ctypes.data_as(C.POINTER(C.c_double)), inl.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(it))
+    if ok < 0:
+        raise ValueError("ransac_affine: the inliers' refit is out of the representable range (|coordinate| >= 2^31, or a centred coordinate >= sqrt(2^42 / inliers))")
     return (M.reshape(2, 3) if ok else None), inl[:m].astype(bool), it.value
+
+
+def ransac_update_iters(ep, max_iters=2000, conf=0.99, L=None):
+    """The selection rule's adaptive iteration count (cv::RANSACUpdateNumIters, 3-point model) for each outlier ratio in ep -> int32 array."""
+    L = L or lib()
+    ep = np.ascontiguousarray(ep, np.float64).ravel()
+    out = np.empty(ep.size, np.int32)
+    L.ko_ransac_update_iters_n(C.c_double(conf), ep.ctypes.data_as(C.c_void_p), C.c_int(ep.size), C.c_int(int(max_iters)),
+                               out.ctypes.data_as(C.c_void_p))
+    return out
 
 
 class _Stages(C.Structure):

@@ -69,7 +69,9 @@ def estimateAffine2D(src, dst):
     L.check(ws.lib.vh_ransac_affine(ws.handle, L.dptr(s), L.dptr(d), None, m, L.dptr(M), L.dptr(inl), L.dptr(st), L.stream_ptr()),
             "vh_ransac_affine")
     ok = int(st.item())
-    return (M.cpu().numpy().reshape(2, 3) if ok else None), inl[:m].cpu().numpy().reshape(-1, 1)
+    if ok < 0:
+        raise ValueError("estimateAffine2D: the inliers' refit is out of the representable range (|coordinate| >= 2^31, or a centred coordinate >= sqrt(2^42 / inliers))")
+    return (M.cpu().numpy().reshape(2, 3) if ok > 0 else None), inl[:m].cpu().numpy().reshape(-1, 1)
 
 
 def KLTregional(im0, im, p0, T, lk_param, fbt=1.0, translateFlag=False):

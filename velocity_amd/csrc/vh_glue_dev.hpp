@@ -70,6 +70,8 @@ __device__ __forceinline__ void klt_glue1_body(StreamWS& ws)
         mnx = fminf(mnx, x0); mxx = fmaxf(mxx, x0); mny = fminf(mny, y0); mxy = fmaxf(mxy, y0);
         if (B.v_small[i]) {
             const float dx = __fsub_rn(B.p_small[2 * i], x0), dy = __fsub_rn(B.p_small[2 * i + 1], y0);
+            // (plain int64 sums, unlike the RANSAC refit's split ones: the terms are displacements of tracks the coarse LK kept, both ends within
+            // a window of the frame, so |dx| < w + 4 win and an overflow needs n (w + 4 win) >= 2^31 -- 250 000 tracks on an 8K frame)
             s[0] += vh_fixq((double)dx, 32); s[1] += vh_fixq((double)dy, 32); s[2] += 1;
         }
     }
@@ -164,7 +166,7 @@ __device__ __forceinline__ void klt_glue2_body(StreamWS& ws)
     const KltIO& io = ws.io;
     const StreamBufs& B = ws.bufs;
     double M[6];
-    if (ws.rstatus) {
+    if (ws.rstatus > 0) {  // (-1: the refit was out of range -- a failure like 0)
         for (int k = 0; k < 6; k++) M[k] = ws.M[k];
     } else {
         // "KLT coarse-affine failure" (KLT.py:128-130): the SURF fallback is out of scope -> keep the translation

@@ -3,7 +3,7 @@
 // sample of hypothesis h comes from a counter-based hash; all VH_RANSAC_ITERS hypotheses are scored in parallel (one
 // wavefront each) and a single thread then replays OpenCV's sequential "best so far + adaptive iteration count" rule
 // over the scores, which gives exactly the result of the sequential algorithm.  The refit sums are exact int64
-// fixed-point sums, so the result does not depend on reduction order.
+// fixed-point sums (refit_split), so the result does not depend on reduction order.
 #include <atomic>
 #include "vh_kernels.hpp"
 #include "vh_glue_dev.hpp"
@@ -107,24 +107,135 @@ __device__ __forceinline__ bool is_inlier(const double* M, float x, float y, flo
     return e <= RANSAC_THRESH2;
 }
 
+// The refit's sums.  The oracle (ko_ransac_affine) defines them: means from split sums -- a coordinate's v = round(x 2^32) is summed as hi = v >> 32
+// and lo = v mod 2^32, both int64 sums exact for any count below 2^31 however far from the origin the points lie (one plain int64 sum of x 2^32
+// overflowed once the inliers' sum of |x| passed 2^31: 3072 points near x = 7e5); mean_total rounds hi 2^32 + lo to double once, which is (double) of
+// the plain sum wherever that did not overflow.  Moments: plain int64 sums of round(p 2^20), p = a product of two centred coordinates, each below
+// 2^42 / count in square.  Out of range (|coordinate| >= 2^31, or a centred coordinate beyond sqrt(2^42 / count): 14 800 px at 20 000 inliers) the
+// refit is unrepresentable: status -1, no inliers, no model.
+#define MEAN_LIM 2147483648.0
+__device__ __forceinline__ int mean_add(long long* hl, float x)
+{
+    if (!(fabsf(x) < (float)MEAN_LIM)) return 1;
+    const long long q = vh_fixq((double)x, 32);
+    hl[0] += q >> 32;
+    hl[1] += q & 0xFFFFFFFFll;
+    return 0;
+}
+__device__ __forceinline__ double mean_total(const long long* hl)
+{
+    const long long hi = hl[0] + (hl[1] >> 32), lo = hl[1] & 0xFFFFFFFFll;  // carry: |hi| < 2^53, lo < 2^32, both exact in double
+    return ldexp(__dadd_rn(ldexp((double)hi, 32), (double)lo), -32);
+}
+__device__ __forceinline__ void moments_add(long long* q, double x, double y, double u, double v)
+{
+    q[0] += vh_fixq(__dmul_rn(x, x), 20); q[1] += vh_fixq(__dmul_rn(x, y), 20); q[2] += vh_fixq(__dmul_rn(y, y), 20);
+    q[3] += vh_fixq(__dmul_rn(x, u), 20); q[4] += vh_fixq(__dmul_rn(y, u), 20);
+    q[5] += vh_fixq(__dmul_rn(x, v), 20); q[6] += vh_fixq(__dmul_rn(y, v), 20);
+}
+
+// Fast path of the refit (inline in both kernels): every inlier coordinate below L = 2^e, e = min(30 - k, floor((38 - k) / 2)), count <= 2^k --
+// pixel-scale input: 8192 px up to 2048 inliers, 4096 px up to 8192.  There the plain int64 sums of round(x 2^32) cannot overflow (count L 2^32 <=
+// 2^62): they are the split sums' exact value, and (double) of them is mean_total.  Centred coordinates stay below 2 L, so the moment sums stay below
+// 2^60 and every product passes the range check ((2 L)^2 <= 2^(40 - k) < 2^42 / count).  Same integers, same doubles as the split path, in the
+// instruction sequence the refit had before the split path existed.
+__device__ __forceinline__ float refit_fast_lim(int count)
+{
+    const int k = 32 - __clz(count - 1);  // count <= 2^k (count >= 3)
+    return ldexpf(1.0f, min(30 - k, (38 - k) >> 1));
+}
+__device__ __forceinline__ bool refit_fast_ok(float x, float y, float u, float v, float L)
+{
+    return ((int)(fabsf(x) < L) & (int)(fabsf(y) < L) & (int)(fabsf(u) < L) & (int)(fabsf(v) < L)) != 0;  // (no short-circuit branches)
+}
+
+// the inliers of this thread, for refit_split: the compacted pairs in LDS (fused kernel) or the points + inlier mask in global memory (k_ransac_select)
+struct InliersLds {
+    const float4* pairs;
+    unsigned bits;
+    int tid;
+    template <typename F>
+    __device__ void operator()(F f) const
+    {
+        for (int j = 0; j < 6; j++)
+            if ((bits >> j) & 1u) {
+                const float4 q = pairs[tid + 512 * j];
+                f(q.x, q.y, q.z, q.w);
+            }
+    }
+};
+struct InliersGlobal {
+    const float* from;
+    const float* to;
+    const uint8_t* inl;
+    int n, tid;
+    template <typename F>
+    __device__ void operator()(F f) const
+    {
+        for (int i = tid; i < n; i += 256)
+            if (inl[i]) f(from[2 * i], from[2 * i + 1], to[2 * i], to[2 * i + 1]);
+    }
+};
+
+template <int NW>
+__device__ bool block_sum_flag(long long* v, int nv, bool flag, long long* sh, int* shf);
+
+// Split path (some coordinate beyond the fast limit): the oracle's sums.  Every thread of the
+// block calls it.  Out: out[0 .. 4) the means, out[4 .. 11) the moments (LDS, valid in every thread on return); false when out of range.
+template <int NW, typename Inliers>
+__device__ __forceinline__ bool refit_split(Inliers each, int count, long long* sh, int* shf, double* out)
+{
+    const double cnt = (double)count;
+    long long q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool flag = false;
+    each([&](float x, float y, float u, float v) { flag |= (mean_add(&q[0], x) | mean_add(&q[2], y) | mean_add(&q[4], u) | mean_add(&q[6], v)) != 0; });
+    if (block_sum_flag<NW>(q, 8, flag, sh, shf)) return false;
+    double mean[4];
+    for (int k = 0; k < 4; k++) mean[k] = __ddiv_rn(mean_total(&q[2 * k]), cnt);
+    const double lim2 = __ddiv_rn(4398046511104.0, cnt);  // 2^42 / count
+    for (int k = 0; k < 7; k++) q[k] = 0;
+    flag = false;
+    each([&](float xf, float yf, float uf, float vf) {
+        const double x = __dsub_rn((double)xf, mean[0]), y = __dsub_rn((double)yf, mean[1]);
+        const double u = __dsub_rn((double)uf, mean[2]), v = __dsub_rn((double)vf, mean[3]);
+        if (__dmul_rn(x, x) < lim2 && __dmul_rn(y, y) < lim2 && __dmul_rn(u, u) < lim2 && __dmul_rn(v, v) < lim2) moments_add(q, x, y, u, v);
+        else flag = true;
+    });
+    if (block_sum_flag<NW>(q, 7, flag, sh, shf)) return false;
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 4; k++) out[k] = mean[k];
+        for (int k = 0; k < 7; k++) out[4 + k] = ldexp((double)q[k], -20);
+    }
+    __syncthreads();
+    return true;
+}
+
+// block-wide exact int64 sums of v[0 .. nv) (valid in every thread) + the OR of every thread's flag; NW wavefronts, sh: [8 * NW], shf: [NW]
+template <int NW>
+__device__ __forceinline__ bool block_sum_flag(long long* v, int nv, bool flag, long long* sh, int* shf)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = 0; k < nv; k++) v[k] = vh_wave_sum_i64(v[k]);
+    const bool wf = __ballot(flag) != 0;
+    __syncthreads();
+    if (lane == 0) {
+        for (int k = 0; k < nv; k++) sh[k * NW + wave] = v[k];
+        shf[wave] = wf;
+    }
+    __syncthreads();
+    bool any = false;
+    for (int k = 0; k < nv; k++) {
+        long long t = 0;
+        for (int w = 0; w < NW; w++) t += sh[k * NW + w];
+        v[k] = t;
+    }
+    for (int w = 0; w < NW; w++) any = any || shf[w] != 0;
+    return any;
+}
+
 __device__ __forceinline__ const RansacJob& rjob(const void* tab, size_t stride, int b)
 {
     return *reinterpret_cast<const RansacJob*>(reinterpret_cast<const char*>(tab) + (size_t)b * stride);
-}
-
-// block-wide sum of NV int64 values; result valid in every thread
-template <int NV>
-__device__ void block_sum_i64(long long* v, long long* sh /* [NV * 4] */)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = vh_wave_sum_i64(v[k]);
-    __syncthreads();
-    if (lane == 0)
-        for (int k = 0; k < NV; k++) sh[k * 4 + wave] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = sh[k * 4] + sh[k * 4 + 1] + sh[k * 4 + 2] + sh[k * 4 + 3];
 }
 
 // inliers of model M among the m compacted pairs, counted by one wavefront (one 16-byte load per pair)
@@ -227,7 +338,9 @@ __global__ __launch_bounds__(256) void k_ransac_select(const void* tab, size_t s
     const int tid = threadIdx.x;
     __shared__ int s_best, s_count;
     __shared__ double s_M[6];
-    __shared__ long long s_red[9 * 4];
+    __shared__ long long s_red[8 * 4];
+    __shared__ int s_flag[4];
+    __shared__ double s_refit[11];
     // the scores of every reachable hypothesis in ONE coalesced round trip: the single-thread replay below walks them with data-dependent
     // control flow, and from global memory every step of it was a full L2 latency (most of this kernel's 14 us)
     __shared__ int s_counts[VH_RANSAC_ITERS];
@@ -272,42 +385,51 @@ __global__ __launch_bounds__(256) void k_ransac_select(const void* tab, size_t s
     for (int k = 0; k < 6; k++) M[k] = s_M[k];
 
     // inlier mask + first fixed-point pass (means), 2^-32 resolution
+    const double cnt = (double)s_count;
+    const float L = refit_fast_lim(s_count);
     long long s1[4] = {0, 0, 0, 0};
+    bool far = false;
     for (int i = tid; i < n; i += 256) {
         bool in = false;
         if (J.valid[i]) {
             const float x = J.from[2 * i], y = J.from[2 * i + 1], u = J.to[2 * i], v = J.to[2 * i + 1];
             in = is_inlier(M, x, y, u, v);
             if (in) {
+                far |= !refit_fast_ok(x, y, u, v, L);
                 s1[0] += vh_fixq((double)x, 32); s1[1] += vh_fixq((double)y, 32);
                 s1[2] += vh_fixq((double)u, 32); s1[3] += vh_fixq((double)v, 32);
             }
         }
         J.inl[i] = in ? 1 : 0;
     }
-    block_sum_i64<4>(s1, s_red);
-    const double cnt = (double)s_count;
-    const double mx = __ddiv_rn(ldexp((double)s1[0], -32), cnt), my = __ddiv_rn(ldexp((double)s1[1], -32), cnt);
-    const double mu = __ddiv_rn(ldexp((double)s1[2], -32), cnt), mv = __ddiv_rn(ldexp((double)s1[3], -32), cnt);
-    __syncthreads();  // J.inl written by this block is re-read below (same thread reads its own entries)
-
-    long long q[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int i = tid; i < n; i += 256) {
-        if (J.inl[i]) {
-            const double x = __dsub_rn((double)J.from[2 * i], mx), y = __dsub_rn((double)J.from[2 * i + 1], my);
-            const double u = __dsub_rn((double)J.to[2 * i], mu), v = __dsub_rn((double)J.to[2 * i + 1], mv);
-            q[0] += vh_fixq(__dmul_rn(x, x), 20); q[1] += vh_fixq(__dmul_rn(x, y), 20); q[2] += vh_fixq(__dmul_rn(y, y), 20);
-            q[3] += vh_fixq(__dmul_rn(x, u), 20); q[4] += vh_fixq(__dmul_rn(y, u), 20);
-            q[5] += vh_fixq(__dmul_rn(x, v), 20); q[6] += vh_fixq(__dmul_rn(y, v), 20);
+    far = block_sum_flag<4>(s1, 4, far, s_red, s_flag);  // (uniform)
+    double mx, my, mu, mv, Sxx, Sxy, Syy, Sxu, Syu, Sxv, Syv;
+    bool ok = true;
+    if (!far) {
+        mx = __ddiv_rn(ldexp((double)s1[0], -32), cnt); my = __ddiv_rn(ldexp((double)s1[1], -32), cnt);
+        mu = __ddiv_rn(ldexp((double)s1[2], -32), cnt); mv = __ddiv_rn(ldexp((double)s1[3], -32), cnt);
+        long long q[7] = {0, 0, 0, 0, 0, 0, 0};
+        for (int i = tid; i < n; i += 256) {  // (each thread re-reads the J.inl entries it wrote)
+            if (J.inl[i]) {
+                const double x = __dsub_rn((double)J.from[2 * i], mx), y = __dsub_rn((double)J.from[2 * i + 1], my);
+                const double u = __dsub_rn((double)J.to[2 * i], mu), v = __dsub_rn((double)J.to[2 * i + 1], mv);
+                moments_add(q, x, y, u, v);
+            }
         }
+        block_sum_flag<4>(q, 7, false, s_red, s_flag);
+        Sxx = ldexp((double)q[0], -20); Sxy = ldexp((double)q[1], -20); Syy = ldexp((double)q[2], -20);
+        Sxu = ldexp((double)q[3], -20); Syu = ldexp((double)q[4], -20); Sxv = ldexp((double)q[5], -20); Syv = ldexp((double)q[6], -20);
+    } else {
+        ok = refit_split<4>(InliersGlobal{J.from, J.to, J.inl, n, tid}, s_count, s_red, s_flag, s_refit);
+        mx = s_refit[0]; my = s_refit[1]; mu = s_refit[2]; mv = s_refit[3];
+        Sxx = s_refit[4]; Sxy = s_refit[5]; Syy = s_refit[6]; Sxu = s_refit[7]; Syu = s_refit[8]; Sxv = s_refit[9]; Syv = s_refit[10];
     }
-    block_sum_i64<7>(q, s_red);
+    if (!ok)
+        for (int i = tid; i < n; i += 256) J.inl[i] = 0;
     if (J.gate_valid)
         for (int i = tid; i < n; i += 256) J.valid[i] = J.inl[i];
-    if (tid == 0) {
-        const double Sxx = ldexp((double)q[0], -20), Sxy = ldexp((double)q[1], -20), Syy = ldexp((double)q[2], -20);
-        const double Sxu = ldexp((double)q[3], -20), Syu = ldexp((double)q[4], -20);
-        const double Sxv = ldexp((double)q[5], -20), Syv = ldexp((double)q[6], -20);
+    if (tid == 0 && !ok) *J.status = -1;
+    if (tid == 0 && ok) {
         const double det = __dsub_rn(__dmul_rn(Sxx, Syy), __dmul_rn(Sxy, Sxy));
         const double tr = __dadd_rn(Sxx, Syy);
         if (s_count >= 3 && det > __dmul_rn(__dmul_rn(1e-9, tr), tr) && det > 0) {
@@ -372,9 +494,11 @@ __device__ __forceinline__ void ransac_fused_body(const void* tab, size_t stride
     int* s_counts = s_idx + RANSAC_FUSED_MAX;                                     // [VH_RANSAC_ITERS]
     __shared__ int wcount[8], base, s_bound, s_best, s_count;
     __shared__ double s_M[6];
-    __shared__ long long s_red[7 * 8];
+    __shared__ long long s_red[8 * 8];
+    __shared__ int s_flag[8], s_far;
+    __shared__ double s_refit[11];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (tid == 0) base = 0;
+    if (tid == 0) { base = 0; s_far = 0; }
     // every chunk's loads are issued before the first barrier (round 6): the compaction was a chain of one global round trip PER 512-pair chunk (four at
     // 2000 pairs: ~6 us of a 21 us single-stream launch); the chunks themselves are then compacted from registers in the same order as before
     constexpr int NCH = RANSAC_FUSED_MAX / 512;
@@ -401,6 +525,9 @@ __device__ __forceinline__ void ransac_fused_body(const void* tab, size_t stride
         }
     }
     __syncthreads();
+    // a valid pair beyond the refit's fast limit for n (>= the inlier count: conservative) sends the refit to the split path: flagged in LDS while the
+    // compaction holds the pair in registers (its barriers order the flag before the refit reads it)
+    const float L = refit_fast_lim(max(n, 1));
 #pragma unroll
     for (int j = 0; j < NCH; j++) {
         if (512 * j >= n) break;  // (uniform)
@@ -417,7 +544,11 @@ __device__ __forceinline__ void ransac_fused_body(const void* tab, size_t stride
             off += w < wave ? cw : 0;
             tot += cw;
         }
-        if (f) { s_idx[off + pre] = i; s_pairs[off + pre] = qv[j]; }
+        if (f) {
+            s_idx[off + pre] = i;
+            s_pairs[off + pre] = qv[j];
+            if (!refit_fast_ok(qv[j].x, qv[j].y, qv[j].z, qv[j].w, L)) s_far = 1;
+        }
         __syncthreads();
         if (tid == 0) base += tot;
         __syncthreads();
@@ -477,58 +608,79 @@ __device__ __forceinline__ void ransac_fused_body(const void* tab, size_t stride
     }
     double M[6];
     for (int k = 0; k < 6; k++) M[k] = s_M[k];
-    auto block_sum = [&](long long* v, int nv) {  // exact int64 sums over the 8 wavefronts
-        for (int k = 0; k < nv; k++) v[k] = vh_wave_sum_i64(v[k]);
-        __syncthreads();
-        if (lane == 0) for (int k = 0; k < nv; k++) s_red[k * 8 + wave] = v[k];
-        __syncthreads();
-        for (int k = 0; k < nv; k++) {
-            long long t = 0;
-            for (int w = 0; w < 8; w++) t += s_red[k * 8 + w];
-            v[k] = t;
-        }
-    };
     // inlier mask over ALL points (0 where !valid) + the refit sums over the compacted pairs in LDS (the same points, the same integers)
     for (int i = tid; i < n; i += 512) J.inl[i] = 0;
     __syncthreads();
-    long long s1[4] = {0, 0, 0, 0};
+    const double cnt = (double)s_count;
     unsigned in_bits = 0;  // this thread's pairs k = tid + 512 j, j < 6
+    double mx, my, mu, mv, Sxx, Sxy, Syy, Sxu, Syu, Sxv, Syv;
+    bool ok = true;
+    if (s_far == 0) {  // (uniform) the fast path
+        auto block_sum = [&](long long* v, int nv) {  // exact int64 sums over the 8 wavefronts
+            for (int k = 0; k < nv; k++) v[k] = vh_wave_sum_i64(v[k]);
+            __syncthreads();
+            if (lane == 0) for (int k = 0; k < nv; k++) s_red[k * 8 + wave] = v[k];
+            __syncthreads();
+            for (int k = 0; k < nv; k++) {
+                long long t = 0;
+                for (int w = 0; w < 8; w++) t += s_red[k * 8 + w];
+                v[k] = t;
+            }
+        };
+        long long s1[4] = {0, 0, 0, 0};
 #pragma unroll
-    for (int j = 0; j < RANSAC_FUSED_MAX / 512; j++) {
-        const int k = tid + 512 * j;
-        if (k < m) {
-            const float4 q = s_pairs[k];
-            if (is_inlier(M, q.x, q.y, q.z, q.w)) {
-                in_bits |= 1u << j;
-                s1[0] += vh_fixq((double)q.x, 32); s1[1] += vh_fixq((double)q.y, 32);
-                s1[2] += vh_fixq((double)q.z, 32); s1[3] += vh_fixq((double)q.w, 32);
-                J.inl[s_idx[k]] = 1;
+        for (int j = 0; j < RANSAC_FUSED_MAX / 512; j++) {
+            const int k = tid + 512 * j;
+            if (k < m) {
+                const float4 q = s_pairs[k];
+                if (is_inlier(M, q.x, q.y, q.z, q.w)) {
+                    in_bits |= 1u << j;
+                    s1[0] += vh_fixq((double)q.x, 32); s1[1] += vh_fixq((double)q.y, 32);
+                    s1[2] += vh_fixq((double)q.z, 32); s1[3] += vh_fixq((double)q.w, 32);
+                    J.inl[s_idx[k]] = 1;
+                }
             }
         }
-    }
-    block_sum(s1, 4);
-    const double cnt = (double)s_count;
-    const double mx = __ddiv_rn(ldexp((double)s1[0], -32), cnt), my = __ddiv_rn(ldexp((double)s1[1], -32), cnt);
-    const double mu = __ddiv_rn(ldexp((double)s1[2], -32), cnt), mv = __ddiv_rn(ldexp((double)s1[3], -32), cnt);
-    long long q7[7] = {0, 0, 0, 0, 0, 0, 0};
+        block_sum(s1, 4);
+        mx = __ddiv_rn(ldexp((double)s1[0], -32), cnt); my = __ddiv_rn(ldexp((double)s1[1], -32), cnt);
+        mu = __ddiv_rn(ldexp((double)s1[2], -32), cnt); mv = __ddiv_rn(ldexp((double)s1[3], -32), cnt);
+        long long q7[7] = {0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int j = 0; j < RANSAC_FUSED_MAX / 512; j++) {
-        if ((in_bits >> j) & 1u) {
-            const float4 q = s_pairs[tid + 512 * j];
-            const double x = __dsub_rn((double)q.x, mx), y = __dsub_rn((double)q.y, my);
-            const double u = __dsub_rn((double)q.z, mu), v = __dsub_rn((double)q.w, mv);
-            q7[0] += vh_fixq(__dmul_rn(x, x), 20); q7[1] += vh_fixq(__dmul_rn(x, y), 20); q7[2] += vh_fixq(__dmul_rn(y, y), 20);
-            q7[3] += vh_fixq(__dmul_rn(x, u), 20); q7[4] += vh_fixq(__dmul_rn(y, u), 20);
-            q7[5] += vh_fixq(__dmul_rn(x, v), 20); q7[6] += vh_fixq(__dmul_rn(y, v), 20);
+        for (int j = 0; j < RANSAC_FUSED_MAX / 512; j++) {
+            if ((in_bits >> j) & 1u) {
+                const float4 q = s_pairs[tid + 512 * j];
+                const double x = __dsub_rn((double)q.x, mx), y = __dsub_rn((double)q.y, my);
+                const double u = __dsub_rn((double)q.z, mu), v = __dsub_rn((double)q.w, mv);
+                q7[0] += vh_fixq(__dmul_rn(x, x), 20); q7[1] += vh_fixq(__dmul_rn(x, y), 20); q7[2] += vh_fixq(__dmul_rn(y, y), 20);
+                q7[3] += vh_fixq(__dmul_rn(x, u), 20); q7[4] += vh_fixq(__dmul_rn(y, u), 20);
+                q7[5] += vh_fixq(__dmul_rn(x, v), 20); q7[6] += vh_fixq(__dmul_rn(y, v), 20);
+            }
         }
+        block_sum(q7, 7);  // (its barriers also order the J.inl stores above before the reads below)
+        Sxx = ldexp((double)q7[0], -20); Sxy = ldexp((double)q7[1], -20); Syy = ldexp((double)q7[2], -20);
+        Sxu = ldexp((double)q7[3], -20); Syu = ldexp((double)q7[4], -20); Sxv = ldexp((double)q7[5], -20); Syv = ldexp((double)q7[6], -20);
+    } else {
+#pragma unroll
+        for (int j = 0; j < RANSAC_FUSED_MAX / 512; j++) {
+            const int k = tid + 512 * j;
+            if (k < m) {
+                const float4 q = s_pairs[k];
+                if (is_inlier(M, q.x, q.y, q.z, q.w)) {
+                    in_bits |= 1u << j;
+                    J.inl[s_idx[k]] = 1;
+                }
+            }
+        }
+        ok = refit_split<8>(InliersLds{s_pairs, in_bits, tid}, s_count, s_red, s_flag, s_refit);  // (its barriers order the J.inl stores)
+        mx = s_refit[0]; my = s_refit[1]; mu = s_refit[2]; mv = s_refit[3];
+        Sxx = s_refit[4]; Sxy = s_refit[5]; Syy = s_refit[6]; Sxu = s_refit[7]; Syu = s_refit[8]; Sxv = s_refit[9]; Syv = s_refit[10];
     }
-    block_sum(q7, 7);  // (its barriers also order the J.inl stores above before the reads below)
+    if (!ok)
+        for (int i = tid; i < n; i += 512) J.inl[i] = 0;  // (the gate below reads the entries this thread cleared)
     if (J.gate_valid)
         for (int i = tid; i < n; i += 512) J.valid[i] = J.inl[i];
-    if (tid == 0) {
-        const double Sxx = ldexp((double)q7[0], -20), Sxy = ldexp((double)q7[1], -20), Syy = ldexp((double)q7[2], -20);
-        const double Sxu = ldexp((double)q7[3], -20), Syu = ldexp((double)q7[4], -20);
-        const double Sxv = ldexp((double)q7[5], -20), Syv = ldexp((double)q7[6], -20);
+    if (tid == 0 && !ok) *J.status = -1;
+    if (tid == 0 && ok) {
         const double det = __dsub_rn(__dmul_rn(Sxx, Syy), __dmul_rn(Sxy, Sxy));
         const double tr = __dadd_rn(Sxx, Syy);
         if (s_count >= 3 && det > __dmul_rn(__dmul_rn(1e-9, tr), tr) && det > 0) {
