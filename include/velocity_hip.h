@@ -218,6 +218,24 @@ VH_API int vh_frame0_init(vh_ctx* ctx, const uint8_t* im, int w, int h, int stri
                           const double* plate_host, int border_x, int border_y, int max_corners, double quality, int block, double k,
                           int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out, uint8_t* vp_out, float* t_out,
                           double* R_out, double* res_out, int* n_out, int* roi_host, void* stream);
+/* (vh_version >= 106) frame-0 initialisation of nb clips of ONE frame size, vidExample.py:105-127 for each, as one device launch sequence per chunk of
+ * clips (below).  Every clip's results are bit-identical to vh_frame0_init on that clip alone.
+ *   frames_host: host array of nb device pointers (w x h frames, row stride `stride`); q_host: host float [nb][4][2]; K_host, plate_host and every
+ *   parameter after them are shared by the batch.  Each clip's boxa / boxb come from its own q, so the ROI sizes may differ between clips.
+ *   Outputs (device, clip b in row b, rows dense at cap = 4 + max_corners): p_out [nb][cap][2], p3_out [nb][cap][3], vp_out [nb][cap], t_out [nb][3],
+ *   R_out [nb][9], res_out [nb], n_out [nb]; roi_host (may be NULL): host int [nb][8] = boxa, boxb.
+ * Every argument is checked before anything is queued: -1 (and no output written) for the checks of vh_frame0_init, nb < 1, a null frame pointer or a
+ * clip whose ROI is empty (vh_last_error names the clip).  The candidates of a clip are compacted and its max_corners strongest are found by a radix
+ * select (max_corners <= 2048: sorted in LDS; above: a segmented sort) -- no full-ROI sort.
+ * Scratch: per context, about 12 bytes per ROI pixel of a chunk.  vh_init_reserve_batch(ctx, nb, w, h) sizes it for nb clips of a w x h ROI and fixes
+ * the chunk size: a call with more clips runs in chunks of that many (results do not depend on the chunking).  Without it, the first call sizes the
+ * scratch for as many of its clips as fit 1 GiB, later calls grow it the same way.  Once the scratch fits, a call only queues kernels (legal under
+ * stream capture); growth inside a capture returns -6, as does a max_corners above 2048 whose sort scratch does not exist yet. */
+VH_API int vh_init_reserve_batch(vh_ctx* ctx, int nb, int w, int h, void* stream);
+VH_API int vh_frame0_init_batch(vh_ctx* ctx, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
+                                const double* K_host, const double* plate_host, int border_x, int border_y, int max_corners, double quality,
+                                int block, double k, int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out,
+                                uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host, void* stream);
 
 /* ---- tracker session: the frame loop body of vidExample.py:133-160 on the device, for ctx->batch streams ------- */
 /* device pointers into the state of one stream (read with vh_copy_to_host / torch) */

@@ -13,6 +13,9 @@
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+
+#include <vector>
 
 #include "vh_ws.hpp"
 
@@ -103,13 +106,11 @@ __global__ void k_init_emit(const unsigned long long* sorted, const unsigned* co
     }
 }
 
-// cornerSubPix: one thread per corner
+// cornerSubPix of corner q (k_init_subpix, k_f0b_subpix: one thread per corner)
 #define SUBPIX_MAXWIN 7
-__global__ __launch_bounds__(64) void k_init_subpix(const uint8_t* im, int w, int h, size_t st, float* pts, int n, const int* n_dev, int win,
-                                                    int max_iter, double eps2, const float* mask)
+__device__ __forceinline__ void subpix_corner(const uint8_t* im, int w, int h, size_t st, float* pts, int q, int win, int max_iter, double eps2,
+                                              const float* mask)
 {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= (n_dev ? min(*n_dev, n) : n)) return;  // n_dev: the detector's count, still on the device (vh_frame0_init)
     const int ww = 2 * win + 1, pw = ww + 2;
     float buf[(2 * SUBPIX_MAXWIN + 3) * (2 * SUBPIX_MAXWIN + 3)];
     const float tx = pts[2 * q], ty = pts[2 * q + 1];
@@ -164,6 +165,14 @@ __global__ __launch_bounds__(64) void k_init_subpix(const uint8_t* im, int w, in
     pts[2 * q] = cx; pts[2 * q + 1] = cy;
 }
 
+__global__ __launch_bounds__(64) void k_init_subpix(const uint8_t* im, int w, int h, size_t st, float* pts, int n, const int* n_dev, int win,
+                                                    int max_iter, double eps2, const float* mask)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (n_dev ? min(*n_dev, n) : n)) return;  // n_dev: the detector's count, still on the device (vh_frame0_init)
+    subpix_corner(im, w, h, st, pts, q, win, max_iter, eps2, mask);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // The scratch of the detector lives in the vh_ctx (vh_ws.hpp: InitScratch; round 4 kept ONE process-global copy: two contexts on two streams raced
 // on its keys / response / counters, a second device reused the first device's allocation).  It is created by the first frame-0 call of a context,
@@ -180,6 +189,7 @@ static void init_scratch_release(InitScratch& I)
 void vh_init_scratch_free(vh_ctx* c)
 {
     if (c) init_scratch_release(c->init);
+    vh_init_batch_scratch_free(c);
 }
 
 static int subpix_mask_offset(int win)  // masks of half-sizes 1 .. win-1 come first
@@ -187,6 +197,29 @@ static int subpix_mask_offset(int win)  // masks of half-sizes 1 .. win-1 come f
     int off = 0;
     for (int k = 1; k < win; k++) off += (2 * k + 1) * (2 * k + 1);
     return off;
+}
+
+// cornerSubPix's Gaussian window for every half-size, computed once on the host in OpenCV's float32 order (bit-identical to the CPU restatement)
+static int subpix_masks_create(float** out)
+{
+    const int mask_floats = subpix_mask_offset(SUBPIX_MAXWIN + 1);
+    VH_CHECK(hipMalloc((void**)out, sizeof(float) * mask_floats));
+    float* hm = new float[mask_floats];
+    for (int win = 1; win <= SUBPIX_MAXWIN; win++) {
+        float* m = hm + subpix_mask_offset(win);
+        const int ww = 2 * win + 1;
+        for (int i = 0; i < ww; i++) {
+            const float y = (float)(i - win) / win, vy = expf(-y * y);
+            for (int j = 0; j < ww; j++) {
+                const float x = (float)(j - win) / win;
+                m[i * ww + j] = (float)(vy * expf(-x * x));
+            }
+        }
+    }
+    const hipError_t e = hipMemcpy(*out, hm, sizeof(float) * mask_floats, hipMemcpyHostToDevice);  // synchronous: hm dies here
+    delete[] hm;
+    VH_CHECK(e);
+    return 0;
 }
 
 static int init_reserve(vh_ctx* c, size_t pixels, hipStream_t s)
@@ -207,24 +240,9 @@ static int init_reserve(vh_ctx* c, size_t pixels, hipStream_t s)
     VH_CHECK(hipMalloc((void**)&I.keys, pixels * 8));
     VH_CHECK(hipMalloc((void**)&I.sorted, pixels * 8));
     VH_CHECK(hipMalloc((void**)&I.counters, 32));
-    const int mask_floats = subpix_mask_offset(SUBPIX_MAXWIN + 1);
-    VH_CHECK(hipMalloc((void**)&I.mask, sizeof(float) * mask_floats));
-    {   // cornerSubPix's Gaussian window for every half-size, computed once on the host in OpenCV's float32 order (bit-identical to the CPU restatement)
-        float* hm = new float[mask_floats];
-        for (int win = 1; win <= SUBPIX_MAXWIN; win++) {
-            float* m = hm + subpix_mask_offset(win);
-            const int ww = 2 * win + 1;
-            for (int i = 0; i < ww; i++) {
-                const float y = (float)(i - win) / win, vy = expf(-y * y);
-                for (int j = 0; j < ww; j++) {
-                    const float x = (float)(j - win) / win;
-                    m[i * ww + j] = (float)(vy * expf(-x * x));
-                }
-            }
-        }
-        const hipError_t e = hipMemcpy(I.mask, hm, sizeof(float) * mask_floats, hipMemcpyHostToDevice);  // synchronous: hm dies here
-        delete[] hm;
-        VH_CHECK(e);
+    {
+        const int r = subpix_masks_create(&I.mask);
+        if (r) return r;
     }
     size_t bytes = 0;
     VH_CHECK(rocprim::radix_sort_keys_desc(nullptr, bytes, I.keys, I.sorted, pixels, 0, 64, 0));
@@ -316,13 +334,9 @@ __global__ void k_frame0_head(Frame0Job J, float* p, double* plate)
 // p3 = addcol0(image2world(K, R, t, p).astype(float)) @ R + t (vidExample.py:119, common.py:49-55); vp = insidebbox(p, boxa) (:126, images.py:22-27);
 // n_out = 4 + corners found.  float64 throughout (the reference's float32 inverse carries ~1e-7; the contract is 1e-4): H = [R[0:2]; t] @ K, its
 // inverse by the adjugate, q = [x y 1] @ inv(H), (X, Y) = q[0:2] / q[2], p3 = X R[0] + Y R[1] + t
-__global__ __launch_bounds__(256) void k_frame0_world(Frame0Job J, const double* R, const float* t, const int* n_corners, const float* p, double* p3,
-                                                      uint8_t* vp, int* n_out)
+// row i < max_n of one clip (k_frame0_world, k_f0b_world)
+__device__ __forceinline__ void frame0_world_row(int i, int n, const Frame0Job& J, const double* R, const float* t, const float* p, double* p3, uint8_t* vp)
 {
-    const int n = min(4 + *n_corners, J.max_n);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) *n_out = n;
-    if (i >= J.max_n) return;
     if (i >= n) { vp[i] = 0; p3[3 * i] = 0; p3[3 * i + 1] = 0; p3[3 * i + 2] = 0; return; }
     const double td[3] = {(double)t[0], (double)t[1], (double)t[2]};
     double H[9];
@@ -346,6 +360,15 @@ __global__ __launch_bounds__(256) void k_frame0_world(Frame0Job J, const double*
     p3[3 * i + 1] = X * R[1] + Y * R[4] + td[1];
     p3[3 * i + 2] = X * R[2] + Y * R[5] + td[2];
     vp[i] = (xf > (float)J.boxa[0] && xf < (float)J.boxa[1] && yf > (float)J.boxa[2] && yf < (float)J.boxa[3]) ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void k_frame0_world(Frame0Job J, const double* R, const float* t, const int* n_corners, const float* p, double* p3,
+                                                      uint8_t* vp, int* n_out)
+{
+    const int n = min(4 + *n_corners, J.max_n);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *n_out = n;
+    if (i >= J.max_n) return;
+    frame0_world_row(i, n, J, R, t, p, p3, vp);
 }
 
 // boundingRect(x, imshape, border) of a few host points (images.py:9-19; floor on all four edges like the device kernel k_bounding_rect)
@@ -412,5 +435,467 @@ extern "C" VH_API int vh_frame0_init(vh_ctx* c, const uint8_t* im, int w, int h,
     vh_launch_pose(d, sizeof(PoseJob), 1, 1, 4, s);
     hipLaunchKernelGGL(k_frame0_world, dim3((J.max_n + 255) / 256), dim3(256), 0, s, J, R_out, t_out, n_corners, p_out, p3_out, vp_out, n_out);
     VH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// vh_frame0_init_batch: vh_frame0_init for nb clips of one frame size as one launch sequence per chunk of clips.  Every stage runs with the
+// clip as a grid dimension; a clip finds its ROI, frame and scratch segment in the chunk's descriptor table (F0Clip).  Per clip the results are
+// bit-identical to vh_frame0_init: the same integer Sobel / Harris sums and float32 response, the same order-preserving atomic maximum, the same
+// candidate test and 64-bit keys, cornerSubPix, pose and world points through the same device code.  Only the ordering step differs: instead
+// of sorting every ROI pixel, the candidates are compacted per clip and the max_corners largest keys are found by a radix select (keys are
+// unique -- the pixel index is part of each -- so their unsigned descending order is the rocPRIM sort's order).
+// ---------------------------------------------------------------------------------------------------------------
+#define F0B_TW 64        // Harris / candidate tile: 64 x 16 pixels, 256 threads
+#define F0B_TH 16
+#define F0B_PIECE 32     // descriptors per upload (one kernel argument of 32 x 88 bytes)
+#define F0B_SEL_MAX 2048 // max_corners up to this: selected keys sorted in LDS; above: rocPRIM segmented sort
+static const size_t F0B_BUDGET = (size_t)1 << 30;  // scratch of a context sized by the first call (include/velocity_hip.h)
+
+struct F0Clip {
+    const uint8_t* roi;        // frame + boxb[2] * stride + boxb[0]
+    const uint8_t* im;         // the frame (cornerSubPix samples the whole frame)
+    unsigned long long seg;    // offset of the clip's response plane and key segment in the chunk's scratch
+    int rw, rh;                // ROI size (boxb)
+    float offx, offy;          // ROI origin
+    int boxa[4];
+    float q[8];
+};
+struct F0ClipPiece {
+    F0Clip c[F0B_PIECE];
+};
+struct F0Shared {
+    double K[9];
+    double plate[12];
+};
+
+// Sobel (k_init_sobel) into an LDS tile with a (block - 1) halo, Harris response (k_init_harris's sums and float32 expression) of 64 x 16 pixels,
+// per-clip maximum.  REFLECT_101 is relative to the clip's ROI: a halo entry holds the Sobel pair of the reflected pixel, as k_init_harris reads it.
+__global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, size_t st, int block, float s2, float kf, float* resp_base, unsigned* cnt)
+{
+    const F0Clip& C = tab[blockIdx.z];
+    const int rw = C.rw, rh = C.rh, tx0 = blockIdx.x * F0B_TW, ty0 = blockIdx.y * F0B_TH;
+    if (tx0 >= rw || ty0 >= rh) return;  // the whole tile lies outside this clip's ROI (grid sized for the chunk's largest)
+    __shared__ int2 g[(F0B_TH + 14) * (F0B_TW + 14)];
+    const int r0 = block / 2, gw = F0B_TW + block - 1, gh = F0B_TH + block - 1;
+    const uint8_t* im = C.roi;
+    for (int i = threadIdx.x; i < gw * gh; i += 256) {
+        const int ly = i / gw, lx = i - ly * gw;
+        const int x = vh_reflect101(tx0 - r0 + lx, rw), y = vh_reflect101(ty0 - r0 + ly, rh);
+        const int xm = vh_reflect101(x - 1, rw), xp = vh_reflect101(x + 1, rw), ym = vh_reflect101(y - 1, rh), yp = vh_reflect101(y + 1, rh);
+        const uint8_t *q0 = im + (size_t)ym * st, *q1 = im + (size_t)y * st, *q2 = im + (size_t)yp * st;
+        g[i] = make_int2((q0[xp] - q0[xm]) + 2 * (q1[xp] - q1[xm]) + (q2[xp] - q2[xm]), (q2[xm] - q0[xm]) + 2 * (q2[x] - q0[x]) + (q2[xp] - q0[xp]));
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 63, x = tx0 + lx;
+    float* resp = resp_base + C.seg;
+    unsigned o = 0u;
+    for (int k = 0; k < F0B_TH / 4; k++) {
+        const int ly = (threadIdx.x >> 6) + 4 * k, y = ty0 + ly;
+        if (x < rw && y < rh) {
+            int sxx = 0, sxy = 0, syy = 0;
+            for (int j = 0; j < block; j++)
+                for (int i = 0; i < block; i++) {
+                    const int2 v = g[(ly + j) * gw + lx + i];
+                    sxx += v.x * v.x; sxy += v.x * v.y; syy += v.y * v.y;
+                }
+            const float a = __fmul_rn((float)sxx, s2), b = __fmul_rn((float)sxy, s2), c = __fmul_rn((float)syy, s2);
+            const float tr = __fadd_rn(a, c);
+            const float r = __fsub_rn(__fsub_rn(__fmul_rn(a, c), __fmul_rn(b, b)), __fmul_rn(__fmul_rn(kf, tr), tr));
+            resp[(size_t)y * rw + x] = r;
+            o = max(o, f2ord(r));
+        }
+    }
+    for (int s = 32; s > 0; s >>= 1) o = max(o, (unsigned)__shfl_xor((int)o, s, 64));  // every lane takes part, inside the ROI or not
+    if (lx == 0 && o) atomicMax(&cnt[4 * blockIdx.z], o);
+}
+
+// k_init_candidates per clip: the thresholded 3x3 local maxima, appended to the clip's key segment through its counter (one atomic per wavefront)
+__global__ __launch_bounds__(256) void k_f0b_candidates(const F0Clip* tab, double quality, const float* resp_base, unsigned long long* keys_base, unsigned* cnt)
+{
+    const F0Clip& C = tab[blockIdx.z];
+    const int rw = C.rw, rh = C.rh, tx0 = blockIdx.x * F0B_TW, ty0 = blockIdx.y * F0B_TH;
+    if (tx0 >= rw || ty0 >= rh) return;
+    const float* resp = resp_base + C.seg;
+    unsigned long long* keys = keys_base + C.seg;
+    unsigned* count = &cnt[4 * blockIdx.z + 1];
+    const float thr = (float)((double)ord2f(cnt[4 * blockIdx.z]) * quality);
+    const int lane = threadIdx.x & 63, x = tx0 + lane;
+    const unsigned cap = (unsigned)rw * (unsigned)rh;
+    for (int k = 0; k < F0B_TH / 4; k++) {
+        const int y = ty0 + (threadIdx.x >> 6) + 4 * k;
+        bool hit = false;
+        unsigned long long key = 0;
+        if (x >= 1 && y >= 1 && x < rw - 1 && y < rh - 1) {
+            const float v0 = resp[(size_t)y * rw + x];
+            if (v0 > thr) {  // THRESH_TOZERO; survivors are compared with the thresholded neighbours
+                float m = v0;
+#pragma unroll
+                for (int j = -1; j <= 1; j++)
+#pragma unroll
+                    for (int i = -1; i <= 1; i++) {
+                        const float u = resp[(size_t)(y + j) * rw + x + i];
+                        if (u > thr && u > m) m = u;
+                    }
+                hit = v0 == m && v0 != 0.f;
+                key = ((unsigned long long)__float_as_uint(v0) << 32) | (unsigned)(y * rw + x);
+            }
+        }
+        const unsigned long long bal = __ballot(hit);
+        if (bal) {
+            const int leader = __ffsll((long long)bal) - 1;
+            unsigned base = 0;
+            if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(bal));
+            base = (unsigned)__shfl((int)base, leader, 64);
+            const unsigned slot = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+            if (hit && slot < cap) keys[slot] = key;
+        }
+    }
+}
+
+// One workgroup per clip: K = min(candidates, max_corners); the keys >= the K-th largest (radix select, 8-bit digits from the top byte down,
+// stopping as soon as the digit's bin holds exactly the keys still wanted) are gathered and -- LDS_SORT -- sorted descending in LDS (bitonic) and
+// written as corners + the ROI origin (k_init_emit), or gathered into the clip's segment of `gsel` for the segmented sort.  Also p[0:4] = q.
+template <bool LDS_SORT>
+__global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int b0, int max_corners, int cap, const unsigned long long* keys_base, unsigned* cnt,
+                                                     float* p_out, unsigned long long* gsel, int* seg_begin, int* seg_end)
+{
+    const int clip = blockIdx.x, tid = threadIdx.x;
+    const F0Clip& C = tab[clip];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned long long s_sel[LDS_SORT ? F0B_SEL_MAX : 1];
+    __shared__ unsigned s_bin, s_krem, s_done, s_n;
+    const unsigned npx = (unsigned)C.rw * (unsigned)C.rh;
+    const unsigned count = min(cnt[4 * clip + 1], npx), K = min(count, (unsigned)max_corners);
+    const unsigned long long* keys = keys_base + C.seg;
+    unsigned long long T = 0;  // the selection: every key >= T (exactly K keys)
+    if (count > K) {
+        unsigned long long prefix = 0, himask = 0;
+        unsigned krem = K;  // keys still wanted among those matching prefix on the bits decided so far
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            for (unsigned i = tid; i < count; i += 1024) {
+                const unsigned long long k = keys[i];
+                if (((k ^ prefix) & himask) == 0) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid < 64) {  // the bin holding rank krem, counted from the top: lane l owns bins 4l .. 4l+3
+                const unsigned h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+                const unsigned own = h0 + h1 + h2 + h3;
+                unsigned v = own;  // -> sum over lanes >= tid
+                for (int off = 1; off < 64; off <<= 1) {
+                    const unsigned t = (unsigned)__shfl_down((int)v, off, 64);
+                    if (tid + off < 64) v += t;
+                }
+                unsigned above = v - own;
+                if (above < krem && krem <= above + own) {
+                    const unsigned hb[4] = {h0, h1, h2, h3};
+                    for (int q = 3; q >= 0; q--) {
+                        if (krem <= above + hb[q]) {
+                            s_bin = 4 * tid + q;
+                            s_krem = krem - above;
+                            s_done = hb[q] == krem - above;
+                            break;
+                        }
+                        above += hb[q];
+                    }
+                }
+            }
+            __syncthreads();
+            prefix |= (unsigned long long)s_bin << shift;
+            himask |= 0xffull << shift;
+            krem = s_krem;
+            if (s_done) break;  // (uniform: read from LDS after the barrier)
+        }
+        T = prefix;
+    }
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    unsigned long long* dst = LDS_SORT ? s_sel : gsel + (size_t)clip * max_corners;
+    for (unsigned i = tid; i < count; i += 1024) {
+        const unsigned long long k = keys[i];
+        if (k >= T) {
+            const unsigned slot = atomicAdd(&s_n, 1u);
+            if (slot < K) dst[slot] = k;
+        }
+    }
+    float* p = p_out + (size_t)(b0 + clip) * cap * 2;
+    if (tid < 8) p[tid] = C.q[tid];  // p = concatenate((q, corners)) (vidExample.py:116)
+    if (tid == 0) cnt[4 * clip + 2] = K;
+    if (!LDS_SORT) {
+        if (tid == 0) { seg_begin[clip] = clip * max_corners; seg_end[clip] = clip * max_corners + (int)K; }
+        return;
+    }
+    unsigned P = 1;
+    while (P < K) P <<= 1;
+    for (unsigned i = K + tid; i < P; i += 1024) s_sel[i] = 0;  // real keys are > 0 (their response is not +-0): padding sorts last
+    __syncthreads();
+    for (unsigned k = 2; k <= P; k <<= 1)
+        for (unsigned j = k >> 1; j > 0; j >>= 1) {
+            for (unsigned i = tid; i < P; i += 1024) {
+                const unsigned l = i ^ j;
+                if (l > i) {
+                    const unsigned long long a = s_sel[i], b = s_sel[l];
+                    if ((i & k) == 0 ? a < b : a > b) { s_sel[i] = b; s_sel[l] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    for (unsigned i = tid; i < K; i += 1024) {
+        const unsigned idx = (unsigned)(s_sel[i] & 0xffffffffull);
+        p[8 + 2 * i] = __fadd_rn((float)(idx % (unsigned)C.rw), C.offx);
+        p[8 + 2 * i + 1] = __fadd_rn((float)(idx / (unsigned)C.rw), C.offy);
+    }
+}
+
+// corners of the segmented-sort route (max_corners > F0B_SEL_MAX), as k_init_emit
+__global__ __launch_bounds__(256) void k_f0b_emit(const F0Clip* tab, int b0, int max_corners, int cap, const unsigned long long* sorted, const unsigned* cnt,
+                                                  float* p_out)
+{
+    const int clip = blockIdx.y;
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= cnt[4 * clip + 2]) return;
+    const F0Clip& C = tab[clip];
+    const unsigned idx = (unsigned)(sorted[(size_t)clip * max_corners + i] & 0xffffffffull);
+    float* p = p_out + (size_t)(b0 + clip) * cap * 2 + 8;
+    p[2 * i] = __fadd_rn((float)(idx % (unsigned)C.rw), C.offx);
+    p[2 * i + 1] = __fadd_rn((float)(idx / (unsigned)C.rw), C.offy);
+}
+
+__global__ __launch_bounds__(64) void k_f0b_subpix(const F0Clip* tab, int b0, int cap, int w, int h, size_t st, const unsigned* cnt, int max_corners, int win,
+                                                   int max_iter, double eps2, const float* mask, float* p_out)
+{
+    const int clip = blockIdx.y, q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= min((int)cnt[4 * clip + 2], max_corners)) return;
+    subpix_corner(tab[clip].im, w, h, st, p_out + (size_t)(b0 + clip) * cap * 2 + 8, q, win, max_iter, eps2, mask);
+}
+
+// per clip: zero the counters, build the plate-pose job of vh_frame0_init (estimateWorldCameraPose(K, q, plate, findR=True) from x0 = [0, 0, 0, 0, 0, 1])
+__global__ __launch_bounds__(64) void k_f0b_setup(const F0Shared* sh, int b0, int n, int cap, float* p_out, float* t_out, double* R_out, double* res_out,
+                                                  unsigned* cnt, int* info, PoseJob* pose)
+{
+    const int clip = blockIdx.x * 64 + threadIdx.x;
+    if (clip >= n) return;
+    const size_t b = (size_t)(b0 + clip);
+    for (int k = 0; k < 4; k++) cnt[4 * clip + k] = 0;
+    PoseJob P;
+    for (int i = 0; i < 9; i++) { P.K[i] = sh->K[i]; P.R[i] = (i % 4 == 0) ? 1.0 : 0.0; }
+    for (int i = 0; i < 6; i++) P.x0[i] = i == 5 ? 1.0 : 0.0;
+    P.p = p_out + b * cap * 2; P.pw = sh->plate; P.p_sel = nullptr; P.pw_sel = nullptr; P.n_ptr = nullptr; P.n = 4; P.mode = 1;
+    P.t_out = t_out + 3 * b; P.R_out = R_out + 9 * b; P.res_out = res_out + b; P.p_proj = nullptr; P.info_out = info + 2 * clip;
+    pose[clip] = P;
+}
+
+__global__ __launch_bounds__(256) void k_f0b_world(const F0Clip* tab, const F0Shared* sh, int b0, int cap, const unsigned* cnt, const double* R_out,
+                                                   const float* t_out, const float* p_out, double* p3_out, uint8_t* vp_out, int* n_out)
+{
+    const int clip = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const size_t b = (size_t)(b0 + clip);
+    const int n = min(4 + (int)cnt[4 * clip + 2], cap);
+    if (i == 0) n_out[b] = n;
+    if (i >= cap) return;
+    Frame0Job J;  // (the fields the row reads)
+    for (int k = 0; k < 9; k++) J.K[k] = sh->K[k];
+    for (int k = 0; k < 4; k++) J.boxa[k] = tab[clip].boxa[k];
+    frame0_world_row(i, n, J, R_out + 9 * b, t_out + 3 * b, p_out + b * cap * 2, p3_out + b * cap * 3, vp_out + b * cap);
+}
+
+static void batch_sel_release(InitBatchScratch& B)
+{
+    (void)hipFree(B.sel); (void)hipFree(B.sorted); (void)hipFree(B.seg); (void)hipFree(B.sort_tmp);
+    B.sel = B.sorted = nullptr; B.seg = nullptr; B.sort_tmp = nullptr; B.sort_bytes = B.sel_cap = 0;
+}
+static void batch_release(InitBatchScratch& B)
+{
+    batch_sel_release(B);
+    (void)hipFree(B.resp); (void)hipFree(B.keys); (void)hipFree(B.cnt); (void)hipFree(B.info); (void)hipFree(B.tab); (void)hipFree(B.shared);
+    (void)hipFree(B.pose); (void)hipFree(B.mask);
+    memset(&B, 0, sizeof(B));
+}
+
+// growth of scratch that kernels queued earlier may still use: after a stream synchronisation, never inside a capture
+static int batch_grow_guard(const InitBatchScratch& B, bool had, hipStream_t s)
+{
+    if (!had) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return vh_fail(-6, "batched frame-0 scratch must grow inside a stream capture: call vh_init_reserve_batch(ctx, nb, w, h) before capturing");
+    VH_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+static size_t batch_clip_bytes(size_t px) { return 12 * px + 24 + sizeof(F0Clip) + sizeof(PoseJob); }
+
+// scratch for chunks of up to `clips` clips and `pix` ROI pixels in all (never shrinks)
+static int batch_reserve(vh_ctx* c, int clips, size_t pix, hipStream_t s)
+{
+    InitBatchScratch& B = c->init_batch;
+    if (B.clips_cap >= clips && B.pix_cap >= pix) return 0;
+    int r = batch_grow_guard(B, B.clips_cap > 0, s);
+    if (r) return r;
+    clips = clips > B.clips_cap ? clips : B.clips_cap;
+    pix = pix > B.pix_cap ? pix : B.pix_cap;
+    const int expl = B.explicit_size;
+    batch_release(B);
+    const int tab_n = (clips + F0B_PIECE - 1) / F0B_PIECE * F0B_PIECE;
+    VH_CHECK(hipMalloc((void**)&B.resp, pix * 4));
+    VH_CHECK(hipMalloc((void**)&B.keys, pix * 8));
+    VH_CHECK(hipMalloc((void**)&B.cnt, sizeof(unsigned) * 4 * clips));
+    VH_CHECK(hipMalloc((void**)&B.info, sizeof(int) * 2 * clips));
+    VH_CHECK(hipMalloc(&B.tab, sizeof(F0Clip) * tab_n));
+    VH_CHECK(hipMalloc(&B.shared, sizeof(F0Shared)));
+    VH_CHECK(hipMalloc((void**)&B.pose, sizeof(PoseJob) * clips));
+    r = subpix_masks_create(&B.mask);
+    if (r) return r;
+    B.clips_cap = clips;
+    B.pix_cap = pix;
+    B.explicit_size = expl;
+    return 0;
+}
+
+// the segmented-sort route's buffers for max_corners above F0B_SEL_MAX
+static int batch_sel_reserve(vh_ctx* c, int max_corners, hipStream_t s)
+{
+    InitBatchScratch& B = c->init_batch;
+    const size_t need = (size_t)B.clips_cap * max_corners;
+    if (B.sel_cap >= need) return 0;
+    if (need > 0x7fffffffu) return vh_fail(-1, "vh_frame0_init_batch: clips x max_corners exceeds the segmented sort's range");
+    int r = batch_grow_guard(B, B.sel_cap > 0, s);
+    if (r) return r;
+    batch_sel_release(B);
+    VH_CHECK(hipMalloc((void**)&B.sel, need * 8));
+    VH_CHECK(hipMalloc((void**)&B.sorted, need * 8));
+    VH_CHECK(hipMalloc((void**)&B.seg, sizeof(int) * 2 * B.clips_cap));
+    size_t bytes = 0;
+    VH_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, B.sel, B.sorted, (unsigned)need, (unsigned)B.clips_cap, B.seg, B.seg + B.clips_cap, 0, 64, 0));
+    VH_CHECK(hipMalloc(&B.sort_tmp, bytes));
+    B.sort_bytes = bytes;
+    B.sel_cap = need;
+    return 0;
+}
+
+void vh_init_batch_scratch_free(vh_ctx* c)
+{
+    if (c) batch_release(c->init_batch);
+}
+
+extern "C" VH_API int vh_init_reserve_batch(vh_ctx* c, int nb, int w, int h, void* stream)
+{
+    if (!c || nb < 1 || w < 1 || h < 1) return vh_fail(-1, "vh_init_reserve_batch: bad arguments");
+    VH_BIND(c, stream);
+    const int r = batch_reserve(c, nb, (size_t)nb * w * h, bound_.s);
+    if (r) return r;
+    c->init_batch.explicit_size = 1;
+    return 0;
+}
+
+extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
+                                           const double* K_host, const double* plate_host, int border_x, int border_y, int max_corners, double quality,
+                                           int block, double k, int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out,
+                                           uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host, void* stream)
+{
+    // every check before anything is queued
+    if (!c || !frames_host || !q_host || !K_host || !plate_host || !p_out || !p3_out || !vp_out || !t_out || !R_out || !res_out || !n_out)
+        return vh_fail(-1, "vh_frame0_init_batch: null argument");
+    if (nb < 1 || w < 3 || h < 3 || stride < w || max_corners < 1 || block < 1 || block > 15 || subpix_win < 1 || subpix_win > SUBPIX_MAXWIN)
+        return vh_fail(-1, "vh_frame0_init_batch: bad arguments");
+    std::vector<F0Clip> clips(nb);
+    std::vector<int> rois(8 * (size_t)nb);  // boxa, boxb of every clip
+    size_t max_px = 0;
+    for (int b = 0; b < nb; b++) {
+        if (!frames_host[b]) {
+            char msg[96];
+            snprintf(msg, sizeof(msg), "vh_frame0_init_batch: clip %d has a null frame", b);
+            return vh_fail(-1, msg);
+        }
+        F0Clip& C = clips[b];
+        memset(&C, 0, sizeof(C));
+        int* boxb = &rois[8 * b + 4];
+        host_bounding_rect(q_host + 8 * b, 4, w, h, 0, 0, C.boxa);  // vidExample.py:107
+        host_bounding_rect(q_host + 8 * b, 4, w, h, border_x, border_y, boxb);  // :108
+        memcpy(&rois[8 * b], C.boxa, sizeof(C.boxa));
+        C.rw = boxb[1] - boxb[0];
+        C.rh = boxb[3] - boxb[2];
+        if (C.rw < 3 || C.rh < 3) {
+            char msg[96];
+            snprintf(msg, sizeof(msg), "vh_frame0_init_batch: the plate ROI of clip %d is empty", b);
+            return vh_fail(-1, msg);
+        }
+        C.im = frames_host[b];
+        C.roi = frames_host[b] + (size_t)boxb[2] * stride + boxb[0];
+        C.offx = (float)boxb[0];
+        C.offy = (float)boxb[2];
+        for (int i = 0; i < 8; i++) C.q[i] = q_host[8 * b + i];
+        const size_t px = (size_t)C.rw * C.rh;
+        max_px = px > max_px ? px : max_px;
+    }
+    VH_BIND(c, stream);
+    hipStream_t s = bound_.s;
+    InitBatchScratch& B = c->init_batch;
+    int r;
+    if (B.explicit_size) {  // chunks of the reserved size; grown only for a ROI larger than the whole scratch
+        r = batch_reserve(c, B.clips_cap, max_px, s);
+    } else {                // as many clips per chunk as the budget holds
+        const size_t fit = F0B_BUDGET / batch_clip_bytes(max_px);
+        const int want = (int)(fit < 1 ? 1 : (fit < (size_t)nb ? fit : (size_t)nb));
+        r = batch_reserve(c, want, (size_t)want * max_px, s);
+    }
+    if (r) return r;
+    if (max_corners > F0B_SEL_MAX && (r = batch_sel_reserve(c, max_corners, s))) return r;
+    if (roi_host) memcpy(roi_host, rois.data(), sizeof(int) * 8 * nb);
+    F0Shared sh;
+    for (int i = 0; i < 9; i++) sh.K[i] = K_host[i];
+    for (int i = 0; i < 12; i++) sh.plate[i] = plate_host[i];
+    F0Shared* d_sh = reinterpret_cast<F0Shared*>(B.shared);
+    F0Clip* d_tab = reinterpret_cast<F0Clip*>(B.tab);
+    VH_CHECK(vh_store(d_sh, sh, s));
+    const int cap = 4 + max_corners;
+    const double scale = 1.0 / (4.0 * block * 255.0);
+    const int iters = subpix_iter < 1 ? 1 : (subpix_iter > 100 ? 100 : subpix_iter);
+    const double eps = subpix_eps < 0 ? 0 : subpix_eps;
+    const float* mask = B.mask + subpix_mask_offset(subpix_win);
+    for (int b0 = 0; b0 < nb;) {
+        // one chunk: as many clips as the scratch holds, their ROI planes back to back
+        int n = 0, mw = 0, mh = 0;
+        size_t px = 0;
+        while (b0 + n < nb && n < B.clips_cap && n < 65535 && px + (size_t)clips[b0 + n].rw * clips[b0 + n].rh <= B.pix_cap) {  // (grid.z <= 65535)
+            F0Clip& C = clips[b0 + n];
+            C.seg = px;
+            px += (size_t)C.rw * C.rh;
+            mw = C.rw > mw ? C.rw : mw;
+            mh = C.rh > mh ? C.rh : mh;
+            n++;
+        }
+        for (int p0 = 0; p0 < n; p0 += F0B_PIECE) {
+            F0ClipPiece piece;
+            memset(&piece, 0, sizeof(piece));
+            for (int i = 0; i < F0B_PIECE && p0 + i < n; i++) piece.c[i] = clips[b0 + p0 + i];
+            VH_CHECK(vh_store(reinterpret_cast<F0ClipPiece*>(d_tab + p0), piece, s));
+        }
+        hipLaunchKernelGGL(k_f0b_setup, dim3((n + 63) / 64), dim3(64), 0, s, d_sh, b0, n, cap, p_out, t_out, R_out, res_out, B.cnt, B.info, B.pose);
+        const dim3 tiles((mw + F0B_TW - 1) / F0B_TW, (mh + F0B_TH - 1) / F0B_TH, n);
+        hipLaunchKernelGGL(k_f0b_harris, tiles, dim3(256), 0, s, d_tab, (size_t)stride, block, (float)(scale * scale), (float)k, B.resp, B.cnt);
+        hipLaunchKernelGGL(k_f0b_candidates, tiles, dim3(256), 0, s, d_tab, quality, B.resp, B.keys, B.cnt);
+        if (max_corners <= F0B_SEL_MAX) {
+            hipLaunchKernelGGL(k_f0b_select<true>, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, cap, B.keys, B.cnt, p_out, nullptr, nullptr, nullptr);
+        } else {
+            int* seg_end = B.seg + B.clips_cap;
+            hipLaunchKernelGGL(k_f0b_select<false>, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, cap, B.keys, B.cnt, p_out, B.sel, B.seg, seg_end);
+            size_t bytes = 0;
+            const unsigned size = (unsigned)n * (unsigned)max_corners;
+            VH_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
+            if (bytes > B.sort_bytes) return vh_fail(-1, "vh_frame0_init_batch: segmented sort scratch too small");
+            bytes = B.sort_bytes;
+            VH_CHECK(rocprim::segmented_radix_sort_keys_desc(B.sort_tmp, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
+            hipLaunchKernelGGL(k_f0b_emit, dim3((max_corners + 255) / 256, n), dim3(256), 0, s, d_tab, b0, max_corners, cap, B.sorted, B.cnt, p_out);
+        }
+        hipLaunchKernelGGL(k_f0b_subpix, dim3((max_corners + 63) / 64, n), dim3(64), 0, s, d_tab, b0, cap, w, h, (size_t)stride, B.cnt, max_corners,
+                           subpix_win, iters, eps * eps, mask, p_out);
+        vh_launch_pose(B.pose, sizeof(PoseJob), n, 1, 4, s);
+        hipLaunchKernelGGL(k_f0b_world, dim3((cap + 255) / 256, n), dim3(256), 0, s, d_tab, d_sh, b0, cap, B.cnt, R_out, t_out, p_out, p3_out, vp_out, n_out);
+        VH_CHECK(hipGetLastError());
+        b0 += n;
+    }
     return 0;
 }

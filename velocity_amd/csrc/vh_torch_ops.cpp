@@ -18,6 +18,7 @@
 #include <mutex>
 #include <tuple>
 #include <utility>
+#include <vector>
 
 #include "../../include/velocity_hip.h"
 
@@ -260,6 +261,41 @@ std::tuple<Tensor, Tensor, Tensor> ba_solve(const Tensor& K, const Tensor& z, co
     return {x, trace, info};
 }
 
+// frame-0 initialisation of a batch of clips (vidExample.py:105-127 for each): frames CUDA uint8 [B,H,W], q [B,4,2] plate corners (host values), K, plate
+// [4,3] world points -> (p [B,cap,2] f32, p3 [B,cap,3] f64, vp [B,cap] u8, t [B,3] f32, R [B,3,3] f64, res [B] f64, n [B] i32, rois [B,8] i32 on the host),
+// cap = 4 + max_corners; row b of each holds what vh_frame0_init gives for clip b (rows beyond n[b]: p 0, p3 0, vp 0)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> frame0_init(const Tensor& frames, const Tensor& q, const Tensor& K, const Tensor& plate,
+                                                                                         int64_t border_x, int64_t border_y, int64_t max_corners, double quality,
+                                                                                         int64_t block, double k, int64_t subpix_win, int64_t subpix_iter,
+                                                                                         double subpix_eps)
+{
+    TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte && frames.dim() == 3 && frames.stride(2) == 1 && frames.stride(1) >= frames.size(2),
+                "frame0_init(frames): expected CUDA uint8 [B,H,W] frames with unit column stride");
+    const int64_t nb = frames.size(0);
+    TORCH_CHECK(nb >= 1 && q.numel() == nb * 8, "frame0_init: q must hold [B,4,2] plate corners");
+    TORCH_CHECK(plate.numel() == 12, "frame0_init: plate must hold 4 x 3 world points");
+    TORCH_CHECK(max_corners >= 1, "frame0_init: max_corners must be >= 1");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(frames.device());
+    void* s = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    const int h = (int)frames.size(1), w = (int)frames.size(2);
+    double Kh[9];
+    host_K(K, Kh);
+    Tensor qh = q.detach().to(at::kCPU, at::kFloat).contiguous(), ph = plate.detach().to(at::kCPU, at::kDouble).contiguous();
+    std::vector<const uint8_t*> ptrs(nb);
+    for (int64_t b = 0; b < nb; b++) ptrs[b] = frames.data_ptr<uint8_t>() + b * frames.stride(0);
+    const int64_t cap = 4 + max_corners;
+    auto opt = frames.options();
+    Tensor p = at::zeros({nb, cap, 2}, opt.dtype(at::kFloat)), p3 = at::empty({nb, cap, 3}, opt.dtype(at::kDouble)), vp = at::empty({nb, cap}, opt.dtype(at::kByte)),
+           t = at::empty({nb, 3}, opt.dtype(at::kFloat)), R = at::empty({nb, 3, 3}, opt.dtype(at::kDouble)), res = at::empty({nb}, opt.dtype(at::kDouble)),
+           n = at::empty({nb}, opt.dtype(at::kInt)), rois = at::empty({nb, 8}, at::TensorOptions().dtype(at::kInt));
+    vh_check(vh_frame0_init_batch(workspace(frames, w, h, 0, s), (int)nb, ptrs.data(), w, h, (int)frames.stride(1), qh.data_ptr<float>(), Kh, ph.data_ptr<double>(),
+                                  (int)border_x, (int)border_y, (int)max_corners, quality, (int)block, k, (int)subpix_win, (int)subpix_iter, subpix_eps,
+                                  p.data_ptr<float>(), p3.data_ptr<double>(), vp.data_ptr<uint8_t>(), t.data_ptr<float>(), R.data_ptr<double>(),
+                                  res.data_ptr<double>(), n.data_ptr<int>(), rois.data_ptr<int>(), s),
+             "vh_frame0_init_batch");
+    return {p, p3, vp, t, R, res, n, rois};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(velocity_hip, m)
@@ -274,6 +310,8 @@ TORCH_LIBRARY(velocity_hip, m)
     m.def("two_view_intercept(Tensor A, Tensor U) -> Tensor");
     m.def("msv1_t(Tensor K, Tensor P, Tensor B, Tensor ids, int ii) -> (Tensor, Tensor, Tensor)");
     m.def("ba_solve(Tensor K, Tensor z, Tensor x0, int nt, int nc, int max_iter=10) -> (Tensor, Tensor, Tensor)");
+    m.def("frame0_init(Tensor frames, Tensor q, Tensor K, Tensor plate, int border_x=700, int border_y=500, int max_corners=1000, float quality=0.01, "
+          "int block=5, float k=0.04, int subpix_win=5, int subpix_iter=100, float subpix_eps=0.001) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
 }
 
 // The inputs that decide the device are CUDA tensors: register under the CUDA (= HIP on ROCm) dispatch key.  There is deliberately NO CPU kernel:
@@ -289,4 +327,5 @@ TORCH_LIBRARY_IMPL(velocity_hip, CUDA, m)
     m.impl("two_view_intercept", &two_view_intercept);
     m.impl("msv1_t", &msv1_t);
     m.impl("ba_solve", &ba_solve);
+    m.impl("frame0_init", &frame0_init);
 }

@@ -72,6 +72,26 @@ struct InitScratch {
     size_t sort_bytes, pixels;
 };
 
+// scratch of the batched frame-0 initialisation (vh_init.hip: vh_frame0_init_batch), owned by the context; one chunk of clips at a time
+struct InitBatchScratch {
+    float* resp;                 // Harris response planes of a chunk's ROIs, back to back (pix_cap floats)
+    unsigned long long* keys;    // candidate keys, one segment per clip at the offset of its plane (pix_cap)
+    unsigned* cnt;               // per clip: [0] max response (ordered bits), [1] candidate count, [2] corners kept, [3] unused
+    int* info;                   // per clip: pose info (iterations, converged)
+    void* tab;                   // per-clip descriptors (F0Clip, vh_init.hip), clips_cap rounded up to a whole upload piece
+    void* shared;                // K and the plate points of the call (F0Shared)
+    PoseJob* pose;               // per-clip plate-pose jobs, built on the device
+    float* mask;                 // cornerSubPix Gaussian windows (as InitScratch::mask)
+    // max_corners above the in-LDS selection: the selected keys of each clip in a segment of max_corners, sorted by rocPRIM
+    unsigned long long *sel, *sorted;
+    int* seg;                    // segment begin [clips_cap] and end [clips_cap] offsets
+    void* sort_tmp;
+    size_t sort_bytes, sel_cap;  // sel_cap: keys per buffer
+    size_t pix_cap;
+    int clips_cap;
+    int explicit_size;           // sized by vh_init_reserve_batch: calls run in chunks of that size instead of growing it
+};
+
 struct vh_ctx {
     int batch, max_w, max_h, max_pts, sw, sh;
     char* arena;
@@ -94,6 +114,7 @@ struct vh_ctx {
     int lk_route[3];           // kernel route (vh_lk_route ids) the last KLTmain took for its three LK launches (vh_profile_lk_routes)
     int lk_win[3];
     InitScratch init;          // created by the first frame-0 call (vh_init.hip)
+    InitBatchScratch init_batch;  // created by the first batched frame-0 call or vh_init_reserve_batch (vh_init.hip)
 };
 
 // A vh_ctx parks the job descriptors of the calls in flight, so it serves ONE HIP stream at a time.  Enforced on the DEVICE: every entry point ends
@@ -204,7 +225,8 @@ struct SessStream {  // device resident, one per video stream
 int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_params& coarse, const vh_lk_params& fine,
                     const SessStream* sess = nullptr, const uint8_t* const* frames = nullptr, int n_max = 0);
 int vh_fail(int code, const char* msg);
-void vh_init_scratch_free(vh_ctx* c);
+void vh_init_scratch_free(vh_ctx* c);        // both frame-0 scratches (vh_init.hip)
+void vh_init_batch_scratch_free(vh_ctx* c);
 
 // optional HIP-event timing of individual launches (vh_profile_begin / vh_profile_end_stages): stage ids
 enum { VH_PROF_LK0 = 0, VH_PROF_LK1 = 1, VH_PROF_LK2 = 2, VH_PROF_WARP = 3, VH_PROF_PYR = 4, VH_PROF_RANSAC = 5, VH_PROF_RESIZE = 6, VH_PROF_SESSION = 7,

@@ -372,6 +372,51 @@ def _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corn
                 loop_seconds=loop_seconds, klt_flags=st["klt_flags"])
 
 
+def _frame0_buffers(torch, nb, cap):
+    """Device outputs of vh_frame0_init_batch for nb clips: p, p3, vp, t, R, res, n."""
+    return (torch.empty((nb, cap, 2), dtype=torch.float32, device="cuda"), torch.empty((nb, cap, 3), dtype=torch.float64, device="cuda"),
+            torch.empty((nb, cap), dtype=torch.uint8, device="cuda"), torch.empty((nb, 3), dtype=torch.float32, device="cuda"),
+            torch.empty((nb, 9), dtype=torch.float64, device="cuda"), torch.empty(nb, dtype=torch.float64, device="cuda"),
+            torch.empty(nb, dtype=torch.int32, device="cuda"))
+
+
+def _frame0_batch_call(lib, ws, frames0, qs, W, H, K64, plate_w, roi_border, max_corners, quality, block, harris_k, subpix, bufs):
+    """vh_frame0_init_batch on the current stream: frames0 = dense CUDA [H, W] frames, qs = their plate corners.  -> host list of nb x 8 ROIs (boxa, boxb)."""
+    nb = len(frames0)
+    q = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 2) for x in qs]))
+    ptrs = (C.c_void_p * nb)(*[f.data_ptr() for f in frames0])
+    rois = (C.c_int * (8 * nb))()
+    win, it, eps = subpix
+    p, p3, vp, t0, R0, res0, n0 = bufs
+    L.check(lib.vh_frame0_init_batch(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p),
+                                     plate_w.ctypes.data_as(L.f64p), int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block),
+                                     float(harris_k), int(win), int(it), float(eps), L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(R0), L.dptr(res0),
+                                     L.dptr(n0), rois, L.stream_ptr()), "vh_frame0_init_batch")
+    return list(rois)
+
+
+def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001)):
+    """Frame 0 of many clips at once (vidExample.py:105-127 for each): `frames` = the clips' first frames (numpy / torch uint8 [H, W] of one size, or one
+    [B, H, W] array), `qs` = their plate corners [4, 2].  One vh_frame0_init_batch launch sequence for all of them.  Returns one dict per clip with the keys
+    of the oracle's frame0: p [n, 2] (the 4 plate corners, then the refined Harris corners), p3 [n, 3], vp [n] bool, t [3], R [3, 3], res, boxa, boxb."""
+    torch = L.torch_cuda()
+    dev = [(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))).cuda().contiguous() for f in frames]
+    H, W = dev[0].shape
+    assert all(d.shape == (H, W) and d.dtype == torch.uint8 for d in dev), "frames must be uint8 and share one size"
+    nb, cap = len(dev), 4 + int(max_corners)
+    ws = L.workspace(W, H)
+    bufs = _frame0_buffers(torch, nb, cap)
+    plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
+    rois = _frame0_batch_call(ws.lib, ws, dev, qs, W, H, L.host_K(K), plate_w, roi_border, max_corners, quality, block, harris_k, subpix, bufs)
+    p, p3, vp, t0, R0, res0, n0 = (x.cpu().numpy() for x in bufs)
+    out = []
+    for b in range(nb):
+        k = int(n0[b])
+        out.append(dict(p=p[b, :k].copy(), p3=p3[b, :k].copy(), vp=vp[b, :k].astype(bool), t=t0[b].copy(), R=R0[b].reshape(3, 3).copy(), res=float(res0[b]),
+                        boxa=tuple(rois[8 * b:8 * b + 4]), boxb=tuple(rois[8 * b + 4:8 * b + 8])))
+    return out
+
+
 def session_groups(streams, tracks=2000):
     """How many TrackerSessions (each on its own HIP stream) to split `streams` resident video streams of ~`tracks` tracks each into.  The stages of a frame
     step that run ONE workgroup per stream (RANSAC, bookkeeping + pose, the glue kernels) leave the chip nearly idle; with a second session on another HIP
@@ -409,8 +454,9 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name]) of ONE frame size and
     length; every clip is a stream of a device-resident TrackerSession, so a frame step is one launch sequence for all the clips of a session
     (vh_session_step_v: each stream has its own clock).  `sessions`: the clips are split into this many sessions, each on its own HIP stream (0 = auto,
-    session_groups(len(clips)): their one-workgroup-per-stream stages overlap the others' LK launches); results do not depend on it.  Frame 0 of every clip
-    runs through vh_frame0_init on the device, its outputs feed vh_session_init_dev directly; nothing is read back before the last frame.  Returns one
+    session_groups(len(clips)): their one-workgroup-per-stream stages overlap the others' LK launches); results do not depend on it.  Frame 0 of the clips
+    of a session runs as ONE vh_frame0_init_batch call on the device, its outputs feed vh_session_init_dev directly; nothing is read back before the last
+    frame.  Returns one
     result dict per clip (the keys of run_sequence; `lines` = that clip's table and summary, printed through `out` if given), each equal to what
     run_sequence returns for the clip alone."""
     import time as _time
@@ -437,30 +483,23 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
         with torch.cuda.stream(hip_streams[g]):  # (a session's context serves one HIP stream: everything of session g is issued on stream g)
             sess.append(TrackerSession(K, W, H, cap, nhist=n, batch=len(members[g]), lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame))
     plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
-    win, it, eps = subpix
     times = np.stack([np.asarray(c["times"], np.float32) for c in clips])  # [clip, frame]
     fnos = np.stack([np.asarray(c.get("frame_numbers", np.arange(n)), np.float32) for c in clips])
-    keep = []
+    keep = [None] * nclip
     t_begin = _time.perf_counter()
-    for b, c in enumerate(clips):
-        ses = sess[owner[b]]
-        lib, ws = ses.lib, ses.ws
-        with torch.cuda.stream(hip_streams[owner[b]]):
-            q = np.ascontiguousarray(np.asarray(c["q"], np.float32).reshape(4, 2))
-            bufs = (torch.empty((cap, 2), dtype=torch.float32, device="cuda"), torch.empty((cap, 3), dtype=torch.float64, device="cuda"),
-                    torch.empty(cap, dtype=torch.uint8, device="cuda"), torch.empty(3, dtype=torch.float32, device="cuda"),
-                    torch.empty(9, dtype=torch.float64, device="cuda"), torch.empty(1, dtype=torch.float64, device="cuda"),
-                    torch.empty(1, dtype=torch.int32, device="cuda"))
+    for g in range(G):
+        ses, mem = sess[g], members[g]
+        with torch.cuda.stream(hip_streams[g]):
+            # frame 0 of every clip of the session: ONE vh_frame0_init_batch launch sequence into rows [slot] of these tensors
+            bufs = _frame0_buffers(torch, len(mem), cap)
+            rois = _frame0_batch_call(ses.lib, ses.ws, [dev[b][0] for b in mem], [clips[b]["q"] for b in mem], W, H, ses.K64, plate_w, roi_border, max_corners,
+                                      quality, block, harris_k, subpix, bufs)
             p, p3, vp, t0, R0, res0, n0 = bufs
-            rois = (C.c_int * 8)()
-            L.check(lib.vh_frame0_init(ws.handle, L.dptr(dev[b][0]), W, H, W, q.ctypes.data_as(L.f32p), ses.K64.ctypes.data_as(L.f64p), plate_w.ctypes.data_as(L.f64p),
-                                       int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block), float(harris_k), int(win), int(it),
-                                       float(eps), L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(R0), L.dptr(res0), L.dptr(n0), rois, L.stream_ptr()),
-                    "vh_frame0_init")
-            L.check(lib.vh_session_init_dev(ses.handle, slot[b], L.dptr(dev[b][0]), W, L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
-                                            float(times[b, 0]), float(fnos[b, 0]), L.stream_ptr()), "vh_session_init_dev")
-            ses._keep[slot[b]] = dev[b][0]
-        keep.append((bufs, tuple(rois)))
+            for j, b in enumerate(mem):
+                L.check(ses.lib.vh_session_init_dev(ses.handle, j, L.dptr(dev[b][0]), W, L.dptr(p[j]), L.dptr(p3[j]), L.dptr(vp[j]), L.dptr(t0[j]), L.dptr(res0[j]),
+                                                    L.dptr(n0[j]), float(times[b, 0]), float(fnos[b, 0]), L.stream_ptr()), "vh_session_init_dev")
+                ses._keep[j] = dev[b][0]
+                keep[b] = (tuple(x[j] for x in bufs), tuple(rois[8 * j:8 * j + 8]))
     t_loop = _time.perf_counter()
     for i in range(1, n):
         for g in range(G):
