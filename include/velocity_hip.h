@@ -192,7 +192,8 @@ VH_API int vh_nls_batch_phase(vh_ctx* ctx, const double* K_host, const double* z
                               size_t* span_offset, size_t* span_doubles, void* stream);
 
 /* ---- frame-0 initialisation ---------------------------------------------------------- */
-/* cv2.goodFeaturesToTrack(roi, maxCorners, qualityLevel, 0, blockSize=block, useHarrisDetector=True, k), vidExample.py:110.
+/* cv2.goodFeaturesToTrack(roi, maxCorners, qualityLevel, 0, blockSize=block, useHarrisDetector=True, k), vidExample.py:110 (other detectors,
+ * min_distance and masks: vh_good_features2).
  * corners: device float [max_corners x 2] (x, y) sorted by response; count: device int[1] */
 VH_API int vh_good_features(vh_ctx* ctx, const uint8_t* im, int w, int h, int stride, int max_corners, double quality, int block,
                             double k, float* corners, int* count, void* stream);
@@ -236,6 +237,27 @@ VH_API int vh_frame0_init_batch(vh_ctx* ctx, int nb, const uint8_t* const* frame
                                 const double* K_host, const double* plate_host, int border_x, int border_y, int max_corners, double quality,
                                 int block, double k, int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out,
                                 uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host, void* stream);
+
+/* (vh_version >= 107) cv2.goodFeaturesToTrack(im, max_corners, quality, min_distance, mask=mask, blockSize=block, useHarrisDetector=use_harris, k) on
+ * the batch kernels of vh_frame0_init_batch with one clip.  vh_good_features above stays the entry of the reference's call (Harris, min_distance 0).
+ *   Response: the integer Sobel pair and block x block sums of vh_good_features, scaled by s2 = (float)(scale^2), scale = 1 / (4 block 255); Harris
+ *   (use_harris != 0) as there, otherwise the minimum eigenvalue (a = sxx s2 / 2, b = sxy s2, c = syy s2 / 2, (a + c) - sqrt((a - c)^2 + b^2)), float32
+ *   with round-to-nearest at every step (a correctly rounded sqrt).  The threshold is quality times the maximum over the pixels where mask != 0 (all pixels without a mask); the
+ *   candidates are the interior 3x3 maxima of the thresholded response that the mask keeps, ordered by response (ties: larger pixel index first).
+ *   min_distance < 1 (negative included): the first max_corners candidates.  Otherwise a candidate is kept iff no corner kept before it lies at
+ *   squared distance < min_distance^2, until max_corners are kept -- for integer positions exactly OpenCV's grid of cvRound(min_distance) cells.
+ *   mask: device uint8 w x h (row stride mask_stride), or NULL.  corners: device float [max_corners x 2] (x, y); count: device int[1].
+ *   -1: bad arguments, max_corners < 1 included, or a NaN / infinite min_distance.  Scratch: that of vh_frame0_init_batch (one clip of w x h). */
+VH_API int vh_good_features2(vh_ctx* ctx, const uint8_t* im, int w, int h, int stride, const uint8_t* mask, int mask_stride, int max_corners,
+                             double quality, double min_distance, int block, int use_harris, double k, float* corners, int* count, void* stream);
+/* (vh_version >= 107) vh_frame0_init_batch with the detector of vh_good_features2 (no mask): use_harris = 0 selects the minimum eigenvalue, min_distance
+ * >= 1 spaces the corners.  use_harris = 1, min_distance = 0 gives vh_frame0_init_batch's results bit for bit, through the same kernels.  The spacing
+ * stage needs no extra scratch (it reuses the clip's response plane) and handles any max_corners without the segmented sort. */
+VH_API int vh_frame0_init_batch2(vh_ctx* ctx, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
+                                 const double* K_host, const double* plate_host, int border_x, int border_y, int max_corners, double quality,
+                                 int block, double k, int use_harris, double min_distance, int subpix_win, int subpix_iter, double subpix_eps,
+                                 float* p_out, double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out,
+                                 int* roi_host, void* stream);
 
 /* ---- tracker session: the frame loop body of vidExample.py:133-160 on the device, for ctx->batch streams ------- */
 /* device pointers into the state of one stream (read with vh_copy_to_host / torch) */

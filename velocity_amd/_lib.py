@@ -103,6 +103,10 @@ _SIGS = {
     "vh_init_reserve_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp]),
     "vh_frame0_init_batch": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, f32p, f64p, f64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                        C.c_double, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, i32p, vp]),
+    "vh_good_features2": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, vp,
+                                    vp, vp]),
+    "vh_frame0_init_batch2": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, f32p, f64p, f64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                        C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, i32p, vp]),
     "vh_msv1_t": (C.c_int, [vp, f64p, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
 }
 

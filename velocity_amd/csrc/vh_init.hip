@@ -448,8 +448,10 @@ extern "C" VH_API int vh_frame0_init(vh_ctx* c, const uint8_t* im, int w, int h,
 // ---------------------------------------------------------------------------------------------------------------
 #define F0B_TW 64        // Harris / candidate tile: 64 x 16 pixels, 256 threads
 #define F0B_TH 16
-#define F0B_PIECE 32     // descriptors per upload (one kernel argument of 32 x 88 bytes)
+#define F0B_PIECE 32     // descriptors per upload (one kernel argument of 32 x 104 bytes)
 #define F0B_SEL_MAX 2048 // max_corners up to this: selected keys sorted in LDS; above: rocPRIM segmented sort
+#define F0B_WIN 2048     // k_f0b_spread: candidates per window (sorted in LDS)
+#define F0B_EMPTY 0xffffffffu
 static const size_t F0B_BUDGET = (size_t)1 << 30;  // scratch of a context sized by the first call (include/velocity_hip.h)
 
 struct F0Clip {
@@ -460,6 +462,8 @@ struct F0Clip {
     float offx, offy;          // ROI origin
     int boxa[4];
     float q[8];
+    const uint8_t* mask;       // ROI-relative detection mask (NULL: none): pixels where it is 0 neither set the maximum nor become corners
+    int mstride, pad_;
 };
 struct F0ClipPiece {
     F0Clip c[F0B_PIECE];
@@ -469,8 +473,11 @@ struct F0Shared {
     double plate[12];
 };
 
-// Sobel (k_init_sobel) into an LDS tile with a (block - 1) halo, Harris response (k_init_harris's sums and float32 expression) of 64 x 16 pixels,
-// per-clip maximum.  REFLECT_101 is relative to the clip's ROI: a halo entry holds the Sobel pair of the reflected pixel, as k_init_harris reads it.
+// Sobel (k_init_sobel) into an LDS tile with a (block - 1) halo, response of 64 x 16 pixels, per-clip maximum over the pixels the clip's mask keeps.
+// HARRIS: k_init_harris's sums and float32 expression; otherwise the minimum eigenvalue of the same structure tensor (OpenCV's calcMinEigenVal:
+// a = sxx s2 / 2, b = sxy s2, c = syy s2 / 2, (a + c) - sqrt((a - c)^2 + b^2), every step rounded to float32).  REFLECT_101 is relative to the clip's
+// ROI: a halo entry holds the Sobel pair of the reflected pixel, as k_init_harris reads it.
+template <bool HARRIS>
 __global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, size_t st, int block, float s2, float kf, float* resp_base, unsigned* cnt)
 {
     const F0Clip& C = tab[blockIdx.z];
@@ -489,6 +496,7 @@ __global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, size_t st
     __syncthreads();
     const int lx = threadIdx.x & 63, x = tx0 + lx;
     float* resp = resp_base + C.seg;
+    const uint8_t* mask = C.mask;
     unsigned o = 0u;
     for (int k = 0; k < F0B_TH / 4; k++) {
         const int ly = (threadIdx.x >> 6) + 4 * k, y = ty0 + ly;
@@ -499,18 +507,25 @@ __global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, size_t st
                     const int2 v = g[(ly + j) * gw + lx + i];
                     sxx += v.x * v.x; sxy += v.x * v.y; syy += v.y * v.y;
                 }
-            const float a = __fmul_rn((float)sxx, s2), b = __fmul_rn((float)sxy, s2), c = __fmul_rn((float)syy, s2);
-            const float tr = __fadd_rn(a, c);
-            const float r = __fsub_rn(__fsub_rn(__fmul_rn(a, c), __fmul_rn(b, b)), __fmul_rn(__fmul_rn(kf, tr), tr));
+            float r;
+            if (HARRIS) {
+                const float a = __fmul_rn((float)sxx, s2), b = __fmul_rn((float)sxy, s2), c = __fmul_rn((float)syy, s2);
+                const float tr = __fadd_rn(a, c);
+                r = __fsub_rn(__fsub_rn(__fmul_rn(a, c), __fmul_rn(b, b)), __fmul_rn(__fmul_rn(kf, tr), tr));
+            } else {
+                const float a = __fmul_rn(__fmul_rn((float)sxx, s2), 0.5f), b = __fmul_rn((float)sxy, s2), c = __fmul_rn(__fmul_rn((float)syy, s2), 0.5f);
+                const float d = __fsub_rn(a, c);
+                r = __fsub_rn(__fadd_rn(a, c), sqrtf(__fadd_rn(__fmul_rn(d, d), __fmul_rn(b, b))));  // (sqrtf: correctly rounded; __fsqrt_rn is not)
+            }
             resp[(size_t)y * rw + x] = r;
-            o = max(o, f2ord(r));
+            if (!mask || mask[(size_t)y * C.mstride + x]) o = max(o, f2ord(r));
         }
     }
     for (int s = 32; s > 0; s >>= 1) o = max(o, (unsigned)__shfl_xor((int)o, s, 64));  // every lane takes part, inside the ROI or not
     if (lx == 0 && o) atomicMax(&cnt[4 * blockIdx.z], o);
 }
 
-// k_init_candidates per clip: the thresholded 3x3 local maxima, appended to the clip's key segment through its counter (one atomic per wavefront)
+// k_init_candidates per clip: the thresholded 3x3 local maxima the clip's mask keeps, appended to the clip's key segment through its counter (one atomic per wavefront)
 __global__ __launch_bounds__(256) void k_f0b_candidates(const F0Clip* tab, double quality, const float* resp_base, unsigned long long* keys_base, unsigned* cnt)
 {
     const F0Clip& C = tab[blockIdx.z];
@@ -537,7 +552,7 @@ __global__ __launch_bounds__(256) void k_f0b_candidates(const F0Clip* tab, doubl
                         const float u = resp[(size_t)(y + j) * rw + x + i];
                         if (u > thr && u > m) m = u;
                     }
-                hit = v0 == m && v0 != 0.f;
+                hit = v0 == m && v0 != 0.f && (!C.mask || C.mask[(size_t)y * C.mstride + x]);
                 key = ((unsigned long long)__float_as_uint(v0) << 32) | (unsigned)(y * rw + x);
             }
         }
@@ -553,12 +568,91 @@ __global__ __launch_bounds__(256) void k_f0b_candidates(const F0Clip* tab, doubl
     }
 }
 
-// One workgroup per clip: K = min(candidates, max_corners); the keys >= the K-th largest (radix select, 8-bit digits from the top byte down,
-// stopping as soon as the digit's bin holds exactly the keys still wanted) are gathered and -- LDS_SORT -- sorted descending in LDS (bitonic) and
-// written as corners + the ROI origin (k_init_emit), or gathered into the clip's segment of `gsel` for the segmented sort.  Also p[0:4] = q.
+// The K-th largest of the keys below `hi` in keys[0:count) (K < their number; 1024 threads): radix select, 8-bit digits from the top byte down, stopping
+// as soon as the digit's bin holds exactly the keys still wanted.  The K largest keys below hi are exactly those >= the result.
+__device__ __forceinline__ unsigned long long f0b_radix_select(const unsigned long long* keys, unsigned count, unsigned K, unsigned long long hi,
+                                                               unsigned* hist, unsigned* s_bin, unsigned* s_krem, unsigned* s_done)
+{
+    const int tid = threadIdx.x;
+    unsigned long long prefix = 0, himask = 0;
+    unsigned krem = K;  // keys still wanted among those matching prefix on the bits decided so far
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for (unsigned i = tid; i < count; i += 1024) {
+            const unsigned long long k = keys[i];
+            if (k < hi && ((k ^ prefix) & himask) == 0) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid < 64) {  // the bin holding rank krem, counted from the top: lane l owns bins 4l .. 4l+3
+            const unsigned h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
+            const unsigned own = h0 + h1 + h2 + h3;
+            unsigned v = own;  // -> sum over lanes >= tid
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned t = (unsigned)__shfl_down((int)v, off, 64);
+                if (tid + off < 64) v += t;
+            }
+            unsigned above = v - own;
+            if (above < krem && krem <= above + own) {
+                const unsigned hb[4] = {h0, h1, h2, h3};
+                for (int q = 3; q >= 0; q--) {
+                    if (krem <= above + hb[q]) {
+                        *s_bin = 4 * tid + q;
+                        *s_krem = krem - above;
+                        *s_done = hb[q] == krem - above;
+                        break;
+                    }
+                    above += hb[q];
+                }
+            }
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)*s_bin << shift;
+        himask |= 0xffull << shift;
+        krem = *s_krem;
+        if (*s_done) break;  // (uniform: read from LDS after the barrier)
+    }
+    return prefix;
+}
+
+// s[0:K) sorted descending in LDS (bitonic over the next power of two, zero padded: real keys are > 0, their response is not +-0); 1024 threads,
+// called after the barrier that follows the gather of s
+__device__ __forceinline__ void f0b_lds_sort_desc(unsigned long long* s, unsigned K)
+{
+    const unsigned tid = threadIdx.x;
+    unsigned P = 1;
+    while (P < K) P <<= 1;
+    for (unsigned i = K + tid; i < P; i += 1024) s[i] = 0;
+    __syncthreads();
+    for (unsigned k = 2; k <= P; k <<= 1)
+        for (unsigned j = k >> 1; j > 0; j >>= 1) {
+            for (unsigned i = tid; i < P; i += 1024) {
+                const unsigned l = i ^ j;
+                if (l > i) {
+                    const unsigned long long a = s[i], b = s[l];
+                    if ((i & k) == 0 ? a < b : a > b) { s[i] = b; s[l] = a; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// Where the detector writes clip b's corners: out + b * ostride, behind the 4 plate corners q when qhead (vh_frame0_init_batch: p = concatenate((q,
+// corners)), vidExample.py:116), from the start otherwise (vh_good_features2).  The count goes to cnt[4 * clip + 2] and, when n_dev is set, n_dev[clip].
+__device__ __forceinline__ float* f0b_corner_row(const F0Clip& C, float* out, size_t ostride, int qhead, int b)
+{
+    float* p = out + (size_t)b * ostride;
+    if (!qhead) return p;
+    if (threadIdx.x < 8) p[threadIdx.x] = C.q[threadIdx.x];
+    return p + 8;
+}
+
+// One workgroup per clip: K = min(candidates, max_corners); the keys >= the K-th largest (f0b_radix_select) are gathered and -- LDS_SORT -- sorted
+// descending in LDS and written as corners + the ROI origin (k_init_emit), or gathered into the clip's segment of `gsel` for the segmented sort.
 template <bool LDS_SORT>
-__global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int b0, int max_corners, int cap, const unsigned long long* keys_base, unsigned* cnt,
-                                                     float* p_out, unsigned long long* gsel, int* seg_begin, int* seg_end)
+__global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int b0, int max_corners, const unsigned long long* keys_base, unsigned* cnt,
+                                                     float* out, size_t ostride, int qhead, int* n_dev, unsigned long long* gsel, int* seg_begin,
+                                                     int* seg_end)
 {
     const int clip = blockIdx.x, tid = threadIdx.x;
     const F0Clip& C = tab[clip];
@@ -569,47 +663,7 @@ __global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int b0, 
     const unsigned count = min(cnt[4 * clip + 1], npx), K = min(count, (unsigned)max_corners);
     const unsigned long long* keys = keys_base + C.seg;
     unsigned long long T = 0;  // the selection: every key >= T (exactly K keys)
-    if (count > K) {
-        unsigned long long prefix = 0, himask = 0;
-        unsigned krem = K;  // keys still wanted among those matching prefix on the bits decided so far
-        for (int shift = 56; shift >= 0; shift -= 8) {
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            for (unsigned i = tid; i < count; i += 1024) {
-                const unsigned long long k = keys[i];
-                if (((k ^ prefix) & himask) == 0) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid < 64) {  // the bin holding rank krem, counted from the top: lane l owns bins 4l .. 4l+3
-                const unsigned h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-                const unsigned own = h0 + h1 + h2 + h3;
-                unsigned v = own;  // -> sum over lanes >= tid
-                for (int off = 1; off < 64; off <<= 1) {
-                    const unsigned t = (unsigned)__shfl_down((int)v, off, 64);
-                    if (tid + off < 64) v += t;
-                }
-                unsigned above = v - own;
-                if (above < krem && krem <= above + own) {
-                    const unsigned hb[4] = {h0, h1, h2, h3};
-                    for (int q = 3; q >= 0; q--) {
-                        if (krem <= above + hb[q]) {
-                            s_bin = 4 * tid + q;
-                            s_krem = krem - above;
-                            s_done = hb[q] == krem - above;
-                            break;
-                        }
-                        above += hb[q];
-                    }
-                }
-            }
-            __syncthreads();
-            prefix |= (unsigned long long)s_bin << shift;
-            himask |= 0xffull << shift;
-            krem = s_krem;
-            if (s_done) break;  // (uniform: read from LDS after the barrier)
-        }
-        T = prefix;
-    }
+    if (count > K) T = f0b_radix_select(keys, count, K, ~0ull, hist, &s_bin, &s_krem, &s_done);
     if (tid == 0) s_n = 0;
     __syncthreads();
     unsigned long long* dst = LDS_SORT ? s_sel : gsel + (size_t)clip * max_corners;
@@ -620,47 +674,144 @@ __global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int b0, 
             if (slot < K) dst[slot] = k;
         }
     }
-    float* p = p_out + (size_t)(b0 + clip) * cap * 2;
-    if (tid < 8) p[tid] = C.q[tid];  // p = concatenate((q, corners)) (vidExample.py:116)
-    if (tid == 0) cnt[4 * clip + 2] = K;
+    float* p = f0b_corner_row(C, out, ostride, qhead, b0 + clip);
+    if (tid == 0) {
+        cnt[4 * clip + 2] = K;
+        if (n_dev) n_dev[clip] = (int)K;
+    }
     if (!LDS_SORT) {
         if (tid == 0) { seg_begin[clip] = clip * max_corners; seg_end[clip] = clip * max_corners + (int)K; }
         return;
     }
-    unsigned P = 1;
-    while (P < K) P <<= 1;
-    for (unsigned i = K + tid; i < P; i += 1024) s_sel[i] = 0;  // real keys are > 0 (their response is not +-0): padding sorts last
-    __syncthreads();
-    for (unsigned k = 2; k <= P; k <<= 1)
-        for (unsigned j = k >> 1; j > 0; j >>= 1) {
-            for (unsigned i = tid; i < P; i += 1024) {
-                const unsigned l = i ^ j;
-                if (l > i) {
-                    const unsigned long long a = s_sel[i], b = s_sel[l];
-                    if ((i & k) == 0 ? a < b : a > b) { s_sel[i] = b; s_sel[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    f0b_lds_sort_desc(s_sel, K);
     for (unsigned i = tid; i < K; i += 1024) {
         const unsigned idx = (unsigned)(s_sel[i] & 0xffffffffull);
-        p[8 + 2 * i] = __fadd_rn((float)(idx % (unsigned)C.rw), C.offx);
-        p[8 + 2 * i + 1] = __fadd_rn((float)(idx / (unsigned)C.rw), C.offy);
+        p[2 * i] = __fadd_rn((float)(idx % (unsigned)C.rw), C.offx);
+        p[2 * i + 1] = __fadd_rn((float)(idx / (unsigned)C.rw), C.offy);
     }
 }
 
 // corners of the segmented-sort route (max_corners > F0B_SEL_MAX), as k_init_emit
-__global__ __launch_bounds__(256) void k_f0b_emit(const F0Clip* tab, int b0, int max_corners, int cap, const unsigned long long* sorted, const unsigned* cnt,
-                                                  float* p_out)
+__global__ __launch_bounds__(256) void k_f0b_emit(const F0Clip* tab, int b0, int max_corners, const unsigned long long* sorted, const unsigned* cnt,
+                                                  float* out, size_t ostride, int qhead)
 {
     const int clip = blockIdx.y;
     const unsigned i = blockIdx.x * 256 + threadIdx.x;
     if (i >= cnt[4 * clip + 2]) return;
     const F0Clip& C = tab[clip];
     const unsigned idx = (unsigned)(sorted[(size_t)clip * max_corners + i] & 0xffffffffull);
-    float* p = p_out + (size_t)(b0 + clip) * cap * 2 + 8;
+    float* p = out + (size_t)(b0 + clip) * ostride + (qhead ? 8 : 0);
     p[2 * i] = __fadd_rn((float)(idx % (unsigned)C.rw), C.offx);
     p[2 * i + 1] = __fadd_rn((float)(idx / (unsigned)C.rw), C.offy);
+}
+
+// goodFeaturesToTrack's minDistance >= 1: walk the candidates in descending key order and keep one iff no corner kept so far lies at squared distance
+// < min_distance^2 (`lim`: the smallest integer >= min_distance^2, so an integer d^2 < lim exactly when d^2 < min_distance^2), until max_corners are
+// kept.  One 1024-thread workgroup per clip.  The candidates come in windows of up to F0B_WIN keys: the largest keys below the previous window's
+// smallest (f0b_radix_select), sorted in LDS.  Wavefront 0 walks a window in chunks of 64, one candidate per lane:
+//   - against the corners kept so far: an occupancy grid of cell x cell cells (cell = floor(min_distance), so every conflict lies in the 3 x 3 cells
+//     around; a cell holds at most `slots` kept corners: 1 for cell <= 2, else 4, one per quarter, whose diagonal is shorter than min_distance),
+//     packed (y << 16 | x).  It lives in the clip's response plane, which k_f0b_candidates was the last to read: gw x gh x slots <= rw x rh words.
+//   - against the earlier lanes of the chunk: a 64-bit conflict mask per lane from positions broadcast by v_readlane,
+//   - then a wave-uniform serial pass over the surviving lanes in order accepts a lane iff its mask meets no lane accepted before it.
+// The result is exactly the sequential greedy walk.
+__global__ __launch_bounds__(1024) void k_f0b_spread(const F0Clip* tab, int b0, int max_corners, const unsigned long long* keys_base, unsigned* grid_base,
+                                                     unsigned* cnt, float* out, size_t ostride, int qhead, int* n_dev, int cell, int slots, int lim)
+{
+    const int clip = blockIdx.x, tid = threadIdx.x;
+    const F0Clip& C = tab[clip];
+    __shared__ unsigned hist[256];
+    __shared__ unsigned long long s_sel[F0B_WIN];
+    __shared__ unsigned s_bin, s_krem, s_done, s_n, s_acc;
+    const int rw = C.rw, rh = C.rh;
+    const unsigned count = min(cnt[4 * clip + 1], (unsigned)rw * (unsigned)rh);
+    const unsigned long long* keys = keys_base + C.seg;
+    unsigned* grid = grid_base + C.seg;
+    const int gw = (rw + cell - 1) / cell, gh = (rh + cell - 1) / cell;
+    for (unsigned i = tid; i < (unsigned)(gw * gh * slots); i += 1024) grid[i] = F0B_EMPTY;
+    float* p = f0b_corner_row(C, out, ostride, qhead, b0 + clip);
+    if (tid == 0) s_acc = 0;
+    __syncthreads();
+    unsigned long long hi = ~0ull;  // the keys still to walk are those below hi
+    unsigned left = count, kept = 0;
+    while (left > 0) {
+        const unsigned W = min(left, (unsigned)F0B_WIN);
+        const unsigned long long T = left > W ? f0b_radix_select(keys, count, W, hi, hist, &s_bin, &s_krem, &s_done) : 0ull;
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+        for (unsigned i = tid; i < count; i += 1024) {
+            const unsigned long long k = keys[i];
+            if (k >= T && k < hi) {
+                const unsigned slot = atomicAdd(&s_n, 1u);
+                if (slot < W) s_sel[slot] = k;
+            }
+        }
+        __syncthreads();
+        f0b_lds_sort_desc(s_sel, W);
+        if (tid < 64) {
+            const int lane = tid;
+            unsigned na = kept;
+            for (unsigned base = 0; base < W && na < (unsigned)max_corners; base += 64) {
+                const unsigned i = base + lane;
+                const bool valid = i < W;
+                const unsigned idx = valid ? (unsigned)(s_sel[i] & 0xffffffffull) : 0u;
+                const int y = (int)(idx / (unsigned)rw), x = (int)idx - y * rw;
+                const int cx = x / cell, cy = y / cell, cid = cy * gw + cx;
+                const unsigned pos = ((unsigned)y << 16) | (unsigned)x;
+                bool ok = valid;
+                int own = 0;  // corners kept in the lane's own cell
+                if (valid) {
+                    for (int yy = max(cy - 1, 0); yy <= min(cy + 1, gh - 1); yy++)
+                        for (int xx = max(cx - 1, 0); xx <= min(cx + 1, gw - 1); xx++) {
+                            const unsigned* g = grid + (size_t)(yy * gw + xx) * slots;
+                            for (int q = 0; q < slots; q++) {
+                                const unsigned e = g[q];
+                                if (e == F0B_EMPTY) break;
+                                const int dx = x - (int)(e & 0xffffu), dy = y - (int)(e >> 16);
+                                if (dx * dx + dy * dy < lim) ok = false;
+                                own += (xx == cx && yy == cy) ? 1 : 0;
+                            }
+                        }
+                }
+                unsigned long long conf = 0, same = 0;  // earlier lanes of the chunk within the distance / in the same cell
+                for (int j = 0; j < 64; j++) {
+                    const unsigned pj = (unsigned)__builtin_amdgcn_readlane((int)pos, j);
+                    const int cj = __builtin_amdgcn_readlane(cid, j);
+                    const int dx = x - (int)(pj & 0xffffu), dy = y - (int)(pj >> 16);
+                    if (j < lane && dx * dx + dy * dy < lim) conf |= 1ull << j;
+                    if (j < lane && cj == cid) same |= 1ull << j;
+                }
+                const unsigned long long cand = __ballot(ok);
+                unsigned long long acc = 0;
+                unsigned room = (unsigned)max_corners - na;
+                for (unsigned long long m = cand; m && room; m &= m - 1) {  // wave-uniform, in key order
+                    const int j = __ffsll((long long)m) - 1;
+                    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)conf, j);
+                    const unsigned hi32 = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(conf >> 32), j);
+                    if (!((((unsigned long long)hi32 << 32) | lo) & acc)) { acc |= 1ull << j; room--; }
+                }
+                if ((acc >> lane) & 1ull) {
+                    const unsigned r = na + (unsigned)__popcll(acc & ((1ull << lane) - 1ull));
+                    p[2 * r] = __fadd_rn((float)x, C.offx);
+                    p[2 * r + 1] = __fadd_rn((float)y, C.offy);
+                    const int q = own + __popcll(acc & same);
+                    if (q < slots) grid[(size_t)cid * slots + q] = pos;
+                }
+                na += (unsigned)__popcll(acc);
+                __threadfence_block();  // the next chunk's lanes read what this one's wrote
+            }
+            if (lane == 0) s_acc = na;
+        }
+        __syncthreads();
+        kept = s_acc;
+        if (kept >= (unsigned)max_corners) break;
+        hi = T;
+        left -= W;
+    }
+    if (tid == 0) {
+        cnt[4 * clip + 2] = kept;
+        if (n_dev) n_dev[clip] = (int)kept;
+    }
 }
 
 __global__ __launch_bounds__(64) void k_f0b_subpix(const F0Clip* tab, int b0, int cap, int w, int h, size_t st, const unsigned* cnt, int max_corners, int win,
@@ -790,23 +941,86 @@ extern "C" VH_API int vh_init_reserve_batch(vh_ctx* c, int nb, int w, int h, voi
     return 0;
 }
 
-extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
-                                           const double* K_host, const double* plate_host, int border_x, int border_y, int max_corners, double quality,
-                                           int block, double k, int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out,
-                                           uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host, void* stream)
+// The detector's parameters of one call (vh_frame0_init_batch2 / vh_good_features2)
+struct F0Detect {
+    int max_corners, block, use_harris;
+    double quality, k, min_distance;
+};
+
+static int f0b_detect_check(const F0Detect& D, int w, int h, const char* fn)
+{
+    char msg[160];
+    if (!std::isfinite(D.min_distance)) {
+        snprintf(msg, sizeof(msg), "%s: min_distance must be finite", fn);
+        return vh_fail(-1, msg);
+    }
+    if (D.min_distance >= 1 && (w > 32767 || h > 32767)) {  // k_f0b_spread packs (y << 16 | x) and squares int distances
+        snprintf(msg, sizeof(msg), "%s: min_distance >= 1 needs a frame of at most 32767 x 32767", fn);
+        return vh_fail(-1, msg);
+    }
+    return 0;
+}
+
+// the detector stages of one chunk of n clips (descriptors at d_tab, counters zeroed, frames of row stride `stride`); mw x mh: the chunk's largest ROI
+static int f0b_detect(InitBatchScratch& B, const F0Clip* d_tab, int b0, int n, int mw, int mh, size_t stride, const F0Detect& D, float* out,
+                      size_t ostride, int qhead, int* n_dev, hipStream_t s)
+{
+    const int max_corners = D.max_corners;
+    const double scale = 1.0 / (4.0 * D.block * 255.0);
+    const dim3 tiles((mw + F0B_TW - 1) / F0B_TW, (mh + F0B_TH - 1) / F0B_TH, n);
+    if (D.use_harris)
+        hipLaunchKernelGGL(k_f0b_harris<true>, tiles, dim3(256), 0, s, d_tab, stride, D.block, (float)(scale * scale), (float)D.k, B.resp, B.cnt);
+    else
+        hipLaunchKernelGGL(k_f0b_harris<false>, tiles, dim3(256), 0, s, d_tab, stride, D.block, (float)(scale * scale), (float)D.k, B.resp, B.cnt);
+    hipLaunchKernelGGL(k_f0b_candidates, tiles, dim3(256), 0, s, d_tab, D.quality, B.resp, B.keys, B.cnt);
+    if (D.min_distance >= 1) {  // (minDistance < 1, negative included, spaces nothing, as in cv2)
+        const double md = D.min_distance, md2 = md * md;
+        const int cell = md >= 32768.0 ? 32768 : (int)floor(md), slots = cell <= 2 ? 1 : 4;
+        const int lim = md2 >= 2147483647.0 ? 0x7fffffff : (int)ceil(md2);
+        hipLaunchKernelGGL(k_f0b_spread, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, B.keys, reinterpret_cast<unsigned*>(B.resp), B.cnt, out, ostride,
+                           qhead, n_dev, cell, slots, lim);
+    } else if (max_corners <= F0B_SEL_MAX) {
+        hipLaunchKernelGGL(k_f0b_select<true>, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, B.keys, B.cnt, out, ostride, qhead, n_dev, nullptr, nullptr,
+                           nullptr);
+    } else {
+        int* seg_end = B.seg + B.clips_cap;
+        hipLaunchKernelGGL(k_f0b_select<false>, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, B.keys, B.cnt, out, ostride, qhead, n_dev, B.sel, B.seg,
+                           seg_end);
+        size_t bytes = 0;
+        const unsigned size = (unsigned)n * (unsigned)max_corners;
+        VH_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
+        if (bytes > B.sort_bytes) return vh_fail(-1, "vh_frame0_init_batch: segmented sort scratch too small");
+        bytes = B.sort_bytes;
+        VH_CHECK(rocprim::segmented_radix_sort_keys_desc(B.sort_tmp, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
+        hipLaunchKernelGGL(k_f0b_emit, dim3((max_corners + 255) / 256, n), dim3(256), 0, s, d_tab, b0, max_corners, B.sorted, B.cnt, out, ostride, qhead);
+    }
+    return 0;
+}
+
+static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host, const double* K_host,
+                            const double* plate_host, int border_x, int border_y, const F0Detect& D, int subpix_win, int subpix_iter, double subpix_eps,
+                            float* p_out, double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host,
+                            void* stream, const char* fn)
 {
     // every check before anything is queued
-    if (!c || !frames_host || !q_host || !K_host || !plate_host || !p_out || !p3_out || !vp_out || !t_out || !R_out || !res_out || !n_out)
-        return vh_fail(-1, "vh_frame0_init_batch: null argument");
-    if (nb < 1 || w < 3 || h < 3 || stride < w || max_corners < 1 || block < 1 || block > 15 || subpix_win < 1 || subpix_win > SUBPIX_MAXWIN)
-        return vh_fail(-1, "vh_frame0_init_batch: bad arguments");
+    char msg[160];
+    if (!c || !frames_host || !q_host || !K_host || !plate_host || !p_out || !p3_out || !vp_out || !t_out || !R_out || !res_out || !n_out) {
+        snprintf(msg, sizeof(msg), "%s: null argument", fn);
+        return vh_fail(-1, msg);
+    }
+    const int max_corners = D.max_corners;
+    if (nb < 1 || w < 3 || h < 3 || stride < w || max_corners < 1 || D.block < 1 || D.block > 15 || subpix_win < 1 || subpix_win > SUBPIX_MAXWIN) {
+        snprintf(msg, sizeof(msg), "%s: bad arguments", fn);
+        return vh_fail(-1, msg);
+    }
+    int r = f0b_detect_check(D, w, h, fn);
+    if (r) return r;
     std::vector<F0Clip> clips(nb);
     std::vector<int> rois(8 * (size_t)nb);  // boxa, boxb of every clip
     size_t max_px = 0;
     for (int b = 0; b < nb; b++) {
         if (!frames_host[b]) {
-            char msg[96];
-            snprintf(msg, sizeof(msg), "vh_frame0_init_batch: clip %d has a null frame", b);
+            snprintf(msg, sizeof(msg), "%s: clip %d has a null frame", fn, b);
             return vh_fail(-1, msg);
         }
         F0Clip& C = clips[b];
@@ -818,8 +1032,7 @@ extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* con
         C.rw = boxb[1] - boxb[0];
         C.rh = boxb[3] - boxb[2];
         if (C.rw < 3 || C.rh < 3) {
-            char msg[96];
-            snprintf(msg, sizeof(msg), "vh_frame0_init_batch: the plate ROI of clip %d is empty", b);
+            snprintf(msg, sizeof(msg), "%s: the plate ROI of clip %d is empty", fn, b);
             return vh_fail(-1, msg);
         }
         C.im = frames_host[b];
@@ -833,7 +1046,7 @@ extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* con
     VH_BIND(c, stream);
     hipStream_t s = bound_.s;
     InitBatchScratch& B = c->init_batch;
-    int r;
+    // (the spacing stage needs no scratch of its own: its occupancy grid reuses the clip's response plane)
     if (B.explicit_size) {  // chunks of the reserved size; grown only for a ROI larger than the whole scratch
         r = batch_reserve(c, B.clips_cap, max_px, s);
     } else {                // as many clips per chunk as the budget holds
@@ -842,7 +1055,7 @@ extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* con
         r = batch_reserve(c, want, (size_t)want * max_px, s);
     }
     if (r) return r;
-    if (max_corners > F0B_SEL_MAX && (r = batch_sel_reserve(c, max_corners, s))) return r;
+    if (max_corners > F0B_SEL_MAX && D.min_distance < 1 && (r = batch_sel_reserve(c, max_corners, s))) return r;
     if (roi_host) memcpy(roi_host, rois.data(), sizeof(int) * 8 * nb);
     F0Shared sh;
     for (int i = 0; i < 9; i++) sh.K[i] = K_host[i];
@@ -851,7 +1064,6 @@ extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* con
     F0Clip* d_tab = reinterpret_cast<F0Clip*>(B.tab);
     VH_CHECK(vh_store(d_sh, sh, s));
     const int cap = 4 + max_corners;
-    const double scale = 1.0 / (4.0 * block * 255.0);
     const int iters = subpix_iter < 1 ? 1 : (subpix_iter > 100 ? 100 : subpix_iter);
     const double eps = subpix_eps < 0 ? 0 : subpix_eps;
     const float* mask = B.mask + subpix_mask_offset(subpix_win);
@@ -874,22 +1086,8 @@ extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* con
             VH_CHECK(vh_store(reinterpret_cast<F0ClipPiece*>(d_tab + p0), piece, s));
         }
         hipLaunchKernelGGL(k_f0b_setup, dim3((n + 63) / 64), dim3(64), 0, s, d_sh, b0, n, cap, p_out, t_out, R_out, res_out, B.cnt, B.info, B.pose);
-        const dim3 tiles((mw + F0B_TW - 1) / F0B_TW, (mh + F0B_TH - 1) / F0B_TH, n);
-        hipLaunchKernelGGL(k_f0b_harris, tiles, dim3(256), 0, s, d_tab, (size_t)stride, block, (float)(scale * scale), (float)k, B.resp, B.cnt);
-        hipLaunchKernelGGL(k_f0b_candidates, tiles, dim3(256), 0, s, d_tab, quality, B.resp, B.keys, B.cnt);
-        if (max_corners <= F0B_SEL_MAX) {
-            hipLaunchKernelGGL(k_f0b_select<true>, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, cap, B.keys, B.cnt, p_out, nullptr, nullptr, nullptr);
-        } else {
-            int* seg_end = B.seg + B.clips_cap;
-            hipLaunchKernelGGL(k_f0b_select<false>, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, cap, B.keys, B.cnt, p_out, B.sel, B.seg, seg_end);
-            size_t bytes = 0;
-            const unsigned size = (unsigned)n * (unsigned)max_corners;
-            VH_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
-            if (bytes > B.sort_bytes) return vh_fail(-1, "vh_frame0_init_batch: segmented sort scratch too small");
-            bytes = B.sort_bytes;
-            VH_CHECK(rocprim::segmented_radix_sort_keys_desc(B.sort_tmp, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
-            hipLaunchKernelGGL(k_f0b_emit, dim3((max_corners + 255) / 256, n), dim3(256), 0, s, d_tab, b0, max_corners, cap, B.sorted, B.cnt, p_out);
-        }
+        r = f0b_detect(B, d_tab, b0, n, mw, mh, (size_t)stride, D, p_out, (size_t)cap * 2, 1, nullptr, s);
+        if (r) return r;
         hipLaunchKernelGGL(k_f0b_subpix, dim3((max_corners + 63) / 64, n), dim3(64), 0, s, d_tab, b0, cap, w, h, (size_t)stride, B.cnt, max_corners,
                            subpix_win, iters, eps * eps, mask, p_out);
         vh_launch_pose(B.pose, sizeof(PoseJob), n, 1, 4, s);
@@ -897,5 +1095,57 @@ extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* con
         VH_CHECK(hipGetLastError());
         b0 += n;
     }
+    return 0;
+}
+
+extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
+                                           const double* K_host, const double* plate_host, int border_x, int border_y, int max_corners, double quality,
+                                           int block, double k, int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out,
+                                           uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host, void* stream)
+{
+    const F0Detect D = {max_corners, block, 1, quality, k, 0.0};
+    return frame0_batch_run(c, nb, frames_host, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out,
+                            p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch");
+}
+
+extern "C" VH_API int vh_frame0_init_batch2(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
+                                            const double* K_host, const double* plate_host, int border_x, int border_y, int max_corners, double quality,
+                                            int block, double k, int use_harris, double min_distance, int subpix_win, int subpix_iter, double subpix_eps,
+                                            float* p_out, double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out,
+                                            int* roi_host, void* stream)
+{
+    const F0Detect D = {max_corners, block, use_harris ? 1 : 0, quality, k, min_distance};
+    return frame0_batch_run(c, nb, frames_host, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out,
+                            p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch2");
+}
+
+// goodFeaturesToTrack of one image on the batch kernels (one clip: the whole image is its ROI, origin 0)
+extern "C" VH_API int vh_good_features2(vh_ctx* c, const uint8_t* im, int w, int h, int stride, const uint8_t* mask, int mask_stride, int max_corners,
+                                        double quality, double min_distance, int block, int use_harris, double k, float* corners, int* count, void* stream)
+{
+    if (!c || !im || !corners || !count || w < 3 || h < 3 || stride < w || (mask && mask_stride < w) || max_corners < 1 || block < 1 || block > 15)
+        return vh_fail(-1, "vh_good_features2: bad arguments");
+    const F0Detect D = {max_corners, block, use_harris ? 1 : 0, quality, k, min_distance};
+    int r = f0b_detect_check(D, w, h, "vh_good_features2");
+    if (r) return r;
+    VH_BIND(c, stream);
+    hipStream_t s = bound_.s;
+    const size_t px = (size_t)w * h;
+    if ((r = batch_reserve(c, 1, px, s))) return r;
+    if (max_corners > F0B_SEL_MAX && min_distance < 1 && (r = batch_sel_reserve(c, max_corners, s))) return r;
+    InitBatchScratch& B = c->init_batch;
+    F0ClipPiece piece;
+    memset(&piece, 0, sizeof(piece));
+    F0Clip& C = piece.c[0];
+    C.roi = C.im = im;
+    C.rw = w;
+    C.rh = h;
+    C.mask = mask;
+    C.mstride = mask_stride;
+    F0Clip* d_tab = reinterpret_cast<F0Clip*>(B.tab);
+    VH_CHECK(vh_store(reinterpret_cast<F0ClipPiece*>(d_tab), piece, s));
+    VH_CHECK(hipMemsetAsync(B.cnt, 0, sizeof(unsigned) * 4, s));
+    if ((r = f0b_detect(B, d_tab, 0, 1, w, h, (size_t)stride, D, corners, 0, 0, count, s))) return r;
+    VH_CHECK(hipGetLastError());
     return 0;
 }

@@ -267,7 +267,7 @@ std::tuple<Tensor, Tensor, Tensor> ba_solve(const Tensor& K, const Tensor& z, co
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> frame0_init(const Tensor& frames, const Tensor& q, const Tensor& K, const Tensor& plate,
                                                                                          int64_t border_x, int64_t border_y, int64_t max_corners, double quality,
                                                                                          int64_t block, double k, int64_t subpix_win, int64_t subpix_iter,
-                                                                                         double subpix_eps)
+                                                                                         double subpix_eps, bool use_harris, double min_distance)
 {
     TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte && frames.dim() == 3 && frames.stride(2) == 1 && frames.stride(1) >= frames.size(2),
                 "frame0_init(frames): expected CUDA uint8 [B,H,W] frames with unit column stride");
@@ -288,12 +288,46 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> frame
     Tensor p = at::zeros({nb, cap, 2}, opt.dtype(at::kFloat)), p3 = at::empty({nb, cap, 3}, opt.dtype(at::kDouble)), vp = at::empty({nb, cap}, opt.dtype(at::kByte)),
            t = at::empty({nb, 3}, opt.dtype(at::kFloat)), R = at::empty({nb, 3, 3}, opt.dtype(at::kDouble)), res = at::empty({nb}, opt.dtype(at::kDouble)),
            n = at::empty({nb}, opt.dtype(at::kInt)), rois = at::empty({nb, 8}, at::TensorOptions().dtype(at::kInt));
-    vh_check(vh_frame0_init_batch(workspace(frames, w, h, 0, s), (int)nb, ptrs.data(), w, h, (int)frames.stride(1), qh.data_ptr<float>(), Kh, ph.data_ptr<double>(),
-                                  (int)border_x, (int)border_y, (int)max_corners, quality, (int)block, k, (int)subpix_win, (int)subpix_iter, subpix_eps,
-                                  p.data_ptr<float>(), p3.data_ptr<double>(), vp.data_ptr<uint8_t>(), t.data_ptr<float>(), R.data_ptr<double>(),
-                                  res.data_ptr<double>(), n.data_ptr<int>(), rois.data_ptr<int>(), s),
-             "vh_frame0_init_batch");
+    if (use_harris && min_distance == 0.0)  // the reference's detector (vidExample.py:110)
+        vh_check(vh_frame0_init_batch(workspace(frames, w, h, 0, s), (int)nb, ptrs.data(), w, h, (int)frames.stride(1), qh.data_ptr<float>(), Kh, ph.data_ptr<double>(),
+                                      (int)border_x, (int)border_y, (int)max_corners, quality, (int)block, k, (int)subpix_win, (int)subpix_iter, subpix_eps,
+                                      p.data_ptr<float>(), p3.data_ptr<double>(), vp.data_ptr<uint8_t>(), t.data_ptr<float>(), R.data_ptr<double>(),
+                                      res.data_ptr<double>(), n.data_ptr<int>(), rois.data_ptr<int>(), s),
+                 "vh_frame0_init_batch");
+    else
+        vh_check(vh_frame0_init_batch2(workspace(frames, w, h, 0, s), (int)nb, ptrs.data(), w, h, (int)frames.stride(1), qh.data_ptr<float>(), Kh,
+                                       ph.data_ptr<double>(), (int)border_x, (int)border_y, (int)max_corners, quality, (int)block, k, use_harris ? 1 : 0,
+                                       min_distance, (int)subpix_win, (int)subpix_iter, subpix_eps, p.data_ptr<float>(), p3.data_ptr<double>(),
+                                       vp.data_ptr<uint8_t>(), t.data_ptr<float>(), R.data_ptr<double>(), res.data_ptr<double>(), n.data_ptr<int>(),
+                                       rois.data_ptr<int>(), s),
+                 "vh_frame0_init_batch2");
     return {p, p3, vp, t, R, res, n, rois};
+}
+
+// cv2.goodFeaturesToTrack(image, max_corners, quality, min_distance, mask=mask, blockSize=block, useHarrisDetector=use_harris, k) through
+// vh_good_features2: image CUDA uint8 [H,W] (unit column stride), mask None or CUDA uint8 [H,W] -> (corners [max_corners,2] f32, rows beyond count 0;
+// count [1] i32), both on the device
+std::tuple<Tensor, Tensor> good_features(const Tensor& image, int64_t max_corners, double quality, double min_distance, const c10::optional<Tensor>& mask,
+                                         int64_t block, bool use_harris, double k)
+{
+    TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kByte && image.dim() == 2 && image.stride(1) == 1 && image.stride(0) >= image.size(1),
+                "good_features(image): expected a CUDA uint8 [H,W] image with unit column stride");
+    TORCH_CHECK(max_corners >= 1, "good_features: max_corners must be >= 1");
+    const int h = (int)image.size(0), w = (int)image.size(1);
+    Tensor m;
+    if (mask.has_value() && mask->defined()) {
+        TORCH_CHECK(mask->is_cuda() && mask->scalar_type() == at::kByte && mask->dim() == 2 && mask->size(0) == h && mask->size(1) == w,
+                    "good_features(mask): expected a CUDA uint8 mask of the image's shape");
+        m = mask->contiguous();
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(image.device());
+    void* s = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    auto opt = image.options();
+    Tensor corners = at::zeros({max_corners, 2}, opt.dtype(at::kFloat)), count = at::zeros({1}, opt.dtype(at::kInt));
+    vh_check(vh_good_features2(workspace(image, w, h, 0, s), image.data_ptr<uint8_t>(), w, h, (int)image.stride(0), m.defined() ? m.data_ptr<uint8_t>() : nullptr,
+                               w, (int)max_corners, quality, min_distance, (int)block, use_harris ? 1 : 0, k, corners.data_ptr<float>(), count.data_ptr<int>(), s),
+             "vh_good_features2");
+    return {corners, count};
 }
 
 }  // namespace
@@ -311,7 +345,10 @@ TORCH_LIBRARY(velocity_hip, m)
     m.def("msv1_t(Tensor K, Tensor P, Tensor B, Tensor ids, int ii) -> (Tensor, Tensor, Tensor)");
     m.def("ba_solve(Tensor K, Tensor z, Tensor x0, int nt, int nc, int max_iter=10) -> (Tensor, Tensor, Tensor)");
     m.def("frame0_init(Tensor frames, Tensor q, Tensor K, Tensor plate, int border_x=700, int border_y=500, int max_corners=1000, float quality=0.01, "
-          "int block=5, float k=0.04, int subpix_win=5, int subpix_iter=100, float subpix_eps=0.001) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+          "int block=5, float k=0.04, int subpix_win=5, int subpix_iter=100, float subpix_eps=0.001, bool use_harris=True, float min_distance=0.0) -> "
+          "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("good_features(Tensor image, int max_corners, float quality, float min_distance=0.0, Tensor? mask=None, int block=3, bool use_harris=True, "
+          "float k=0.04) -> (Tensor corners, Tensor count)");
 }
 
 // The inputs that decide the device are CUDA tensors: register under the CUDA (= HIP on ROCm) dispatch key.  There is deliberately NO CPU kernel:
@@ -328,4 +365,5 @@ TORCH_LIBRARY_IMPL(velocity_hip, CUDA, m)
     m.impl("msv1_t", &msv1_t);
     m.impl("ba_solve", &ba_solve);
     m.impl("frame0_init", &frame0_init);
+    m.impl("good_features", &good_features);
 }

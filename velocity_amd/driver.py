@@ -2,6 +2,7 @@
 state of `batch` video streams on the GPU and advances all of them one frame per step() through vh_session_step.
 Inputs are torch CUDA uint8 frames (dense, H x W); results (P, B, S, masks, points) are read back on demand."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -247,7 +248,7 @@ def summary_lines(S, n, frame_numbers, seconds):
 
 def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01,
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
-                 out=print, clock=None, name="sequence"):
+                 out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0):
     """The packaged counterpart of vidExample.py:52-178 (minus video decode and plots) on one clip.
 
     frames  sequence of n uint8 [H, W] gray frames (numpy arrays or CUDA tensors): what `cv2.cvtColor(cap.read(), BGR2GRAY)` / `cv2.imread(.., 0)` hands
@@ -260,6 +261,8 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             product; a host loop on the drop-in functions -- what INTEGRATION.md's import switch gives a maintainer -- lives in tools/dropin_loop.py as a
             measurement harness).
     live    True prints every row as its frame finishes (one small read-back per frame, like the reference); False runs the whole clip first.
+    use_harris, min_distance   the frame-0 detector (goodFeaturesToTrack's useHarrisDetector / minDistance; the defaults are the reference's call).  Any
+            other setting runs frame 0 as a one-clip vh_frame0_init_batch2, whose results for the defaults equal vh_frame0_init's.
     out     line sink (default print); clock: time source for the procTime column / fps line (default time.perf_counter).
 
     Prints the reference's header, one 9-column row per frame (vidExample.py:165) and the `Speed = ... +/- ... km/h / Res = ...` summary (:177-178).
@@ -287,7 +290,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     t_begin = clock()
     if route == "session":
         res = _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corners, quality, block, harris_k, subpix, msv_frame, lk_coarse,
-                           lk_fine, emit, clock, live)
+                           lk_fine, emit, clock, live, use_harris, min_distance)
     else:
         raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
     seconds = clock() - t_begin
@@ -304,7 +307,7 @@ def _plate_points(country):
 
 
 def _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corners, quality, block, harris_k, subpix, msv_frame, lk_coarse, lk_fine,
-                 emit, clock, live):
+                 emit, clock, live, use_harris=True, min_distance=0.0):
     torch = L.torch_cuda()
     tic = clock()
     dev = [f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)) for f in frames]
@@ -324,10 +327,14 @@ def _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corn
     rois = (C.c_int * 8)()
     plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
     win, it, eps = subpix
-    L.check(lib.vh_frame0_init(ws.handle, L.dptr(dev[0]), W, H, W, q.ctypes.data_as(L.f32p), ses.K64.ctypes.data_as(L.f64p), plate_w.ctypes.data_as(L.f64p),
-                               int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block), float(harris_k), int(win), int(it),
-                               float(eps), L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(R0), L.dptr(res0), L.dptr(n0), rois, L.stream_ptr()),
-            "vh_frame0_init")
+    if _default_detector(use_harris, min_distance):
+        L.check(lib.vh_frame0_init(ws.handle, L.dptr(dev[0]), W, H, W, q.ctypes.data_as(L.f32p), ses.K64.ctypes.data_as(L.f64p), plate_w.ctypes.data_as(L.f64p),
+                                   int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block), float(harris_k), int(win), int(it),
+                                   float(eps), L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(R0), L.dptr(res0), L.dptr(n0), rois, L.stream_ptr()),
+                "vh_frame0_init")
+    else:  # one clip of the batch entry (bit-identical per clip to vh_frame0_init for the reference's detector)
+        rois = _frame0_batch_call(lib, ws, [dev[0]], [q], W, H, ses.K64, plate_w, roi_border, max_corners, quality, block, harris_k, subpix,
+                                  (p, p3, vp, t0, R0, res0, n0), use_harris, min_distance)
     L.check(lib.vh_session_init_dev(ses.handle, 0, L.dptr(dev[0]), W, L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
                                     float(times[0]), float(frame_numbers[0]), L.stream_ptr()), "vh_session_init_dev")
     ses._keep[0] = dev[0]
@@ -380,25 +387,42 @@ def _frame0_buffers(torch, nb, cap):
             torch.empty(nb, dtype=torch.int32, device="cuda"))
 
 
-def _frame0_batch_call(lib, ws, frames0, qs, W, H, K64, plate_w, roi_border, max_corners, quality, block, harris_k, subpix, bufs):
-    """vh_frame0_init_batch on the current stream: frames0 = dense CUDA [H, W] frames, qs = their plate corners.  -> host list of nb x 8 ROIs (boxa, boxb)."""
+def _default_detector(use_harris, min_distance):
+    """The reference's detector (vidExample.py:110: Harris, minDistance 0), which keeps the entry points it always used."""
+    if not math.isfinite(float(min_distance)):
+        raise ValueError(f"min_distance must be finite, got {min_distance}")
+    return bool(use_harris) and float(min_distance) == 0.0
+
+
+def _frame0_batch_call(lib, ws, frames0, qs, W, H, K64, plate_w, roi_border, max_corners, quality, block, harris_k, subpix, bufs, use_harris=True,
+                       min_distance=0.0):
+    """vh_frame0_init_batch (the reference's detector) or vh_frame0_init_batch2 (any other) on the current stream: frames0 = dense CUDA [H, W] frames,
+    qs = their plate corners.  -> host list of nb x 8 ROIs (boxa, boxb)."""
     nb = len(frames0)
     q = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 2) for x in qs]))
     ptrs = (C.c_void_p * nb)(*[f.data_ptr() for f in frames0])
     rois = (C.c_int * (8 * nb))()
     win, it, eps = subpix
     p, p3, vp, t0, R0, res0, n0 = bufs
-    L.check(lib.vh_frame0_init_batch(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p),
-                                     plate_w.ctypes.data_as(L.f64p), int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block),
-                                     float(harris_k), int(win), int(it), float(eps), L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(R0), L.dptr(res0),
-                                     L.dptr(n0), rois, L.stream_ptr()), "vh_frame0_init_batch")
+    if _default_detector(use_harris, min_distance):
+        L.check(lib.vh_frame0_init_batch(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p),
+                                         plate_w.ctypes.data_as(L.f64p), int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block),
+                                         float(harris_k), int(win), int(it), float(eps), L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(R0),
+                                         L.dptr(res0), L.dptr(n0), rois, L.stream_ptr()), "vh_frame0_init_batch")
+    else:
+        L.check(lib.vh_frame0_init_batch2(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p),
+                                          plate_w.ctypes.data_as(L.f64p), int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block),
+                                          float(harris_k), 1 if use_harris else 0, float(min_distance), int(win), int(it), float(eps), L.dptr(p), L.dptr(p3),
+                                          L.dptr(vp), L.dptr(t0), L.dptr(R0), L.dptr(res0), L.dptr(n0), rois, L.stream_ptr()), "vh_frame0_init_batch2")
     return list(rois)
 
 
-def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001)):
+def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
+                 use_harris=True, min_distance=0.0):
     """Frame 0 of many clips at once (vidExample.py:105-127 for each): `frames` = the clips' first frames (numpy / torch uint8 [H, W] of one size, or one
     [B, H, W] array), `qs` = their plate corners [4, 2].  One vh_frame0_init_batch launch sequence for all of them.  Returns one dict per clip with the keys
-    of the oracle's frame0: p [n, 2] (the 4 plate corners, then the refined Harris corners), p3 [n, 3], vp [n] bool, t [3], R [3, 3], res, boxa, boxb."""
+    of the oracle's frame0: p [n, 2] (the 4 plate corners, then the refined corners), p3 [n, 3], vp [n] bool, t [3], R [3, 3], res, boxa, boxb.
+    use_harris=False: Shi-Tomasi (minimum eigenvalue) corners; min_distance >= 1: corners at least that far apart (vh_frame0_init_batch2)."""
     torch = L.torch_cuda()
     dev = [(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))).cuda().contiguous() for f in frames]
     H, W = dev[0].shape
@@ -407,7 +431,8 @@ def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corner
     ws = L.workspace(W, H)
     bufs = _frame0_buffers(torch, nb, cap)
     plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
-    rois = _frame0_batch_call(ws.lib, ws, dev, qs, W, H, L.host_K(K), plate_w, roi_border, max_corners, quality, block, harris_k, subpix, bufs)
+    rois = _frame0_batch_call(ws.lib, ws, dev, qs, W, H, L.host_K(K), plate_w, roi_border, max_corners, quality, block, harris_k, subpix, bufs, use_harris,
+                              min_distance)
     p, p3, vp, t0, R0, res0, n0 = (x.cpu().numpy() for x in bufs)
     out = []
     for b in range(nb):
@@ -450,13 +475,13 @@ def session_streams(n):
 
 
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
-                  msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0):
+                  msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name]) of ONE frame size and
     length; every clip is a stream of a device-resident TrackerSession, so a frame step is one launch sequence for all the clips of a session
     (vh_session_step_v: each stream has its own clock).  `sessions`: the clips are split into this many sessions, each on its own HIP stream (0 = auto,
     session_groups(len(clips)): their one-workgroup-per-stream stages overlap the others' LK launches); results do not depend on it.  Frame 0 of the clips
     of a session runs as ONE vh_frame0_init_batch call on the device, its outputs feed vh_session_init_dev directly; nothing is read back before the last
-    frame.  Returns one
+    frame.  use_harris / min_distance: the frame-0 detector, as in run_sequence.  Returns one
     result dict per clip (the keys of run_sequence; `lines` = that clip's table and summary, printed through `out` if given), each equal to what
     run_sequence returns for the clip alone."""
     import time as _time
@@ -493,7 +518,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
             # frame 0 of every clip of the session: ONE vh_frame0_init_batch launch sequence into rows [slot] of these tensors
             bufs = _frame0_buffers(torch, len(mem), cap)
             rois = _frame0_batch_call(ses.lib, ses.ws, [dev[b][0] for b in mem], [clips[b]["q"] for b in mem], W, H, ses.K64, plate_w, roi_border, max_corners,
-                                      quality, block, harris_k, subpix, bufs)
+                                      quality, block, harris_k, subpix, bufs, use_harris, min_distance)
             p, p3, vp, t0, R0, res0, n0 = bufs
             for j, b in enumerate(mem):
                 L.check(ses.lib.vh_session_init_dev(ses.handle, j, L.dptr(dev[b][0]), W, L.dptr(p[j]), L.dptr(p3[j]), L.dptr(vp[j]), L.dptr(t0[j]), L.dptr(res0[j]),
@@ -538,12 +563,14 @@ def main(argv=None):
     ap.add_argument("--seq", default="b")
     ap.add_argument("--border", type=int, nargs=2, default=None, help="ROI border around the plate (vidExample.py:108 uses 700 500; the 1024 x 768 stills fixture needs 180 140)")
     ap.add_argument("--msv-frame", type=int, default=5)
+    ap.add_argument("--min-distance", type=float, default=0.0, help="minimum distance between the frame-0 corners (vidExample.py:110 uses 0)")
+    ap.add_argument("--shi-tomasi", action="store_true", help="frame-0 corners by the minimum-eigenvalue detector instead of Harris")
     a = ap.parse_args(argv)
     d = np.load(a.clip)
     fr = d[f"{a.seq}_frames"]
     border = tuple(a.border) if a.border else ((700, 500) if fr.shape[2] >= 1900 else (180, 140))
     run_sequence(fr, d[f"{a.seq}_q"], d[f"{a.seq}_K"], times=d[f"{a.seq}_times"], roi_border=border, msv_frame=a.msv_frame,
-                 name=f"{a.clip}:{a.seq}")
+                 name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance)
 
 
 if __name__ == "__main__":
