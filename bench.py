@@ -5,7 +5,11 @@ One "step" = one tracked frame for every resident stream: KLTmain (3-stage pyram
 warp) + estimateWorldCameraPose(findR=False) + the track-state bookkeeping, all device resident (vh_session_step),
 frames already in HBM when the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--config c2|c3] [--params baseline|ref] [--scene plane|roll]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--config c2|c3] [--params baseline|ref] [--scene plane|roll] [--full]
+
+A plain run does only what the headline figure needs: it sets up the workload, runs the W warm-up and K timed steps, writes the outputs of the last step
+(--dump-outputs) and prints the line.  Everything else -- the post-run parity attestation `verified`, the CPU baselines, the `extras` legs and the BA legs
+(with N > 1 also the idle-latency probe of the exchange) -- runs only with --full, which then does exactly what a default run did before the option.
 
 N > 1: one rank per GPU over RCCL, launched either by the driver through torch.distributed.run or -- when no torchrun
 environment is present -- by bench.py itself (self_launch); every rank tracks its own S streams (weak scaling, no
@@ -13,13 +17,14 @@ data-path collective) and all-gathers the packed track state every 30 frames (co
 velocity_amd.driver.session_groups gives (two from 64 streams), each on its own HIP stream (--groups).
 
 Rank 0 prints ONE compact JSON line on stdout (compact_line: <= 4096 bytes -- the driver keeps a bounded tail of stdout and a longer line does not parse)
-with the contract's fields, `roofline` (dominant kernel, measured live with HIP events inside the library), `cpu_baseline` (the CPU port on all host
-cores; the one-core figure beside it), `verified`, `build_id` and few-number summaries of `ba`, `extras` and `multi_gpu`.  The FULL record goes to the
-detail file (--detail, default bench_detail.json): `roofline_detail`, `ba` (config 5: LM iterations/s of one window and of 8 / 64 batched windows, with its
-own structured-CPU baseline and both roofline fractions), and at N = 1 the `extras` legs in full: the same streams as ONE session (per-kernel table with every
-kernel alone on the chip), the HARD SCENE (noise, gain drift, moving foreground, textureless band: every KLTmain gate fires) and the reference's REAL STILLS,
-each at 256 and 8 streams; one stream alone (latency); the drop-in route (KLT.KLTmain + NLS.estimateWorldCameraPose per call); the reference's own LK
-parameters (utils/KLT.py:106-107); config C3 (4K / 5000 tracks, with its own CPU baseline); the camera-roll scene; shuffled track order.
+with the contract's fields, `roofline` (dominant kernel, measured live with HIP events inside the library during the timed steps), `build_id`, the
+`multi_gpu` summary and, with --full, `cpu_baseline` (the CPU port on all host cores; the one-core figure beside it), `verified` and few-number summaries
+of `ba` and `extras`.  The FULL record goes to the detail file (--detail, default bench_detail.json): `roofline_detail` and, with --full, `ba` (config 5:
+LM iterations/s of one window and of 8 / 64 batched windows, with its own structured-CPU baseline and both roofline fractions), and at N = 1 the `extras`
+legs in full: the same streams as ONE session (per-kernel table with every kernel alone on the chip), the HARD SCENE (noise, gain drift, moving foreground,
+textureless band: every KLTmain gate fires) and the reference's REAL STILLS, each at 256 and 8 streams; one stream alone (latency); the drop-in route
+(KLT.KLTmain + NLS.estimateWorldCameraPose per call); the reference's own LK parameters (utils/KLT.py:106-107); config C3 (4K / 5000 tracks, with its own
+CPU baseline); the camera-roll scene; shuffled track order.
 
 Support code lives in benchlib/ (workloads, roofline objects, BA legs); everything that touches oracle/ -- the CPU
 baselines and the post-run parity attestation `verified` -- is in THIS file (the only bench code allowed to import it).
@@ -185,7 +190,7 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--streams", type=int, default=int(os.environ.get("VH_BENCH_STREAMS", 256)), help="video streams resident per GPU (throughput saturates here: 128 -> 31.4k, 256 -> 33.1k, 512 -> +2 %)")
+    ap.add_argument("--streams", type=int, default=int(os.environ.get("VH_BENCH_STREAMS", 256)), help="video streams resident per GPU (throughput saturates here: 128 -> 31.4k, 256 -> 33.1k, 512 -> +2 %%)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--params", default="baseline", choices=["baseline", "ref"],
                     help="baseline: coarse stages use the config's pyramid depth; ref: exactly utils/KLT.py:106-107 (maxLevel=4)")
@@ -199,28 +204,32 @@ def parse():
     ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="keep timing further blocks of --steps steps until the timed region is at least this long (an external sampler can "
                          "then corroborate the run); 0 (default) = exactly --steps steps")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of each cpu_baseline leg (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: `verified`, the CPU baselines, the extras legs and the BA legs (off by default: a "
+                         "plain run sets up, warms up, times --steps steps, dumps and prints its line); --verify-frames 0, --cpu-seconds 0, --no-extras and "
+                         "--no-ba trim a --full run")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of each cpu_baseline leg (--full; 0 disables)")
     ap.add_argument("--exchange-every", type=int, default=30)
     ap.add_argument("--fine-max-count", type=int, default=0, help="calibration aid (tools/pmc_lk_calib.sh): cap the Newton iterations of the fine LK stage")
     ap.add_argument("--coarse-max-count", type=int, default=0, help="calibration aid (tools/pmc_lk_calib.sh): cap the Newton iterations of the coarse LK stages")
     ap.add_argument("--verify-frames", type=int, default=4,
-                    help="after the timed region, replay this many further frames of two resident streams through the CPU oracle and report "
-                         "`verified` (0 disables)")
-    ap.add_argument("--no-ba", action="store_true", help="skip the BA (config 5) leg")
+                    help="--full: after the timed region, replay this many further frames of two resident streams through the CPU oracle and report "
+                         "`verified` (0 disables); --only-leg: frames of its own `verified`")
+    ap.add_argument("--no-ba", action="store_true", help="--full: skip the BA (config 5) leg")
     ap.add_argument("--only-ba", action="store_true", help="run only the BA (config 5) leg and print its object (profiling aid)")
     ap.add_argument("--only-leg", default="", help="run only one episode leg and print its object: hard_scene[:streams] | real_texture[:streams] (profiling aid)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (single stream, reference parameters, C3, roll scene)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the extra legs (single stream, reference parameters, C3, roll scene)")
     ap.add_argument("--groups", type=int, default=int(os.environ.get("VH_BENCH_GROUPS", 0)),
                     help="split the resident streams into this many sessions, each on its own HIP stream: the one-workgroup-per-stream stages of one session "
                          "(RANSAC, bookkeeping + pose, glue) run while the other's LK launches fill the chip.  0 = auto: 2 sessions for 2-4 and from 64 streams, 4 for "
-                         "8-32 streams (+3 % at 256 streams, +15 % at 8)")
+                         "8-32 streams (+3 %% at 256 streams, +15 %% at 8)")
     ap.add_argument("--host-frames", action="store_true",
                     help="frames start in pinned HOST memory and are uploaded every step (PCIe-inclusive rate; never the headline value)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the track-state exchange even with one rank (smoke test of the N>1 path)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend (nccl = RCCL over xGMI; gloo only for tests)")
     ap.add_argument("--verbose", action="store_true", help="wall-clock stamps of the legs on stderr")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="file that receives the FULL record (roofline_detail, every extras / BA leg); stdout carries only the compact contract line")
+                    help="file that receives the FULL record (roofline_detail; with --full every extras / BA leg); stdout carries only the compact contract line")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last one computed (the packed track state of every resident stream of rank 0) as "
                          "DIR/<name>.npy, float32 / float64, at most 64 MB: two builds run with the same arguments can be compared output for output")
@@ -654,12 +663,13 @@ def main():
         if dumped:
             out["dump_outputs"] = dumped
         cpu_args = (cfg, wl.K, wl.frames[: a.ring], wl.p0, wl.p3, wl.vp, wl.lkc, wl.lkf)
-        if a.verify_frames > 0:
+        if a.full and a.verify_frames > 0:
             out["verified"] = verify(wl, wl.done_steps + 1, nframes=a.verify_frames)
     if use_dist and ex is not None:
         last = ex.wait().clone()  # the LAST exchange of the timed run, read before anything else touches the process group
         desc = ex.describe()  # collective (all_gather_object): every rank calls it
-        desc["exchange_device_us_idle"] = ex.measure_idle_latency()  # collective too; scratch buffers, None under gloo
+        if a.full:  # a probe of its own (collective too; scratch buffers, None under gloo)
+            desc["exchange_device_us_idle"] = ex.measure_idle_latency()
         if rank == 0:
             g = vdist.unpack_state(last[0, 0], N)
             assert g["n_cur"] == st["n_cur"] or g["frame_i"] <= st["frame_i"], "exchanged track state is inconsistent"
@@ -670,19 +680,19 @@ def main():
             out["dist"] = desc
 
     if rank == 0:
-        if a.cpu_seconds > 0 and world == 1:
+        if a.full and a.cpu_seconds > 0 and world == 1:
             stamp("verified; cpu_baseline ...")
             out["cpu_baseline"] = cpu_baseline(*cpu_args, a.cpu_seconds, 0)
             out["cpu_baseline_1core"] = cpu_baseline(*cpu_args, a.cpu_seconds, 1)
             stamp("cpu_baseline done")
             out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
     wl.close()
-    if not a.no_ba and world > 1:  # multi-GPU BA first: its point_sharded / replica figures belong in the head of the line
+    if a.full and not a.no_ba and world > 1:  # multi-GPU BA first: its point_sharded / replica figures belong in the head of the line
         ba = bench_ba_multi_gpu(rank, world, barrier, reduce_max)
         if rank == 0:
             out["ba"] = ba
     if rank == 0:
-        if not a.no_extras and world == 1 and not a.host_frames:
+        if a.full and not a.no_extras and world == 1 and not a.host_frames:
             c2 = a.config == "c2"
             legs = {}
             if wl.G > 1:
@@ -716,7 +726,7 @@ def main():
             legs["other_config"] = extra_leg(a, "c3" if c2 else "c2", a.params, a.scene, 64 if c2 else 128, 24 if c2 else 60, 6, dev,
                                               cpu_seconds=a.cpu_seconds)  # 64 4K streams = 320 000 tracks in flight; CPU port timed on the same frames
             out["extras"] = legs
-        if not a.no_ba and world == 1:
+        if a.full and not a.no_ba and world == 1:
             stamp("extras done; BA ...")
             ba, first = bench_ba()
             if a.cpu_seconds > 0 and first is not None:

@@ -194,3 +194,29 @@ def test_steps_set_the_timed_steps_and_outputs_can_be_dumped(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "/tmp/out"])
     assert b.parse().dump_outputs == "/tmp/out"
     assert b.DUMP_MAX_BYTES == 64 << 20
+
+
+def test_full_is_an_option_off_by_default(monkeypatch):
+    """A plain run times the headline only; the parity replay, CPU baselines, extras and BA legs run with --full (whose trims keep their defaults)."""
+    import sys
+
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = b.parse()
+    assert a.full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = b.parse()
+    assert a.full is True and a.verify_frames == 4 and a.cpu_seconds == 12.0 and not a.no_ba and not a.no_extras
+
+
+def test_help_prints(monkeypatch, capsys):
+    """`bench.py --help` lists --full (help strings are %-formatted: a bare percent sign once made it raise)."""
+    import sys
+
+    import pytest
+
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--help"])
+    with pytest.raises(SystemExit) as e:
+        b.parse()
+    assert e.value.code == 0 and "--full" in capsys.readouterr().out

@@ -142,7 +142,7 @@ def test_track_state_exchange_world2_real_sessions(tmp_path):
 def test_bench_self_launches_two_ranks_on_one_device(tmp_path):
     """`python bench.py --gpus 2` without a torchrun environment starts its own two ranks and reports n_gpus = 2 (here: both on
     cuda:0 over gloo); the whole-job value counts the frames of both ranks."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--oversubscribe", "--streams", "2", "--steps", "6",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--oversubscribe", "--streams", "2", "--steps", "6",
            "--warmup", "2", "--no-ba", "--cpu-seconds", "0", "--exchange-every", "3", "--min-seconds", "0", "--no-extras", "--detail", str(tmp_path / "detail.json")]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -278,7 +278,7 @@ def test_bench_eight_ranks_oversubscribed_prints_n_gpus_8(tmp_path):
     """`python bench.py --gpus 8 --backend gloo`: the driver's 8-GPU launch shape (8 ranks, weak scaling, exchange every 30
     frames); the line says n_gpus 8 and its dist record shows 8 ranks seen in the last gather.  One rank per device (_need_gpus)."""
     _need_gpus(8)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--streams", "1", "--steps", "32",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--backend", "gloo", "--streams", "1", "--steps", "32",
            "--warmup", "2", "--no-ba", "--cpu-seconds", "0", "--exchange-every", "30", "--min-seconds", "0", "--no-extras", "--verify-frames", "2",
            "--detail", str(tmp_path / "detail.json")]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}

@@ -156,7 +156,7 @@ def test_bench_distributed_path_one_rank():
 
 
 def test_bench_prints_exactly_one_compact_contract_line(tmp_path):
-    """`python bench.py` writes ONE stdout line, a JSON object of <= 4096 bytes that carries the contract's fields with `roofline` and
+    """`python bench.py --full` writes ONE stdout line, a JSON object of <= 4096 bytes that carries the contract's fields with `roofline` and
     `cpu_baseline`; nothing on stderr without --verbose apart from warnings; the long objects are in the detail file."""
     import json
     import os
@@ -166,7 +166,7 @@ def test_bench_prints_exactly_one_compact_contract_line(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     detail = tmp_path / "bench_detail.json"
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--no-extras", "--no-ba", "--cpu-seconds", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-extras", "--no-ba", "--cpu-seconds", "1",
                         "--detail", str(detail)], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = r.stdout.splitlines()
@@ -182,6 +182,32 @@ def test_bench_prints_exactly_one_compact_contract_line(tmp_path):
     assert d["verified"]["bit_exact"] is True and d["verified"]["pose_within_1e5"] is True
     full = json.load(open(detail))
     assert full["value"] == d["value"] and "roofline_detail" in full and full["roofline_detail"]["kernels"]
+
+
+def test_plain_bench_run_times_the_headline_only(tmp_path):
+    """Without --full, `python bench.py` sets up, warms up, times exactly --steps steps and prints its line: the roofline of those steps is there, the
+    legs that take runs or replays of their own (`verified`, `cpu_baseline`, `extras`, `ba`) are not, neither on the line nor in the detail file."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    detail = tmp_path / "bench_detail.json"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--streams", "4", "--steps", "6", "--warmup", "2", "--detail", str(detail)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{") and len(lines[0].encode()) <= 4096, r.stdout[:600]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "roofline", "build_id"):
+        assert key in d, key
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["timed_steps"] == 6 and d["value"] > 0 and d["roofline"]["us_per_launch"] > 0
+    full = json.load(open(detail))
+    for key in ("verified", "cpu_baseline", "cpu_baseline_1core", "gpu_over_cpu", "extras", "ba"):
+        assert key not in d and key not in full, key
+    assert full["value"] == d["value"] and full["roofline_detail"]["kernels"]
 
 
 def test_bench_dump_outputs_are_the_last_timed_step_and_repeat_exactly(tmp_path):

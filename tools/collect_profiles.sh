@@ -31,7 +31,7 @@ bash $R/tools/pmc_lk_calib.sh $S > $OUT/lk_calib.log 2>&1
 M=$(ls $R/profiles/r[0-9][0-9]_lk_valu_model.json 2>/dev/null | tail -1)
 if ! [ -s $R/gpurun_out/lk_valu_model.json ]; then echo "collect_profiles: the instruction-cost fit FAILED (see lk_calib.log): the bench line will price with the previous round's model"; tail -5 $OUT/lk_calib.log; fi
 if [ -s $R/gpurun_out/lk_valu_model.json ]; then cp $R/gpurun_out/lk_valu_model.json $OUT/lk_valu_model.json; [ -n "$M" ] && cp $R/gpurun_out/lk_valu_model.json $M; fi
-python $R/bench.py --streams $S --verbose --detail $OUT/bench_default.json > $OUT/bench_default.line 2> $OUT/bench_default.err
+python $R/bench.py --full --streams $S --verbose --detail $OUT/bench_default.json > $OUT/bench_default.line 2> $OUT/bench_default.err
 for s in 1 2 4 8 16 32 64 128 256; do
   python $R/bench.py --streams $s --steps 60 --warmup 10 --cpu-seconds 0 --no-ba --no-extras --min-seconds 1 --detail /dev/null 2>/dev/null | tail -1 > $OUT/sweep_$s.json
 done

@@ -28,7 +28,7 @@ def last_json(path):
     return json.loads(lines[-1])
 
 
-bench = json.load(open(os.path.join(SRC, "bench_default.json")))  # the FULL record (bench.py --detail); the compact stdout line is bench_default.line
+bench = json.load(open(os.path.join(SRC, "bench_default.json")))  # the FULL record (bench.py --full --detail); the compact stdout line is bench_default.line
 S = bench["config"]["streams_per_gpu"]
 json.dump(bench, open(os.path.join(DST, f"{tag}_bench_default.json"), "w"), indent=1)
 line = os.path.join(SRC, "bench_default.line")
@@ -252,7 +252,7 @@ o = [f"# Round {tag[1:]} profiles (1x MI355X)\n",
      f"box, before anything was profiled: **{suite[-1] if suite else 'n/a'}** (`profiles/{tag}_gate.json`; the collection aborts when either check fails).\n",
      f"Regenerate: `gpurun -- bash tools/collect_profiles.sh {S}` then `python tools/summarize_profiles.py {tag}`.\n",
      f"## Default bench: C2 (1080p, 2000 tracks, 3 pyramid levels), {S} streams resident per GPU\n",
-     f"`python bench.py` -> `profiles/{tag}_bench_default.json`: **{bench['value']:.0f} tracked frames/s** ({bench['ms_per_step']} ms per step of {S} "
+     f"`python bench.py --full` -> `profiles/{tag}_bench_default.json`: **{bench['value']:.0f} tracked frames/s** ({bench['ms_per_step']} ms per step of {S} "
      f"frames), CPU port {cb['value']:.1f} frames/s on {cb['cores']} host cores ({bench['gpu_over_cpu']}x), {cb1.get('value', 0):.1f} frames/s on 1 core; "
      f"BA {bench['ba']['iters_per_s']:.0f} LM iterations/s (one window), CPU {bench['ba'].get('cpu_baseline', {}).get('value', 0):.1f} it/s.\n",
      f"`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --streams {S} --steps 40 --warmup 5 --cpu-seconds 0 --no-ba --no-extras --min-seconds 0` -> "
