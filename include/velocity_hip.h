@@ -259,6 +259,48 @@ VH_API int vh_frame0_init_batch2(vh_ctx* ctx, int nb, const uint8_t* const* fram
                                  float* p_out, double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out,
                                  int* roi_host, void* stream);
 
+/* ---- recovery by feature matching (vh_version >= 108) ------------------------------------------------------------ */
+/* Parameters of vh_match_affine; NULL means the defaults in brackets.  levels [5]: images per frame at scale 2^(-l/4), 1..8; query_per_level [500] /
+ * train_per_level [1000]: corner budget per level of im1 / im2, 1..2048; block [5]: blockSize of the detector; border_x, border_y [50, 50]: border of the
+ * query ROI boundingRect(p1, shape, border); a match is good iff ratio_den * d1 < ratio_num * d2 [4, 5]; min_good [10]: fewer good matches report
+ * status 0; quality [0.01]: qualityLevel of the detector. */
+typedef struct {
+    int levels, query_per_level, train_per_level, block, border_x, border_y, ratio_num, ratio_den, min_good;
+    double quality;
+} vh_match_params;
+/* estimateAffine2D_SURF(im1, im2, p1, scale=1), utils/KLT.py:10-33 (stand-in, see DESIGN.md "Recovery by feature matching"): the affine im1 -> im2 from
+ * multi-scale Shi-Tomasi corners (the detector of vh_good_features2 under a mask: 16 px from every edge, im1 also inside boundingRect(p1) scaled to the
+ * level), 256-bit intensity-comparison descriptors on the 5x5 box sum of each level image, brute-force 2-nearest-neighbour Hamming matching with the
+ * ratio test, and vh_ransac_affine on the good pairs.  ONE device-resident launch sequence: no count leaves the device between detection and RANSAC.
+ * Deviation from the reference: it grows the ROI border by 10 px in a host loop until it has 10 good matches, without a bound; this call makes one pass
+ * with the fixed border and reports status 0 instead.
+ *   p1: device float [n x 2], n >= 1.  cap = levels * query_per_level must not exceed the context's max_pts.
+ *   Outputs (device): M double[6] (2x3; zeros without a model), inl uint8[cap] (inlier flag of good pair k; zeros beyond the good pairs),
+ *   pairs float[cap x 4] (may be NULL): good pair k = (query x, y, train x, y) in level-0 coordinates, query order,
+ *   info int[4] = status (1 model found, 0 none), good pairs, inliers, query keypoints.
+ * -1 (nothing queued): null pointers, n < 1, parameters out of the ranges above, a frame whose smallest level is below 3 x 3, cap > max_pts. */
+VH_API int vh_match_affine(vh_ctx* ctx, const uint8_t* im1, const uint8_t* im2, int w, int h, int stride1, int stride2, const float* p1, int n,
+                           const vh_match_params* params_host, double* M, uint8_t* inl, float* pairs, int* info, void* stream);
+/* scratch of vh_match_affine (level images, masks, box sums, keypoints, descriptors; about 20 bytes per frame pixel) and of the detector it drives:
+ * created by the first call, or here -- e.g. before a stream capture, inside which it cannot grow (-6). */
+VH_API int vh_match_reserve(vh_ctx* ctx, int w, int h, const vh_match_params* params_host, void* stream);
+/* device pointers to the intermediate results of the last vh_match_affine call of a context (parity tests).  Image 0 is the query (im1), 1 the train image */
+typedef struct {
+    const float* kp[2][8];    /* detector output of every level, level coordinates (x, y), cnt[image][level] rows          */
+    const int* cnt;           /* [2][8] keypoints per image and level                                                      */
+    const float* pos[2];      /* level-0 positions of all keypoints of an image, level-major, detector order in a level    */
+    const uint8_t* desc[2];   /* 32 bytes per keypoint, same order (np.packbits bit order)                                 */
+    const int* nn;            /* per query keypoint: nearest train index, its distance, second nearest index, its distance */
+    const uint8_t* good;      /* per query keypoint: passed the ratio test                                                 */
+    const int* roi;           /* 4: boundingRect(p1, shape, border) = x0, x1, y0, y1                                       */
+    int levels, lw[8], lh[8]; /* level sizes                                                                               */
+} vh_match_stages;
+VH_API int vh_match_stage_ptrs(vh_ctx* ctx, vh_match_stages* out_host);
+/* the descriptor's sampling pattern as compiled into the kernel: out_host int[256 x 4] = (ax, ay, bx, by) */
+VH_API int vh_match_pairs(int* out_host);
+/* kernels of vh_match.hip queued by this process so far (tests: a default KLTmain queues none) */
+VH_API long long vh_match_launch_count(void);
+
 /* ---- tracker session: the frame loop body of vidExample.py:133-160 on the device, for ctx->batch streams ------- */
 /* device pointers into the state of one stream (read with vh_copy_to_host / torch) */
 typedef struct {

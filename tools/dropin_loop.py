@@ -20,10 +20,11 @@ if ROOT not in sys.path:
 class DropinLoop:
     """Tracker state kept on the HOST between calls of the drop-in functions."""
 
-    def __init__(self, K, n_frames, plate="Chile", roi_border=(700, 500), detector=None, msv_frame=5, lk_coarse=None, lk_fine=None):
+    def __init__(self, K, n_frames, plate="Chile", roi_border=(700, 500), detector=None, msv_frame=5, lk_coarse=None, lk_fine=None, fallback=False):
         self.K, self.n, self.plate, self.roi_border = K, int(n_frames), plate, tuple(roi_border)
         self.detector = {**dict(max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001)), **(detector or {})}
         self.msv_frame, self.lk_coarse, self.lk_fine = msv_frame, lk_coarse, lk_fine
+        self.fallback = bool(fallback)  # KLTmain's recovery by feature matching when the coarse stage fails (default off)
         self.poses = np.zeros((self.n, 14), np.float32)  # the reference's B: world position, relative position, ..., time, frame number
         self.stats = np.zeros((self.n, 9), np.float32)   # the reference's S: one table row per frame
         self.travelled = 0.0
@@ -59,7 +60,8 @@ class DropinLoop:
         from velocity_amd.common import norm
 
         self.poses[i, 12:14] = (stamp, number)
-        self.pts, ok, self.prev_quarter = KLT.KLTmain(im, self.prev, self.prev_quarter, self.pts, lk_coarse=self.lk_coarse, lk_fine=self.lk_fine)
+        self.pts, ok, self.prev_quarter = KLT.KLTmain(im, self.prev, self.prev_quarter, self.pts, lk_coarse=self.lk_coarse, lk_fine=self.lk_fine,
+                                                         fallback=self.fallback)
         self.alive[self.alive] = ok
         self.for_pose &= self.alive
         t, self.R, res, proj = NLS.estimateWorldCameraPose(self.K, self.pts[self.for_pose[self.alive]], self.world[self.for_pose], R=self.R, findR=False)
@@ -93,7 +95,7 @@ class DropinLoop:
 
 
 def run_sequence_dropin(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
-                        harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=print, clock=None, name="sequence"):
+                        harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=print, clock=None, name="sequence", fallback=False):
     """velocity_amd.driver.run_sequence's arguments and result keys, through DropinLoop.  Prints the same header / rows / summary."""
     from velocity_amd.driver import TABLE_HEADER, summary_lines, table_row
 
@@ -116,7 +118,8 @@ def run_sequence_dropin(frames, q, K, fps=None, times=None, frame_numbers=None, 
 
     emit(f"Starting image processing on {name} ...")
     emit(TABLE_HEADER)
-    loop = DropinLoop(K, n, plate, roi_border, dict(max_corners=max_corners, quality=quality, block=block, harris_k=harris_k, subpix=subpix), msv_frame, lk_coarse, lk_fine)
+    loop = DropinLoop(K, n, plate, roi_border, dict(max_corners=max_corners, quality=quality, block=block, harris_k=harris_k, subpix=subpix), msv_frame, lk_coarse, lk_fine,
+                      fallback=fallback)
     t_begin = clock()
     t_loop = None
     for i, im in enumerate(frames):

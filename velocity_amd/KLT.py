@@ -74,6 +74,76 @@ def estimateAffine2D(src, dst):
     return (M.cpu().numpy().reshape(2, 3) if ok > 0 else None), inl[:m].cpu().numpy().reshape(-1, 1)
 
 
+def _match_call(im1, im2, p1, params):
+    """One vh_match_affine call -> (M [6] f64, inl [cap] u8, pairs [cap, 4] f32, info [4] i32) as device tensors; nothing is read back."""
+    torch = L.torch_cuda()
+    a, h, w, sa = L.img_dev(im1)
+    b, h2, w2, sb = L.img_dev(im2)
+    if (h, w) != (h2, w2):
+        raise ValueError("im1 and im2 must have the same shape")
+    p = L.to_dev(p1, torch.float32).reshape(-1, 2)
+    mp = L.match_params(params)
+    cap = mp.levels * mp.query_per_level
+    ws = L.workspace(w, h, cap)
+    M = torch.zeros(6, dtype=torch.float64, device="cuda")
+    inl = torch.zeros(max(cap, 1), dtype=torch.uint8, device="cuda")
+    pairs = torch.zeros((max(cap, 1), 4), dtype=torch.float32, device="cuda")
+    info = torch.zeros(4, dtype=torch.int32, device="cuda")
+    L.check(ws.lib.vh_match_affine(ws.handle, L.dptr(a), L.dptr(b), w, h, sa, sb, L.dptr(p), p.shape[0], C.byref(mp), L.dptr(M), L.dptr(inl), L.dptr(pairs),
+                                   L.dptr(info), L.stream_ptr()), "vh_match_affine")
+    return M, inl, pairs, info
+
+
+def estimateAffine2D_SURF(im1, im2, p1, scale=1.0, **params):
+    """Stand-in for estimateAffine2D_SURF (utils/KLT.py:10-33): the affine im1 -> im2 from feature matches around the tracks p1 ->
+    (T23 f64 [2,3] | None, inliers u8 [good,1]).  SURF itself is non-free: corners on five scales, binary descriptors, Hamming matching with the ratio
+    test and the RANSAC stand-in (vh_match_affine; DESIGN.md "Recovery by feature matching").  One pass with a fixed ROI border: where the reference would
+    grow the border until it has 10 good matches, this returns None.  `params`: _lib.MATCH_DEFAULTS keys.
+
+    scale != 1, as the reference: both images through images.resize_nearest, p1 * scale, the matched pairs divided by scale before RANSAC."""
+    from . import images
+
+    p1 = np.asarray(p1.cpu().numpy() if _is_tensor(p1) else p1, np.float32).reshape(-1, 2)
+    if len(p1) == 0:
+        return None, np.zeros((0, 1), np.uint8)
+    if scale != 1.0:
+        im1, im2 = images.resize_nearest(im1, scale), images.resize_nearest(im2, scale)
+        p1 = p1 * np.float32(scale)
+    M, inl, pairs, info = _match_call(im1, im2, p1, params)
+    st, good = (int(x) for x in info.cpu().numpy()[:2])
+    if scale != 1.0:
+        pr = pairs[:good].cpu().numpy() / np.float32(scale)
+        if good < max(int(L.match_params(params).min_good), 3):
+            return None, np.zeros((good, 1), np.uint8)
+        return estimateAffine2D(pr[:, :2], pr[:, 2:])
+    return (M.cpu().numpy().reshape(2, 3) if st > 0 else None), inl[:good].cpu().numpy().reshape(-1, 1)
+
+
+def match_stages():
+    """Intermediate results of the last estimateAffine2D_SURF / vh_match_affine call on the current stream's workspace (host copies), for the parity
+    tests: dict(kp: [image][level] float32 [n, 2], pos, desc: [image] arrays, nn int32 [nq, 4], good uint8 [nq], roi, dims [(w, h)])."""
+    import torch
+
+    ws = L.workspace()
+    st = L.MatchStages()
+    L.check(ws.lib.vh_match_stage_ptrs(ws.handle, C.byref(st)), "vh_match_stage_ptrs")
+    torch.cuda.synchronize()
+
+    def rd(ptr, count, dtype):
+        out = np.empty(count, dtype)
+        if count:
+            L.check(ws.lib.vh_copy_to_host(out.ctypes.data, ptr, out.nbytes, L.stream_ptr()), "vh_copy_to_host")
+        return out
+
+    nl = st.levels
+    cnt = rd(st.cnt, 16, np.int32).reshape(2, 8)[:, :nl]
+    tot = cnt.sum(1)
+    return dict(cnt=cnt, kp=[[rd(st.kp[i][l], 2 * int(cnt[i, l]), np.float32).reshape(-1, 2) for l in range(nl)] for i in range(2)],
+                pos=[rd(st.pos[i], 2 * int(tot[i]), np.float32).reshape(-1, 2) for i in range(2)],
+                desc=[rd(st.desc[i], 32 * int(tot[i]), np.uint8).reshape(-1, 32) for i in range(2)], nn=rd(st.nn, 4 * int(tot[0]), np.int32).reshape(-1, 4),
+                good=rd(st.good, int(tot[0]), np.uint8), roi=rd(st.roi, 4, np.int32), dims=[(st.lw[l], st.lh[l]) for l in range(nl)])
+
+
 def KLTregional(im0, im, p0, T, lk_param, fbt=1.0, translateFlag=False):
     """ROI warp + forward/backward LK + map back (utils/KLT.py:55-95) -> (p [N,2] f32, v [N] bool)."""
     torch = L.torch_cuda()
@@ -125,11 +195,15 @@ def _img_dev_cached(a, roles):
     return L.img_dev(a) + (key,)
 
 
-def KLTmain(im, im0, im0_small, p0, lk_coarse=None, lk_fine=None, return_all=False):
+def KLTmain(im, im0, im0_small, p0, lk_coarse=None, lk_fine=None, return_all=False, fallback=False, fallback_params=None):
     """Three-stage coarse-to-fine tracker (utils/KLT.py:99-134) -> (p[v] [M,2] f32, v [N] bool, im_small u8 [H/4,W/4]).
 
     lk_coarse / lk_fine default to the reference's constants (KLT.py:106-107); `return_all=True` additionally returns
-    the un-compacted point array and the failure flags.
+    the un-compacted point array and the failure flags (bit 0: coarse-affine failure, bit 1: the recovery ran, bit 2: it found a model).
+
+    `fallback=True` (default off: nothing changes) runs the reference's recovery branch (KLT.py:130-133) when the coarse stage fails: the affine from
+    estimateAffine2D_SURF(im0, im, p0) replaces the mean translation and the fine stage (KLTregional, fbt=0.3) runs with it.  Without a model the result of
+    the blind fine stage stands, as today.  `fallback_params`: estimateAffine2D_SURF's keyword arguments.
 
     Host arrays: `im` is uploaded; `im0` / `im0_small` are taken from the device copies of the previous call when they are the arrays that call uploaded /
     returned (see UPLOAD_CACHE above); positions, status and the failure flag come back in ONE device-to-host copy and `p[v]` is formed on the host.
@@ -180,7 +254,27 @@ def KLTmain(im, im0, im0_small, p0, lk_coarse=None, lk_fine=None, return_all=Fal
         if return_all:
             res += (p_host.copy(), fl)
     if fl & 1:
-        print("KLT coarse-affine failure, running SURF matches full scale.")  # KLT.py:129 (fallback itself is out of scope)
+        print("KLT coarse-affine failure, running SURF matches full scale.")  # KLT.py:129
+        if fallback and n > 0:
+            res = _klt_recover(a, b, p, lc, lf, res, fl, keep, return_all, fallback_params)
+    return res
+
+
+def _klt_recover(im, im0, p0, lc, lf, res, fl, keep, return_all, params):
+    """The recovery branch of KLTmain (KLT.py:130-133), composed on the host from the stateless entry points (the rare branch; KLTmain has just read the
+    flag back anyway): T23 = estimateAffine2D_SURF(im0, im, p0); with a model, p, v = KLTregional(im0, im, p0, T23.T, lk_fine, fbt=0.3)."""
+    fl |= 2
+    T23, _ = estimateAffine2D_SURF(im0, im, p0, **(params or {}))
+    small = res[2]
+    if T23 is not None:
+        fl |= 4
+        fine = dict(winSize=(lf.win, lf.win), maxLevel=lf.max_level, criteria=(TERM_CRITERIA_COUNT | TERM_CRITERIA_EPS, lf.max_count, lf.eps))
+        p_all, vb = KLTregional(im0, im, p0, T23.T, fine, fbt=0.3)  # p0 is a device tensor: tensors come back
+        if not keep:
+            p_all, vb = p_all.cpu().numpy(), vb.cpu().numpy()
+        res = (p_all[vb], vb, small) + ((p_all, fl) if return_all else ())
+    elif return_all:
+        res = res[:4] + (fl,)
     return res
 
 

@@ -34,6 +34,20 @@ class SessionView(C.Structure):
                                       ("n0", C.c_int), ("nhist", C.c_int)]
 
 
+class MatchParams(C.Structure):
+    """vh_match_params (defaults: MATCH_DEFAULTS)."""
+
+    _fields_ = [(k, C.c_int) for k in ("levels", "query_per_level", "train_per_level", "block", "border_x", "border_y", "ratio_num", "ratio_den",
+                                       "min_good")] + [("quality", C.c_double)]
+
+
+class MatchStages(C.Structure):
+    _fields_ = [("kp", (vp * 8) * 2), ("cnt", vp), ("pos", vp * 2), ("desc", vp * 2), ("nn", vp), ("good", vp), ("roi", vp), ("levels", C.c_int),
+                ("lw", C.c_int * 8), ("lh", C.c_int * 8)]
+
+
+MATCH_DEFAULTS = dict(levels=5, query_per_level=500, train_per_level=1000, block=5, border_x=50, border_y=50, ratio_num=4, ratio_den=5, min_good=10,
+                      quality=0.01)
 LK_COARSE = dict(win=15, max_level=4, max_count=10, eps=0.1)  # utils/KLT.py:106
 LK_FINE = dict(win=51, max_level=0, max_count=30, eps=0.001)  # utils/KLT.py:107
 
@@ -107,6 +121,11 @@ _SIGS = {
                                     vp, vp]),
     "vh_frame0_init_batch2": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, f32p, f64p, f64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                         C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, i32p, vp]),
+    "vh_match_affine": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(MatchParams), vp, vp, vp, vp, vp]),
+    "vh_match_reserve": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MatchParams), vp]),
+    "vh_match_stage_ptrs": (C.c_int, [vp, C.POINTER(MatchStages)]),
+    "vh_match_pairs": (C.c_int, [i32p]),
+    "vh_match_launch_count": (C.c_longlong, []),
     "vh_msv1_t": (C.c_int, [vp, f64p, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
 }
 
@@ -293,6 +312,16 @@ def workspace(w=0, h=0, n=0):
 def host_K(K):
     """The intrinsics as the C ABI takes them: 9 contiguous float64 (K.astype(float), utils/NLS.py:22-24,196 -- a float32 K widens exactly)."""
     return np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+
+
+def match_params(d=None):
+    """MATCH_DEFAULTS overridden by `d` -> MatchParams (unknown keys raise)."""
+    d = dict(d or {})
+    bad = set(d) - set(MATCH_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown matching parameters {sorted(bad)} (known: {sorted(MATCH_DEFAULTS)})")
+    m = dict(MATCH_DEFAULTS, **d)
+    return MatchParams(*[int(m[k]) for k, _ in MatchParams._fields_[:-1]], float(m["quality"]))
 
 
 def lk_params(d):

@@ -30,7 +30,7 @@ int vh_fail(int code, const char* msg)
 }
 #define VH_LAUNCH_CHECK() VH_CHECK(hipGetLastError())
 
-extern "C" VH_API int vh_version(void) { return 107; }
+extern "C" VH_API int vh_version(void) { return 108; }
 void vh_lk_force_generic(int on);
 extern "C" VH_API void vh_debug_force_generic_lk(int on) { vh_lk_force_generic(on); }
 void vh_ransac_force_path(int mode);
@@ -121,6 +121,7 @@ extern "C" VH_API void vh_ctx_destroy(vh_ctx* c)
     if (!c) return;
     vh_ba_graph_cache_free(c->ba_graphs);
     vh_init_scratch_free(c);
+    vh_match_scratch_free(c);
     (void)hipFree(c->arena);
     if (c->bound_ev) (void)hipEventDestroy(c->bound_ev);
     for (int k = 0; k < 2 * c->prof_cap; k++) (void)hipEventDestroy(c->prof_ev[k]);

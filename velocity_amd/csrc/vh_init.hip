@@ -931,6 +931,8 @@ void vh_init_batch_scratch_free(vh_ctx* c)
     if (c) batch_release(c->init_batch);
 }
 
+int vh_init_batch_reserve_one(vh_ctx* c, size_t pixels, hipStream_t s) { return batch_reserve(c, 1, pixels, s); }
+
 extern "C" VH_API int vh_init_reserve_batch(vh_ctx* c, int nb, int w, int h, void* stream)
 {
     if (!c || nb < 1 || w < 1 || h < 1) return vh_fail(-1, "vh_init_reserve_batch: bad arguments");

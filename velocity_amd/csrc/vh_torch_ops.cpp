@@ -330,6 +330,31 @@ std::tuple<Tensor, Tensor> good_features(const Tensor& image, int64_t max_corner
     return {corners, count};
 }
 
+// estimateAffine2D_SURF(im1, im2, p1, scale=1) stand-in (utils/KLT.py:10-33) through vh_match_affine -> (M [2,3] f64 (zeros without a model),
+// inliers [levels * query_per_level] u8 (flag of good pair k; zeros beyond the good pairs), info [4] i32 = status, good pairs, inliers, query keypoints)
+std::tuple<Tensor, Tensor, Tensor> match_affine(const Tensor& im1, const Tensor& im2, const Tensor& p1, int64_t levels, int64_t query_per_level,
+                                                int64_t train_per_level, int64_t block, int64_t border_x, int64_t border_y, int64_t ratio_num, int64_t ratio_den,
+                                                int64_t min_good, double quality)
+{
+    check_image(im1, "match_affine(im1)");
+    check_image(im2, "match_affine(im2)");
+    TORCH_CHECK(im1.sizes() == im2.sizes(), "match_affine: im1 and im2 differ in size");
+    TORCH_CHECK(levels >= 1 && levels <= 8 && query_per_level >= 1 && query_per_level <= 2048, "match_affine: levels 1..8, query_per_level 1..2048");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(im1.device());
+    void* s = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    const int h = (int)im1.size(0), w = (int)im1.size(1);
+    Tensor p = as_points(p1, "match_affine(p1)");
+    const int n = (int)p.size(0), cap = (int)(levels * query_per_level);
+    auto opt = im1.options();
+    Tensor M = at::zeros({2, 3}, opt.dtype(at::kDouble)), inl = at::zeros({cap}, opt.dtype(at::kByte)), info = at::zeros({4}, opt.dtype(at::kInt));
+    vh_match_params P{(int)levels, (int)query_per_level, (int)train_per_level, (int)block, (int)border_x, (int)border_y, (int)ratio_num, (int)ratio_den,
+                      (int)min_good, quality};
+    vh_check(vh_match_affine(workspace(im1, w, h, cap, s), im1.data_ptr<uint8_t>(), im2.data_ptr<uint8_t>(), w, h, (int)im1.stride(0), (int)im2.stride(0),
+                             p.data_ptr<float>(), n, &P, M.data_ptr<double>(), inl.data_ptr<uint8_t>(), nullptr, info.data_ptr<int>(), s),
+             "vh_match_affine");
+    return {M, inl, info};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(velocity_hip, m)
@@ -349,6 +374,8 @@ TORCH_LIBRARY(velocity_hip, m)
           "(Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("good_features(Tensor image, int max_corners, float quality, float min_distance=0.0, Tensor? mask=None, int block=3, bool use_harris=True, "
           "float k=0.04) -> (Tensor corners, Tensor count)");
+    m.def("match_affine(Tensor im1, Tensor im2, Tensor p1, int levels=5, int query_per_level=500, int train_per_level=1000, int block=5, int border_x=50, "
+          "int border_y=50, int ratio_num=4, int ratio_den=5, int min_good=10, float quality=0.01) -> (Tensor M, Tensor inliers, Tensor info)");
 }
 
 // The inputs that decide the device are CUDA tensors: register under the CUDA (= HIP on ROCm) dispatch key.  There is deliberately NO CPU kernel:
@@ -366,4 +393,5 @@ TORCH_LIBRARY_IMPL(velocity_hip, CUDA, m)
     m.impl("ba_solve", &ba_solve);
     m.impl("frame0_init", &frame0_init);
     m.impl("good_features", &good_features);
+    m.impl("match_affine", &match_affine);
 }

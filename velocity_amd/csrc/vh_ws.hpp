@@ -115,6 +115,7 @@ struct vh_ctx {
     int lk_win[3];
     InitScratch init;          // created by the first frame-0 call (vh_init.hip)
     InitBatchScratch init_batch;  // created by the first batched frame-0 call or vh_init_reserve_batch (vh_init.hip)
+    void* match;               // scratch of vh_match_affine (MatchScratch, vh_match.hip), created by its first call or vh_match_reserve
 };
 
 // A vh_ctx parks the job descriptors of the calls in flight, so it serves ONE HIP stream at a time.  Enforced on the DEVICE: every entry point ends
@@ -227,6 +228,8 @@ int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_p
 int vh_fail(int code, const char* msg);
 void vh_init_scratch_free(vh_ctx* c);        // both frame-0 scratches (vh_init.hip)
 void vh_init_batch_scratch_free(vh_ctx* c);
+int vh_init_batch_reserve_one(vh_ctx* c, size_t pixels, hipStream_t s);  // the batched detector's scratch for one clip of `pixels` (what vh_good_features2 needs)
+void vh_match_scratch_free(vh_ctx* c);       // vh_match.hip
 
 // optional HIP-event timing of individual launches (vh_profile_begin / vh_profile_end_stages): stage ids
 enum { VH_PROF_LK0 = 0, VH_PROF_LK1 = 1, VH_PROF_LK2 = 2, VH_PROF_WARP = 3, VH_PROF_PYR = 4, VH_PROF_RANSAC = 5, VH_PROF_RESIZE = 6, VH_PROF_SESSION = 7,
