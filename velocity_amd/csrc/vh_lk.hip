@@ -944,11 +944,92 @@ struct LK3 {
     static constexpr int OFF_RED = ((OFF_PJ + (RJ + PAD_ROWS) * PJ_PITCH + 16 + 15) / 16) * 16;
     static constexpr int MAX_TPW = 8;                           // launch slots one workgroup may solve one after the other (k_lk3)
     static constexpr int OFF_RES = OFF_RED + 2 * NW * 4 * 8;   // their result records (8 dwords each), written out after the last one
-    static constexpr int LDS_BYTES = OFF_RES + MAX_TPW * 32;
+    // The lane map: what a thread's place in the workgroup alone decides -- its strip column(s) and first row(s), and with them its addresses in the
+    // two staged regions and the v_perm selectors that pack (and mask) its gradient pairs.  Slots fall into selector classes: SPLIT 0 = [0, KA),
+    // 1 = [KA, K-1), 2 = K-1; otherwise 0 = the slots that always lie inside the window, 1 = the last PAD_ROWS slots of a run (below the window in the
+    // last run(s)).  k_lk3 writes the map to LDS once per workgroup (OFF_TAB), lk3_level reads it back per level: three 16-byte groups per thread,
+    // group-major (group g of thread t at OFF_TAB + 16 * (g * T + t): consecutive lanes read consecutive 16 bytes)
+    struct Lane {
+        int jA, rA, jB, rB;
+        bool on;
+        unsigned s01[3], s23[3];
+    };
+    static constexpr unsigned SEL_NONE = 0x0c0c0c0cu;
+    static constexpr unsigned sel01_of(int cnt) { return cnt >= 2 ? 0x07060302u : (cnt == 1 ? 0x0c0c0302u : SEL_NONE); }
+    static constexpr unsigned sel23_of(int cnt) { return cnt >= 4 ? 0x07060302u : (cnt == 3 ? 0x0c0c0302u : SEL_NONE); }
+    static constexpr int NCLS = SPLIT ? 3 : 2;
+    static constexpr int slot_cls(int k) { return SPLIT ? (k < KA ? 0 : (k < K - 1 ? 1 : 2)) : (k < K - PAD_ROWS ? 0 : 1); }
+    static constexpr Lane lane(int tid)
+    {
+        Lane l{};
+        if (SPLIT) {
+            constexpr int MAIN = RUNS * SPR;  // 52
+            const bool main_lane = tid < MAIN;
+            const int run = tid / SPR;
+            l.jA = main_lane ? tid - run * SPR : tid - MAIN;
+            l.rA = main_lane ? run * K : RUNS * K;
+            const bool tail = !main_lane && tid < MAIN + KA;  // carries one strip of the last column in its last slot
+            l.jB = main_lane ? l.jA : SPR - 1;
+            l.rB = main_lane ? l.rA : (tail ? RUNS * K + (tid - MAIN) - (K - 1) : 0);
+            l.on = true;
+            const int cntA = WIN - 4 * l.jA < 4 ? WIN - 4 * l.jA : 4, cntL = WIN - 4 * (SPR - 1);
+            l.s01[0] = sel01_of(cntA); l.s23[0] = sel23_of(cntA);
+            l.s01[1] = main_lane ? l.s01[0] : SEL_NONE; l.s23[1] = main_lane ? l.s23[0] : SEL_NONE;
+            l.s01[2] = main_lane ? l.s01[0] : (tail ? sel01_of(cntL) : SEL_NONE); l.s23[2] = main_lane ? l.s23[0] : (tail ? sel23_of(cntL) : SEL_NONE);
+        } else {
+            const int run = tid / SPR;
+            l.jA = l.jB = tid - run * SPR;
+            l.rA = l.rB = run * K;
+            l.on = run < RUNS;
+            const int cnt = WIN - 4 * l.jA < 4 ? WIN - 4 * l.jA : 4;
+            // only the last PAD_ROWS strips of a run can hang below the window, and only in runs that start within PAD_ROWS rows of its bottom edge
+            const bool below = l.rA + (K - PAD_ROWS > 0 ? K - PAD_ROWS : 0) >= WIN;
+            l.s01[0] = sel01_of(cnt); l.s23[0] = sel23_of(cnt);
+            l.s01[1] = l.s01[2] = below ? SEL_NONE : l.s01[0]; l.s23[1] = l.s23[2] = below ? SEL_NONE : l.s23[0];
+        }
+        return l;
+    }
+    // one selector per class is enough: every slot of a class that holds a strip lies inside the window, for every thread (asserted in lk3_level)
+    static constexpr bool classes_hold()
+    {
+        for (int t = 0; t < T; t++) {
+            const Lane l = lane(t);
+            if (!l.on) continue;
+            for (int k = 0; k < K; k++) {
+                const int c = slot_cls(k), row = (k < KA ? l.rA : l.rB) + k;
+                if (l.s01[c] != SEL_NONE && (row < 0 || row >= WIN)) return false;
+                if (!SPLIT && l.s01[c] == SEL_NONE && row < WIN) return false;
+            }
+        }
+        return true;
+    }
+    // the lanes of a wavefront whose slots of class c hold a strip (one-wavefront kernels: lane = thread)
+    static constexpr unsigned long long live_mask(int c)
+    {
+        unsigned long long m = 0;
+        for (int t = 0; t < 64; t++) m |= (unsigned long long)(lane(t).on && lane(t).s01[c] != SEL_NONE) << t;
+        return m;
+    }
+    static constexpr unsigned long long on_mask()
+    {
+        unsigned long long m = 0;
+        for (int t = 0; t < 64; t++) m |= (unsigned long long)lane(t).on << t;
+        return m;
+    }
+    static constexpr int OFF_TAB = ((OFF_RES + MAX_TPW * 32 + 15) / 16) * 16;
+    static constexpr int LDS_BYTES = OFF_TAB + 3 * 16 * T;
+    static_assert(NW != 1 || WIN != 51 || LDS_BYTES <= 160 * 1024 / 12, "k_lk3<51, 1, 4>: 12 workgroups per CU must fit in LDS");
 };
 
 typedef const uint2 __attribute__((address_space(1)))* gptr_u32x2;
 typedef int __attribute__((address_space(3)))* lds_i32;
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+typedef u32x4_t __attribute__((address_space(3)))* lds_u32x4;
+
+// A lane predicate that is a FIXED set of lanes, as a 64-bit literal: the mask is a scalar constant (s_mov) where a compare of the thread index is a vector
+// instruction whose result hipcc hoists out of the track loop and, short of scalar registers, parks in a VGPR lane (v_writelane) and fetches again
+// (v_readlane) at every use.  Only where lane = thread index, or the predicate is one of the lane index.
+__device__ __forceinline__ bool lane_in(unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 
 // stage ROWS x PITCH bytes of image `im` starting at pixel (rx, ry) into LDS (region-aligned rows).  Compile-time
 // extents: the loop is fully unrolled and every global load of the batch is issued before the first LDS store, so a
@@ -1074,58 +1155,39 @@ __device__ __forceinline__ void lk3_level(const ImgDesc I, const ImgDesc J, int 
 
     const bool inside_I = ipx >= 1 && ipy >= 1 && ipx + WIN + 1 <= I.w - 1 && ipy + WIN + 1 <= I.h - 1;
     // this lane's strips: slots 0..KA-1 = column jA, window rows rA + k; slots KA..K-1 = column jB, rows rB + k (one segment unless C::SPLIT).
-    // selA / selB / selC: the v_perm selectors that pack (and mask) the gradient pairs of slots [0, KA), [KA, K-1) and K-1
-    int jA, rA, jB, rB;
-    bool lane_on;
-    unsigned selA01, selA23, selB01, selB23, selC01, selC23;
-    const auto sel01_of = [](int cnt) { return cnt >= 2 ? 0x07060302u : (cnt == 1 ? 0x0c0c0302u : 0x0c0c0c0cu); };
-    const auto sel23_of = [](int cnt) { return cnt >= 4 ? 0x07060302u : (cnt == 3 ? 0x0c0c0302u : 0x0c0c0c0cu); };
-    if constexpr (C::SPLIT) {
-        constexpr int MAIN = C::RUNS * C::SPR;  // 52
-        const bool main_lane = tid < MAIN;
-        const int run = tid / C::SPR;
-        jA = main_lane ? tid - run * C::SPR : tid - MAIN;
-        rA = main_lane ? run * C::K : C::RUNS * C::K;
-        const bool tail = !main_lane && tid < MAIN + C::KA;  // carries one strip of the last column in its last slot
-        jB = main_lane ? jA : C::SPR - 1;
-        rB = main_lane ? rA : (tail ? C::RUNS * C::K + (tid - MAIN) - (C::K - 1) : 0);
-        lane_on = true;
-        const int cntA = min(4, WIN - 4 * jA), cntL = WIN - 4 * (C::SPR - 1);
-        selA01 = sel01_of(cntA); selA23 = sel23_of(cntA);
-        selB01 = main_lane ? selA01 : 0x0c0c0c0cu; selB23 = main_lane ? selA23 : 0x0c0c0c0cu;
-        selC01 = main_lane ? selA01 : (tail ? sel01_of(cntL) : 0x0c0c0c0cu); selC23 = main_lane ? selA23 : (tail ? sel23_of(cntL) : 0x0c0c0c0cu);
-    } else {
-        const int run = tid / C::SPR;
-        jA = jB = tid - run * C::SPR;
-        rA = rB = run * C::K;
-        lane_on = run < C::RUNS;
-        const int cnt = min(4, WIN - 4 * jA);
-        selA01 = selB01 = selC01 = sel01_of(cnt);
-        selA23 = selB23 = selC23 = sel23_of(cnt);
-    }
+    // The map depends on the thread alone (LK3::Lane): k_lk3 wrote it to LDS before the first track, and it comes back here with three 16-byte LDS loads
+    // per level, which take no VALU slot and keep ~50 loop-invariant registers out of the track loop.
+    // selA / selB / selC: the v_perm selectors that pack (and mask) the gradient pairs of the slots of class 0 / 1 / 2 (LK3::slot_cls)
+    static_assert(C::classes_hold(), "a selector class mixes slots inside and below the window");
+    const lds_u32x4 tab = (lds_u32x4)(smem + C::OFF_TAB) + tid;  // (an explicit LDS pointer, as the result records of k_lk3)
+    const u32x4_t tg0 = tab[0], tg1 = tab[C::T], tg2 = tab[2 * C::T];
+    const unsigned selA01 = tg1.x, selA23 = tg1.y, selB01 = tg1.z, selB23 = tg1.w, selC01 = tg2.x, selC23 = tg2.y;
+    // (column and row as numbers: the border set-up and the err pass only)
+    const int jA = (int)(tg2.z & 255u), rA = (int)((tg2.z >> 8) & 255u), jB = (int)((tg2.z >> 16) & 255u), rB = (int)(tg2.z >> 24);
+    constexpr unsigned long long ON = C::on_mask(), LIVE[3] = {C::live_mask(0), C::live_mask(1), C::live_mask(C::NCLS - 1)};
+    const bool lane_on = C::LANES == C::T ? true : (C::T == 64 ? lane_in(ON) : tid < C::LANES);
     // (k is a compile-time constant wherever these are used: the strip loops are fully unrolled)
     const auto slot_col = [&](int k) { return k < C::KA ? jA : jB; };
     const auto slot_row = [&](int k) { return (k < C::KA ? rA : rB) + k; };
     const auto slot_sel = [&](int k, unsigned& s01, unsigned& s23) {
-        if (C::SPLIT) {
-            s01 = k < C::KA ? selA01 : (k < C::K - 1 ? selB01 : selC01);
-            s23 = k < C::KA ? selA23 : (k < C::K - 1 ? selB23 : selC23);
-        } else {
-            // only the last PAD_ROWS strips of a run can hang below the window: the selector is a per-level lane constant everywhere else
-            const bool below = k >= C::K - C::PAD_ROWS && rA + k >= WIN;
-            s01 = below ? 0x0c0c0c0cu : selA01;
-            s23 = below ? 0x0c0c0c0cu : selA23;
-        }
+        const int c = C::slot_cls(k);
+        s01 = c == 0 ? selA01 : (c == 1 ? selB01 : selC01);
+        s23 = c == 0 ? selA23 : (c == 1 ? selB23 : selC23);
     };
-    const auto slot_live = [&](int k) { unsigned a, b; slot_sel(k, a, b); return a != 0x0c0c0c0cu; };  // the slot holds a strip of the window
+    const auto slot_live = [&](int k) {  // the slot holds a strip of the window
+        if (C::T == 64) return lane_in(LIVE[C::slot_cls(k)]);
+        unsigned a, b;
+        slot_sel(k, a, b);
+        return a != C::SEL_NONE;
+    };
     constexpr int slot_base = 0, slot_stride = 1;
     constexpr int PIP = C::PI_PITCH >> 2;
     int part[3] = {0, 0, 0};
     if (lane_on && inside_I) {
         // interior: rolling V rows (see strip_setup_linear): patch rows y .. y+3 feed strip y; one new row per strip
         const unsigned wt = pack16(w0.w00, w0.w01), wb = pack16(w0.w10, w0.w11);
-        const unsigned* colA = pI + jA + rA * PIP;
-        const unsigned* colB = pI + jB + rB * PIP;
+        const unsigned* colA = reinterpret_cast<const unsigned*>(smem + tg0.x);  // pI + jA + rA * PIP
+        const unsigned* colB = reinterpret_cast<const unsigned*>(smem + tg0.y);  // pI + jB + rB * PIP
         const auto patch_row = [&](int k, int dr) { return (k < C::KA ? colA : colB) + (k + dr) * PIP; };  // patch row slot_row(k) + dr, this lane's 8 bytes
         unsigned prB[6];
         int H0[4], H1[4], G0[4], G1[4], Vm[4];  // of V rows y, y+1 (Vm = the middle row's sample columns, for the template value)
@@ -1210,11 +1272,11 @@ __device__ __forceinline__ void lk3_level(const ImgDesc I, const ImgDesc J, int 
     D = __fdiv_rn(1.f, D);
     const int ncI[2] = {-cI[0], -cI[1]};
     constexpr int PJP = C::PJ_PITCH >> 2;
-    unsigned lcA = (unsigned)(C::OFF_PJ + 4 * (rA * PJP + jA)), lcB = (unsigned)(C::OFF_PJ + 4 * (rB * PJP + jB));  // (((inx - rjx) + 4 j) >> 2 = ((inx - rjx) >> 2) + j)
-    // opaque to the compiler, once per level.  NOT `asm volatile`: a volatile asm counts as a possible store to any memory, and every load of the
-    // pyramid descriptors behind it turns from a scalar load into a per-lane global load (round 5: +17 vector loads, -17 scalar loads and +48 VALU
+    // C::OFF_PJ + 4 * (rA * PJP + jA) and the same of (rB, jB): (((inx - rjx) + 4 j) >> 2 = ((inx - rjx) >> 2) + j).  Out of the table they are opaque to the
+    // compiler, as the iterations need them (below).  An `asm volatile` must never do that job: it counts as a possible store to any memory, and every load
+    // of the pyramid descriptors behind it turns from a scalar load into a per-lane global load (round 5: +17 vector loads, -17 scalar loads and +48 VALU
     // instructions per track, +25 % wait cycles, +4-5 % kernel time -- what made every earlier form of this change slower than the code it shortened)
-    asm("" : "+v"(lcA), "+v"(lcB));
+    const unsigned lcA = tg0.z, lcB = tg0.w;
 
     // packed byte pairs of window row y (strip column j) of the staged search region at window origin (inx, iny)
     // The strip starts at byte `off` of the staged row: its 5 bytes lie inside the two dwords at off >> 2, and the byte pair (c, c+1) is ONE
@@ -1372,6 +1434,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 1
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int phase = 0, tot_iter = 0, tot_setup = 0;
     unsigned ndone = 0;
+    {   // this thread's lane map (LK3::Lane), once per workgroup and ahead of the track loop: a store inside the loop body would turn the descriptors' scalar
+        // loads into vector loads (see the end of the loop)
+        using C = LK3<WIN, NW, M>;
+        constexpr int PIP = C::PI_PITCH >> 2, PJP = C::PJ_PITCH >> 2;
+        const typename C::Lane l = C::lane((int)threadIdx.x);
+        const lds_u32x4 tab = (lds_u32x4)(smem + C::OFF_TAB) + threadIdx.x;
+        tab[0] = u32x4_t{(unsigned)(C::OFF_PI + 4 * (l.jA + l.rA * PIP)), (unsigned)(C::OFF_PI + 4 * (l.jB + l.rB * PIP)),
+                         (unsigned)(C::OFF_PJ + 4 * (l.rA * PJP + l.jA)), (unsigned)(C::OFF_PJ + 4 * (l.rB * PJP + l.jB))};
+        tab[C::T] = u32x4_t{l.s01[0], l.s23[0], l.s01[1], l.s23[1]};
+        tab[2 * C::T] = u32x4_t{l.s01[2], l.s23[2], (unsigned)(l.jA | l.rA << 8 | l.jB << 16 | l.rB << 24), 0u};
+        __syncthreads();
+    }
     // A workgroup solves `tpw` consecutive launch slots one after the other (tracks that are neighbours in the launch order): fewer, longer-lived
     // workgroups.  Everything but the slot counter is re-derived per track (scalar loads of the job descriptor): values kept live across the loop cost
     // scalar registers the track code spills
@@ -1418,7 +1492,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 1
         }
         // the track's results wait in LDS: a global store inside this loop would make every descriptor load of the NEXT track a possibly-clobbered load,
         // i.e. a vector load instead of a scalar one (the same effect as the volatile asm of DESIGN.md section 9)
-        if (tid == 0) {
+        if (NW == 1 ? lane_in(1ull) : tid == 0) {
             // (an explicit LDS pointer: through a generic one hipcc counts these stores as possible writes to the job descriptors too)
             lds_i32 rec = (lds_i32)(smem + LK3<WIN, NW, M>::OFF_RES) + 8 * ti;
             rec[0] = pt; rec[1] = __float_as_int(fx); rec[2] = __float_as_int(fy); rec[3] = st != 0;
