@@ -418,6 +418,48 @@ def test_klt_main_in_spatial_launch_order_is_bit_exact(seq, spatial_launch_order
             assert np.array_equal(G["p_coarse"], S["p_coarse"], equal_nan=True) and np.array_equal(G["v_coarse"], S["v_coarse"])
 
 
+def test_every_lk_route_maps_back_and_records_through_the_shared_epilogue():
+    """Every LK kernel ends in the same map-back / store code (lk_store_track): under every forced route the translate and the affine map-back of
+    KLTregional and the praw_out record that KLTmain's later stages read must equal the oracle bit for bit -- on a small scene whose border points
+    give each case live AND dead tracks (asserted on the oracle alone, before any device call)."""
+    from velocity_amd import KLT
+    from velocity_amd import _lib as L
+
+    W, H = 320, 240
+    m = synth.AffineMotion(W, H, tx=3.5, ty=-1.25)
+    f0 = synth.render_frame(W, H, m, 0).numpy()
+    f1 = synth.render_frame(W, H, m, 1).numpy()
+    rng = np.random.default_rng(11)
+    pts = np.concatenate([synth.grid_tracks(96, W, H), rng.uniform(-12, 14, (12, 2)),
+                          rng.uniform([W - 14, H - 14], [W + 12, H + 12], (12, 2))]).astype(np.float32)
+    T_tr = np.array([[1, 0], [0, 1], [3.6, -1.3]])
+    T_af = m.matrix(1).T
+    regional = {"translate coarse": (T_tr, CV_COARSE, KO.LK_COARSE, 1.0, True),
+                "affine fine": (T_af, CV_FINE, KO.LK_FINE, 0.3, False),
+                "affine coarse": (T_af, CV_COARSE, KO.LK_COARSE, 1.0, False)}
+    want = {k: KO.klt_regional(f0, f1, pts, T, ko_lk, fbt=fbt, translate=tr)[:2] for k, (T, _, ko_lk, fbt, tr) in regional.items()}
+    lkc = dict(max_level=4)
+    ep, ev, _, S = KO.klt_main(f1, f0, None, pts, lk_coarse=lkc, stages=True)
+    assert S["flags"] == 0
+    for k, v in list((k, v) for k, (_, v) in want.items()) + [("klt_main", ev)]:
+        assert v.sum() >= 10 and (~v).sum() >= 10, f"{k}: {int(v.sum())} live / {int((~v).sum())} dead tracks"
+
+    lib = L.load()
+    for route in range(9):
+        lib.vh_debug_force_generic_lk(route)
+        try:
+            for k, (T, cv_lk, _, fbt, tr) in regional.items():
+                p, v = KLT.KLTregional(f0, f1, pts, T, cv_lk, fbt=fbt, translateFlag=tr)
+                assert np.array_equal(v, want[k][1]) and np.array_equal(p, want[k][0]), f"route {route}, {k}"
+            for order in (-1, 1):
+                lib.vh_debug_klt_order(order)
+                p, v, _, p_all, flags = KLT.KLTmain(f1, f0, None, pts, lk_coarse=lkc, return_all=True)
+                assert flags == 0 and np.array_equal(v, ev) and np.array_equal(p_all, S["p_all"]) and np.array_equal(p, ep), f"route {route}, order {order}"
+        finally:
+            lib.vh_debug_klt_order(-1)
+            lib.vh_debug_force_generic_lk(0)
+
+
 @pytest.mark.parametrize("coarse_levels", [4, 2])
 def test_klt_main_on_the_scene_that_fires_every_status_gate(coarse_levels):
     """synth.gate_scene: independent foreground motion, a textureless band, a saturated patch, tracks across the frame border.  Unlike the plain scenes

@@ -4,48 +4,21 @@
 // the result, forward-backward gate, and the map-back of KLTregional (KLT.py:86-89) / the 1/4-scale stage (KLT.py:115).
 // Arithmetic follows SURVEY Appendix A: Scharr derivatives (never materialised), 14-bit fixed-point bilinear weights,
 // int16 template / gradient windows, exact integer window sums converted once to float32, so every implementation in this
-// file returns the same bits.  Four implementations, routed by vh_launch_lk (window size and number of tracks in flight):
+// file returns the same bits.  Five implementations, routed by vh_launch_lk (window size and number of tracks in flight):
 //   k_lk            per-sample reference kernel, one wavefront per track (any window; fallback for windows > 63 px)
 //   k_lk_strip<W>   strips of 4 samples per lane on packed 16-bit dot products, one wavefront per track, loads from L1/L2
 //   k_lk3<W,NW,M>   LDS-staged patch + search region, NW wavefronts per track, vertical strip runs (the 51x51 fine stage)
 //   k_lk_q<W>       4 tracks per wavefront, one 16-lane DPP row per track, template in registers (the 15x15 coarse stages)
+//   k_lk_o<W>       8 tracks per wavefront, half a DPP row per track, two window rows per lane (the 15x15 coarse stages at full load)
+// An implementation is its window sampling and its window-sum reduction: a level functor (LK*Level below).  What a track computes from the
+// reduced sums (level start, 2x2 system and its gate, Newton update and stop rules, final in-level check), the loop over the levels, the
+// forward-backward gate, and a kernel's prologue (job row, launch slot -> point, start point) and epilogue (map-back, output stores, statistics)
+// exist once, in vh_lk_shared.hpp.
 #include <atomic>
 
 #include "vh_kernels.hpp"
 #include "vh_valu.hpp"
-
-#define W_BITS 14
-#define LK_FLT_SCALE (1.f / (1 << 20))
-
-// (float)v for |v| < 2^53 with ONE rounding: hi * 2^32 + lo is exact in float64, the final conversion rounds once --
-// identical to the int64 -> float32 conversion, in 5 instructions instead of the compiler's ~15-instruction sequence
-// The per-track inputs of a launch (count, launch order, start points) hang off pointers that were themselves loaded from the job descriptor: read through a
-// GLOBAL pointer (where the address is workgroup uniform they then come through the scalar cache), not through the generic one hipcc assumes -- a
-// workgroup otherwise starts with a chain of three dependent flat loads before its first image row is requested
-typedef const int __attribute__((address_space(1)))* gptr_i32;
-typedef const float __attribute__((address_space(1)))* gptr_f32;
-#define LK_N_OF(job) ((job).n_ptr ? *(gptr_i32)(job).n_ptr : (job).n)
-
-__device__ __forceinline__ float i64_to_f32(long long v)
-{
-    const double d = __dadd_rn(__dmul_rn((double)(int)(v >> 32), 4294967296.0), (double)(unsigned)(v & 0xffffffffll));
-    return (float)d;
-}
-
-struct Win {
-    int w00, w01, w10, w11;
-};
-
-__device__ __forceinline__ Win bilinear_weights(float a, float b)
-{
-    Win w;
-    const float ia = __fsub_rn(1.f, a), ib = __fsub_rn(1.f, b);
-    w.w00 = vh_round(__fmul_rn(__fmul_rn(ia, ib), (float)(1 << W_BITS)));
-    w.w01 = vh_round(__fmul_rn(__fmul_rn(a, ib), (float)(1 << W_BITS)));
-    w.w10 = vh_round(__fmul_rn(__fmul_rn(ia, b), (float)(1 << W_BITS)));
-    w.w11 = (1 << W_BITS) - w.w00 - w.w01 - w.w10;
-    return w;
-}
+#include "vh_lk_shared.hpp"
 
 // REFLECT_101 sample (image border of the pyramid levels)
 __device__ __forceinline__ int pix_r(const ImgDesc& im, int x, int y)
@@ -110,25 +83,24 @@ __device__ __forceinline__ int search_sample(const ImgDesc& im, int gx, int gy, 
 }
 
 // One point on one level.  All control flow is wave-uniform.
-__device__ void lk_level(const ImgDesc I, const ImgDesc J, int win, int level, int top_level, int max_count, double eps2,
-                         float p0x, float p0y, float& nxo, float& nyo, int& status, float& err, short* ldsI, int* ldsD, int lane,
-                         int& n_iter, int& n_setup, bool want_err)
+struct LKLevel {  // the level functor of k_lk (see lk_track)
+    int win, max_count;
+    double eps2;
+    short* ldsI;
+    int* ldsD;
+    int lane, n_iter, n_setup;
+    __device__ void operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo, float& nyo, int& status,
+                               float& err, bool want_err);
+};
+__device__ void LKLevel::operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo, float& nyo,
+                                    int& status, float& err, bool want_err)
 {
-    const float half = (float)(win - 1) * 0.5f;
-    const float lscale = __uint_as_float((unsigned)(127 - level) << 23);  // 2^-level exactly = (float)(1. / (1 << level)), without the f64 division
-    float px = __fmul_rn(p0x, lscale), py = __fmul_rn(p0y, lscale);
-    float nx, ny;
-    if (level == top_level) { nx = px; ny = py; }
-    else { nx = __fmul_rn(nxo, 2.f); ny = __fmul_rn(nyo, 2.f); }
-    nxo = nx; nyo = ny;
-
-    px = __fsub_rn(px, half); py = __fsub_rn(py, half);
-    const int ipx = vh_floor(px), ipy = vh_floor(py);
-    if (ipx < -win || ipx >= I.w || ipy < -win || ipy >= I.h) {
-        if (level == 0) { status = 0; err = 0.f; }
-        return;
-    }
-    Win w = bilinear_weights(__fsub_rn(px, (float)ipx), __fsub_rn(py, (float)ipy));
+    LKStart s;
+    if (!lk_level_start(p0x, p0y, level, top_level, win, I, nxo, nyo, status, err, s)) return;
+    const float half = s.half;
+    const int ipx = s.ipx, ipy = s.ipy;
+    float nx = s.nx, ny = s.ny;
+    Win w = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
     const int npx = win * win;
     const int xinc = 64 % win, yinc = 64 / win;
     const int x_first = lane % win, y_first = lane / win;
@@ -154,22 +126,16 @@ __device__ void lk_level(const ImgDesc I, const ImgDesc J, int win, int level, i
     sA11 = vh_wave_sum_i64(sA11);
     sA12 = vh_wave_sum_i64(sA12);
     sA22 = vh_wave_sum_i64(sA22);
-    const float A11 = __fmul_rn(i64_to_f32(sA11), LK_FLT_SCALE), A12 = __fmul_rn(i64_to_f32(sA12), LK_FLT_SCALE), A22 = __fmul_rn(i64_to_f32(sA22), LK_FLT_SCALE);
-    float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-    const float dA = __fsub_rn(A11, A22);
-    const float disc = __fadd_rn(__fmul_rn(dA, dA), __fmul_rn(__fmul_rn(4.f, A12), A12));
-    const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), vh_sqrtf(disc)), (float)(2 * win * win));
-    if (minEig < 1e-4f || D < 1.1920929e-07f) {
+    LKSys S;
+    if (!lk_system(sA11, sA12, sA22, win, S)) {
         if (level == 0) status = 0;
         return;
     }
-    D = __fdiv_rn(1.f, D);
 
-    nx = __fsub_rn(nx, half); ny = __fsub_rn(ny, half);
     float pdx = 0.f, pdy = 0.f;
     for (int j = 0; j < max_count; j++) {
         const int inx = vh_floor(nx), iny = vh_floor(ny);
-        if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) {
+        if (lk_outside(inx, iny, win, J)) {
             if (level == 0) status = 0;
             break;
         }
@@ -189,24 +155,13 @@ __device__ void lk_level(const ImgDesc I, const ImgDesc J, int win, int level, i
         }
         sb1 = vh_wave_sum_i64(sb1);
         sb2 = vh_wave_sum_i64(sb2);
-        const float b1 = __fmul_rn(i64_to_f32(sb1), LK_FLT_SCALE), b2 = __fmul_rn(i64_to_f32(sb2), LK_FLT_SCALE);
-        const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, b2), __fmul_rn(A22, b1)), D);
-        const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, b1), __fmul_rn(A11, b2)), D);
-        nx = __fadd_rn(nx, dx); ny = __fadd_rn(ny, dy);
-        nxo = __fadd_rn(nx, half); nyo = __fadd_rn(ny, half);
-        if (__dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy)) <= eps2) break;
-        if (j > 0 && fabsf(__fadd_rn(dx, pdx)) < 0.01f && fabsf(__fadd_rn(dy, pdy)) < 0.01f) {
-            nxo = __fsub_rn(nxo, __fmul_rn(dx, 0.5f));
-            nyo = __fsub_rn(nyo, __fmul_rn(dy, 0.5f));
-            break;
-        }
-        pdx = dx; pdy = dy;
+        if (lk_step(S, sb1, sb2, half, j, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
     }
 
     if (status && level == 0) {
-        const float fx = __fsub_rn(nxo, half), fy = __fsub_rn(nyo, half);
-        const int inx = vh_floor(fx), iny = vh_floor(fy);
-        if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) { status = 0; return; }
+        float fx, fy;
+        int inx, iny;
+        if (!lk_final_origin(nxo, nyo, half, win, J, fx, fy, inx, iny)) { status = 0; return; }
         if (!want_err) return;  // err is discarded by the caller (KLT.py:83 `pa, v, _`): only the bounds rule matters
         w = bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny));
         const bool interior = inx >= 0 && iny >= 0 && inx + win <= J.w - 1 && iny + win <= J.h - 1;
@@ -220,79 +175,25 @@ __device__ void lk_level(const ImgDesc I, const ImgDesc J, int win, int level, i
             if (x >= win) { x -= win; y++; }
         }
         se = vh_wave_sum_i64(se);
-        err = __fmul_rn((float)se, __fdiv_rn(1.f, (float)(32 * win * win)));
+        err = lk_err_of((float)se, win);
     }
-}
-
-__device__ void lk_track(const PyrDesc& PI, const PyrDesc& PJ, int win, int max_count, double eps2, float px, float py, float& ox,
-                         float& oy, int& status, float& err, short* ldsI, int* ldsD, int lane, int& n_iter, int& n_setup, bool want_err)
-{
-    const int nl = min(PI.nlevels, PJ.nlevels);
-    status = 1;
-    err = 0.f;
-    ox = 0.f; oy = 0.f;
-    for (int level = nl - 1; level >= 0; level--)
-        lk_level(PI.lv[level], PJ.lv[level], win, level, nl - 1, max_count, eps2, px, py, ox, oy, status, err, ldsI, ldsD, lane, n_iter, n_setup, want_err);
 }
 
 // grid = (max points, batch), block = one wavefront
 __global__ __launch_bounds__(64) void k_lk(const void* job_tab, size_t tab_stride)
 {
-    const LKJob& job = *reinterpret_cast<const LKJob*>(reinterpret_cast<const char*>(job_tab) + (size_t)blockIdx.y * tab_stride);
-    const int n = LK_N_OF(job);
-    if ((int)blockIdx.x >= n) return;
-    const int pt = job.order ? ((gptr_i32)job.order)[blockIdx.x] : (int)blockIdx.x;  // launch slot -> point (LKJob::order)
-    const int lane = threadIdx.x;
+    const LKJob& job = lk_job_row(job_tab, tab_stride, blockIdx.y);
+    int pt;
+    float px, py;
+    if (!lk_slot_start(job, (int)blockIdx.x, pt, px, py)) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int kmax = (job.win * job.win + 63) / 64;
-    int* ldsD = reinterpret_cast<int*>(smem);
-    short* ldsI = reinterpret_cast<short*>(smem + (size_t)kmax * 64 * 4);
-
-    const float qx = ((gptr_f32)job.p_in)[2 * pt], qy = ((gptr_f32)job.p_in)[2 * pt + 1];
-    const float px = __fsub_rn(__fmul_rn(qx, job.in_scale), job.in_off[0]);
-    const float py = __fsub_rn(__fmul_rn(qy, job.in_scale), job.in_off[1]);
-
-    float fx, fy, err;
-    int st, n_iter = 0, n_setup = 0;
-    lk_track(job.I, job.J, job.win, job.max_count, job.eps2, px, py, fx, fy, st, err, ldsI, ldsD, lane, n_iter, n_setup, job.err_out != nullptr);
-    float fbe = 0.f;
-    if (job.fbt >= 0.f) {
-        float bx = 0.f, by = 0.f, e2;
-        int st2 = 0;
-        // forward status 0: `v = v & v2 & (fbe < fbt)` (KLT.py:50) is 0 whatever the backward pass finds, and the point returned is the forward one, so
-        // the backward pass is skipped unless the caller asked for fbe itself (vh_pyr_lk); in the 4- / 8-tracks-per-wavefront kernels the dead tracks'
-        // lanes sit out the pass (exec mask), and a wavefront whose tracks are all dead skips it
-        if (st || job.fbe_out) lk_track(job.J, job.I, job.win, job.max_count, job.eps2, fx, fy, bx, by, st2, e2, ldsI, ldsD, lane, n_iter, n_setup, false);
-        const float ddx = __fsub_rn(px, bx), ddy = __fsub_rn(py, by);
-        fbe = vh_sqrtf(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)));
-        st = st && st2 && (fbe < job.fbt);
-    }
-    if (lane == 0) {
-        float ox, oy;
-        if (job.out_mode == VH_OUT_SCALE) {
-            ox = __fdiv_rn(fx, job.out_scale);
-            oy = __fdiv_rn(fy, job.out_scale);
-        } else {
-            const float ax = __fadd_rn(fx, job.in_off[0]), ay = __fadd_rn(fy, job.in_off[1]);
-            if (job.out_mode == VH_OUT_TRANSLATE) {
-                ox = __fadd_rn(ax, job.out_off[0]);
-                oy = __fadd_rn(ay, job.out_off[1]);
-            } else {
-                ox = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[0]), __fmul_rn(ay, job.T[2])), job.T[4]);
-                oy = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[1]), __fmul_rn(ay, job.T[3])), job.T[5]);
-            }
-        }
-        job.p_out[2 * pt] = ox;
-        job.p_out[2 * pt + 1] = oy;
-        job.v_out[pt] = (uint8_t)(st != 0);
-        if (job.err_out) job.err_out[pt] = err;
-        if (job.fbe_out) job.fbe_out[pt] = fbe;
-        if (job.praw_out) { job.praw_out[2 * pt] = fx; job.praw_out[2 * pt + 1] = fy; }
-        if (job.stats) {
-            unsigned long long* st = job.stats + (size_t)(blockIdx.x & (VH_LK_STAT_SLOTS - 1)) * 16;  // (counters spread over VH_LK_STAT_SLOTS lines: see StreamWS::lk_stats)
-            atomicAdd(&st[0], (unsigned long long)n_iter);
-            atomicAdd(&st[1], (unsigned long long)n_setup);
-        }
+    LKLevel lf{job.win, job.max_count, job.eps2, reinterpret_cast<short*>(smem + (size_t)kmax * 64 * 4), reinterpret_cast<int*>(smem), (int)threadIdx.x, 0, 0};
+    LKResult R;
+    lk_solve(job, px, py, lf, R);
+    if (threadIdx.x == 0) {
+        lk_store_track(job, pt, R.fx, R.fy, R.st, R.err, R.fbe);
+        lk_add_stats(job, blockIdx.x, lf.n_iter, lf.n_setup);
     }
 }
 
@@ -597,21 +498,13 @@ __device__ void lk_level_strip(const ImgDesc I, const ImgDesc J, int win_rt, int
     const int win = WIN_T ? WIN_T : win_rt;
     const int spr = (win + 3) >> 2;   // strips per window row
     const int nstrips = spr * win;
-    const float half = (float)(win - 1) * 0.5f;
-    const float lscale = __uint_as_float((unsigned)(127 - level) << 23);  // 2^-level exactly = (float)(1. / (1 << level)), without the f64 division
-    float px = __fmul_rn(p0x, lscale), py = __fmul_rn(p0y, lscale);
-    float nx, ny;
-    if (level == top_level) { nx = px; ny = py; }
-    else { nx = __fmul_rn(nxo, 2.f); ny = __fmul_rn(nyo, 2.f); }
-    nxo = nx; nyo = ny;
-
-    px = __fsub_rn(px, half); py = __fsub_rn(py, half);
-    const int ipx = vh_floor(px), ipy = vh_floor(py);
-    if (ipx < -win || ipx >= I.w || ipy < -win || ipy >= I.h) {
-        if (level == 0) { status = 0; err = 0.f; }
-        return;
-    }
-    const Win w0 = bilinear_weights(__fsub_rn(px, (float)ipx), __fsub_rn(py, (float)ipy));
+    const int reach = 4 * spr + 8;    // bytes from the first one that the aligned row reads of a strip row may touch (lk_block_inside)
+    LKStart s;
+    if (!lk_level_start(p0x, p0y, level, top_level, win, I, nxo, nyo, status, err, s)) return;
+    const float half = s.half;
+    const int ipx = s.ipx, ipy = s.ipy;
+    float nx = s.nx, ny = s.ny;
+    const Win w0 = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
     n_setup++;
     // strip coordinates of this lane: s = lane + 64 k -> (row, 4*col); advanced incrementally
     const int j_first = lane % spr, y_first = lane / spr;
@@ -619,11 +512,9 @@ __device__ void lk_level_strip(const ImgDesc I, const ImgDesc J, int win_rt, int
 
     int a11 = 0, a12 = 0, a22 = 0;
     {
-        // interior window: the patch [ipx-1, ipx+win+1] x [ipy-1, ipy+win+1] lies inside the level (V identity).  The aligned 12-byte row reads of a
-        // strip (and the padding samples of the last strip) may run past either end of a row: harmless inside the level, excluded where they would
-        // leave it (first row to the left, last row to the right)
-        const bool fast = ipx >= 1 && ipy >= 1 && ipx + win + 3 <= I.w && ipy + win + 2 <= I.h && !(ipy == 1 && ipx < 4) &&
-                          !(ipy + win + 2 == I.h && ipx + 4 * spr + 7 > I.w);
+        // interior window: the patch [ipx-1, ipx+win+1] x [ipy-1, ipy+win+1] lies inside the level (V identity), and so do the aligned 12-byte row
+        // reads of a strip (and the padding samples of the last strip)
+        const bool fast = lk_block_inside(I, ipx - 1, ipy - 1, win + 3, reach);
         if constexpr (WIN_T != 0 && ((((WIN_T + 3) >> 2) * WIN_T + 63) / 64) <= 2) {
             constexpr int SPR = (WIN_T + 3) >> 2, NS = SPR * WIN_T, KMAX = (NS + 63) / 64, G = KMAX < 3 ? KMAX : 3;
 #pragma unroll
@@ -669,28 +560,21 @@ __device__ void lk_level_strip(const ImgDesc I, const ImgDesc J, int win_rt, int
     const long long sA11 = ROWSAFE ? wave_sum_i32_rows(a11) : wave_sum_i32_wide(a11);
     const long long sA12 = ROWSAFE ? wave_sum_i32_rows(a12) : wave_sum_i32_wide(a12);
     const long long sA22 = ROWSAFE ? wave_sum_i32_rows(a22) : wave_sum_i32_wide(a22);
-    const float A11 = __fmul_rn(i64_to_f32(sA11), LK_FLT_SCALE), A12 = __fmul_rn(i64_to_f32(sA12), LK_FLT_SCALE), A22 = __fmul_rn(i64_to_f32(sA22), LK_FLT_SCALE);
-    float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-    const float dA = __fsub_rn(A11, A22);
-    const float disc = __fadd_rn(__fmul_rn(dA, dA), __fmul_rn(__fmul_rn(4.f, A12), A12));
-    const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), vh_sqrtf(disc)), (float)(2 * win * win));
-    if (minEig < 1e-4f || D < 1.1920929e-07f) {
+    LKSys S;
+    if (!lk_system(sA11, sA12, sA22, win, S)) {
         if (level == 0) status = 0;
         return;
     }
-    D = __fdiv_rn(1.f, D);
 
-    nx = __fsub_rn(nx, half); ny = __fsub_rn(ny, half);
     float pdx = 0.f, pdy = 0.f;
     for (int it = 0; it < max_count; it++) {
         const int inx = vh_floor(nx), iny = vh_floor(ny);
-        if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) {
+        if (lk_outside(inx, iny, win, J)) {
             if (level == 0) status = 0;
             break;
         }
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny)));
-        const bool fast = inx >= 0 && iny >= 0 && inx + win + 2 <= J.w && iny + win + 1 <= J.h && !(iny == 0 && inx < 3) &&
-                          !(iny + win + 1 == J.h && inx + 4 * spr + 8 > J.w);  // see the set-up
+        const bool fast = lk_block_inside(J, inx, iny, win + 1, reach);
         n_iter++;
         int b1 = 0, b2 = 0;
         if constexpr (WIN_T != 0 && ((((WIN_T + 3) >> 2) * WIN_T + 63) / 64) <= 2) {
@@ -743,28 +627,16 @@ __device__ void lk_level_strip(const ImgDesc I, const ImgDesc J, int win_rt, int
         }
         const long long sb1 = ROWSAFE ? wave_sum_i32_rows(b1) : wave_sum_i32_wide(b1);
         const long long sb2 = ROWSAFE ? wave_sum_i32_rows(b2) : wave_sum_i32_wide(b2);
-        const float fb1 = __fmul_rn(i64_to_f32(sb1), LK_FLT_SCALE), fb2 = __fmul_rn(i64_to_f32(sb2), LK_FLT_SCALE);
-        const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, fb2), __fmul_rn(A22, fb1)), D);
-        const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, fb1), __fmul_rn(A11, fb2)), D);
-        nx = __fadd_rn(nx, dx); ny = __fadd_rn(ny, dy);
-        nxo = __fadd_rn(nx, half); nyo = __fadd_rn(ny, half);
-        if (__dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy)) <= eps2) break;
-        if (it > 0 && fabsf(__fadd_rn(dx, pdx)) < 0.01f && fabsf(__fadd_rn(dy, pdy)) < 0.01f) {
-            nxo = __fsub_rn(nxo, __fmul_rn(dx, 0.5f));
-            nyo = __fsub_rn(nyo, __fmul_rn(dy, 0.5f));
-            break;
-        }
-        pdx = dx; pdy = dy;
+        if (lk_step(S, sb1, sb2, half, it, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
     }
 
     if (status && level == 0) {
-        const float fx = __fsub_rn(nxo, half), fy = __fsub_rn(nyo, half);
-        const int inx = vh_floor(fx), iny = vh_floor(fy);
-        if (inx < -win || inx >= J.w || iny < -win || iny >= J.h) { status = 0; return; }
+        float fx, fy;
+        int inx, iny;
+        if (!lk_final_origin(nxo, nyo, half, win, J, fx, fy, inx, iny)) { status = 0; return; }
         if (!want_err) return;  // err is discarded by the caller (KLT.py:83 `pa, v, _`): only the bounds rule matters
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
-        const bool fast = inx >= 0 && iny >= 0 && inx + win + 2 <= J.w && iny + win + 1 <= J.h && !(iny == 0 && inx < 3) &&
-                          !(iny + win + 1 == J.h && inx + 4 * spr + 8 > J.w);  // see the set-up
+        const bool fast = lk_block_inside(J, inx, iny, win + 1, reach);
         int se = 0;
         int j = j_first, y = y_first, k = 0;
         for (int s = lane; s < nstrips; s += 64, k++) {
@@ -783,21 +655,8 @@ __device__ void lk_level_strip(const ImgDesc I, const ImgDesc J, int win_rt, int
             if (j >= spr) { j -= spr; y++; }
         }
         const long long sse = ROWSAFE ? wave_sum_i32_rows(se) : wave_sum_i32_wide(se);
-        err = __fmul_rn(i64_to_f32(sse), __fdiv_rn(1.f, (float)(32 * win * win)));
+        err = lk_err_of(i64_to_f32(sse), win);
     }
-}
-
-template <int WIN_T>
-__device__ void lk_track_strip(const PyrDesc& PI, const PyrDesc& PJ, int win, int max_count, double eps2, float px, float py, float& ox,
-                               float& oy, int& status, float& err, uint2* tI, uint2* tX, uint2* tY, int lane, int& n_iter, int& n_setup, bool want_err)
-{
-    const int nl = min(PI.nlevels, PJ.nlevels);
-    status = 1;
-    err = 0.f;
-    ox = 0.f; oy = 0.f;
-    for (int level = nl - 1; level >= 0; level--)
-        lk_level_strip<WIN_T>(PI.lv[level], PJ.lv[level], win, level, nl - 1, max_count, eps2, px, py, ox, oy, status, err, tI, tX, tY, lane,
-                              n_iter, n_setup, want_err);
 }
 
 
@@ -835,65 +694,41 @@ __device__ __forceinline__ void lk_block_xy(unsigned& bx, unsigned& by, unsigned
 // workgroups visit every XCD, so a stream that carries more tracks than the others cannot hold one XCD -- and with it the in-order dispatcher -- back)
 static inline unsigned lk_group_arg(unsigned g, int batch) { return g | (batch < 64 ? LK_GRP_ROTATE : 0u); }
 
+// The level functor of k_lk_strip (see lk_track) only forwards to the function above.  With the level body as the functor's own operator() --
+// the form of the other four kernels -- hipcc allocates k_lk_strip<15> differently: 472 instead of 358 v_readlane / v_writelane of parked scalar
+// registers, +340 instructions, and a coarse launch of one stream took 20.89 / 28.21 us against the parent's 20.52 / 27.88 us (profiles/lk_shared/ab.json, first_try)
+template <int WIN_T>
+struct LKStripLevel {
+    int win_rt, max_count;
+    double eps2;
+    uint2 *tI, *tX, *tY;
+    int lane, n_iter, n_setup;
+    __device__ __forceinline__ void operator()(const ImgDesc& I, const ImgDesc& J, int level, int top_level, float p0x, float p0y, float& nxo, float& nyo,
+                                               int& status, float& err, bool want_err)
+    {
+        lk_level_strip<WIN_T>(I, J, win_rt, level, top_level, max_count, eps2, p0x, p0y, nxo, nyo, status, err, tI, tX, tY, lane, n_iter, n_setup, want_err);
+    }
+};
+
 template <int WIN_T>
 __global__ __launch_bounds__(64) void k_lk_strip(const void* job_tab, size_t tab_stride)
 {
     unsigned blk_x, blk_y;
     lk_block_xy<false>(blk_x, blk_y);
-    const LKJob& job = *reinterpret_cast<const LKJob*>(reinterpret_cast<const char*>(job_tab) + (size_t)blk_y * tab_stride);
-    const int n = LK_N_OF(job);
-    if ((int)blk_x >= n) return;
-    const int pt = job.order ? ((gptr_i32)job.order)[blk_x] : (int)blk_x;  // launch slot -> point (LKJob::order)
-    const int lane = threadIdx.x;
+    const LKJob& job = lk_job_row(job_tab, tab_stride, blk_y);
+    int pt;
+    float px, py;
+    if (!lk_slot_start(job, (int)blk_x, pt, px, py)) return;
     const int win = WIN_T ? WIN_T : job.win;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int kmax = (((win + 3) >> 2) * win + 63) / 64;
     uint2* tI = reinterpret_cast<uint2*>(smem);
-    uint2* tX = tI + kmax * 64;
-    uint2* tY = tX + kmax * 64;
-
-    const float qx = ((gptr_f32)job.p_in)[2 * pt], qy = ((gptr_f32)job.p_in)[2 * pt + 1];
-    const float px = __fsub_rn(__fmul_rn(qx, job.in_scale), job.in_off[0]);
-    const float py = __fsub_rn(__fmul_rn(qy, job.in_scale), job.in_off[1]);
-
-    float fx, fy, err;
-    int st, n_iter = 0, n_setup = 0;
-    lk_track_strip<WIN_T>(job.I, job.J, win, job.max_count, job.eps2, px, py, fx, fy, st, err, tI, tX, tY, lane, n_iter, n_setup, job.err_out != nullptr);
-    float fbe = 0.f;
-    if (job.fbt >= 0.f) {
-        float bx = 0.f, by = 0.f, e2;
-        int st2 = 0;
-        if (st || job.fbe_out) lk_track_strip<WIN_T>(job.J, job.I, win, job.max_count, job.eps2, fx, fy, bx, by, st2, e2, tI, tX, tY, lane, n_iter, n_setup, false);
-        const float ddx = __fsub_rn(px, bx), ddy = __fsub_rn(py, by);
-        fbe = vh_sqrtf(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)));
-        st = st && st2 && (fbe < job.fbt);
-    }
-    if (lane == 0) {
-        float ox, oy;
-        if (job.out_mode == VH_OUT_SCALE) {
-            ox = __fdiv_rn(fx, job.out_scale);
-            oy = __fdiv_rn(fy, job.out_scale);
-        } else {
-            const float ax = __fadd_rn(fx, job.in_off[0]), ay = __fadd_rn(fy, job.in_off[1]);
-            if (job.out_mode == VH_OUT_TRANSLATE) {
-                ox = __fadd_rn(ax, job.out_off[0]);
-                oy = __fadd_rn(ay, job.out_off[1]);
-            } else {
-                ox = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[0]), __fmul_rn(ay, job.T[2])), job.T[4]);
-                oy = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[1]), __fmul_rn(ay, job.T[3])), job.T[5]);
-            }
-        }
-        job.p_out[2 * pt] = ox;
-        job.p_out[2 * pt + 1] = oy;
-        job.v_out[pt] = (uint8_t)(st != 0);
-        if (job.err_out) job.err_out[pt] = err;
-        if (job.fbe_out) job.fbe_out[pt] = fbe;
-        if (job.praw_out) { job.praw_out[2 * pt] = fx; job.praw_out[2 * pt + 1] = fy; }
-        if (job.stats) {
-            unsigned long long* st = job.stats + (size_t)(blk_x & (VH_LK_STAT_SLOTS - 1)) * 16;  // (counters spread over VH_LK_STAT_SLOTS lines: see StreamWS::lk_stats)
-            atomicAdd(&st[0], (unsigned long long)n_iter);
-            atomicAdd(&st[1], (unsigned long long)n_setup);
-        }
+    LKStripLevel<WIN_T> lf{win, job.max_count, job.eps2, tI, tI + kmax * 64, tI + 2 * kmax * 64, (int)threadIdx.x, 0, 0};
+    LKResult R;
+    lk_solve(job, px, py, lf, R);
+    if (threadIdx.x == 0) {
+        lk_store_track(job, pt, R.fx, R.fy, R.st, R.err, R.fbe);
+        lk_add_stats(job, blk_x, lf.n_iter, lf.n_setup);
     }
 }
 
@@ -931,7 +766,7 @@ struct LK3 {
     static constexpr int PJ_WIDTH = ((2 * M + 4 * (SPR - 1)) >> 2) * 4 + 8;   // a row read takes two dwords
     static constexpr int PJ_PITCH = PJ_WIDTH + 4;                                // odd dword pitch (LDS banks)
     // The template of a lane's K strips (its Scharr gradients, 2 x 8 bytes per strip; the samples themselves enter only through the sums c, see
-    // lk3_level) stays in REGISTERS for the whole level: LDS then
+    // LK3Level) stays in REGISTERS for the whole level: LDS then
     // holds the two image regions only (~7.7 KB per workgroup for 51x51) and the VGPR file, not LDS, bounds the occupancy.  With the template in
     // LDS (24.5 KB per workgroup: 6 workgroups = 3 wavefronts per SIMD) the kernel lost 14 % per workgroup of occupancy taken away.
     // Every lane runs all K strips of its run with NO per-strip branch: strips below the window (the tail of the last run(s)) are computed from
@@ -947,7 +782,7 @@ struct LK3 {
     // The lane map: what a thread's place in the workgroup alone decides -- its strip column(s) and first row(s), and with them its addresses in the
     // two staged regions and the v_perm selectors that pack (and mask) its gradient pairs.  Slots fall into selector classes: SPLIT 0 = [0, KA),
     // 1 = [KA, K-1), 2 = K-1; otherwise 0 = the slots that always lie inside the window, 1 = the last PAD_ROWS slots of a run (below the window in the
-    // last run(s)).  k_lk3 writes the map to LDS once per workgroup (OFF_TAB), lk3_level reads it back per level: three 16-byte groups per thread,
+    // last run(s)).  k_lk3 writes the map to LDS once per workgroup (OFF_TAB), LK3Level reads it back per level: three 16-byte groups per thread,
     // group-major (group g of thread t at OFF_TAB + 16 * (g * T + t): consecutive lanes read consecutive 16 bytes)
     struct Lane {
         int jA, rA, jB, rB;
@@ -989,7 +824,7 @@ struct LK3 {
         }
         return l;
     }
-    // one selector per class is enough: every slot of a class that holds a strip lies inside the window, for every thread (asserted in lk3_level)
+    // one selector per class is enough: every slot of a class that holds a strip lies inside the window, for every thread (asserted in LK3Level)
     static constexpr bool classes_hold()
     {
         for (int t = 0; t < T; t++) {
@@ -1114,8 +949,19 @@ __device__ __forceinline__ void block_sum_wide(const int* part, long long* tot, 
 }
 
 template <int WIN, int NW, int M>
-__device__ __forceinline__ void lk3_level(const ImgDesc I, const ImgDesc J, int level, int top_level, int max_count, double eps2, float p0x, float p0y,
-                          float& nxo, float& nyo, int& status, float& err, char* smem, int tid, int& phase, int& n_iter, int& n_setup, bool want_err)
+struct LK3Level {  // the level functor of k_lk3 (see lk_track); phase: which half of the double-buffered block reduction comes next
+    int max_count;
+    double eps2;
+    char* smem;
+    int tid;
+    int& phase;
+    int n_iter, n_setup;
+    __device__ __forceinline__ void operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo, float& nyo,
+                                               int& status, float& err, bool want_err);
+};
+template <int WIN, int NW, int M>
+__device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y,
+                                                                 float& nxo, float& nyo, int& status, float& err, bool want_err)
 {
     using C = LK3<WIN, NW, M>;
     // this lane's template gradients (registers: every index below is a compile-time constant).  The template SAMPLES are not kept: with
@@ -1128,23 +974,13 @@ __device__ __forceinline__ void lk3_level(const ImgDesc I, const ImgDesc J, int 
     long long* red = reinterpret_cast<long long*>(smem + C::OFF_RED);
     const int wave = tid >> 6;
 
-    const float half = (float)(WIN - 1) * 0.5f;
-    const float lscale = __uint_as_float((unsigned)(127 - level) << 23);  // 2^-level exactly = (float)(1. / (1 << level)), without the f64 division
-    float px = __fmul_rn(p0x, lscale), py = __fmul_rn(p0y, lscale);
-    float nx, ny;
-    if (level == top_level) { nx = px; ny = py; }
-    else { nx = __fmul_rn(nxo, 2.f); ny = __fmul_rn(nyo, 2.f); }
-    nxo = nx; nyo = ny;
-
-    px = __fsub_rn(px, half); py = __fsub_rn(py, half);
-    const int ipx = vh_floor(px), ipy = vh_floor(py);
-    if (ipx < -WIN || ipx >= I.w || ipy < -WIN || ipy >= I.h) {
-        if (level == 0) { status = 0; err = 0.f; }
-        return;
-    }
-    const Win w0 = bilinear_weights(__fsub_rn(px, (float)ipx), __fsub_rn(py, (float)ipy));
+    LKStart s;
+    if (!lk_level_start(p0x, p0y, level, top_level, WIN, I, nxo, nyo, status, err, s)) return;
+    const float half = s.half;
+    const int ipx = s.ipx, ipy = s.ipy;
+    float nx = s.nx, ny = s.ny;
+    const Win w0 = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
     n_setup++;
-    nx = __fsub_rn(nx, half); ny = __fsub_rn(ny, half);
 
     // one batch of global loads: template patch + search region around the predicted position
     int rjx = vh_floor(nx) - M, rjy = vh_floor(ny) - M;
@@ -1260,16 +1096,11 @@ __device__ __forceinline__ void lk3_level(const ImgDesc I, const ImgDesc J, int 
     }
     long long sA[3];
     block_sum_wide<NW, 3, (C::K == 1 && C::T == 64)>(part, sA, red, phase, wave);
-    const float A11 = __fmul_rn(i64_to_f32(sA[0]), LK_FLT_SCALE), A12 = __fmul_rn(i64_to_f32(sA[1]), LK_FLT_SCALE), A22 = __fmul_rn(i64_to_f32(sA[2]), LK_FLT_SCALE);
-    float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-    const float dA = __fsub_rn(A11, A22);
-    const float disc = __fadd_rn(__fmul_rn(dA, dA), __fmul_rn(__fmul_rn(4.f, A12), A12));
-    const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), vh_sqrtf(disc)), (float)(2 * WIN * WIN));
-    if (minEig < 1e-4f || D < 1.1920929e-07f) {
+    LKSys S;
+    if (!lk_system(sA[0], sA[1], sA[2], WIN, S)) {
         if (level == 0) status = 0;
         return;
     }
-    D = __fdiv_rn(1.f, D);
     const int ncI[2] = {-cI[0], -cI[1]};
     constexpr int PJP = C::PJ_PITCH >> 2;
     // C::OFF_PJ + 4 * (rA * PJP + jA) and the same of (rB, jB): (((inx - rjx) + 4 j) >> 2 = ((inx - rjx) >> 2) + j).  Out of the table they are opaque to the
@@ -1300,7 +1131,7 @@ __device__ __forceinline__ void lk3_level(const ImgDesc I, const ImgDesc J, int 
     float pdx = 0.f, pdy = 0.f;
     for (int it = 0; it < max_count; it++) {
         const int inx = vh_floor(nx), iny = vh_floor(ny);
-        if (inx < -WIN || inx >= J.w || iny < -WIN || iny >= J.h) {
+        if (lk_outside(inx, iny, WIN, J)) {
             if (level == 0) status = 0;
             break;
         }
@@ -1355,24 +1186,13 @@ __device__ __forceinline__ void lk3_level(const ImgDesc I, const ImgDesc J, int 
         }
         long long sb[2];
         block_sum_wide<NW, 2, (C::K == 1 && C::T == 64)>(b, sb, red, phase, wave);
-        const float fb1 = __fmul_rn(i64_to_f32(sb[0]), LK_FLT_SCALE), fb2 = __fmul_rn(i64_to_f32(sb[1]), LK_FLT_SCALE);
-        const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, fb2), __fmul_rn(A22, fb1)), D);
-        const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, fb1), __fmul_rn(A11, fb2)), D);
-        nx = __fadd_rn(nx, dx); ny = __fadd_rn(ny, dy);
-        nxo = __fadd_rn(nx, half); nyo = __fadd_rn(ny, half);
-        if (__dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy)) <= eps2) break;
-        if (it > 0 && fabsf(__fadd_rn(dx, pdx)) < 0.01f && fabsf(__fadd_rn(dy, pdy)) < 0.01f) {
-            nxo = __fsub_rn(nxo, __fmul_rn(dx, 0.5f));
-            nyo = __fsub_rn(nyo, __fmul_rn(dy, 0.5f));
-            break;
-        }
-        pdx = dx; pdy = dy;
+        if (lk_step(S, sb[0], sb[1], half, it, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
     }
 
     if (status && level == 0) {
-        const float fx = __fsub_rn(nxo, half), fy = __fsub_rn(nyo, half);
-        const int inx = vh_floor(fx), iny = vh_floor(fy);
-        if (inx < -WIN || inx >= J.w || iny < -WIN || iny >= J.h) { status = 0; return; }
+        float fx, fy;
+        int inx, iny;
+        if (!lk_final_origin(nxo, nyo, half, WIN, J, fx, fy, inx, iny)) { status = 0; return; }
         if (!want_err) return;  // err is discarded by the caller (KLT.py:83 `pa, v, _`): only the bounds rule matters
         if (!region_holds(inx, iny)) restage(inx, iny);
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
@@ -1406,21 +1226,8 @@ __device__ __forceinline__ void lk3_level(const ImgDesc I, const ImgDesc J, int 
         }
         long long sse[1];
         block_sum_wide<NW, 1, (C::K == 1 && C::T == 64)>(se, sse, red, phase, wave);
-        err = __fmul_rn(i64_to_f32(sse[0]), __fdiv_rn(1.f, (float)(32 * WIN * WIN)));
+        err = lk_err_of(i64_to_f32(sse[0]), WIN);
     }
-}
-
-template <int WIN, int NW, int M>
-__device__ __forceinline__ void lk3_track(const PyrDesc& PI, const PyrDesc& PJ, int max_count, double eps2, float px, float py, float& ox, float& oy,
-                          int& status, float& err, char* smem, int tid, int& phase, int& n_iter, int& n_setup, bool want_err)
-{
-    const int nl = min(PI.nlevels, PJ.nlevels);
-    status = 1;
-    err = 0.f;
-    ox = 0.f; oy = 0.f;
-    for (int level = nl - 1; level >= 0; level--)
-        lk3_level<WIN, NW, M>(PI.lv[level], PJ.lv[level], level, nl - 1, max_count, eps2, px, py, ox, oy, status, err, smem, tid, phase, n_iter,
-                              n_setup, want_err);
 }
 
 // (forcing 5 or 6 workgroups per CU through the second launch bound spills and measured 3-8 % slower; a 128-VGPR cap
@@ -1451,92 +1258,54 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 1
     // scalar registers the track code spills
 #pragma unroll 1
     for (unsigned ti = 0; ti < tpw; ti++) {
-        const LKJob& job = *reinterpret_cast<const LKJob*>(reinterpret_cast<const char*>(job_tab) + (size_t)blk_y * tab_stride);
-        const int n = LK_N_OF(job);
-        const unsigned slot = blk_x * tpw + ti;
-        if ((int)slot >= n) break;
-        const int tid = threadIdx.x;
-        const int max_count = job.max_count;
-        const double eps2 = job.eps2;
-        const float fbt = job.fbt;
-        // the point index and the start position are workgroup uniform and live until the epilogue: as SCALARS (the loads below come back in vector registers,
+        const LKJob& job = lk_job_row(job_tab, tab_stride, blk_y);
+        // the point index and the start position are workgroup uniform and live until the epilogue: as SCALARS (their loads come back in vector registers,
         // and hipcc then parks them in scratch for the length of the kernel: 7 spilled registers, 28 bytes of scratch traffic per lane and track)
-        const int pt = __builtin_amdgcn_readfirstlane(job.order ? ((gptr_i32)job.order)[slot] : (int)slot);  // launch slot -> point (LKJob::order)
-
-        const float qx = ((gptr_f32)job.p_in)[2 * pt], qy = ((gptr_f32)job.p_in)[2 * pt + 1];
-        const float px = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__fsub_rn(__fmul_rn(qx, job.in_scale), job.in_off[0]))));
-        const float py = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__fsub_rn(__fmul_rn(qy, job.in_scale), job.in_off[1]))));
+        int pt;
+        float px, py;
+        if (!lk_slot_start<true>(job, (int)(blk_x * tpw + ti), pt, px, py)) break;
+        const float fbt = job.fbt;
+        LK3Level<WIN, NW, M> lf{job.max_count, job.eps2, smem, (int)threadIdx.x, phase, 0, 0};
 
         // forward pass, then (fbt >= 0) the backward pass from its result: ONE copy of the track code in a loop over the direction -- two inlined copies
-        // doubled the kernel and recomputed the per-lane mapping / masks of lk3_level in each
+        // doubled the kernel and recomputed the per-lane mapping / masks of LK3Level in each
         float fx = 0.f, fy = 0.f, err = 0.f, bx = 0.f, by = 0.f;
-        int st = 0, st2 = 0, n_iter = 0, n_setup = 0;
+        int st = 0, st2 = 0;
         const int ndir = fbt >= 0.f ? 2 : 1;
         const bool want_err = job.err_out != nullptr;
     #pragma unroll 1
         for (int dir = 0; dir < ndir; dir++) {
-            if (dir == 1 && !st && !job.fbe_out) break;  // forward status 0 (block uniform): the backward pass cannot change v or p (see k_lk)
+            if (dir == 1 && !st && !job.fbe_out) break;  // forward status 0 (block uniform): the backward pass cannot change v or p (see lk_solve)
             const PyrDesc& PA = dir ? job.J : job.I;
             const PyrDesc& PB = dir ? job.I : job.J;
             float ox, oy, e;
             int s;
-            lk3_track<WIN, NW, M>(PA, PB, max_count, eps2, dir ? fx : px, dir ? fy : py, ox, oy, s, e, smem, tid, phase, n_iter, n_setup, want_err && dir == 0);
+            lk_track(PA, PB, dir ? fx : px, dir ? fy : py, ox, oy, s, e, want_err && dir == 0, lf);
             if (dir == 0) { fx = ox; fy = oy; st = s; err = e; }
             else { bx = ox; by = oy; st2 = s; }
         }
-        float fbe = 0.f;
-        if (fbt >= 0.f) {
-            const float ddx = __fsub_rn(px, bx), ddy = __fsub_rn(py, by);
-            fbe = vh_sqrtf(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)));
-            st = st && st2 && (fbe < fbt);
-        }
+        const float fbe = fbt >= 0.f ? lk_fb_gate(px, py, bx, by, fbt, st2, st) : 0.f;
         // the track's results wait in LDS: a global store inside this loop would make every descriptor load of the NEXT track a possibly-clobbered load,
         // i.e. a vector load instead of a scalar one (the same effect as the volatile asm of DESIGN.md section 9)
-        if (NW == 1 ? lane_in(1ull) : tid == 0) {
+        if (NW == 1 ? lane_in(1ull) : threadIdx.x == 0) {
             // (an explicit LDS pointer: through a generic one hipcc counts these stores as possible writes to the job descriptors too)
             lds_i32 rec = (lds_i32)(smem + LK3<WIN, NW, M>::OFF_RES) + 8 * ti;
             rec[0] = pt; rec[1] = __float_as_int(fx); rec[2] = __float_as_int(fy); rec[3] = st != 0;
             rec[4] = __float_as_int(err); rec[5] = __float_as_int(fbe);
         }
-        tot_iter += n_iter; tot_setup += n_setup;
+        tot_iter += lf.n_iter; tot_setup += lf.n_setup;
         ndone = ti + 1;
         // The LAST memory operation of the loop body must not be a plain store: hipcc's scalar-load test (is a load clobbered anywhere in the function?) takes
         // whatever definition reaches the loop header over the back edge at face value when it is a store -- LDS or not -- and only looks through fences
         // and barriers with alias analysis.  With the record stores last, every descriptor load of the track code became a vector load.
         __syncthreads();
     }
-    const LKJob& job = *reinterpret_cast<const LKJob*>(reinterpret_cast<const char*>(job_tab) + (size_t)blk_y * tab_stride);
+    const LKJob& job = lk_job_row(job_tab, tab_stride, blk_y);
     if (threadIdx.x < ndone) {
         const int* rec = reinterpret_cast<const int*>(smem + LK3<WIN, NW, M>::OFF_RES) + 8 * threadIdx.x;
-        const int pt = rec[0];
-        const float fx = __int_as_float(rec[1]), fy = __int_as_float(rec[2]), err = __int_as_float(rec[4]), fbe = __int_as_float(rec[5]);
-        const int st = rec[3];
-        float ox, oy;
-        if (job.out_mode == VH_OUT_SCALE) {
-            ox = __fdiv_rn(fx, job.out_scale);
-            oy = __fdiv_rn(fy, job.out_scale);
-        } else {
-            const float ax = __fadd_rn(fx, job.in_off[0]), ay = __fadd_rn(fy, job.in_off[1]);
-            if (job.out_mode == VH_OUT_TRANSLATE) {
-                ox = __fadd_rn(ax, job.out_off[0]);
-                oy = __fadd_rn(ay, job.out_off[1]);
-            } else {
-                ox = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[0]), __fmul_rn(ay, job.T[2])), job.T[4]);
-                oy = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[1]), __fmul_rn(ay, job.T[3])), job.T[5]);
-            }
-        }
-        job.p_out[2 * pt] = ox;
-        job.p_out[2 * pt + 1] = oy;
-        job.v_out[pt] = (uint8_t)(st != 0);
-        if (job.err_out) job.err_out[pt] = err;
-        if (job.fbe_out) job.fbe_out[pt] = fbe;
-        if (job.praw_out) { job.praw_out[2 * pt] = fx; job.praw_out[2 * pt + 1] = fy; }
+        lk_store_track(job, rec[0], __int_as_float(rec[1]), __int_as_float(rec[2]), rec[3], __int_as_float(rec[4]), __int_as_float(rec[5]));
     }
-    if (threadIdx.x == 0 && job.stats && ndone) {
-        unsigned long long* st = job.stats + (size_t)(blk_x & (VH_LK_STAT_SLOTS - 1)) * 16;  // (counters spread over VH_LK_STAT_SLOTS lines: see StreamWS::lk_stats)
-        atomicAdd(&st[0], (unsigned long long)tot_iter);
-        atomicAdd(&st[1], (unsigned long long)tot_setup);
-    }
+    if (threadIdx.x == 0 && ndone) lk_add_stats(job, blk_x, tot_iter, tot_setup);
 }
 
 // =================================================================================================================
@@ -1617,39 +1386,36 @@ __device__ __forceinline__ void load_row_words(const ImgDesc& im, int gx, int gy
 }
 
 template <int WIN>
-__device__ __forceinline__ void lkq_level(const ImgDesc I, const ImgDesc J, int level, int top_level, int max_count, double eps2, float p0x,
-                                          float p0y, float& nxo, float& nyo, int& status, float& err, int r, int& n_iter, int& n_setup,
-                                          bool want_err)
+struct LKQLevel {  // the level functor of k_lk_q (see lk_track); r: this lane's place in its track's lanes
+    int max_count;
+    double eps2;
+    int r, n_iter, n_setup;
+    __device__ __forceinline__ void operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo, float& nyo,
+                                               int& status, float& err, bool want_err);
+};
+template <int WIN>
+__device__ __forceinline__ void LKQLevel<WIN>::operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo,
+                                                          float& nyo, int& status, float& err, bool want_err)
 {
     constexpr int NS = (WIN + 3) >> 2;  // strips per row
-    const float half = (float)(WIN - 1) * 0.5f;
-    const float lscale = __uint_as_float((unsigned)(127 - level) << 23);  // 2^-level exactly = (float)(1. / (1 << level)), without the f64 division
-    float px = __fmul_rn(p0x, lscale), py = __fmul_rn(p0y, lscale);
-    float nx, ny;
-    if (level == top_level) { nx = px; ny = py; }
-    else { nx = __fmul_rn(nxo, 2.f); ny = __fmul_rn(nyo, 2.f); }
-    nxo = nx; nyo = ny;
-
-    px = __fsub_rn(px, half); py = __fsub_rn(py, half);
-    const int ipx = vh_floor(px), ipy = vh_floor(py);
-    if (ipx < -WIN || ipx >= I.w || ipy < -WIN || ipy >= I.h) {
-        if (level == 0) { status = 0; err = 0.f; }
-        return;
-    }
-    const Win w0 = bilinear_weights(__fsub_rn(px, (float)ipx), __fsub_rn(py, (float)ipy));
+    constexpr int reach = WIN + 9;      // bytes from the first one that the aligned row reads of a lane may touch (lk_block_inside)
+    LKStart s;
+    if (!lk_level_start(p0x, p0y, level, top_level, WIN, I, nxo, nyo, status, err, s)) return;
+    const float half = s.half;
+    const int ipx = s.ipx, ipy = s.ipy;
+    float nx = s.nx, ny = s.ny;
+    const Win w0 = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
     n_setup++;
 
     int a11 = 0, a12 = 0, a22 = 0;
-    // template gradients of this lane's row (registers); the template SAMPLES are not kept: sum (J - I) Ix = sum J Ix - cI (see lk3_level)
+    // template gradients of this lane's row (registers); the template SAMPLES are not kept: sum (J - I) Ix = sum J Ix - cI (see LK3Level)
     uint2 tX[NS], tY[NS];
     int cI[2] = {0, 0};
 #pragma unroll
     for (int j = 0; j < NS; j++) { tX[j] = make_uint2(0, 0); tY[j] = make_uint2(0, 0); }
-    // interior window: the (WIN+3)^2 patch [ipx-1, ipx+WIN+1] x [ipy-1, ipy+WIN+1] lies inside the level, so the V identity holds.  The aligned
-    // 24-byte row reads may run a few bytes past either end of a row: harmless inside the level, excluded where that would leave it (first row to
-    // the left, last row to the right)
-    const bool fast_I = ipx >= 1 && ipy >= 1 && ipx + WIN + 3 <= I.w && ipy + WIN + 2 <= I.h && !(ipy == 1 && ipx < 4) &&
-                        !(ipy + WIN + 2 == I.h && ipx + WIN + 8 > I.w);
+    // interior window: the (WIN+3)^2 patch [ipx-1, ipx+WIN+1] x [ipy-1, ipy+WIN+1] lies inside the level, so the V identity holds, and so do the
+    // aligned 24-byte row reads
+    const bool fast_I = lk_block_inside(I, ipx - 1, ipy - 1, WIN + 3, reach);
     const unsigned w0t = pack16(w0.w00, w0.w01), w0b = pack16(w0.w10, w0.w11);
     if (fast_I) {
         // Interior window, all 16 lanes of the track (lane WIN feeds lane WIN-1).  Lane r reads patch rows r .. r+2 and builds V rows r and r+1 over
@@ -1756,29 +1522,21 @@ __device__ __forceinline__ void lkq_level(const ImgDesc I, const ImgDesc J, int 
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    const float A11 = __fmul_rn(i64_to_f32(row16_sum_wide(a11)), LK_FLT_SCALE), A12 = __fmul_rn(i64_to_f32(row16_sum_wide(a12)), LK_FLT_SCALE),
-                A22 = __fmul_rn(i64_to_f32(row16_sum_wide(a22)), LK_FLT_SCALE);
-    float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-    const float dA = __fsub_rn(A11, A22);
-    const float disc = __fadd_rn(__fmul_rn(dA, dA), __fmul_rn(__fmul_rn(4.f, A12), A12));
-    const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), vh_sqrtf(disc)), (float)(2 * WIN * WIN));
-    if (minEig < 1e-4f || D < 1.1920929e-07f) {
+    LKSys S;
+    if (!lk_system(row16_sum_wide(a11), row16_sum_wide(a12), row16_sum_wide(a22), WIN, S)) {
         if (level == 0) status = 0;
         return;
     }
-    D = __fdiv_rn(1.f, D);
 
-    nx = __fsub_rn(nx, half); ny = __fsub_rn(ny, half);
     float pdx = 0.f, pdy = 0.f;
     for (int it = 0; it < max_count; it++) {
         const int inx = vh_floor(nx), iny = vh_floor(ny);
-        if (inx < -WIN || inx >= J.w || iny < -WIN || iny >= J.h) {
+        if (lk_outside(inx, iny, WIN, J)) {
             if (level == 0) status = 0;
             break;
         }
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny)));
-        const bool fast = J.pad >= VH_LV_PAD || (inx >= 0 && iny >= 0 && inx + WIN + 2 <= J.w && iny + WIN + 1 <= J.h && !(iny == 0 && inx < 3) &&
-                                                 !(iny + WIN + 1 == J.h && inx + WIN + 9 > J.w));  // bordered level, or rows inside the level (exclusions as fast_I)
+        const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);  // bordered level, or rows inside the level
         n_iter++;
         unsigned p01[NS], p23[NS];
         lkq_sample_row<NS>(J, inx, iny, r, fast, w.wt, w.wb, p01, p23);  // lane r = row r (lane WIN holds the last bottom row)
@@ -1789,28 +1547,16 @@ __device__ __forceinline__ void lkq_level(const ImgDesc I, const ImgDesc J, int 
             b1 = dot2(p23[j], tX[j].y, dot2(p01[j], tX[j].x, b1));
             b2 = dot2(p23[j], tY[j].y, dot2(p01[j], tY[j].x, b2));
         }
-        const float fb1 = __fmul_rn(i64_to_f32(row16_sum_wide(b1)), LK_FLT_SCALE), fb2 = __fmul_rn(i64_to_f32(row16_sum_wide(b2)), LK_FLT_SCALE);
-        const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, fb2), __fmul_rn(A22, fb1)), D);
-        const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, fb1), __fmul_rn(A11, fb2)), D);
-        nx = __fadd_rn(nx, dx); ny = __fadd_rn(ny, dy);
-        nxo = __fadd_rn(nx, half); nyo = __fadd_rn(ny, half);
-        if (__dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy)) <= eps2) break;
-        if (it > 0 && fabsf(__fadd_rn(dx, pdx)) < 0.01f && fabsf(__fadd_rn(dy, pdy)) < 0.01f) {
-            nxo = __fsub_rn(nxo, __fmul_rn(dx, 0.5f));
-            nyo = __fsub_rn(nyo, __fmul_rn(dy, 0.5f));
-            break;
-        }
-        pdx = dx; pdy = dy;
+        if (lk_step(S, row16_sum_wide(b1), row16_sum_wide(b2), half, it, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
     }
 
     if (status && level == 0) {
-        const float fx = __fsub_rn(nxo, half), fy = __fsub_rn(nyo, half);
-        const int inx = vh_floor(fx), iny = vh_floor(fy);
-        if (inx < -WIN || inx >= J.w || iny < -WIN || iny >= J.h) { status = 0; return; }
+        float fx, fy;
+        int inx, iny;
+        if (!lk_final_origin(nxo, nyo, half, WIN, J, fx, fy, inx, iny)) { status = 0; return; }
         if (!want_err) return;
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
-        const bool fast = J.pad >= VH_LV_PAD || (inx >= 0 && iny >= 0 && inx + WIN + 2 <= J.w && iny + WIN + 1 <= J.h && !(iny == 0 && inx < 3) &&
-                                                 !(iny + WIN + 1 == J.h && inx + WIN + 9 > J.w));  // bordered level, or rows inside the level (exclusions as fast_I)
+        const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);  // bordered level, or rows inside the level
         unsigned p01[NS], p23[NS], i01[NS], i23[NS];
         lkq_sample_row<NS>(J, inx, iny, r, fast, w.wt, w.wb, p01, p23);
         // the template samples again (not kept by the set-up): the same bilinear sampling of I at the template origin
@@ -1824,20 +1570,8 @@ __device__ __forceinline__ void lkq_level(const ImgDesc I, const ImgDesc J, int 
 #pragma unroll
             for (int c = 0; c < 4; c++) se += (c < cnt && r < WIN) ? (d[c] < 0 ? -d[c] : d[c]) : 0;
         }
-        err = __fmul_rn(i64_to_f32(row16_sum_wide(se)), __fdiv_rn(1.f, (float)(32 * WIN * WIN)));
+        err = lk_err_of(i64_to_f32(row16_sum_wide(se)), WIN);
     }
-}
-
-template <int WIN>
-__device__ __forceinline__ void lkq_track(const PyrDesc& PI, const PyrDesc& PJ, int max_count, double eps2, float px, float py, float& ox,
-                                          float& oy, int& status, float& err, int r, int& n_iter, int& n_setup, bool want_err)
-{
-    const int nl = min(PI.nlevels, PJ.nlevels);
-    status = 1;
-    err = 0.f;
-    ox = 0.f; oy = 0.f;
-    for (int level = nl - 1; level >= 0; level--)
-        lkq_level<WIN>(PI.lv[level], PJ.lv[level], level, nl - 1, max_count, eps2, px, py, ox, oy, status, err, r, n_iter, n_setup, want_err);
 }
 
 template <int WIN>
@@ -1846,55 +1580,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
     static_assert(WIN <= 15, "lane WIN of every 16-lane row carries the extra bottom row");
     unsigned blk_x, blk_y;
     lk_block_xy<true>(blk_x, blk_y, grp);
-    const LKJob& job = *reinterpret_cast<const LKJob*>(reinterpret_cast<const char*>(job_tab) + (size_t)blk_y * tab_stride);
-    const int n = LK_N_OF(job);
+    const LKJob& job = lk_job_row(job_tab, tab_stride, blk_y);
     const int slot = (int)blk_x * 4 + (threadIdx.x >> 4);
-    if (slot >= n) return;
-    const int pt = job.order ? ((gptr_i32)job.order)[slot] : slot;  // launch slot -> point (LKJob::order)  // whole 16-lane rows leave together
-    const int r = threadIdx.x & 15;
-
-    const float qx = ((gptr_f32)job.p_in)[2 * pt], qy = ((gptr_f32)job.p_in)[2 * pt + 1];
-    const float px = __fsub_rn(__fmul_rn(qx, job.in_scale), job.in_off[0]);
-    const float py = __fsub_rn(__fmul_rn(qy, job.in_scale), job.in_off[1]);
-
-    float fx, fy, err;
-    int st, n_iter = 0, n_setup = 0;
-    lkq_track<WIN>(job.I, job.J, job.max_count, job.eps2, px, py, fx, fy, st, err, r, n_iter, n_setup, job.err_out != nullptr);
-    float fbe = 0.f;
-    if (job.fbt >= 0.f) {
-        float bx = 0.f, by = 0.f, e2;
-        int st2 = 0;
-        if (st || job.fbe_out) lkq_track<WIN>(job.J, job.I, job.max_count, job.eps2, fx, fy, bx, by, st2, e2, r, n_iter, n_setup, false);
-        const float ddx = __fsub_rn(px, bx), ddy = __fsub_rn(py, by);
-        fbe = vh_sqrtf(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)));
-        st = st && st2 && (fbe < job.fbt);
-    }
-    if (r == 0) {
-        float ox, oy;
-        if (job.out_mode == VH_OUT_SCALE) {
-            ox = __fdiv_rn(fx, job.out_scale);
-            oy = __fdiv_rn(fy, job.out_scale);
-        } else {
-            const float ax = __fadd_rn(fx, job.in_off[0]), ay = __fadd_rn(fy, job.in_off[1]);
-            if (job.out_mode == VH_OUT_TRANSLATE) {
-                ox = __fadd_rn(ax, job.out_off[0]);
-                oy = __fadd_rn(ay, job.out_off[1]);
-            } else {
-                ox = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[0]), __fmul_rn(ay, job.T[2])), job.T[4]);
-                oy = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[1]), __fmul_rn(ay, job.T[3])), job.T[5]);
-            }
-        }
-        job.p_out[2 * pt] = ox;
-        job.p_out[2 * pt + 1] = oy;
-        job.v_out[pt] = (uint8_t)(st != 0);
-        if (job.err_out) job.err_out[pt] = err;
-        if (job.fbe_out) job.fbe_out[pt] = fbe;
-        if (job.praw_out) { job.praw_out[2 * pt] = fx; job.praw_out[2 * pt + 1] = fy; }
-        if (job.stats) {
-            unsigned long long* st = job.stats + (size_t)((unsigned)slot & (VH_LK_STAT_SLOTS - 1)) * 16;  // (counters spread over VH_LK_STAT_SLOTS lines: see StreamWS::lk_stats)
-            atomicAdd(&st[0], (unsigned long long)n_iter);
-            atomicAdd(&st[1], (unsigned long long)n_setup);
-        }
+    int pt;
+    float px, py;
+    if (!lk_slot_start(job, slot, pt, px, py)) return;  // whole 16-lane rows leave together
+    LKQLevel<WIN> lf{job.max_count, job.eps2, (int)(threadIdx.x & 15), 0, 0};
+    LKResult R;
+    lk_solve(job, px, py, lf, R);
+    if (lf.r == 0) {
+        lk_store_track(job, pt, R.fx, R.fy, R.st, R.err, R.fbe);
+        lk_add_stats(job, (unsigned)slot, lf.n_iter, lf.n_setup);
     }
 }
 
@@ -1948,33 +1644,31 @@ __device__ __forceinline__ void lko_sample_rows(const ImgDesc& im, int x0, int y
 }
 
 template <int WIN>
-__device__ __forceinline__ void lko_level(const ImgDesc I, const ImgDesc J, int level, int top_level, int max_count, double eps2, float p0x,
-                                          float p0y, float& nxo, float& nyo, int& status, float& err, int r, int& n_iter, int& n_setup,
-                                          bool want_err)
+struct LKOLevel {  // the level functor of k_lk_o (see lk_track); r: this lane's place in its track's lanes
+    int max_count;
+    double eps2;
+    int r, n_iter, n_setup;
+    __device__ __forceinline__ void operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo, float& nyo,
+                                               int& status, float& err, bool want_err);
+};
+template <int WIN>
+__device__ __forceinline__ void LKOLevel<WIN>::operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo,
+                                                          float& nyo, int& status, float& err, bool want_err)
 {
     constexpr int NS = (WIN + 3) >> 2;  // strips per row
-    const float half = (float)(WIN - 1) * 0.5f;
-    const float lscale = __uint_as_float((unsigned)(127 - level) << 23);
-    float px = __fmul_rn(p0x, lscale), py = __fmul_rn(p0y, lscale);
-    float nx, ny;
-    if (level == top_level) { nx = px; ny = py; }
-    else { nx = __fmul_rn(nxo, 2.f); ny = __fmul_rn(nyo, 2.f); }
-    nxo = nx; nyo = ny;
-
-    px = __fsub_rn(px, half); py = __fsub_rn(py, half);
-    const int ipx = vh_floor(px), ipy = vh_floor(py);
-    if (ipx < -WIN || ipx >= I.w || ipy < -WIN || ipy >= I.h) {
-        if (level == 0) { status = 0; err = 0.f; }
-        return;
-    }
-    const Win w0 = bilinear_weights(__fsub_rn(px, (float)ipx), __fsub_rn(py, (float)ipy));
+    constexpr int reach = WIN + 9;      // bytes from the first one that the aligned row reads of a lane may touch (lk_block_inside)
+    LKStart s;
+    if (!lk_level_start(p0x, p0y, level, top_level, WIN, I, nxo, nyo, status, err, s)) return;
+    const float half = s.half;
+    const int ipx = s.ipx, ipy = s.ipy;
+    float nx = s.nx, ny = s.ny;
+    const Win w0 = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
     n_setup++;
 
     int a11 = 0, a12 = 0, a22 = 0;
     uint2 tXa[NS], tYa[NS], tXb[NS], tYb[NS];  // template gradients of window rows 2r (a) and 2r + 1 (b)
     int cI[2] = {0, 0};
-    const bool fast_I = ipx >= 1 && ipy >= 1 && ipx + WIN + 3 <= I.w && ipy + WIN + 2 <= I.h && !(ipy == 1 && ipx < 4) &&
-                        !(ipy + WIN + 2 == I.h && ipx + WIN + 8 > I.w);
+    const bool fast_I = lk_block_inside(I, ipx - 1, ipy - 1, WIN + 3, reach);
     const unsigned w0t = pack16(w0.w00, w0.w01), w0b = pack16(w0.w10, w0.w11);
     const bool rowb = 2 * r + 1 < WIN;  // (row 2r is always a window row)
     // accumulate one strip of one window row: template samples vI, gradients vX / vY (already masked)
@@ -1988,7 +1682,7 @@ __device__ __forceinline__ void lko_level(const ImgDesc I, const ImgDesc J, int 
     if (fast_I) {
         // Lane r reads patch rows 2r .. 2r+3 (patch row 0 = image row ipy - 1) and builds V rows 2r, 2r+1, 2r+2 over the NC columns its strips share
         // (V = bilinear weights . patch, no rounding); V row 2r+3 is the neighbour's V row 2(r+1)+1 (DPP).  Window row w uses V rows w, w+1, w+2:
-        //   S = 3 (V_w + V_w+2) + 10 V_w+1,  dV = V_w+2 - V_w,  Ix = S[c+2] - S[c],  Iy = 3 (dV[c] + dV[c+2]) + 10 dV[c+1]   (see lkq_level)
+        //   S = 3 (V_w + V_w+2) + 10 V_w+1,  dV = V_w+2 - V_w,  Ix = S[c+2] - S[c],  Iy = 3 (dV[c] + dV[c+2]) + 10 dV[c+1]   (see LKQLevel)
         constexpr int NC = 4 * NS + 2;
         unsigned a[4][NS + 1];
 #pragma unroll
@@ -2052,7 +1746,7 @@ __device__ __forceinline__ void lko_level(const ImgDesc I, const ImgDesc J, int 
         }
     } else {
         // Window at the image border: the derivative image is 0 OUTSIDE the level, so the Scharr gradients of the integer pixels are built (packed
-        // int16 pairs (k, k+1), see lkq_level), zeroed outside, then interpolated like any other image.  Lane r holds pixel rows 2r-1 .. 2r+2 of the
+        // int16 pairs (k, k+1), see LKQLevel), zeroed outside, then interpolated like any other image.  Lane r holds pixel rows 2r-1 .. 2r+2 of the
         // window (image rows ipy + 2r - 1 ..) and gradient rows 2r, 2r+1; gradient / pixel row 2r+2 is lane r+1's first row (DPP).
         unsigned a[4][NS + 1];
 #pragma unroll
@@ -2117,29 +1811,21 @@ __device__ __forceinline__ void lko_level(const ImgDesc I, const ImgDesc J, int 
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    const float A11 = __fmul_rn(oct_sum_f32(a11), LK_FLT_SCALE), A12 = __fmul_rn(oct_sum_f32(a12), LK_FLT_SCALE),
-                A22 = __fmul_rn(oct_sum_f32(a22), LK_FLT_SCALE);
-    float D = __fsub_rn(__fmul_rn(A11, A22), __fmul_rn(A12, A12));
-    const float dAf = __fsub_rn(A11, A22);
-    const float disc = __fadd_rn(__fmul_rn(dAf, dAf), __fmul_rn(__fmul_rn(4.f, A12), A12));
-    const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(A22, A11), vh_sqrtf(disc)), (float)(2 * WIN * WIN));
-    if (minEig < 1e-4f || D < 1.1920929e-07f) {
+    LKSys S;
+    if (!lk_system(oct_sum_f32(a11), oct_sum_f32(a12), oct_sum_f32(a22), WIN, S)) {
         if (level == 0) status = 0;
         return;
     }
-    D = __fdiv_rn(1.f, D);
 
-    nx = __fsub_rn(nx, half); ny = __fsub_rn(ny, half);
     float pdx = 0.f, pdy = 0.f;
     for (int it = 0; it < max_count; it++) {
         const int inx = vh_floor(nx), iny = vh_floor(ny);
-        if (inx < -WIN || inx >= J.w || iny < -WIN || iny >= J.h) {
+        if (lk_outside(inx, iny, WIN, J)) {
             if (level == 0) status = 0;
             break;
         }
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny)));
-        const bool fast = J.pad >= VH_LV_PAD || (inx >= 0 && iny >= 0 && inx + WIN + 2 <= J.w && iny + WIN + 1 <= J.h && !(iny == 0 && inx < 3) &&
-                                                 !(iny + WIN + 1 == J.h && inx + WIN + 9 > J.w));
+        const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);
         n_iter++;
         unsigned pa01[NS], pa23[NS], pb01[NS], pb23[NS];
         lko_sample_rows<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, pa01, pa23, pb01, pb23);
@@ -2151,28 +1837,16 @@ __device__ __forceinline__ void lko_level(const ImgDesc I, const ImgDesc J, int 
             b1 = dot2(pb23[j], tXb[j].y, dot2(pb01[j], tXb[j].x, b1));
             b2 = dot2(pb23[j], tYb[j].y, dot2(pb01[j], tYb[j].x, b2));
         }
-        const float fb1 = __fmul_rn(oct_sum_f32(b1), LK_FLT_SCALE), fb2 = __fmul_rn(oct_sum_f32(b2), LK_FLT_SCALE);
-        const float dx = __fmul_rn(__fsub_rn(__fmul_rn(A12, fb2), __fmul_rn(A22, fb1)), D);
-        const float dy = __fmul_rn(__fsub_rn(__fmul_rn(A12, fb1), __fmul_rn(A11, fb2)), D);
-        nx = __fadd_rn(nx, dx); ny = __fadd_rn(ny, dy);
-        nxo = __fadd_rn(nx, half); nyo = __fadd_rn(ny, half);
-        if (__dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy)) <= eps2) break;
-        if (it > 0 && fabsf(__fadd_rn(dx, pdx)) < 0.01f && fabsf(__fadd_rn(dy, pdy)) < 0.01f) {
-            nxo = __fsub_rn(nxo, __fmul_rn(dx, 0.5f));
-            nyo = __fsub_rn(nyo, __fmul_rn(dy, 0.5f));
-            break;
-        }
-        pdx = dx; pdy = dy;
+        if (lk_step(S, oct_sum_f32(b1), oct_sum_f32(b2), half, it, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
     }
 
     if (status && level == 0) {
-        const float fx = __fsub_rn(nxo, half), fy = __fsub_rn(nyo, half);
-        const int inx = vh_floor(fx), iny = vh_floor(fy);
-        if (inx < -WIN || inx >= J.w || iny < -WIN || iny >= J.h) { status = 0; return; }
+        float fx, fy;
+        int inx, iny;
+        if (!lk_final_origin(nxo, nyo, half, WIN, J, fx, fy, inx, iny)) { status = 0; return; }
         if (!want_err) return;
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
-        const bool fast = J.pad >= VH_LV_PAD || (inx >= 0 && iny >= 0 && inx + WIN + 2 <= J.w && iny + WIN + 1 <= J.h && !(iny == 0 && inx < 3) &&
-                                                 !(iny + WIN + 1 == J.h && inx + WIN + 9 > J.w));
+        const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);
         unsigned pa01[NS], pa23[NS], pb01[NS], pb23[NS], ia01[NS], ia23[NS], ib01[NS], ib23[NS];
         lko_sample_rows<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, pa01, pa23, pb01, pb23);
         lko_sample_rows<NS, WIN>(I, ipx, ipy, r, fast_I || I.pad >= VH_LV_PAD, w0t, w0b, ia01, ia23, ib01, ib23);
@@ -2189,20 +1863,8 @@ __device__ __forceinline__ void lko_level(const ImgDesc I, const ImgDesc J, int 
                 se += (c < cnt && rowb) ? (db[c] < 0 ? -db[c] : db[c]) : 0;
             }
         }
-        err = __fmul_rn(oct_sum_f32(se), __fdiv_rn(1.f, (float)(32 * WIN * WIN)));
+        err = lk_err_of(oct_sum_f32(se), WIN);
     }
-}
-
-template <int WIN>
-__device__ __forceinline__ void lko_track(const PyrDesc& PI, const PyrDesc& PJ, int max_count, double eps2, float px, float py, float& ox,
-                                          float& oy, int& status, float& err, int r, int& n_iter, int& n_setup, bool want_err)
-{
-    const int nl = min(PI.nlevels, PJ.nlevels);
-    status = 1;
-    err = 0.f;
-    ox = 0.f; oy = 0.f;
-    for (int level = nl - 1; level >= 0; level--)
-        lko_level<WIN>(PI.lv[level], PJ.lv[level], level, nl - 1, max_count, eps2, px, py, ox, oy, status, err, r, n_iter, n_setup, want_err);
 }
 
 template <int WIN>
@@ -2211,55 +1873,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
     static_assert(WIN == 15, "8 lanes x 2 rows: row 15 is the dummy that feeds nothing");
     unsigned blk_x, blk_y;
     lk_block_xy<true>(blk_x, blk_y, grp);
-    const LKJob& job = *reinterpret_cast<const LKJob*>(reinterpret_cast<const char*>(job_tab) + (size_t)blk_y * tab_stride);
-    const int n = LK_N_OF(job);
+    const LKJob& job = lk_job_row(job_tab, tab_stride, blk_y);
     const int slot = (int)blk_x * 8 + (threadIdx.x >> 3);
-    if (slot >= n) return;  // whole 8-lane groups leave together
-    const int pt = job.order ? ((gptr_i32)job.order)[slot] : slot;  // launch slot -> point (LKJob::order)
-    const int r = threadIdx.x & 7;
-
-    const float qx = ((gptr_f32)job.p_in)[2 * pt], qy = ((gptr_f32)job.p_in)[2 * pt + 1];
-    const float px = __fsub_rn(__fmul_rn(qx, job.in_scale), job.in_off[0]);
-    const float py = __fsub_rn(__fmul_rn(qy, job.in_scale), job.in_off[1]);
-
-    float fx, fy, err;
-    int st, n_iter = 0, n_setup = 0;
-    lko_track<WIN>(job.I, job.J, job.max_count, job.eps2, px, py, fx, fy, st, err, r, n_iter, n_setup, job.err_out != nullptr);
-    float fbe = 0.f;
-    if (job.fbt >= 0.f) {
-        float bx = 0.f, by = 0.f, e2;
-        int st2 = 0;
-        if (st || job.fbe_out) lko_track<WIN>(job.J, job.I, job.max_count, job.eps2, fx, fy, bx, by, st2, e2, r, n_iter, n_setup, false);
-        const float ddx = __fsub_rn(px, bx), ddy = __fsub_rn(py, by);
-        fbe = vh_sqrtf(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)));
-        st = st && st2 && (fbe < job.fbt);
-    }
-    if (r == 0) {
-        float ox, oy;
-        if (job.out_mode == VH_OUT_SCALE) {
-            ox = __fdiv_rn(fx, job.out_scale);
-            oy = __fdiv_rn(fy, job.out_scale);
-        } else {
-            const float ax = __fadd_rn(fx, job.in_off[0]), ay = __fadd_rn(fy, job.in_off[1]);
-            if (job.out_mode == VH_OUT_TRANSLATE) {
-                ox = __fadd_rn(ax, job.out_off[0]);
-                oy = __fadd_rn(ay, job.out_off[1]);
-            } else {
-                ox = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[0]), __fmul_rn(ay, job.T[2])), job.T[4]);
-                oy = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[1]), __fmul_rn(ay, job.T[3])), job.T[5]);
-            }
-        }
-        job.p_out[2 * pt] = ox;
-        job.p_out[2 * pt + 1] = oy;
-        job.v_out[pt] = (uint8_t)(st != 0);
-        if (job.err_out) job.err_out[pt] = err;
-        if (job.fbe_out) job.fbe_out[pt] = fbe;
-        if (job.praw_out) { job.praw_out[2 * pt] = fx; job.praw_out[2 * pt + 1] = fy; }
-        if (job.stats) {
-            unsigned long long* st = job.stats + (size_t)((unsigned)slot & (VH_LK_STAT_SLOTS - 1)) * 16;  // (counters spread over VH_LK_STAT_SLOTS lines: see StreamWS::lk_stats)
-            atomicAdd(&st[0], (unsigned long long)n_iter);
-            atomicAdd(&st[1], (unsigned long long)n_setup);
-        }
+    int pt;
+    float px, py;
+    if (!lk_slot_start(job, slot, pt, px, py)) return;  // whole 8-lane groups leave together
+    LKOLevel<WIN> lf{job.max_count, job.eps2, (int)(threadIdx.x & 7), 0, 0};
+    LKResult R;
+    lk_solve(job, px, py, lf, R);
+    if (lf.r == 0) {
+        lk_store_track(job, pt, R.fx, R.fy, R.st, R.err, R.fbe);
+        lk_add_stats(job, (unsigned)slot, lf.n_iter, lf.n_setup);
     }
 }
 

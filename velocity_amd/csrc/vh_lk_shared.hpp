@@ -1,0 +1,242 @@
+// What every pyramidal-LK kernel of vh_lk.hip shares: the per-track scalar arithmetic of one level, the loop over the
+// levels, and a kernel's prologue and epilogue.  The kernels differ only in how they sample a window and reduce a window sum; everything a track
+// computes FROM the reduced sums is defined here once, so the float sequence per track -- and with it the bit-identity of the implementations --
+// holds by construction.  Every function keeps an explicit __f*_rn / __d*_rn call per rounding: nothing here may be contracted or reassociated.
+// Also here, because both sides use them: the fixed-point scales (W_BITS, LK_FLT_SCALE), the bilinear weights of a window origin (Win,
+// bilinear_weights: every level computes them from the origins the functions below return) and the one-rounding int64 -> float32 conversion of a
+// window sum (i64_to_f32).
+#pragma once
+#include "vh_kernels.hpp"
+#include "vh_valu.hpp"
+
+#define W_BITS 14
+#define LK_FLT_SCALE (1.f / (1 << 20))
+
+// The per-track inputs of a launch (count, launch order, start points) hang off pointers that were themselves loaded from the job descriptor: read
+// through a GLOBAL pointer (where the address is workgroup uniform they then come through the scalar cache), not through the generic one hipcc
+// assumes -- a workgroup otherwise starts with a chain of three dependent flat loads before its first image row is requested
+typedef const int __attribute__((address_space(1)))* gptr_i32;
+typedef const float __attribute__((address_space(1)))* gptr_f32;
+#define LK_N_OF(job) ((job).n_ptr ? *(gptr_i32)(job).n_ptr : (job).n)
+
+// (float)v for |v| < 2^53 with ONE rounding: hi * 2^32 + lo is exact in float64, the final conversion rounds once -- identical to the
+// int64 -> float32 conversion, in 5 instructions instead of the compiler's ~15-instruction sequence
+__device__ __forceinline__ float i64_to_f32(long long v)
+{
+    const double d = __dadd_rn(__dmul_rn((double)(int)(v >> 32), 4294967296.0), (double)(unsigned)(v & 0xffffffffll));
+    return (float)d;
+}
+
+struct Win {
+    int w00, w01, w10, w11;
+};
+
+__device__ __forceinline__ Win bilinear_weights(float a, float b)
+{
+    Win w;
+    const float ia = __fsub_rn(1.f, a), ib = __fsub_rn(1.f, b);
+    w.w00 = vh_round(__fmul_rn(__fmul_rn(ia, ib), (float)(1 << W_BITS)));
+    w.w01 = vh_round(__fmul_rn(__fmul_rn(a, ib), (float)(1 << W_BITS)));
+    w.w10 = vh_round(__fmul_rn(__fmul_rn(ia, b), (float)(1 << W_BITS)));
+    w.w11 = (1 << W_BITS) - w.w00 - w.w01 - w.w10;
+    return w;
+}
+
+// ---- one level of one track ------------------------------------------------------------------------------------------------------------------------
+
+// a window whose origin is the integer pixel (ix, iy) lies wholly outside the level
+__device__ __forceinline__ bool lk_outside(int ix, int iy, int win, const ImgDesc& im) { return ix < -win || ix >= im.w || iy < -win || iy >= im.h; }
+
+// The aligned dword row reads of an e x e pixel block at (x, y) may run past either end of a row (`reach` bytes from x at most): harmless inside the
+// level, excluded where they would leave it (first row to the left, last row to the right).  The template patch of a window at (ipx, ipy) is the block
+// e = win + 3 at (ipx - 1, ipy - 1) (then the V identity of strip_setup_linear holds as well), a search window at (inx, iny) the block e = win + 1.
+__device__ __forceinline__ bool lk_block_inside(const ImgDesc& im, int x, int y, int e, int reach)
+{
+    return x >= 0 && y >= 0 && x + e + 1 <= im.w && y + e <= im.h && !(y == 0 && x < 3) && !(y + e == im.h && x + reach > im.w);
+}
+
+// Level start: the template origin (px, py) with its integer part (ipx, ipy), and the predicted origin (nx, ny) of the search window; (nxo, nyo), the
+// track's position on the level (window CENTRE), is carried from level to level.
+struct LKStart {
+    float half, px, py, nx, ny;
+    int ipx, ipy;
+};
+// false: the template origin lies outside the level -- the level is skipped, and on level 0 the track is dead
+__device__ __forceinline__ bool lk_level_start(float p0x, float p0y, int level, int top_level, int win, const ImgDesc& I, float& nxo, float& nyo,
+                                               int& status, float& err, LKStart& s)
+{
+    s.half = (float)(win - 1) * 0.5f;
+    const float lscale = __uint_as_float((unsigned)(127 - level) << 23);  // 2^-level exactly = (float)(1. / (1 << level)), without the f64 division
+    const float cx = __fmul_rn(p0x, lscale), cy = __fmul_rn(p0y, lscale);
+    if (level != top_level) { nxo = __fmul_rn(nxo, 2.f); nyo = __fmul_rn(nyo, 2.f); }
+    else { nxo = cx; nyo = cy; }
+    s.px = __fsub_rn(cx, s.half); s.py = __fsub_rn(cy, s.half);
+    s.nx = __fsub_rn(nxo, s.half); s.ny = __fsub_rn(nyo, s.half);
+    s.ipx = vh_floor(s.px); s.ipy = vh_floor(s.py);
+    if (lk_outside(s.ipx, s.ipy, win, I)) {
+        if (level == 0) { status = 0; err = 0.f; }
+        return false;
+    }
+    return true;
+}
+
+// The 2x2 system of a level from the three window sums of Ix Ix, Ix Iy, Iy Iy (exact integers, converted once to float32): false when the
+// min-eigenvalue / determinant gate rejects the window.  iD = 1 / determinant.
+struct LKSys {
+    float A11, A12, A22, iD;
+};
+__device__ __forceinline__ bool lk_system(float s11, float s12, float s22, int win, LKSys& S)
+{
+    S.A11 = __fmul_rn(s11, LK_FLT_SCALE); S.A12 = __fmul_rn(s12, LK_FLT_SCALE); S.A22 = __fmul_rn(s22, LK_FLT_SCALE);
+    const float D = __fsub_rn(__fmul_rn(S.A11, S.A22), __fmul_rn(S.A12, S.A12));
+    const float dA = __fsub_rn(S.A11, S.A22);
+    const float disc = __fadd_rn(__fmul_rn(dA, dA), __fmul_rn(__fmul_rn(4.f, S.A12), S.A12));
+    const float minEig = __fdiv_rn(__fsub_rn(__fadd_rn(S.A22, S.A11), vh_sqrtf(disc)), (float)(2 * win * win));
+    if (minEig < 1e-4f || D < 1.1920929e-07f) return false;
+    S.iD = __fdiv_rn(1.f, D);
+    return true;
+}
+__device__ __forceinline__ bool lk_system(long long s11, long long s12, long long s22, int win, LKSys& S)
+{
+    return lk_system(i64_to_f32(s11), i64_to_f32(s12), i64_to_f32(s22), win, S);
+}
+
+// One Newton update from the two window sums of (J - I) Ix, (J - I) Iy of iteration `it`: moves the search origin (nx, ny) and the position
+// (nxo, nyo); true when the level is finished (step below eps, or the +-0.01 oscillation rule, which takes half of the last step back).
+__device__ __forceinline__ bool lk_step(const LKSys& S, float sb1, float sb2, float half, int it, double eps2, float& nx, float& ny, float& nxo,
+                                        float& nyo, float& pdx, float& pdy)
+{
+    const float b1 = __fmul_rn(sb1, LK_FLT_SCALE), b2 = __fmul_rn(sb2, LK_FLT_SCALE);
+    const float dx = __fmul_rn(__fsub_rn(__fmul_rn(S.A12, b2), __fmul_rn(S.A22, b1)), S.iD);
+    const float dy = __fmul_rn(__fsub_rn(__fmul_rn(S.A12, b1), __fmul_rn(S.A11, b2)), S.iD);
+    nx = __fadd_rn(nx, dx); ny = __fadd_rn(ny, dy);
+    nxo = __fadd_rn(nx, half); nyo = __fadd_rn(ny, half);
+    if (__dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy)) <= eps2) return true;
+    if (it > 0 && fabsf(__fadd_rn(dx, pdx)) < 0.01f && fabsf(__fadd_rn(dy, pdy)) < 0.01f) {
+        nxo = __fsub_rn(nxo, __fmul_rn(dx, 0.5f));
+        nyo = __fsub_rn(nyo, __fmul_rn(dy, 0.5f));
+        return true;
+    }
+    pdx = dx; pdy = dy;
+    return false;
+}
+__device__ __forceinline__ bool lk_step(const LKSys& S, long long sb1, long long sb2, float half, int it, double eps2, float& nx, float& ny,
+                                        float& nxo, float& nyo, float& pdx, float& pdy)
+{
+    return lk_step(S, i64_to_f32(sb1), i64_to_f32(sb2), half, it, eps2, nx, ny, nxo, nyo, pdx, pdy);
+}
+
+// After the iterations of level 0: the final window origin (fx, fy) with its integer part, where the err pass samples J.  False: it left the level
+// (the track is dead).
+__device__ __forceinline__ bool lk_final_origin(float nxo, float nyo, float half, int win, const ImgDesc& J, float& fx, float& fy, int& inx, int& iny)
+{
+    fx = __fsub_rn(nxo, half); fy = __fsub_rn(nyo, half);
+    inx = vh_floor(fx); iny = vh_floor(fy);
+    return !lk_outside(inx, iny, win, J);
+}
+__device__ __forceinline__ float lk_err_of(float sum_abs, int win) { return __fmul_rn(sum_abs, __fdiv_rn(1.f, (float)(32 * win * win))); }
+
+// ---- one track --------------------------------------------------------------------------------------------------------------------------------------
+
+// All levels of one track, coarse to fine.  `lf` is a kernel's level functor: lf(I, J, level, top_level, px, py, ox, oy, status, err, want_err) solves one
+// level and keeps what the kernel needs from level to level (its lanes' place in the window, LDS pointers, the statistics counts) as its state.
+template <class LevelFn>
+__device__ __forceinline__ void lk_track(const PyrDesc& PI, const PyrDesc& PJ, float px, float py, float& ox, float& oy, int& status, float& err,
+                                         bool want_err, LevelFn& lf)
+{
+    const int nl = min(PI.nlevels, PJ.nlevels);
+    status = 1;
+    err = 0.f;
+    ox = 0.f; oy = 0.f;
+    for (int level = nl - 1; level >= 0; level--) lf(PI.lv[level], PJ.lv[level], level, nl - 1, px, py, ox, oy, status, err, want_err);
+}
+
+// forward-backward gate (KLT.py:50): returns fbe, the distance between the start point and where the backward pass ended
+__device__ __forceinline__ float lk_fb_gate(float px, float py, float bx, float by, float fbt, int st2, int& st)
+{
+    const float ddx = __fsub_rn(px, bx), ddy = __fsub_rn(py, by);
+    const float fbe = vh_sqrtf(__fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)));
+    st = st && st2 && (fbe < fbt);
+    return fbe;
+}
+
+// what a track returns: the forward result in LK image coordinates, its status after the gate, err of the forward pass, forward-backward error
+struct LKResult {
+    float fx, fy, err, fbe;
+    int st;
+};
+// Forward pass, then (fbt >= 0) the backward pass from its result and the gate.
+// Forward status 0: `v = v & v2 & (fbe < fbt)` is 0 whatever the backward pass finds, and the point returned is the forward one, so the backward pass
+// is skipped unless the caller asked for fbe itself (vh_pyr_lk); in the 4- / 8-tracks-per-wavefront kernels the dead tracks' lanes sit out the pass
+// (exec mask), and a wavefront whose tracks are all dead skips it.  (k_lk3 runs the two passes as ONE copy of the track code in a loop.)
+template <class LevelFn>
+__device__ __forceinline__ void lk_solve(const LKJob& job, float px, float py, LevelFn& lf, LKResult& R)
+{
+    lk_track(job.I, job.J, px, py, R.fx, R.fy, R.st, R.err, job.err_out != nullptr, lf);
+    R.fbe = 0.f;
+    if (job.fbt >= 0.f) {
+        float bx = 0.f, by = 0.f, e2;
+        int st2 = 0;
+        if (R.st || job.fbe_out) lk_track(job.J, job.I, R.fx, R.fy, bx, by, st2, e2, false, lf);
+        R.fbe = lk_fb_gate(px, py, bx, by, job.fbt, st2, R.st);
+    }
+}
+
+// ---- kernel prologue and epilogue ---------------------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ const LKJob& lk_job_row(const void* job_tab, size_t tab_stride, unsigned row)
+{
+    return *reinterpret_cast<const LKJob*>(reinterpret_cast<const char*>(job_tab) + (size_t)row * tab_stride);
+}
+
+// Launch slot -> point (LKJob::order) and its start point in LK image coordinates; false: the slot is beyond the job's tracks.
+// UNIFORM: the slot is the same for the whole workgroup, and the point index and the start position come back as SCALARS (readfirstlane).
+template <bool UNIFORM = false>
+__device__ __forceinline__ bool lk_slot_start(const LKJob& job, int slot, int& pt, float& px, float& py)
+{
+    if (slot >= LK_N_OF(job)) return false;
+    pt = job.order ? ((gptr_i32)job.order)[slot] : slot;
+    if (UNIFORM) pt = __builtin_amdgcn_readfirstlane(pt);
+    const float qx = ((gptr_f32)job.p_in)[2 * pt], qy = ((gptr_f32)job.p_in)[2 * pt + 1];
+    px = __fsub_rn(__fmul_rn(qx, job.in_scale), job.in_off[0]);
+    py = __fsub_rn(__fmul_rn(qy, job.in_scale), job.in_off[1]);
+    if (UNIFORM) {
+        px = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(px)));
+        py = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(py)));
+    }
+    return true;
+}
+
+// map-back of one track to frame coordinates (LKJob::out_mode) and its output stores: ONE thread per track calls this
+__device__ __forceinline__ void lk_store_track(const LKJob& job, int pt, float fx, float fy, int st, float err, float fbe)
+{
+    float ox, oy;
+    if (job.out_mode == VH_OUT_SCALE) {
+        ox = __fdiv_rn(fx, job.out_scale);
+        oy = __fdiv_rn(fy, job.out_scale);
+    } else {
+        const float ax = __fadd_rn(fx, job.in_off[0]), ay = __fadd_rn(fy, job.in_off[1]);
+        if (job.out_mode == VH_OUT_TRANSLATE) {
+            ox = __fadd_rn(ax, job.out_off[0]);
+            oy = __fadd_rn(ay, job.out_off[1]);
+        } else {
+            ox = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[0]), __fmul_rn(ay, job.T[2])), job.T[4]);
+            oy = __fadd_rn(__fadd_rn(__fmul_rn(ax, job.T[1]), __fmul_rn(ay, job.T[3])), job.T[5]);
+        }
+    }
+    job.p_out[2 * pt] = ox;
+    job.p_out[2 * pt + 1] = oy;
+    job.v_out[pt] = (uint8_t)(st != 0);
+    if (job.err_out) job.err_out[pt] = err;
+    if (job.fbe_out) job.fbe_out[pt] = fbe;
+    if (job.praw_out) { job.praw_out[2 * pt] = fx; job.praw_out[2 * pt + 1] = fy; }
+}
+
+// statistics of the tracks one thread answers for (counters spread over VH_LK_STAT_SLOTS lines: see StreamWS::lk_stats)
+__device__ __forceinline__ void lk_add_stats(const LKJob& job, unsigned slot, int n_iter, int n_setup)
+{
+    if (!job.stats) return;
+    unsigned long long* st = job.stats + (size_t)(slot & (VH_LK_STAT_SLOTS - 1)) * 16;
+    atomicAdd(&st[0], (unsigned long long)n_iter);
+    atomicAdd(&st[1], (unsigned long long)n_setup);
+}
