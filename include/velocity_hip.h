@@ -284,6 +284,17 @@ VH_API int vh_match_affine(vh_ctx* ctx, const uint8_t* im1, const uint8_t* im2, 
 /* scratch of vh_match_affine (level images, masks, box sums, keypoints, descriptors; about 20 bytes per frame pixel) and of the detector it drives:
  * created by the first call, or here -- e.g. before a stream capture, inside which it cannot grow (-6). */
 VH_API int vh_match_reserve(vh_ctx* ctx, int w, int h, const vh_match_params* params_host, void* stream);
+/* (vh_version >= 109) vh_match_affine for nb frame pairs of ONE frame size as one launch sequence: every matcher kernel runs once with the pair as a
+ * grid dimension, the detector makes one pass over the 2 x levels x nb level images, RANSAC is one launch over nb jobs (vh_match_affine is the batch of
+ * one).  im1_host, im2_host, p1_host: HOST arrays of nb device pointers, n_host: host int[nb].  Outputs (device): M double[nb][6], inl uint8[nb][cap],
+ * pairs float[nb][cap][4] (may be NULL), info int[nb][4]; each pair's are bit-identical to vh_match_affine on that pair alone.
+ * vh_match_stage_ptrs then shows the LAST pair of the call.
+ * -1 (nothing queued): what vh_match_affine refuses, nb < 1, nb x 2 x levels > 65535, a null entry in a pointer array, an n below 1. */
+VH_API int vh_match_affine_batch(vh_ctx* ctx, int nb, const uint8_t* const* im1_host, const uint8_t* const* im2_host, int w, int h, int stride1,
+                                 int stride2, const float* const* p1_host, const int* n_host, const vh_match_params* params_host, double* M, uint8_t* inl,
+                                 float* pairs, int* info, void* stream);
+/* vh_match_reserve for calls of up to nb pairs (the scratch is per pair: about 20 bytes per frame pixel, and 34 more in the detector) */
+VH_API int vh_match_reserve_batch(vh_ctx* ctx, int nb, int w, int h, const vh_match_params* params_host, void* stream);
 /* device pointers to the intermediate results of the last vh_match_affine call of a context (parity tests).  Image 0 is the query (im1), 1 the train image */
 typedef struct {
     const float* kp[2][8];    /* detector output of every level, level coordinates (x, y), cnt[image][level] rows          */
@@ -352,6 +363,20 @@ VH_API int vh_session_step(vh_session* s, const uint8_t* const* frames_dev, floa
 VH_API int vh_session_step_v(vh_session* s, const uint8_t* const* frames_dev, const float* time_s_dev, const float* frame_no_dev,
                              void* stream);
 VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
+/* (vh_version >= 109) the recovery branch of KLTmain (utils/KLT.py:130-133) inside the session; default OFF: a step then queues exactly the launches it
+ * always did and a stream whose coarse stage fails reports klt_flags & 1 and goes on with what the blind fine stage kept.
+ * on != 0 (params_host: the matcher's parameters, NULL = defaults) creates everything the branch needs -- a private context of the session's frame
+ * size, the matcher's scratch for up to 16 pairs, a pinned host record -- so no step allocates.  Every step then, between KLTmain and the bookkeeping:
+ *   - reads {klt_flags, n_cur} of every stream back: ONE small device-to-host copy and ONE hipStreamSynchronize PER STEP, whether a stream failed or not.
+ *     The host therefore no longer runs ahead of the device; leave the option off for clips that do not need it.
+ *   - for the streams with klt_flags & 1 and n_cur > 0: vh_match_affine_batch(im0, frame, p, n_cur) (at most 16 pairs per call), a second
+ *     synchronisation to read status and M, and for every stream with a model KLTregional(im0, im, p0, T23.T, lk_fine, fbt = 0.3) into that stream's KLTmain
+ *     outputs.  klt_flags gets bit 1 (the recovery ran) and, with a model, bit 2.  Without a model the blind fine stage's result stands.
+ * A step of a session with the option on CANNOT be captured into a graph (it waits for the stream): under a stream capture it returns -6 before
+ * anything is queued.  on == 0 turns the option off again and keeps what was created. */
+VH_API int vh_session_set_fallback(vh_session* s, int on, const vh_match_params* params_host);
+/* counts_host int[batch][2]: steps of each stream (since its vh_session_init) in which the recovery ran / in which it found a model */
+VH_API int vh_session_recoveries(vh_session* s, int* counts_host);
 /* Packed track state of every stream for the cross-GPU exchange (RCCL all-gather, DESIGN.md "multi-GPU"):
  * out = device float32 [batch][8 + 3*n0]: {n_cur, n_pose, frame_i, klt_flags, t[3], res | p (n0 x 2) | ids (n0, int32 bits)} */
 /* Fused frame ingest for every stream of the session (vidExample.py:91 + KLT.py:111-113 in ONE pass over the BGR frames): bgr_frames_dev / gray_frames_dev =

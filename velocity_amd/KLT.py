@@ -94,6 +94,33 @@ def _match_call(im1, im2, p1, params):
     return M, inl, pairs, info
 
 
+def _match_call_batch(ims1, ims2, ps1, params):
+    """One vh_match_affine_batch call over len(ims1) frame pairs of one size -> (M [nb, 6] f64, inl [nb, cap] u8, pairs [nb, cap, 4] f32, info [nb, 4] i32)
+    as device tensors; nothing is read back.  Every pair's rows equal what _match_call returns for it alone."""
+    torch = L.torch_cuda()
+    nb = len(ims1)
+    if nb < 1 or len(ims2) != nb or len(ps1) != nb:
+        raise ValueError("need as many second frames and point sets as first frames, at least one")
+    a = [L.img_dev(x) for x in ims1]
+    b = [L.img_dev(x) for x in ims2]
+    h, w, sa, sb = a[0][1], a[0][2], a[0][3], b[0][3]
+    if any(x[1:] != (h, w, sa) for x in a) or any(x[1:] != (h, w, sb) for x in b):
+        raise ValueError("the frames of a batch must share one shape and row stride")
+    p = [L.to_dev(x, torch.float32).reshape(-1, 2) for x in ps1]
+    mp = L.match_params(params)
+    cap = mp.levels * mp.query_per_level
+    ws = L.workspace(w, h, cap)
+    M = torch.zeros((nb, 6), dtype=torch.float64, device="cuda")
+    inl = torch.zeros((nb, max(cap, 1)), dtype=torch.uint8, device="cuda")
+    pairs = torch.zeros((nb, max(cap, 1), 4), dtype=torch.float32, device="cuda")
+    info = torch.zeros((nb, 4), dtype=torch.int32, device="cuda")
+    tab = lambda ts: C.cast((C.c_void_p * nb)(*[t.data_ptr() for t in ts]), C.c_void_p)  # noqa: E731
+    n = (C.c_int * nb)(*[x.shape[0] for x in p])
+    L.check(ws.lib.vh_match_affine_batch(ws.handle, nb, tab([x[0] for x in a]), tab([x[0] for x in b]), w, h, sa, sb, tab(p), n, C.byref(mp), L.dptr(M),
+                                         L.dptr(inl), L.dptr(pairs), L.dptr(info), L.stream_ptr()), "vh_match_affine_batch")
+    return M, inl, pairs, info
+
+
 def estimateAffine2D_SURF(im1, im2, p1, scale=1.0, **params):
     """Stand-in for estimateAffine2D_SURF (utils/KLT.py:10-33): the affine im1 -> im2 from feature matches around the tracks p1 ->
     (T23 f64 [2,3] | None, inliers u8 [good,1]).  SURF itself is non-free: corners on five scales, binary descriptors, Hamming matching with the ratio

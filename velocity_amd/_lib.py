@@ -123,6 +123,10 @@ _SIGS = {
                                         C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, i32p, vp]),
     "vh_match_affine": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(MatchParams), vp, vp, vp, vp, vp]),
     "vh_match_reserve": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MatchParams), vp]),
+    "vh_match_affine_batch": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, C.POINTER(MatchParams), vp, vp, vp, vp, vp]),
+    "vh_match_reserve_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(MatchParams), vp]),
+    "vh_session_set_fallback": (C.c_int, [vp, C.c_int, C.POINTER(MatchParams)]),
+    "vh_session_recoveries": (C.c_int, [vp, i32p]),
     "vh_match_stage_ptrs": (C.c_int, [vp, C.POINTER(MatchStages)]),
     "vh_match_pairs": (C.c_int, [i32p]),
     "vh_match_launch_count": (C.c_longlong, []),

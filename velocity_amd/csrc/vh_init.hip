@@ -448,7 +448,7 @@ extern "C" VH_API int vh_frame0_init(vh_ctx* c, const uint8_t* im, int w, int h,
 // ---------------------------------------------------------------------------------------------------------------
 #define F0B_TW 64        // Harris / candidate tile: 64 x 16 pixels, 256 threads
 #define F0B_TH 16
-#define F0B_PIECE 32     // descriptors per upload (one kernel argument of 32 x 104 bytes)
+#define F0B_PIECE 16     // descriptors per upload (one kernel argument of 16 x 128 bytes; kernel arguments end at 4 KB)
 #define F0B_SEL_MAX 2048 // max_corners up to this: selected keys sorted in LDS; above: rocPRIM segmented sort
 #define F0B_WIN 2048     // k_f0b_spread: candidates per window (sorted in LDS)
 #define F0B_EMPTY 0xffffffffu
@@ -463,8 +463,13 @@ struct F0Clip {
     int boxa[4];
     float q[8];
     const uint8_t* mask;       // ROI-relative detection mask (NULL: none): pixels where it is 0 neither set the maximum nor become corners
-    int mstride, pad_;
+    int mstride;
+    int stride;                // row stride of the clip's frame
+    float* out;                // the clip's corner row (vh_frame0_init_batch: the 4 plate corners q go first)
+    int* n_out;                // the clip's corner count (NULL: only cnt[4 * clip + 2])
+    int max_corners, pad_;     // the clip's corner budget (the spacing and segmented-sort routes need one budget for the whole chunk)
 };
+static_assert(sizeof(F0Clip) == 128, "F0ClipPiece is sized by hand");
 struct F0ClipPiece {
     F0Clip c[F0B_PIECE];
 };
@@ -478,7 +483,7 @@ struct F0Shared {
 // a = sxx s2 / 2, b = sxy s2, c = syy s2 / 2, (a + c) - sqrt((a - c)^2 + b^2), every step rounded to float32).  REFLECT_101 is relative to the clip's
 // ROI: a halo entry holds the Sobel pair of the reflected pixel, as k_init_harris reads it.
 template <bool HARRIS>
-__global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, size_t st, int block, float s2, float kf, float* resp_base, unsigned* cnt)
+__global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, int block, float s2, float kf, float* resp_base, unsigned* cnt)
 {
     const F0Clip& C = tab[blockIdx.z];
     const int rw = C.rw, rh = C.rh, tx0 = blockIdx.x * F0B_TW, ty0 = blockIdx.y * F0B_TH;
@@ -486,6 +491,7 @@ __global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, size_t st
     __shared__ int2 g[(F0B_TH + 14) * (F0B_TW + 14)];
     const int r0 = block / 2, gw = F0B_TW + block - 1, gh = F0B_TH + block - 1;
     const uint8_t* im = C.roi;
+    const size_t st = (size_t)C.stride;
     for (int i = threadIdx.x; i < gw * gh; i += 256) {
         const int ly = i / gw, lx = i - ly * gw;
         const int x = vh_reflect101(tx0 - r0 + lx, rw), y = vh_reflect101(ty0 - r0 + ly, rh);
@@ -637,25 +643,25 @@ __device__ __forceinline__ void f0b_lds_sort_desc(unsigned long long* s, unsigne
         }
 }
 
-// Where the detector writes clip b's corners: out + b * ostride, behind the 4 plate corners q when qhead (vh_frame0_init_batch: p = concatenate((q,
-// corners)), vidExample.py:116), from the start otherwise (vh_good_features2).  The count goes to cnt[4 * clip + 2] and, when n_dev is set, n_dev[clip].
-__device__ __forceinline__ float* f0b_corner_row(const F0Clip& C, float* out, size_t ostride, int qhead, int b)
+// Where the detector writes a clip's corners: its row C.out, behind the 4 plate corners q when qhead (vh_frame0_init_batch: p = concatenate((q,
+// corners)), vidExample.py:116), from the start otherwise (vh_good_features2).  The count goes to cnt[4 * clip + 2] and, when set, *C.n_out.
+__device__ __forceinline__ float* f0b_corner_row(const F0Clip& C, int qhead)
 {
-    float* p = out + (size_t)b * ostride;
+    float* p = C.out;
     if (!qhead) return p;
     if (threadIdx.x < 8) p[threadIdx.x] = C.q[threadIdx.x];
     return p + 8;
 }
 
-// One workgroup per clip: K = min(candidates, max_corners); the keys >= the K-th largest (f0b_radix_select) are gathered and -- LDS_SORT -- sorted
-// descending in LDS and written as corners + the ROI origin (k_init_emit), or gathered into the clip's segment of `gsel` for the segmented sort.
+// One workgroup per clip: K = min(candidates, the budget) -- the clip's own when LDS_SORT, the chunk's otherwise; the keys >= the K-th largest
+// (f0b_radix_select) are gathered and -- LDS_SORT -- sorted descending in LDS and written as corners + the ROI origin (k_init_emit), or gathered into the clip's segment of `gsel` for the segmented sort.
 template <bool LDS_SORT>
-__global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int b0, int max_corners, const unsigned long long* keys_base, unsigned* cnt,
-                                                     float* out, size_t ostride, int qhead, int* n_dev, unsigned long long* gsel, int* seg_begin,
-                                                     int* seg_end)
+__global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int max_corners, const unsigned long long* keys_base, unsigned* cnt, int qhead,
+                                                     unsigned long long* gsel, int* seg_begin, int* seg_end)
 {
     const int clip = blockIdx.x, tid = threadIdx.x;
     const F0Clip& C = tab[clip];
+    if (LDS_SORT) max_corners = min(C.max_corners, F0B_SEL_MAX);
     __shared__ unsigned hist[256];
     __shared__ unsigned long long s_sel[LDS_SORT ? F0B_SEL_MAX : 1];
     __shared__ unsigned s_bin, s_krem, s_done, s_n;
@@ -674,10 +680,10 @@ __global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int b0, 
             if (slot < K) dst[slot] = k;
         }
     }
-    float* p = f0b_corner_row(C, out, ostride, qhead, b0 + clip);
+    float* p = f0b_corner_row(C, qhead);
     if (tid == 0) {
         cnt[4 * clip + 2] = K;
-        if (n_dev) n_dev[clip] = (int)K;
+        if (C.n_out) *C.n_out = (int)K;
     }
     if (!LDS_SORT) {
         if (tid == 0) { seg_begin[clip] = clip * max_corners; seg_end[clip] = clip * max_corners + (int)K; }
@@ -692,15 +698,14 @@ __global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int b0, 
 }
 
 // corners of the segmented-sort route (max_corners > F0B_SEL_MAX), as k_init_emit
-__global__ __launch_bounds__(256) void k_f0b_emit(const F0Clip* tab, int b0, int max_corners, const unsigned long long* sorted, const unsigned* cnt,
-                                                  float* out, size_t ostride, int qhead)
+__global__ __launch_bounds__(256) void k_f0b_emit(const F0Clip* tab, int max_corners, const unsigned long long* sorted, const unsigned* cnt, int qhead)
 {
     const int clip = blockIdx.y;
     const unsigned i = blockIdx.x * 256 + threadIdx.x;
     if (i >= cnt[4 * clip + 2]) return;
     const F0Clip& C = tab[clip];
     const unsigned idx = (unsigned)(sorted[(size_t)clip * max_corners + i] & 0xffffffffull);
-    float* p = out + (size_t)(b0 + clip) * ostride + (qhead ? 8 : 0);
+    float* p = C.out + (qhead ? 8 : 0);
     p[2 * i] = __fadd_rn((float)(idx % (unsigned)C.rw), C.offx);
     p[2 * i + 1] = __fadd_rn((float)(idx / (unsigned)C.rw), C.offy);
 }
@@ -715,8 +720,8 @@ __global__ __launch_bounds__(256) void k_f0b_emit(const F0Clip* tab, int b0, int
 //   - against the earlier lanes of the chunk: a 64-bit conflict mask per lane from positions broadcast by v_readlane,
 //   - then a wave-uniform serial pass over the surviving lanes in order accepts a lane iff its mask meets no lane accepted before it.
 // The result is exactly the sequential greedy walk.
-__global__ __launch_bounds__(1024) void k_f0b_spread(const F0Clip* tab, int b0, int max_corners, const unsigned long long* keys_base, unsigned* grid_base,
-                                                     unsigned* cnt, float* out, size_t ostride, int qhead, int* n_dev, int cell, int slots, int lim)
+__global__ __launch_bounds__(1024) void k_f0b_spread(const F0Clip* tab, int max_corners, const unsigned long long* keys_base, unsigned* grid_base,
+                                                     unsigned* cnt, int qhead, int cell, int slots, int lim)
 {
     const int clip = blockIdx.x, tid = threadIdx.x;
     const F0Clip& C = tab[clip];
@@ -729,7 +734,7 @@ __global__ __launch_bounds__(1024) void k_f0b_spread(const F0Clip* tab, int b0, 
     unsigned* grid = grid_base + C.seg;
     const int gw = (rw + cell - 1) / cell, gh = (rh + cell - 1) / cell;
     for (unsigned i = tid; i < (unsigned)(gw * gh * slots); i += 1024) grid[i] = F0B_EMPTY;
-    float* p = f0b_corner_row(C, out, ostride, qhead, b0 + clip);
+    float* p = f0b_corner_row(C, qhead);
     if (tid == 0) s_acc = 0;
     __syncthreads();
     unsigned long long hi = ~0ull;  // the keys still to walk are those below hi
@@ -810,7 +815,7 @@ __global__ __launch_bounds__(1024) void k_f0b_spread(const F0Clip* tab, int b0, 
     }
     if (tid == 0) {
         cnt[4 * clip + 2] = kept;
-        if (n_dev) n_dev[clip] = (int)kept;
+        if (C.n_out) *C.n_out = (int)kept;
     }
 }
 
@@ -931,8 +936,6 @@ void vh_init_batch_scratch_free(vh_ctx* c)
     if (c) batch_release(c->init_batch);
 }
 
-int vh_init_batch_reserve_one(vh_ctx* c, size_t pixels, hipStream_t s) { return batch_reserve(c, 1, pixels, s); }
-
 extern "C" VH_API int vh_init_reserve_batch(vh_ctx* c, int nb, int w, int h, void* stream)
 {
     if (!c || nb < 1 || w < 1 || h < 1) return vh_fail(-1, "vh_init_reserve_batch: bad arguments");
@@ -963,38 +966,59 @@ static int f0b_detect_check(const F0Detect& D, int w, int h, const char* fn)
     return 0;
 }
 
-// the detector stages of one chunk of n clips (descriptors at d_tab, counters zeroed, frames of row stride `stride`); mw x mh: the chunk's largest ROI
-static int f0b_detect(InitBatchScratch& B, const F0Clip* d_tab, int b0, int n, int mw, int mh, size_t stride, const F0Detect& D, float* out,
-                      size_t ostride, int qhead, int* n_dev, hipStream_t s)
+// the detector stages of one chunk of n clips (descriptors at d_tab, their host copies at h, counters zeroed).  A clip brings its own frame stride, corner
+// row, count pointer and corner budget, so one chunk may hold images of different sizes (the level images of vh_match_affine_batch).  The per-clip budget is
+// served by the in-LDS selection only: the spacing and segmented-sort routes lay their scratch out for one budget and refuse a mixed chunk.
+// The tile grid is sized for the chunk's largest ROI; the tiles beyond a smaller clip's ROI return at once.
+static int f0b_detect(InitBatchScratch& B, const F0Clip* d_tab, const F0Clip* h, int n, const F0Detect& D, int qhead, hipStream_t s)
 {
-    const int max_corners = D.max_corners;
+    int mw = 0, mh = 0, max_corners = 0;
+    bool mixed = false;
+    for (int i = 0; i < n; i++) {
+        mw = h[i].rw > mw ? h[i].rw : mw;
+        mh = h[i].rh > mh ? h[i].rh : mh;
+        max_corners = h[i].max_corners > max_corners ? h[i].max_corners : max_corners;
+        mixed = mixed || h[i].max_corners != h[0].max_corners;
+    }
+    if (mixed && (D.min_distance >= 1 || max_corners > F0B_SEL_MAX))
+        return vh_fail(-1, "batched detector: clips of different corner budgets need min_distance < 1 and budgets of at most 2048");
     const double scale = 1.0 / (4.0 * D.block * 255.0);
     const dim3 tiles((mw + F0B_TW - 1) / F0B_TW, (mh + F0B_TH - 1) / F0B_TH, n);
     if (D.use_harris)
-        hipLaunchKernelGGL(k_f0b_harris<true>, tiles, dim3(256), 0, s, d_tab, stride, D.block, (float)(scale * scale), (float)D.k, B.resp, B.cnt);
+        hipLaunchKernelGGL(k_f0b_harris<true>, tiles, dim3(256), 0, s, d_tab, D.block, (float)(scale * scale), (float)D.k, B.resp, B.cnt);
     else
-        hipLaunchKernelGGL(k_f0b_harris<false>, tiles, dim3(256), 0, s, d_tab, stride, D.block, (float)(scale * scale), (float)D.k, B.resp, B.cnt);
+        hipLaunchKernelGGL(k_f0b_harris<false>, tiles, dim3(256), 0, s, d_tab, D.block, (float)(scale * scale), (float)D.k, B.resp, B.cnt);
     hipLaunchKernelGGL(k_f0b_candidates, tiles, dim3(256), 0, s, d_tab, D.quality, B.resp, B.keys, B.cnt);
     if (D.min_distance >= 1) {  // (minDistance < 1, negative included, spaces nothing, as in cv2)
         const double md = D.min_distance, md2 = md * md;
         const int cell = md >= 32768.0 ? 32768 : (int)floor(md), slots = cell <= 2 ? 1 : 4;
         const int lim = md2 >= 2147483647.0 ? 0x7fffffff : (int)ceil(md2);
-        hipLaunchKernelGGL(k_f0b_spread, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, B.keys, reinterpret_cast<unsigned*>(B.resp), B.cnt, out, ostride,
-                           qhead, n_dev, cell, slots, lim);
+        hipLaunchKernelGGL(k_f0b_spread, dim3(n), dim3(1024), 0, s, d_tab, max_corners, B.keys, reinterpret_cast<unsigned*>(B.resp), B.cnt, qhead, cell, slots,
+                           lim);
     } else if (max_corners <= F0B_SEL_MAX) {
-        hipLaunchKernelGGL(k_f0b_select<true>, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, B.keys, B.cnt, out, ostride, qhead, n_dev, nullptr, nullptr,
-                           nullptr);
+        hipLaunchKernelGGL(k_f0b_select<true>, dim3(n), dim3(1024), 0, s, d_tab, max_corners, B.keys, B.cnt, qhead, nullptr, nullptr, nullptr);
     } else {
         int* seg_end = B.seg + B.clips_cap;
-        hipLaunchKernelGGL(k_f0b_select<false>, dim3(n), dim3(1024), 0, s, d_tab, b0, max_corners, B.keys, B.cnt, out, ostride, qhead, n_dev, B.sel, B.seg,
-                           seg_end);
+        hipLaunchKernelGGL(k_f0b_select<false>, dim3(n), dim3(1024), 0, s, d_tab, max_corners, B.keys, B.cnt, qhead, B.sel, B.seg, seg_end);
         size_t bytes = 0;
         const unsigned size = (unsigned)n * (unsigned)max_corners;
         VH_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
         if (bytes > B.sort_bytes) return vh_fail(-1, "vh_frame0_init_batch: segmented sort scratch too small");
         bytes = B.sort_bytes;
         VH_CHECK(rocprim::segmented_radix_sort_keys_desc(B.sort_tmp, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
-        hipLaunchKernelGGL(k_f0b_emit, dim3((max_corners + 255) / 256, n), dim3(256), 0, s, d_tab, b0, max_corners, B.sorted, B.cnt, out, ostride, qhead);
+        hipLaunchKernelGGL(k_f0b_emit, dim3((max_corners + 255) / 256, n), dim3(256), 0, s, d_tab, max_corners, B.sorted, B.cnt, qhead);
+    }
+    return 0;
+}
+
+// stream-ordered upload of n descriptors to d_tab, F0B_PIECE per kernel argument
+static int f0b_upload(F0Clip* d_tab, const F0Clip* h, int n, hipStream_t s)
+{
+    for (int p0 = 0; p0 < n; p0 += F0B_PIECE) {
+        F0ClipPiece piece;
+        memset(&piece, 0, sizeof(piece));
+        for (int i = 0; i < F0B_PIECE && p0 + i < n; i++) piece.c[i] = h[p0 + i];
+        VH_CHECK(vh_store(reinterpret_cast<F0ClipPiece*>(d_tab + p0), piece, s));
     }
     return 0;
 }
@@ -1042,6 +1066,9 @@ static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host
         C.offx = (float)boxb[0];
         C.offy = (float)boxb[2];
         for (int i = 0; i < 8; i++) C.q[i] = q_host[8 * b + i];
+        C.stride = stride;
+        C.max_corners = max_corners;
+        C.out = p_out + (size_t)b * (4 + max_corners) * 2;
         const size_t px = (size_t)C.rw * C.rh;
         max_px = px > max_px ? px : max_px;
     }
@@ -1071,24 +1098,17 @@ static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host
     const float* mask = B.mask + subpix_mask_offset(subpix_win);
     for (int b0 = 0; b0 < nb;) {
         // one chunk: as many clips as the scratch holds, their ROI planes back to back
-        int n = 0, mw = 0, mh = 0;
+        int n = 0;
         size_t px = 0;
         while (b0 + n < nb && n < B.clips_cap && n < 65535 && px + (size_t)clips[b0 + n].rw * clips[b0 + n].rh <= B.pix_cap) {  // (grid.z <= 65535)
             F0Clip& C = clips[b0 + n];
             C.seg = px;
             px += (size_t)C.rw * C.rh;
-            mw = C.rw > mw ? C.rw : mw;
-            mh = C.rh > mh ? C.rh : mh;
             n++;
         }
-        for (int p0 = 0; p0 < n; p0 += F0B_PIECE) {
-            F0ClipPiece piece;
-            memset(&piece, 0, sizeof(piece));
-            for (int i = 0; i < F0B_PIECE && p0 + i < n; i++) piece.c[i] = clips[b0 + p0 + i];
-            VH_CHECK(vh_store(reinterpret_cast<F0ClipPiece*>(d_tab + p0), piece, s));
-        }
+        if ((r = f0b_upload(d_tab, &clips[b0], n, s))) return r;
         hipLaunchKernelGGL(k_f0b_setup, dim3((n + 63) / 64), dim3(64), 0, s, d_sh, b0, n, cap, p_out, t_out, R_out, res_out, B.cnt, B.info, B.pose);
-        r = f0b_detect(B, d_tab, b0, n, mw, mh, (size_t)stride, D, p_out, (size_t)cap * 2, 1, nullptr, s);
+        r = f0b_detect(B, d_tab, &clips[b0], n, D, 1, s);
         if (r) return r;
         hipLaunchKernelGGL(k_f0b_subpix, dim3((max_corners + 63) / 64, n), dim3(64), 0, s, d_tab, b0, cap, w, h, (size_t)stride, B.cnt, max_corners,
                            subpix_win, iters, eps * eps, mask, p_out);
@@ -1121,6 +1141,51 @@ extern "C" VH_API int vh_frame0_init_batch2(vh_ctx* c, int nb, const uint8_t* co
                             p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch2");
 }
 
+// one chunk of whole-image clips whose scratch the caller has reserved (batch_reserve: n clips, the sum of their pixels): response planes back to back
+static int f0b_run_clips(vh_ctx* c, F0Clip* clips, int n, const F0Detect& D, hipStream_t s)
+{
+    InitBatchScratch& B = c->init_batch;
+    size_t px = 0;
+    for (int i = 0; i < n; i++) {
+        clips[i].seg = px;
+        px += (size_t)clips[i].rw * clips[i].rh;
+    }
+    if (n > B.clips_cap || px > B.pix_cap) return vh_fail(-1, "batched detector: scratch smaller than the chunk");
+    F0Clip* d_tab = reinterpret_cast<F0Clip*>(B.tab);
+    int r = f0b_upload(d_tab, clips, n, s);
+    if (r) return r;
+    VH_CHECK(hipMemsetAsync(B.cnt, 0, sizeof(unsigned) * 4 * n, s));
+    return f0b_detect(B, d_tab, clips, n, D, 0, s);
+}
+
+int vh_detect_reserve(vh_ctx* c, int clips, size_t pixels, hipStream_t s) { return batch_reserve(c, clips, pixels, s); }
+
+// goodFeaturesToTrack (Shi-Tomasi or Harris, min_distance 0, masked) of n images of any sizes, strides and budgets (each at most 2048) as ONE pass of the
+// batch kernels; per image bit-identical to vh_good_features2 on it alone.  Scratch: vh_detect_reserve(n, the sum of the images' pixels).
+int vh_detect_images(vh_ctx* c, const vh_detect_image* im, int n, double quality, int block, int use_harris, double k, hipStream_t s)
+{
+    if (n < 1 || n > 65535) return vh_fail(-1, "vh_detect_images: 1 .. 65535 images");  // (grid.z)
+    std::vector<F0Clip> clips((size_t)n);
+    for (int i = 0; i < n; i++) {
+        F0Clip& C = clips[i];
+        memset(&C, 0, sizeof(C));
+        if (!im[i].im || !im[i].corners || !im[i].count || im[i].w < 3 || im[i].h < 3 || im[i].stride < im[i].w || (im[i].mask && im[i].mask_stride < im[i].w) ||
+            im[i].max_corners < 1 || im[i].max_corners > F0B_SEL_MAX)
+            return vh_fail(-1, "vh_detect_images: bad image descriptor");
+        C.roi = C.im = im[i].im;
+        C.rw = im[i].w;
+        C.rh = im[i].h;
+        C.stride = im[i].stride;
+        C.mask = im[i].mask;
+        C.mstride = im[i].mask_stride;
+        C.max_corners = im[i].max_corners;
+        C.out = im[i].corners;
+        C.n_out = im[i].count;
+    }
+    const F0Detect D = {0, block, use_harris ? 1 : 0, quality, k, 0.0};
+    return f0b_run_clips(c, clips.data(), n, D, s);
+}
+
 // goodFeaturesToTrack of one image on the batch kernels (one clip: the whole image is its ROI, origin 0)
 extern "C" VH_API int vh_good_features2(vh_ctx* c, const uint8_t* im, int w, int h, int stride, const uint8_t* mask, int mask_stride, int max_corners,
                                         double quality, double min_distance, int block, int use_harris, double k, float* corners, int* count, void* stream)
@@ -1135,19 +1200,18 @@ extern "C" VH_API int vh_good_features2(vh_ctx* c, const uint8_t* im, int w, int
     const size_t px = (size_t)w * h;
     if ((r = batch_reserve(c, 1, px, s))) return r;
     if (max_corners > F0B_SEL_MAX && min_distance < 1 && (r = batch_sel_reserve(c, max_corners, s))) return r;
-    InitBatchScratch& B = c->init_batch;
-    F0ClipPiece piece;
-    memset(&piece, 0, sizeof(piece));
-    F0Clip& C = piece.c[0];
+    F0Clip C;
+    memset(&C, 0, sizeof(C));
     C.roi = C.im = im;
     C.rw = w;
     C.rh = h;
+    C.stride = stride;
     C.mask = mask;
     C.mstride = mask_stride;
-    F0Clip* d_tab = reinterpret_cast<F0Clip*>(B.tab);
-    VH_CHECK(vh_store(reinterpret_cast<F0ClipPiece*>(d_tab), piece, s));
-    VH_CHECK(hipMemsetAsync(B.cnt, 0, sizeof(unsigned) * 4, s));
-    if ((r = f0b_detect(B, d_tab, 0, 1, w, h, (size_t)stride, D, corners, 0, 0, count, s))) return r;
+    C.max_corners = max_corners;
+    C.out = corners;
+    C.n_out = count;
+    if ((r = f0b_run_clips(c, &C, 1, D, s))) return r;
     VH_CHECK(hipGetLastError());
     return 0;
 }

@@ -2,16 +2,21 @@
 // (KLT.py:126-133) asks for the frame-to-frame affine when the coarse stage fails.  Algorithm and its NumPy model: tests/match_ref.py; DESIGN.md
 // "Recovery by feature matching".
 //
-// One call is ONE device-resident launch sequence on the caller's stream:
-//   k_bounding_rect (query ROI) -> per frame and level > 0: ROI warp kernel (vh_remap_affine: the level images) -> k_match_mask (all masks) ->
-//   k_match_box5 (all box sums) -> per frame and level: the batched frame-0 detector with one clip (vh_good_features2) -> k_match_describe (every keypoint
-//   of both frames) -> k_match_2nn -> k_match_compact (good pairs, query order) -> RANSAC (vh_launch_ransac, device pair count) -> k_match_info.
+// One call -- vh_match_affine_batch, nb frame pairs of one frame size; vh_match_affine is the batch of one -- is ONE device-resident launch sequence on
+// the caller's stream:
+//   per pair: k_bounding_rect (query ROI) and, per frame and level > 0, the ROI warp kernel (vh_remap_affine: the level images) -> k_match_mask (all
+//   masks) -> k_match_box5 (all box sums) -> ONE pass of the batched frame-0 detector over the 2 x levels x nb level images (vh_detect_images) ->
+//   k_match_describe (every keypoint of both frames) -> k_match_2nn -> k_match_compact (good pairs, query order) -> RANSAC (vh_launch_ransac over nb
+//   jobs, device pair counts) -> k_match_info.
+// The pair is a grid dimension of every k_match_* kernel (one launch each whatever nb is); a pair's MatchJob is read from a device table.
 // Counts stay on the device: every kernel is launched over the budgets and reads the keypoint counts the detector left.
 // Everything is integer except the level-0 position of a keypoint, (x + 0.5) * inv_s - 0.5 in float32 (two roundings: the build has -ffp-contract=off).
 #include <atomic>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+
+#include <vector>
 
 #include "vh_ws.hpp"
 
@@ -37,7 +42,7 @@ struct MatchLevel {  // one level image of one frame
     float scale, inv_scale;
 };
 
-struct MatchJob {  // travels as a kernel argument
+struct MatchJob {  // one frame pair; the kernels read it from a device table
     MatchLevel lv[2][VH_MATCH_MAX_LEVELS];  // [0]: query frame (im1), [1]: train frame (im2)
     int levels, budget[2];
     const int* roi;     // 4: query ROI at level 0 (x0, x1, y0, y1)
@@ -49,6 +54,10 @@ struct MatchJob {  // travels as a kernel argument
     float *from, *to;   // qcap x 2 each: the good pairs RANSAC reads
     float* pairs_out;   // caller's qcap x 4 (may be null)
     int ratio_num, ratio_den;
+    const int* status;  // RANSAC's verdict on this pair
+    const uint8_t* inl; // caller's qcap inlier flags (RANSAC's output)
+    double* M;          // caller's 6
+    int* info;          // caller's 4
 };
 
 static std::atomic<long long> g_match_launches{0};
@@ -67,9 +76,10 @@ __device__ __forceinline__ int match_prefix(const MatchJob& J, int img, int leve
 }
 
 // ---- masks of every level of both frames: BORDER px from every edge; the query frame also inside its ROI scaled to the level ----------------------
-__global__ __launch_bounds__(256) void k_match_mask(MatchJob J)
+__global__ __launch_bounds__(256) void k_match_mask(const MatchJob* tab, int levels)
 {
-    const int img = blockIdx.z / J.levels, l = blockIdx.z % J.levels;
+    const MatchJob& J = tab[blockIdx.z / (2 * levels)];
+    const int img = (blockIdx.z / levels) & 1, l = blockIdx.z % levels;
     const MatchLevel& L = J.lv[img][l];
     const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= L.w || y >= L.h) return;
@@ -84,9 +94,10 @@ __global__ __launch_bounds__(256) void k_match_mask(MatchJob J)
 }
 
 // ---- 5x5 box sums of every level of both frames (zero outside the image): four neighbouring pixels per thread -------------------------------------
-__global__ __launch_bounds__(256) void k_match_box5(MatchJob J)
+__global__ __launch_bounds__(256) void k_match_box5(const MatchJob* tab, int levels)
 {
-    const int img = blockIdx.z / J.levels, l = blockIdx.z % J.levels;
+    const MatchJob& J = tab[blockIdx.z / (2 * levels)];
+    const int img = (blockIdx.z / levels) & 1, l = blockIdx.z % levels;
     const MatchLevel& L = J.lv[img][l];
     const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
     if (x4 >= L.w || y >= L.h) return;
@@ -111,8 +122,9 @@ __global__ __launch_bounds__(256) void k_match_box5(MatchJob J)
 }
 
 // ---- descriptors: one wavefront per keypoint slot of every level of both frames; four comparisons per lane, each round collected by a ballot -------
-__global__ __launch_bounds__(256) void k_match_describe(MatchJob J)
+__global__ __launch_bounds__(256) void k_match_describe(const MatchJob* tab)
 {
+    const MatchJob& J = tab[blockIdx.z];
     const int img = blockIdx.y / J.levels, l = blockIdx.y % J.levels;
     const MatchLevel& L = J.lv[img][l];
     const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -143,8 +155,9 @@ __global__ __launch_bounds__(256) void k_match_describe(MatchJob J)
 
 // ---- 2-nearest-neighbour Hamming matching: one wavefront per query, lanes stride over the train descriptors ---------------------------------------
 // A candidate is the key (distance << 20 | train index): smaller key = (distance, index) ascending, all keys of a query distinct.
-__global__ __launch_bounds__(256) void k_match_2nn(MatchJob J)
+__global__ __launch_bounds__(256) void k_match_2nn(const MatchJob* tab)
 {
+    const MatchJob& J = tab[blockIdx.y];
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int nq = match_prefix(J, 0, J.levels), nt = match_prefix(J, 1, J.levels);
     if (q >= nq) return;  // (wave-uniform)
@@ -179,8 +192,9 @@ __global__ __launch_bounds__(256) void k_match_2nn(MatchJob J)
 }
 
 // ---- the good pairs, in query order, into the arrays RANSAC reads (and the caller's pair list) -----------------------------------------------------
-__global__ __launch_bounds__(1024) void k_match_compact(MatchJob J)
+__global__ __launch_bounds__(1024) void k_match_compact(const MatchJob* tab)
 {
+    const MatchJob& J = tab[blockIdx.x];
     __shared__ int wcount[16];
     __shared__ int base;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -217,8 +231,13 @@ __global__ __launch_bounds__(1024) void k_match_compact(MatchJob J)
 }
 
 // ---- info = (status, good pairs, inliers, query keypoints) ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_match_info(MatchJob J, const int* status, const uint8_t* inl, double* M, int* info)
+__global__ __launch_bounds__(256) void k_match_info(const MatchJob* tab)
 {
+    const MatchJob& J = tab[blockIdx.x];
+    const int* status = J.status;
+    const uint8_t* inl = J.inl;
+    double* M = J.M;
+    int* info = J.info;
     __shared__ int s_sum;
     if (threadIdx.x == 0) s_sum = 0;
     __syncthreads();
@@ -244,7 +263,6 @@ __global__ __launch_bounds__(256) void k_match_info(MatchJob J, const int* statu
 struct MatchScratch {
     char* base;
     size_t bytes;
-    int* status;           // RANSAC status of the last call
     vh_match_stages last;  // what vh_match_stage_ptrs hands out
     int have_last;
 };
@@ -277,49 +295,84 @@ static int match_check(const vh_match_params& P, int w, int h, const char* fn)
     return 0;
 }
 
-// Lays the scratch out (base may be null: size only) and fills the job's pointers.
-static size_t match_carve(char* base, int w, int h, const vh_match_params& P, MatchJob* J, int** status)
+// the pair is part of grid.z of the mask and box-sum kernels and of the detector's tile grid
+static int match_check_nb(int nb, const vh_match_params& P, const char* fn)
+{
+    char msg[160];
+    if (nb < 1 || (long long)nb * 2 * P.levels > 65535) {
+        snprintf(msg, sizeof(msg), "%s: bad arguments (nb >= 1 and nb x 2 x levels <= 65535)", fn);
+        return vh_fail(-1, msg);
+    }
+    return 0;
+}
+
+struct MatchPairBufs {  // per-pair scratch outside the MatchJob
+    int *status, *idx, *counts, *m, *bound;
+    float4* rpairs;
+};
+struct MatchLayout {
+    int* cnt;         // nb x 2 x VH_MATCH_MAX_LEVELS keypoint counts, zeroed by one memset per call
+    MatchJob* jobs;   // nb
+    RansacJob* rjobs; // nb
+    size_t bytes, level_px;  // level_px: pixels of the 2 x levels level images of one pair
+};
+
+// Lays the scratch of nb pairs out (base may be null: sizes only) and fills the jobs' pointers (J, X: nb entries each, may be null).
+static MatchLayout match_carve(char* base, int nb, int w, int h, const vh_match_params& P, MatchJob* J, MatchPairBufs* X)
 {
     size_t off = 0;
     auto carve = [&](size_t bytes) { char* p = base ? base + off : nullptr; off = match_align(off + bytes); return p; };
     const int qcap = P.levels * P.query_per_level, tcap = P.levels * P.train_per_level;
-    int* cnt = (int*)carve(sizeof(int) * 2 * VH_MATCH_MAX_LEVELS);
-    int* roi = (int*)carve(sizeof(int) * 4);
-    int* small = (int*)carve(sizeof(int) * 2);
-    for (int img = 0; img < 2; img++) {
-        const int budget = img ? P.train_per_level : P.query_per_level;
-        for (int l = 0; l < P.levels; l++) {
-            int wl, hl;
-            match_dims(w, h, l, &wl, &hl);
-            const size_t px = (size_t)wl * hl;
-            uint8_t* image = (uint8_t*)carve(l ? px : 0);
-            uint8_t* mask = (uint8_t*)carve(px);
-            unsigned short* box = (unsigned short*)carve(2 * px);
-            float* kp = (float*)carve(sizeof(float) * 2 * budget);
-            if (J) {
-                MatchLevel& L = J->lv[img][l];
-                if (l) { L.img = image; L.stride = wl; }
-                L.w = wl; L.h = hl; L.mask = mask; L.box = box; L.kp = kp; L.cnt = cnt + img * VH_MATCH_MAX_LEVELS + l;
-                L.scale = (float)match_scale(l);
-                L.inv_scale = (float)(1.0 / match_scale(l));
+    MatchLayout Y;
+    Y.level_px = 0;
+    Y.cnt = (int*)carve(sizeof(int) * 2 * VH_MATCH_MAX_LEVELS * nb);
+    Y.jobs = (MatchJob*)carve(sizeof(MatchJob) * nb);
+    Y.rjobs = (RansacJob*)carve(sizeof(RansacJob) * nb);
+    for (int b = 0; b < nb; b++) {
+        int* cnt = Y.cnt + (size_t)b * 2 * VH_MATCH_MAX_LEVELS;
+        int* roi = (int*)carve(sizeof(int) * 4);
+        int* small = (int*)carve(sizeof(int) * 4);
+        for (int img = 0; img < 2; img++) {
+            const int budget = img ? P.train_per_level : P.query_per_level;
+            for (int l = 0; l < P.levels; l++) {
+                int wl, hl;
+                match_dims(w, h, l, &wl, &hl);
+                const size_t px = (size_t)wl * hl;
+                if (b == 0) Y.level_px += px;
+                uint8_t* image = (uint8_t*)carve(l ? px : 0);
+                uint8_t* mask = (uint8_t*)carve(px);
+                unsigned short* box = (unsigned short*)carve(2 * px);
+                float* kp = (float*)carve(sizeof(float) * 2 * budget);
+                if (J) {
+                    MatchLevel& L = J[b].lv[img][l];
+                    if (l) { L.img = image; L.stride = wl; }
+                    L.w = wl; L.h = hl; L.mask = mask; L.box = box; L.kp = kp; L.cnt = cnt + img * VH_MATCH_MAX_LEVELS + l;
+                    L.scale = (float)match_scale(l);
+                    L.inv_scale = (float)(1.0 / match_scale(l));
+                }
             }
         }
+        float* pos0 = (float*)carve(sizeof(float) * 2 * qcap);
+        float* pos1 = (float*)carve(sizeof(float) * 2 * tcap);
+        uint8_t* desc0 = (uint8_t*)carve((size_t)32 * qcap);
+        uint8_t* desc1 = (uint8_t*)carve((size_t)32 * tcap);
+        int* nn = (int*)carve(sizeof(int) * 4 * qcap);
+        uint8_t* good = (uint8_t*)carve(qcap);
+        float* from = (float*)carve(sizeof(float) * 2 * qcap);
+        float* to = (float*)carve(sizeof(float) * 2 * qcap);
+        int* idx = (int*)carve(sizeof(int) * qcap);
+        float4* rpairs = (float4*)carve(sizeof(float4) * qcap);
+        int* counts = (int*)carve(sizeof(int) * VH_RANSAC_ITERS);
+        if (J) {
+            MatchJob& Q = J[b];
+            Q.levels = P.levels; Q.budget[0] = P.query_per_level; Q.budget[1] = P.train_per_level;
+            Q.roi = roi; Q.pos[0] = pos0; Q.pos[1] = pos1; Q.desc[0] = desc0; Q.desc[1] = desc1; Q.nn = nn; Q.good = good; Q.ngood = small;
+            Q.from = from; Q.to = to; Q.ratio_num = P.ratio_num; Q.ratio_den = P.ratio_den; Q.status = small + 1;
+        }
+        if (X) { X[b].status = small + 1; X[b].m = small + 2; X[b].bound = small + 3; X[b].idx = idx; X[b].rpairs = rpairs; X[b].counts = counts; }
     }
-    float* pos0 = (float*)carve(sizeof(float) * 2 * qcap);
-    float* pos1 = (float*)carve(sizeof(float) * 2 * tcap);
-    uint8_t* desc0 = (uint8_t*)carve((size_t)32 * qcap);
-    uint8_t* desc1 = (uint8_t*)carve((size_t)32 * tcap);
-    int* nn = (int*)carve(sizeof(int) * 4 * qcap);
-    uint8_t* good = (uint8_t*)carve(qcap);
-    float* from = (float*)carve(sizeof(float) * 2 * qcap);
-    float* to = (float*)carve(sizeof(float) * 2 * qcap);
-    if (J) {
-        J->levels = P.levels; J->budget[0] = P.query_per_level; J->budget[1] = P.train_per_level;
-        J->roi = roi; J->pos[0] = pos0; J->pos[1] = pos1; J->desc[0] = desc0; J->desc[1] = desc1; J->nn = nn; J->good = good; J->ngood = small;
-        J->from = from; J->to = to; J->ratio_num = P.ratio_num; J->ratio_den = P.ratio_den;
-    }
-    if (status) *status = small + 1;
-    return off;
+    Y.bytes = off;
+    return Y;
 }
 
 void vh_match_scratch_free(vh_ctx* c)
@@ -331,10 +384,11 @@ void vh_match_scratch_free(vh_ctx* c)
     c->match = nullptr;
 }
 
-// scratch for a w x h frame with parameters P (never shrinks); growth waits for the stream, and is refused inside a capture
-static int match_reserve(vh_ctx* c, int w, int h, const vh_match_params& P, hipStream_t s)
+// scratch for nb pairs of w x h frames with parameters P (never shrinks); growth waits for the stream, and is refused inside a capture
+static int match_reserve(vh_ctx* c, int nb, int w, int h, const vh_match_params& P, hipStream_t s)
 {
-    int r = vh_init_batch_reserve_one(c, (size_t)w * h, s);  // the detector's own scratch, for the largest level
+    const MatchLayout Y = match_carve(nullptr, nb, w, h, P, nullptr, nullptr);
+    int r = vh_detect_reserve(c, 2 * P.levels * nb, Y.level_px * nb, s);  // the detector's own scratch: one pass over every level image
     if (r) return r;
     if (!c->match) {
         MatchScratch* S = new (std::nothrow) MatchScratch();
@@ -343,12 +397,13 @@ static int match_reserve(vh_ctx* c, int w, int h, const vh_match_params& P, hipS
         c->match = S;
     }
     MatchScratch* S = static_cast<MatchScratch*>(c->match);
-    const size_t need = match_carve(nullptr, w, h, P, nullptr, nullptr);
+    const size_t need = Y.bytes;
     if (need <= S->bytes) return 0;
     if (S->base) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return vh_fail(-6, "the matching scratch must grow inside a stream capture: call vh_match_reserve(ctx, w, h, params) before capturing");
+            return vh_fail(-6, "the matching scratch must grow inside a stream capture: call vh_match_reserve(ctx, w, h, params) or vh_match_reserve_batch "
+                               "before capturing");
         VH_CHECK(hipStreamSynchronize(s));
         (void)hipFree(S->base);
         S->base = nullptr;
@@ -360,6 +415,16 @@ static int match_reserve(vh_ctx* c, int w, int h, const vh_match_params& P, hipS
     return 0;
 }
 
+extern "C" VH_API int vh_match_reserve_batch(vh_ctx* c, int nb, int w, int h, const vh_match_params* params_host, void* stream)
+{
+    if (!c) return vh_fail(-1, "vh_match_reserve_batch: bad arguments");
+    const vh_match_params P = params_host ? *params_host : MATCH_DEFAULTS;
+    int r = match_check(P, w, h, "vh_match_reserve_batch");
+    if (r || (r = match_check_nb(nb, P, "vh_match_reserve_batch"))) return r;
+    VH_BIND(c, stream);
+    return match_reserve(c, nb, w, h, P, bound_.s);
+}
+
 extern "C" VH_API int vh_match_reserve(vh_ctx* c, int w, int h, const vh_match_params* params_host, void* stream)
 {
     if (!c) return vh_fail(-1, "vh_match_reserve: bad arguments");
@@ -367,7 +432,102 @@ extern "C" VH_API int vh_match_reserve(vh_ctx* c, int w, int h, const vh_match_p
     int r = match_check(P, w, h, "vh_match_reserve");
     if (r) return r;
     VH_BIND(c, stream);
-    return match_reserve(c, w, h, P, bound_.s);
+    return match_reserve(c, 1, w, h, P, bound_.s);
+}
+
+// stream-ordered upload of n descriptors, as many per kernel argument as 2 KiB hold
+template <typename T, int N>
+struct MatchPiece {
+    T v[N];
+};
+template <typename T>
+static int match_upload(T* dst, const T* src, int n, hipStream_t s)
+{
+    constexpr int PER = sizeof(T) >= 2048 ? 1 : (int)(2048 / sizeof(T));
+    typedef MatchPiece<T, PER> Piece;
+    for (int i0 = 0; i0 < n; i0 += PER) {
+        if (n - i0 >= PER) {
+            Piece piece;
+            memcpy(piece.v, src + i0, sizeof(piece));
+            VH_CHECK(vh_store(reinterpret_cast<Piece*>(dst + i0), piece, s));
+        } else {
+            for (int i = i0; i < n; i++) VH_CHECK(vh_store(dst + i, src[i], s));  // (a whole piece would write past the table's end)
+        }
+    }
+    return 0;
+}
+
+// the launch sequence of nb pairs; every argument has been checked.  M [nb][6], inl [nb][qcap], pairs [nb][qcap][4] or null, info [nb][4]
+static int match_run(vh_ctx* c, int nb, const uint8_t* const* im1, const uint8_t* const* im2, int w, int h, int stride1, int stride2, const float* const* p1,
+                     const int* n, const vh_match_params& P, double* M, uint8_t* inl, float* pairs, int* info, hipStream_t s)
+{
+    const int qcap = P.levels * P.query_per_level;
+    int r = match_reserve(c, nb, w, h, P, s);
+    if (r) return r;
+    MatchScratch* S = static_cast<MatchScratch*>(c->match);
+    std::vector<MatchJob> J((size_t)nb);
+    std::vector<MatchPairBufs> X((size_t)nb);
+    std::vector<RansacJob> R((size_t)nb);
+    memset(J.data(), 0, sizeof(MatchJob) * nb);
+    memset(R.data(), 0, sizeof(RansacJob) * nb);
+    const MatchLayout Y = match_carve(S->base, nb, w, h, P, J.data(), X.data());
+    const StreamBufs& B = c->h_bufs[0];
+    for (int b = 0; b < nb; b++) {
+        MatchJob& Q = J[b];
+        Q.lv[0][0].img = im1[b]; Q.lv[0][0].stride = stride1;
+        Q.lv[1][0].img = im2[b]; Q.lv[1][0].stride = stride2;
+        Q.pairs_out = pairs ? pairs + (size_t)b * qcap * 4 : nullptr;
+        Q.inl = inl + (size_t)b * qcap; Q.M = M + 6 * (size_t)b; Q.info = info + 4 * (size_t)b;
+        // estimateAffine2D on the good pairs: the device count is the job's n, fewer than min_good (or three) pairs report status 0
+        RansacJob& A = R[b];
+        A.from = Q.from; A.to = Q.to; A.valid = B.v_all; A.n_ptr = Q.ngood; A.n = qcap; A.min_valid = P.min_good - 1; A.gate_valid = 0;
+        A.idx = X[b].idx; A.pairs = X[b].rpairs; A.counts = X[b].counts; A.m_out = X[b].m; A.bound = X[b].bound; A.M = Q.M;
+        A.inl = inl + (size_t)b * qcap; A.status = X[b].status;
+    }
+    VH_CHECK(hipMemsetAsync(Y.cnt, 0, sizeof(int) * 2 * VH_MATCH_MAX_LEVELS * nb, s));
+    VH_CHECK(hipMemsetAsync(inl, 0, (size_t)qcap * nb, s));
+    VH_CHECK(hipMemsetAsync(M, 0, sizeof(double) * 6 * nb, s));
+    if ((r = match_upload(Y.jobs, J.data(), nb, s)) || (r = match_upload(Y.rjobs, R.data(), nb, s))) return r;
+    std::vector<vh_detect_image> D((size_t)nb * 2 * P.levels);
+    for (int b = 0; b < nb; b++) {
+        const MatchJob& Q = J[b];
+        if ((r = vh_bounding_rect(c, p1[b], n[b], w, h, P.border_x, P.border_y, const_cast<int*>(Q.roi), s))) return r;
+        // level images: level 0 resampled at ((x + 0.5) / s - 0.5, (y + 0.5) / s - 0.5), bilinear
+        for (int img = 0; img < 2; img++)
+            for (int l = 0; l < P.levels; l++) {
+                const MatchLevel& L = Q.lv[img][l];
+                D[((size_t)b * 2 + img) * P.levels + l] = vh_detect_image{L.img, L.w, L.h, L.stride, L.mask, L.w, Q.budget[img], L.kp, L.cnt};
+                if (!l) continue;
+                const double sc = match_scale(l);
+                const float T[6] = {(float)(1.0 / sc), 0.f, 0.f, (float)(1.0 / sc), (float)(0.5 / sc - 0.5), (float)(0.5 / sc - 0.5)};
+                if ((r = vh_remap_affine(c, Q.lv[img][0].img, w, h, Q.lv[img][0].stride, T, 0, L.w, 0, L.h, const_cast<uint8_t*>(L.img), s))) return r;
+            }
+    }
+    const int nz = 2 * P.levels * nb;
+    MATCH_LAUNCH(k_match_mask, dim3((w + 255) / 256, h, nz), dim3(256), s, Y.jobs, P.levels);
+    MATCH_LAUNCH(k_match_box5, dim3((w + 255) / 256, (h + 3) / 4, nz), dim3(64, 4), s, Y.jobs, P.levels);
+    // corners: ONE pass of the batched frame-0 detector over every level image of every pair (Shi-Tomasi, min_distance 0, masked)
+    if ((r = vh_detect_images(c, D.data(), nz, P.quality, P.block, 0, 0.04, s))) return r;
+    const int bmax = P.query_per_level > P.train_per_level ? P.query_per_level : P.train_per_level;
+    MATCH_LAUNCH(k_match_describe, dim3((bmax + 3) / 4, 2 * P.levels, nb), dim3(256), s, Y.jobs);
+    MATCH_LAUNCH(k_match_2nn, dim3((qcap + 3) / 4, nb), dim3(256), s, Y.jobs);
+    MATCH_LAUNCH(k_match_compact, dim3(nb), dim3(1024), s, Y.jobs);
+    vh_launch_ransac(Y.rjobs, sizeof(RansacJob), nb, qcap, s);
+    MATCH_LAUNCH(k_match_info, dim3(nb), dim3(256), s, Y.jobs);
+    VH_CHECK(hipGetLastError());
+
+    const MatchJob& Q = J[nb - 1];  // the stages of the call's last pair stay readable (vh_match_stage_ptrs)
+    vh_match_stages& V = S->last;
+    memset(&V, 0, sizeof(V));
+    for (int img = 0; img < 2; img++) {
+        for (int l = 0; l < P.levels; l++) V.kp[img][l] = Q.lv[img][l].kp;
+        V.pos[img] = Q.pos[img];
+        V.desc[img] = Q.desc[img];
+    }
+    V.cnt = Q.lv[0][0].cnt; V.nn = Q.nn; V.good = Q.good; V.roi = Q.roi; V.levels = P.levels;
+    for (int l = 0; l < P.levels; l++) { V.lw[l] = Q.lv[0][l].w; V.lh[l] = Q.lv[0][l].h; }
+    S->have_last = 1;
+    return 0;
 }
 
 extern "C" VH_API int vh_match_affine(vh_ctx* c, const uint8_t* im1, const uint8_t* im2, int w, int h, int stride1, int stride2, const float* p1, int n,
@@ -378,69 +538,26 @@ extern "C" VH_API int vh_match_affine(vh_ctx* c, const uint8_t* im1, const uint8
     const vh_match_params P = params_host ? *params_host : MATCH_DEFAULTS;
     int r = match_check(P, w, h, "vh_match_affine");
     if (r) return r;
-    const int qcap = P.levels * P.query_per_level;
-    if (qcap > c->max_pts) return vh_fail(-1, "vh_match_affine: levels x query_per_level exceeds the context's max_pts");
+    if (P.levels * P.query_per_level > c->max_pts) return vh_fail(-1, "vh_match_affine: levels x query_per_level exceeds the context's max_pts");
     VH_BIND(c, stream);
-    hipStream_t s = bound_.s;
-    if ((r = match_reserve(c, w, h, P, s))) return r;
-    MatchScratch* S = static_cast<MatchScratch*>(c->match);
-    MatchJob J;
-    memset(&J, 0, sizeof(J));
-    int* status = nullptr;
-    match_carve(S->base, w, h, P, &J, &status);
-    J.lv[0][0].img = im1; J.lv[0][0].stride = stride1;
-    J.lv[1][0].img = im2; J.lv[1][0].stride = stride2;
-    J.pairs_out = pairs;
-    S->status = status;
-    int* cnt = J.lv[0][0].cnt;
-    int* roi = const_cast<int*>(J.roi);
+    return match_run(c, 1, &im1, &im2, w, h, stride1, stride2, &p1, &n, P, M, inl, pairs, info, bound_.s);
+}
 
-    VH_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * 2 * VH_MATCH_MAX_LEVELS, s));
-    VH_CHECK(hipMemsetAsync(inl, 0, (size_t)qcap, s));
-    VH_CHECK(hipMemsetAsync(M, 0, sizeof(double) * 6, s));
-    if ((r = vh_bounding_rect(c, p1, n, w, h, P.border_x, P.border_y, roi, s))) return r;
-    // level images: level 0 resampled at ((x + 0.5) / s - 0.5, (y + 0.5) / s - 0.5), bilinear
-    for (int img = 0; img < 2; img++)
-        for (int l = 1; l < P.levels; l++) {
-            const double sc = match_scale(l);
-            const float T[6] = {(float)(1.0 / sc), 0.f, 0.f, (float)(1.0 / sc), (float)(0.5 / sc - 0.5), (float)(0.5 / sc - 0.5)};
-            const MatchLevel& L = J.lv[img][l];
-            if ((r = vh_remap_affine(c, J.lv[img][0].img, w, h, J.lv[img][0].stride, T, 0, L.w, 0, L.h, const_cast<uint8_t*>(L.img), s))) return r;
-        }
-    MATCH_LAUNCH(k_match_mask, dim3((w + 255) / 256, h, 2 * P.levels), dim3(256), s, J);
-    MATCH_LAUNCH(k_match_box5, dim3((w + 255) / 256, (h + 3) / 4, 2 * P.levels), dim3(64, 4), s, J);
-    // corners: ten single-clip passes of the batched frame-0 detector (Shi-Tomasi, min_distance 0, masked)
-    for (int img = 0; img < 2; img++)
-        for (int l = 0; l < P.levels; l++) {
-            const MatchLevel& L = J.lv[img][l];
-            if ((r = vh_good_features2(c, L.img, L.w, L.h, L.stride, L.mask, L.w, J.budget[img], P.quality, 0.0, P.block, 0, 0.04, L.kp, L.cnt, s))) return r;
-        }
-    const int bmax = J.budget[0] > J.budget[1] ? J.budget[0] : J.budget[1];
-    MATCH_LAUNCH(k_match_describe, dim3((bmax + 3) / 4, 2 * P.levels), dim3(256), s, J);
-    MATCH_LAUNCH(k_match_2nn, dim3((qcap + 3) / 4), dim3(256), s, J);
-    MATCH_LAUNCH(k_match_compact, dim3(1), dim3(1024), s, J);
-    // estimateAffine2D on the good pairs: the device count is the job's n, fewer than min_good (or three) pairs report status 0
-    const StreamBufs& B = c->h_bufs[0];
-    RansacJob R;
-    memset(&R, 0, sizeof(R));
-    R.from = J.from; R.to = J.to; R.valid = B.v_all; R.n_ptr = J.ngood; R.n = qcap; R.min_valid = P.min_good - 1; R.gate_valid = 0;
-    R.idx = B.idx; R.pairs = B.pairs; R.counts = B.counts; R.m_out = &c->d_ws[0].m; R.bound = &c->d_ws[0].rbound; R.M = M; R.inl = inl; R.status = status;
-    VH_CHECK(vh_store(&c->d_ws[0].ransac, R, s));
-    vh_launch_ransac(&c->d_ws[0].ransac, sizeof(StreamWS), 1, qcap, s);
-    MATCH_LAUNCH(k_match_info, dim3(1), dim3(256), s, J, status, inl, M, info);
-    VH_CHECK(hipGetLastError());
-
-    vh_match_stages& V = S->last;
-    memset(&V, 0, sizeof(V));
-    for (int img = 0; img < 2; img++) {
-        for (int l = 0; l < P.levels; l++) V.kp[img][l] = J.lv[img][l].kp;
-        V.pos[img] = J.pos[img];
-        V.desc[img] = J.desc[img];
-    }
-    V.cnt = cnt; V.nn = J.nn; V.good = J.good; V.roi = J.roi; V.levels = P.levels;
-    for (int l = 0; l < P.levels; l++) { V.lw[l] = J.lv[0][l].w; V.lh[l] = J.lv[0][l].h; }
-    S->have_last = 1;
-    return 0;
+extern "C" VH_API int vh_match_affine_batch(vh_ctx* c, int nb, const uint8_t* const* im1_host, const uint8_t* const* im2_host, int w, int h, int stride1,
+                                            int stride2, const float* const* p1_host, const int* n_host, const vh_match_params* params_host, double* M,
+                                            uint8_t* inl, float* pairs, int* info, void* stream)
+{
+    if (!c || !im1_host || !im2_host || !p1_host || !n_host || !M || !inl || !info || stride1 < w || stride2 < w)
+        return vh_fail(-1, "vh_match_affine_batch: bad arguments (null pointer or a row stride below the width)");
+    const vh_match_params P = params_host ? *params_host : MATCH_DEFAULTS;
+    int r = match_check(P, w, h, "vh_match_affine_batch");
+    if (r || (r = match_check_nb(nb, P, "vh_match_affine_batch"))) return r;
+    for (int b = 0; b < nb; b++)
+        if (!im1_host[b] || !im2_host[b] || !p1_host[b] || n_host[b] < 1)
+            return vh_fail(-1, "vh_match_affine_batch: a pair has a null frame, null points or n < 1");
+    if (P.levels * P.query_per_level > c->max_pts) return vh_fail(-1, "vh_match_affine_batch: levels x query_per_level exceeds the context's max_pts");
+    VH_BIND(c, stream);
+    return match_run(c, nb, im1_host, im2_host, w, h, stride1, stride2, p1_host, n_host, P, M, inl, pairs, info, bound_.s);
 }
 
 extern "C" VH_API int vh_match_stage_ptrs(vh_ctx* c, vh_match_stages* out)

@@ -18,6 +18,31 @@
 // velocity_amd/driver.py::TrackerSession.state() hands the reference's [5, N0, nhist] view to the caller.
 __device__ __host__ __forceinline__ size_t sess_P(int row, int track, int frame, int N0) { return ((size_t)frame * 5 + row) * (size_t)N0 + track; }
 
+// The recovery branch of KLTmain (KLT.py:130-133) for the session's streams (vh_session_set_fallback; off unless asked for).  The failure predicate is read
+// on the HOST: one small record per stream and step.  The rare branch is composed from the stateless entry points -- vh_match_affine_batch over the
+// failed streams, then KLTregional per stream with a model -- on a context of the session's own: those entry points park their job descriptors in slot 0
+// of the context they are given, where the session's context keeps stream 0's.
+#define SESS_FB_CHUNK 16  // failed streams per vh_match_affine_batch call (bounds the matcher's scratch: it is per pair)
+struct SessFbRec {
+    int flags, n_cur;
+    const uint8_t* im0;
+    const uint8_t* im;
+};
+struct SessFallback {
+    int on, chunk;
+    vh_match_params params;
+    vh_ctx* ctx;        // batch 1, the session's frame size, max_pts >= max(N0, levels x query_per_level)
+    SessFbRec* h_rec;   // pinned [batch]
+    SessFbRec* d_rec;   // [batch]
+    double* d_M;        // [chunk][6]
+    int* d_info;        // [chunk][4]
+    uint8_t* d_inl;     // [chunk][levels x query_per_level]
+    double* h_M;        // pinned, as d_M
+    int* h_info;        // pinned, as d_info
+    int inl_cap;        // bytes of d_inl
+    int* counts;        // host [batch][2]: the recovery ran, it found a model
+};
+
 struct vh_session {
     vh_ctx* ctx;
     int batch, N0, nhist, w, h, msv_frame, k_is_f32;
@@ -28,6 +53,7 @@ struct vh_session {
     IngestJob* d_ingest;  // [batch] descriptors of the fused BGR ingest
     int* h_frame;      // per stream: frames stepped since its vh_session_init (host mirror of SessStream::frame_i; the
                        // reference fires fcnMSV1_t at `i == msvFrame` of EACH video, vidExample.py:155)
+    SessFallback fb;
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -197,6 +223,20 @@ __global__ __launch_bounds__(256) void k_sess_after_msv(SessStream* ss_all, int 
     for (int g = threadIdx.x; g < S.N0; g += 256) S.vp[g] = S.vg[g];
 }
 
+// what the host needs to decide whether a stream's recovery runs, and to run it: after KLTmain, before the bookkeeping (p_cur, n_cur and im0 are still the
+// previous frame's)
+__global__ void k_sess_fb_gather(const SessStream* ss_all, const uint8_t* const* frames, SessFbRec* rec, int batch)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    const SessStream& S = ss_all[b];
+    rec[b] = SessFbRec{S.klt_flags, S.n_cur, S.im0, frames[b]};
+}
+__global__ void k_sess_fb_flags(SessStream* S, int bits)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) S->klt_flags |= bits;
+}
+
 // frame-0 initialisation (vidExample.py:125-131, 151-153)
 // t0_dev / res0_dev / n_dev (all may be null): plate pose, its residual and the number of frame-0 tracks taken from DEVICE memory -- the outputs of
 // vh_frame0_init -- instead of the by-value arguments; with n_dev < N0 the tail rows are tracks that never existed (vg 0, history NaN)
@@ -255,6 +295,7 @@ extern "C" VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, i
     if (!s) return vh_fail(-1, "out of host memory");
     s->ctx = ctx; s->batch = ctx->batch; s->N0 = n0; s->nhist = nhist; s->w = w; s->h = h; s->msv_frame = msv_frame; s->k_is_f32 = k_is_float32 ? 1 : 0;
     s->coarse = *coarse; s->fine = *fine;
+    memset(&s->fb, 0, sizeof(s->fb));
     const int dw = (int)lrint(w * 0.25), dh = (int)lrint(h * 0.25);
     s->h_ss = new SessStream[s->batch];
     memset(s->h_ss, 0, sizeof(SessStream) * s->batch);
@@ -309,9 +350,114 @@ extern "C" VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, i
     return 0;
 }
 
+static void sess_fb_release(SessFallback& F)
+{
+    (void)hipFree(F.d_rec); (void)hipFree(F.d_M); (void)hipFree(F.d_info); (void)hipFree(F.d_inl);
+    (void)hipHostFree(F.h_rec); (void)hipHostFree(F.h_M); (void)hipHostFree(F.h_info);
+    if (F.ctx) vh_ctx_destroy(F.ctx);
+    delete[] F.counts;
+    memset(&F, 0, sizeof(F));
+}
+
+extern "C" VH_API int vh_session_set_fallback(vh_session* s, int on, const vh_match_params* params_host)
+{
+    if (!s) return vh_fail(-1, "vh_session_set_fallback: bad arguments");
+    SessFallback& F = s->fb;
+    if (!on) { F.on = 0; return 0; }
+    if (s->w < 4 || s->h < 4) return vh_fail(-1, "vh_session_set_fallback: the recovery needs frames of at least 4 x 4");
+    const int chunk = s->batch < SESS_FB_CHUNK ? s->batch : SESS_FB_CHUNK;
+    // the matcher checks its parameters itself (-1, nothing created); its defaults come back through a context that exists, so the first reserve is
+    // on a context sized for the defaults' query budget and repeated if the parameters ask for more
+    vh_match_params P = {5, 500, 1000, 5, 50, 50, 4, 5, 10, 0.01};  // (vh_match_affine's defaults, include/velocity_hip.h)
+    if (params_host) P = *params_host;
+    if (P.levels < 1 || P.levels > 8 || P.query_per_level < 1 || P.query_per_level > 2048) return vh_fail(-1, "vh_session_set_fallback: bad matcher parameters");
+    const int qcap = P.levels * P.query_per_level, pts = s->N0 > qcap ? s->N0 : qcap;
+    if (F.ctx && F.ctx->max_pts < pts) {  // a larger query budget than the context was made for
+        VH_CHECK(hipDeviceSynchronize());
+        vh_ctx_destroy(F.ctx);
+        F.ctx = nullptr;
+    }
+    int r = 0;
+    if (!F.ctx && (r = vh_ctx_create(&F.ctx, 1, s->w, s->h, pts))) return r;
+    if ((r = vh_match_reserve_batch(F.ctx, chunk, s->w, s->h, &P, nullptr))) return r;
+    if (!F.h_rec) {
+        F.counts = new int[2 * (size_t)s->batch]();
+        VH_CHECK(hipHostMalloc((void**)&F.h_rec, sizeof(SessFbRec) * s->batch, hipHostMallocDefault));
+        VH_CHECK(hipHostMalloc((void**)&F.h_M, sizeof(double) * 6 * chunk, hipHostMallocDefault));
+        VH_CHECK(hipHostMalloc((void**)&F.h_info, sizeof(int) * 4 * chunk, hipHostMallocDefault));
+        VH_CHECK(hipMalloc((void**)&F.d_rec, sizeof(SessFbRec) * s->batch));
+        VH_CHECK(hipMalloc((void**)&F.d_M, sizeof(double) * 6 * chunk));
+        VH_CHECK(hipMalloc((void**)&F.d_info, sizeof(int) * 4 * chunk));
+    }
+    if (F.inl_cap < qcap * chunk) {
+        if (F.d_inl) { VH_CHECK(hipDeviceSynchronize()); (void)hipFree(F.d_inl); F.d_inl = nullptr; F.inl_cap = 0; }
+        VH_CHECK(hipMalloc((void**)&F.d_inl, (size_t)qcap * chunk));
+        F.inl_cap = qcap * chunk;
+    }
+    F.params = P;
+    F.chunk = chunk;
+    F.on = 1;
+    return 0;
+}
+
+extern "C" VH_API int vh_session_recoveries(vh_session* s, int* counts_host)
+{
+    if (!s || !counts_host) return vh_fail(-1, "vh_session_recoveries: bad arguments");
+    for (int k = 0; k < 2 * s->batch; k++) counts_host[k] = s->fb.counts ? s->fb.counts[k] : 0;
+    return 0;
+}
+
+// KLT.py:126-133 for every stream whose coarse stage has just failed; queued between KLTmain and the bookkeeping of the step
+static int session_recover(vh_session* s, const uint8_t* const* frames_dev, hipStream_t st)
+{
+    SessFallback& F = s->fb;
+    const int nb = s->batch, w = s->w, h = s->h;
+    hipLaunchKernelGGL(k_sess_fb_gather, dim3((nb + 63) / 64), dim3(64), 0, st, s->d_ss, frames_dev, F.d_rec, nb);
+    VH_CHECK(hipMemcpyAsync(F.h_rec, F.d_rec, sizeof(SessFbRec) * nb, hipMemcpyDeviceToHost, st));
+    VH_CHECK(hipStreamSynchronize(st));  // the host read of the option: once per step
+    int failed[SESS_FB_CHUNK], m = 0;
+    for (int b = 0; b <= nb; b++) {
+        if (b < nb && (F.h_rec[b].flags & 1) && F.h_rec[b].n_cur > 0) failed[m++] = b;  // `fallback and n > 0` (an empty stream is left alone)
+        if (m == 0 || (m < F.chunk && b < nb)) continue;
+        const uint8_t *im1[SESS_FB_CHUNK], *im2[SESS_FB_CHUNK];
+        const float* p1[SESS_FB_CHUNK];
+        int n[SESS_FB_CHUNK];
+        for (int i = 0; i < m; i++) {
+            const SessFbRec& R = F.h_rec[failed[i]];
+            im1[i] = R.im0; im2[i] = R.im; p1[i] = s->h_ss[failed[i]].p_cur; n[i] = R.n_cur;
+        }
+        int r = vh_match_affine_batch(F.ctx, m, im1, im2, w, h, w, w, p1, n, &F.params, F.d_M, F.d_inl, nullptr, F.d_info, st);
+        if (r) return r;
+        VH_CHECK(hipMemcpyAsync(F.h_M, F.d_M, sizeof(double) * 6 * m, hipMemcpyDeviceToHost, st));
+        VH_CHECK(hipMemcpyAsync(F.h_info, F.d_info, sizeof(int) * 4 * m, hipMemcpyDeviceToHost, st));
+        VH_CHECK(hipStreamSynchronize(st));  // (failing steps only)
+        for (int i = 0; i < m; i++) {
+            const int b2 = failed[i];
+            const SessStream& H = s->h_ss[b2];
+            int bits = 2;
+            F.counts[2 * b2]++;
+            if (F.h_info[4 * i] > 0) {
+                bits |= 4;
+                F.counts[2 * b2 + 1]++;
+                // KLTregional(im0, im, p0, T23.T, lk_fine, fbt=0.3): T = float32(T23.T), 3 x 2 row-major (KLT.py:58)
+                const double* M = F.h_M + 6 * i;
+                const float T[6] = {(float)M[0], (float)M[3], (float)M[1], (float)M[4], (float)M[2], (float)M[5]};
+                r = vh_klt_regional(F.ctx, im1[i], im2[i], w, h, w, w, H.p_cur, n[i], T, &s->fine, 0.3f, 0, H.p_all, H.v, nullptr, st);
+                if (r) return r;
+            }
+            hipLaunchKernelGGL(k_sess_fb_flags, dim3(1), dim3(64), 0, st, s->d_ss + b2, bits);
+        }
+        m = 0;
+    }
+    SESS_CHECK();
+    return 0;
+}
+
 extern "C" VH_API void vh_session_destroy(vh_session* s)
 {
     if (!s) return;
+    (void)hipDeviceSynchronize();
+    sess_fb_release(s->fb);
     (void)hipFree(s->arena);
     delete[] s->h_ss;
     delete[] s->h_frame;
@@ -331,6 +477,7 @@ static int session_init(vh_session* s, int slot, const uint8_t* frame0, int stri
     int r = vh_resize_quarter(s->ctx, frame0, s->w, s->h, stride, s->h_ss[slot].small[1], stream);
     if (r) return r;
     s->h_frame[slot] = 0;  // a (re-)initialised slot starts a new clip: its MSV frame counts from here
+    if (s->fb.counts) s->fb.counts[2 * slot] = s->fb.counts[2 * slot + 1] = 0;
     SESS_CHECK();
     return 0;
 }
@@ -354,12 +501,20 @@ static int session_step(vh_session* s, const uint8_t* const* frames_dev, float t
                         const float* frame_nos_dev, void* stream)
 {
     if (!s || !frames_dev) return vh_fail(-1, "vh_session_step: bad arguments");
+    if (s->fb.on) {  // the recovery reads the failure flags on the host: not something a graph can replay
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+        if (cs != hipStreamCaptureStatusNone)
+            return vh_fail(-6, "vh_session_step: a session with the recovery on (vh_session_set_fallback) waits for the stream in every step and cannot be "
+                               "captured; turn the option off to capture");
+    }
     VH_BIND(s->ctx, stream);
     hipStream_t st = bound_.s;
     vh_ctx* c = s->ctx;
     const int nb = s->batch;
     int r = vh_run_klt_main(c, 0, nb, st, s->coarse, s->fine, s->d_ss, frames_dev, s->N0);  // the set-up kernel also fetches this frame's KltIO from the session
     if (r) return r;
+    if (s->fb.on && (r = session_recover(s, frames_dev, st))) return r;
     if (s->N0 <= 4096) {
         const int rec = vh_prof_start(s->ctx, st);
         hipLaunchKernelGGL(k_sess_frame, dim3(nb), dim3(SESS_NT), 0, st, s->d_ss, frames_dev, time_s, frame_no, times_dev, frame_nos_dev);

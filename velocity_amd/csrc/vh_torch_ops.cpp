@@ -355,6 +355,42 @@ std::tuple<Tensor, Tensor, Tensor> match_affine(const Tensor& im1, const Tensor&
     return {M, inl, info};
 }
 
+// match_affine for B frame pairs in one launch sequence (vh_match_affine_batch): im1, im2 [B, H, W] u8, p1 = B point sets [n_b, 2] ->
+// (M [B, 2, 3] f64, inliers [B, levels * query_per_level] u8, info [B, 4] i32), each row what match_affine returns for the pair alone
+std::tuple<Tensor, Tensor, Tensor> match_affine_batch(const Tensor& im1, const Tensor& im2, at::TensorList p1, int64_t levels, int64_t query_per_level,
+                                                      int64_t train_per_level, int64_t block, int64_t border_x, int64_t border_y, int64_t ratio_num,
+                                                      int64_t ratio_den, int64_t min_good, double quality)
+{
+    TORCH_CHECK(im1.is_cuda() && im2.is_cuda() && im1.scalar_type() == at::kByte && im2.scalar_type() == at::kByte && im1.dim() == 3 && im2.dim() == 3,
+                "match_affine_batch: expected CUDA uint8 frames [B, H, W]");
+    TORCH_CHECK(im1.sizes() == im2.sizes() && im1.size(0) >= 1, "match_affine_batch: im1 and im2 differ in size, or are empty");
+    TORCH_CHECK((int64_t)p1.size() == im1.size(0), "match_affine_batch: one point set per frame pair");
+    TORCH_CHECK(levels >= 1 && levels <= 8 && query_per_level >= 1 && query_per_level <= 2048, "match_affine_batch: levels 1..8, query_per_level 1..2048");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(im1.device());
+    void* s = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    Tensor a = im1.stride(2) == 1 ? im1 : im1.contiguous(), b = im2.stride(2) == 1 ? im2 : im2.contiguous();
+    const int nb = (int)a.size(0), h = (int)a.size(1), w = (int)a.size(2), cap = (int)(levels * query_per_level);
+    std::vector<Tensor> pts;
+    std::vector<const uint8_t*> pa, pb;
+    std::vector<const float*> pp;
+    std::vector<int> n;
+    for (int i = 0; i < nb; i++) {
+        pts.push_back(as_points(p1[i], "match_affine_batch(p1)"));
+        pa.push_back(a.data_ptr<uint8_t>() + (size_t)i * a.stride(0));
+        pb.push_back(b.data_ptr<uint8_t>() + (size_t)i * b.stride(0));
+        pp.push_back(pts.back().data_ptr<float>());
+        n.push_back((int)pts.back().size(0));
+    }
+    auto opt = im1.options();
+    Tensor M = at::zeros({nb, 2, 3}, opt.dtype(at::kDouble)), inl = at::zeros({nb, cap}, opt.dtype(at::kByte)), info = at::zeros({nb, 4}, opt.dtype(at::kInt));
+    vh_match_params P{(int)levels, (int)query_per_level, (int)train_per_level, (int)block, (int)border_x, (int)border_y, (int)ratio_num, (int)ratio_den,
+                      (int)min_good, quality};
+    vh_check(vh_match_affine_batch(workspace(im1, w, h, cap, s), nb, pa.data(), pb.data(), w, h, (int)a.stride(1), (int)b.stride(1), pp.data(), n.data(), &P,
+                                   M.data_ptr<double>(), inl.data_ptr<uint8_t>(), nullptr, info.data_ptr<int>(), s),
+             "vh_match_affine_batch");
+    return {M, inl, info};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(velocity_hip, m)
@@ -376,6 +412,8 @@ TORCH_LIBRARY(velocity_hip, m)
           "float k=0.04) -> (Tensor corners, Tensor count)");
     m.def("match_affine(Tensor im1, Tensor im2, Tensor p1, int levels=5, int query_per_level=500, int train_per_level=1000, int block=5, int border_x=50, "
           "int border_y=50, int ratio_num=4, int ratio_den=5, int min_good=10, float quality=0.01) -> (Tensor M, Tensor inliers, Tensor info)");
+    m.def("match_affine_batch(Tensor im1, Tensor im2, Tensor[] p1, int levels=5, int query_per_level=500, int train_per_level=1000, int block=5, "
+          "int border_x=50, int border_y=50, int ratio_num=4, int ratio_den=5, int min_good=10, float quality=0.01) -> (Tensor M, Tensor inliers, Tensor info)");
 }
 
 // The inputs that decide the device are CUDA tensors: register under the CUDA (= HIP on ROCm) dispatch key.  There is deliberately NO CPU kernel:
@@ -394,4 +432,5 @@ TORCH_LIBRARY_IMPL(velocity_hip, CUDA, m)
     m.impl("frame0_init", &frame0_init);
     m.impl("good_features", &good_features);
     m.impl("match_affine", &match_affine);
+    m.impl("match_affine_batch", &match_affine_batch);
 }

@@ -228,7 +228,17 @@ int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_p
 int vh_fail(int code, const char* msg);
 void vh_init_scratch_free(vh_ctx* c);        // both frame-0 scratches (vh_init.hip)
 void vh_init_batch_scratch_free(vh_ctx* c);
-int vh_init_batch_reserve_one(vh_ctx* c, size_t pixels, hipStream_t s);  // the batched detector's scratch for one clip of `pixels` (what vh_good_features2 needs)
+// the batched frame-0 detector on whole images of different sizes, strides and corner budgets (vh_init.hip; the level images of vh_match_affine_batch)
+struct vh_detect_image {
+    const uint8_t* im;
+    int w, h, stride;
+    const uint8_t* mask;  // w x h detection mask, rows mask_stride apart (may be null)
+    int mask_stride, max_corners;  // budget 1 .. 2048
+    float* corners;       // max_corners x 2
+    int* count;           // 1
+};
+int vh_detect_reserve(vh_ctx* c, int clips, size_t pixels, hipStream_t s);  // scratch for one pass over `clips` images of `pixels` pixels in all (never shrinks)
+int vh_detect_images(vh_ctx* c, const vh_detect_image* images_host, int n, double quality, int block, int use_harris, double k, hipStream_t s);
 void vh_match_scratch_free(vh_ctx* c);       // vh_match.hip
 
 // optional HIP-event timing of individual launches (vh_profile_begin / vh_profile_end_stages): stage ids

@@ -10,7 +10,11 @@ from . import _lib as L
 
 
 class TrackerSession:
-    def __init__(self, K, width, height, n0, nhist=20, batch=1, lk_coarse=None, lk_fine=None, msv_frame=5):
+    def __init__(self, K, width, height, n0, nhist=20, batch=1, lk_coarse=None, lk_fine=None, msv_frame=5, fallback=False, fallback_params=None):
+        """fallback=True (default off: a step queues exactly what it always did): the recovery branch of KLTmain (KLT.py:130-133) for a stream whose coarse
+        stage fails -- the affine from feature matching (vh_match_affine_batch over the failed streams; `fallback_params`: _lib.MATCH_DEFAULTS keys)
+        drives the fine stage.  It costs ONE host read per step (the failure flags), so the host no longer runs ahead of the device, and such a step cannot
+        be captured into a graph: leave it off for clips that do not need it (include/velocity_hip.h, vh_session_set_fallback)."""
         torch = L.torch_cuda()
         self.torch = torch
         self.batch, self.w, self.h, self.n0, self.nhist = batch, width, height, n0, nhist
@@ -24,6 +28,10 @@ class TrackerSession:
         L.check(self.lib.vh_session_create(C.byref(h), self.ws.handle, n0, nhist, width, height, self.K64.ctypes.data_as(L.f64p), k_is_f32,
                                            C.byref(self.lkc), C.byref(self.lkf), int(msv_frame)), "vh_session_create")
         self.handle = h
+        self.fallback = bool(fallback)
+        if self.fallback:
+            mp = L.match_params(fallback_params)
+            L.check(self.lib.vh_session_set_fallback(h, 1, C.byref(mp)), "vh_session_set_fallback")
         self._frames = torch.zeros(batch, dtype=torch.int64, device="cuda")  # device table of frame pointers
         self._keep = [None] * batch
         self._init_keep = []
@@ -105,6 +113,12 @@ class TrackerSession:
         L.check(self.lib.vh_session_ingest_bgr(self.handle, L.dptr(bgr_tab), 3 * self.w, L.dptr(self._gray_tab[k]), L.stream_ptr()), "vh_session_ingest_bgr")
         self.step(frames_table=self._gray_tab[k], time_s=time_s, frame_no=frame_no)
         return self._gray[k]
+
+    def recoveries(self):
+        """int [batch, 2]: per stream, the steps since its init_stream in which the recovery ran / in which it found a model."""
+        out = np.zeros((self.batch, 2), np.int32)
+        L.check(self.lib.vh_session_recoveries(self.handle, out.ctypes.data_as(L.i32p)), "vh_session_recoveries")
+        return out
 
     def view(self, slot=0):
         v = L.SessionView()
@@ -248,7 +262,7 @@ def summary_lines(S, n, frame_numbers, seconds):
 
 def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01,
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
-                 out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0):
+                 out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
     """The packaged counterpart of vidExample.py:52-178 (minus video decode and plots) on one clip.
 
     frames  sequence of n uint8 [H, W] gray frames (numpy arrays or CUDA tensors): what `cv2.cvtColor(cap.read(), BGR2GRAY)` / `cv2.imread(.., 0)` hands
@@ -263,6 +277,8 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     live    True prints every row as its frame finishes (one small read-back per frame, like the reference); False runs the whole clip first.
     use_harris, min_distance   the frame-0 detector (goodFeaturesToTrack's useHarrisDetector / minDistance; the defaults are the reference's call).  Any
             other setting runs frame 0 as a one-clip vh_frame0_init_batch2, whose results for the defaults equal vh_frame0_init's.
+    fallback   True: a frame whose coarse KLT stage fails recovers the motion by feature matching (TrackerSession(fallback=True): one host read per
+            frame step; default off).  The result then carries `recoveries` = [the recovery ran, it found a model] counts.
     out     line sink (default print); clock: time source for the procTime column / fps line (default time.perf_counter).
 
     Prints the reference's header, one 9-column row per frame (vidExample.py:165) and the `Speed = ... +/- ... km/h / Res = ...` summary (:177-178).
@@ -290,7 +306,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     t_begin = clock()
     if route == "session":
         res = _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corners, quality, block, harris_k, subpix, msv_frame, lk_coarse,
-                           lk_fine, emit, clock, live, use_harris, min_distance)
+                           lk_fine, emit, clock, live, use_harris, min_distance, fallback, fallback_params)
     else:
         raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
     seconds = clock() - t_begin
@@ -307,14 +323,15 @@ def _plate_points(country):
 
 
 def _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corners, quality, block, harris_k, subpix, msv_frame, lk_coarse, lk_fine,
-                 emit, clock, live, use_harris=True, min_distance=0.0):
+                 emit, clock, live, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
     torch = L.torch_cuda()
     tic = clock()
     dev = [f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)) for f in frames]
     dev = [f.cuda(non_blocking=True).contiguous() for f in dev]
     H, W = dev[0].shape
     n, cap = len(dev), 4 + int(max_corners)
-    ses = TrackerSession(K, W, H, cap, nhist=n, batch=1, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame)
+    ses = TrackerSession(K, W, H, cap, nhist=n, batch=1, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback,
+                         fallback_params=fallback_params)
     lib, ws = ses.lib, ses.ws
     # frame 0 (vidExample.py:105-131): one device sequence; its outputs are the session's frame-0 state without touching the host
     p = torch.empty((cap, 2), dtype=torch.float32, device="cuda")
@@ -376,7 +393,7 @@ def _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corn
     k = n_tr  # rows beyond the tracks found at frame 0 never existed (the session was sized for 4 + max_corners)
     return dict(S=S, B=st["B"], P=st["P"][:, :k, :], vg=st["vg"][:k], vp=st["vp"][:k], p=st["p"], p3=st["p3"][:k], ids=st["ids"], n_tracks0=n_tr,
                 t0=t0.cpu().numpy(), R0=R0.cpu().numpy().reshape(3, 3), res0=float(res0.item()), boxa=tuple(rois[0:4]), boxb=tuple(rois[4:8]),
-                loop_seconds=loop_seconds, klt_flags=st["klt_flags"])
+                loop_seconds=loop_seconds, klt_flags=st["klt_flags"], recoveries=ses.recoveries()[0])
 
 
 def _frame0_buffers(torch, nb, cap):
@@ -475,13 +492,14 @@ def session_streams(n):
 
 
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
-                  msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0):
+                  msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name]) of ONE frame size and
     length; every clip is a stream of a device-resident TrackerSession, so a frame step is one launch sequence for all the clips of a session
     (vh_session_step_v: each stream has its own clock).  `sessions`: the clips are split into this many sessions, each on its own HIP stream (0 = auto,
     session_groups(len(clips)): their one-workgroup-per-stream stages overlap the others' LK launches); results do not depend on it.  Frame 0 of the clips
     of a session runs as ONE vh_frame0_init_batch call on the device, its outputs feed vh_session_init_dev directly; nothing is read back before the last
-    frame.  use_harris / min_distance: the frame-0 detector, as in run_sequence.  Returns one
+    frame.  use_harris / min_distance: the frame-0 detector, as in run_sequence.  fallback: the recovery by feature matching, as in run_sequence (the failed streams
+    of a session share one vh_match_affine_batch call per step).  Returns one
     result dict per clip (the keys of run_sequence; `lines` = that clip's table and summary, printed through `out` if given), each equal to what
     run_sequence returns for the clip alone."""
     import time as _time
@@ -506,7 +524,8 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     sess = []
     for g in range(G):
         with torch.cuda.stream(hip_streams[g]):  # (a session's context serves one HIP stream: everything of session g is issued on stream g)
-            sess.append(TrackerSession(K, W, H, cap, nhist=n, batch=len(members[g]), lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame))
+            sess.append(TrackerSession(K, W, H, cap, nhist=n, batch=len(members[g]), lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame,
+                                       fallback=fallback, fallback_params=fallback_params))
     plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
     times = np.stack([np.asarray(c["times"], np.float32) for c in clips])  # [clip, frame]
     fnos = np.stack([np.asarray(c.get("frame_numbers", np.arange(n)), np.float32) for c in clips])
@@ -548,7 +567,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
                 out(ln)
         results.append(dict(S=S, B=st["B"], P=st["P"][:, :k, :], vg=st["vg"][:k], vp=st["vp"][:k], p=st["p"], p3=st["p3"][:k], ids=st["ids"], n_tracks0=k,
                             t0=t0.cpu().numpy(), R0=R0.cpu().numpy().reshape(3, 3), res0=float(res0.item()), boxa=rois[0:4], boxb=rois[4:8],
-                            klt_flags=st["klt_flags"], lines=lines, seconds=seconds, ms_per_frame=1e3 * loop_seconds / (n - 1), sessions=G))
+                            klt_flags=st["klt_flags"], recoveries=sess[owner[b]].recoveries()[slot[b]], lines=lines, seconds=seconds, ms_per_frame=1e3 * loop_seconds / (n - 1), sessions=G))
     return results
 
 
@@ -564,13 +583,14 @@ def main(argv=None):
     ap.add_argument("--border", type=int, nargs=2, default=None, help="ROI border around the plate (vidExample.py:108 uses 700 500; the 1024 x 768 stills fixture needs 180 140)")
     ap.add_argument("--msv-frame", type=int, default=5)
     ap.add_argument("--min-distance", type=float, default=0.0, help="minimum distance between the frame-0 corners (vidExample.py:110 uses 0)")
+    ap.add_argument("--fallback", action="store_true", help="recover the motion by feature matching when the coarse KLT stage fails (one host read per frame)")
     ap.add_argument("--shi-tomasi", action="store_true", help="frame-0 corners by the minimum-eigenvalue detector instead of Harris")
     a = ap.parse_args(argv)
     d = np.load(a.clip)
     fr = d[f"{a.seq}_frames"]
     border = tuple(a.border) if a.border else ((700, 500) if fr.shape[2] >= 1900 else (180, 140))
     run_sequence(fr, d[f"{a.seq}_q"], d[f"{a.seq}_K"], times=d[f"{a.seq}_times"], roi_border=border, msv_frame=a.msv_frame,
-                 name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance)
+                 name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback)
 
 
 if __name__ == "__main__":
