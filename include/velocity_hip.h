@@ -95,7 +95,8 @@ VH_API int vh_bounding_rect(vh_ctx* ctx, const float* p, int n, int imw, int imh
 
 /* ---- tracker -------------------------------------------------------------------------------------------------- */
 /* cv2calcOpticalFlowPyrLK(im1, im2, p1, None, fbt, **lk), utils/KLT.py:37-51.  fbt < 0 means fbt=None.
- * Outputs: p2 n x 2, v n (uint8 0/1), err n (may be NULL), fbe n (may be NULL). */
+ * Outputs: p2 n x 2, v n (uint8 0/1), err n (may be NULL), fbe n (may be NULL).
+ * Windows from 3 to 165: a larger one does not fit a workgroup's LDS and is refused (non-zero, vh_last_error names it) before anything is enqueued. */
 VH_API int vh_pyr_lk(vh_ctx* ctx, const uint8_t* im1, const uint8_t* im2, int w, int h, int stride1, int stride2, const float* p1,
                      int n, const vh_lk_params* lk_host, float fbt, float* p2, uint8_t* v, float* err, float* fbe, void* stream);
 /* cv2.estimateAffine2D(from[valid], to[valid], method=RANSAC), utils/KLT.py:116,127 (deterministic stand-in, see

@@ -614,6 +614,11 @@ extern "C" VH_API int vh_pyr_lk(vh_ctx* c, const uint8_t* im1, const uint8_t* im
     if (!c || !lk || lk->win < 3 || lk->max_level < 0 || w < 4 || h < 4 || stride1 < w || stride2 < w || n < 0)
         return vh_fail(-1, "vh_pyr_lk: bad arguments (need win >= 3, max_level >= 0, w, h >= 4, strides >= w)");
     if (w > c->max_w || h > c->max_h || n > c->max_pts) return vh_fail(-1, "vh_pyr_lk: image or point count exceeds the workspace");
+    if (!vh_lk_window_fits(lk->win)) {  // refused before anything is enqueued: no descriptor store, no pyramid level
+        char msg[128];
+        snprintf(msg, sizeof(msg), "vh_pyr_lk: win = %d is too large for LDS (the largest window is %d)", lk->win, vh_lk_max_window());
+        return vh_fail(-2, msg);
+    }
     if (n <= 0) return 0;
     VH_BIND(c, stream);
     hipStream_t s = bound_.s;

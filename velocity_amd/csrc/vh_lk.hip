@@ -1991,6 +1991,19 @@ const char* vh_lk_route_name(int route, int win)
     }
 }
 
+// Dynamic LDS of the per-sample kernel (the only one for windows above 63): the packed gradient pair (int32) and the template sample (int16) of every
+// window pixel, in whole passes of the wavefront.  A workgroup has 160 KiB, so the largest window any route can solve is 165 x 165 (166 is refused).
+// vh_pyr_lk asks vh_lk_window_fits before it enqueues anything; the other callers (vh_klt_regional, vh_klt_main, the session) still learn it from
+// vh_launch_lk's -2, after their set-up kernels are queued.
+static size_t lk_per_sample_lds(int win) { return (size_t)(((long long)win * win + 63) / 64) * 64 * 6; }
+bool vh_lk_window_fits(int win) { return win >= 1 && lk_per_sample_lds(win) <= 160 * 1024; }
+int vh_lk_max_window()
+{
+    int win = 64;
+    while (vh_lk_window_fits(win + 1)) win++;
+    return win;
+}
+
 int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, int win, hipStream_t s, int* route_out, int* tpw_out)
 {
     if (route_out) *route_out = 0;
@@ -2011,9 +2024,8 @@ int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, i
         return launch_strip<0>(job_tab, tab_stride, batch, max_n, win, s);
     default: break;
     }
-    const int kmax = (win * win + 63) / 64;
-    const size_t lds = (size_t)kmax * 64 * 6;
-    if (lds > 160 * 1024) return -2;
+    if (!vh_lk_window_fits(win)) return -2;
+    const size_t lds = lk_per_sample_lds(win);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
