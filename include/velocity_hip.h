@@ -193,17 +193,29 @@ VH_API int vh_nls_batch_phase(vh_ctx* ctx, const double* K_host, const double* z
                               size_t* span_offset, size_t* span_doubles, void* stream);
 
 /* ---- frame-0 initialisation ---------------------------------------------------------- */
-/* cv2.goodFeaturesToTrack(roi, maxCorners, qualityLevel, 0, blockSize=block, useHarrisDetector=True, k), vidExample.py:110 (other detectors,
- * min_distance and masks: vh_good_features2).
- * corners: device float [max_corners x 2] (x, y) sorted by response; count: device int[1] */
+/* ONE detector and ONE frame-0 sequence serve every entry of this section: the batch kernels of vh_frame0_init_batch, with the clip as a grid
+ * dimension.  vh_good_features and vh_good_features2 run the detector on one whole-image clip, vh_frame0_init is vh_frame0_init_batch with nb = 1.
+ * Scratch: per context, about 12 bytes per ROI pixel of a chunk of clips, created by the first call that needs it or by vh_init_reserve /
+ * vh_init_reserve_batch; the cornerSubPix masks belong to the context from vh_ctx_create on. */
+/* cv2.goodFeaturesToTrack(roi, maxCorners, qualityLevel, 0, blockSize=block, useHarrisDetector=True, k), vidExample.py:110: vh_good_features2 with
+ * use_harris = 1, min_distance = 0 and no mask (the same code; the response, the candidates and their order are described there).
+ * corners: device float [max_corners x 2] (x, y) sorted by response; count: device int[1].  -1: a null pointer, w or h < 3, stride < w,
+ * max_corners < 1, block outside 1..15. */
 VH_API int vh_good_features(vh_ctx* ctx, const uint8_t* im, int w, int h, int stride, int max_corners, double quality, int block,
                             double k, float* corners, int* count, void* stream);
-/* cv2.cornerSubPix(im, pts, (win,win), (-1,-1), (EPS+MAX_ITER, max_iter, eps)), vidExample.py:113-115.  pts refined in place */
+/* cv2.cornerSubPix(im, pts, (win,win), (-1,-1), (EPS+MAX_ITER, max_iter, eps)), vidExample.py:113-115.  pts refined in place.  Needs no scratch:
+ * one kernel launch, legal under stream capture on any context. */
 VH_API int vh_corner_subpix(vh_ctx* ctx, const uint8_t* im, int w, int h, int stride, float* pts, int n, int win, int max_iter,
                             double eps, void* stream);
 
-/* cv2.cornerSubPix / goodFeaturesToTrack scratch of this context (Harris planes, sort keys, Gaussian masks): created by the first frame-0 call, or
- * explicitly here -- e.g. before a stream capture, inside which it cannot be allocated.  Sized for max(w x h, the context's max_w x max_h). */
+/* The detector scratch of this context (response planes, candidate keys, counters, descriptors) for the one-image entries: created by the first
+ * frame-0 call for the image at hand, or explicitly here -- e.g. before a stream capture, inside which it can be neither allocated nor grown (-6;
+ * vh_last_error names this call).  After it, vh_good_features, vh_good_features2, vh_corner_subpix and vh_frame0_init on an image (ROI) of up to
+ * max(w x h, the context's max_w x max_h) pixels only queue kernels.  It keeps the chunk size the context has (at least one clip) and does not fix it:
+ * the chunking of vh_frame0_init_batch is vh_init_reserve_batch's to set.
+ * One case it does not cover: max_corners > 2048 (with min_distance < 1) sorts through a second scratch sized by the budget, which exists only after
+ * one eager call with that budget; inside a capture such a call returns -6 until then.  (The first-generation detector, a full sort of every pixel,
+ * had no such case.) */
 VH_API int vh_init_reserve(vh_ctx* ctx, int w, int h, void* stream);
 /* Frame-0 initialisation of one video, vidExample.py:105-127, as ONE device-resident launch sequence (no host round trip between its steps):
  *   boxa / boxb = boundingRect(q, imshape, border=(0,0) / (border_x, border_y))                (:107-108, images.py:9-19; q_host: the 4 clicked corners, host)
@@ -215,13 +227,16 @@ VH_API int vh_init_reserve(vh_ctx* ctx, int w, int h, void* stream);
  *   vp = insidebbox(p, boxa)                                                                                                   (:126, images.py:22-27)
  * Outputs (device, sized for 4 + max_corners tracks): p_out [.. x 2] float32, p3_out [.. x 3] float64, vp_out uint8, t_out float[3], R_out double[9]
  * (float32-rounded like NLS.py:180), res_out double[1], n_out int[1] = 4 + corners found (rows beyond it: vp 0, p3 0).  roi_host (may be NULL): host
- * int[8] = boxa, boxb.  The outputs feed vh_session_init directly. */
+ * int[8] = boxa, boxb.  The outputs feed vh_session_init directly.
+ * This is vh_frame0_init_batch (below) with nb = 1, whose output layout for one clip is exactly this one.  Every argument is checked before anything
+ * is queued or written, roi_host included: -1 for a null argument, w or h < 3, stride < w, max_corners < 1, block outside 1..15, subpix_win outside
+ * 1..7, or an empty plate ROI (boxb below 3 x 3). */
 VH_API int vh_frame0_init(vh_ctx* ctx, const uint8_t* im, int w, int h, int stride, const float* q_host, const double* K_host,
                           const double* plate_host, int border_x, int border_y, int max_corners, double quality, int block, double k,
                           int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out, uint8_t* vp_out, float* t_out,
                           double* R_out, double* res_out, int* n_out, int* roi_host, void* stream);
 /* (vh_version >= 106) frame-0 initialisation of nb clips of ONE frame size, vidExample.py:105-127 for each, as one device launch sequence per chunk of
- * clips (below).  Every clip's results are bit-identical to vh_frame0_init on that clip alone.
+ * clips (below).  A clip's results do not depend on the clips beside it: they are what vh_frame0_init (this call with nb = 1) gives for it.
  *   frames_host: host array of nb device pointers (w x h frames, row stride `stride`); q_host: host float [nb][4][2]; K_host, plate_host and every
  *   parameter after them are shared by the batch.  Each clip's boxa / boxb come from its own q, so the ROI sizes may differ between clips.
  *   Outputs (device, clip b in row b, rows dense at cap = 4 + max_corners): p_out [nb][cap][2], p3_out [nb][cap][3], vp_out [nb][cap], t_out [nb][3],
@@ -232,7 +247,8 @@ VH_API int vh_frame0_init(vh_ctx* ctx, const uint8_t* im, int w, int h, int stri
  * Scratch: per context, about 12 bytes per ROI pixel of a chunk.  vh_init_reserve_batch(ctx, nb, w, h) sizes it for nb clips of a w x h ROI and fixes
  * the chunk size: a call with more clips runs in chunks of that many (results do not depend on the chunking).  Without it, the first call sizes the
  * scratch for as many of its clips as fit 1 GiB, later calls grow it the same way.  Once the scratch fits, a call only queues kernels (legal under
- * stream capture); growth inside a capture returns -6, as does a max_corners above 2048 whose sort scratch does not exist yet. */
+ * stream capture); allocation or growth inside a capture returns -6, as does a max_corners above 2048 whose sort scratch does not exist yet (one
+ * eager call with that budget creates it). */
 VH_API int vh_init_reserve_batch(vh_ctx* ctx, int nb, int w, int h, void* stream);
 VH_API int vh_frame0_init_batch(vh_ctx* ctx, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
                                 const double* K_host, const double* plate_host, int border_x, int border_y, int max_corners, double quality,
@@ -240,15 +256,18 @@ VH_API int vh_frame0_init_batch(vh_ctx* ctx, int nb, const uint8_t* const* frame
                                 uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host, void* stream);
 
 /* (vh_version >= 107) cv2.goodFeaturesToTrack(im, max_corners, quality, min_distance, mask=mask, blockSize=block, useHarrisDetector=use_harris, k) on
- * the batch kernels of vh_frame0_init_batch with one clip.  vh_good_features above stays the entry of the reference's call (Harris, min_distance 0).
- *   Response: the integer Sobel pair and block x block sums of vh_good_features, scaled by s2 = (float)(scale^2), scale = 1 / (4 block 255); Harris
- *   (use_harris != 0) as there, otherwise the minimum eigenvalue (a = sxx s2 / 2, b = sxy s2, c = syy s2 / 2, (a + c) - sqrt((a - c)^2 + b^2)), float32
+ * the batch kernels of vh_frame0_init_batch with one clip.  vh_good_features above is this call with use_harris = 1, min_distance = 0 and no mask:
+ * the same code, kept as the entry of the reference's call.
+ *   Response: the integer Sobel pair (aperture 3, REFLECT_101) and the block x block sums of its products, exact integers, scaled by
+ *   s2 = (float)(scale^2), scale = 1 / (4 block 255): a = sxx s2, b = sxy s2, c = syy s2.  Harris (use_harris != 0): (a c - b b) - (k (a + c)) (a + c);
+ *   otherwise the minimum eigenvalue (a = sxx s2 / 2, b = sxy s2, c = syy s2 / 2, (a + c) - sqrt((a - c)^2 + b^2)), float32
  *   with round-to-nearest at every step (a correctly rounded sqrt).  The threshold is quality times the maximum over the pixels where mask != 0 (all pixels without a mask); the
  *   candidates are the interior 3x3 maxima of the thresholded response that the mask keeps, ordered by response (ties: larger pixel index first).
  *   min_distance < 1 (negative included): the first max_corners candidates.  Otherwise a candidate is kept iff no corner kept before it lies at
  *   squared distance < min_distance^2, until max_corners are kept -- for integer positions exactly OpenCV's grid of cvRound(min_distance) cells.
  *   mask: device uint8 w x h (row stride mask_stride), or NULL.  corners: device float [max_corners x 2] (x, y); count: device int[1].
- *   -1: bad arguments, max_corners < 1 included, or a NaN / infinite min_distance.  Scratch: that of vh_frame0_init_batch (one clip of w x h). */
+ *   -1: bad arguments, max_corners < 1 included, or a NaN / infinite min_distance.  Scratch: that of vh_frame0_init_batch (one clip of w x h; vh_init_reserve).
+ *   Inside a stream capture max_corners > 2048 with min_distance < 1 needs one eager call with that budget first (vh_init_reserve, above). */
 VH_API int vh_good_features2(vh_ctx* ctx, const uint8_t* im, int w, int h, int stride, const uint8_t* mask, int mask_stride, int max_corners,
                              double quality, double min_distance, int block, int use_harris, double k, float* corners, int* count, void* stream);
 /* (vh_version >= 107) vh_frame0_init_batch with the detector of vh_good_features2 (no mask): use_harris = 0 selects the minimum eigenvalue, min_distance

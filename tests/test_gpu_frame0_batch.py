@@ -1,8 +1,10 @@
-"""Frame 0 of many clips in one launch sequence (vh_frame0_init_batch, torch.ops.velocity_hip.frame0_init, driver.frame0_batch, run_sequences).
+"""Frame 0 of many clips in one launch sequence (vh_frame0_init_batch, torch.ops.velocity_hip.frame0_init, driver.frame0_batch, run_sequences) and of one
+clip (vh_frame0_init, the batch of one).
 
-Every clip of a batch must be bit-identical to vh_frame0_init on that clip alone (Harris corners, cornerSubPix, plate pose, world points, masks, ROIs),
-whatever the chunking, the stream, a graph capture or a second context running beside it; against the oracle's frame0 the corners / masks / ROIs are
-exact and the pose holds the tolerances of test_gpu_stills._run_both."""
+Against the oracle's frame0 the corners / masks / ROIs are exact and the pose holds the tolerances of test_gpu_stills._run_both: that comparison carries
+the arithmetic.  Every clip of a batch must also be bit-identical to vh_frame0_init on that clip alone (Harris corners, cornerSubPix, plate pose, world
+points, masks, ROIs), whatever the chunking, the stream, a graph capture or a second context running beside it: both run the same kernels, so this
+guards the one-clip wrapper's output layout and the independence of a clip from its neighbours."""
 import ctypes as C
 import os
 
@@ -179,7 +181,7 @@ def test_chunked_call_equals_one_chunk(stills):
 
 def test_many_candidates_select_and_large_max_corners(stills):
     """A textured frame with ~23 k candidates in a full-frame ROI: max_corners 1000 (radix select, LDS sort) and 3000 (above the in-LDS bound: the segmented
-    sort route) both equal the single call."""
+    sort route) both equal the oracle and the single call, for both clips."""
     from velocity_amd import _lib as L
     from velocity_amd import synth
 
@@ -195,9 +197,58 @@ def test_many_candidates_select_and_large_max_corners(stills):
         L.check(rc, "vh_frame0_init_batch")
         got = _host(outs, rois, 2)
         assert got["n"][0] == 4 + mc and got["n"][1] == 4 + mc, got["n"]
-        _same_as_single(got, 0, _single(f, q, K, border=border, max_corners=mc))
-        _same_as_single(got, 1, _single(f2, q, K, border=border, max_corners=mc))
-    _same_as_oracle(got, 0, _oracle(f, q, K, border=border, max_corners=3000))
+        for b, frame in enumerate((f, f2)):
+            _same_as_single(got, b, _single(frame, q, K, border=border, max_corners=mc))
+            _same_as_oracle(got, b, _oracle(frame, q, K, border=border, max_corners=mc))
+
+
+def test_single_call_on_a_tiny_frame_equals_the_oracle():
+    """vh_frame0_init at the ABI on a 96 x 64 frame whose border-clipped plate ROI (30 x 15) is smaller than one 64 x 16 detector tile, and on the same
+    frame as uniform grey (no corner: exactly the 4 plate corners)."""
+    from velocity_amd import synth
+
+    W, H, border = 96, 64, (8, 5)
+    K = np.array([[100.0, 0, 0], [0, 100.0, 0], [48.0, 32.0, 1.0]])
+    q = _plate_quad(K, -0.05, -0.02, 3.0)
+    textured = synth.render_frame(W, H, synth.AffineMotion(W, H), 0, seed=0x5EED).numpy()
+    for frame, corners in ((textured, True), (np.full((H, W), 128, np.uint8), False)):
+        ref = _oracle(frame, q, K, border=border)
+        x0, x1, y0, y1 = ref["boxb"]
+        assert 3 <= x1 - x0 < 64 and 3 <= y1 - y0 < 16, ref["boxb"]
+        assert (len(ref["p"]) > 8) if corners else (len(ref["p"]) == 4), len(ref["p"])
+        one = _single(frame, q, K, border=border)
+        got = {key: np.asarray(val)[None] for key, val in one.items()}
+        _same_as_oracle(got, 0, ref)
+        assert np.all(one["p3"][one["n"]:] == 0) and np.all(one["vp"][one["n"]:] == 0)  # rows beyond n: zero
+
+
+def test_single_call_refuses_what_it_always_refused():
+    """vh_frame0_init's rejections as the batch of one: a null argument, bad arguments and an empty plate ROI return -1, name the entry, queue nothing."""
+    from velocity_amd import _lib as L
+
+    torch = L.torch_cuda()
+    W, H = 96, 64
+    ws = L.Workspace(1, W, H, 64)
+    f = torch.full((H, W), 128, dtype=torch.uint8, device="cuda")
+    K64, plate = L.host_K(np.array([[100.0, 0, 0], [0, 100.0, 0], [48.0, 32.0, 1.0]])), _plate()
+    inside = np.float32([[40, 29], [53, 29], [53, 34], [40, 34]])
+    outs = _outputs(torch, 1, 54)
+
+    def call(q, w=W, block=5, null=None):
+        p, p3, vp, t, R, res, n = (None if k == null else L.dptr(x) for k, x in enumerate(outs))
+        rois = (C.c_int * 8)()
+        q = np.ascontiguousarray(q, np.float32)
+        return ws.lib.vh_frame0_init(ws.handle, L.dptr(f), w, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p), plate.ctypes.data_as(L.f64p), 8, 5, 50,
+                                     0.01, block, 0.04, 5, 100, 0.001, p, p3, vp, t, R, res, n, rois, L.stream_ptr())
+
+    for kwargs, word in ((dict(q=inside, null=4), b"null argument"), (dict(q=inside, w=2), b"bad arguments"), (dict(q=inside, block=16), b"bad arguments"),
+                         (dict(q=inside + np.float32([5000, 0])), b"empty")):
+        assert call(**kwargs) == -1
+        msg = ws.lib.vh_last_error()
+        assert msg.startswith(b"vh_frame0_init:") and word in msg, msg
+    torch.cuda.synchronize()
+    assert bool((outs[0] == SENT_F).all()) and int(outs[6].item()) == SENT_I
+    assert call(inside) == 0
 
 
 def test_graph_capture_replays_the_eager_result(stills):

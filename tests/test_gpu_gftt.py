@@ -1,4 +1,4 @@
-"""goodFeaturesToTrack with the Shi-Tomasi detector, minDistance and a mask on the device (vh_good_features2, vh_frame0_init_batch2, the
+"""goodFeaturesToTrack on the device: the Harris and Shi-Tomasi detectors, minDistance and a mask (vh_good_features, vh_good_features2, vh_frame0_init_batch2, the
 goodFeaturesToTrack shim, torch.ops.velocity_hip.good_features, driver.run_sequences).  Every comparison is bit-exact: coordinates, order and count
 against tests/gftt_ref.py, which tests/test_gftt_cpu.py pins to the oracle (Harris, minDistance 0) and to OpenCV's spacing grid."""
 import ctypes as C
@@ -163,6 +163,94 @@ def test_old_parameters_through_the_new_entry(images):
             rc, new = _gf2(t, mc, 0.0, block, True)
             assert rc == 0 and np.array_equal(new, old), (block, mc)
             assert np.array_equal(new, KO.good_features(img, max_corners=mc, quality=0.01, block=block, k=0.04))
+
+
+def _gf1(img_t, mc, block, quality=0.01, k=0.04):
+    """vh_good_features through ctypes -> corners [n, 2] numpy."""
+    import torch
+
+    from velocity_amd import _lib as L
+
+    h, w = img_t.shape
+    ws = L.workspace()
+    out = torch.full((mc, 2), -7.0, dtype=torch.float32, device="cuda")
+    cnt = torch.full((1,), -5, dtype=torch.int32, device="cuda")
+    L.check(ws.lib.vh_good_features(ws.handle, L.dptr(img_t), w, h, img_t.stride(0), mc, quality, block, k, L.dptr(out), L.dptr(cnt), L.stream_ptr()),
+            "vh_good_features")
+    return out[:int(cnt.item())].cpu().numpy()
+
+
+SMALL_SIZES = ((3, 3), (4, 3), (5, 5), (7, 40), (63, 15), (64, 16), (65, 17), (129, 33), (200, 9))  # (w, h) around the detector's 64 x 16 tile
+SMALL_BLOCKS = (1, 2, 4, 5, 15)
+SMALL_BUDGETS = (1, 50, 3000)  # a one-key select, the in-LDS sort, the segmented sort
+STRIDED = (65, 17)  # this size runs as a view of a larger tensor
+
+
+def _small_images():
+    rng = np.random.default_rng(7)
+    return {wh: rng.integers(0, 256, (wh[1], wh[0]), dtype=np.uint8) for wh in SMALL_SIZES}
+
+
+def _small_refs(img):
+    """{(block, max_corners): (Harris corners of the C oracle, Shi-Tomasi corners of gftt_ref)}, with the counts the test relies on asserted."""
+    w, h = img.shape[1], img.shape[0]
+    refs = {}
+    for block in SMALL_BLOCKS:
+        for mc in SMALL_BUDGETS:
+            refs[block, mc] = (KO.good_features(img, mc, 0.01, block, 0.04), G.good_features(img, mc, 0.01, 0.0, block=block, use_harris=False))
+        n = len(refs[block, 3000][0])
+        if block == 1:
+            assert n == 0, (w, h, n)  # a rank-one structure tensor has no positive Harris response
+        elif w >= 7 and h >= 7:
+            assert n >= 1, (w, h, block)  # the case compares corners, not two empty lists
+    if (w, h) == (5, 5):  # 25 pixels, 9 of them interior: some blocks leave no candidate, not all
+        assert any(len(refs[block, 3000][0]) for block in SMALL_BLOCKS[1:])
+    return refs
+
+
+@pytest.mark.parametrize("size", SMALL_SIZES, ids=lambda wh: f"{wh[0]}x{wh[1]}")
+def test_small_and_awkward_shapes_through_both_entries(size):
+    """The only detector on images below, at and just past its 64 x 16 tile, with even blocks and a halo wider than the image (block 15: REFLECT_101
+    folds more than once), at budgets that take the one-key select, the in-LDS sort and the segmented sort: vh_good_features and vh_good_features2
+    equal the C oracle bit for bit (Harris), vh_good_features2 equals gftt_ref (Shi-Tomasi)."""
+    import torch
+
+    img = _small_images()[size]
+    w, h = size
+    refs = _small_refs(img)
+    if size == STRIDED:
+        big = torch.full((h + 9, w + 30), 255, dtype=torch.uint8, device="cuda")
+        big[4:4 + h, 11:11 + w] = torch.from_numpy(img).cuda()
+        t = big[4:4 + h, 11:11 + w]
+        assert t.stride(0) != w
+    else:
+        t = torch.from_numpy(img).cuda()
+    for (block, mc), (harris, shi) in refs.items():
+        assert np.array_equal(_gf1(t, mc, block), harris), ("vh_good_features", block, mc)
+        rc, got = _gf2(t, mc, 0.0, block, True)
+        assert rc == 0 and np.array_equal(got, harris), ("vh_good_features2 harris", block, mc)
+        rc, got = _gf2(t, mc, 0.0, block, False)
+        assert rc == 0 and np.array_equal(got, shi), ("vh_good_features2 shi-tomasi", block, mc)
+
+
+def test_equal_responses_keep_the_larger_pixel_index_first():
+    """A periodic 80 x 32 image whose candidates share a few exactly equal responses: the order among equals (larger pixel index first) must hold through
+    the select threshold (10 corners: the threshold falls inside a run of equal responses) and the full list (3000)."""
+    import torch
+
+    img = np.tile(np.array([[0, 255, 0, 0], [255, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0]], np.uint8), (8, 20))
+    assert img.shape == (32, 80)
+    t = torch.from_numpy(img).cuda()
+    full = KO.good_features(img, 3000, 0.01, 3, 0.04)
+    resp = G.response(img, 3, True)
+    vals = resp[full[:, 1].astype(int), full[:, 0].astype(int)]
+    assert len(full) > 100 and len(np.unique(vals)) < len(full) // 4 and vals[9] == vals[10], "the image must give many equal responses, across the cut at 10"
+    ten = KO.good_features(img, 10, 0.01, 3, 0.04)
+    assert np.array_equal(ten, full[:10])
+    for mc, want in ((10, ten), (3000, full)):
+        assert np.array_equal(_gf1(t, mc, 3), want), mc
+        rc, got = _gf2(t, mc, 0.0, 3, True)
+        assert rc == 0 and np.array_equal(got, want), mc
 
 
 def test_torch_op_equals_the_shim(images):

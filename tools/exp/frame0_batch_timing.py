@@ -1,8 +1,8 @@
-"""What frame 0 costs per clip: the per-clip vh_frame0_init loop (what run_sequences did before vh_version 106) against one vh_frame0_init_batch call per
-session, on synthetic 1920 x 1080 clips (synth.render_frame, one seed per clip; the plate quad is worldPointsLicensePlate("Chile") projected through
+"""What frame 0 costs per clip: a per-clip loop of vh_frame0_init calls -- each a batch of ONE clip through the same kernels; until vh_version 106 the
+loop run_sequences ran, then on the first-generation detector that sorted every ROI pixel -- against one vh_frame0_init_batch call per session, on synthetic 1920 x 1080 clips (synth.render_frame, one seed per clip; the plate quad is worldPointsLicensePlate("Chile") projected through
 synth.K_1080P at 3.5 - 5 m, a different position per clip), roi_border (700, 500), 1000 corners.  Clips are grouped into sessions as run_sequences groups them.
 
-For every size: (a) vh_frame0_init + vh_session_init_dev per clip, (b) vh_frame0_init_batch per session + vh_session_init_dev per clip; warmed up, each
+For every size: (a) vh_frame0_init (a one-clip batch per call) + vh_session_init_dev per clip, (b) vh_frame0_init_batch per session + vh_session_init_dev per clip; warmed up, each
 repetition ends in a device synchronise, a and b alternate; median / min / max.  The outputs of both paths are compared (n, p, t, R bit for bit).  For scale
 it also times the 19-step tracking loop of the same clips (run_sequences' loop_seconds).
 
@@ -69,7 +69,7 @@ class Setup:
         torch.cuda.synchronize()
 
     def run_a(self):
-        """vh_frame0_init + vh_session_init_dev per clip (the loop run_sequences ran before vh_frame0_init_batch)."""
+        """vh_frame0_init (a one-clip batch per call) + vh_session_init_dev per clip (the loop run_sequences ran before vh_frame0_init_batch)."""
         win, it, eps = SUBPIX
         for g, mem in enumerate(self.members):
             ses = self.sess[g]

@@ -66,7 +66,7 @@ for cname, key in (("FETCH_SIZE", "fetch_kib"), ("WRITE_SIZE", "write_kib")):
             continue
         per.setdefault(r["Kernel_Name"].replace("void ", "").split("(")[0], []).append(float(r["Counter_Value"]))
     nsteps = max(len(per.get("k_klt_setup", [])), 1)
-    _step_tot[key] = sum(sum(v) for k, v in per.items() if not k.startswith(("k_sess_init", "k_init_", "k_frame0"))) / nsteps
+    _step_tot[key] = sum(sum(v) for k, v in per.items() if not k.startswith(("k_sess_init", "k_init_", "k_frame0", "k_f0b_"))) / nsteps
     for k, v in per.items():
         n = len(v)
         v = v[n // 4:]  # drop the warm-up quarter

@@ -111,6 +111,8 @@ extern "C" VH_API int vh_ctx_create(vh_ctx** out, int batch, int max_w, int max_
         if (e == hipSuccess) e = hipMemset(hb[b].v_all, 1, max_pts);
     }
     if (e != hipSuccess) { (void)hipFree(c->arena); delete[] hb; delete c; vh_set_error("hipMemcpy(bufs)", e, __FILE__, __LINE__); return (int)e; }
+    const int mr = vh_subpix_masks_create(&c->subpix_mask);
+    if (mr) { (void)hipFree(c->arena); delete[] hb; delete c; return mr; }
     c->h_bufs = hb;
     *out = c;
     return 0;

@@ -1,18 +1,20 @@
 // Frame-0 initialisation: cv2.goodFeaturesToTrack(roi, 1000, 0.01, 0, blockSize=5,
 // useHarrisDetector=True) and cv2.cornerSubPix(im, p, (5,5), (-1,-1), (EPS+MAX_ITER, 100, 0.001)), vidExample.py:110-115.
 //
-// Harris: Sobel sums and the block x block sums of their products are exact integers (scaled once), the response is a
-// fixed float32 expression, the maximum is an order-independent atomic max on an order-preserving integer image of the
-// float, local maxima above quality * max are appended as 64-bit keys (response bits << 32 | pixel index) and sorted
-// descending with rocPRIM's device radix sort (ties: higher index first, like OpenCV's pointer comparison).
-// cornerSubPix: one thread per corner runs OpenCV's iteration verbatim (float32 bilinear patch, float64 accumulation in
-// row-major order), so results are bit-identical to the CPU restatement; the Gaussian mask is computed once on the host.
+// ONE detector serves every entry: the k_f0b_* kernels, with the clip (an image or the plate ROI of a frame) as a grid dimension.  vh_good_features and
+// vh_good_features2 run it on one whole-image clip, vh_frame0_init is vh_frame0_init_batch with one clip, vh_detect_images (vh_match.hip) runs it on images
+// of different sizes.  Sobel sums and the block x block sums of their products are exact integers (scaled once), the response (Harris or the minimum
+// eigenvalue) is a fixed float32 expression, the maximum is an order-independent atomic max on an order-preserving integer image of the float.  The
+// thresholded 3x3 local maxima are compacted per clip as 64-bit keys (response bits << 32 | pixel index); the max_corners largest are found by a radix
+// select and sorted descending (in LDS up to 2048 keys, by rocPRIM's segmented sort above; ties: higher index first, like OpenCV's pointer
+// comparison) -- no sort over every pixel.  min_distance >= 1 walks the candidates greedily instead (k_f0b_spread).
+// cornerSubPix: one thread per corner runs OpenCV's iteration verbatim (float32 bilinear patch, float64 accumulation in row-major order), so results
+// are bit-identical to the CPU restatement; the Gaussian masks are computed once per context on the host (vh_subpix_masks_create).
 #include <math.h>
 #include <string.h>
 
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <vector>
@@ -28,82 +30,6 @@ __device__ __forceinline__ float ord2f(unsigned u)
 {
     const unsigned b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
     return __uint_as_float(b);
-}
-
-// Sobel 3x3 (aperture 3) with REFLECT_101, packed (dx, dy) int16 per pixel
-__global__ __launch_bounds__(256) void k_init_sobel(const uint8_t* im, int w, int h, size_t st, int* dxy)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
-    const int xm = vh_reflect101(x - 1, w), xp = vh_reflect101(x + 1, w), ym = vh_reflect101(y - 1, h), yp = vh_reflect101(y + 1, h);
-    const uint8_t *r0 = im + (size_t)ym * st, *r1 = im + (size_t)y * st, *r2 = im + (size_t)yp * st;
-    const int dx = (r0[xp] - r0[xm]) + 2 * (r1[xp] - r1[xm]) + (r2[xp] - r2[xm]);
-    const int dy = (r2[xm] - r0[xm]) + 2 * (r2[x] - r0[x]) + (r2[xp] - r0[xp]);
-    dxy[(size_t)y * w + x] = (dx & 0xffff) | (dy << 16);
-}
-
-// Harris response + global maximum
-__global__ __launch_bounds__(256) void k_init_harris(const int* dxy, int w, int h, int block, float s2, float kf, float* resp, unsigned* maxord)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    unsigned o = 0u;
-    if (x < w && y < h) {
-        const int r0 = block / 2;
-        int sxx = 0, sxy = 0, syy = 0;
-        for (int j = 0; j < block; j++) {
-            const int yy = vh_reflect101(y - r0 + j, h);
-            for (int i = 0; i < block; i++) {
-                const int xx = vh_reflect101(x - r0 + i, w);
-                const int v = dxy[(size_t)yy * w + xx];
-                const int a = (int)(short)(v & 0xffff), b = v >> 16;
-                sxx += a * a; sxy += a * b; syy += b * b;
-            }
-        }
-        const float a = __fmul_rn((float)sxx, s2), b = __fmul_rn((float)sxy, s2), c = __fmul_rn((float)syy, s2);
-        const float tr = __fadd_rn(a, c);
-        const float r = __fsub_rn(__fsub_rn(__fmul_rn(a, c), __fmul_rn(b, b)), __fmul_rn(__fmul_rn(kf, tr), tr));
-        resp[(size_t)y * w + x] = r;
-        o = f2ord(r);
-    }
-    for (int s = 32; s > 0; s >>= 1) o = max(o, (unsigned)__shfl_xor((int)o, s, 64));
-    if ((threadIdx.x & 63) == 0 && o) atomicMax(maxord, o);
-}
-
-// local maxima of the thresholded response (interior pixels) -> 64-bit sort keys
-__global__ __launch_bounds__(256) void k_init_candidates(const float* resp, int w, int h, const unsigned* maxord, double quality,
-                                                         unsigned long long* keys, unsigned* count, unsigned cap)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x < 1 || y < 1 || x >= w - 1 || y >= h - 1) return;
-    const float thr = (float)((double)ord2f(*maxord) * quality);
-    const float v0 = resp[(size_t)y * w + x];
-    if (!(v0 > thr)) return;  // THRESH_TOZERO; survivors are compared with the thresholded neighbours
-    float m = v0;
-#pragma unroll
-    for (int j = -1; j <= 1; j++)
-#pragma unroll
-        for (int i = -1; i <= 1; i++) {
-            const float u = resp[(size_t)(y + j) * w + x + i];
-            if (u > thr && u > m) m = u;
-        }
-    if (v0 == m && v0 != 0.f) {
-        const unsigned slot = atomicAdd(count, 1u);
-        if (slot < cap) keys[slot] = ((unsigned long long)__float_as_uint(v0) << 32) | (unsigned)(y * w + x);
-    }
-}
-
-__global__ void k_init_emit(const unsigned long long* sorted, const unsigned* count, unsigned cap, int max_corners, int w, float offx, float offy,
-                            float* corners, int* n_out)
-{
-    const unsigned n = min(min(*count, cap), (unsigned)max_corners);
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) *n_out = (int)n;
-    if (i < n) {
-        const unsigned idx = (unsigned)(sorted[i] & 0xffffffffull);
-        // + the ROI's origin (vidExample.py:110-112: `goodFeaturesToTrack(roi, ...) + np.float32([boxb[0], boxb[2]])`: integer-valued float32, exact)
-        corners[2 * i] = __fadd_rn((float)(idx % (unsigned)w), offx);
-        corners[2 * i + 1] = __fadd_rn((float)(idx / (unsigned)w), offy);
-    }
 }
 
 // cornerSubPix of corner q (k_init_subpix, k_f0b_subpix: one thread per corner)
@@ -165,31 +91,12 @@ __device__ __forceinline__ void subpix_corner(const uint8_t* im, int w, int h, s
     pts[2 * q] = cx; pts[2 * q + 1] = cy;
 }
 
-__global__ __launch_bounds__(64) void k_init_subpix(const uint8_t* im, int w, int h, size_t st, float* pts, int n, const int* n_dev, int win,
-                                                    int max_iter, double eps2, const float* mask)
+__global__ __launch_bounds__(64) void k_init_subpix(const uint8_t* im, int w, int h, size_t st, float* pts, int n, int win, int max_iter, double eps2,
+                                                    const float* mask)
 {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= (n_dev ? min(*n_dev, n) : n)) return;  // n_dev: the detector's count, still on the device (vh_frame0_init)
+    if (q >= n) return;
     subpix_corner(im, w, h, st, pts, q, win, max_iter, eps2, mask);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The scratch of the detector lives in the vh_ctx (vh_ws.hpp: InitScratch; round 4 kept ONE process-global copy: two contexts on two streams raced
-// on its keys / response / counters, a second device reused the first device's allocation).  It is created by the first frame-0 call of a context,
-// sized for max(the context's max_w x max_h, the image at hand), together with the Gaussian masks of cornerSubPix for every window half-size
-// (uploaded once, synchronously, at creation: the calls themselves are kernel launches only -- no host synchronisation, legal under stream capture
-// once the scratch exists; vh_init_reserve() creates it explicitly).  A larger image than the scratch was made for grows it after waiting for the
-// context's stream (refused while that stream is capturing).
-static void init_scratch_release(InitScratch& I)
-{
-    (void)hipFree(I.dxy); (void)hipFree(I.resp); (void)hipFree(I.keys); (void)hipFree(I.sorted);
-    (void)hipFree(I.counters); (void)hipFree(I.mask); (void)hipFree(I.sort_tmp);
-    memset(&I, 0, sizeof(I));
-}
-void vh_init_scratch_free(vh_ctx* c)
-{
-    if (c) init_scratch_release(c->init);
-    vh_init_batch_scratch_free(c);
 }
 
 static int subpix_mask_offset(int win)  // masks of half-sizes 1 .. win-1 come first
@@ -199,8 +106,9 @@ static int subpix_mask_offset(int win)  // masks of half-sizes 1 .. win-1 come f
     return off;
 }
 
-// cornerSubPix's Gaussian window for every half-size, computed once on the host in OpenCV's float32 order (bit-identical to the CPU restatement)
-static int subpix_masks_create(float** out)
+// cornerSubPix's Gaussian window for every half-size (679 floats), computed on the host in OpenCV's float32 order (bit-identical to the CPU
+// restatement) and uploaded synchronously: once per context, by vh_ctx_create, so that no frame-0 call ever uploads anything
+int vh_subpix_masks_create(float** out)
 {
     const int mask_floats = subpix_mask_offset(SUBPIX_MAXWIN + 1);
     VH_CHECK(hipMalloc((void**)out, sizeof(float) * mask_floats));
@@ -218,132 +126,39 @@ static int subpix_masks_create(float** out)
     }
     const hipError_t e = hipMemcpy(*out, hm, sizeof(float) * mask_floats, hipMemcpyHostToDevice);  // synchronous: hm dies here
     delete[] hm;
+    if (e != hipSuccess) { (void)hipFree(*out); *out = nullptr; }
     VH_CHECK(e);
     return 0;
 }
 
-static int init_reserve(vh_ctx* c, size_t pixels, hipStream_t s)
-{
-    InitScratch& I = c->init;
-    if (I.pixels >= pixels) return 0;
-    if (I.pixels) {  // growth: kernels queued through this context may still use the old buffers
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return vh_fail(-6, "frame-0 scratch must grow inside a stream capture: call vh_init_reserve(ctx, w, h) before capturing");
-        VH_CHECK(hipStreamSynchronize(s));
-    }
-    const size_t ctx_px = (size_t)c->max_w * (size_t)c->max_h;
-    if (pixels < ctx_px && ctx_px <= ((size_t)1 << 26)) pixels = ctx_px;  // any image the context was created for fits: no growth later
-    init_scratch_release(I);
-    VH_CHECK(hipMalloc((void**)&I.dxy, pixels * 4));
-    VH_CHECK(hipMalloc((void**)&I.resp, pixels * 4));
-    VH_CHECK(hipMalloc((void**)&I.keys, pixels * 8));
-    VH_CHECK(hipMalloc((void**)&I.sorted, pixels * 8));
-    VH_CHECK(hipMalloc((void**)&I.counters, 32));
-    {
-        const int r = subpix_masks_create(&I.mask);
-        if (r) return r;
-    }
-    size_t bytes = 0;
-    VH_CHECK(rocprim::radix_sort_keys_desc(nullptr, bytes, I.keys, I.sorted, pixels, 0, 64, 0));
-    VH_CHECK(hipMalloc(&I.sort_tmp, bytes));
-    I.sort_bytes = bytes;
-    I.pixels = pixels;
-    return 0;
-}
-
-extern "C" VH_API int vh_init_reserve(vh_ctx* c, int w, int h, void* stream)
-{
-    if (!c || w < 1 || h < 1) return vh_fail(-1, "vh_init_reserve: bad arguments");
-    VH_BIND(c, stream);
-    return init_reserve(c, (size_t)w * h, bound_.s);
-}
-
-// goodFeaturesToTrack on the stream s; (offx, offy) is added to every corner (the ROI origin); count stays on the device
-static int good_features_run(vh_ctx* c, const uint8_t* im, int w, int h, int stride, int max_corners, double quality, int block, double k, float offx,
-                             float offy, float* corners, int* count, hipStream_t s)
-{
-    const size_t pixels = (size_t)w * h;
-    int r = init_reserve(c, pixels, s);
-    if (r) return r;
-    InitScratch& I = c->init;
-    const double scale = 1.0 / (4.0 * block * 255.0);
-    VH_CHECK(hipMemsetAsync(I.counters, 0, 16, s));
-    VH_CHECK(hipMemsetAsync(I.keys, 0, pixels * 8, s));  // unused tail of the key buffer = 0 keys, which sort last
-    dim3 blk(256), grd((w + 63) / 64, (h + 3) / 4);
-    hipLaunchKernelGGL(k_init_sobel, grd, blk, 0, s, im, w, h, (size_t)stride, I.dxy);
-    hipLaunchKernelGGL(k_init_harris, grd, blk, 0, s, I.dxy, w, h, block, (float)(scale * scale), (float)k, I.resp, I.counters);
-    hipLaunchKernelGGL(k_init_candidates, grd, blk, 0, s, I.resp, w, h, I.counters, quality, I.keys, I.counters + 1, (unsigned)pixels);
-    // the candidate count stays on the device: the whole (zero padded) key buffer is sorted
-    size_t bytes = I.sort_bytes;
-    VH_CHECK(rocprim::radix_sort_keys_desc(I.sort_tmp, bytes, I.keys, I.sorted, pixels, 0, 64, s));
-    hipLaunchKernelGGL(k_init_emit, dim3((max_corners + 255) / 256), dim3(256), 0, s, I.sorted, I.counters + 1, (unsigned)pixels, max_corners, w, offx,
-                       offy, corners, count);
-    VH_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" VH_API int vh_good_features(vh_ctx* c, const uint8_t* im, int w, int h, int stride, int max_corners, double quality, int block,
-                                       double k, float* corners, int* count, void* stream)
-{
-    if (!c || w < 3 || h < 3 || max_corners < 1 || block < 1 || block > 15) return vh_fail(-1, "vh_good_features: bad arguments");
-    VH_BIND(c, stream);
-    return good_features_run(c, im, w, h, stride, max_corners, quality, block, k, 0.f, 0.f, corners, count, bound_.s);
-}
-
-static int corner_subpix_run(vh_ctx* c, const uint8_t* im, int w, int h, int stride, float* pts, int n, const int* n_dev, int win, int max_iter,
-                             double eps, hipStream_t s)
-{
-    int r = init_reserve(c, 1, s);
-    if (r) return r;
-    max_iter = max_iter < 1 ? 1 : (max_iter > 100 ? 100 : max_iter);
-    if (eps < 0) eps = 0;
-    hipLaunchKernelGGL(k_init_subpix, dim3((n + 63) / 64), dim3(64), 0, s, im, w, h, (size_t)stride, pts, n, n_dev, win, max_iter, eps * eps,
-                       c->init.mask + subpix_mask_offset(win));
-    VH_CHECK(hipGetLastError());
-    return 0;
-}
-
+// needs no detector scratch: the masks belong to the context
 extern "C" VH_API int vh_corner_subpix(vh_ctx* c, const uint8_t* im, int w, int h, int stride, float* pts, int n, int win, int max_iter,
                                        double eps, void* stream)
 {
     if (!c || win < 1 || win > SUBPIX_MAXWIN || n < 0) return vh_fail(-1, "vh_corner_subpix: bad arguments (window half-size 1..7)");
     if (n == 0) return 0;
     VH_BIND(c, stream);
-    return corner_subpix_run(c, im, w, h, stride, pts, n, nullptr, win, max_iter, eps, bound_.s);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// vh_frame0_init: vidExample.py:105-127 as one device-resident sequence
-// ---------------------------------------------------------------------------------------------------------------
-struct Frame0Job {
-    double K[9];
-    float q[8];          // the clicked plate corners (vidExample.py:104-106)
-    double plate[12];    // worldPointsLicensePlate (common.py:150-156), 4 x 3
-    int boxa[4];         // boundingRect(q, border 0): x0 x1 y0 y1
-    int max_n;           // 4 + max_corners
-};
-
-// p[0:4] = q (vidExample.py:116 `p = np.concatenate((q, p))`: the corners found sit behind them already)
-__global__ void k_frame0_head(Frame0Job J, float* p, double* plate)
-{
-    if (threadIdx.x < 8) p[threadIdx.x] = J.q[threadIdx.x];
-    if (threadIdx.x < 12) plate[threadIdx.x] = J.plate[threadIdx.x];
+    max_iter = max_iter < 1 ? 1 : (max_iter > 100 ? 100 : max_iter);
+    if (eps < 0) eps = 0;
+    hipLaunchKernelGGL(k_init_subpix, dim3((n + 63) / 64), dim3(64), 0, bound_.s, im, w, h, (size_t)stride, pts, n, win, max_iter, eps * eps,
+                       c->subpix_mask + subpix_mask_offset(win));
+    VH_CHECK(hipGetLastError());
+    return 0;
 }
 
 // p3 = addcol0(image2world(K, R, t, p).astype(float)) @ R + t (vidExample.py:119, common.py:49-55); vp = insidebbox(p, boxa) (:126, images.py:22-27);
 // n_out = 4 + corners found.  float64 throughout (the reference's float32 inverse carries ~1e-7; the contract is 1e-4): H = [R[0:2]; t] @ K, its
 // inverse by the adjugate, q = [x y 1] @ inv(H), (X, Y) = q[0:2] / q[2], p3 = X R[0] + Y R[1] + t
-// row i < max_n of one clip (k_frame0_world, k_f0b_world)
-__device__ __forceinline__ void frame0_world_row(int i, int n, const Frame0Job& J, const double* R, const float* t, const float* p, double* p3, uint8_t* vp)
+// row i < cap of one clip (k_f0b_world); boxa: the clip's boundingRect(q, border 0)
+__device__ __forceinline__ void frame0_world_row(int i, int n, const double* K, const int* boxa, const double* R, const float* t, const float* p, double* p3, uint8_t* vp)
 {
     if (i >= n) { vp[i] = 0; p3[3 * i] = 0; p3[3 * i + 1] = 0; p3[3 * i + 2] = 0; return; }
     const double td[3] = {(double)t[0], (double)t[1], (double)t[2]};
     double H[9];
     for (int c = 0; c < 3; c++) {
-        H[0 + c] = R[0] * J.K[0 + c] + R[1] * J.K[3 + c] + R[2] * J.K[6 + c];
-        H[3 + c] = R[3] * J.K[0 + c] + R[4] * J.K[3 + c] + R[5] * J.K[6 + c];
-        H[6 + c] = td[0] * J.K[0 + c] + td[1] * J.K[3 + c] + td[2] * J.K[6 + c];
+        H[0 + c] = R[0] * K[0 + c] + R[1] * K[3 + c] + R[2] * K[6 + c];
+        H[3 + c] = R[3] * K[0 + c] + R[4] * K[3 + c] + R[5] * K[6 + c];
+        H[6 + c] = td[0] * K[0 + c] + td[1] * K[3 + c] + td[2] * K[6 + c];
     }
     const double c00 = H[4] * H[8] - H[5] * H[7], c01 = H[5] * H[6] - H[3] * H[8], c02 = H[3] * H[7] - H[4] * H[6];
     const double det = H[0] * c00 + H[1] * c01 + H[2] * c02;
@@ -359,16 +174,7 @@ __device__ __forceinline__ void frame0_world_row(int i, int n, const Frame0Job& 
     p3[3 * i] = X * R[0] + Y * R[3] + td[0];
     p3[3 * i + 1] = X * R[1] + Y * R[4] + td[1];
     p3[3 * i + 2] = X * R[2] + Y * R[5] + td[2];
-    vp[i] = (xf > (float)J.boxa[0] && xf < (float)J.boxa[1] && yf > (float)J.boxa[2] && yf < (float)J.boxa[3]) ? 1 : 0;
-}
-__global__ __launch_bounds__(256) void k_frame0_world(Frame0Job J, const double* R, const float* t, const int* n_corners, const float* p, double* p3,
-                                                      uint8_t* vp, int* n_out)
-{
-    const int n = min(4 + *n_corners, J.max_n);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) *n_out = n;
-    if (i >= J.max_n) return;
-    frame0_world_row(i, n, J, R, t, p, p3, vp);
+    vp[i] = (xf > (float)boxa[0] && xf < (float)boxa[1] && yf > (float)boxa[2] && yf < (float)boxa[3]) ? 1 : 0;
 }
 
 // boundingRect(x, imshape, border) of a few host points (images.py:9-19; floor on all four edges like the device kernel k_bounding_rect)
@@ -386,65 +192,11 @@ static void host_bounding_rect(const float* q, int n, int imw, int imh, int bx, 
     roi[0] = x0 > 1 ? x0 : 1; roi[1] = x1 < imw ? x1 : imw; roi[2] = y0 > 1 ? y0 : 1; roi[3] = y1 < imh ? y1 : imh;
 }
 
-extern "C" VH_API int vh_frame0_init(vh_ctx* c, const uint8_t* im, int w, int h, int stride, const float* q_host, const double* K_host,
-                                     const double* plate_host, int border_x, int border_y, int max_corners, double quality, int block, double k,
-                                     int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out, uint8_t* vp_out, float* t_out,
-                                     double* R_out, double* res_out, int* n_out, int* roi_host, void* stream)
-{
-    if (!c || !im || !q_host || !K_host || !plate_host || !p_out || !p3_out || !vp_out || !t_out || !R_out || !res_out || !n_out)
-        return vh_fail(-1, "vh_frame0_init: null argument");
-    if (w < 3 || h < 3 || stride < w || max_corners < 1 || block < 1 || block > 15 || subpix_win < 1 || subpix_win > SUBPIX_MAXWIN)
-        return vh_fail(-1, "vh_frame0_init: bad arguments");
-    VH_BIND(c, stream);
-    hipStream_t s = bound_.s;
-    Frame0Job J;
-    memset(&J, 0, sizeof(J));
-    for (int i = 0; i < 9; i++) J.K[i] = K_host[i];
-    for (int i = 0; i < 8; i++) J.q[i] = q_host[i];
-    for (int i = 0; i < 12; i++) J.plate[i] = plate_host[i];
-    J.max_n = 4 + max_corners;
-    int boxb[4];
-    host_bounding_rect(q_host, 4, w, h, 0, 0, J.boxa);           // vidExample.py:107
-    host_bounding_rect(q_host, 4, w, h, border_x, border_y, boxb);  // :108
-    if (roi_host) for (int i = 0; i < 4; i++) { roi_host[i] = J.boxa[i]; roi_host[4 + i] = boxb[i]; }
-    const int rw = boxb[1] - boxb[0], rh = boxb[3] - boxb[2];
-    if (rw < 3 || rh < 3) return vh_fail(-1, "vh_frame0_init: the plate ROI is empty");
-    {
-        int r0 = init_reserve(c, (size_t)rw * rh, s);
-        if (r0) return r0;
-    }
-    // Harris corners of the ROI view im[boxb[2]:boxb[3], boxb[0]:boxb[1]] (:109-112), refined on the full image (:113-115), behind the 4 plate corners (:116)
-    int* n_corners = reinterpret_cast<int*>(c->init.counters) + 4;  // the detector's count (own word: k_frame0_world's blocks read it while one of them writes n_out)
-    int r = good_features_run(c, im + (size_t)boxb[2] * stride + boxb[0], rw, rh, stride, max_corners, quality, block, k, (float)boxb[0], (float)boxb[2],
-                              p_out + 8, n_corners, s);
-    if (r) return r;
-    r = corner_subpix_run(c, im, w, h, stride, p_out + 8, max_corners, n_corners, subpix_win, subpix_iter, subpix_eps, s);
-    if (r) return r;
-    // plate pose from the 4 corners (:118): estimateWorldCameraPose(K, q, plate, findR=True) from x0 = [rpy(I), (0, 0, 1)] (NLS.py:9,20)
-    double* plate_dev = c->d_small + 32;
-    hipLaunchKernelGGL(k_frame0_head, dim3(1), dim3(64), 0, s, J, p_out, plate_dev);
-    PoseJob P;
-    memset(&P, 0, sizeof(P));
-    for (int i = 0; i < 9; i++) { P.K[i] = K_host[i]; P.R[i] = (i % 4 == 0) ? 1.0 : 0.0; }
-    P.x0[5] = 1.0;
-    P.p = p_out; P.pw = plate_dev; P.n = 4; P.mode = 1;
-    P.t_out = t_out; P.R_out = R_out; P.res_out = res_out; P.p_proj = nullptr; P.info_out = reinterpret_cast<int*>(c->init.counters + 2);
-    static_assert(sizeof(PoseJob) <= sizeof(LKJob), "PoseJob must fit in the LKJob slot");
-    PoseJob* d = reinterpret_cast<PoseJob*>(&c->d_ws[0].lk);  // parked like every stateless call's descriptor
-    VH_CHECK(vh_store(d, P, s));
-    vh_launch_pose(d, sizeof(PoseJob), 1, 1, 4, s);
-    hipLaunchKernelGGL(k_frame0_world, dim3((J.max_n + 255) / 256), dim3(256), 0, s, J, R_out, t_out, n_corners, p_out, p3_out, vp_out, n_out);
-    VH_CHECK(hipGetLastError());
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// vh_frame0_init_batch: vh_frame0_init for nb clips of one frame size as one launch sequence per chunk of clips.  Every stage runs with the
-// clip as a grid dimension; a clip finds its ROI, frame and scratch segment in the chunk's descriptor table (F0Clip).  Per clip the results are
-// bit-identical to vh_frame0_init: the same integer Sobel / Harris sums and float32 response, the same order-preserving atomic maximum, the same
-// candidate test and 64-bit keys, cornerSubPix, pose and world points through the same device code.  Only the ordering step differs: instead
-// of sorting every ROI pixel, the candidates are compacted per clip and the max_corners largest keys are found by a radix select (keys are
-// unique -- the pixel index is part of each -- so their unsigned descending order is the rocPRIM sort's order).
+// The detector and vh_frame0_init_batch: vidExample.py:105-127 for nb clips of one frame size as one launch sequence per chunk of clips.  Every stage
+// runs with the clip as a grid dimension; a clip finds its ROI, frame and scratch segment in the chunk's descriptor table (F0Clip).  A clip's results do
+// not depend on the clips beside it or on the chunking.  The candidates are compacted per clip and the max_corners largest keys are found by a radix
+// select (keys are unique -- the pixel index is part of each -- so their unsigned descending order is a full sort's order).
 // ---------------------------------------------------------------------------------------------------------------
 #define F0B_TW 64        // Harris / candidate tile: 64 x 16 pixels, 256 threads
 #define F0B_TH 16
@@ -478,10 +230,10 @@ struct F0Shared {
     double plate[12];
 };
 
-// Sobel (k_init_sobel) into an LDS tile with a (block - 1) halo, response of 64 x 16 pixels, per-clip maximum over the pixels the clip's mask keeps.
-// HARRIS: k_init_harris's sums and float32 expression; otherwise the minimum eigenvalue of the same structure tensor (OpenCV's calcMinEigenVal:
+// Sobel 3x3 (aperture 3, REFLECT_101; the pair (dx, dy) per pixel) into an LDS tile with a (block - 1) halo, response of 64 x 16 pixels, per-clip maximum over the pixels the clip's mask keeps.
+// HARRIS: the block x block sums of the products and det - k trace^2 in float32; otherwise the minimum eigenvalue of the same structure tensor (OpenCV's calcMinEigenVal:
 // a = sxx s2 / 2, b = sxy s2, c = syy s2 / 2, (a + c) - sqrt((a - c)^2 + b^2), every step rounded to float32).  REFLECT_101 is relative to the clip's
-// ROI: a halo entry holds the Sobel pair of the reflected pixel, as k_init_harris reads it.
+// ROI: a halo entry holds the Sobel pair of the reflected pixel.
 template <bool HARRIS>
 __global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, int block, float s2, float kf, float* resp_base, unsigned* cnt)
 {
@@ -531,7 +283,7 @@ __global__ __launch_bounds__(256) void k_f0b_harris(const F0Clip* tab, int block
     if (lx == 0 && o) atomicMax(&cnt[4 * blockIdx.z], o);
 }
 
-// k_init_candidates per clip: the thresholded 3x3 local maxima the clip's mask keeps, appended to the clip's key segment through its counter (one atomic per wavefront)
+// the thresholded 3x3 local maxima the clip's mask keeps, appended to the clip's key segment through its counter (one atomic per wavefront)
 __global__ __launch_bounds__(256) void k_f0b_candidates(const F0Clip* tab, double quality, const float* resp_base, unsigned long long* keys_base, unsigned* cnt)
 {
     const F0Clip& C = tab[blockIdx.z];
@@ -654,7 +406,8 @@ __device__ __forceinline__ float* f0b_corner_row(const F0Clip& C, int qhead)
 }
 
 // One workgroup per clip: K = min(candidates, the budget) -- the clip's own when LDS_SORT, the chunk's otherwise; the keys >= the K-th largest
-// (f0b_radix_select) are gathered and -- LDS_SORT -- sorted descending in LDS and written as corners + the ROI origin (k_init_emit), or gathered into the clip's segment of `gsel` for the segmented sort.
+// (f0b_radix_select) are gathered and -- LDS_SORT -- sorted descending in LDS and written as corners + the ROI origin
+// (vidExample.py:110-112: `goodFeaturesToTrack(roi, ...) + np.float32([boxb[0], boxb[2]])`: integer-valued float32, exact), or gathered into the clip's segment of `gsel` for the segmented sort.
 template <bool LDS_SORT>
 __global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int max_corners, const unsigned long long* keys_base, unsigned* cnt, int qhead,
                                                      unsigned long long* gsel, int* seg_begin, int* seg_end)
@@ -697,7 +450,7 @@ __global__ __launch_bounds__(1024) void k_f0b_select(const F0Clip* tab, int max_
     }
 }
 
-// corners of the segmented-sort route (max_corners > F0B_SEL_MAX), as k_init_emit
+// corners of the segmented-sort route (max_corners > F0B_SEL_MAX)
 __global__ __launch_bounds__(256) void k_f0b_emit(const F0Clip* tab, int max_corners, const unsigned long long* sorted, const unsigned* cnt, int qhead)
 {
     const int clip = blockIdx.y;
@@ -851,10 +604,7 @@ __global__ __launch_bounds__(256) void k_f0b_world(const F0Clip* tab, const F0Sh
     const int n = min(4 + (int)cnt[4 * clip + 2], cap);
     if (i == 0) n_out[b] = n;
     if (i >= cap) return;
-    Frame0Job J;  // (the fields the row reads)
-    for (int k = 0; k < 9; k++) J.K[k] = sh->K[k];
-    for (int k = 0; k < 4; k++) J.boxa[k] = tab[clip].boxa[k];
-    frame0_world_row(i, n, J, R_out + 9 * b, t_out + 3 * b, p_out + b * cap * 2, p3_out + b * cap * 3, vp_out + b * cap);
+    frame0_world_row(i, n, sh->K, tab[clip].boxa, R_out + 9 * b, t_out + 3 * b, p_out + b * cap * 2, p3_out + b * cap * 3, vp_out + b * cap);
 }
 
 static void batch_sel_release(InitBatchScratch& B)
@@ -866,29 +616,37 @@ static void batch_release(InitBatchScratch& B)
 {
     batch_sel_release(B);
     (void)hipFree(B.resp); (void)hipFree(B.keys); (void)hipFree(B.cnt); (void)hipFree(B.info); (void)hipFree(B.tab); (void)hipFree(B.shared);
-    (void)hipFree(B.pose); (void)hipFree(B.mask);
+    (void)hipFree(B.pose);
     memset(&B, 0, sizeof(B));
 }
 
-// growth of scratch that kernels queued earlier may still use: after a stream synchronisation, never inside a capture
-static int batch_grow_guard(const InitBatchScratch& B, bool had, hipStream_t s)
+// what a caller does ahead of a capture so that the entry it called finds its scratch (the -6 message names it)
+static const char* const F0B_RESERVE_ONE = "call vh_init_reserve(ctx, w, h) before capturing";
+static const char* const F0B_RESERVE_BATCH = "call vh_init_reserve_batch(ctx, nb, w, h) before capturing";
+static const char* const F0B_RESERVE_MATCH = "call vh_match_reserve(ctx, w, h, params) or vh_match_reserve_batch before capturing";
+static const char* const F0B_RESERVE_SORT = "make one eager call with this max_corners before capturing";
+
+// allocation or growth of the scratch: never inside a capture; when kernels queued earlier may still use it (had), after a stream synchronisation
+static int batch_grow_guard(bool had, hipStream_t s, const char* remedy)
 {
-    if (!had) return 0;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return vh_fail(-6, "batched frame-0 scratch must grow inside a stream capture: call vh_init_reserve_batch(ctx, nb, w, h) before capturing");
-    VH_CHECK(hipStreamSynchronize(s));
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "frame-0 scratch must grow inside a stream capture: %s", remedy);
+        return vh_fail(-6, msg);
+    }
+    if (had) VH_CHECK(hipStreamSynchronize(s));
     return 0;
 }
 
 static size_t batch_clip_bytes(size_t px) { return 12 * px + 24 + sizeof(F0Clip) + sizeof(PoseJob); }
 
 // scratch for chunks of up to `clips` clips and `pix` ROI pixels in all (never shrinks)
-static int batch_reserve(vh_ctx* c, int clips, size_t pix, hipStream_t s)
+static int batch_reserve(vh_ctx* c, int clips, size_t pix, hipStream_t s, const char* remedy)
 {
     InitBatchScratch& B = c->init_batch;
     if (B.clips_cap >= clips && B.pix_cap >= pix) return 0;
-    int r = batch_grow_guard(B, B.clips_cap > 0, s);
+    int r = batch_grow_guard(B.clips_cap > 0, s, remedy);
     if (r) return r;
     clips = clips > B.clips_cap ? clips : B.clips_cap;
     pix = pix > B.pix_cap ? pix : B.pix_cap;
@@ -902,8 +660,6 @@ static int batch_reserve(vh_ctx* c, int clips, size_t pix, hipStream_t s)
     VH_CHECK(hipMalloc(&B.tab, sizeof(F0Clip) * tab_n));
     VH_CHECK(hipMalloc(&B.shared, sizeof(F0Shared)));
     VH_CHECK(hipMalloc((void**)&B.pose, sizeof(PoseJob) * clips));
-    r = subpix_masks_create(&B.mask);
-    if (r) return r;
     B.clips_cap = clips;
     B.pix_cap = pix;
     B.explicit_size = expl;
@@ -916,8 +672,8 @@ static int batch_sel_reserve(vh_ctx* c, int max_corners, hipStream_t s)
     InitBatchScratch& B = c->init_batch;
     const size_t need = (size_t)B.clips_cap * max_corners;
     if (B.sel_cap >= need) return 0;
-    if (need > 0x7fffffffu) return vh_fail(-1, "vh_frame0_init_batch: clips x max_corners exceeds the segmented sort's range");
-    int r = batch_grow_guard(B, B.sel_cap > 0, s);
+    if (need > 0x7fffffffu) return vh_fail(-1, "frame-0 detector: clips x max_corners exceeds the segmented sort's range");
+    int r = batch_grow_guard(B.sel_cap > 0, s, F0B_RESERVE_SORT);
     if (r) return r;
     batch_sel_release(B);
     VH_CHECK(hipMalloc((void**)&B.sel, need * 8));
@@ -931,19 +687,36 @@ static int batch_sel_reserve(vh_ctx* c, int max_corners, hipStream_t s)
     return 0;
 }
 
-void vh_init_batch_scratch_free(vh_ctx* c)
+void vh_init_scratch_free(vh_ctx* c)
 {
-    if (c) batch_release(c->init_batch);
+    if (!c) return;
+    batch_release(c->init_batch);
+    (void)hipFree(c->subpix_mask);
+    c->subpix_mask = nullptr;
 }
 
 extern "C" VH_API int vh_init_reserve_batch(vh_ctx* c, int nb, int w, int h, void* stream)
 {
     if (!c || nb < 1 || w < 1 || h < 1) return vh_fail(-1, "vh_init_reserve_batch: bad arguments");
     VH_BIND(c, stream);
-    const int r = batch_reserve(c, nb, (size_t)nb * w * h, bound_.s);
+    const int r = batch_reserve(c, nb, (size_t)nb * w * h, bound_.s, F0B_RESERVE_BATCH);
     if (r) return r;
     c->init_batch.explicit_size = 1;
     return 0;
+}
+
+// The one-image entries (vh_good_features, vh_good_features2, vh_frame0_init) on an image of up to max(w x h, the context's max_w x max_h) pixels only
+// queue kernels after this: scratch for chunks of the size the context already has (at least one clip) and that many pixels.  It leaves the chunking of
+// vh_frame0_init_batch alone (explicit_size is vh_init_reserve_batch's).
+extern "C" VH_API int vh_init_reserve(vh_ctx* c, int w, int h, void* stream)
+{
+    if (!c || w < 1 || h < 1) return vh_fail(-1, "vh_init_reserve: bad arguments");
+    VH_BIND(c, stream);
+    size_t pixels = (size_t)w * h;
+    const size_t ctx_px = (size_t)c->max_w * (size_t)c->max_h;
+    if (pixels < ctx_px && ctx_px <= ((size_t)1 << 26)) pixels = ctx_px;  // any image the context was created for fits: no growth later
+    const int clips = c->init_batch.clips_cap > 1 ? c->init_batch.clips_cap : 1;
+    return batch_reserve(c, clips, pixels, bound_.s, F0B_RESERVE_ONE);
 }
 
 // The detector's parameters of one call (vh_frame0_init_batch2 / vh_good_features2)
@@ -1003,7 +776,7 @@ static int f0b_detect(InitBatchScratch& B, const F0Clip* d_tab, const F0Clip* h,
         size_t bytes = 0;
         const unsigned size = (unsigned)n * (unsigned)max_corners;
         VH_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
-        if (bytes > B.sort_bytes) return vh_fail(-1, "vh_frame0_init_batch: segmented sort scratch too small");
+        if (bytes > B.sort_bytes) return vh_fail(-1, "frame-0 detector: segmented sort scratch too small");
         bytes = B.sort_bytes;
         VH_CHECK(rocprim::segmented_radix_sort_keys_desc(B.sort_tmp, bytes, B.sel, B.sorted, size, (unsigned)n, B.seg, seg_end, 0, 64, s));
         hipLaunchKernelGGL(k_f0b_emit, dim3((max_corners + 255) / 256, n), dim3(256), 0, s, d_tab, max_corners, B.sorted, B.cnt, qhead);
@@ -1026,7 +799,7 @@ static int f0b_upload(F0Clip* d_tab, const F0Clip* h, int n, hipStream_t s)
 static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host, const double* K_host,
                             const double* plate_host, int border_x, int border_y, const F0Detect& D, int subpix_win, int subpix_iter, double subpix_eps,
                             float* p_out, double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host,
-                            void* stream, const char* fn)
+                            void* stream, const char* fn, const char* remedy)
 {
     // every check before anything is queued
     char msg[160];
@@ -1077,11 +850,11 @@ static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host
     InitBatchScratch& B = c->init_batch;
     // (the spacing stage needs no scratch of its own: its occupancy grid reuses the clip's response plane)
     if (B.explicit_size) {  // chunks of the reserved size; grown only for a ROI larger than the whole scratch
-        r = batch_reserve(c, B.clips_cap, max_px, s);
+        r = batch_reserve(c, B.clips_cap, max_px, s, remedy);
     } else {                // as many clips per chunk as the budget holds
         const size_t fit = F0B_BUDGET / batch_clip_bytes(max_px);
         const int want = (int)(fit < 1 ? 1 : (fit < (size_t)nb ? fit : (size_t)nb));
-        r = batch_reserve(c, want, (size_t)want * max_px, s);
+        r = batch_reserve(c, want, (size_t)want * max_px, s, remedy);
     }
     if (r) return r;
     if (max_corners > F0B_SEL_MAX && D.min_distance < 1 && (r = batch_sel_reserve(c, max_corners, s))) return r;
@@ -1095,7 +868,7 @@ static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host
     const int cap = 4 + max_corners;
     const int iters = subpix_iter < 1 ? 1 : (subpix_iter > 100 ? 100 : subpix_iter);
     const double eps = subpix_eps < 0 ? 0 : subpix_eps;
-    const float* mask = B.mask + subpix_mask_offset(subpix_win);
+    const float* mask = c->subpix_mask + subpix_mask_offset(subpix_win);
     for (int b0 = 0; b0 < nb;) {
         // one chunk: as many clips as the scratch holds, their ROI planes back to back
         int n = 0;
@@ -1127,7 +900,7 @@ extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* con
 {
     const F0Detect D = {max_corners, block, 1, quality, k, 0.0};
     return frame0_batch_run(c, nb, frames_host, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out,
-                            p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch");
+                            p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch", F0B_RESERVE_BATCH);
 }
 
 extern "C" VH_API int vh_frame0_init_batch2(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
@@ -1138,7 +911,18 @@ extern "C" VH_API int vh_frame0_init_batch2(vh_ctx* c, int nb, const uint8_t* co
 {
     const F0Detect D = {max_corners, block, use_harris ? 1 : 0, quality, k, min_distance};
     return frame0_batch_run(c, nb, frames_host, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out,
-                            p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch2");
+                            p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch2", F0B_RESERVE_BATCH);
+}
+
+// frame 0 of one video: the batch of one clip.  Its output layout is the single call's (cap = 4 + max_corners rows, roi_host int[8])
+extern "C" VH_API int vh_frame0_init(vh_ctx* c, const uint8_t* im, int w, int h, int stride, const float* q_host, const double* K_host,
+                                     const double* plate_host, int border_x, int border_y, int max_corners, double quality, int block, double k,
+                                     int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out, uint8_t* vp_out, float* t_out,
+                                     double* R_out, double* res_out, int* n_out, int* roi_host, void* stream)
+{
+    const F0Detect D = {max_corners, block, 1, quality, k, 0.0};
+    return frame0_batch_run(c, 1, &im, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out, p3_out,
+                            vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init", F0B_RESERVE_ONE);
 }
 
 // one chunk of whole-image clips whose scratch the caller has reserved (batch_reserve: n clips, the sum of their pixels): response planes back to back
@@ -1158,7 +942,7 @@ static int f0b_run_clips(vh_ctx* c, F0Clip* clips, int n, const F0Detect& D, hip
     return f0b_detect(B, d_tab, clips, n, D, 0, s);
 }
 
-int vh_detect_reserve(vh_ctx* c, int clips, size_t pixels, hipStream_t s) { return batch_reserve(c, clips, pixels, s); }
+int vh_detect_reserve(vh_ctx* c, int clips, size_t pixels, hipStream_t s) { return batch_reserve(c, clips, pixels, s, F0B_RESERVE_MATCH); }
 
 // goodFeaturesToTrack (Shi-Tomasi or Harris, min_distance 0, masked) of n images of any sizes, strides and budgets (each at most 2048) as ONE pass of the
 // batch kernels; per image bit-identical to vh_good_features2 on it alone.  Scratch: vh_detect_reserve(n, the sum of the images' pixels).
@@ -1186,20 +970,21 @@ int vh_detect_images(vh_ctx* c, const vh_detect_image* im, int n, double quality
     return f0b_run_clips(c, clips.data(), n, D, s);
 }
 
-// goodFeaturesToTrack of one image on the batch kernels (one clip: the whole image is its ROI, origin 0)
-extern "C" VH_API int vh_good_features2(vh_ctx* c, const uint8_t* im, int w, int h, int stride, const uint8_t* mask, int mask_stride, int max_corners,
-                                        double quality, double min_distance, int block, int use_harris, double k, float* corners, int* count, void* stream)
+// goodFeaturesToTrack of one image: one clip whose ROI is the whole image, origin 0 (fn: the entry that was called)
+static int good_features_one(vh_ctx* c, const uint8_t* im, int w, int h, int stride, const uint8_t* mask, int mask_stride, const F0Detect& D, float* corners,
+                             int* count, void* stream, const char* fn)
 {
-    if (!c || !im || !corners || !count || w < 3 || h < 3 || stride < w || (mask && mask_stride < w) || max_corners < 1 || block < 1 || block > 15)
-        return vh_fail(-1, "vh_good_features2: bad arguments");
-    const F0Detect D = {max_corners, block, use_harris ? 1 : 0, quality, k, min_distance};
-    int r = f0b_detect_check(D, w, h, "vh_good_features2");
+    if (!c || !im || !corners || !count || w < 3 || h < 3 || stride < w || (mask && mask_stride < w) || D.max_corners < 1 || D.block < 1 || D.block > 15) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: bad arguments", fn);
+        return vh_fail(-1, msg);
+    }
+    int r = f0b_detect_check(D, w, h, fn);
     if (r) return r;
     VH_BIND(c, stream);
     hipStream_t s = bound_.s;
-    const size_t px = (size_t)w * h;
-    if ((r = batch_reserve(c, 1, px, s))) return r;
-    if (max_corners > F0B_SEL_MAX && min_distance < 1 && (r = batch_sel_reserve(c, max_corners, s))) return r;
+    if ((r = batch_reserve(c, 1, (size_t)w * h, s, F0B_RESERVE_ONE))) return r;
+    if (D.max_corners > F0B_SEL_MAX && D.min_distance < 1 && (r = batch_sel_reserve(c, D.max_corners, s))) return r;
     F0Clip C;
     memset(&C, 0, sizeof(C));
     C.roi = C.im = im;
@@ -1208,10 +993,25 @@ extern "C" VH_API int vh_good_features2(vh_ctx* c, const uint8_t* im, int w, int
     C.stride = stride;
     C.mask = mask;
     C.mstride = mask_stride;
-    C.max_corners = max_corners;
+    C.max_corners = D.max_corners;
     C.out = corners;
     C.n_out = count;
     if ((r = f0b_run_clips(c, &C, 1, D, s))) return r;
     VH_CHECK(hipGetLastError());
     return 0;
+}
+
+// the reference's call (vidExample.py:110): Harris, min_distance 0, no mask
+extern "C" VH_API int vh_good_features(vh_ctx* c, const uint8_t* im, int w, int h, int stride, int max_corners, double quality, int block,
+                                       double k, float* corners, int* count, void* stream)
+{
+    const F0Detect D = {max_corners, block, 1, quality, k, 0.0};
+    return good_features_one(c, im, w, h, stride, nullptr, 0, D, corners, count, stream, "vh_good_features");
+}
+
+extern "C" VH_API int vh_good_features2(vh_ctx* c, const uint8_t* im, int w, int h, int stride, const uint8_t* mask, int mask_stride, int max_corners,
+                                        double quality, double min_distance, int block, int use_harris, double k, float* corners, int* count, void* stream)
+{
+    const F0Detect D = {max_corners, block, use_harris ? 1 : 0, quality, k, min_distance};
+    return good_features_one(c, im, w, h, stride, mask, mask_stride, D, corners, count, stream, "vh_good_features2");
 }

@@ -61,18 +61,7 @@ struct StreamWS {
     const int* order;  // bufs.order when this call launches its LK kernels in spatial order, else null
 };
 
-// scratch of the frame-0 detector (vh_init.hip: goodFeaturesToTrack / cornerSubPix), owned by the context that uses it
-struct InitScratch {
-    int* dxy;
-    float* resp;
-    unsigned long long *keys, *sorted;
-    unsigned* counters;  // [0] max (ordered bits), [1] candidate count, [2..3] pose info, [4] corner count of vh_frame0_init
-    float* mask;         // cornerSubPix Gaussian windows of every half-size 1..7, back to back
-    void* sort_tmp;
-    size_t sort_bytes, pixels;
-};
-
-// scratch of the batched frame-0 initialisation (vh_init.hip: vh_frame0_init_batch), owned by the context; one chunk of clips at a time
+// scratch of the frame-0 detector and initialisation (vh_init.hip: every goodFeaturesToTrack / frame-0 entry), owned by the context; one chunk of clips at a time
 struct InitBatchScratch {
     float* resp;                 // Harris response planes of a chunk's ROIs, back to back (pix_cap floats)
     unsigned long long* keys;    // candidate keys, one segment per clip at the offset of its plane (pix_cap)
@@ -81,7 +70,6 @@ struct InitBatchScratch {
     void* tab;                   // per-clip descriptors (F0Clip, vh_init.hip), clips_cap rounded up to a whole upload piece
     void* shared;                // K and the plate points of the call (F0Shared)
     PoseJob* pose;               // per-clip plate-pose jobs, built on the device
-    float* mask;                 // cornerSubPix Gaussian windows (as InitScratch::mask)
     // max_corners above the in-LDS selection: the selected keys of each clip in a segment of max_corners, sorted by rocPRIM
     unsigned long long *sel, *sorted;
     int* seg;                    // segment begin [clips_cap] and end [clips_cap] offsets
@@ -113,8 +101,8 @@ struct vh_ctx {
     int lk_tpw[3];             // launch slots per workgroup of those launches (1 unless the one-wavefront LDS-staged kernel looped; vh_profile_lk_tpw)
     int lk_route[3];           // kernel route (vh_lk_route ids) the last KLTmain took for its three LK launches (vh_profile_lk_routes)
     int lk_win[3];
-    InitScratch init;          // created by the first frame-0 call (vh_init.hip)
-    InitBatchScratch init_batch;  // created by the first batched frame-0 call or vh_init_reserve_batch (vh_init.hip)
+    float* subpix_mask;        // cornerSubPix Gaussian windows of every half-size 1..7, back to back (vh_subpix_masks_create, at vh_ctx_create)
+    InitBatchScratch init_batch;  // created by the first frame-0 call, vh_init_reserve or vh_init_reserve_batch (vh_init.hip)
     void* match;               // scratch of vh_match_affine (MatchScratch, vh_match.hip), created by its first call or vh_match_reserve
 };
 
@@ -226,8 +214,8 @@ struct SessStream {  // device resident, one per video stream
 int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_params& coarse, const vh_lk_params& fine,
                     const SessStream* sess = nullptr, const uint8_t* const* frames = nullptr, int n_max = 0);
 int vh_fail(int code, const char* msg);
-void vh_init_scratch_free(vh_ctx* c);        // both frame-0 scratches (vh_init.hip)
-void vh_init_batch_scratch_free(vh_ctx* c);
+int vh_subpix_masks_create(float** out);     // the cornerSubPix mask table of a new context (vh_init.hip; synchronous upload)
+void vh_init_scratch_free(vh_ctx* c);        // the frame-0 scratch and the mask table (vh_init.hip)
 // the batched frame-0 detector on whole images of different sizes, strides and corner budgets (vh_init.hip; the level images of vh_match_affine_batch)
 struct vh_detect_image {
     const uint8_t* im;

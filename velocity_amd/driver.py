@@ -270,13 +270,13 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     q       float32 [4, 2]: the hand-clicked plate corners of frame 0 (the .mat file's `q`, vidExample.py:31-32)
     K       the camera's 3 x 3 intrinsic matrix, reference layout (images.py:148-151)
     fps / times / frame_numbers   B[i, 12] (seconds; `CAP_PROP_POS_MSEC / 1000` or the EXIF time) and B[i, 13] per frame: either `times` or `fps`
-    route   "session": frame 0 through vh_frame0_init (Harris -> cornerSubPix -> plate pose -> image2world -> insidebbox, ONE device sequence) straight
+    route   "session": frame 0 as a batch of one clip (vh_frame0_init_batch: Harris -> cornerSubPix -> plate pose -> image2world -> insidebbox, ONE device sequence) straight
             into a device-resident TrackerSession -- nothing but the frames goes up and nothing but the printed rows comes down (the only route of the
             product; a host loop on the drop-in functions -- what INTEGRATION.md's import switch gives a maintainer -- lives in tools/dropin_loop.py as a
             measurement harness).
     live    True prints every row as its frame finishes (one small read-back per frame, like the reference); False runs the whole clip first.
-    use_harris, min_distance   the frame-0 detector (goodFeaturesToTrack's useHarrisDetector / minDistance; the defaults are the reference's call).  Any
-            other setting runs frame 0 as a one-clip vh_frame0_init_batch2, whose results for the defaults equal vh_frame0_init's.
+    use_harris, min_distance   the frame-0 detector (goodFeaturesToTrack's useHarrisDetector / minDistance; the defaults are the reference's call; any
+            other setting goes through vh_frame0_init_batch2).
     fallback   True: a frame whose coarse KLT stage fails recovers the motion by feature matching (TrackerSession(fallback=True): one host read per
             frame step; default off).  The result then carries `recoveries` = [the recovery ran, it found a model] counts.
     out     line sink (default print); clock: time source for the procTime column / fps line (default time.perf_counter).
@@ -341,17 +341,9 @@ def _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corn
     R0 = torch.empty(9, dtype=torch.float64, device="cuda")
     res0 = torch.empty(1, dtype=torch.float64, device="cuda")
     n0 = torch.empty(1, dtype=torch.int32, device="cuda")
-    rois = (C.c_int * 8)()
     plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
-    win, it, eps = subpix
-    if _default_detector(use_harris, min_distance):
-        L.check(lib.vh_frame0_init(ws.handle, L.dptr(dev[0]), W, H, W, q.ctypes.data_as(L.f32p), ses.K64.ctypes.data_as(L.f64p), plate_w.ctypes.data_as(L.f64p),
-                                   int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block), float(harris_k), int(win), int(it),
-                                   float(eps), L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(R0), L.dptr(res0), L.dptr(n0), rois, L.stream_ptr()),
-                "vh_frame0_init")
-    else:  # one clip of the batch entry (bit-identical per clip to vh_frame0_init for the reference's detector)
-        rois = _frame0_batch_call(lib, ws, [dev[0]], [q], W, H, ses.K64, plate_w, roi_border, max_corners, quality, block, harris_k, subpix,
-                                  (p, p3, vp, t0, R0, res0, n0), use_harris, min_distance)
+    rois = _frame0_batch_call(lib, ws, [dev[0]], [q], W, H, ses.K64, plate_w, roi_border, max_corners, quality, block, harris_k, subpix,
+                              (p, p3, vp, t0, R0, res0, n0), use_harris, min_distance)
     L.check(lib.vh_session_init_dev(ses.handle, 0, L.dptr(dev[0]), W, L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
                                     float(times[0]), float(frame_numbers[0]), L.stream_ptr()), "vh_session_init_dev")
     ses._keep[0] = dev[0]

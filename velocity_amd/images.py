@@ -79,11 +79,10 @@ def resize_nearest(im, fx, fy=None):
 
 
 def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, blockSize=3, useHarrisDetector=True, k=0.04, *, mask=None):
-    """cv2.goodFeaturesToTrack -> float32 [n,1,2].  The reference's call (vidExample.py:110: Harris, minDistance 0, no mask) runs vh_good_features;
-    every other one vh_good_features2: the minimum-eigenvalue (Shi-Tomasi) detector with useHarrisDetector=False, corners spaced greedily by
-    minDistance >= 1 (for integer positions exactly cv2's grid), a uint8 mask of the image's shape (numpy or CUDA tensor; 0 excludes a pixel from the
-    maximum and from the corners).  Deviation: useHarrisDetector defaults to True (cv2: False), as it always has here; maxCorners <= 0 is refused
-    (cv2: unlimited)."""
+    """cv2.goodFeaturesToTrack -> float32 [n,1,2] through vh_good_features2, whatever the parameters: the reference's call (vidExample.py:110: Harris,
+    minDistance 0, no mask), the minimum-eigenvalue (Shi-Tomasi) detector with useHarrisDetector=False, corners spaced greedily by minDistance >= 1 (for
+    integer positions exactly cv2's grid), a uint8 mask of the image's shape (numpy or CUDA tensor; 0 excludes a pixel from the maximum and from the
+    corners).  Deviation: useHarrisDetector defaults to True (cv2: False), as it always has here; maxCorners <= 0 is refused (cv2: unlimited)."""
     torch = L.torch_cuda()
     t, h, w, st = L.img_dev(image)
     mdist = float(minDistance)
@@ -97,13 +96,8 @@ def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, blockSize=
     out = torch.zeros((max(int(maxCorners), 1), 2), dtype=torch.float32, device="cuda")
     cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
     ws = L.workspace()
-    if useHarrisDetector and mdist == 0.0 and m is None:
-        L.check(ws.lib.vh_good_features(ws.handle, L.dptr(t), w, h, st, int(maxCorners), float(qualityLevel), int(blockSize), float(k), L.dptr(out),
-                                        L.dptr(cnt), L.stream_ptr()), "vh_good_features")
-    else:
-        L.check(ws.lib.vh_good_features2(ws.handle, L.dptr(t), w, h, st, L.dptr(m) if m is not None else None, mst, int(maxCorners), float(qualityLevel),
-                                         mdist, int(blockSize), 1 if useHarrisDetector else 0, float(k), L.dptr(out), L.dptr(cnt), L.stream_ptr()),
-                "vh_good_features2")
+    L.check(ws.lib.vh_good_features2(ws.handle, L.dptr(t), w, h, st, L.dptr(m) if m is not None else None, mst, int(maxCorners), float(qualityLevel), mdist,
+                                     int(blockSize), 1 if useHarrisDetector else 0, float(k), L.dptr(out), L.dptr(cnt), L.stream_ptr()), "vh_good_features2")
     n = int(cnt.item())
     return out[:n].cpu().numpy().reshape(n, 1, 2)
 
