@@ -382,6 +382,43 @@ VH_API int vh_session_step(vh_session* s, const uint8_t* const* frames_dev, floa
  * run (they are that step's im0). */
 VH_API int vh_session_step_v(vh_session* s, const uint8_t* const* frames_dev, const float* time_s_dev, const float* frame_no_dev,
                              void* stream);
+/* (vh_version >= 110) vh_session_step_v in which a stream may SIT THE STEP OUT: two cameras of different frame rates, a slot whose clip has ended while
+ * its neighbours run on, a slot no clip has been given yet.  Idleness is stated once per side and the two must agree:
+ *   - the DEVICE learns it from the frame table: frames_dev[b] == NULL <=> stream b is idle;
+ *   - the HOST learns it from active_host, a host uint8[batch]: active_host[b] == 0 <=> stream b is idle (the library mirrors each stream's frame
+ *     counter on the host to decide whether the MSV launches are queued; it never reads the device table).
+ * The step is the same fixed launch sequence as ever; an idle stream is a descriptor with empty extents (no tracks, nothing to resize, no pyramid to
+ * build) that every launch passes by.  After the step an idle stream's whole state -- masks, points, history, records, frame counter, previous frame,
+ * quarter-scale images, klt_flags, recovery counters -- is byte for byte what it was, and nothing of it was used: a slot that was never initialised is a
+ * legal idle stream.  A stream parked at its MSV frame is NOT re-triangulated when a neighbour reaches its own, and with the recovery on it reports no
+ * failure whatever flag its last active step left.  time_s_dev[b] / frame_no_dev[b] of an idle stream are not read.
+ * Frame lifetime: the frame of a stream's active step is read again (as im0) by that stream's NEXT ACTIVE step and must stay alive until that step has
+ * run, however many idle steps lie between.
+ * vh_session_step and vh_session_step_v are unchanged: every stream steps, every frame pointer must be non-NULL; for an active stream the three entries
+ * compute bit-identical results. */
+VH_API int vh_session_step_some(vh_session* s, const uint8_t* const* frames_dev, const uint8_t* active_host, const float* time_s_dev,
+                                const float* frame_no_dev, void* stream);
+/* (vh_version >= 110) everything a stream hands back, packed into ONE contiguous device record by one launch, for one device-to-host copy per finished
+ * clip (vh_session_ptrs + one vh_copy_to_host per array stops the device fourteen times).  The fields are BYTE OFFSETS into the record; a C consumer
+ * reads through them, never through a remembered layout.  Every array starts on a multiple of 8 bytes. */
+typedef struct {
+    size_t bytes;                               /* size of the record                                                         */
+    size_t n_cur, n_pose, frame_i, klt_flags;   /* int32 each                                                                 */
+    size_t pose_info;                           /* int32[2]   iterations, converged                                           */
+    size_t t;                                   /* float32[3] last pose translation                                           */
+    size_t res;                                 /* float64    last rms reprojection residual                                  */
+    size_t vg, vp;                              /* uint8[n0]                                                                  */
+    size_t ids;                                 /* int32[n0]  rows [0, n_cur) as vh_session_view::ids, -1 behind them         */
+    size_t p;                                   /* float32[n0][2]  rows [0, n_cur) as vh_session_view::p, 0 behind them       */
+    size_t p3;                                  /* float64[n0][3]                                                             */
+    size_t B, S;                                /* float32[nhist][14], float32[nhist][9]                                      */
+    size_t P;                                   /* float32[5][n0][nhist]: the REFERENCE's order (vidExample.py:128), transposed on the device */
+    int n0, nhist;
+} vh_session_record;
+/* size in bytes of a record of this session (0 and vh_last_error on a NULL session); layout_host (may be NULL) receives the offsets */
+VH_API size_t vh_session_export_size(const vh_session* s, vh_session_record* layout_host);
+/* packs stream `slot` into rec_dev (device memory, vh_session_export_size bytes, 8-byte aligned) on `stream`: one launch, no scratch, no wait */
+VH_API int vh_session_export(vh_session* s, int slot, void* rec_dev, void* stream);
 VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
 /* (vh_version >= 109) the recovery branch of KLTmain (utils/KLT.py:130-133) inside the session; default OFF: a step then queues exactly the launches it
  * always did and a stream whose coarse stage fails reports klt_flags & 1 and goes on with what the blind fine stage kept.

@@ -34,6 +34,13 @@ class SessionView(C.Structure):
                                       ("n0", C.c_int), ("nhist", C.c_int)]
 
 
+class SessionRecord(C.Structure):
+    """vh_session_record: byte offsets of the fields of an exported stream record."""
+
+    _fields_ = [(k, C.c_size_t) for k in ("bytes", "n_cur", "n_pose", "frame_i", "klt_flags", "pose_info", "t", "res", "vg", "vp", "ids", "p", "p3", "B", "S",
+                                          "P")] + [("n0", C.c_int), ("nhist", C.c_int)]
+
+
 class MatchParams(C.Structure):
     """vh_match_params (defaults: MATCH_DEFAULTS)."""
 
@@ -96,6 +103,9 @@ _SIGS = {
     "vh_session_init_dev": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]),
     "vh_session_step": (C.c_int, [vp, vp, C.c_float, C.c_float, vp]),
     "vh_session_step_v": (C.c_int, [vp, vp, vp, vp, vp]),
+    "vh_session_step_some": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    "vh_session_export_size": (C.c_size_t, [vp, C.POINTER(SessionRecord)]),
+    "vh_session_export": (C.c_int, [vp, C.c_int, vp, vp]),
     "vh_session_ptrs": (C.c_int, [vp, C.c_int, C.POINTER(SessionView)]),
     "vh_session_pack_state": (C.c_int, [vp, vp, vp]),
     "vh_debug_force_generic_lk": (None, [C.c_int]),

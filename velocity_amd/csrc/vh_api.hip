@@ -30,7 +30,7 @@ int vh_fail(int code, const char* msg)
 }
 #define VH_LAUNCH_CHECK() VH_CHECK(hipGetLastError())
 
-extern "C" VH_API int vh_version(void) { return 109; }
+extern "C" VH_API int vh_version(void) { return 110; }
 void vh_lk_force_generic(int on);
 extern "C" VH_API void vh_debug_force_generic_lk(int on) { vh_lk_force_generic(on); }
 void vh_ransac_force_path(int mode);
@@ -206,22 +206,26 @@ __global__ __launch_bounds__(KO_THREADS) void k_klt_setup(StreamWS* ws_all, cons
 __device__ void klt_setup_descriptors(StreamWS& ws, const SessStream* ss_all, const uint8_t* const* frames, const vh_lk_params& coarse,
                                       const vh_lk_params& fine, int use_order)
 {
+    // a session stream that sits this step out (vh_session_step_some: a NULL frame pointer): a descriptor with empty extents -- no tracks, nothing to resize,
+    // no pyramid to build, no flag word to write -- so every launch of the step passes it by and nothing reads the missing frame
+    bool idle = false;
     if (ss_all) {  // session mode: this frame's KLTmain call (vidExample.py:134) straight from the stream state
         const SessStream& S = ss_all[blockIdx.x];
         KltIO& o = ws.io;
         o.im = frames[blockIdx.x];
+        idle = o.im == nullptr;
         o.im0 = S.im0;
         o.im0_small = S.small[1 - S.pp];
         o.im_small = S.small[S.pp];
         o.p0 = S.p_cur;
-        o.n_ptr = &S.n_cur;
+        o.n_ptr = idle ? nullptr : &S.n_cur;
         o.n = 0;
         o.p_all = S.p_all;
         o.v = S.v;
-        o.flags = const_cast<int*>(&S.klt_flags);
+        o.flags = idle ? nullptr : const_cast<int*>(&S.klt_flags);
         o.w = S.w; o.h = S.h; o.stride = S.stride; o.stride0 = S.stride;
-        o.reuse_prev_small = S.frame_i >= 1 ? 1 : 0;  // the previous step built the pyramid of what is now im0_small
-        o.have_small = S.small_ready == S.frame_i + 1 ? 1 : 0;  // vh_session_ingest_bgr wrote this frame's quarter-scale image already
+        o.reuse_prev_small = idle || S.frame_i >= 1 ? 1 : 0;  // the previous step built the pyramid of what is now im0_small
+        o.have_small = idle || S.small_ready == S.frame_i + 1 ? 1 : 0;  // vh_session_ingest_bgr wrote this frame's quarter-scale image already
         o.coarse = coarse; o.fine = fine;
         o.fbt_coarse = 1.0f; o.fbt_fine = 0.3f;
         ws.pp = S.pp;
@@ -248,7 +252,7 @@ __device__ void klt_setup_descriptors(StreamWS& ws, const SessStream* ss_all, co
     fill_pyramid(J.I, small_prev, dw, dh, dw, B.small_lv[prev], io.coarse.win, io.coarse.max_level);
     fill_pyramid(J.J, small_cur, dw, dh, dw, B.small_lv[cur], io.coarse.win, io.coarse.max_level);
     ws.pb[0] = PyrBuild{&J.I, io.reuse_prev_small ? 0 : 1, 0};
-    ws.pb[1] = PyrBuild{&J.J, 1, 0};
+    ws.pb[1] = PyrBuild{&J.J, idle ? 0 : 1, 0};
     fill_lk_common(J, io.coarse, io.p0, nullptr, n);
     J.order = ws.order;
     J.p_out = B.p_small; J.v_out = B.v_small;

@@ -10,8 +10,9 @@
 #include "vh_pose_dev.hpp"
 
 template <int MODE, int NLS_THREADS>
-__global__ __launch_bounds__(NLS_THREADS) void k_pose(const void* tab, size_t stride)
+__global__ __launch_bounds__(NLS_THREADS) void k_pose(const void* tab, size_t stride, const void* const* live)
 {
+    if (live && live[blockIdx.x] == nullptr) return;  // (a session stream that sits this step out)
     const PoseJob J = pjob(tab, stride, blockIdx.x);  // by value: pointers / counts live in SGPRs
     if (J.mode != MODE) return;
     pose_solve<MODE, NLS_THREADS>(J);
@@ -212,8 +213,10 @@ __global__ __launch_bounds__(MSV_THREADS) void k_msv1(MsvJob J) { msv1_body(J); 
 // of ~0.2 ms each at the frame where every stream of a batch re-triangulates).  `tab` points at the MsvJob inside stream 0's device record, records are
 // `stride` bytes apart, and the stream's own frame counter sits `frame_off` bytes from its job: only the streams that are AT their MSV frame run
 // (vidExample.py:155 `if i == msvFrame`), the other workgroups leave at once.
-__global__ __launch_bounds__(MSV_THREADS) void k_msv1_tab(const void* tab, size_t stride, ptrdiff_t frame_off, int fire_frame)
+__global__ __launch_bounds__(MSV_THREADS) void k_msv1_tab(const void* tab, size_t stride, ptrdiff_t frame_off, int fire_frame, const void* const* live)
 {
+    // a stream that sat this step out may be PARKED at its MSV frame: it was re-triangulated when it got there, not again when a neighbour fires
+    if (live && live[blockIdx.x] == nullptr) return;
     const char* base = reinterpret_cast<const char*>(tab) + (size_t)blockIdx.x * stride;
     if (*reinterpret_cast<const int*>(base + frame_off) != fire_frame) return;
     msv1_body(*reinterpret_cast<const MsvJob*>(base));
@@ -222,13 +225,13 @@ __global__ __launch_bounds__(MSV_THREADS) void k_msv1_tab(const void* tab, size_
 // ---------------------------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------------------------
-void vh_launch_pose(const void* tab, size_t stride, int batch, int mode, int max_n, hipStream_t s)
+void vh_launch_pose(const void* tab, size_t stride, int batch, int mode, int max_n, hipStream_t s, const void* const* live)
 {
     // translation fit: 4 wavefronts keep up to 4096 points in registers; an LM iteration is then bound by the block
     // reduction + the serial 3x3 update, which 16 wavefronts only make longer (74 us vs 50 us per 2000-point fit)
-    if (mode == 0 && max_n <= 4096) hipLaunchKernelGGL((k_pose<0, 256>), dim3(batch), dim3(256), 0, s, tab, stride);
-    else if (mode == 0) hipLaunchKernelGGL((k_pose<0, 1024>), dim3(batch), dim3(1024), 0, s, tab, stride);
-    else hipLaunchKernelGGL((k_pose<1, 256>), dim3(batch), dim3(256), 0, s, tab, stride);
+    if (mode == 0 && max_n <= 4096) hipLaunchKernelGGL((k_pose<0, 256>), dim3(batch), dim3(256), 0, s, tab, stride, live);
+    else if (mode == 0) hipLaunchKernelGGL((k_pose<0, 1024>), dim3(batch), dim3(1024), 0, s, tab, stride, live);
+    else hipLaunchKernelGGL((k_pose<1, 256>), dim3(batch), dim3(256), 0, s, tab, stride, live);
 }
 void vh_launch_world2image(const double* C, const double* pw, int n, double* out, hipStream_t s)
 {
@@ -258,7 +261,7 @@ void vh_launch_msv1(const MsvJob& job, hipStream_t s)
 {
     hipLaunchKernelGGL(k_msv1, dim3(1), dim3(MSV_THREADS), sizeof(double) * 3 * (size_t)job.nf, s, job);
 }
-void vh_launch_msv1_tab(const void* tab, size_t stride, ptrdiff_t frame_off, int fire_frame, int nf, int batch, hipStream_t s)
+void vh_launch_msv1_tab(const void* tab, size_t stride, ptrdiff_t frame_off, int fire_frame, int nf, int batch, hipStream_t s, const void* const* live)
 {
-    hipLaunchKernelGGL(k_msv1_tab, dim3(batch), dim3(MSV_THREADS), sizeof(double) * 3 * (size_t)nf, s, tab, stride, frame_off, fire_frame);
+    hipLaunchKernelGGL(k_msv1_tab, dim3(batch), dim3(MSV_THREADS), sizeof(double) * 3 * (size_t)nf, s, tab, stride, frame_off, fire_frame, live);
 }

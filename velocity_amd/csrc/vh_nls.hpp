@@ -38,7 +38,8 @@ struct MsvJob {
     int* info_out;        // out 2
 };
 
-void vh_launch_pose(const void* tab, size_t stride, int batch, int mode, int max_n, hipStream_t s);
+// live (may be null): device table of `batch` pointers, job b is skipped where live[b] is NULL (the frame table of a session step)
+void vh_launch_pose(const void* tab, size_t stride, int batch, int mode, int max_n, hipStream_t s, const void* const* live = nullptr);
 void vh_launch_world2image(const double* C, const double* pw, int n, double* out, hipStream_t s);
 void vh_launch_image2world(const double* Hi, const double* p, int n, double* out, hipStream_t s);
 void vh_launch_pixel2uvec(double cx, double cy, double f, const double* p, int n, double* out, hipStream_t s);
@@ -46,5 +47,7 @@ void vh_launch_pixel2uvec_f32(float cx, float cy, float f, const float* p, int n
 void vh_launch_two_view(const double* A, const double* U, int nf, int nv, double* out, hipStream_t s);
 void vh_launch_n_view(const double* A, const double* U, int nf, int nv, double* out, hipStream_t s);
 void vh_launch_msv1(const MsvJob& job, hipStream_t s);
-// the same for `batch` jobs that live `stride` bytes apart in device memory; a job runs when the int `frame_off` bytes from it equals fire_frame
-void vh_launch_msv1_tab(const void* tab, size_t stride, ptrdiff_t frame_off, int fire_frame, int nf, int batch, hipStream_t s);
+// the same for `batch` jobs that live `stride` bytes apart in device memory; a job runs when the int `frame_off` bytes from it equals fire_frame and
+// (live given) live[b] is not NULL
+void vh_launch_msv1_tab(const void* tab, size_t stride, ptrdiff_t frame_off, int fire_frame, int nf, int batch, hipStream_t s,
+                        const void* const* live = nullptr);

@@ -184,10 +184,17 @@ __device__ __forceinline__ void sess_book_b(SessStream& S, const uint8_t* const*
     }
 }
 
-__global__ __launch_bounds__(256) void k_sess_book_a(SessStream* ss_all) { sess_book_a<256>(ss_all[blockIdx.x]); }
+// A stream whose frame pointer is NULL sits the step out (vh_session_step_some): its workgroup leaves before it has read or written anything, so
+// frame_i, pp, im0, the counts, the pose and the records stay exactly what they were.
+__global__ __launch_bounds__(256) void k_sess_book_a(SessStream* ss_all, const uint8_t* const* frames)
+{
+    if (frames[blockIdx.x] == nullptr) return;
+    sess_book_a<256>(ss_all[blockIdx.x]);
+}
 __global__ __launch_bounds__(256) void k_sess_book_b(SessStream* ss_all, const uint8_t* const* frames, float time_s, float frame_no,
                                                      const float* times, const float* frame_nos)
 {
+    if (frames[blockIdx.x] == nullptr) return;
     sess_book_b<256>(ss_all[blockIdx.x], frames, time_s, frame_no, times, frame_nos);
 }
 
@@ -200,6 +207,7 @@ __global__ __launch_bounds__(256) void k_sess_book_b(SessStream* ss_all, const u
 __global__ __launch_bounds__(SESS_NT) void k_sess_frame(SessStream* ss_all, const uint8_t* const* frames, float time_s, float frame_no,
                                                         const float* times, const float* frame_nos)
 {
+    if (frames[blockIdx.x] == nullptr) return;  // an idle stream (see k_sess_book_a)
     SessStream& S = ss_all[blockIdx.x];
     sess_book_a<SESS_NT>(S);
     __threadfence_block();
@@ -212,8 +220,9 @@ __global__ __launch_bounds__(SESS_NT) void k_sess_frame(SessStream* ss_all, cons
 }
 
 // p3[vg] = p3hat - t ; vp = vg   (vidExample.py:159-160)
-__global__ __launch_bounds__(256) void k_sess_after_msv(SessStream* ss_all, int msv_frame)
+__global__ __launch_bounds__(256) void k_sess_after_msv(SessStream* ss_all, const uint8_t* const* frames, int msv_frame)
 {
+    if (frames[blockIdx.x] == nullptr) return;  // an idle stream parked at its MSV frame was re-triangulated when it got there
     SessStream& S = ss_all[blockIdx.x];
     if (S.frame_i != msv_frame) return;  // only the streams whose own frame counter is at the MSV frame
     for (int k = threadIdx.x; k < S.n_cur; k += 256) {
@@ -230,7 +239,8 @@ __global__ void k_sess_fb_gather(const SessStream* ss_all, const uint8_t* const*
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     const SessStream& S = ss_all[b];
-    rec[b] = SessFbRec{S.klt_flags, S.n_cur, S.im0, frames[b]};
+    // an idle stream still carries the flag word of its last active step: it reports no failure, and its recovery counters do not move
+    rec[b] = SessFbRec{frames[b] ? S.klt_flags : 0, S.n_cur, S.im0, frames[b]};
 }
 __global__ void k_sess_fb_flags(SessStream* S, int bits)
 {
@@ -497,8 +507,9 @@ extern "C" VH_API int vh_session_init_dev(vh_session* s, int slot, const uint8_t
     return session_init(s, slot, frame0, stride, p, p3, vp, nullptr, time0, frame_no, 0.f, t0_dev, res0_dev, n_dev, stream);
 }
 
+// active (host, may be null: every stream steps): the host's copy of "frames_dev[b] is not NULL", for the frame counters it mirrors
 static int session_step(vh_session* s, const uint8_t* const* frames_dev, float time_s, float frame_no, const float* times_dev,
-                        const float* frame_nos_dev, void* stream)
+                        const float* frame_nos_dev, const uint8_t* active, void* stream)
 {
     if (!s || !frames_dev) return vh_fail(-1, "vh_session_step: bad arguments");
     if (s->fb.on) {  // the recovery reads the failure flags on the host: not something a graph can replay
@@ -520,35 +531,137 @@ static int session_step(vh_session* s, const uint8_t* const* frames_dev, float t
         hipLaunchKernelGGL(k_sess_frame, dim3(nb), dim3(SESS_NT), 0, st, s->d_ss, frames_dev, time_s, frame_no, times_dev, frame_nos_dev);
         vh_prof_stop(s->ctx, rec, VH_PROF_SESSION, st);
     } else {  // more pose tracks than 256 threads keep in registers: the 1024-thread pose kernel between the two bookkeeping halves
-        hipLaunchKernelGGL(k_sess_book_a, dim3(nb), dim3(256), 0, st, s->d_ss);
-        vh_launch_pose(&s->d_ss[0].pose, sizeof(SessStream), nb, 0, s->N0, st);
+        hipLaunchKernelGGL(k_sess_book_a, dim3(nb), dim3(256), 0, st, s->d_ss, frames_dev);
+        vh_launch_pose(&s->d_ss[0].pose, sizeof(SessStream), nb, 0, s->N0, st, reinterpret_cast<const void* const*>(frames_dev));
         hipLaunchKernelGGL(k_sess_book_b, dim3(nb), dim3(256), 0, st, s->d_ss, frames_dev, time_s, frame_no, times_dev, frame_nos_dev);
     }
     // fcnMSV1_t fires when a stream reaches ITS frame msv_frame (vidExample.py:155), whenever that stream was initialised
     const bool msv_ok = sess_msv_fires(s->msv_frame, s->nhist);
     bool any = false;
     for (int b = 0; b < nb; b++) {
+        if (active && !active[b]) continue;  // an idle stream's clock stands still
         const int fi = ++s->h_frame[b];
         if (msv_ok && fi == s->msv_frame) any = true;
     }
-    // ONE launch for every stream: a workgroup runs only when its stream's own frame counter is at the MSV frame (k_msv1_tab)
+    // ONE launch for every stream: a workgroup runs only when its stream stepped in this call and its own frame counter is at the MSV frame (k_msv1_tab)
     if (any) vh_launch_msv1_tab(&s->d_ss[0].msv, sizeof(SessStream), (ptrdiff_t)offsetof(SessStream, frame_i) - (ptrdiff_t)offsetof(SessStream, msv),
-                                s->msv_frame, s->msv_frame + 1, nb, st);
-    if (any) hipLaunchKernelGGL(k_sess_after_msv, dim3(nb), dim3(256), 0, st, s->d_ss, s->msv_frame);
+                                s->msv_frame, s->msv_frame + 1, nb, st, reinterpret_cast<const void* const*>(frames_dev));
+    if (any) hipLaunchKernelGGL(k_sess_after_msv, dim3(nb), dim3(256), 0, st, s->d_ss, frames_dev, s->msv_frame);
     SESS_CHECK();
     return 0;
 }
 
 extern "C" VH_API int vh_session_step(vh_session* s, const uint8_t* const* frames_dev, float time_s, float frame_no, void* stream)
 {
-    return session_step(s, frames_dev, time_s, frame_no, nullptr, nullptr, stream);
+    return session_step(s, frames_dev, time_s, frame_no, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" VH_API int vh_session_step_v(vh_session* s, const uint8_t* const* frames_dev, const float* time_s_dev, const float* frame_no_dev,
                                         void* stream)
 {
     if (!time_s_dev || !frame_no_dev) return vh_fail(-1, "vh_session_step_v: bad arguments");
-    return session_step(s, frames_dev, 0.f, 0.f, time_s_dev, frame_no_dev, stream);
+    return session_step(s, frames_dev, 0.f, 0.f, time_s_dev, frame_no_dev, nullptr, stream);
+}
+
+extern "C" VH_API int vh_session_step_some(vh_session* s, const uint8_t* const* frames_dev, const uint8_t* active_host, const float* time_s_dev,
+                                           const float* frame_no_dev, void* stream)
+{
+    if (!active_host || !time_s_dev || !frame_no_dev) return vh_fail(-1, "vh_session_step_some: bad arguments");
+    return session_step(s, frames_dev, 0.f, 0.f, time_s_dev, frame_no_dev, active_host, stream);
+}
+
+// ---- one record per stream: everything a finished clip hands back, packed for ONE device-to-host copy -------------------------------------------------
+// Layout (vh_session_record, byte offsets): a 48-byte header {n_cur, n_pose, frame_i, klt_flags, pose_info[2], t[3], pad, res}, then vg, vp, ids, p, p3,
+// B, S and the history P in the REFERENCE's [5][N0][nhist] order; every array starts on a multiple of 8 bytes.
+static void sess_record_layout(int N0, int nhist, vh_session_record* L)
+{
+    size_t off = 0;
+    auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
+    L->n_cur = put(4 * sizeof(int)) + 0; L->n_pose = L->n_cur + 4; L->frame_i = L->n_cur + 8; L->klt_flags = L->n_cur + 12;
+    L->pose_info = put(2 * sizeof(int));
+    L->t = put(3 * sizeof(float));
+    L->res = put(sizeof(double));
+    L->vg = put((size_t)N0); L->vp = put((size_t)N0);
+    L->ids = put(sizeof(int) * (size_t)N0);
+    L->p = put(sizeof(float) * 2 * (size_t)N0);
+    L->p3 = put(sizeof(double) * 3 * (size_t)N0);
+    L->B = put(sizeof(float) * 14 * (size_t)nhist);
+    L->S = put(sizeof(float) * 9 * (size_t)nhist);
+    L->P = put(sizeof(float) * 5 * (size_t)N0 * (size_t)nhist);
+    L->bytes = off;
+    L->n0 = N0; L->nhist = nhist;
+}
+
+// One launch per record.  Workgroups [0, 5 * ceil(N0 / 64)) transpose the history, one tile of 64 tracks x 64 frames at a time through LDS: the read walks
+// the tracks of one frame (the device's frame-major rows), the write walks the frames of one track (the reference's rows) -- both sides coalesced.  The
+// workgroups behind them copy the flat arrays; the last one also writes the header.
+#define SESS_EXP_TILE 64
+#define SESS_EXP_FLAT 8
+__global__ __launch_bounds__(256) void k_sess_export(const SessStream* ss, vh_session_record L, char* rec, int tiles)
+{
+    const SessStream& S = *ss;
+    const int N0 = S.N0, nh = S.nhist, tid = threadIdx.x;
+    if ((int)blockIdx.x < 5 * tiles) {
+        __shared__ float tile[SESS_EXP_TILE][SESS_EXP_TILE + 1];
+        const int row = blockIdx.x / tiles, g0 = (blockIdx.x - row * tiles) * SESS_EXP_TILE;
+        float* out = reinterpret_cast<float*>(rec + L.P) + (size_t)row * N0 * nh;
+        const int lx = tid & 63, ly = tid >> 6;
+        for (int f0 = 0; f0 < nh; f0 += SESS_EXP_TILE) {
+            for (int f = ly; f < SESS_EXP_TILE; f += 4)
+                if (f0 + f < nh && g0 + lx < N0) tile[f][lx] = S.P[sess_P(row, g0 + lx, f0 + f, N0)];
+            __syncthreads();
+            const int fw = min(SESS_EXP_TILE, nh - f0);  // frames of this tile: consecutive threads walk them, then the next track (adjacent when fw == nhist)
+            for (int e = tid; e < SESS_EXP_TILE * fw; e += 256) {
+                const int g = e / fw, f = e - g * fw;
+                if (g0 + g < N0) out[(size_t)(g0 + g) * nh + f0 + f] = tile[f][g];
+            }
+            __syncthreads();
+        }
+        return;
+    }
+    const int part = blockIdx.x - 5 * tiles, step = SESS_EXP_FLAT * 256, k0 = part * 256 + tid;
+    uint8_t* vg = reinterpret_cast<uint8_t*>(rec + L.vg);
+    uint8_t* vp = reinterpret_cast<uint8_t*>(rec + L.vp);
+    int* ids = reinterpret_cast<int*>(rec + L.ids);
+    float* p = reinterpret_cast<float*>(rec + L.p);
+    double* p3 = reinterpret_cast<double*>(rec + L.p3);
+    float* B = reinterpret_cast<float*>(rec + L.B);
+    float* R = reinterpret_cast<float*>(rec + L.S);
+    const int n = S.n_cur;
+    for (int k = k0; k < N0; k += step) { vg[k] = S.vg[k]; vp[k] = S.vp[k]; ids[k] = k < n ? S.ids[k] : -1; }  // rows past n_cur: no track (-1, 0)
+    for (int k = k0; k < 2 * N0; k += step) p[k] = k < 2 * n ? S.p_cur[k] : 0.f;
+    for (int k = k0; k < 3 * N0; k += step) p3[k] = S.p3[k];
+    for (int k = k0; k < 14 * nh; k += step) B[k] = S.B[k];
+    for (int k = k0; k < 9 * nh; k += step) R[k] = S.S[k];
+    if (part == SESS_EXP_FLAT - 1 && tid == 0) {
+        int* h = reinterpret_cast<int*>(rec + L.n_cur);
+        h[0] = n; h[1] = S.n_pose; h[2] = S.frame_i; h[3] = S.klt_flags;
+        int* pi = reinterpret_cast<int*>(rec + L.pose_info);
+        pi[0] = S.pose_info[0]; pi[1] = S.pose_info[1];
+        float* t = reinterpret_cast<float*>(rec + L.t);
+        t[0] = S.t[0]; t[1] = S.t[1]; t[2] = S.t[2]; t[3] = 0.f;  // (the pad word: the whole record is defined)
+        *reinterpret_cast<double*>(rec + L.res) = S.res;
+    }
+}
+
+extern "C" VH_API size_t vh_session_export_size(const vh_session* s, vh_session_record* layout_host)
+{
+    if (!s) { vh_fail(-1, "vh_session_export_size: bad arguments"); return 0; }
+    vh_session_record L;
+    sess_record_layout(s->N0, s->nhist, &L);
+    if (layout_host) *layout_host = L;
+    return L.bytes;
+}
+
+extern "C" VH_API int vh_session_export(vh_session* s, int slot, void* rec_dev, void* stream)
+{
+    if (!s || !rec_dev || slot < 0 || slot >= s->batch || (reinterpret_cast<uintptr_t>(rec_dev) & 7)) return vh_fail(-1, "vh_session_export: bad arguments (the record must be 8-byte aligned)");
+    vh_session_record L;
+    sess_record_layout(s->N0, s->nhist, &L);
+    const int tiles = (s->N0 + SESS_EXP_TILE - 1) / SESS_EXP_TILE;
+    hipLaunchKernelGGL(k_sess_export, dim3(5 * tiles + SESS_EXP_FLAT), dim3(256), 0, (hipStream_t)stream, s->d_ss + slot, L, reinterpret_cast<char*>(rec_dev), tiles);
+    SESS_CHECK();
+    return 0;
 }
 
 // packed track state of every stream for the cross-GPU exchange (K20): per stream a record of 8 + 3*N0 float32 words

@@ -56,27 +56,38 @@ class TrackerSession:
         self._init_keep = [k for k in self._init_keep if k[0] != slot] + [(slot, pd, p3d, vpd)]
 
     def set_frames(self, frames):
-        """frames: list of `batch` CUDA uint8 [H,W] tensors (kept alive until the next call replaces them)."""
+        """frames: list of `batch` CUDA uint8 [H,W] tensors (kept alive until the next call replaces them); a None entry is a stream that sits the step
+        out: its table entry is a null pointer and the frame of its last active step stays alive (it is the im0 of its next active one).
+        -> None when every stream has a frame, else the host mask uint8 [batch] of the active streams."""
         torch = self.torch
+        assert len(frames) == self.batch
         ptrs = []
         for f in frames:
+            if f is None:
+                ptrs.append(0)
+                continue
             assert f.is_cuda and f.dtype == torch.uint8 and f.shape == (self.h, self.w) and f.is_contiguous()
             ptrs.append(f.data_ptr())
         self._prev_keep = self._keep
-        self._keep = list(frames)
+        self._keep = [k if f is None else f for f, k in zip(frames, self._keep)]
         self._frames.copy_(torch.tensor(ptrs, dtype=torch.int64), non_blocking=False)
+        return None if all(ptrs) else np.array([1 if q else 0 for q in ptrs], np.uint8)
 
-    def step(self, frames=None, time_s=0.0, frame_no=0.0, frames_table=None):
+    def step(self, frames=None, time_s=0.0, frame_no=0.0, frames_table=None, active=None):
         """One frame for every stream.  Either `frames` (list of tensors) or `frames_table` (int64 CUDA tensor of pointers).
+
+        A stream may sit the step out (vh_session_step_some): a None entry of `frames`, or with `frames_table` a zero pointer AND a zero in `active`
+        (host uint8 [batch]; the two must agree).  Its state is untouched -- a slot that was never initialised is a legal idle stream -- and its last
+        frame stays alive until its next active step.  Without idle streams the step takes exactly the calls it always took.
 
         time_s / frame_no: scalars (every stream shares the clock) or sequences / tensors of `batch` values (independent videos,
         each with its own CAP_PROP_POS_MSEC and frame counter).  With `frames_table` the caller owns the frame buffers: the
         frames of step i are read again by step i+1 (as im0) and must stay alive until that step has run."""
         if frames is not None:
-            self.set_frames(frames)
+            active = self.set_frames(frames)
         tab = self._frames if frames_table is None else frames_table
         is_t = [hasattr(x, "is_cuda") for x in (time_s, frame_no)]  # torch tensors first: numpy must never see a CUDA tensor
-        if not any(is_t) and np.ndim(time_s) == 0 and np.ndim(frame_no) == 0:
+        if active is None and not any(is_t) and np.ndim(time_s) == 0 and np.ndim(frame_no) == 0:
             L.check(self.lib.vh_session_step(self.handle, L.dptr(tab), float(time_s), float(frame_no), L.stream_ptr()), "vh_session_step")
             return
         torch = self.torch
@@ -90,26 +101,49 @@ class TrackerSession:
         tv, fv = clock(time_s, is_t[0]), clock(frame_no, is_t[1])
         assert tv.numel() == self.batch and fv.numel() == self.batch
         self._clock_keep = (tv, fv)
+        if active is not None:
+            act = np.ascontiguousarray(active, np.uint8)
+            assert act.shape == (self.batch,)
+            L.check(self.lib.vh_session_step_some(self.handle, L.dptr(tab), act.ctypes.data, L.dptr(tv), L.dptr(fv), L.stream_ptr()), "vh_session_step_some")
+            return
         L.check(self.lib.vh_session_step_v(self.handle, L.dptr(tab), L.dptr(tv), L.dptr(fv), L.stream_ptr()), "vh_session_step_v")
 
     def step_bgr(self, frames_bgr, time_s=0.0, frame_no=0.0):
         """One frame for every stream straight from BGR frames (the decoder's output, vidExample.py:89-91): the fused ingest writes the gray frames
         and the quarter-scale images in one pass (vh_session_ingest_bgr), then the step runs on them.  frames_bgr: list of `batch` CUDA uint8 [H,W,3]
-        tensors.  The session owns two sets of gray buffers (a frame is read by two steps: as `im`, then as `im0`)."""
+        tensors.  The session owns two sets of gray buffers (a frame is read by two steps: as `im`, then as `im0`).
+        A None entry is a stream that sits the step out, as in step(): nothing of it is ingested, and its gray frame of its last active step is kept (each
+        stream alternates between its two buffers on its own active steps).  Returns the gray frames of the step: the [batch, H, W] buffer, or with idle
+        streams a list with None in their places."""
         torch = self.torch
+        assert len(frames_bgr) == self.batch
         if getattr(self, "_gray", None) is None:
             self._gray = [torch.empty((self.batch, self.h, self.w), dtype=torch.uint8, device="cuda") for _ in range(2)]
             self._gray_tab = [torch.tensor([g[b].data_ptr() for b in range(self.batch)], dtype=torch.int64, device="cuda") for g in self._gray]
             self._gray_i = 0
+            self._gray_k = [0] * self.batch  # per stream: the buffer its next active step writes
         ptrs = []
         for f in frames_bgr:
+            if f is None:
+                ptrs.append(0)
+                continue
             assert f.is_cuda and f.dtype == torch.uint8 and f.shape == (self.h, self.w, 3) and f.is_contiguous()
             ptrs.append(f.data_ptr())
         self._bgr_keep = list(frames_bgr)
         bgr_tab = torch.tensor(ptrs, dtype=torch.int64).cuda()
         self._bgr_tab_keep = bgr_tab
-        k = self._gray_i
-        self._gray_i ^= 1
+        if not all(ptrs) or len(set(self._gray_k)) > 1:  # some stream is idle now, or was: the streams no longer alternate in step
+            ks = self._gray_k
+            gray = [None if not q else self._gray[ks[b]][b] for b, q in enumerate(ptrs)]
+            gtab = torch.tensor([0 if g is None else g.data_ptr() for g in gray], dtype=torch.int64).cuda()
+            self._gray_k = [k ^ 1 if q else k for k, q in zip(ks, ptrs)]
+            L.check(self.lib.vh_session_ingest_bgr(self.handle, L.dptr(bgr_tab), 3 * self.w, L.dptr(gtab), L.stream_ptr()), "vh_session_ingest_bgr")
+            self._gray_tab_keep = gtab
+            self.step(frames_table=gtab, time_s=time_s, frame_no=frame_no, active=np.array([1 if q else 0 for q in ptrs], np.uint8))
+            return gray
+        k = self._gray_k[0]
+        self._gray_k = [k ^ 1] * self.batch
+        self._gray_i = k ^ 1
         L.check(self.lib.vh_session_ingest_bgr(self.handle, L.dptr(bgr_tab), 3 * self.w, L.dptr(self._gray_tab[k]), L.stream_ptr()), "vh_session_ingest_bgr")
         self.step(frames_table=self._gray_tab[k], time_s=time_s, frame_no=frame_no)
         return self._gray[k]
@@ -155,6 +189,34 @@ class TrackerSession:
             frame_i=int(self._rd(v.frame_i, 1, np.int32)[0]), klt_flags=int(self._rd(v.klt_flags, 1, np.int32)[0]),
             pose_info=self._rd(v.pose_info, 2, np.int32))
 
+    def record_layout(self):
+        """vh_session_record of this session: byte offsets of the fields of an exported record (and `bytes`, its size)."""
+        if getattr(self, "_layout", None) is None:
+            lay = L.SessionRecord()
+            if not self.lib.vh_session_export_size(self.handle, C.byref(lay)):
+                L.check(-1, "vh_session_export_size")
+            self._layout = lay
+        return self._layout
+
+    def export(self, slot=0, out=None):
+        """Everything state() returns, without stopping the device: ONE launch packs the stream into a contiguous record (vh_session_export: the history
+        is transposed to the reference's [5, N0, nhist] on the device), ONE asynchronous copy brings it into the pinned buffer `out` (uint8 torch tensor
+        of record_layout().bytes bytes; a new one if None) and an event marks its arrival.  Returns a handle: .done() polls, .result() waits for the event
+        and returns the dict of state() (fresh arrays: `out` may be reused afterwards); .recoveries are the stream's recovery counters (vh_session_recoveries)
+        at the time of the call.  Issue it on the session's HIP stream, like every call of the session."""
+        torch = self.torch
+        lay = self.record_layout()
+        if getattr(self, "_rec_dev", None) is None:
+            self._rec_dev = torch.empty(lay.bytes, dtype=torch.uint8, device="cuda")  # one per session: packs and copies are ordered by its stream
+        if out is None:
+            out = torch.empty(lay.bytes, dtype=torch.uint8).pin_memory()
+        assert out.dtype == torch.uint8 and out.numel() >= lay.bytes and out.is_pinned() and out.is_contiguous()
+        L.check(self.lib.vh_session_export(self.handle, slot, L.dptr(self._rec_dev), L.stream_ptr()), "vh_session_export")
+        out[: lay.bytes].copy_(self._rec_dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return ExportedState(out, lay, ev, self.recoveries()[slot])
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -163,6 +225,39 @@ class TrackerSession:
                 self.handle = None
         except Exception:
             pass
+
+
+class ExportedState:
+    """A stream's state on its way to the host (TrackerSession.export)."""
+
+    def __init__(self, buf, layout, event, recoveries):
+        self.buf, self.layout, self.event, self.recoveries = buf, layout, event, recoveries
+        self._res = None
+
+    def done(self):
+        """True once the record has arrived (never waits)."""
+        return self._res is not None or self.event.query()
+
+    def result(self):
+        if self._res is None:
+            self.event.synchronize()
+            self._res = unpack_record(self.buf.numpy(), self.layout)
+        return self._res
+
+
+def unpack_record(raw, lay):
+    """A vh_session_record (uint8 array `raw`, offsets `lay`) as the dict TrackerSession.state() returns; every array is a copy."""
+    n0, nh = lay.n0, lay.nhist
+
+    def rd(off, count, dtype):
+        return np.frombuffer(raw, dtype, count, off).copy()
+
+    n_cur, n_pose, frame_i, klt_flags = (int(rd(off, 1, np.int32)[0]) for off in (lay.n_cur, lay.n_pose, lay.frame_i, lay.klt_flags))
+    return dict(vg=rd(lay.vg, n0, np.uint8).astype(bool), vp=rd(lay.vp, n0, np.uint8).astype(bool), p=rd(lay.p, 2 * n_cur, np.float32).reshape(n_cur, 2),
+                ids=rd(lay.ids, n_cur, np.int32), P=rd(lay.P, 5 * n0 * nh, np.float32).reshape(5, n0, nh), B=rd(lay.B, nh * 14, np.float32).reshape(nh, 14),
+                S=rd(lay.S, nh * 9, np.float32).reshape(nh, 9), p3=rd(lay.p3, 3 * n0, np.float64).reshape(n0, 3), t=rd(lay.t, 3, np.float32),
+                res=float(rd(lay.res, 1, np.float64)[0]), n_cur=n_cur, n_pose=n_pose, frame_i=frame_i, klt_flags=klt_flags,
+                pose_info=rd(lay.pose_info, 2, np.int32))
 
 
 class HostFrameFeeder:
@@ -523,9 +618,12 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     fnos = np.stack([np.asarray(c.get("frame_numbers", np.arange(n)), np.float32) for c in clips])
     keep = [None] * nclip
     t_begin = _time.perf_counter()
+    f0_events = []
     for g in range(G):
         ses, mem = sess[g], members[g]
         with torch.cuda.stream(hip_streams[g]):
+            f0_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+            f0_events[-1][0].record()
             # frame 0 of every clip of the session: ONE vh_frame0_init_batch launch sequence into rows [slot] of these tensors
             bufs = _frame0_buffers(torch, len(mem), cap)
             rois = _frame0_batch_call(ses.lib, ses.ws, [dev[b][0] for b in mem], [clips[b]["q"] for b in mem], W, H, ses.K64, plate_w, roi_border, max_corners,
@@ -536,6 +634,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
                                                     L.dptr(n0[j]), float(times[b, 0]), float(fnos[b, 0]), L.stream_ptr()), "vh_session_init_dev")
                 ses._keep[j] = dev[b][0]
                 keep[b] = (tuple(x[j] for x in bufs), tuple(rois[8 * j:8 * j + 8]))
+            f0_events[-1][1].record()
     t_loop = _time.perf_counter()
     for i in range(1, n):
         for g in range(G):
@@ -544,6 +643,8 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     torch.cuda.synchronize()
     loop_seconds = _time.perf_counter() - t_loop
     seconds = _time.perf_counter() - t_begin
+    # what tools/exp/queue_timing.py reads: device time of the frame-0 block of every session (events on its stream), to set beside run_queue's
+    run_sequences.last_stats = dict(sessions=G, steps=n - 1, admission_ms=float(sum(a.elapsed_time(b) for a, b in f0_events)), admissions=G)
     results = []
     for b, c in enumerate(clips):
         st = sess[owner[b]].state(slot[b])
@@ -561,6 +662,246 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
                             t0=t0.cpu().numpy(), R0=R0.cpu().numpy().reshape(3, 3), res0=float(res0.item()), boxa=rois[0:4], boxb=rois[4:8],
                             klt_flags=st["klt_flags"], recoveries=sess[owner[b]].recoveries()[slot[b]], lines=lines, seconds=seconds, ms_per_frame=1e3 * loop_seconds / (n - 1), sessions=G))
     return results
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# a queue of clips of any length on a fixed set of resident streams
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _slot_split(streams, sessions):
+    """Slots per session: `streams` slots in contiguous blocks over `sessions` sessions (the rule of run_sequences)."""
+    owner = [b * sessions // streams for b in range(streams)]
+    return [owner.count(g) for g in range(sessions)]
+
+
+def _queue_steps(next_length, sizes):
+    """The schedule of run_queue, one global step at a time.  `next_length()` hands out the length (frames, >= 2) of the next clip of the FIFO, or None when
+    the queue is empty; it is called only when a slot is free, in (session, slot) order.  Yields per step dict(admit, frames, done):
+      admit   [(session, slot, clip)]: the clips that take a free slot at this step -- their frame 0 is initialised before the sessions step;
+      frames  [session][slot] -> (clip, frame index) the slot tracks in this step's launch sequence, or None: the slot is empty and sits the step out;
+      done    [(session, slot, clip)]: the clips whose last frame this was -- exported and freed, so the slot is refilled at the very next step."""
+    slots = [[None] * n for n in sizes]
+    clip, empty = 0, False
+    while True:
+        admit = []
+        for g, ses in enumerate(slots):
+            for j, cur in enumerate(ses):
+                if cur is None and not empty:
+                    n = next_length()
+                    if n is None:
+                        empty = True
+                        continue
+                    if n < 2:
+                        raise ValueError(f"clip {clip} has {n} frames: a clip needs at least two")
+                    ses[j] = [clip, 1, int(n)]
+                    admit.append((g, j, clip))
+                    clip += 1
+        if not any(cur is not None for ses in slots for cur in ses):
+            return
+        frames = [[None if cur is None else (cur[0], cur[1]) for cur in ses] for ses in slots]
+        done = []
+        for g, ses in enumerate(slots):
+            for j, cur in enumerate(ses):
+                if cur is not None:
+                    cur[1] += 1
+                    if cur[1] == cur[2]:
+                        done.append((g, j, cur[0]))
+                        ses[j] = None
+        yield dict(admit=admit, frames=frames, done=done)
+
+
+def queue_plan(lengths, streams, sessions=1):
+    """The whole schedule run_queue follows for clips of these lengths (a pure function: no device): the list of the steps of _queue_steps.  Greedy and
+    FIFO: at every global step each free slot takes the next waiting clip, in (session, slot) order; a clip of n frames is admitted (frame 0) and tracked
+    (frame 1) in its first step and holds its slot for n - 1 consecutive steps."""
+    it = iter(lengths)
+    sessions = max(1, min(int(sessions), int(streams)))
+    return list(_queue_steps(lambda: next(it, None), _slot_split(int(streams), sessions)))
+
+
+def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
+              harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=None, use_harris=True, min_distance=0.0, fallback=False,
+              fallback_params=None):
+    """A queue of clips of ANY length on `streams` resident streams: what run_sequences is for clips of one length.  `clips` = any iterable of
+    dict(frames, q, times[, frame_numbers, name]) of ONE frame size, each of >= 2 frames; it is consumed lazily -- a clip is pulled when a slot is free
+    for it and its frames go up then, so at most `streams` clips are resident -- and may hold more clips than fit on the device at once.
+    max_frames   the sessions' history length: no clip may be longer (ValueError when it is admitted); required unless `clips` is a list.
+    sessions     the slots are split over this many TrackerSessions, each on its own HIP stream (0 = auto, session_groups(streams)); results do not
+                 depend on it.
+    The schedule is queue_plan's: one shared FIFO; at every global step each free slot takes the next clip, all admissions of a session are ONE frame-0
+    batch call (+ one vh_session_init_dev per slot) on the session's stream, then every session issues ONE step in which its empty slots sit out
+    (vh_session_step_some); a clip that has just had its last frame is exported (TrackerSession.export: one launch, one copy) and its slot is free.
+    With fallback=False the loop never waits for the device except for a result whose pinned buffer is needed again (a ring of 2 x streams) and at
+    the end of the run; frames given as CUDA tensors are used in place, host frames are uploaded on a side stream.
+    on_result(index, result) is called as results land (polled at every step, never waited for); returns the results in input order.  A result has
+    the keys of run_sequences' results, P / B / S cut to the clip's own length and the track rows to n_tracks0; `lines` = the clip's table and summary."""
+    import time as _time
+
+    torch = L.torch_cuda()
+    if max_frames is None:
+        if not isinstance(clips, (list, tuple)):
+            raise ValueError("run_queue: max_frames is required unless `clips` is a list")
+        max_frames = max(len(c["frames"]) for c in clips)
+    nhist, streams = int(max_frames), int(streams)
+    assert streams >= 1 and nhist >= 2
+    cap = 4 + int(max_corners)
+    G = int(sessions) if sessions and sessions > 0 else session_groups(streams, max_corners)
+    G = max(1, min(G, streams))
+    sizes = _slot_split(streams, G)
+    hip_streams = session_streams(G)
+    main, upload = hip_streams[0], _upload_stream()
+    plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
+    source = iter(clips)
+    pulled = {}          # clip index -> the clip as its slot uses it (dropped when the clip is done)
+    size = [None]
+
+    def next_length():
+        c = next(source, None)
+        if c is None:
+            return None
+        k = next_length.count
+        n = len(c["frames"])
+        if n > nhist:
+            raise ValueError(f"run_queue: clip {k} has {n} frames, more than max_frames = {nhist}")
+        if n >= 2:
+            host = [f for f in c["frames"] if not (isinstance(f, torch.Tensor) and f.is_cuda)]
+            with torch.cuda.stream(upload if host else main):  # (host frames: an upload that waits for nothing the sessions have queued)
+                dev = [(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))).cuda(non_blocking=True).contiguous() for f in c["frames"]]
+            size[0] = size[0] or tuple(dev[0].shape)
+            assert all(d.shape == size[0] and d.dtype == torch.uint8 for d in dev), "clips must share one frame size"
+            pulled[k] = dict(dev=dev, uploaded=bool(host), q=c["q"], times=np.asarray(c["times"], np.float32),
+                             fnos=np.asarray(c.get("frame_numbers", np.arange(n)), np.float32), frame_numbers=c.get("frame_numbers", list(range(n))),
+                             name=c.get("name", f"clip {k}"), n=n)
+        next_length.count += 1
+        return n
+
+    next_length.count = 0
+    sess, rec_bytes = [], 0
+    ring, ring_i = [], 0   # pinned records + frame-0 extras, 2 x streams of them; entry: [record, extras, pending job or None]
+    pending, results, t_admit = [], {}, []
+    t_begin = _time.perf_counter()
+
+    def deliver(job):
+        st = job["handle"].result()
+        c, n = job["clip"], job["clip"]["n"]
+        x = job["extras"].numpy().copy()
+        k = int(st["S"][0, 2])  # the tracks found at frame 0 (k_sess_init writes the count there); rows beyond them never existed
+        S = st["S"][:n].copy()
+        seconds = _time.perf_counter() - job["t_admit"]
+        S[0, 1] = 0.0
+        S[1:, 1] = seconds / (n - 1)  # every row carries the mean time of the clip's frame steps in the queue
+        lines = [f"Starting image processing on {c['name']} ...", TABLE_HEADER] + [table_row(S[i]) for i in range(n)]
+        lines += summary_lines(S, n, c["frame_numbers"], seconds)
+        if out is not None:
+            for ln in lines:
+                out(ln)
+        rois = job["rois"]
+        res = dict(S=S, B=st["B"][:n].copy(), P=st["P"][:, :k, :n].copy(), vg=st["vg"][:k], vp=st["vp"][:k], p=st["p"], p3=st["p3"][:k], ids=st["ids"],
+                   n_tracks0=k, t0=st["B"][0, 0:3].copy(), R0=x[0:9].reshape(3, 3), res0=float(x[9]), boxa=rois[0:4], boxb=rois[4:8], klt_flags=st["klt_flags"],
+                   recoveries=job["handle"].recoveries, lines=lines, seconds=seconds, ms_per_frame=1e3 * seconds / (n - 1), sessions=G)
+        results[job["index"]] = res
+        job["entry"][2] = None
+        pending.remove(job)
+        if on_result is not None:
+            on_result(job["index"], res)
+
+    held = [[None] * n for n in sizes]  # per slot: what the clip's result needs besides the record (frame-0 outputs, ROIs, admission time)
+    idle_slots = steps = 0
+    for step in _queue_steps(next_length, sizes):
+        for job in [j for j in pending if j["handle"].done()]:
+            deliver(job)
+        if not sess:  # the first clips have been pulled: the frame size is known
+            H, W = size[0]
+            for g in range(G):
+                with torch.cuda.stream(hip_streams[g]):  # (a session's context serves one HIP stream: everything of session g is issued on stream g)
+                    ses = TrackerSession(K, W, H, cap, nhist=nhist, batch=sizes[g], lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame,
+                                         fallback=fallback, fallback_params=fallback_params)
+                    # the frame-0 scratch for a full house, so that no later admission grows it (growing waits for the stream)
+                    L.check(ses.lib.vh_init_reserve_batch(ses.ws.handle, sizes[g], W, H, L.stream_ptr()), "vh_init_reserve_batch")
+                    sess.append(ses)
+            rec_bytes = sess[0].record_layout().bytes
+            ring = [[torch.empty(rec_bytes, dtype=torch.uint8).pin_memory(), torch.empty(10, dtype=torch.float64).pin_memory(), None] for _ in range(2 * streams)]
+        for g in range(G):
+            ses, hs = sess[g], hip_streams[g]
+            adm = [(j, k) for gg, j, k in step["admit"] if gg == g]
+            with torch.cuda.stream(hs):
+                if adm:
+                    if hs != main:
+                        hs.wait_stream(main)   # frames the caller produced on the current stream
+                    if any(pulled[k]["uploaded"] for _, k in adm):
+                        hs.wait_stream(upload)
+                    for _, k in adm:
+                        if pulled[k]["uploaded"] or hs != main:  # frames allocated on another stream than the one that reads them
+                            for f in pulled[k]["dev"]:
+                                f.record_stream(hs)
+                    ev0 = torch.cuda.Event(enable_timing=True)
+                    ev1 = torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                    # frame 0 of every clip this session admits now: ONE batch call into rows [a] of these tensors, then one init per slot
+                    bufs = _frame0_buffers(torch, len(adm), cap)
+                    rois = _frame0_batch_call(ses.lib, ses.ws, [pulled[k]["dev"][0] for _, k in adm], [pulled[k]["q"] for _, k in adm], W, H, ses.K64, plate_w,
+                                              roi_border, max_corners, quality, block, harris_k, subpix, bufs, use_harris, min_distance)
+                    p, p3, vp, t0, R0, res0, n0 = bufs
+                    for a, (j, k) in enumerate(adm):
+                        c = pulled[k]
+                        L.check(ses.lib.vh_session_init_dev(ses.handle, j, L.dptr(c["dev"][0]), W, L.dptr(p[a]), L.dptr(p3[a]), L.dptr(vp[a]), L.dptr(t0[a]),
+                                                            L.dptr(res0[a]), L.dptr(n0[a]), float(c["times"][0]), float(c["fnos"][0]), L.stream_ptr()),
+                                "vh_session_init_dev")
+                        held[g][j] = dict(bufs=bufs, row=a, rois=tuple(rois[8 * a:8 * a + 8]), t_admit=_time.perf_counter())
+                    ev1.record()
+                    t_admit.append((ev0, ev1))
+                # ONE step of the session: a pointer per slot (null: the slot sits the step out), its clock, and the host's copy of who is active
+                row = step["frames"][g]
+                idle_slots += sum(e is None for e in row)
+                if not any(row):
+                    continue  # (nothing resident in this session: no launch sequence at all)
+                ptrs = np.array([0 if e is None else pulled[e[0]]["dev"][e[1]].data_ptr() for e in row], np.int64)
+                clk = np.array([[0.0 if e is None else pulled[e[0]]["times"][e[1]] for e in row], [0.0 if e is None else pulled[e[0]]["fnos"][e[1]] for e in row]],
+                               np.float32)
+                tab = torch.from_numpy(ptrs).pin_memory().cuda(non_blocking=True)  # (pinned staging: a pageable upload would wait for the stream)
+                clk = torch.from_numpy(clk).pin_memory().cuda(non_blocking=True)
+                ses._queue_keep = (tab, clk)
+                ses.step(frames_table=tab, time_s=clk[0], frame_no=clk[1], active=(ptrs != 0).astype(np.uint8))
+                for gg, j, k in step["done"]:
+                    if gg != g:
+                        continue
+                    entry = ring[ring_i % len(ring)]
+                    ring_i += 1
+                    if entry[2] is not None:
+                        deliver(entry[2])  # the one wait of the loop: this pinned buffer still holds a result nobody has taken
+                    hd = held[g][j]
+                    handle = ses.export(j, out=entry[0])
+                    # (the plate pose of frame 0 is no part of the stream's state: 80 bytes beside the record)
+                    entry[1].copy_(torch.cat([hd["bufs"][4][hd["row"]], hd["bufs"][5][hd["row"]:hd["row"] + 1]]), non_blocking=True)
+                    handle.event.record()
+                    job = dict(handle=handle, extras=entry[1], entry=entry, index=k, clip={q: v for q, v in pulled.pop(k).items() if q != "dev"},
+                               rois=hd["rois"], t_admit=hd["t_admit"])
+                    entry[2] = job
+                    pending.append(job)
+                    held[g][j] = None
+        steps += 1
+        for job in [j for j in pending if j["handle"].done()]:
+            deliver(job)
+    for hs in hip_streams:
+        hs.synchronize()
+    for job in list(pending):
+        deliver(job)
+    seconds = _time.perf_counter() - t_begin
+    n_clips = next_length.count
+    run_queue.last_stats = dict(steps=steps, sessions=G, mean_idle_slots=idle_slots / max(steps, 1), seconds=seconds,
+                                admission_ms=float(sum(a.elapsed_time(b) for a, b in t_admit)), admissions=len(t_admit))
+    return [results[k] for k in range(n_clips)]
+
+
+_UPLOAD_STREAMS = {}
+
+
+def _upload_stream():
+    """The side stream run_queue uploads host frames on (one per device, created once, like the session streams)."""
+    torch = L.torch_cuda()
+    dev = torch.cuda.current_device()
+    if dev not in _UPLOAD_STREAMS:
+        _UPLOAD_STREAMS[dev] = torch.cuda.Stream(device=dev)
+    return _UPLOAD_STREAMS[dev]
 
 
 def main(argv=None):
