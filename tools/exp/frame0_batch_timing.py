@@ -27,6 +27,7 @@ from velocity_amd.common import worldPointsLicensePlate  # noqa: E402
 
 W, H, BORDER, MC, NFR = 1920, 1080, (700, 500), 1000, 20
 SUBPIX = (5, 100, 0.001)
+SETTINGS = D.Frame0Settings(roi_border=BORDER, max_corners=MC, subpix=SUBPIX)  # (everything else: the reference's call)
 
 
 def plate_quad(b):
@@ -49,13 +50,12 @@ def make_clips(n, frames=NFR):
 
 
 class Setup:
-    """Sessions, streams and output buffers of one size, as run_sequences builds them."""
+    """Sessions and streams of one size, as run_sequences builds them, and the output buffers of path (a)."""
 
     def __init__(self, clips):
         torch = L.torch_cuda()
         self.torch, self.clips = torch, clips
         n = len(clips)
-        self.cap = 4 + MC
         G = D.session_groups(n, MC)
         owner = [b * G // n for b in range(n)]
         self.members = [[b for b in range(n) if owner[b] == g] for g in range(G)]
@@ -63,9 +63,8 @@ class Setup:
         self.sess = []
         for g in range(G):
             with torch.cuda.stream(self.streams[g]):
-                self.sess.append(D.TrackerSession(synth.K_1080P, W, H, self.cap, nhist=NFR, batch=len(self.members[g])))
-        self.plate = np.ascontiguousarray(np.asarray(worldPointsLicensePlate("Chile"), np.float64).reshape(12))
-        self.bufs = {k: [D._frame0_buffers(torch, len(m), self.cap) for m in self.members] for k in ("a", "b")}
+                self.sess.append(D.TrackerSession(synth.K_1080P, W, H, SETTINGS.cap, nhist=NFR, batch=len(self.members[g])))
+        self.bufs = [SETTINGS.outputs(len(m)) for m in self.members]
         torch.cuda.synchronize()
 
     def run_a(self):
@@ -73,14 +72,14 @@ class Setup:
         win, it, eps = SUBPIX
         for g, mem in enumerate(self.members):
             ses = self.sess[g]
-            p, p3, vp, t0, R0, res0, n0 = self.bufs["a"][g]
+            p, p3, vp, t0, R0, res0, n0 = self.bufs[g]
             with self.torch.cuda.stream(self.streams[g]):
                 for j, b in enumerate(mem):
                     f0 = self.clips[b]["frames"][0]
                     q = np.ascontiguousarray(self.clips[b]["q"])
                     rois = (C.c_int * 8)()
                     L.check(ses.lib.vh_frame0_init(ses.ws.handle, L.dptr(f0), W, H, W, q.ctypes.data_as(L.f32p), ses.K64.ctypes.data_as(L.f64p),
-                                                   self.plate.ctypes.data_as(L.f64p), BORDER[0], BORDER[1], MC, 0.01, 5, 0.04, win, it, eps, L.dptr(p[j]),
+                                                   SETTINGS.plate_w.ctypes.data_as(L.f64p), BORDER[0], BORDER[1], MC, 0.01, 5, 0.04, win, it, eps, L.dptr(p[j]),
                                                    L.dptr(p3[j]), L.dptr(vp[j]), L.dptr(t0[j]), L.dptr(R0[j]), L.dptr(res0[j]), L.dptr(n0[j]), rois,
                                                    L.stream_ptr()), "vh_frame0_init")
                     L.check(ses.lib.vh_session_init_dev(ses.handle, j, L.dptr(f0), W, L.dptr(p[j]), L.dptr(p3[j]), L.dptr(vp[j]), L.dptr(t0[j]),
@@ -88,28 +87,23 @@ class Setup:
         self.torch.cuda.synchronize()
 
     def run_b(self):
-        """one vh_frame0_init_batch per session + vh_session_init_dev per clip (run_sequences since vh_version 106)."""
-        for g, mem in enumerate(self.members):
-            ses = self.sess[g]
-            bufs = self.bufs["b"][g]
-            p, p3, vp, t0, R0, res0, n0 = bufs
-            with self.torch.cuda.stream(self.streams[g]):
-                D._frame0_batch_call(ses.lib, ses.ws, [self.clips[b]["frames"][0] for b in mem], [self.clips[b]["q"] for b in mem], W, H, ses.K64, self.plate,
-                                     BORDER, MC, 0.01, 5, 0.04, SUBPIX, bufs)
-                for j, b in enumerate(mem):
-                    L.check(ses.lib.vh_session_init_dev(ses.handle, j, L.dptr(self.clips[b]["frames"][0]), W, L.dptr(p[j]), L.dptr(p3[j]), L.dptr(vp[j]),
-                                                        L.dptr(t0[j]), L.dptr(res0[j]), L.dptr(n0[j]), 0.0, 0.0, L.stream_ptr()), "vh_session_init_dev")
+        """TrackerSession.admit per session: one vh_frame0_init_batch + vh_session_init_dev per clip (run_sequences since vh_version 106)."""
+        self.admitted = []
+        for ses, hs, mem in zip(self.sess, self.streams, self.members):
+            with self.torch.cuda.stream(hs):
+                self.admitted.append(ses.admit([(j, self.clips[b]["frames"][0], self.clips[b]["q"], 0.0, 0.0) for j, b in enumerate(mem)], SETTINGS))
         self.torch.cuda.synchronize()
 
     def same(self):
-        """Both paths computed the same frame 0 (n, p[:n], t, R bit for bit)."""
-        for ba, bb in zip(self.bufs["a"], self.bufs["b"]):
+        """Both paths computed the same frame 0 (n, p[:n], t, R bit for bit): the outputs of (a) against what the admission of (b), the last to run, left
+        in the sessions."""
+        for ses, adm, ba in zip(self.sess, self.admitted, self.bufs):
             pa, _, _, ta, Ra, _, na = (x.cpu().numpy() for x in ba)
-            pb, _, _, tb, Rb, _, nb = (x.cpu().numpy() for x in bb)
-            if not (np.array_equal(na, nb) and np.array_equal(ta, tb) and np.array_equal(Ra, Rb)):
-                return False
-            if not all(np.array_equal(pa[j, :na[j]], pb[j, :nb[j]]) for j in range(len(na))):
-                return False
+            for j in range(ses.batch):
+                st = ses.state(j)
+                if not (st["n_cur"] == na[j] and np.array_equal(st["p"], pa[j, :na[j]]) and np.array_equal(st["t"], ta[j])
+                        and np.array_equal(adm[j].R0.cpu().numpy(), Ra[j])):
+                    return False
         return True
 
 

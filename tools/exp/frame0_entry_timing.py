@@ -15,11 +15,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from frame0_batch_timing import BORDER, MC, SUBPIX, H, W, plate_quad  # noqa: E402
+from frame0_batch_timing import BORDER, MC, SETTINGS, SUBPIX, H, W, plate_quad  # noqa: E402
 from velocity_amd import _lib as L  # noqa: E402
-from velocity_amd import driver as D  # noqa: E402
 from velocity_amd import synth  # noqa: E402
-from velocity_amd.common import worldPointsLicensePlate  # noqa: E402
 
 REPS, WARMUP = 30, 5
 
@@ -42,12 +40,12 @@ def timed(torch, fn):
 def main():
     torch = L.torch_cuda()
     f = synth.render_frame(W, H, synth.AffineMotion(W, H), 0, seed=0xC0FFEE, device="cuda").contiguous()
-    ws = L.Workspace(1, W, H, 4 + MC)
+    ws = L.Workspace(1, W, H, SETTINGS.cap)
     lib = ws.lib
     q = np.ascontiguousarray(plate_quad(0))
     K64 = L.host_K(synth.K_1080P)
-    plate = np.ascontiguousarray(np.asarray(worldPointsLicensePlate("Chile"), np.float64).reshape(12))
-    p, p3, vp, t0, R0, res0, n0 = (x[0] for x in D._frame0_buffers(torch, 1, 4 + MC))
+    plate = SETTINGS.plate_w
+    p, p3, vp, t0, R0, res0, n0 = (x[0] for x in SETTINGS.outputs(1))
     rois = (C.c_int * 8)()
     win, it, eps = SUBPIX
     corners = torch.zeros((MC, 2), dtype=torch.float32, device="cuda")

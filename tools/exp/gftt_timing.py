@@ -7,6 +7,7 @@ device synchronise, the settings alternate; median / min / max, and the mean cor
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/exp/gftt_timing.py --profile 256     (every setting once per rep)
 """
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -17,30 +18,23 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from frame0_batch_timing import BORDER, MC, SUBPIX, H, W, Setup, make_clips, stats  # noqa: E402
+from frame0_batch_timing import BORDER, MC, SETTINGS as HARRIS_MD0, Setup, make_clips, stats  # noqa: E402
 from velocity_amd import _lib as L  # noqa: E402
-from velocity_amd import driver as D  # noqa: E402
 
-SETTINGS = (("harris_md0", True, 0.0), ("shi_tomasi_md0", False, 0.0), ("shi_tomasi_md10", False, 10.0), ("shi_tomasi_md30", False, 30.0))
+SETTINGS = (("harris_md0", HARRIS_MD0),) + tuple((f"shi_tomasi_md{md}", dataclasses.replace(HARRIS_MD0, use_harris=False, min_distance=float(md))) for md in (0, 10, 30))
 
 
-def run(s, use_harris, md):
-    """frame 0 of every clip: one batch call per session + vh_session_init_dev per clip, as run_sequences does it."""
-    for g, mem in enumerate(s.members):
-        ses = s.sess[g]
-        bufs = s.bufs["b"][g]
-        p, p3, vp, t0, R0, res0, n0 = bufs
-        with s.torch.cuda.stream(s.streams[g]):
-            D._frame0_batch_call(ses.lib, ses.ws, [s.clips[b]["frames"][0] for b in mem], [s.clips[b]["q"] for b in mem], W, H, ses.K64, s.plate, BORDER, MC,
-                                 0.01, 5, 0.04, SUBPIX, bufs, use_harris, md)
-            for j, b in enumerate(mem):
-                L.check(ses.lib.vh_session_init_dev(ses.handle, j, L.dptr(s.clips[b]["frames"][0]), W, L.dptr(p[j]), L.dptr(p3[j]), L.dptr(vp[j]),
-                                                    L.dptr(t0[j]), L.dptr(res0[j]), L.dptr(n0[j]), 0.0, 0.0, L.stream_ptr()), "vh_session_init_dev")
+def run(s, settings):
+    """frame 0 of every clip: TrackerSession.admit per session (one batch call + vh_session_init_dev per clip), as run_sequences does it."""
+    for ses, hs, mem in zip(s.sess, s.streams, s.members):
+        with s.torch.cuda.stream(hs):
+            ses.admit([(j, s.clips[b]["frames"][0], s.clips[b]["q"], 0.0, 0.0) for j, b in enumerate(mem)], settings)
     s.torch.cuda.synchronize()
 
 
 def corners_kept(s):
-    return float(np.mean(np.concatenate([b[6].cpu().numpy() for b in s.bufs["b"]]) - 4))
+    """Mean corners per clip of the last admission: the streams' track counts without the 4 plate corners."""
+    return float(np.mean([ses._rd(ses.view(j).n_cur, 1, np.int32)[0] for ses in s.sess for j in range(ses.batch)]) - 4)
 
 
 def main():
@@ -55,26 +49,26 @@ def main():
     if a.profile:
         s = Setup(make_clips(a.profile, frames=1))
         for _ in range(a.warmup + a.reps):
-            for _, h, md in SETTINGS:
-                run(s, h, md)
+            for _, settings in SETTINGS:
+                run(s, settings)
         print(f"profiled {a.warmup + a.reps} passes of {len(SETTINGS)} settings at {a.profile} clips")
         return
     rows = []
     for n in a.sizes:
         s = Setup(make_clips(n, frames=1))
         for _ in range(a.warmup):
-            for _, h, md in SETTINGS:
-                run(s, h, md)
-        times = {name: [] for name, _, _ in SETTINGS}
+            for _, settings in SETTINGS:
+                run(s, settings)
+        times = {name: [] for name, _ in SETTINGS}
         kept = {}
         for _ in range(a.reps):
-            for name, h, md in SETTINGS:
+            for name, settings in SETTINGS:
                 t = time.perf_counter()
-                run(s, h, md)
+                run(s, settings)
                 times[name].append(time.perf_counter() - t)
                 kept[name] = corners_kept(s)
         row = dict(nclips=n, sessions=len(s.members))
-        for name, _, _ in SETTINGS:
+        for name, _ in SETTINGS:
             row[name] = dict(stats(times[name]), corners_per_clip=kept[name])
         row["st_md10_over_harris_md0"] = row["shi_tomasi_md10"]["median_ms"] / row["harris_md0"]["median_ms"]
         print(json.dumps(row), flush=True)

@@ -2,7 +2,10 @@
 state of `batch` video streams on the GPU and advances all of them one frame per step() through vh_session_step.
 Inputs are torch CUDA uint8 frames (dense, H x W); results (P, B, S, masks, points) are read back on demand."""
 import ctypes as C
+import dataclasses
+import functools
 import math
+import typing
 
 import numpy as np
 
@@ -33,15 +36,16 @@ class TrackerSession:
             mp = L.match_params(fallback_params)
             L.check(self.lib.vh_session_set_fallback(h, 1, C.byref(mp)), "vh_session_set_fallback")
         self._frames = torch.zeros(batch, dtype=torch.int64, device="cuda")  # device table of frame pointers
+        # the lifetime rule of a slot: its current frame (the im0 of its next step) and the device inputs of its initialisation (read by a kernel that may
+        # not have run yet) stay alive until the slot is initialised again -- by init_stream or by admit, which both replace the slot's entries here
         self._keep = [None] * batch
-        self._init_keep = []
+        self._init_keep = [None] * batch
 
     def init_stream(self, slot, frame0, p, p3, vp, t0, time0=0.0, frame_no=0.0, res0=0.0):
         """Frame-0 state (vidExample.py:116-131): points p [n0,2], world points p3 [n0,3], pose mask vp, plate pose t0.  numpy arrays or CUDA tensors
         (tensors of the right dtype are used in place: a stream can be re-initialised without touching the host)."""
         torch = self.torch
-        f0 = frame0 if isinstance(frame0, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frame0))
-        f0 = f0.cuda().contiguous()
+        f0 = _to_device([frame0])[0]
         assert f0.shape == (self.h, self.w) and f0.dtype == torch.uint8
 
         def dev(a, np_dtype, t_dtype):
@@ -52,8 +56,27 @@ class TrackerSession:
         t0 = np.ascontiguousarray(np.asarray(t0, np.float32).reshape(3))
         L.check(self.lib.vh_session_init(self.handle, slot, L.dptr(f0), self.w, L.dptr(pd), L.dptr(p3d), L.dptr(vpd), t0.ctypes.data_as(L.f32p),
                                          float(time0), float(frame_no), float(res0), L.stream_ptr()), "vh_session_init")
-        self._keep[slot] = f0
-        self._init_keep = [k for k in self._init_keep if k[0] != slot] + [(slot, pd, p3d, vpd)]
+        self._keep[slot], self._init_keep[slot] = f0, (pd, p3d, vpd)
+
+    def admit(self, entries, settings):
+        """THE admission (vidExample.py:105-131 for each clip): frame 0 of every entry computed and installed on the device, on the current stream.
+        entries = [(slot, frame0, q, time0, frame_no0), ...]: frame0 a dense CUDA uint8 [H, W] tensor, q the clicked plate corners [4, 2]; settings: a
+        Frame0Settings whose .cap is this session's track capacity.  ONE frame-0 batch call for all entries, in the given order, then one
+        vh_session_init_dev per entry, fed by the batch's device outputs (count included: nothing is read back).  The session keeps each slot's frame
+        and its rows of those outputs alive until the slot is initialised again.  Returns one Admitted per entry: the frame-0 facts a result needs and
+        the stream's state does not hold."""
+        assert settings.cap == self.n0, "the session's track capacity must be 4 + max_corners"
+        assert all(e[1].is_cuda and e[1].dtype == self.torch.uint8 and e[1].shape == (self.h, self.w) and e[1].is_contiguous() for e in entries)
+        bufs = settings.outputs(len(entries))
+        rois = _frame0_batch_call(self.ws, [e[1] for e in entries], [e[2] for e in entries], self.K64, settings, bufs)
+        out = []
+        for a, (slot, f0, _, time0, frame_no0) in enumerate(entries):
+            p, p3, vp, t0, R0, res0, n0 = rows = tuple(x[a:a + 1] for x in bufs)
+            L.check(self.lib.vh_session_init_dev(self.handle, slot, L.dptr(f0), self.w, L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
+                                                 float(time0), float(frame_no0), L.stream_ptr()), "vh_session_init_dev")
+            self._keep[slot], self._init_keep[slot] = f0, rows
+            out.append(Admitted(tuple(rois[8 * a:8 * a + 4]), tuple(rois[8 * a + 4:8 * a + 8]), R0[0], res0))
+        return out
 
     def set_frames(self, frames):
         """frames: list of `batch` CUDA uint8 [H,W] tensors (kept alive until the next call replaces them); a None entry is a stream that sits the step
@@ -355,6 +378,133 @@ def summary_lines(S, n, frame_numbers, seconds):
     return [a, b]
 
 
+@dataclasses.dataclass(frozen=True)
+class Frame0Settings:
+    """How frame 0 of a clip is initialised (vidExample.py:105-127): the plate, the ROI border around it, goodFeaturesToTrack's and cornerSubPix's
+    arguments.  The defaults are the reference's call; the drivers build one from their keywords and hand it down whole."""
+    plate: str = "Chile"
+    roi_border: tuple = (700, 500)
+    max_corners: int = 1000
+    quality: float = 0.01
+    block: int = 5
+    harris_k: float = 0.04
+    subpix: tuple = (5, 100, 0.001)
+    use_harris: bool = True
+    min_distance: float = 0.0
+
+    def __post_init__(self):
+        if not math.isfinite(float(self.min_distance)):
+            raise ValueError(f"min_distance must be finite, got {self.min_distance}")
+
+    @property
+    def cap(self):
+        """Track capacity of a session these settings fill: the 4 plate corners + max_corners."""
+        return 4 + int(self.max_corners)
+
+    @functools.cached_property
+    def plate_w(self):
+        """The plate's world points as the C ABI takes them: 12 contiguous float64."""
+        from .common import worldPointsLicensePlate
+
+        return np.ascontiguousarray(np.asarray(worldPointsLicensePlate(self.plate), np.float64).reshape(12))
+
+    @property
+    def reference_detector(self):
+        """The reference's detector (vidExample.py:110: Harris, minDistance 0), which keeps the entry point it always used."""
+        return bool(self.use_harris) and float(self.min_distance) == 0.0
+
+    def outputs(self, nb):
+        """Device outputs of a frame-0 batch call for nb clips: p, p3, vp, t, R, res, n."""
+        torch, cap = L.torch_cuda(), self.cap
+        layout = (((nb, cap, 2), torch.float32), ((nb, cap, 3), torch.float64), ((nb, cap), torch.uint8), ((nb, 3), torch.float32), ((nb, 9), torch.float64),
+                  ((nb,), torch.float64), ((nb,), torch.int32))
+        return tuple(torch.empty(shape, dtype=dtype, device="cuda") for shape, dtype in layout)
+
+
+class Admitted(typing.NamedTuple):
+    """What frame 0 of a clip leaves besides the stream's state: the ROIs (host ints) and the plate pose -- R0 [9] float64, res0 [1] float64: device
+    views out of TrackerSession.admit, host values (R0 [3, 3], res0 a float) into clip_result."""
+    boxa: tuple
+    boxb: tuple
+    R0: object
+    res0: object
+
+    def host(self):
+        """The device views read back (waits for the stream)."""
+        return self._replace(R0=self.R0.cpu().numpy(), res0=float(self.res0.item()))
+
+
+def _to_device(frames, non_blocking=False):
+    """uint8 gray frames (numpy arrays or torch tensors) -> dense CUDA tensors, uploaded on the current stream; CUDA tensors are used in place."""
+    torch = L.torch_cuda()
+    return [(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))).cuda(non_blocking=non_blocking).contiguous() for f in frames]
+
+
+def _frame0_batch_call(ws, frames0, qs, K64, settings, bufs):
+    """vh_frame0_init_batch (the reference's detector) or vh_frame0_init_batch2 (any other) on the current stream: frames0 = dense CUDA [H, W] frames of
+    one size, qs = their plate corners, bufs = settings.outputs(len(frames0)).  -> host list of nb x 8 ROIs (boxa, boxb)."""
+    s, lib, nb = settings, ws.lib, len(frames0)
+    H, W = frames0[0].shape
+    q = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 2) for x in qs]))
+    ptrs = (C.c_void_p * nb)(*[f.data_ptr() for f in frames0])
+    rois = (C.c_int * (8 * nb))()
+    win, it, eps = s.subpix
+    if s.reference_detector:
+        fn, name, detector = lib.vh_frame0_init_batch, "vh_frame0_init_batch", ()
+    else:
+        fn, name, detector = lib.vh_frame0_init_batch2, "vh_frame0_init_batch2", (1 if s.use_harris else 0, float(s.min_distance))
+    L.check(fn(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p), s.plate_w.ctypes.data_as(L.f64p),
+               int(s.roi_border[0]), int(s.roi_border[1]), int(s.max_corners), float(s.quality), int(s.block), float(s.harris_k), *detector, int(win), int(it),
+               float(eps), *[L.dptr(x) for x in bufs], rois, L.stream_ptr()), name)
+    return list(rois)
+
+
+def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
+                 use_harris=True, min_distance=0.0):
+    """Frame 0 of many clips at once (vidExample.py:105-127 for each): `frames` = the clips' first frames (numpy / torch uint8 [H, W] of one size, or one
+    [B, H, W] array), `qs` = their plate corners [4, 2].  One vh_frame0_init_batch launch sequence for all of them.  Returns one dict per clip with the keys
+    of the oracle's frame0: p [n, 2] (the 4 plate corners, then the refined corners), p3 [n, 3], vp [n] bool, t [3], R [3, 3], res, boxa, boxb.
+    use_harris=False: Shi-Tomasi (minimum eigenvalue) corners; min_distance >= 1: corners at least that far apart (vh_frame0_init_batch2)."""
+    settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
+    torch = L.torch_cuda()
+    dev = _to_device(frames)
+    H, W = dev[0].shape
+    assert all(d.shape == (H, W) and d.dtype == torch.uint8 for d in dev), "frames must be uint8 and share one size"
+    bufs = settings.outputs(len(dev))
+    rois = _frame0_batch_call(L.workspace(W, H), dev, qs, L.host_K(K), settings, bufs)
+    p, p3, vp, t0, R0, res0, n0 = (x.cpu().numpy() for x in bufs)
+    out = []
+    for b in range(len(dev)):
+        k = int(n0[b])
+        out.append(dict(p=p[b, :k].copy(), p3=p3[b, :k].copy(), vp=vp[b, :k].astype(bool), t=t0[b].copy(), R=R0[b].reshape(3, 3).copy(), res=float(res0[b]),
+                        boxa=tuple(rois[8 * b:8 * b + 4]), boxb=tuple(rois[8 * b + 4:8 * b + 8])))
+    return out
+
+
+def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=None):
+    """THE result of a clip, whichever driver ran it (a pure function: numpy in, fresh arrays out, no device).
+    st       the stream's state after the clip's last frame (TrackerSession.state / ExportedState.result).  Its session may have been sized for longer
+             clips and has room for 4 + max_corners tracks: the history is cut to the clip's n frames and to the k tracks frame 0 found (S[0, 2]:
+             k_sess_init writes the count there; rows beyond them never existed)
+    clip     dict(n, name, frame_numbers); f0: the clip's Admitted with host values
+    seconds  the wall time the `Processed ...` line reports; step_seconds: the mean time of a frame step, which rows 1.. of the procTime column carry
+             (row 0: 0) unless `proc` gives the column frame by frame (run_sequence's live table)
+    `lines` = the start line, TABLE_HEADER, one table_row per frame and the two summary_lines."""
+    n, k = clip["n"], int(st["S"][0, 2])
+    S = st["S"][:n].copy()
+    S[0, 1] = 0.0
+    S[1:, 1] = step_seconds
+    if proc is not None:
+        S[:, 1] = proc
+    B = st["B"][:n].copy()
+    lines = [f"Starting image processing on {clip['name']} ...", TABLE_HEADER] + [table_row(S[i]) for i in range(n)]  # vidExample.py:50
+    lines += summary_lines(S, n, clip["frame_numbers"], seconds)
+    return dict(S=S, B=B, P=st["P"][:, :k, :n].copy(), vg=st["vg"][:k].copy(), vp=st["vp"][:k].copy(), p=st["p"].copy(), p3=st["p3"][:k].copy(),
+                ids=st["ids"].copy(), n_tracks0=k, t0=B[0, 0:3].copy(), R0=np.array(f0.R0, np.float64).reshape(3, 3), res0=float(f0.res0), boxa=tuple(f0.boxa),
+                boxb=tuple(f0.boxb), klt_flags=st["klt_flags"], recoveries=recoveries, lines=lines, seconds=seconds, ms_per_frame=1e3 * step_seconds,
+                sessions=sessions)
+
+
 def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01,
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
                  out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
@@ -365,7 +515,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     q       float32 [4, 2]: the hand-clicked plate corners of frame 0 (the .mat file's `q`, vidExample.py:31-32)
     K       the camera's 3 x 3 intrinsic matrix, reference layout (images.py:148-151)
     fps / times / frame_numbers   B[i, 12] (seconds; `CAP_PROP_POS_MSEC / 1000` or the EXIF time) and B[i, 13] per frame: either `times` or `fps`
-    route   "session": frame 0 as a batch of one clip (vh_frame0_init_batch: Harris -> cornerSubPix -> plate pose -> image2world -> insidebbox, ONE device sequence) straight
+    route   "session": frame 0 as a batch of one clip (TrackerSession.admit: Harris -> cornerSubPix -> plate pose -> image2world -> insidebbox, ONE device sequence) straight
             into a device-resident TrackerSession -- nothing but the frames goes up and nothing but the printed rows comes down (the only route of the
             product; a host loop on the drop-in functions -- what INTEGRATION.md's import switch gives a maintainer -- lives in tools/dropin_loop.py as a
             measurement harness).
@@ -377,173 +527,52 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     out     line sink (default print); clock: time source for the procTime column / fps line (default time.perf_counter).
 
     Prints the reference's header, one 9-column row per frame (vidExample.py:165) and the `Speed = ... +/- ... km/h / Res = ...` summary (:177-178).
-    Returns dict(S, B, P, vg, vp, p, p3, lines, seconds, ms_per_frame, n_tracks0)."""
+    Returns clip_result's dict (sessions = 1)."""
     import time as _time
 
+    settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
+    if route != "session":
+        raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
     clock = clock or _time.perf_counter
+    emit = out or (lambda line: None)
     n = len(frames)
     assert n >= 2, "a clip needs at least two frames"
-    q = np.ascontiguousarray(np.asarray(q, np.float32).reshape(4, 2))
     if times is None:
         assert fps, "give `times` or `fps`"
-        times = [np.float32(k / fps) for k in range(n)]
+        times = [k / fps for k in range(n)]
     times = [np.float32(t) for t in times]
     frame_numbers = list(range(n)) if frame_numbers is None else list(frame_numbers)
-    lines = []
-
-    def emit(line):
-        lines.append(line)
-        if out is not None:
-            out(line)
-
     emit(f"Starting image processing on {name} ...")  # vidExample.py:50
     emit(TABLE_HEADER)
-    t_begin = clock()
-    if route == "session":
-        res = _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corners, quality, block, harris_k, subpix, msv_frame, lk_coarse,
-                           lk_fine, emit, clock, live, use_harris, min_distance, fallback, fallback_params)
-    else:
-        raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
-    seconds = clock() - t_begin
-    for line in summary_lines(res["S"], n, frame_numbers, seconds):
-        emit(line)
-    res.update(lines=lines, seconds=seconds, ms_per_frame=1e3 * res.pop("loop_seconds") / (n - 1))
-    return res
-
-
-def _plate_points(country):
-    from .common import worldPointsLicensePlate
-
-    return worldPointsLicensePlate(country)
-
-
-def _run_session(frames, q, K, times, frame_numbers, plate, roi_border, max_corners, quality, block, harris_k, subpix, msv_frame, lk_coarse, lk_fine,
-                 emit, clock, live, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
-    torch = L.torch_cuda()
-    tic = clock()
-    dev = [f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)) for f in frames]
-    dev = [f.cuda(non_blocking=True).contiguous() for f in dev]
+    t_begin = tic = clock()
+    dev = _to_device(frames, non_blocking=True)
     H, W = dev[0].shape
-    n, cap = len(dev), 4 + int(max_corners)
-    ses = TrackerSession(K, W, H, cap, nhist=n, batch=1, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback,
-                         fallback_params=fallback_params)
-    lib, ws = ses.lib, ses.ws
-    # frame 0 (vidExample.py:105-131): one device sequence; its outputs are the session's frame-0 state without touching the host
-    p = torch.empty((cap, 2), dtype=torch.float32, device="cuda")
-    p3 = torch.empty((cap, 3), dtype=torch.float64, device="cuda")
-    vp = torch.empty(cap, dtype=torch.uint8, device="cuda")
-    t0 = torch.empty(3, dtype=torch.float32, device="cuda")
-    R0 = torch.empty(9, dtype=torch.float64, device="cuda")
-    res0 = torch.empty(1, dtype=torch.float64, device="cuda")
-    n0 = torch.empty(1, dtype=torch.int32, device="cuda")
-    plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
-    rois = _frame0_batch_call(lib, ws, [dev[0]], [q], W, H, ses.K64, plate_w, roi_border, max_corners, quality, block, harris_k, subpix,
-                              (p, p3, vp, t0, R0, res0, n0), use_harris, min_distance)
-    L.check(lib.vh_session_init_dev(ses.handle, 0, L.dptr(dev[0]), W, L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
-                                    float(times[0]), float(frame_numbers[0]), L.stream_ptr()), "vh_session_init_dev")
-    ses._keep[0] = dev[0]
-    ses._init_keep.append((0, p, p3, vp, t0, res0, n0))
+    ses = _SessionSet(1, 1, max_corners).create(K, W, H, settings, n, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback,
+                                                 fallback_params=fallback_params)[0]
+    f0 = ses.admit([(0, dev[0], q, times[0], frame_numbers[0])], settings)[0]
     view = ses.view(0)
-    rows = np.zeros((n, 9), np.float32)
-
-    def row(i):
-        r = ses._rd(C.c_void_p(view.S + 4 * 9 * i), 9, np.float32)  # one 36-byte read-back (synchronises, like the reference's print)
-        return r
-
     proc = np.zeros(n)
+
+    def row(i):  # the live table: one 36-byte read-back (synchronises, like the reference's print)
+        r = ses._rd(C.c_void_p(view.S + 4 * 9 * i), 9, np.float32)
+        proc[i] = r[1] = clock() - tic
+        emit(table_row(r))
+
     if live:
-        rows[0] = row(0)
-        proc[0] = clock() - tic
-        rows[0, 1] = proc[0]
-        emit(table_row(rows[0]))
+        row(0)
     t_loop = clock()
     for i in range(1, n):
         tic = clock()
         ses.step([dev[i]], time_s=float(times[i]), frame_no=float(frame_numbers[i]))
         if live:
-            rows[i] = row(i)
-            proc[i] = clock() - tic
-            rows[i, 1] = proc[i]
-            emit(table_row(rows[i]))
-    torch.cuda.synchronize()
-    loop_seconds = clock() - t_loop
-    st = ses.state(0)
-    n_tr = int(n0.item())
-    if not live:  # the whole clip ran first: every row carries the mean time per frame
-        rows = st["S"].copy()
-        rows[0, 1] = 0.0
-        rows[1:, 1] = loop_seconds / (n - 1)
-        for i in range(n):
-            emit(table_row(rows[i]))
-    S = st["S"].copy()
-    S[:, 1] = rows[:, 1]
-    k = n_tr  # rows beyond the tracks found at frame 0 never existed (the session was sized for 4 + max_corners)
-    return dict(S=S, B=st["B"], P=st["P"][:, :k, :], vg=st["vg"][:k], vp=st["vp"][:k], p=st["p"], p3=st["p3"][:k], ids=st["ids"], n_tracks0=n_tr,
-                t0=t0.cpu().numpy(), R0=R0.cpu().numpy().reshape(3, 3), res0=float(res0.item()), boxa=tuple(rois[0:4]), boxb=tuple(rois[4:8]),
-                loop_seconds=loop_seconds, klt_flags=st["klt_flags"], recoveries=ses.recoveries()[0])
-
-
-def _frame0_buffers(torch, nb, cap):
-    """Device outputs of vh_frame0_init_batch for nb clips: p, p3, vp, t, R, res, n."""
-    return (torch.empty((nb, cap, 2), dtype=torch.float32, device="cuda"), torch.empty((nb, cap, 3), dtype=torch.float64, device="cuda"),
-            torch.empty((nb, cap), dtype=torch.uint8, device="cuda"), torch.empty((nb, 3), dtype=torch.float32, device="cuda"),
-            torch.empty((nb, 9), dtype=torch.float64, device="cuda"), torch.empty(nb, dtype=torch.float64, device="cuda"),
-            torch.empty(nb, dtype=torch.int32, device="cuda"))
-
-
-def _default_detector(use_harris, min_distance):
-    """The reference's detector (vidExample.py:110: Harris, minDistance 0), which keeps the entry points it always used."""
-    if not math.isfinite(float(min_distance)):
-        raise ValueError(f"min_distance must be finite, got {min_distance}")
-    return bool(use_harris) and float(min_distance) == 0.0
-
-
-def _frame0_batch_call(lib, ws, frames0, qs, W, H, K64, plate_w, roi_border, max_corners, quality, block, harris_k, subpix, bufs, use_harris=True,
-                       min_distance=0.0):
-    """vh_frame0_init_batch (the reference's detector) or vh_frame0_init_batch2 (any other) on the current stream: frames0 = dense CUDA [H, W] frames,
-    qs = their plate corners.  -> host list of nb x 8 ROIs (boxa, boxb)."""
-    nb = len(frames0)
-    q = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 2) for x in qs]))
-    ptrs = (C.c_void_p * nb)(*[f.data_ptr() for f in frames0])
-    rois = (C.c_int * (8 * nb))()
-    win, it, eps = subpix
-    p, p3, vp, t0, R0, res0, n0 = bufs
-    if _default_detector(use_harris, min_distance):
-        L.check(lib.vh_frame0_init_batch(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p),
-                                         plate_w.ctypes.data_as(L.f64p), int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block),
-                                         float(harris_k), int(win), int(it), float(eps), L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(R0),
-                                         L.dptr(res0), L.dptr(n0), rois, L.stream_ptr()), "vh_frame0_init_batch")
-    else:
-        L.check(lib.vh_frame0_init_batch2(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p),
-                                          plate_w.ctypes.data_as(L.f64p), int(roi_border[0]), int(roi_border[1]), int(max_corners), float(quality), int(block),
-                                          float(harris_k), 1 if use_harris else 0, float(min_distance), int(win), int(it), float(eps), L.dptr(p), L.dptr(p3),
-                                          L.dptr(vp), L.dptr(t0), L.dptr(R0), L.dptr(res0), L.dptr(n0), rois, L.stream_ptr()), "vh_frame0_init_batch2")
-    return list(rois)
-
-
-def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
-                 use_harris=True, min_distance=0.0):
-    """Frame 0 of many clips at once (vidExample.py:105-127 for each): `frames` = the clips' first frames (numpy / torch uint8 [H, W] of one size, or one
-    [B, H, W] array), `qs` = their plate corners [4, 2].  One vh_frame0_init_batch launch sequence for all of them.  Returns one dict per clip with the keys
-    of the oracle's frame0: p [n, 2] (the 4 plate corners, then the refined corners), p3 [n, 3], vp [n] bool, t [3], R [3, 3], res, boxa, boxb.
-    use_harris=False: Shi-Tomasi (minimum eigenvalue) corners; min_distance >= 1: corners at least that far apart (vh_frame0_init_batch2)."""
-    torch = L.torch_cuda()
-    dev = [(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))).cuda().contiguous() for f in frames]
-    H, W = dev[0].shape
-    assert all(d.shape == (H, W) and d.dtype == torch.uint8 for d in dev), "frames must be uint8 and share one size"
-    nb, cap = len(dev), 4 + int(max_corners)
-    ws = L.workspace(W, H)
-    bufs = _frame0_buffers(torch, nb, cap)
-    plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
-    rois = _frame0_batch_call(ws.lib, ws, dev, qs, W, H, L.host_K(K), plate_w, roi_border, max_corners, quality, block, harris_k, subpix, bufs, use_harris,
-                              min_distance)
-    p, p3, vp, t0, R0, res0, n0 = (x.cpu().numpy() for x in bufs)
-    out = []
-    for b in range(nb):
-        k = int(n0[b])
-        out.append(dict(p=p[b, :k].copy(), p3=p3[b, :k].copy(), vp=vp[b, :k].astype(bool), t=t0[b].copy(), R=R0[b].reshape(3, 3).copy(), res=float(res0[b]),
-                        boxa=tuple(rois[8 * b:8 * b + 4]), boxb=tuple(rois[8 * b + 4:8 * b + 8])))
-    return out
+            row(i)
+    ses.torch.cuda.synchronize()
+    step_seconds = (clock() - t_loop) / (n - 1)
+    st, recoveries, f0 = ses.state(0), ses.recoveries()[0], f0.host()
+    res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None)
+    for line in res["lines"][-2 if live else 2:]:  # (not live: the whole clip ran first, and every row carries the mean time per frame)
+        emit(line)
+    return res
 
 
 def session_groups(streams, tracks=2000):
@@ -578,101 +607,92 @@ def session_streams(n):
     return [torch.cuda.current_stream()] + pool[: max(n - 1, 0)]
 
 
+def _slot_split(streams, sessions):
+    """Slots per session: `streams` slots in contiguous blocks over `sessions` sessions."""
+    owner = [b * sessions // streams for b in range(streams)]
+    return [owner.count(g) for g in range(sessions)]
+
+
+class _SessionSet:
+    """`streams` resident streams as TrackerSessions, each on its own HIP stream of the pool: `sessions` of them (0 = auto, session_groups(streams, tracks)),
+    never more than streams.  sizes[g]: the slots of session g; first[g]: the index of its slot 0 among all the streams (contiguous blocks);
+    hip_streams[g]: the stream everything of session g is issued on (a session's context serves one HIP stream)."""
+
+    def __init__(self, streams, sessions, tracks):
+        G = int(sessions) if sessions and sessions > 0 else session_groups(streams, tracks)
+        self.sizes = _slot_split(streams, max(1, min(G, streams)))
+        self.first = [sum(self.sizes[:g]) for g in range(len(self.sizes))]
+        self.hip_streams = session_streams(len(self.sizes))
+        self.sess = []
+
+    def create(self, K, W, H, settings, nhist, **session_kw):
+        """The sessions, once the frame size is known: W x H frames, room for settings.cap tracks and nhist frames per stream."""
+        torch = L.torch_cuda()
+        for hs, size in zip(self.hip_streams, self.sizes):
+            with torch.cuda.stream(hs):
+                self.sess.append(TrackerSession(K, W, H, settings.cap, nhist=nhist, batch=size, **session_kw))
+        return self.sess
+
+
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
                   msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name]) of ONE frame size and
     length; every clip is a stream of a device-resident TrackerSession, so a frame step is one launch sequence for all the clips of a session
     (vh_session_step_v: each stream has its own clock).  `sessions`: the clips are split into this many sessions, each on its own HIP stream (0 = auto,
     session_groups(len(clips)): their one-workgroup-per-stream stages overlap the others' LK launches); results do not depend on it.  Frame 0 of the clips
-    of a session runs as ONE vh_frame0_init_batch call on the device, its outputs feed vh_session_init_dev directly; nothing is read back before the last
-    frame.  use_harris / min_distance: the frame-0 detector, as in run_sequence.  fallback: the recovery by feature matching, as in run_sequence (the failed streams
-    of a session share one vh_match_affine_batch call per step).  Returns one
-    result dict per clip (the keys of run_sequence; `lines` = that clip's table and summary, printed through `out` if given), each equal to what
-    run_sequence returns for the clip alone."""
+    of a session is ONE TrackerSession.admit (one frame-0 batch call on the device, its outputs feed vh_session_init_dev directly); nothing is read back
+    before the last frame.  use_harris / min_distance: the frame-0 detector, as in run_sequence.  fallback: the recovery by feature matching, as in
+    run_sequence (the failed streams of a session share one vh_match_affine_batch call per step).  Returns one result dict per clip (clip_result's;
+    `lines` = that clip's table and summary, printed through `out` if given), each equal to what run_sequence returns for the clip alone."""
     import time as _time
 
+    settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
     nclip = len(clips)
     assert nclip >= 1
     n = len(clips[0]["frames"])
-    dev = [[(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))).cuda().contiguous() for f in c["frames"]] for c in clips]
+    dev = [_to_device(c["frames"]) for c in clips]
     H, W = dev[0][0].shape
     assert all(len(d) == n and d[0].shape == (H, W) for d in dev), "clips must share frame size and length"
-    cap = 4 + int(max_corners)
-    G = int(sessions) if sessions and sessions > 0 else session_groups(nclip, max_corners)
-    G = max(1, min(G, nclip))
-    owner = [b * G // nclip for b in range(nclip)]                    # clip -> session (contiguous blocks)
-    members = [[b for b in range(nclip) if owner[b] == g] for g in range(G)]
-    slot = {b: members[owner[b]].index(b) for b in range(nclip)}
-    hip_streams = session_streams(G)
-    main = hip_streams[0]
-    for st_ in hip_streams[1:]:
-        st_.wait_stream(main)  # the frame uploads above ran on the current stream
-    sess = []
-    for g in range(G):
-        with torch.cuda.stream(hip_streams[g]):  # (a session's context serves one HIP stream: everything of session g is issued on stream g)
-            sess.append(TrackerSession(K, W, H, cap, nhist=n, batch=len(members[g]), lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame,
-                                       fallback=fallback, fallback_params=fallback_params))
-    plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
+    group = _SessionSet(nclip, sessions, max_corners)
+    for hs in group.hip_streams[1:]:
+        hs.wait_stream(group.hip_streams[0])  # the frame uploads above ran on the current stream
+    sess = group.create(K, W, H, settings, n, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params)
+    members = [list(range(a, a + size)) for a, size in zip(group.first, group.sizes)]  # session -> its clips, in slot order
     times = np.stack([np.asarray(c["times"], np.float32) for c in clips])  # [clip, frame]
     fnos = np.stack([np.asarray(c.get("frame_numbers", np.arange(n)), np.float32) for c in clips])
-    keep = [None] * nclip
     t_begin = _time.perf_counter()
-    f0_events = []
-    for g in range(G):
-        ses, mem = sess[g], members[g]
-        with torch.cuda.stream(hip_streams[g]):
+    f0, f0_events = [], []
+    for ses, hs, mem in zip(sess, group.hip_streams, members):
+        with torch.cuda.stream(hs):
             f0_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
             f0_events[-1][0].record()
-            # frame 0 of every clip of the session: ONE vh_frame0_init_batch launch sequence into rows [slot] of these tensors
-            bufs = _frame0_buffers(torch, len(mem), cap)
-            rois = _frame0_batch_call(ses.lib, ses.ws, [dev[b][0] for b in mem], [clips[b]["q"] for b in mem], W, H, ses.K64, plate_w, roi_border, max_corners,
-                                      quality, block, harris_k, subpix, bufs, use_harris, min_distance)
-            p, p3, vp, t0, R0, res0, n0 = bufs
-            for j, b in enumerate(mem):
-                L.check(ses.lib.vh_session_init_dev(ses.handle, j, L.dptr(dev[b][0]), W, L.dptr(p[j]), L.dptr(p3[j]), L.dptr(vp[j]), L.dptr(t0[j]), L.dptr(res0[j]),
-                                                    L.dptr(n0[j]), float(times[b, 0]), float(fnos[b, 0]), L.stream_ptr()), "vh_session_init_dev")
-                ses._keep[j] = dev[b][0]
-                keep[b] = (tuple(x[j] for x in bufs), tuple(rois[8 * j:8 * j + 8]))
+            f0 += ses.admit([(j, dev[b][0], clips[b]["q"], times[b, 0], fnos[b, 0]) for j, b in enumerate(mem)], settings)
             f0_events[-1][1].record()
     t_loop = _time.perf_counter()
     for i in range(1, n):
-        for g in range(G):
-            with torch.cuda.stream(hip_streams[g]):
-                sess[g].step([dev[b][i] for b in members[g]], time_s=times[members[g], i], frame_no=fnos[members[g], i])
+        for ses, hs, mem in zip(sess, group.hip_streams, members):
+            with torch.cuda.stream(hs):
+                ses.step([dev[b][i] for b in mem], time_s=times[mem, i], frame_no=fnos[mem, i])
     torch.cuda.synchronize()
-    loop_seconds = _time.perf_counter() - t_loop
+    step_seconds = (_time.perf_counter() - t_loop) / (n - 1)  # every row carries the mean time of a frame step (of ALL clips)
     seconds = _time.perf_counter() - t_begin
     # what tools/exp/queue_timing.py reads: device time of the frame-0 block of every session (events on its stream), to set beside run_queue's
-    run_sequences.last_stats = dict(sessions=G, steps=n - 1, admission_ms=float(sum(a.elapsed_time(b) for a, b in f0_events)), admissions=G)
+    run_sequences.last_stats = dict(sessions=len(sess), steps=n - 1, admission_ms=float(sum(a.elapsed_time(b) for a, b in f0_events)), admissions=len(sess))
     results = []
-    for b, c in enumerate(clips):
-        st = sess[owner[b]].state(slot[b])
-        (p, p3, vp, t0, R0, res0, n0), rois = keep[b]
-        k = int(n0.item())
-        S = st["S"].copy()
-        S[0, 1] = 0.0
-        S[1:, 1] = loop_seconds / (n - 1)  # every row carries the mean time of a frame step (of ALL clips)
-        lines = [f"Starting image processing on {c.get('name', f'clip {b}')} ...", TABLE_HEADER] + [table_row(S[i]) for i in range(n)]
-        lines += summary_lines(S, n, c.get("frame_numbers", list(range(n))), seconds)
-        if out is not None:
-            for ln in lines:
-                out(ln)
-        results.append(dict(S=S, B=st["B"], P=st["P"][:, :k, :], vg=st["vg"][:k], vp=st["vp"][:k], p=st["p"], p3=st["p3"][:k], ids=st["ids"], n_tracks0=k,
-                            t0=t0.cpu().numpy(), R0=R0.cpu().numpy().reshape(3, 3), res0=float(res0.item()), boxa=rois[0:4], boxb=rois[4:8],
-                            klt_flags=st["klt_flags"], recoveries=sess[owner[b]].recoveries()[slot[b]], lines=lines, seconds=seconds, ms_per_frame=1e3 * loop_seconds / (n - 1), sessions=G))
+    for ses, mem in zip(sess, members):
+        for j, b in enumerate(mem):
+            meta = dict(n=n, name=clips[b].get("name", f"clip {b}"), frame_numbers=clips[b].get("frame_numbers", list(range(n))))
+            results.append(clip_result(ses.state(j), meta, f0[b].host(), seconds, step_seconds, len(sess), ses.recoveries()[j]))
+            if out is not None:
+                for ln in results[-1]["lines"]:
+                    out(ln)
     return results
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
 # a queue of clips of any length on a fixed set of resident streams
 # ----------------------------------------------------------------------------------------------------------------------------------
-def _slot_split(streams, sessions):
-    """Slots per session: `streams` slots in contiguous blocks over `sessions` sessions (the rule of run_sequences)."""
-    owner = [b * sessions // streams for b in range(streams)]
-    return [owner.count(g) for g in range(sessions)]
-
-
 def _queue_steps(next_length, sizes):
     """The schedule of run_queue, one global step at a time.  `next_length()` hands out the length (frames, >= 2) of the next clip of the FIFO, or None when
     the queue is empty; it is called only when a slot is free, in (session, slot) order.  Yields per step dict(admit, frames, done):
@@ -727,15 +747,17 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
     max_frames   the sessions' history length: no clip may be longer (ValueError when it is admitted); required unless `clips` is a list.
     sessions     the slots are split over this many TrackerSessions, each on its own HIP stream (0 = auto, session_groups(streams)); results do not
                  depend on it.
-    The schedule is queue_plan's: one shared FIFO; at every global step each free slot takes the next clip, all admissions of a session are ONE frame-0
-    batch call (+ one vh_session_init_dev per slot) on the session's stream, then every session issues ONE step in which its empty slots sit out
-    (vh_session_step_some); a clip that has just had its last frame is exported (TrackerSession.export: one launch, one copy) and its slot is free.
+    The schedule is queue_plan's: one shared FIFO; at every global step each free slot takes the next clip, all admissions of a session are ONE
+    TrackerSession.admit (one frame-0 batch call + one vh_session_init_dev per slot) on the session's stream, then every session issues ONE step in which
+    its empty slots sit out (vh_session_step_some); a clip that has just had its last frame is exported (TrackerSession.export: one launch, one copy) and
+    its slot is free.
     With fallback=False the loop never waits for the device except for a result whose pinned buffer is needed again (a ring of 2 x streams) and at
     the end of the run; frames given as CUDA tensors are used in place, host frames are uploaded on a side stream.
-    on_result(index, result) is called as results land (polled at every step, never waited for); returns the results in input order.  A result has
-    the keys of run_sequences' results, P / B / S cut to the clip's own length and the track rows to n_tracks0; `lines` = the clip's table and summary."""
+    on_result(index, result) is called as results land (polled at every step, never waited for); returns the results in input order.  A result is
+    clip_result's: P / B / S cut to the clip's own length and the track rows to n_tracks0; `lines` = the clip's table and summary."""
     import time as _time
 
+    settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
     if max_frames is None:
         if not isinstance(clips, (list, tuple)):
@@ -743,13 +765,9 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
         max_frames = max(len(c["frames"]) for c in clips)
     nhist, streams = int(max_frames), int(streams)
     assert streams >= 1 and nhist >= 2
-    cap = 4 + int(max_corners)
-    G = int(sessions) if sessions and sessions > 0 else session_groups(streams, max_corners)
-    G = max(1, min(G, streams))
-    sizes = _slot_split(streams, G)
-    hip_streams = session_streams(G)
-    main, upload = hip_streams[0], _upload_stream()
-    plate_w = np.ascontiguousarray(np.asarray(_plate_points(plate), np.float64).reshape(12))
+    group = _SessionSet(streams, sessions, max_corners)
+    G, sess = len(group.sizes), group.sess
+    main, upload = group.hip_streams[0], _upload_stream()
     source = iter(clips)
     pulled = {}          # clip index -> the clip as its slot uses it (dropped when the clip is done)
     size = [None]
@@ -765,7 +783,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
         if n >= 2:
             host = [f for f in c["frames"] if not (isinstance(f, torch.Tensor) and f.is_cuda)]
             with torch.cuda.stream(upload if host else main):  # (host frames: an upload that waits for nothing the sessions have queued)
-                dev = [(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))).cuda(non_blocking=True).contiguous() for f in c["frames"]]
+                dev = _to_device(c["frames"], non_blocking=True)
             size[0] = size[0] or tuple(dev[0].shape)
             assert all(d.shape == size[0] and d.dtype == torch.uint8 for d in dev), "clips must share one frame size"
             pulled[k] = dict(dev=dev, uploaded=bool(host), q=c["q"], times=np.asarray(c["times"], np.float32),
@@ -775,78 +793,58 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
         return n
 
     next_length.count = 0
-    sess, rec_bytes = [], 0
-    ring, ring_i = [], 0   # pinned records + frame-0 extras, 2 x streams of them; entry: [record, extras, pending job or None]
-    pending, results, t_admit = [], {}, []
+    ring, ring_i = [], 0   # pinned records + frame-0 extras, 2 x streams of them; entry: [record, extras, the job whose result it holds or None]
+    pending, results, t_admit = [], {}, []   # pending: the ring entries that hold a job, oldest first
     t_begin = _time.perf_counter()
 
-    def deliver(job):
-        st = job["handle"].result()
-        c, n = job["clip"], job["clip"]["n"]
-        x = job["extras"].numpy().copy()
-        k = int(st["S"][0, 2])  # the tracks found at frame 0 (k_sess_init writes the count there); rows beyond them never existed
-        S = st["S"][:n].copy()
-        seconds = _time.perf_counter() - job["t_admit"]
-        S[0, 1] = 0.0
-        S[1:, 1] = seconds / (n - 1)  # every row carries the mean time of the clip's frame steps in the queue
-        lines = [f"Starting image processing on {c['name']} ...", TABLE_HEADER] + [table_row(S[i]) for i in range(n)]
-        lines += summary_lines(S, n, c["frame_numbers"], seconds)
+    def deliver(entry):
+        handle, index, clip, f0, t0 = entry[2]
+        st = handle.result()
+        x = entry[1].numpy().copy()
+        seconds = _time.perf_counter() - t0  # the clip's time in the queue: every row carries the mean over its frame steps
+        res = results[index] = clip_result(st, clip, f0._replace(R0=x[0:9], res0=x[9]), seconds, seconds / (clip["n"] - 1), G, handle.recoveries)
+        entry[2] = None
+        pending[:] = [e for e in pending if e is not entry]
         if out is not None:
-            for ln in lines:
+            for ln in res["lines"]:
                 out(ln)
-        rois = job["rois"]
-        res = dict(S=S, B=st["B"][:n].copy(), P=st["P"][:, :k, :n].copy(), vg=st["vg"][:k], vp=st["vp"][:k], p=st["p"], p3=st["p3"][:k], ids=st["ids"],
-                   n_tracks0=k, t0=st["B"][0, 0:3].copy(), R0=x[0:9].reshape(3, 3), res0=float(x[9]), boxa=rois[0:4], boxb=rois[4:8], klt_flags=st["klt_flags"],
-                   recoveries=job["handle"].recoveries, lines=lines, seconds=seconds, ms_per_frame=1e3 * seconds / (n - 1), sessions=G)
-        results[job["index"]] = res
-        job["entry"][2] = None
-        pending.remove(job)
         if on_result is not None:
-            on_result(job["index"], res)
+            on_result(index, res)
 
-    held = [[None] * n for n in sizes]  # per slot: what the clip's result needs besides the record (frame-0 outputs, ROIs, admission time)
+    def poll():
+        for entry in [e for e in pending if e[2][0].done()]:
+            deliver(entry)
+
+    held = [[None] * n for n in group.sizes]  # per slot: (the resident clip's Admitted, its admission time)
     idle_slots = steps = 0
-    for step in _queue_steps(next_length, sizes):
-        for job in [j for j in pending if j["handle"].done()]:
-            deliver(job)
+    for step in _queue_steps(next_length, group.sizes):
+        poll()
         if not sess:  # the first clips have been pulled: the frame size is known
             H, W = size[0]
-            for g in range(G):
-                with torch.cuda.stream(hip_streams[g]):  # (a session's context serves one HIP stream: everything of session g is issued on stream g)
-                    ses = TrackerSession(K, W, H, cap, nhist=nhist, batch=sizes[g], lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame,
-                                         fallback=fallback, fallback_params=fallback_params)
-                    # the frame-0 scratch for a full house, so that no later admission grows it (growing waits for the stream)
-                    L.check(ses.lib.vh_init_reserve_batch(ses.ws.handle, sizes[g], W, H, L.stream_ptr()), "vh_init_reserve_batch")
-                    sess.append(ses)
+            group.create(K, W, H, settings, nhist, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params)
+            for ses, hs in zip(sess, group.hip_streams):
+                with torch.cuda.stream(hs):  # the frame-0 scratch for a full house, so that no later admission grows it (growing waits for the stream)
+                    L.check(ses.lib.vh_init_reserve_batch(ses.ws.handle, ses.batch, W, H, L.stream_ptr()), "vh_init_reserve_batch")
             rec_bytes = sess[0].record_layout().bytes
             ring = [[torch.empty(rec_bytes, dtype=torch.uint8).pin_memory(), torch.empty(10, dtype=torch.float64).pin_memory(), None] for _ in range(2 * streams)]
-        for g in range(G):
-            ses, hs = sess[g], hip_streams[g]
-            adm = [(j, k) for gg, j, k in step["admit"] if gg == g]
+        for g, (ses, hs) in enumerate(zip(sess, group.hip_streams)):
+            adm = [(j, pulled[k]) for gg, j, k in step["admit"] if gg == g]
             with torch.cuda.stream(hs):
                 if adm:
                     if hs != main:
                         hs.wait_stream(main)   # frames the caller produced on the current stream
-                    if any(pulled[k]["uploaded"] for _, k in adm):
+                    if any(c["uploaded"] for _, c in adm):
                         hs.wait_stream(upload)
-                    for _, k in adm:
-                        if pulled[k]["uploaded"] or hs != main:  # frames allocated on another stream than the one that reads them
-                            for f in pulled[k]["dev"]:
+                    for _, c in adm:
+                        if c["uploaded"] or hs != main:  # frames allocated on another stream than the one that reads them
+                            for f in c["dev"]:
                                 f.record_stream(hs)
                     ev0 = torch.cuda.Event(enable_timing=True)
                     ev1 = torch.cuda.Event(enable_timing=True)
                     ev0.record()
-                    # frame 0 of every clip this session admits now: ONE batch call into rows [a] of these tensors, then one init per slot
-                    bufs = _frame0_buffers(torch, len(adm), cap)
-                    rois = _frame0_batch_call(ses.lib, ses.ws, [pulled[k]["dev"][0] for _, k in adm], [pulled[k]["q"] for _, k in adm], W, H, ses.K64, plate_w,
-                                              roi_border, max_corners, quality, block, harris_k, subpix, bufs, use_harris, min_distance)
-                    p, p3, vp, t0, R0, res0, n0 = bufs
-                    for a, (j, k) in enumerate(adm):
-                        c = pulled[k]
-                        L.check(ses.lib.vh_session_init_dev(ses.handle, j, L.dptr(c["dev"][0]), W, L.dptr(p[a]), L.dptr(p3[a]), L.dptr(vp[a]), L.dptr(t0[a]),
-                                                            L.dptr(res0[a]), L.dptr(n0[a]), float(c["times"][0]), float(c["fnos"][0]), L.stream_ptr()),
-                                "vh_session_init_dev")
-                        held[g][j] = dict(bufs=bufs, row=a, rois=tuple(rois[8 * a:8 * a + 8]), t_admit=_time.perf_counter())
+                    f0s = ses.admit([(j, c["dev"][0], c["q"], c["times"][0], c["fnos"][0]) for j, c in adm], settings)
+                    for (j, _), f0 in zip(adm, f0s):
+                        held[g][j] = (f0, _time.perf_counter())
                     ev1.record()
                     t_admit.append((ev0, ev1))
                 # ONE step of the session: a pointer per slot (null: the slot sits the step out), its clock, and the host's copy of who is active
@@ -867,29 +865,26 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
                     entry = ring[ring_i % len(ring)]
                     ring_i += 1
                     if entry[2] is not None:
-                        deliver(entry[2])  # the one wait of the loop: this pinned buffer still holds a result nobody has taken
-                    hd = held[g][j]
+                        deliver(entry)  # the one wait of the loop: this pinned buffer still holds a result nobody has taken
+                    f0, t0 = held[g][j]
                     handle = ses.export(j, out=entry[0])
                     # (the plate pose of frame 0 is no part of the stream's state: 80 bytes beside the record)
-                    entry[1].copy_(torch.cat([hd["bufs"][4][hd["row"]], hd["bufs"][5][hd["row"]:hd["row"] + 1]]), non_blocking=True)
+                    entry[1].copy_(torch.cat([f0.R0, f0.res0]), non_blocking=True)
                     handle.event.record()
-                    job = dict(handle=handle, extras=entry[1], entry=entry, index=k, clip={q: v for q, v in pulled.pop(k).items() if q != "dev"},
-                               rois=hd["rois"], t_admit=hd["t_admit"])
-                    entry[2] = job
-                    pending.append(job)
+                    c = pulled.pop(k)
+                    entry[2] = (handle, k, dict(n=c["n"], name=c["name"], frame_numbers=c["frame_numbers"]), f0, t0)
+                    pending.append(entry)
                     held[g][j] = None
         steps += 1
-        for job in [j for j in pending if j["handle"].done()]:
-            deliver(job)
-    for hs in hip_streams:
+        poll()
+    for hs in group.hip_streams:
         hs.synchronize()
-    for job in list(pending):
-        deliver(job)
+    for entry in list(pending):
+        deliver(entry)
     seconds = _time.perf_counter() - t_begin
-    n_clips = next_length.count
     run_queue.last_stats = dict(steps=steps, sessions=G, mean_idle_slots=idle_slots / max(steps, 1), seconds=seconds,
                                 admission_ms=float(sum(a.elapsed_time(b) for a, b in t_admit)), admissions=len(t_admit))
-    return [results[k] for k in range(n_clips)]
+    return [results[k] for k in range(next_length.count)]
 
 
 _UPLOAD_STREAMS = {}
