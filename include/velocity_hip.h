@@ -454,6 +454,10 @@ VH_API void vh_debug_force_generic_lk(int on);
 /* test hook (vh_version >= 105): launch slots one workgroup of the one-wavefront LDS-staged LK kernel (k_lk3<.., 1, ..>, routes 3 and 5) solves one after the
  * other -- 0: chosen by load (1 below 49 152 tracks in flight, 2 from there, 4 from 98 304), n > 0: n (clamped to 8).  Bit-identical results. */
 VH_API void vh_debug_lk3_tpw(int n);
+/* test hook (vh_version >= 111): residency of the one-wavefront 51x51 LDS-staged kernel (k_lk3<51, 1, 4>, route 5) as the runtime sees it, at the dynamic
+ * LDS size its launches pass -- out[0]: workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor), out[1]: registers per lane, out[2]: scratch bytes
+ * per lane, out[3]: LDS bytes per workgroup (hipFuncGetAttributes + the dynamic size).  Launches no kernel. */
+VH_API int vh_debug_lk3_residency(int out[4]);
 
 /* test hook: estimateAffine2D stand-in -- 1: always the three-kernel path (hypotheses spread over the chip), 2: the fused
  * one-workgroup-per-stream kernel whenever the problem fits it (latency path), 0: default routing by batch size.  Bit-identical results. */

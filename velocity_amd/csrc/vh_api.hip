@@ -30,7 +30,7 @@ int vh_fail(int code, const char* msg)
 }
 #define VH_LAUNCH_CHECK() VH_CHECK(hipGetLastError())
 
-extern "C" VH_API int vh_version(void) { return 110; }
+extern "C" VH_API int vh_version(void) { return 111; }
 void vh_lk_force_generic(int on);
 extern "C" VH_API void vh_debug_force_generic_lk(int on) { vh_lk_force_generic(on); }
 void vh_ransac_force_path(int mode);
@@ -424,6 +424,14 @@ extern "C" VH_API int vh_profile_lk_tpw(vh_ctx* c, int* tpw_host)
 
 void vh_lk3_set_tpw(int n);
 extern "C" VH_API void vh_debug_lk3_tpw(int n) { vh_lk3_set_tpw(n); }
+
+int vh_lk3_residency(int out[4]);
+extern "C" VH_API int vh_debug_lk3_residency(int out[4])
+{
+    if (!out) return vh_fail(-1, "vh_debug_lk3_residency: bad arguments");
+    const int rc = vh_lk3_residency(out);
+    return rc ? vh_fail(rc, "vh_debug_lk3_residency: the runtime refused the occupancy / attribute query") : 0;
+}
 
 extern "C" VH_API int vh_profile_lk_routes(vh_ctx* c, int* routes_host, char* names_host)
 {

@@ -778,12 +778,17 @@ struct LK3 {
     static constexpr int OFF_PJ = OFF_PI + (PI_ROWS + PAD_ROWS) * PI_PITCH + 8;
     static constexpr int OFF_RED = ((OFF_PJ + (RJ + PAD_ROWS) * PJ_PITCH + 16 + 15) / 16) * 16;
     static constexpr int MAX_TPW = 8;                           // launch slots one workgroup may solve one after the other (k_lk3)
-    static constexpr int OFF_RES = OFF_RED + 2 * NW * 4 * 8;   // their result records (8 dwords each), written out after the last one
+    static constexpr int REC_DW = 6;                            // dwords of a result record: point, fx, fy, status, err, fbe
+    static constexpr int OFF_RES = OFF_RED + 2 * NW * 4 * 8;   // their result records, written out after the last one
     // The lane map: what a thread's place in the workgroup alone decides -- its strip column(s) and first row(s), and with them its addresses in the
     // two staged regions and the v_perm selectors that pack (and mask) its gradient pairs.  Slots fall into selector classes: SPLIT 0 = [0, KA),
     // 1 = [KA, K-1), 2 = K-1; otherwise 0 = the slots that always lie inside the window, 1 = the last PAD_ROWS slots of a run (below the window in the
-    // last run(s)).  k_lk3 writes the map to LDS once per workgroup (OFF_TAB), LK3Level reads it back per level: three 16-byte groups per thread,
-    // group-major (group g of thread t at OFF_TAB + 16 * (g * T + t): consecutive lanes read consecutive 16 bytes)
+    // last run(s)).  k_lk3 writes the map to LDS once per workgroup (OFF_TAB), LK3Level reads every word back where it is first needed (LDS reads take no
+    // VALU slot, and a word read late is not held through the set-up's register peak).  Eleven arrays of one dword per thread (word i of thread t at
+    // OFF_TAB + 4 * (i * T + t)): every read goes through the ONE address 4 * t with the array in the offset field, two words are one ds_read2st64_b32,
+    // and reads that are far apart in the code cannot be merged into one early 16-byte read.  TAB_COL: the lane's byte offsets in the patch (set-up),
+    // TAB_LC: in the search region (iterations), TAB_SEL + 2 c: the selectors of class c (set-up, from the first slot of the class), TAB_JR: columns
+    // and rows as numbers (border set-up and err pass)
     struct Lane {
         int jA, rA, jB, rB;
         bool on;
@@ -851,15 +856,18 @@ struct LK3 {
         for (int t = 0; t < 64; t++) m |= (unsigned long long)lane(t).on << t;
         return m;
     }
-    static constexpr int OFF_TAB = ((OFF_RES + MAX_TPW * 32 + 15) / 16) * 16;
-    static constexpr int LDS_BYTES = OFF_TAB + 3 * 16 * T;
-    static_assert(NW != 1 || WIN != 51 || LDS_BYTES <= 160 * 1024 / 12, "k_lk3<51, 1, 4>: 12 workgroups per CU must fit in LDS");
+    static constexpr int OFF_TAB = ((OFF_RES + MAX_TPW * 4 * REC_DW + 15) / 16) * 16;
+    static constexpr int TAB_COL = 0, TAB_LC = 2, TAB_SEL = 4, TAB_JR = 10, TAB_WORDS = 11;
+    static constexpr int LDS_BYTES = OFF_TAB + 4 * TAB_WORDS * T;
+    static_assert(NW != 1 || WIN != 51 || LDS_BYTES <= 160 * 1024 / 16, "k_lk3<51, 1, 4>: 16 workgroups per CU (4 wavefronts per SIMD) must fit in LDS");
 };
 
 typedef const uint2 __attribute__((address_space(1)))* gptr_u32x2;
 typedef int __attribute__((address_space(3)))* lds_i32;
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef u32x4_t __attribute__((address_space(3)))* lds_u32x4;
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned __attribute__((address_space(3)))* lds_u32;
 
 // A lane predicate that is a FIXED set of lanes, as a 64-bit literal: the mask is a scalar constant (s_mov) where a compare of the thread index is a vector
 // instruction whose result hipcc hoists out of the track loop and, short of scalar registers, parks in a VGPR lane (v_writelane) and fetches again
@@ -950,8 +958,7 @@ __device__ __forceinline__ void block_sum_wide(const int* part, long long* tot, 
 
 template <int WIN, int NW, int M>
 struct LK3Level {  // the level functor of k_lk3 (see lk_track); phase: which half of the double-buffered block reduction comes next
-    int max_count;
-    double eps2;
+    const LKJob& job;  // max_count and eps2 are read where the iterations start, not held across the direction and level loops
     char* smem;
     int tid;
     int& phase;
@@ -991,30 +998,25 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
 
     const bool inside_I = ipx >= 1 && ipy >= 1 && ipx + WIN + 1 <= I.w - 1 && ipy + WIN + 1 <= I.h - 1;
     // this lane's strips: slots 0..KA-1 = column jA, window rows rA + k; slots KA..K-1 = column jB, rows rB + k (one segment unless C::SPLIT).
-    // The map depends on the thread alone (LK3::Lane): k_lk3 wrote it to LDS before the first track, and it comes back here with three 16-byte LDS loads
-    // per level, which take no VALU slot and keep ~50 loop-invariant registers out of the track loop.
-    // selA / selB / selC: the v_perm selectors that pack (and mask) the gradient pairs of the slots of class 0 / 1 / 2 (LK3::slot_cls)
+    // The map depends on the thread alone (LK3::Lane): k_lk3 wrote it to LDS before the first track, and every word of it comes back where it is first
+    // needed (LDS loads take no VALU slot): ~50 loop-invariant registers stay out of the track loop, and no word is held through the set-up's register
+    // peak unless the set-up uses it -- what brought the one-wavefront 51 x 51 kernel under 128 VGPRs (LK3_FINE_WAVES).
+    // cls_sel(c): the v_perm selectors that pack (and mask) the gradient pairs of the slots of class c (LK3::slot_cls)
     static_assert(C::classes_hold(), "a selector class mixes slots inside and below the window");
-    const lds_u32x4 tab = (lds_u32x4)(smem + C::OFF_TAB) + tid;  // (an explicit LDS pointer, as the result records of k_lk3)
-    const u32x4_t tg0 = tab[0], tg1 = tab[C::T], tg2 = tab[2 * C::T];
-    const unsigned selA01 = tg1.x, selA23 = tg1.y, selB01 = tg1.z, selB23 = tg1.w, selC01 = tg2.x, selC23 = tg2.y;
-    // (column and row as numbers: the border set-up and the err pass only)
-    const int jA = (int)(tg2.z & 255u), rA = (int)((tg2.z >> 8) & 255u), jB = (int)((tg2.z >> 16) & 255u), rB = (int)(tg2.z >> 24);
+    // (explicit LDS pointers, as the result records of k_lk3)
+    const lds_u32 tab = (lds_u32)(smem + C::OFF_TAB) + tid;
+    const auto tab_pair = [&](int i) { return u32x2_t{tab[i * C::T], tab[(i + 1) * C::T]}; };
+    const auto cls_sel = [&](int c) { return tab_pair(C::TAB_SEL + 2 * c); };
+    // (column and row as numbers: the border set-up and the err pass only, each reads the word itself)
+    const auto lane_jr = [&]() { return tab[C::TAB_JR * C::T]; };
     constexpr unsigned long long ON = C::on_mask(), LIVE[3] = {C::live_mask(0), C::live_mask(1), C::live_mask(C::NCLS - 1)};
     const bool lane_on = C::LANES == C::T ? true : (C::T == 64 ? lane_in(ON) : tid < C::LANES);
     // (k is a compile-time constant wherever these are used: the strip loops are fully unrolled)
-    const auto slot_col = [&](int k) { return k < C::KA ? jA : jB; };
-    const auto slot_row = [&](int k) { return (k < C::KA ? rA : rB) + k; };
-    const auto slot_sel = [&](int k, unsigned& s01, unsigned& s23) {
-        const int c = C::slot_cls(k);
-        s01 = c == 0 ? selA01 : (c == 1 ? selB01 : selC01);
-        s23 = c == 0 ? selA23 : (c == 1 ? selB23 : selC23);
-    };
+    const auto slot_col = [&](unsigned jr, int k) { return (int)((k < C::KA ? jr : jr >> 16) & 255u); };
+    const auto slot_row = [&](unsigned jr, int k) { return (int)((k < C::KA ? jr >> 8 : jr >> 24) & 255u) + k; };
     const auto slot_live = [&](int k) {  // the slot holds a strip of the window
         if (C::T == 64) return lane_in(LIVE[C::slot_cls(k)]);
-        unsigned a, b;
-        slot_sel(k, a, b);
-        return a != C::SEL_NONE;
+        return cls_sel(C::slot_cls(k)).x != C::SEL_NONE;
     };
     constexpr int slot_base = 0, slot_stride = 1;
     constexpr int PIP = C::PI_PITCH >> 2;
@@ -1022,8 +1024,9 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
     if (lane_on && inside_I) {
         // interior: rolling V rows (see strip_setup_linear): patch rows y .. y+3 feed strip y; one new row per strip
         const unsigned wt = pack16(w0.w00, w0.w01), wb = pack16(w0.w10, w0.w11);
-        const unsigned* colA = reinterpret_cast<const unsigned*>(smem + tg0.x);  // pI + jA + rA * PIP
-        const unsigned* colB = reinterpret_cast<const unsigned*>(smem + tg0.y);  // pI + jB + rB * PIP
+        const u32x2_t col = tab_pair(C::TAB_COL);
+        const unsigned* colA = reinterpret_cast<const unsigned*>(smem + col.x);  // pI + jA + rA * PIP
+        const unsigned* colB = reinterpret_cast<const unsigned*>(smem + col.y);  // pI + jB + rB * PIP
         const auto patch_row = [&](int k, int dr) { return (k < C::KA ? colA : colB) + (k + dr) * PIP; };  // patch row slot_row(k) + dr, this lane's 8 bytes
         unsigned prB[6];
         int H0[4], H1[4], G0[4], G1[4], Vm[4];  // of V rows y, y+1 (Vm = the middle row's sample columns, for the template value)
@@ -1048,10 +1051,13 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
             const unsigned* rn = patch_row(0, 3);
             nlo = rn[0]; nhi = rn[1];
         }
+        // the selectors of a class are read at the class's first slot: one pair of registers serves all classes
+        u32x2_t sel = cls_sel(C::slot_cls(0));  // (four wavefronts per track: every slot is of class 1)
 #pragma unroll
         for (int k = 0; k < C::K; k++) {
             {   // no branch per strip: see LK3 (rows past the patch read the padding / the next buffer: harmless garbage, masked by the selector)
                 const unsigned clo = nlo, chi = nhi;
+                if (k > 0 && C::slot_cls(k) != C::slot_cls(k - 1)) sel = cls_sel(C::slot_cls(k));
                 if (k + 1 < C::K) {
                     const unsigned* rn = patch_row(k + 1, 3);
                     nlo = rn[0]; nhi = rn[1];
@@ -1061,9 +1067,7 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
                 setup_row_pairs(clo, chi, prN);
                 setup_v_row(prB, prN, wt, wb, V2);
                 setup_hg_row(V2, H2, G2, k + 2);
-                unsigned s01, s23;
-                slot_sel(k, s01, s23);
-                setup_from_hg(H0, H1, H2, G0, G2, Vm, s01, s23, tI, tX, tY, slot_base + k * slot_stride, part[0], part[1], part[2]);
+                setup_from_hg(H0, H1, H2, G0, G2, Vm, sel.x, sel.y, tI, tX, tY, slot_base + k * slot_stride, part[0], part[1], part[2]);
                 cI[0] = dot2(tI[k].y, tX[k].y, dot2(tI[k].x, tX[k].x, cI[0]));
                 cI[1] = dot2(tI[k].y, tY[k].y, dot2(tI[k].x, tY[k].x, cI[1]));
 #pragma unroll
@@ -1074,9 +1078,10 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
             }
         }
     } else if (lane_on) {
+        const unsigned jr = lane_jr();
 #pragma unroll
         for (int k = 0; k < C::K; k++) {
-            const int y = slot_row(k), j = slot_col(k);
+            const int y = slot_row(jr, k), j = slot_col(jr, k);
             if (!slot_live(k)) {  // slots without a strip are zeros (the iterations read every slot)
                 const uint2 z = make_uint2(0u, 0u);
                 tI[slot_base + k * slot_stride] = z; tX[slot_base + k * slot_stride] = z; tY[slot_base + k * slot_stride] = z;
@@ -1107,7 +1112,8 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
     // compiler, as the iterations need them (below).  An `asm volatile` must never do that job: it counts as a possible store to any memory, and every load
     // of the pyramid descriptors behind it turns from a scalar load into a per-lane global load (round 5: +17 vector loads, -17 scalar loads and +48 VALU
     // instructions per track, +25 % wait cycles, +4-5 % kernel time -- what made every earlier form of this change slower than the code it shortened)
-    const unsigned lcA = tg0.z, lcB = tg0.w;
+    const u32x2_t lc = tab_pair(C::TAB_LC);
+    const unsigned lcA = lc.x, lcB = lc.y;
 
     // packed byte pairs of window row y (strip column j) of the staged search region at window origin (inx, iny)
     // The strip starts at byte `off` of the staged row: its 5 bytes lie inside the two dwords at off >> 2, and the byte pair (c, c+1) is ONE
@@ -1129,6 +1135,8 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
     };
 
     float pdx = 0.f, pdy = 0.f;
+    const int max_count = job.max_count;
+    const double eps2 = job.eps2;
     for (int it = 0; it < max_count; it++) {
         const int inx = vh_floor(nx), iny = vh_floor(ny);
         if (lk_outside(inx, iny, WIN, J)) {
@@ -1193,15 +1201,18 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
         float fx, fy;
         int inx, iny;
         if (!lk_final_origin(nxo, nyo, half, WIN, J, fx, fy, inx, iny)) { status = 0; return; }
-        if (!want_err) return;  // err is discarded by the caller (KLT.py:83 `pa, v, _`): only the bounds rule matters
+        // err is discarded by the caller (KLT.py:83 `pa, v, _`): only the bounds rule matters.  (want_err says which pass this is; whether the job asks for err
+        // is read here, where it matters, not carried through the track as one more scalar)
+        if (!want_err || !job.err_out) return;
         if (!region_holds(inx, iny)) restage(inx, iny);
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
         int se[1] = {0};
         if (lane_on) {
+            const unsigned jr = lane_jr();
 #pragma unroll
             for (int k = 0; k < C::K; k++) {
                 if (slot_live(k)) {
-                    const int y = slot_row(k), j = slot_col(k), cnt = min(4, WIN - 4 * j);
+                    const int y = slot_row(jr, k), j = slot_col(jr, k), cnt = min(4, WIN - 4 * j);
                     unsigned top[4], bot[4], p01, p23;
                     region_row_pairs(inx, iny, j, y, top);
                     region_row_pairs(inx, iny, j, y + 1, bot);
@@ -1232,8 +1243,15 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
 
 // (forcing 5 or 6 workgroups per CU through the second launch bound spills and measured 3-8 % slower; a 128-VGPR cap
 // + a 3-pixel search margin to fit 7 workgroups of the 2-wave variant per CU: 11 spilled registers, 5 % slower: not used)
+// Wavefronts per SIMD the one-wavefront 51 x 51 kernel is compiled for: it needs 127 VGPRs and 10 208 bytes of LDS, so FOUR workgroups per SIMD (16 per CU)
+// are resident without a spilled register (tests/test_gpu_lk3_residency.py asks the runtime).  A/B on one box against the same code held at three
+// wavefronts: fine launch 1741 -> 1646 us, the headline +1.6 % (profiles/lk3_residency/ab.json).  (-DLK3_FINE_WAVES=3: experiments only.)
+#ifndef LK3_FINE_WAVES
+#define LK3_FINE_WAVES 4
+#endif
+#define LK3_WAVES (NW == 1 ? (WIN == 51 ? LK3_FINE_WAVES : 3) : 4)
 template <int WIN, int NW, int M>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 1 ? 3 : 4))) void k_lk3(const void* job_tab, size_t tab_stride, unsigned grp, unsigned tpw)
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LK3_WAVES))) void k_lk3(const void* job_tab, size_t tab_stride, unsigned grp, unsigned tpw)
 {
     unsigned blk_x0, blk_y0;
     lk_block_xy<true>(blk_x0, blk_y0, grp);
@@ -1246,11 +1264,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 1
         using C = LK3<WIN, NW, M>;
         constexpr int PIP = C::PI_PITCH >> 2, PJP = C::PJ_PITCH >> 2;
         const typename C::Lane l = C::lane((int)threadIdx.x);
-        const lds_u32x4 tab = (lds_u32x4)(smem + C::OFF_TAB) + threadIdx.x;
-        tab[0] = u32x4_t{(unsigned)(C::OFF_PI + 4 * (l.jA + l.rA * PIP)), (unsigned)(C::OFF_PI + 4 * (l.jB + l.rB * PIP)),
-                         (unsigned)(C::OFF_PJ + 4 * (l.rA * PJP + l.jA)), (unsigned)(C::OFF_PJ + 4 * (l.rB * PJP + l.jB))};
-        tab[C::T] = u32x4_t{l.s01[0], l.s23[0], l.s01[1], l.s23[1]};
-        tab[2 * C::T] = u32x4_t{l.s01[2], l.s23[2], (unsigned)(l.jA | l.rA << 8 | l.jB << 16 | l.rB << 24), 0u};
+        const lds_u32 tab = (lds_u32)(smem + C::OFF_TAB) + threadIdx.x;
+        tab[(C::TAB_COL + 0) * C::T] = (unsigned)(C::OFF_PI + 4 * (l.jA + l.rA * PIP));
+        tab[(C::TAB_COL + 1) * C::T] = (unsigned)(C::OFF_PI + 4 * (l.jB + l.rB * PIP));
+        tab[(C::TAB_LC + 0) * C::T] = (unsigned)(C::OFF_PJ + 4 * (l.rA * PJP + l.jA));
+        tab[(C::TAB_LC + 1) * C::T] = (unsigned)(C::OFF_PJ + 4 * (l.rB * PJP + l.jB));
+#pragma unroll
+        for (int c = 0; c < 3; c++) { tab[(C::TAB_SEL + 2 * c) * C::T] = l.s01[c]; tab[(C::TAB_SEL + 2 * c + 1) * C::T] = l.s23[c]; }
+        tab[C::TAB_JR * C::T] = (unsigned)(l.jA | l.rA << 8 | l.jB << 16 | l.rB << 24);
         __syncthreads();
     }
     // A workgroup solves `tpw` consecutive launch slots one after the other (tracks that are neighbours in the launch order): fewer, longer-lived
@@ -1264,15 +1285,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 1
         int pt;
         float px, py;
         if (!lk_slot_start<true>(job, (int)(blk_x * tpw + ti), pt, px, py)) break;
-        const float fbt = job.fbt;
-        LK3Level<WIN, NW, M> lf{job.max_count, job.eps2, smem, (int)threadIdx.x, phase, 0, 0};
+        LK3Level<WIN, NW, M> lf{job, smem, (int)threadIdx.x, phase, 0, 0};
 
         // forward pass, then (fbt >= 0) the backward pass from its result: ONE copy of the track code in a loop over the direction -- two inlined copies
         // doubled the kernel and recomputed the per-lane mapping / masks of LK3Level in each
         float fx = 0.f, fy = 0.f, err = 0.f, bx = 0.f, by = 0.f;
         int st = 0, st2 = 0;
-        const int ndir = fbt >= 0.f ? 2 : 1;
-        const bool want_err = job.err_out != nullptr;
+        const int ndir = job.fbt >= 0.f ? 2 : 1;
     #pragma unroll 1
         for (int dir = 0; dir < ndir; dir++) {
             if (dir == 1 && !st && !job.fbe_out) break;  // forward status 0 (block uniform): the backward pass cannot change v or p (see lk_solve)
@@ -1280,16 +1299,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 1
             const PyrDesc& PB = dir ? job.I : job.J;
             float ox, oy, e;
             int s;
-            lk_track(PA, PB, dir ? fx : px, dir ? fy : py, ox, oy, s, e, want_err && dir == 0, lf);
+            lk_track(PA, PB, dir ? fx : px, dir ? fy : py, ox, oy, s, e, dir == 0, lf);
             if (dir == 0) { fx = ox; fy = oy; st = s; err = e; }
             else { bx = ox; by = oy; st2 = s; }
         }
+        const float fbt = job.fbt;  // (read again: one scalar load instead of a register held across both passes)
         const float fbe = fbt >= 0.f ? lk_fb_gate(px, py, bx, by, fbt, st2, st) : 0.f;
         // the track's results wait in LDS: a global store inside this loop would make every descriptor load of the NEXT track a possibly-clobbered load,
         // i.e. a vector load instead of a scalar one (the same effect as the volatile asm of DESIGN.md section 9)
         if (NW == 1 ? lane_in(1ull) : threadIdx.x == 0) {
             // (an explicit LDS pointer: through a generic one hipcc counts these stores as possible writes to the job descriptors too)
-            lds_i32 rec = (lds_i32)(smem + LK3<WIN, NW, M>::OFF_RES) + 8 * ti;
+            lds_i32 rec = (lds_i32)(smem + LK3<WIN, NW, M>::OFF_RES) + LK3<WIN, NW, M>::REC_DW * ti;
             rec[0] = pt; rec[1] = __float_as_int(fx); rec[2] = __float_as_int(fy); rec[3] = st != 0;
             rec[4] = __float_as_int(err); rec[5] = __float_as_int(fbe);
         }
@@ -1302,7 +1322,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 1
     }
     const LKJob& job = lk_job_row(job_tab, tab_stride, blk_y);
     if (threadIdx.x < ndone) {
-        const int* rec = reinterpret_cast<const int*>(smem + LK3<WIN, NW, M>::OFF_RES) + 8 * threadIdx.x;
+        const int* rec = reinterpret_cast<const int*>(smem + LK3<WIN, NW, M>::OFF_RES) + LK3<WIN, NW, M>::REC_DW * threadIdx.x;
         lk_store_track(job, rec[0], __int_as_float(rec[1]), __int_as_float(rec[2]), rec[3], __int_as_float(rec[4]), __int_as_float(rec[5]));
     }
     if (threadIdx.x == 0 && ndone) lk_add_stats(job, blk_x, tot_iter, tot_setup);
@@ -1908,12 +1928,35 @@ static int launch_lkq(const void* job_tab, size_t tab_stride, int batch, int max
 static std::atomic<int> g_lk3_tpw{getenv("VH_LK3_TPW") ? atoi(getenv("VH_LK3_TPW")) : 0};
 void vh_lk3_set_tpw(int n) { g_lk3_tpw.store(n < 0 ? 0 : n, std::memory_order_relaxed); }
 
+// dynamic LDS of a k_lk3 launch
 template <int WIN, int NW, int M>
-static int launch_lk3(const void* job_tab, size_t tab_stride, int batch, int max_n, hipStream_t s, int* tpw_out)
+static int lk3_lds_bytes()
 {
     // VH_LK_LDS_PAD (experiments only): extra dynamic LDS per workgroup = fewer resident wavefronts per SIMD (the occupancy sensitivity behind DESIGN.md section 9)
     static const int pad = [] { const char* e = getenv("VH_LK_LDS_PAD"); return e ? atoi(e) : 0; }();
-    const int lds = LK3<WIN, NW, M>::LDS_BYTES + pad;
+    return LK3<WIN, NW, M>::LDS_BYTES + pad;
+}
+
+// test hook (vh_debug_lk3_residency): what the runtime makes of k_lk3<51, 1, 4> at the dynamic LDS size launch_lk3 passes -- workgroups per CU, registers,
+// scratch bytes per lane, LDS bytes per workgroup.  Launches nothing.
+int vh_lk3_residency(int out[4])
+{
+    const void* fn = reinterpret_cast<const void*>(k_lk3<51, 1, 4>);
+    const int lds = lk3_lds_bytes<51, 1, 4>();
+    int blocks = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 64, (size_t)lds);
+    if (e != hipSuccess) return (int)e;
+    hipFuncAttributes a;
+    e = hipFuncGetAttributes(&a, fn);
+    if (e != hipSuccess) return (int)e;
+    out[0] = blocks; out[1] = a.numRegs; out[2] = (int)a.localSizeBytes; out[3] = (int)a.sharedSizeBytes + lds;
+    return 0;
+}
+
+template <int WIN, int NW, int M>
+static int launch_lk3(const void* job_tab, size_t tab_stride, int batch, int max_n, hipStream_t s, int* tpw_out)
+{
+    const int lds = lk3_lds_bytes<WIN, NW, M>();
     static const unsigned grp = getenv("VH_LK3_G") ? (unsigned)atoi(getenv("VH_LK3_G")) : 16u;  // (environment: experiments only)
     // Launch slots per workgroup (one-wavefront kernel): a 51 x 51 track keeps a workgroup for ~22 us, and starting one (dispatch, LDS allocation, the block
     // remap, the first descriptor loads) is not free: 4 consecutive slots per workgroup measured 3620 -> 3520 us per launch at 512 000 tracks (2: 3580,
