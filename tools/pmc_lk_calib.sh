@@ -3,11 +3,15 @@
 # a least-squares fit of   wave instructions per launch = A x template set-ups + B x Newton iterations   against the kernel's own counters (the bench
 # line prints them), and a check run (the roll scene) that states the model's error.  Run on the GPU box; writes gpurun_out/lk_valu_model.json
 # (copy to profiles/r03_lk_valu_model.json).  Usage: bash tools/pmc_lk_calib.sh [streams]
+# VH_LIB (velocity_amd/_lib.py) selects another build of the library, e.g. the parent's for a before / after pair.
+# Every profiled run has its own time limit (PMC_TIMEOUT seconds, default 240) and the script stops at the first run that fails: nothing more is started on
+# a GPU that a run has just faulted or hung.
 S=${1:-256}
 R=/root/repo; OUT=$R/gpurun_out/pmc_calib; rm -rf $OUT $R/gpurun_out/lk_valu_model.json; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 run() {  # tag, extra bench flags
-  rocprofv3 --kernel-trace --kernel-include-regex "k_lk3|k_lk_o|k_lk_q" --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/$1 -- \
-    python $R/bench.py --streams $S --groups 1 --steps 4 --warmup 2 --cpu-seconds 0 --no-ba --no-extras --min-seconds 0 --detail $OUT/$1.json --verify-frames 0 $2 > $OUT/$1.log 2>&1
+  timeout -k 10 ${PMC_TIMEOUT:-240} rocprofv3 --kernel-trace --kernel-include-regex "k_lk3|k_lk_o|k_lk_q" --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/$1 -- \
+    python $R/bench.py --streams $S --groups 1 --steps 4 --warmup 2 --cpu-seconds 0 --no-ba --no-extras --min-seconds 0 --detail $OUT/$1.json --verify-frames 0 $2 > $OUT/$1.log 2>&1 \
+    || { echo "pmc_lk_calib: run $1 failed: stopping"; tail -5 $OUT/$1.log; exit 1; }
 }
 run default ""
 run cap1 "--fine-max-count 1"
@@ -15,7 +19,7 @@ run cap3 "--fine-max-count 3"
 run roll "--scene roll"
 run ccap1 "--coarse-max-count 1"
 run ccap2 "--coarse-max-count 2"
-python - <<PY
+python - <<PY || exit 1
 import csv, glob, json
 import numpy as np
 pts, cpts = {}, {}

@@ -1362,16 +1362,85 @@ __device__ __forceinline__ unsigned row_pair(const unsigned* a, int c)
          : q == 2 ? __builtin_amdgcn_perm(0u, a[w], 0x0c030c02u)
                   : __builtin_amdgcn_perm(a[w + 1], a[w], 0x0c040c03u);
 }
+// The interior paths keep the dwords a lane loaded as they are -- `sh` bytes in front of the pixel, sh = byte phase of the address -- and fold the
+// phase into the v_perm that builds a byte pair anyway: pair (c, c+1) is bytes (c & 3) + sh and (c & 3) + sh + 1 <= 7 of the two neighbouring dwords
+// (c >> 2, (c >> 2) + 1).  The selectors are per lane, four per loaded block of rows (one for every c & 3), where aligning the words to the pixel
+// first cost a v_alignbyte per word and row.
+struct PairSel {
+    unsigned q[4];
+};
+__device__ __forceinline__ PairSel pair_selectors(unsigned sh)
+{
+    PairSel s;
+    s.q[0] = 0x0c010c00u + sh * 0x00010001u;
+#pragma unroll
+    for (int k = 1; k < 4; k++) s.q[k] = s.q[0] + (unsigned)k * 0x00010001u;
+    return s;
+}
+__device__ __forceinline__ unsigned row_pair(const unsigned* d, const PairSel& s, int c) { return __builtin_amdgcn_perm(d[(c >> 2) + 1], d[c >> 2], s.q[c & 3]); }
+
+typedef unsigned __attribute__((aligned(1))) u32_unaligned;
+typedef const u32_unaligned __attribute__((address_space(1)))* gptr_u32_unaligned;
+// ROWS consecutive rows of image im from pixel (gx, gy): NWORDS + 1 dwords per row, d[rr][i] = bytes 4i - sh .. 4i - sh + 3 counted from the pixel;
+// returns sh (0..3), ONE phase for all the rows.  NWORDS = dwords the pairs read counted from the pixel: the bytes touched are a subset of what
+// load_row_words<NWORDS> touches.
+// fast: scalar base + 32-bit lane offset (the form of stage_region; the base is moved to the corner of the border ring, so the offset of a window that
+// reaches into the ring stays positive), one 32-bit add per further row.  Rows a multiple of 4 bytes apart -- every level the library builds -- are
+// aligned dword loads.  Any other pitch (level 0 of a caller's image) keeps the phase of the first row: the further rows are then dword loads at an
+// unaligned address, which the global memory path serves, and they stay within 3 bytes in front of the pixel like the aligned ones (lk_block_inside).
+// !fast: REFLECT_101 byte loads packed at phase 0, addressed from the same scalar base (a second base pointer live in the Newton loops is one more
+// scalar pair for hipcc to park in a VGPR lane).  Offsets are 32-bit and rows and pitch go through a 24-bit multiply: a level is smaller than 4 GiB,
+// as in stage_region.
+template <int NWORDS, int ROWS>
+__device__ __forceinline__ unsigned load_rows_words(const ImgDesc& im, int gx, int gy, bool fast, unsigned (*d)[NWORDS + 1])
+{
+    unsigned sh = 0;
+    const uint8_t* corner = im.p - (ptrdiff_t)im.pad * (im.stride + 1);
+    const unsigned bsh = (unsigned)(reinterpret_cast<uintptr_t>(corner) & 3);
+    const uint8_t* bp = corner - bsh;                               // dword aligned, wave uniform
+    const unsigned org = (unsigned)(im.pad * (im.stride + 1)) + bsh;  // pixel (0, 0) from bp
+    if (fast) {
+        const unsigned off0 = (unsigned)(__mul24(gy, im.stride) + gx) + org;
+        sh = off0 & 3u;
+        const unsigned aoff = off0 & ~3u;
+#pragma unroll
+        for (int rr = 0; rr < ROWS; rr++) {
+            gptr_u32_unaligned ap = (gptr_u32_unaligned)(bp + (aoff + (unsigned)rr * (unsigned)im.stride));
+#pragma unroll
+            for (int i = 0; i <= NWORDS; i++) d[rr][i] = ap[i];
+        }
+    } else {
+#pragma unroll
+        for (int rr = 0; rr < ROWS; rr++) {
+            const uint8_t* row = bp + (org + (unsigned)vh_reflect101_near(gy + rr, im.h) * (unsigned)im.stride);
+            // every row computes its own column indices (the empty asm hides that they are the same): kept from row to row, the 4 NWORDS of them cost
+            // k_lk_o 20 VGPRs, and with them scratch at four wavefronts per SIMD
+            int gxr = gx;
+            if (rr > 0) asm("; row %1" : "+v"(gxr) : "n"(rr));
+            // all column indices first (branch free), then all byte loads: one memory round trip per row
+            unsigned b[4 * NWORDS];
+#pragma unroll
+            for (int k = 0; k < 4 * NWORDS; k++) b[k] = row[vh_reflect101_near(gxr + k, im.w)];
+#pragma unroll
+            for (int i = 0; i < NWORDS; i++) d[rr][i] = b[4 * i] | (b[4 * i + 1] << 8) | (b[4 * i + 2] << 16) | (b[4 * i + 3] << 24);
+            d[rr][NWORDS] = 0;
+        }
+    }
+    return sh;
+}
+
 // bilinear x32 samples of row r's NS strips at (x0, y0 + r) of image im: lane r holds row y0 + r, the row below comes from lane r + 1
-template <int NS>
+template <int NS, int WIN>
 __device__ __forceinline__ void lkq_sample_row(const ImgDesc& im, int x0, int y0, int r, bool fast, unsigned wt, unsigned wb, unsigned* p01, unsigned* p23)
 {
-    unsigned top[NS + 1];
-    load_row_words<NS + 1>(im, x0, y0 + r, fast, top);
+    static_assert(WIN <= 4 * NS, "pairs up to (WIN - 1, WIN): NS dwords from the pixel");
+    unsigned top[1][NS + 1];
+    const PairSel sel = pair_selectors(load_rows_words<NS, 1>(im, x0, y0 + r, fast, top));
     int v[4 * NS];
 #pragma unroll
     for (int c = 0; c < 4 * NS; c++) {
-        const unsigned pr = row_pair(top, c);
+        if (c >= WIN) { v[c] = 0; continue; }  // columns >= WIN are never used (zero template gradients there, masked in the err sum): not computed
+        const unsigned pr = row_pair(top[0], sel, c);
         v[c] = (dot2c_next_lane(dot2_first(pr, wt), pr, wb) << (16 - (W_BITS - 5))) + (1 << (W_BITS - 5 - 1 + 16 - (W_BITS - 5)));
     }
 #pragma unroll
@@ -1381,7 +1450,7 @@ __device__ __forceinline__ void lkq_sample_row(const ImgDesc& im, int x0, int y0
     }
 }
 
-// NW5 = number of aligned 4-byte words a lane needs from one image row, starting at pixel (gx, gy): word i = bytes 4i..4i+3
+// The border set-ups: NWORDS dwords of one image row ALIGNED to pixel (gx, gy), word i = bytes 4i..4i+3 (row_pair(a, c) takes its pairs from them)
 template <int NWORDS>
 __device__ __forceinline__ void load_row_words(const ImgDesc& im, int gx, int gy, bool fast, unsigned* a)
 {
@@ -1444,12 +1513,11 @@ __device__ __forceinline__ void LKQLevel<WIN>::operator()(const ImgDesc I, const
         //   Ix = S[c+2] - S[c],   Iy = 3 (dV[c] + dV[c+2]) + 10 dV[c+1]
         // both kept x4 with the rounding folded in (column c of S carries 2^14 c), so descale + int16 packing is the upper half (pack_hi16).
         constexpr int NC = 4 * NS + 2;
-        unsigned a[3][NS + 1];
-#pragma unroll
-        for (int rr = 0; rr < 3; rr++) load_row_words<NS + 1>(I, ipx - 1, ipy + r - 1 + rr, true, a[rr]);
+        unsigned a[3][NS + 2];  // (pairs up to (NC - 1, NC): NS + 1 dwords from the pixel)
+        const PairSel sel = pair_selectors(load_rows_words<NS + 1, 3>(I, ipx - 1, ipy + r - 1, true, a));
         int S4[NC], dV[NC], V1[NC];
         auto column = [&](int c) {
-            const unsigned q0 = row_pair(a[0], c), q1 = row_pair(a[1], c), q2 = row_pair(a[2], c);
+            const unsigned q0 = row_pair(a[0], sel, c), q1 = row_pair(a[1], sel, c), q2 = row_pair(a[2], sel, c);
             const int v0 = dot2(q1, w0b, dot2_first(q0, w0t));
             V1[c] = dot2(q2, w0b, dot2_first(q1, w0t));
             const int v2 = (int)dpp_from_next_lane((unsigned)V1[c]);
@@ -1559,7 +1627,7 @@ __device__ __forceinline__ void LKQLevel<WIN>::operator()(const ImgDesc I, const
         const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);  // bordered level, or rows inside the level
         n_iter++;
         unsigned p01[NS], p23[NS];
-        lkq_sample_row<NS>(J, inx, iny, r, fast, w.wt, w.wb, p01, p23);  // lane r = row r (lane WIN holds the last bottom row)
+        lkq_sample_row<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, p01, p23);  // lane r = row r (lane WIN holds the last bottom row)
         int b1 = -cI[0], b2 = -cI[1];
 #pragma unroll
         for (int j = 0; j < NS; j++) {
@@ -1578,9 +1646,9 @@ __device__ __forceinline__ void LKQLevel<WIN>::operator()(const ImgDesc I, const
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
         const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);  // bordered level, or rows inside the level
         unsigned p01[NS], p23[NS], i01[NS], i23[NS];
-        lkq_sample_row<NS>(J, inx, iny, r, fast, w.wt, w.wb, p01, p23);
+        lkq_sample_row<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, p01, p23);
         // the template samples again (not kept by the set-up): the same bilinear sampling of I at the template origin
-        lkq_sample_row<NS>(I, ipx, ipy, r, fast_I || I.pad >= VH_LV_PAD, w0t, w0b, i01, i23);
+        lkq_sample_row<NS, WIN>(I, ipx, ipy, r, fast_I || I.pad >= VH_LV_PAD, w0t, w0b, i01, i23);
         int se = 0;
 #pragma unroll
         for (int j = 0; j < NS; j++) {
@@ -1644,9 +1712,10 @@ template <int NS, int WIN>
 __device__ __forceinline__ void lko_sample_rows(const ImgDesc& im, int x0, int y0, int r, bool fast, unsigned wt, unsigned wb, unsigned* a01,
                                                 unsigned* a23, unsigned* b01, unsigned* b23)
 {
-    unsigned top[NS + 1], mid[NS + 1];
-    load_row_words<NS + 1>(im, x0, y0 + 2 * r, fast, top);
-    load_row_words<NS + 1>(im, x0, y0 + 2 * r + 1, fast, mid);
+    static_assert(WIN <= 4 * NS, "pairs up to (WIN - 1, WIN): NS dwords from the pixel");
+    unsigned rows[2][NS + 1];
+    const PairSel sel = pair_selectors(load_rows_words<NS, 2>(im, x0, y0 + 2 * r, fast, rows));
+    const unsigned *top = rows[0], *mid = rows[1];
     constexpr int SH = 16 - (W_BITS - 5), RND = 1 << (W_BITS - 5 - 1 + 16 - (W_BITS - 5));
 #pragma unroll
     for (int j = 0; j < NS; j++) {
@@ -1654,7 +1723,7 @@ __device__ __forceinline__ void lko_sample_rows(const ImgDesc& im, int x0, int y
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             if (4 * j + c >= WIN) continue;
-            const unsigned pa = row_pair(top, 4 * j + c), pb = row_pair(mid, 4 * j + c);
+            const unsigned pa = row_pair(top, sel, 4 * j + c), pb = row_pair(mid, sel, 4 * j + c);
             va[c] = (dot2(pb, wb, dot2_first(pa, wt)) << SH) + RND;
             vb[c] = (dot2c_next_lane(dot2_first(pb, wt), pa, wb) << SH) + RND;
         }
@@ -1704,12 +1773,11 @@ __device__ __forceinline__ void LKOLevel<WIN>::operator()(const ImgDesc I, const
         // (V = bilinear weights . patch, no rounding); V row 2r+3 is the neighbour's V row 2(r+1)+1 (DPP).  Window row w uses V rows w, w+1, w+2:
         //   S = 3 (V_w + V_w+2) + 10 V_w+1,  dV = V_w+2 - V_w,  Ix = S[c+2] - S[c],  Iy = 3 (dV[c] + dV[c+2]) + 10 dV[c+1]   (see LKQLevel)
         constexpr int NC = 4 * NS + 2;
-        unsigned a[4][NS + 1];
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) load_row_words<NS + 1>(I, ipx - 1, ipy - 1 + 2 * r + rr, true, a[rr]);
+        unsigned a[4][NS + 2];  // (pairs up to (NC - 1, NC): NS + 1 dwords from the pixel)
+        const PairSel sel = pair_selectors(load_rows_words<NS + 1, 4>(I, ipx - 1, ipy - 1 + 2 * r, true, a));
         int SA[NC], SB[NC], dA[NC], dB[NC], CA[NC], CB[NC];
         auto column = [&](int c) {
-            const unsigned q0 = row_pair(a[0], c), q1 = row_pair(a[1], c), q2 = row_pair(a[2], c), q3 = row_pair(a[3], c);
+            const unsigned q0 = row_pair(a[0], sel, c), q1 = row_pair(a[1], sel, c), q2 = row_pair(a[2], sel, c), q3 = row_pair(a[3], sel, c);
             const int va = dot2(q1, w0b, dot2_first(q0, w0t));
             const int vb = dot2(q2, w0b, dot2_first(q1, w0t));
             const int vc = dot2(q3, w0b, dot2_first(q2, w0t));
