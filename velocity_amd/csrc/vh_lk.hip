@@ -254,6 +254,25 @@ __device__ __forceinline__ long long wave_sum1_i32_wide_swap(int a)
     const int z = dpp_row_sum(fold16_pair(x, x));  // rows 0,1: a.lo, rows 2,3: a.hi
     return (long long)__builtin_amdgcn_readlane(z, 32) * 65536ll + (long long)__builtin_amdgcn_readlane(z, 0);
 }
+// The same two reductions for the pair form of the per-track arithmetic (vh_lk_shared.hpp; one wavefront per track): one more v_permlane32_swap puts the
+// (lo, hi) halves of a value into the same lane, and the sum is converted where it lies -- no v_readlane, no recombination on the scalar unit.
+// wave_sum2_f32_pair: ((float)sum a | (float)sum b), a pair; wave_sum1_f32_lane0: (float)sum a, of which LANE 0 is the contract (the caller reads it back
+// as a scalar; the other lanes happen to hold the same float).
+__device__ __forceinline__ float wide_rows_to_f32(int z)  // rows of z: the lo halves in rows 0 and 1, the hi halves in rows 2 and 3
+{
+    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)z, (unsigned)z, false, false);  // r[0]: rows 0, 1, 0, 1 of z; r[1]: rows 2, 3, 2, 3
+    return wide_halves_to_f32((int)r[0], (int)r[1]);
+}
+__device__ __forceinline__ float wave_sum2_f32_pair(int a, int b)
+{
+    const int x = fold32_pair(a & 0xffff, a >> 16), y = fold32_pair(b & 0xffff, b >> 16);
+    return wide_rows_to_f32(dpp_row_sum(fold16_pair(x, y)));  // rows: a.lo, b.lo, a.hi, b.hi
+}
+__device__ __forceinline__ float wave_sum1_f32_lane0(int a)
+{
+    const int x = fold32_pair(a & 0xffff, a >> 16);
+    return wide_rows_to_f32(dpp_row_sum(fold16_pair(x, x)));  // rows 0,1: a.lo, rows 2,3: a.hi
+}
 
 // wave-wide sum when 16 lanes of partials provably fit int32 (one 4-sample strip per lane: 16 * 4 * 8160 * 4080 < 2^31):
 // one DPP chain per value instead of two
@@ -981,16 +1000,33 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
     long long* red = reinterpret_cast<long long*>(smem + C::OFF_RED);
     const int wave = tid >> 6;
 
-    LKStart s;
-    if (!lk_level_start(p0x, p0y, level, top_level, WIN, I, nxo, nyo, status, err, s)) return;
-    const float half = s.half;
-    const int ipx = s.ipx, ipy = s.ipy;
-    float nx = s.nx, ny = s.ny;
-    const Win w0 = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
+    // One wavefront per track: the per-track arithmetic runs on PAIRS, x in rows 0 / 2 and y in rows 1 / 3 of one register (vh_lk_shared.hpp): n = (nx | ny),
+    // no = (nxo | nyo), pd = (pdx | pdy).  The scalars nxo, nyo carry the position from level to level; `leave` hands them back at every way out.
+    constexpr bool PAIR = NW == 1;
+    float half, nx = 0.f, ny = 0.f, n = 0.f, no = 0.f;
+    int ipx, ipy, rjx, rjy;
+    Win w0;
+    const auto leave = [&]() {
+        if constexpr (PAIR) { nxo = pair_x(no); nyo = pair_y(no); }
+    };
+    if constexpr (PAIR) {
+        LKStartPair s;
+        no = pair_of(nxo, nyo);
+        if (!lk_level_start_pair(pair_of(p0x, p0y), level, top_level, WIN, I, no, status, err, s)) { leave(); return; }
+        half = s.half; ipx = s.ipx; ipy = s.ipy; n = s.n;
+        w0 = bilinear_weights_pair(__fsub_rn(s.p, (float)s.ip));
+        const int rj = vh_floor(n);
+        rjx = pair_x(rj) - M; rjy = pair_y(rj) - M;
+    } else {
+        LKStart s;
+        if (!lk_level_start(p0x, p0y, level, top_level, WIN, I, nxo, nyo, status, err, s)) return;
+        half = s.half; ipx = s.ipx; ipy = s.ipy; nx = s.nx; ny = s.ny;
+        w0 = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
+        rjx = vh_floor(nx) - M; rjy = vh_floor(ny) - M;
+    }
     n_setup++;
 
     // one batch of global loads: template patch + search region around the predicted position
-    int rjx = vh_floor(nx) - M, rjy = vh_floor(ny) - M;
     __syncthreads();  // previous users of the patch buffers are done
     stage_region<C::T, C::PI_ROWS, C::PI_PITCH>(I, ipx - 1, ipy - 1, pI, tid);
     stage_region<C::T, C::RJ, C::PJ_WIDTH, C::PJ_PITCH>(J, rjx, rjy, pJ, tid);
@@ -1099,13 +1135,24 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
             __builtin_amdgcn_sched_barrier(0);  // keep the K strips of this (rare) border path sequential: register pressure
         }
     }
-    long long sA[3];
-    block_sum_wide<NW, 3, (C::K == 1 && C::T == 64)>(part, sA, red, phase, wave);
     LKSys S;
-    if (!lk_system(sA[0], sA[1], sA[2], WIN, S)) {
+    bool solvable;
+    if constexpr (PAIR) {  // the three sums are converted in the lanes the reduction leaves them in; lk_system itself is not symmetric and stays scalar
+        const float s11_12 = wave_sum2_f32_pair(part[0], part[1]);
+        // (all three as scalars, the third from lane 0 of 64 equal ones: a sum left in a vector register counts as divergent, and the gate's branch with it)
+        solvable = lk_system(pair_x(s11_12), pair_y(s11_12), pair_x(wave_sum1_f32_lane0(part[2])), WIN, S);
+    } else {
+        long long sA[3];
+        block_sum_wide<NW, 3, (C::K == 1 && C::T == 64)>(part, sA, red, phase, wave);
+        solvable = lk_system(sA[0], sA[1], sA[2], WIN, S);
+    }
+    if (!solvable) {
         if (level == 0) status = 0;
+        leave();
         return;
     }
+    LKSysPair SP{};
+    if constexpr (PAIR) SP = lk_system_pair(S);
     const int ncI[2] = {-cI[0], -cI[1]};
     constexpr int PJP = C::PJ_PITCH >> 2;
     // C::OFF_PJ + 4 * (rA * PJP + jA) and the same of (rB, jB): (((inx - rjx) + 4 j) >> 2 = ((inx - rjx) >> 2) + j).  Out of the table they are opaque to the
@@ -1134,17 +1181,20 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
         __syncthreads();
     };
 
-    float pdx = 0.f, pdy = 0.f;
+    float pdx = 0.f, pdy = 0.f, pd = 0.f;
     const int max_count = job.max_count;
     const double eps2 = job.eps2;
     for (int it = 0; it < max_count; it++) {
-        const int inx = vh_floor(nx), iny = vh_floor(ny);
+        int inx, iny, in = 0;
+        if constexpr (PAIR) { in = vh_floor(n); inx = pair_x(in); iny = pair_y(in); }
+        else { inx = vh_floor(nx); iny = vh_floor(ny); }
         if (lk_outside(inx, iny, WIN, J)) {
             if (level == 0) status = 0;
             break;
         }
         if (!region_holds(inx, iny)) restage(inx, iny);
-        const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny)));
+        const StripWeights w = strip_weights(PAIR ? bilinear_weights_pair(__fsub_rn(n, (float)in))
+                                                  : bilinear_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny)));
         n_iter++;
         int b[2] = {ncI[0], ncI[1]};  // (lanes without strips keep -c: the first strip of the others starts from it without a copy)
         if (lane_on) {
@@ -1192,20 +1242,29 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
                 }
             }
         }
-        long long sb[2];
-        block_sum_wide<NW, 2, (C::K == 1 && C::T == 64)>(b, sb, red, phase, wave);
-        if (lk_step(S, sb[0], sb[1], half, it, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
+        if constexpr (PAIR) {
+            if (lk_step_pair(SP, wave_sum2_f32_pair(b[0], b[1]), half, it, eps2, n, no, pd)) break;
+        } else {
+            long long sb[2];
+            block_sum_wide<NW, 2, (C::K == 1 && C::T == 64)>(b, sb, red, phase, wave);
+            if (lk_step(S, sb[0], sb[1], half, it, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
+        }
     }
+    leave();
 
     if (status && level == 0) {
-        float fx, fy;
-        int inx, iny;
-        if (!lk_final_origin(nxo, nyo, half, WIN, J, fx, fy, inx, iny)) { status = 0; return; }
+        float fx = 0.f, fy = 0.f, f = 0.f;
+        int inx, iny, in = 0;
+        if (!(PAIR ? lk_final_origin_pair(no, half, WIN, J, f, in, inx, iny) : lk_final_origin(nxo, nyo, half, WIN, J, fx, fy, inx, iny))) {
+            status = 0;
+            return;
+        }
         // err is discarded by the caller (KLT.py:83 `pa, v, _`): only the bounds rule matters.  (want_err says which pass this is; whether the job asks for err
         // is read here, where it matters, not carried through the track as one more scalar)
         if (!want_err || !job.err_out) return;
         if (!region_holds(inx, iny)) restage(inx, iny);
-        const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
+        const StripWeights w = strip_weights(PAIR ? bilinear_weights_pair(__fsub_rn(f, (float)in))
+                                                  : bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
         int se[1] = {0};
         if (lane_on) {
             const unsigned jr = lane_jr();
@@ -1246,6 +1305,7 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
 // Wavefronts per SIMD the one-wavefront 51 x 51 kernel is compiled for: it needs 127 VGPRs and 10 208 bytes of LDS, so FOUR workgroups per SIMD (16 per CU)
 // are resident without a spilled register (tests/test_gpu_lk3_residency.py asks the runtime).  A/B on one box against the same code held at three
 // wavefronts: fine launch 1741 -> 1646 us, the headline +1.6 % (profiles/lk3_residency/ab.json).  (-DLK3_FINE_WAVES=3: experiments only.)
+// (With the per-track arithmetic on pairs, profiles/lk3_pair/: 121 VGPRs.)
 #ifndef LK3_FINE_WAVES
 #define LK3_FINE_WAVES 4
 #endif

@@ -5,6 +5,9 @@
 // Also here, because both sides use them: the fixed-point scales (W_BITS, LK_FLT_SCALE), the bilinear weights of a window origin (Win,
 // bilinear_weights: every level computes them from the origins the functions below return) and the one-rounding int64 -> float32 conversion of a
 // window sum (i64_to_f32).
+// The level arithmetic exists in TWO forms of the same float sequence, next to each other below: the scalar form (lk_level_start, lk_step,
+// lk_final_origin, bilinear_weights: k_lk, k_lk_strip, k_lk_q, k_lk_o and k_lk3 with more than one wavefront per track) and the pair form (the *_pair
+// functions: k_lk3 with ONE wavefront per track, <51, 1, 4> and <15, 1, 6>), which runs the x and the y statement of the scalar form in two lanes at once.
 #pragma once
 #include "vh_kernels.hpp"
 #include "vh_valu.hpp"
@@ -135,6 +138,110 @@ __device__ __forceinline__ bool lk_final_origin(float nxo, float nyo, float half
     return !lk_outside(inx, iny, win, J);
 }
 __device__ __forceinline__ float lk_err_of(float sum_abs, int win) { return __fmul_rn(sum_abs, __fdiv_rn(1.f, (float)(32 * win * win))); }
+
+// ---- the same level on PAIRS --------------------------------------------------------------------------------------------------------------------------
+// Where ONE wavefront owns a track (k_lk3 with NW == 1: <51, 1, 4> and <15, 1, 6>) the functions above would compute the same floats on all 64 lanes, and
+// they are symmetric in x and y almost line for line.  A PAIR is one register that holds the x value in the lanes of DPP rows 0 and 2 and the y value in the
+// lanes of rows 1 and 3 (lanes 0 and 16 are read back: pair_x / pair_y) -- where the exact reduction of two window sums leaves them anyway.  Each function
+// below is its scalar namesake above with the x and the y statement as ONE statement on a pair: per component the float operations and their order are
+// literally the same (every rounding still its own __f*_rn / __d*_rn call), so the results are the same bits.  The few cross terms (A12 b2 / A12 b1, dx^2 +
+// dy^2, the weight products) take the other component through pair_other, an LDS-pipe lane swap that takes no VALU slot.  What has to be a scalar -- an integer
+// origin, the weights, the stop decision -- is read back with v_readlane and is then an SGPR.
+// The scalar form stays the definition for every other kernel (k_lk, k_lk_strip, k_lk_q, k_lk_o and k_lk3 with NW > 1, whose sums come back through LDS into
+// every thread); a change to one form is a change to both.
+
+// rows 0 / 2: x, rows 1 / 3: y (one v_mov_dpp whose row mask leaves the even rows as they are; no v_cndmask)
+__device__ __forceinline__ float pair_of(float x, float y)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(y), 0xE4, 0xa, 0xf, false));  // quad_perm [0,1,2,3], rows 1 and 3
+}
+// lane l gets lane l ^ 16: (x | y) -> (y | x).  ds_swizzle, bit mode: and 0x1f, or 0, xor 0x10
+__device__ __forceinline__ int pair_other(int p) { return __builtin_amdgcn_ds_swizzle(p, 0x401f); }
+__device__ __forceinline__ float pair_other(float p) { return __int_as_float(pair_other(__float_as_int(p))); }
+__device__ __forceinline__ double pair_other(double p)
+{
+    return __hiloint2double(pair_other(__double2hiint(p)), pair_other(__double2loint(p)));
+}
+__device__ __forceinline__ int pair_x(int p) { return __builtin_amdgcn_readlane(p, 0); }
+__device__ __forceinline__ int pair_y(int p) { return __builtin_amdgcn_readlane(p, 16); }
+__device__ __forceinline__ float pair_x(float p) { return __int_as_float(pair_x(__float_as_int(p))); }
+__device__ __forceinline__ float pair_y(float p) { return __int_as_float(pair_y(__float_as_int(p))); }
+
+// (float)(hi * 65536 + lo), the exact window sum whose 16-bit halves were summed apart (wave_sum2_i32_wide: |hi| <= 64 * 2^15, 0 <= lo < 64 * 2^16), with ONE
+// rounding and without leaving the lane: hi * 65536 + lo is exact in float64 (< 2^38), so this is the float i64_to_f32 gives for the recombined int64
+__device__ __forceinline__ float wide_halves_to_f32(int lo, int hi) { return (float)__dadd_rn(__dmul_rn((double)hi, 65536.0), (double)lo); }
+
+// bilinear_weights of the fractions (a | b): (ia ib | ib ia) and (a ib | b ia) are two products, scaled, rounded and converted once each
+__device__ __forceinline__ Win bilinear_weights_pair(float ab)
+{
+    Win w;
+    const float iab = __fsub_rn(1.f, ab), iba = pair_other(iab);
+    const int m00 = vh_round(__fmul_rn(__fmul_rn(iab, iba), (float)(1 << W_BITS)));
+    const int m01 = vh_round(__fmul_rn(__fmul_rn(ab, iba), (float)(1 << W_BITS)));
+    w.w00 = pair_x(m00);
+    w.w01 = pair_x(m01);
+    w.w10 = pair_y(m01);
+    w.w11 = (1 << W_BITS) - w.w00 - w.w01 - w.w10;
+    return w;
+}
+
+// lk_level_start: p0 = (p0x | p0y), no = (nxo | nyo)
+struct LKStartPair {
+    float half, p, n;  // (px | py), (nx | ny)
+    int ip;            // (ipx | ipy), and as scalars:
+    int ipx, ipy;
+};
+__device__ __forceinline__ bool lk_level_start_pair(float p0, int level, int top_level, int win, const ImgDesc& I, float& no, int& status, float& err,
+                                                    LKStartPair& s)
+{
+    s.half = (float)(win - 1) * 0.5f;
+    const float lscale = __uint_as_float((unsigned)(127 - level) << 23);
+    const float c = __fmul_rn(p0, lscale);
+    if (level != top_level) no = __fmul_rn(no, 2.f);
+    else no = c;
+    s.p = __fsub_rn(c, s.half);
+    s.n = __fsub_rn(no, s.half);
+    s.ip = vh_floor(s.p);
+    s.ipx = pair_x(s.ip); s.ipy = pair_y(s.ip);
+    if (lk_outside(s.ipx, s.ipy, win, I)) {
+        if (level == 0) { status = 0; err = 0.f; }
+        return false;
+    }
+    return true;
+}
+
+// what lk_step reads of a level's system: A12 and iD in every lane, the diagonal as (A22 | A11)
+struct LKSysPair {
+    float A12, Ad, iD;
+};
+__device__ __forceinline__ LKSysPair lk_system_pair(const LKSys& S) { return LKSysPair{S.A12, pair_of(S.A22, S.A11), S.iD}; }
+
+// lk_step: sb = (sb1 | sb2) as floats, n = (nx | ny), no = (nxo | nyo), pd = (pdx | pdy)
+__device__ __forceinline__ bool lk_step_pair(const LKSysPair& S, float sb, float half, int it, double eps2, float& n, float& no, float& pd)
+{
+    const float b = __fmul_rn(sb, LK_FLT_SCALE);
+    const float d = __fmul_rn(__fsub_rn(pair_other(__fmul_rn(S.A12, b)), __fmul_rn(S.Ad, b)), S.iD);  // (dx | dy)
+    n = __fadd_rn(n, d);
+    no = __fadd_rn(n, half);
+    const double q = __dmul_rn((double)d, (double)d);
+    if (__builtin_amdgcn_ballot_w64(__dadd_rn(q, pair_other(q)) <= eps2) & 1ull) return true;  // lane 0: dx^2 + dy^2
+    constexpr unsigned long long XY = 1ull | 1ull << 16;
+    if (it > 0 && (__builtin_amdgcn_ballot_w64(fabsf(__fadd_rn(d, pd)) < 0.01f) & XY) == XY) {
+        no = __fsub_rn(no, __fmul_rn(d, 0.5f));
+        return true;
+    }
+    pd = d;
+    return false;
+}
+
+// lk_final_origin: f = (fx | fy), in = its integer part as a pair, (inx, iny) the same as scalars
+__device__ __forceinline__ bool lk_final_origin_pair(float no, float half, int win, const ImgDesc& J, float& f, int& in, int& inx, int& iny)
+{
+    f = __fsub_rn(no, half);
+    in = vh_floor(f);
+    inx = pair_x(in); iny = pair_y(in);
+    return !lk_outside(inx, iny, win, J);
+}
 
 // ---- one track --------------------------------------------------------------------------------------------------------------------------------------
 
