@@ -278,6 +278,24 @@ VH_API int vh_frame0_init_batch2(vh_ctx* ctx, int nb, const uint8_t* const* fram
                                  int block, double k, int use_harris, double min_distance, int subpix_win, int subpix_iter, double subpix_eps,
                                  float* p_out, double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out,
                                  int* roi_host, void* stream);
+/* (vh_version >= 111) the camera of one clip of vh_frame0_init_batch3: its frame size, the row stride of its frame and its intrinsics (K in the layout of
+ * K_host above; k_is_float32 states how the caller holds K -- frame 0 computes in float64 either way, the field travels with the camera so that the
+ * same record serves vh_session_set_camera). */
+typedef struct vh_clip_camera {
+    int w, h, stride, k_is_float32;
+    double K[9];
+} vh_clip_camera;
+/* (vh_version >= 111) vh_frame0_init_batch2 for clips of DIFFERENT cameras: cams_host, a host array of nb vh_clip_camera, takes the place of the shared
+ * w, h, stride and K_host; the plate and every detector parameter stay shared by the batch.  Clip b's boundingRect, its argument checks, its cornerSubPix
+ * and its pose / image2world use cams_host[b] alone.  This is THE frame-0 implementation: vh_frame0_init, vh_frame0_init_batch and vh_frame0_init_batch2
+ * are this call with one camera replicated (the same kernels, the same results bit for bit), and a clip's outputs are what vh_frame0_init gives for it
+ * alone.  Outputs, chunking and scratch as vh_frame0_init_batch (vh_init_reserve_batch(ctx, nb, w, h) with the LARGEST w x h of the clips to come).
+ * Every argument is checked before anything is queued: -1 for what vh_frame0_init_batch2 refuses, with vh_last_error naming the clip whose camera has
+ * w or h < 3, stride < w, a null frame or an empty plate ROI. */
+VH_API int vh_frame0_init_batch3(vh_ctx* ctx, int nb, const uint8_t* const* frames_host, const vh_clip_camera* cams_host, const float* q_host,
+                                 const double* plate_host, int border_x, int border_y, int max_corners, double quality, int block, double k,
+                                 int use_harris, double min_distance, int subpix_win, int subpix_iter, double subpix_eps, float* p_out, double* p3_out,
+                                 uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host, void* stream);
 
 /* ---- recovery by feature matching (vh_version >= 108) ------------------------------------------------------------ */
 /* Parameters of vh_match_affine; NULL means the defaults in brackets.  levels [5]: images per frame at scale 2^(-l/4), 1..8; query_per_level [500] /
@@ -360,14 +378,24 @@ typedef struct {
     int n0, nhist;
 } vh_session_view;
 
-/* K_host: 9 doubles; k_is_float32 != 0: the caller's K array is float32 (vidExample.py:29-33), so fcnMSV1_t builds its rays in
+/* w x h: the LARGEST frame a slot of the session can hold, and with K_host / k_is_float32 the camera every slot starts with (vh_session_set_camera gives a
+ * slot its own).  K_host: 9 doubles; k_is_float32 != 0: the caller's K array is float32 (vidExample.py:29-33), so fcnMSV1_t builds its rays in
  * float32 like numpy does.  n0 = number of initial tracks, nhist = number of frames of history (P, B, S rows),
  * msv_frame = frame index at which fcnMSV1_t re-triangulates (vidExample.py:155; <= 0 disables; a frame the history reaches -- < nhist -- must be below
  * 2048: -1 otherwise, the limit of vh_msv1_t). */
 VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, int nhist, int w, int h, const double* K_host,
                              int k_is_float32, const vh_lk_params* coarse_host, const vh_lk_params* fine_host, int msv_frame);
 VH_API void vh_session_destroy(vh_session* s);
-/* frame-0 state of stream `slot` (vidExample.py:116-131): p n0 x 2, p3 n0 x 3, vp n0 (device); t0_host = plate pose t */
+/* (vh_version >= 111) the camera of ONE slot: frame size w x h and intrinsics (K_host: 9 doubles; k_is_float32 as in vh_session_create) that the slot's
+ * next vh_session_init / vh_session_init_dev and the steps after it use -- the slot's frames, its quarter-scale images, its pose fit and its fcnMSV1_t.
+ * The streams of a session may so differ in resolution and focal length; every launch of a step is sized for the session's w x h and a smaller stream's
+ * surplus workgroups leave at once.  Stream-ordered (one small launch, no host wait): legal between two steps while earlier steps are still queued; the
+ * slot's state of its previous clip is void from the call on (initialise it again before its next active step).  A slot that never gets the call keeps
+ * the session's w, h and K.  -1 (vh_last_error names the slot and the limit; nothing written): a bad slot, a null K_host, w or h below 4, w above the
+ * session's w or h above its h (a portrait frame does not fit a landscape session of the same area: each side must fit). */
+VH_API int vh_session_set_camera(vh_session* s, int slot, int w, int h, const double* K_host, int k_is_float32, void* stream);
+/* frame-0 state of stream `slot` (vidExample.py:116-131): p n0 x 2, p3 n0 x 3, vp n0 (device); t0_host = plate pose t.  frame0: the slot's w x h frame
+ * (vh_session_set_camera; the session's size without it) with rows `stride` >= w bytes apart -- the row stride of every later frame of the slot too. */
 VH_API int vh_session_init(vh_session* s, int slot, const uint8_t* frame0, int stride, const float* p, const double* p3,
                            const uint8_t* vp, const float* t0_host, float time0, float frame_no, float res0, void* stream);
 /* the same straight from the outputs of vh_frame0_init, all still on the device (no read-back between frame 0 and the loop): t0_dev float[3], res0_dev
@@ -375,7 +403,7 @@ VH_API int vh_session_init(vh_session* s, int slot, const uint8_t* frame0, int s
  * that never existed (vg = 0, history NaN, S[0,2] = *n_dev). */
 VH_API int vh_session_init_dev(vh_session* s, int slot, const uint8_t* frame0, int stride, const float* p, const double* p3, const uint8_t* vp,
                                const float* t0_dev, const double* res0_dev, const int* n_dev, float time0, float frame_no, void* stream);
-/* one frame for every stream: frames_dev = device array of ctx->batch frame pointers (dense, w x h) */
+/* one frame for every stream: frames_dev = device array of ctx->batch frame pointers (stream b's frame has that slot's size and the row stride of its frame 0) */
 VH_API int vh_session_step(vh_session* s, const uint8_t* const* frames_dev, float time_s, float frame_no, void* stream);
 /* the same with one timestamp / frame number PER STREAM (device float[batch] each): independent videos with their own
  * CAP_PROP_POS_MSEC / frame counters (vidExample.py:142: B[i,12:14]).  The frames of step i must stay alive until step i+1 has
@@ -422,11 +450,11 @@ VH_API int vh_session_export(vh_session* s, int slot, void* rec_dev, void* strea
 VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
 /* (vh_version >= 109) the recovery branch of KLTmain (utils/KLT.py:130-133) inside the session; default OFF: a step then queues exactly the launches it
  * always did and a stream whose coarse stage fails reports klt_flags & 1 and goes on with what the blind fine stage kept.
- * on != 0 (params_host: the matcher's parameters, NULL = defaults) creates everything the branch needs -- a private context of the session's frame
+ * on != 0 (params_host: the matcher's parameters, NULL = defaults) creates everything the branch needs -- a private context of the session's (maximum) frame
  * size, the matcher's scratch for up to 16 pairs, a pinned host record -- so no step allocates.  Every step then, between KLTmain and the bookkeeping:
  *   - reads {klt_flags, n_cur} of every stream back: ONE small device-to-host copy and ONE hipStreamSynchronize PER STEP, whether a stream failed or not.
  *     The host therefore no longer runs ahead of the device; leave the option off for clips that do not need it.
- *   - for the streams with klt_flags & 1 and n_cur > 0: vh_match_affine_batch(im0, frame, p, n_cur) (at most 16 pairs per call), a second
+ *   - for the streams with klt_flags & 1 and n_cur > 0: vh_match_affine_batch(im0, frame, p, n_cur) (at most 16 pairs per call, one call per distinct frame size among them), a second
  *     synchronisation to read status and M, and for every stream with a model KLTregional(im0, im, p0, T23.T, lk_fine, fbt = 0.3) into that stream's KLTmain
  *     outputs.  klt_flags gets bit 1 (the recovery ran) and, with a model, bit 2.  Without a model the blind fine stage's result stands.
  * A step of a session with the option on CANNOT be captured into a graph (it waits for the stream): under a stream capture it returns -6 before
@@ -437,8 +465,9 @@ VH_API int vh_session_recoveries(vh_session* s, int* counts_host);
 /* Packed track state of every stream for the cross-GPU exchange (RCCL all-gather, DESIGN.md "multi-GPU"):
  * out = device float32 [batch][8 + 3*n0]: {n_cur, n_pose, frame_i, klt_flags, t[3], res | p (n0 x 2) | ids (n0, int32 bits)} */
 /* Fused frame ingest for every stream of the session (vidExample.py:91 + KLT.py:111-113 in ONE pass over the BGR frames): bgr_frames_dev / gray_frames_dev =
- * device arrays of ctx->batch pointers (h x w x 3 with rows bgr_stride bytes apart; dense w x h gray destinations owned by the caller, a null BGR pointer skips
- * the stream).  Writes the gray frames and, straight into the session, the quarter-scale images the next vh_session_step starts from (that step then
+ * device arrays of ctx->batch pointers (stream b: h_b x w_b x 3 at that slot's size, rows bgr_stride bytes apart -- bgr_stride == 0: dense rows of
+ * 3 w_b bytes for every stream, the form for slots of different widths; a non-zero value is one stride for all streams and must cover the widest slot --
+ * and w_b x h_b gray destinations owned by the caller with the slot's row stride; a null BGR pointer skips the stream).  Writes the gray frames and, straight into the session, the quarter-scale images the next vh_session_step starts from (that step then
  * skips its own resize); pass the same gray frames to that step. */
 VH_API int vh_session_ingest_bgr(vh_session* s, const uint8_t* const* bgr_frames_dev, int bgr_stride, uint8_t* const* gray_frames_dev, void* stream);
 VH_API int vh_session_pack_state(vh_session* s, float* out, void* stream);

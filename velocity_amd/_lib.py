@@ -48,6 +48,12 @@ class MatchParams(C.Structure):
                                        "min_good")] + [("quality", C.c_double)]
 
 
+class ClipCamera(C.Structure):
+    """vh_clip_camera: the camera of one clip of vh_frame0_init_batch3 (frame size, row stride of its frame, how the caller holds K, K as host_K gives it)."""
+
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("stride", C.c_int), ("k_is_float32", C.c_int), ("K", C.c_double * 9)]
+
+
 class MatchStages(C.Structure):
     _fields_ = [("kp", (vp * 8) * 2), ("cnt", vp), ("pos", vp * 2), ("desc", vp * 2), ("nn", vp), ("good", vp), ("roi", vp), ("levels", C.c_int),
                 ("lw", C.c_int * 8), ("lh", C.c_int * 8)]
@@ -132,6 +138,9 @@ _SIGS = {
                                     vp, vp]),
     "vh_frame0_init_batch2": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, f32p, f64p, f64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                         C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, i32p, vp]),
+    "vh_frame0_init_batch3": (C.c_int, [vp, C.c_int, vp, C.POINTER(ClipCamera), f32p, f64p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int,
+                                        C.c_double, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, i32p, vp]),
+    "vh_session_set_camera": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, f64p, C.c_int, vp]),
     "vh_match_affine": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(MatchParams), vp, vp, vp, vp, vp]),
     "vh_match_reserve": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MatchParams), vp]),
     "vh_match_affine_batch": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, C.POINTER(MatchParams), vp, vp, vp, vp, vp]),
@@ -329,6 +338,16 @@ def workspace(w=0, h=0, n=0):
 def host_K(K):
     """The intrinsics as the C ABI takes them: 9 contiguous float64 (K.astype(float), utils/NLS.py:22-24,196 -- a float32 K widens exactly)."""
     return np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+
+
+def k_is_float32(K):
+    """1 when the caller holds K as a float32 array: numpy then builds fcnMSV1_t's rays in float32 (utils/MSV.py:15-17)."""
+    return int(getattr(K, "dtype", None) == np.float32)
+
+
+def clip_camera(w, h, K, stride=None):
+    """A ClipCamera of a dense (or `stride`-pitched) w x h frame with intrinsics K."""
+    return ClipCamera(int(w), int(h), int(w if stride is None else stride), k_is_float32(K), (C.c_double * 9)(*host_K(K)))
 
 
 def match_params(d=None):

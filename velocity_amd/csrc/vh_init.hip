@@ -226,9 +226,18 @@ struct F0ClipPiece {
     F0Clip c[F0B_PIECE];
 };
 struct F0Shared {
-    double K[9];
     double plate[12];
 };
+// A clip's camera (vh_clip_camera: frame size and intrinsics; the row stride is F0Clip's), in a table of its own beside the descriptors and uploaded the
+// same way: F0Clip stays at its 128 bytes.
+struct F0Cam {
+    double K[9];
+    int w, h;
+};
+struct F0CamPiece {
+    F0Cam c[F0B_PIECE];
+};
+static_assert(sizeof(F0CamPiece) <= 3072, "one kernel argument (vh_store)");
 
 // Sobel 3x3 (aperture 3, REFLECT_101; the pair (dx, dy) per pixel) into an LDS tile with a (block - 1) halo, response of 64 x 16 pixels, per-clip maximum over the pixels the clip's mask keeps.
 // HARRIS: the block x block sums of the products and det - k trace^2 in float32; otherwise the minimum eigenvalue of the same structure tensor (OpenCV's calcMinEigenVal:
@@ -572,16 +581,16 @@ __global__ __launch_bounds__(1024) void k_f0b_spread(const F0Clip* tab, int max_
     }
 }
 
-__global__ __launch_bounds__(64) void k_f0b_subpix(const F0Clip* tab, int b0, int cap, int w, int h, size_t st, const unsigned* cnt, int max_corners, int win,
+__global__ __launch_bounds__(64) void k_f0b_subpix(const F0Clip* tab, const F0Cam* cam, int b0, int cap, const unsigned* cnt, int max_corners, int win,
                                                    int max_iter, double eps2, const float* mask, float* p_out)
 {
     const int clip = blockIdx.y, q = blockIdx.x * 64 + threadIdx.x;
     if (q >= min((int)cnt[4 * clip + 2], max_corners)) return;
-    subpix_corner(tab[clip].im, w, h, st, p_out + (size_t)(b0 + clip) * cap * 2 + 8, q, win, max_iter, eps2, mask);
+    subpix_corner(tab[clip].im, cam[clip].w, cam[clip].h, (size_t)tab[clip].stride, p_out + (size_t)(b0 + clip) * cap * 2 + 8, q, win, max_iter, eps2, mask);
 }
 
 // per clip: zero the counters, build the plate-pose job of vh_frame0_init (estimateWorldCameraPose(K, q, plate, findR=True) from x0 = [0, 0, 0, 0, 0, 1])
-__global__ __launch_bounds__(64) void k_f0b_setup(const F0Shared* sh, int b0, int n, int cap, float* p_out, float* t_out, double* R_out, double* res_out,
+__global__ __launch_bounds__(64) void k_f0b_setup(const F0Shared* sh, const F0Cam* cam, int b0, int n, int cap, float* p_out, float* t_out, double* R_out, double* res_out,
                                                   unsigned* cnt, int* info, PoseJob* pose)
 {
     const int clip = blockIdx.x * 64 + threadIdx.x;
@@ -589,14 +598,14 @@ __global__ __launch_bounds__(64) void k_f0b_setup(const F0Shared* sh, int b0, in
     const size_t b = (size_t)(b0 + clip);
     for (int k = 0; k < 4; k++) cnt[4 * clip + k] = 0;
     PoseJob P;
-    for (int i = 0; i < 9; i++) { P.K[i] = sh->K[i]; P.R[i] = (i % 4 == 0) ? 1.0 : 0.0; }
+    for (int i = 0; i < 9; i++) { P.K[i] = cam[clip].K[i]; P.R[i] = (i % 4 == 0) ? 1.0 : 0.0; }
     for (int i = 0; i < 6; i++) P.x0[i] = i == 5 ? 1.0 : 0.0;
     P.p = p_out + b * cap * 2; P.pw = sh->plate; P.p_sel = nullptr; P.pw_sel = nullptr; P.n_ptr = nullptr; P.n = 4; P.mode = 1;
     P.t_out = t_out + 3 * b; P.R_out = R_out + 9 * b; P.res_out = res_out + b; P.p_proj = nullptr; P.info_out = info + 2 * clip;
     pose[clip] = P;
 }
 
-__global__ __launch_bounds__(256) void k_f0b_world(const F0Clip* tab, const F0Shared* sh, int b0, int cap, const unsigned* cnt, const double* R_out,
+__global__ __launch_bounds__(256) void k_f0b_world(const F0Clip* tab, const F0Cam* cam, int b0, int cap, const unsigned* cnt, const double* R_out,
                                                    const float* t_out, const float* p_out, double* p3_out, uint8_t* vp_out, int* n_out)
 {
     const int clip = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
@@ -604,7 +613,7 @@ __global__ __launch_bounds__(256) void k_f0b_world(const F0Clip* tab, const F0Sh
     const int n = min(4 + (int)cnt[4 * clip + 2], cap);
     if (i == 0) n_out[b] = n;
     if (i >= cap) return;
-    frame0_world_row(i, n, sh->K, tab[clip].boxa, R_out + 9 * b, t_out + 3 * b, p_out + b * cap * 2, p3_out + b * cap * 3, vp_out + b * cap);
+    frame0_world_row(i, n, cam[clip].K, tab[clip].boxa, R_out + 9 * b, t_out + 3 * b, p_out + b * cap * 2, p3_out + b * cap * 3, vp_out + b * cap);
 }
 
 static void batch_sel_release(InitBatchScratch& B)
@@ -615,7 +624,7 @@ static void batch_sel_release(InitBatchScratch& B)
 static void batch_release(InitBatchScratch& B)
 {
     batch_sel_release(B);
-    (void)hipFree(B.resp); (void)hipFree(B.keys); (void)hipFree(B.cnt); (void)hipFree(B.info); (void)hipFree(B.tab); (void)hipFree(B.shared);
+    (void)hipFree(B.resp); (void)hipFree(B.keys); (void)hipFree(B.cnt); (void)hipFree(B.info); (void)hipFree(B.tab); (void)hipFree(B.cam); (void)hipFree(B.shared);
     (void)hipFree(B.pose);
     memset(&B, 0, sizeof(B));
 }
@@ -639,7 +648,7 @@ static int batch_grow_guard(bool had, hipStream_t s, const char* remedy)
     return 0;
 }
 
-static size_t batch_clip_bytes(size_t px) { return 12 * px + 24 + sizeof(F0Clip) + sizeof(PoseJob); }
+static size_t batch_clip_bytes(size_t px) { return 12 * px + 24 + sizeof(F0Clip) + sizeof(F0Cam) + sizeof(PoseJob); }
 
 // scratch for chunks of up to `clips` clips and `pix` ROI pixels in all (never shrinks)
 static int batch_reserve(vh_ctx* c, int clips, size_t pix, hipStream_t s, const char* remedy)
@@ -658,6 +667,7 @@ static int batch_reserve(vh_ctx* c, int clips, size_t pix, hipStream_t s, const 
     VH_CHECK(hipMalloc((void**)&B.cnt, sizeof(unsigned) * 4 * clips));
     VH_CHECK(hipMalloc((void**)&B.info, sizeof(int) * 2 * clips));
     VH_CHECK(hipMalloc(&B.tab, sizeof(F0Clip) * tab_n));
+    VH_CHECK(hipMalloc(&B.cam, sizeof(F0Cam) * tab_n));
     VH_CHECK(hipMalloc(&B.shared, sizeof(F0Shared)));
     VH_CHECK(hipMalloc((void**)&B.pose, sizeof(PoseJob) * clips));
     B.clips_cap = clips;
@@ -796,24 +806,49 @@ static int f0b_upload(F0Clip* d_tab, const F0Clip* h, int n, hipStream_t s)
     return 0;
 }
 
-static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host, const double* K_host,
+// the cameras of the same n clips, beside their descriptors
+static int f0b_upload_cams(F0Cam* d_cam, const vh_clip_camera* h, int n, hipStream_t s)
+{
+    for (int p0 = 0; p0 < n; p0 += F0B_PIECE) {
+        F0CamPiece piece;
+        memset(&piece, 0, sizeof(piece));
+        for (int i = 0; i < F0B_PIECE && p0 + i < n; i++) {
+            for (int k = 0; k < 9; k++) piece.c[i].K[k] = h[p0 + i].K[k];
+            piece.c[i].w = h[p0 + i].w; piece.c[i].h = h[p0 + i].h;
+        }
+        VH_CHECK(vh_store(reinterpret_cast<F0CamPiece*>(d_cam + p0), piece, s));
+    }
+    return 0;
+}
+
+// THE frame-0 sequence (vh_frame0_init_batch3; the other entries replicate one camera): cams = nb host cameras, one per clip
+static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host, const vh_clip_camera* cams, const float* q_host,
                             const double* plate_host, int border_x, int border_y, const F0Detect& D, int subpix_win, int subpix_iter, double subpix_eps,
                             float* p_out, double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host,
                             void* stream, const char* fn, const char* remedy)
 {
     // every check before anything is queued
     char msg[160];
-    if (!c || !frames_host || !q_host || !K_host || !plate_host || !p_out || !p3_out || !vp_out || !t_out || !R_out || !res_out || !n_out) {
+    if (!c || !frames_host || !cams || !q_host || !plate_host || !p_out || !p3_out || !vp_out || !t_out || !R_out || !res_out || !n_out) {
         snprintf(msg, sizeof(msg), "%s: null argument", fn);
         return vh_fail(-1, msg);
     }
     const int max_corners = D.max_corners;
-    if (nb < 1 || w < 3 || h < 3 || stride < w || max_corners < 1 || D.block < 1 || D.block > 15 || subpix_win < 1 || subpix_win > SUBPIX_MAXWIN) {
+    if (nb < 1 || max_corners < 1 || D.block < 1 || D.block > 15 || subpix_win < 1 || subpix_win > SUBPIX_MAXWIN) {
         snprintf(msg, sizeof(msg), "%s: bad arguments", fn);
         return vh_fail(-1, msg);
     }
-    int r = f0b_detect_check(D, w, h, fn);
-    if (r) return r;
+    int r = 0;
+    for (int b = 0; b < nb; b++) {  // every clip's camera
+        const int w = cams[b].w, h = cams[b].h;
+        if (w < 3 || h < 3 || cams[b].stride < w) {
+            snprintf(msg, sizeof(msg), "%s: bad arguments (clip %d: a %d x %d frame with row stride %d)", fn, b, w, h, cams[b].stride);
+            return vh_fail(-1, msg);
+        }
+        char who[96];
+        snprintf(who, sizeof(who), "%s: clip %d", fn, b);
+        if ((r = f0b_detect_check(D, w, h, b ? who : fn))) return r;
+    }
     std::vector<F0Clip> clips(nb);
     std::vector<int> rois(8 * (size_t)nb);  // boxa, boxb of every clip
     size_t max_px = 0;
@@ -824,6 +859,7 @@ static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host
         }
         F0Clip& C = clips[b];
         memset(&C, 0, sizeof(C));
+        const int w = cams[b].w, h = cams[b].h, stride = cams[b].stride;
         int* boxb = &rois[8 * b + 4];
         host_bounding_rect(q_host + 8 * b, 4, w, h, 0, 0, C.boxa);  // vidExample.py:107
         host_bounding_rect(q_host + 8 * b, 4, w, h, border_x, border_y, boxb);  // :108
@@ -860,10 +896,10 @@ static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host
     if (max_corners > F0B_SEL_MAX && D.min_distance < 1 && (r = batch_sel_reserve(c, max_corners, s))) return r;
     if (roi_host) memcpy(roi_host, rois.data(), sizeof(int) * 8 * nb);
     F0Shared sh;
-    for (int i = 0; i < 9; i++) sh.K[i] = K_host[i];
     for (int i = 0; i < 12; i++) sh.plate[i] = plate_host[i];
     F0Shared* d_sh = reinterpret_cast<F0Shared*>(B.shared);
     F0Clip* d_tab = reinterpret_cast<F0Clip*>(B.tab);
+    F0Cam* d_cam = reinterpret_cast<F0Cam*>(B.cam);
     VH_CHECK(vh_store(d_sh, sh, s));
     const int cap = 4 + max_corners;
     const int iters = subpix_iter < 1 ? 1 : (subpix_iter > 100 ? 100 : subpix_iter);
@@ -879,18 +915,37 @@ static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host
             px += (size_t)C.rw * C.rh;
             n++;
         }
-        if ((r = f0b_upload(d_tab, &clips[b0], n, s))) return r;
-        hipLaunchKernelGGL(k_f0b_setup, dim3((n + 63) / 64), dim3(64), 0, s, d_sh, b0, n, cap, p_out, t_out, R_out, res_out, B.cnt, B.info, B.pose);
+        if ((r = f0b_upload(d_tab, &clips[b0], n, s)) || (r = f0b_upload_cams(d_cam, cams + b0, n, s))) return r;
+        hipLaunchKernelGGL(k_f0b_setup, dim3((n + 63) / 64), dim3(64), 0, s, d_sh, d_cam, b0, n, cap, p_out, t_out, R_out, res_out, B.cnt, B.info, B.pose);
         r = f0b_detect(B, d_tab, &clips[b0], n, D, 1, s);
         if (r) return r;
-        hipLaunchKernelGGL(k_f0b_subpix, dim3((max_corners + 63) / 64, n), dim3(64), 0, s, d_tab, b0, cap, w, h, (size_t)stride, B.cnt, max_corners,
+        hipLaunchKernelGGL(k_f0b_subpix, dim3((max_corners + 63) / 64, n), dim3(64), 0, s, d_tab, d_cam, b0, cap, B.cnt, max_corners,
                            subpix_win, iters, eps * eps, mask, p_out);
         vh_launch_pose(B.pose, sizeof(PoseJob), n, 1, 4, s);
-        hipLaunchKernelGGL(k_f0b_world, dim3((cap + 255) / 256, n), dim3(256), 0, s, d_tab, d_sh, b0, cap, B.cnt, R_out, t_out, p_out, p3_out, vp_out, n_out);
+        hipLaunchKernelGGL(k_f0b_world, dim3((cap + 255) / 256, n), dim3(256), 0, s, d_tab, d_cam, b0, cap, B.cnt, R_out, t_out, p_out, p3_out, vp_out, n_out);
         VH_CHECK(hipGetLastError());
         b0 += n;
     }
     return 0;
+}
+
+// the entries of ONE camera (vh_frame0_init, vh_frame0_init_batch, vh_frame0_init_batch2): that camera for every clip
+static int frame0_one_camera(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host, const double* K_host,
+                             const double* plate_host, int border_x, int border_y, const F0Detect& D, int subpix_win, int subpix_iter, double subpix_eps,
+                             float* p_out, double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host,
+                             void* stream, const char* fn, const char* remedy)
+{
+    char msg[160];
+    if (!K_host) {
+        snprintf(msg, sizeof(msg), "%s: null argument", fn);
+        return vh_fail(-1, msg);
+    }
+    vh_clip_camera cam;
+    cam.w = w; cam.h = h; cam.stride = stride; cam.k_is_float32 = 0;
+    for (int i = 0; i < 9; i++) cam.K[i] = K_host[i];
+    const std::vector<vh_clip_camera> cams((size_t)(nb > 0 ? nb : 1), cam);
+    return frame0_batch_run(c, nb, frames_host, cams.data(), q_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out, p3_out,
+                            vp_out, t_out, R_out, res_out, n_out, roi_host, stream, fn, remedy);
 }
 
 extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
@@ -899,8 +954,8 @@ extern "C" VH_API int vh_frame0_init_batch(vh_ctx* c, int nb, const uint8_t* con
                                            uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host, void* stream)
 {
     const F0Detect D = {max_corners, block, 1, quality, k, 0.0};
-    return frame0_batch_run(c, nb, frames_host, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out,
-                            p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch", F0B_RESERVE_BATCH);
+    return frame0_one_camera(c, nb, frames_host, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out,
+                             p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch", F0B_RESERVE_BATCH);
 }
 
 extern "C" VH_API int vh_frame0_init_batch2(vh_ctx* c, int nb, const uint8_t* const* frames_host, int w, int h, int stride, const float* q_host,
@@ -910,8 +965,19 @@ extern "C" VH_API int vh_frame0_init_batch2(vh_ctx* c, int nb, const uint8_t* co
                                             int* roi_host, void* stream)
 {
     const F0Detect D = {max_corners, block, use_harris ? 1 : 0, quality, k, min_distance};
-    return frame0_batch_run(c, nb, frames_host, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out,
-                            p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch2", F0B_RESERVE_BATCH);
+    return frame0_one_camera(c, nb, frames_host, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out,
+                             p3_out, vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch2", F0B_RESERVE_BATCH);
+}
+
+extern "C" VH_API int vh_frame0_init_batch3(vh_ctx* c, int nb, const uint8_t* const* frames_host, const vh_clip_camera* cams_host, const float* q_host,
+                                            const double* plate_host, int border_x, int border_y, int max_corners, double quality, int block, double k,
+                                            int use_harris, double min_distance, int subpix_win, int subpix_iter, double subpix_eps, float* p_out,
+                                            double* p3_out, uint8_t* vp_out, float* t_out, double* R_out, double* res_out, int* n_out, int* roi_host,
+                                            void* stream)
+{
+    const F0Detect D = {max_corners, block, use_harris ? 1 : 0, quality, k, min_distance};
+    return frame0_batch_run(c, nb, frames_host, cams_host, q_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out, p3_out,
+                            vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init_batch3", F0B_RESERVE_BATCH);
 }
 
 // frame 0 of one video: the batch of one clip.  Its output layout is the single call's (cap = 4 + max_corners rows, roi_host int[8])
@@ -921,8 +987,8 @@ extern "C" VH_API int vh_frame0_init(vh_ctx* c, const uint8_t* im, int w, int h,
                                      double* R_out, double* res_out, int* n_out, int* roi_host, void* stream)
 {
     const F0Detect D = {max_corners, block, 1, quality, k, 0.0};
-    return frame0_batch_run(c, 1, &im, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out, p3_out,
-                            vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init", F0B_RESERVE_ONE);
+    return frame0_one_camera(c, 1, &im, w, h, stride, q_host, K_host, plate_host, border_x, border_y, D, subpix_win, subpix_iter, subpix_eps, p_out, p3_out,
+                             vp_out, t_out, R_out, res_out, n_out, roi_host, stream, "vh_frame0_init", F0B_RESERVE_ONE);
 }
 
 // one chunk of whole-image clips whose scratch the caller has reserved (batch_reserve: n clips, the sum of their pixels): response planes back to back

@@ -3,9 +3,11 @@
 // pose-track selection, NaN-padded history P), estimateWorldCameraPose(findR=False), the B/S result records and, at
 // the MSV frame, fcnMSV1_t.  One step = a fixed sequence of launches over all streams, no host round trip.
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <new>
+#include <vector>
 
 #include <stddef.h>
 
@@ -31,7 +33,7 @@ struct SessFbRec {
 struct SessFallback {
     int on, chunk;
     vh_match_params params;
-    vh_ctx* ctx;        // batch 1, the session's frame size, max_pts >= max(N0, levels x query_per_level)
+    vh_ctx* ctx;        // batch 1, the session's (maximum) frame size, max_pts >= max(N0, levels x query_per_level)
     SessFbRec* h_rec;   // pinned [batch]
     SessFbRec* d_rec;   // [batch]
     double* d_M;        // [chunk][6]
@@ -49,7 +51,7 @@ struct vh_session {
     vh_lk_params coarse, fine;
     char* arena;
     SessStream* d_ss;
-    SessStream* h_ss;  // host mirror of the pointer fields
+    SessStream* h_ss;  // host mirror of the pointer fields and of every slot's camera (w, h, K: vh_session_set_camera) and row stride
     IngestJob* d_ingest;  // [batch] descriptors of the fused BGR ingest
     int* h_frame;      // per stream: frames stepped since its vh_session_init (host mirror of SessStream::frame_i; the
                        // reference fires fcnMSV1_t at `i == msvFrame` of EACH video, vidExample.py:155)
@@ -252,7 +254,7 @@ __global__ void k_sess_fb_flags(SessStream* S, int bits)
 // vh_frame0_init -- instead of the by-value arguments; with n_dev < N0 the tail rows are tracks that never existed (vg 0, history NaN)
 __global__ __launch_bounds__(256) void k_sess_init(SessStream* ss, const float* p, const double* p3, const uint8_t* vp, const uint8_t* frame0,
                                                    float t0x, float t0y, float t0z, float time0, float frame_no, float res0, const float* t0_dev,
-                                                   const double* res0_dev, const int* n_dev)
+                                                   const double* res0_dev, const int* n_dev, int stride)
 {
     SessStream& S = *ss;
     const int tid = threadIdx.x, N0 = S.N0, nh = S.nhist;
@@ -283,12 +285,27 @@ __global__ __launch_bounds__(256) void k_sess_init(SessStream* ss, const float* 
         S.t0 = time0; S.r_total = 0.f; S.res = res0_dev ? *res0_dev : (double)res0;
         S.S[0] = 0.f; S.S[2] = (float)n; S.S[3] = res0; S.S[4] = nanv; S.S[8] = nanv;
         S.im0 = frame0;
+        S.stride = stride;  // rows of this slot's frames (frame 0 and every later one)
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
+// the camera of one slot (vh_session_set_camera): frame size and intrinsics, in the three places the step reads K from
+struct SessCamera {
+    double K[9];
+    int w, h, f32;
+};
+__global__ void k_sess_camera(SessStream* ss, SessCamera cam)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    SessStream& S = *ss;
+    for (int k = 0; k < 9; k++) { S.K[k] = cam.K[k]; S.pose.K[k] = cam.K[k]; S.msv.K[k] = cam.K[k]; }
+    S.msv.f32_rays = cam.f32;
+    S.w = cam.w; S.h = cam.h; S.stride = cam.w;
+}
+
 // fcnMSV1_t (vidExample.py:155-160) can fire for this session: the predicate that both sizes its scratch and gates its launch
 static inline bool sess_msv_fires(int msv_frame, int nhist) { return msv_frame >= 1 && msv_frame + 1 <= 2048 && msv_frame < nhist; }
 
@@ -417,18 +434,31 @@ extern "C" VH_API int vh_session_recoveries(vh_session* s, int* counts_host)
     return 0;
 }
 
-// KLT.py:126-133 for every stream whose coarse stage has just failed; queued between KLTmain and the bookkeeping of the step
+// KLT.py:126-133 for every stream whose coarse stage has just failed; queued between KLTmain and the bookkeeping of the step.  The matcher takes pairs of
+// ONE frame size per call, so the failed streams are served in groups of equal (w, h, stride), each of at most `chunk` pairs, in slot order: a session of
+// one camera makes exactly the calls it always made.
 static int session_recover(vh_session* s, const uint8_t* const* frames_dev, hipStream_t st)
 {
     SessFallback& F = s->fb;
-    const int nb = s->batch, w = s->w, h = s->h;
+    const int nb = s->batch;
     hipLaunchKernelGGL(k_sess_fb_gather, dim3((nb + 63) / 64), dim3(64), 0, st, s->d_ss, frames_dev, F.d_rec, nb);
     VH_CHECK(hipMemcpyAsync(F.h_rec, F.d_rec, sizeof(SessFbRec) * nb, hipMemcpyDeviceToHost, st));
     VH_CHECK(hipStreamSynchronize(st));  // the host read of the option: once per step
-    int failed[SESS_FB_CHUNK], m = 0;
-    for (int b = 0; b <= nb; b++) {
-        if (b < nb && (F.h_rec[b].flags & 1) && F.h_rec[b].n_cur > 0) failed[m++] = b;  // `fallback and n > 0` (an empty stream is left alone)
-        if (m == 0 || (m < F.chunk && b < nb)) continue;
+    std::vector<int> todo;
+    for (int b = 0; b < nb; b++)
+        if ((F.h_rec[b].flags & 1) && F.h_rec[b].n_cur > 0) todo.push_back(b);  // `fallback and n > 0` (an empty stream is left alone)
+    std::vector<char> served(todo.size(), 0);
+    for (size_t first = 0; first < todo.size(); first++) {
+        if (served[first]) continue;
+        const SessStream& H0 = s->h_ss[todo[first]];
+        const int w = H0.w, h = H0.h, stride = H0.stride;
+        int failed[SESS_FB_CHUNK], m = 0;
+        for (size_t k = first; k < todo.size() && m < F.chunk; k++) {
+            const SessStream& Hk = s->h_ss[todo[k]];
+            if (served[k] || Hk.w != w || Hk.h != h || Hk.stride != stride) continue;
+            served[k] = 1;
+            failed[m++] = todo[k];
+        }
         const uint8_t *im1[SESS_FB_CHUNK], *im2[SESS_FB_CHUNK];
         const float* p1[SESS_FB_CHUNK];
         int n[SESS_FB_CHUNK];
@@ -436,7 +466,7 @@ static int session_recover(vh_session* s, const uint8_t* const* frames_dev, hipS
             const SessFbRec& R = F.h_rec[failed[i]];
             im1[i] = R.im0; im2[i] = R.im; p1[i] = s->h_ss[failed[i]].p_cur; n[i] = R.n_cur;
         }
-        int r = vh_match_affine_batch(F.ctx, m, im1, im2, w, h, w, w, p1, n, &F.params, F.d_M, F.d_inl, nullptr, F.d_info, st);
+        int r = vh_match_affine_batch(F.ctx, m, im1, im2, w, h, stride, stride, p1, n, &F.params, F.d_M, F.d_inl, nullptr, F.d_info, st);
         if (r) return r;
         VH_CHECK(hipMemcpyAsync(F.h_M, F.d_M, sizeof(double) * 6 * m, hipMemcpyDeviceToHost, st));
         VH_CHECK(hipMemcpyAsync(F.h_info, F.d_info, sizeof(int) * 4 * m, hipMemcpyDeviceToHost, st));
@@ -452,12 +482,11 @@ static int session_recover(vh_session* s, const uint8_t* const* frames_dev, hipS
                 // KLTregional(im0, im, p0, T23.T, lk_fine, fbt=0.3): T = float32(T23.T), 3 x 2 row-major (KLT.py:58)
                 const double* M = F.h_M + 6 * i;
                 const float T[6] = {(float)M[0], (float)M[3], (float)M[1], (float)M[4], (float)M[2], (float)M[5]};
-                r = vh_klt_regional(F.ctx, im1[i], im2[i], w, h, w, w, H.p_cur, n[i], T, &s->fine, 0.3f, 0, H.p_all, H.v, nullptr, st);
+                r = vh_klt_regional(F.ctx, im1[i], im2[i], w, h, stride, stride, H.p_cur, n[i], T, &s->fine, 0.3f, 0, H.p_all, H.v, nullptr, st);
                 if (r) return r;
             }
             hipLaunchKernelGGL(k_sess_fb_flags, dim3(1), dim3(64), 0, st, s->d_ss + b2, bits);
         }
-        m = 0;
     }
     SESS_CHECK();
     return 0;
@@ -474,17 +503,53 @@ extern "C" VH_API void vh_session_destroy(vh_session* s)
     delete s;
 }
 
+extern "C" VH_API int vh_session_set_camera(vh_session* s, int slot, int w, int h, const double* K_host, int k_is_float32, void* stream)
+{
+    char msg[200];
+    if (!s) return vh_fail(-1, "vh_session_set_camera: null session");
+    if (slot < 0 || slot >= s->batch) {
+        snprintf(msg, sizeof(msg), "vh_session_set_camera: slot %d is outside the session's %d slots", slot, s->batch);
+        return vh_fail(-1, msg);
+    }
+    if (!K_host) {
+        snprintf(msg, sizeof(msg), "vh_session_set_camera: slot %d: null K_host", slot);
+        return vh_fail(-1, msg);
+    }
+    if (w < 4 || h < 4 || w > s->w || h > s->h) {
+        snprintf(msg, sizeof(msg), "vh_session_set_camera: slot %d: a %d x %d frame is outside what the session holds (4 x 4 up to %d x %d, each side)", slot, w,
+                 h, s->w, s->h);
+        return vh_fail(-1, msg);
+    }
+    VH_BIND(s->ctx, stream);
+    SessCamera cam;
+    for (int k = 0; k < 9; k++) cam.K[k] = K_host[k];
+    cam.w = w; cam.h = h; cam.f32 = k_is_float32 ? 1 : 0;
+    hipLaunchKernelGGL(k_sess_camera, dim3(1), dim3(64), 0, bound_.s, s->d_ss + slot, cam);
+    SESS_CHECK();
+    SessStream& H = s->h_ss[slot];  // the host mirror: what the argument checks and the recovery branch read
+    for (int k = 0; k < 9; k++) { H.K[k] = cam.K[k]; H.pose.K[k] = cam.K[k]; H.msv.K[k] = cam.K[k]; }
+    H.msv.f32_rays = cam.f32;
+    H.w = w; H.h = h; H.stride = w;
+    return 0;
+}
+
 static int session_init(vh_session* s, int slot, const uint8_t* frame0, int stride, const float* p, const double* p3, const uint8_t* vp,
                         const float* t0_host, float time0, float frame_no, float res0, const float* t0_dev, const double* res0_dev, const int* n_dev,
                         void* stream)
 {
-    if (stride != s->w) return vh_fail(-1, "vh_session_init: frames must be dense (stride == width)");
+    SessStream& H = s->h_ss[slot];
+    if (stride < H.w) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "vh_session_init: slot %d: row stride %d is below the slot's frame width %d", slot, stride, H.w);
+        return vh_fail(-1, msg);
+    }
     VH_BIND(s->ctx, stream);
     hipStream_t st = bound_.s;
     hipLaunchKernelGGL(k_sess_init, dim3(1), dim3(256), 0, st, s->d_ss + slot, p, p3, vp, frame0, t0_host ? t0_host[0] : 0.f, t0_host ? t0_host[1] : 0.f,
-                       t0_host ? t0_host[2] : 0.f, time0, frame_no, res0, t0_dev, res0_dev, n_dev);
+                       t0_host ? t0_host[2] : 0.f, time0, frame_no, res0, t0_dev, res0_dev, n_dev, stride);
     // quarter-scale copy of frame 0 = im0_small of the first step (pp starts at 0 -> previous index 1)
-    int r = vh_resize_quarter(s->ctx, frame0, s->w, s->h, stride, s->h_ss[slot].small[1], stream);
+    int r = vh_resize_quarter(s->ctx, frame0, H.w, H.h, stride, H.small[1], stream);
+    H.stride = stride;
     if (r) return r;
     s->h_frame[slot] = 0;  // a (re-)initialised slot starts a new clip: its MSV frame counts from here
     if (s->fb.counts) s->fb.counts[2 * slot] = s->fb.counts[2 * slot + 1] = 0;
@@ -691,7 +756,7 @@ __global__ void k_sess_ingest_jobs(SessStream* ss_all, IngestJob* jobs, const ui
     SessStream& S = ss_all[b];
     IngestJob J;
     J.bgr = bgr[b]; J.gray = gray[b]; J.small = S.small[S.pp];
-    J.w = S.w; J.h = S.h; J.bgr_stride = bgr_stride; J.gray_stride = S.stride;
+    J.w = S.w; J.h = S.h; J.bgr_stride = bgr_stride ? bgr_stride : 3 * S.w; J.gray_stride = S.stride;  // (0: dense rows of this stream's own width)
     J.dw = __double2int_rn(S.w * 0.25); J.dh = __double2int_rn(S.h * 0.25); J.small_stride = J.dw;
     jobs[b] = J;
     if (J.bgr != nullptr) S.small_ready = S.frame_i + 1;
@@ -699,7 +764,12 @@ __global__ void k_sess_ingest_jobs(SessStream* ss_all, IngestJob* jobs, const ui
 
 extern "C" VH_API int vh_session_ingest_bgr(vh_session* s, const uint8_t* const* bgr_frames_dev, int bgr_stride, uint8_t* const* gray_frames_dev, void* stream)
 {
-    if (!s || !bgr_frames_dev || !gray_frames_dev || bgr_stride < 3 * s->w) return vh_fail(-1, "vh_session_ingest_bgr: bad arguments");
+    if (!s || !bgr_frames_dev || !gray_frames_dev || bgr_stride < 0) return vh_fail(-1, "vh_session_ingest_bgr: bad arguments");
+    if (bgr_stride) {  // one stride for every stream: it must cover the widest slot (a session of one camera: 3 x its width, as ever)
+        int mw = 0;
+        for (int b = 0; b < s->batch; b++) mw = s->h_ss[b].w > mw ? s->h_ss[b].w : mw;
+        if (bgr_stride < 3 * mw) return vh_fail(-1, "vh_session_ingest_bgr: bgr_stride is below 3 x the widest slot (0 = dense rows per stream)");
+    }
     VH_BIND(s->ctx, stream);
     hipStream_t st = bound_.s;
     hipLaunchKernelGGL(k_sess_ingest_jobs, dim3((s->batch + 63) / 64), dim3(64), 0, st, s->d_ss, s->d_ingest, bgr_frames_dev, bgr_stride, gray_frames_dev, s->batch);

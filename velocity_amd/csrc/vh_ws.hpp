@@ -68,6 +68,7 @@ struct InitBatchScratch {
     unsigned* cnt;               // per clip: [0] max response (ordered bits), [1] candidate count, [2] corners kept, [3] unused
     int* info;                   // per clip: pose info (iterations, converged)
     void* tab;                   // per-clip descriptors (F0Clip, vh_init.hip), clips_cap rounded up to a whole upload piece
+    void* cam;                   // per-clip cameras (F0Cam: frame size and K), beside tab and as long
     void* shared;                // K and the plate points of the call (F0Shared)
     PoseJob* pose;               // per-clip plate-pose jobs, built on the device
     // max_corners above the in-LDS selection: the selected keys of each clip in a segment of max_corners, sorted by rocPRIM

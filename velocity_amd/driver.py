@@ -1,6 +1,7 @@
 """Device-resident counterpart of the reference's frame loop (vidExample.py:75-171): TrackerSession keeps the track
 state of `batch` video streams on the GPU and advances all of them one frame per step() through vh_session_step.
-Inputs are torch CUDA uint8 frames (dense, H x W); results (P, B, S, masks, points) are read back on demand."""
+Inputs are torch CUDA uint8 frames (dense, H x W; a stream's frame size and intrinsics are its own, up to the session's
+maximum); results (P, B, S, masks, points) are read back on demand."""
 import ctypes as C
 import dataclasses
 import functools
@@ -14,7 +15,8 @@ from . import _lib as L
 
 class TrackerSession:
     def __init__(self, K, width, height, n0, nhist=20, batch=1, lk_coarse=None, lk_fine=None, msv_frame=5, fallback=False, fallback_params=None):
-        """fallback=True (default off: a step queues exactly what it always did): the recovery branch of KLTmain (KLT.py:130-133) for a stream whose coarse
+        """width x height: the LARGEST frame a slot can hold; K: the camera a slot has until init_stream / admit gives it another (vh_session_set_camera).
+        fallback=True (default off: a step queues exactly what it always did): the recovery branch of KLTmain (KLT.py:130-133) for a stream whose coarse
         stage fails -- the affine from feature matching (vh_match_affine_batch over the failed streams; `fallback_params`: _lib.MATCH_DEFAULTS keys)
         drives the fine stage.  It costs ONE host read per step (the failure flags), so the host no longer runs ahead of the device, and such a step cannot
         be captured into a graph: leave it off for clips that do not need it (include/velocity_hip.h, vh_session_set_fallback)."""
@@ -24,7 +26,9 @@ class TrackerSession:
         self.ws = L.Workspace(batch, width, height, n0)
         self.lib = self.ws.lib
         self.K64 = L.host_K(K)
-        k_is_f32 = int(getattr(K, "dtype", None) == np.float32)  # numpy builds fcnMSV1_t's rays in float32 then (utils/MSV.py:15-17)
+        k_is_f32 = L.k_is_float32(K)  # numpy builds fcnMSV1_t's rays in float32 then (utils/MSV.py:15-17)
+        self._cam0 = (width, height, self.K64.tobytes(), k_is_f32)
+        self._cam = [self._cam0] * batch  # host mirror of every slot's camera: (w, h, K bytes, K is float32)
         self.lkc = L.lk_params(dict(L.LK_COARSE, **(lk_coarse or {})))
         self.lkf = L.lk_params(dict(L.LK_FINE, **(lk_fine or {})))
         h = C.c_void_p()
@@ -41,12 +45,30 @@ class TrackerSession:
         self._keep = [None] * batch
         self._init_keep = [None] * batch
 
-    def init_stream(self, slot, frame0, p, p3, vp, t0, time0=0.0, frame_no=0.0, res0=0.0):
+    def slot_size(self, slot):
+        """(H, W) of the frames slot `slot` takes."""
+        return self._cam[slot][1], self._cam[slot][0]
+
+    def _set_camera(self, slot, w, h, K):
+        """The slot's frame size and intrinsics (K None: the session's) for its next initialisation: vh_session_set_camera, stream-ordered, and only when
+        they differ from what the slot has -- a session of one camera never makes the call."""
+        cam = self._cam0[2:] if K is None else (L.host_K(K).tobytes(), L.k_is_float32(K))
+        cam = (int(w), int(h)) + cam
+        if cam != self._cam[slot]:
+            K64 = np.frombuffer(cam[2], np.float64)
+            L.check(self.lib.vh_session_set_camera(self.handle, slot, cam[0], cam[1], K64.ctypes.data_as(L.f64p), cam[3], L.stream_ptr()), "vh_session_set_camera")
+            self._cam[slot] = cam
+
+    def init_stream(self, slot, frame0, p, p3, vp, t0, time0=0.0, frame_no=0.0, res0=0.0, K=None):
         """Frame-0 state (vidExample.py:116-131): points p [n0,2], world points p3 [n0,3], pose mask vp, plate pose t0.  numpy arrays or CUDA tensors
-        (tensors of the right dtype are used in place: a stream can be re-initialised without touching the host)."""
+        (tensors of the right dtype are used in place: a stream can be re-initialised without touching the host).  The slot takes its frame size from
+        frame0.shape (at most the session's) and its intrinsics from K (None: the session's)."""
         torch = self.torch
         f0 = _to_device([frame0])[0]
-        assert f0.shape == (self.h, self.w) and f0.dtype == torch.uint8
+        assert f0.dim() == 2 and f0.dtype == torch.uint8
+        fh, fw = f0.shape
+        if fw > self.w or fh > self.h:
+            raise ValueError(f"init_stream: slot {slot}: a {fw} x {fh} frame does not fit the session's {self.w} x {self.h}")
 
         def dev(a, np_dtype, t_dtype):
             return L.to_dev(a if isinstance(a, torch.Tensor) else np.asarray(a).astype(np_dtype), t_dtype)
@@ -54,42 +76,52 @@ class TrackerSession:
         pd, p3d, vpd = dev(p, np.float32, torch.float32), dev(p3, np.float64, torch.float64), dev(vp, np.uint8, torch.uint8)
         assert pd.shape == (self.n0, 2) and p3d.shape == (self.n0, 3) and vpd.shape == (self.n0,)
         t0 = np.ascontiguousarray(np.asarray(t0, np.float32).reshape(3))
-        L.check(self.lib.vh_session_init(self.handle, slot, L.dptr(f0), self.w, L.dptr(pd), L.dptr(p3d), L.dptr(vpd), t0.ctypes.data_as(L.f32p),
+        self._set_camera(slot, fw, fh, K)
+        L.check(self.lib.vh_session_init(self.handle, slot, L.dptr(f0), fw, L.dptr(pd), L.dptr(p3d), L.dptr(vpd), t0.ctypes.data_as(L.f32p),
                                          float(time0), float(frame_no), float(res0), L.stream_ptr()), "vh_session_init")
         self._keep[slot], self._init_keep[slot] = f0, (pd, p3d, vpd)
 
     def admit(self, entries, settings):
         """THE admission (vidExample.py:105-131 for each clip): frame 0 of every entry computed and installed on the device, on the current stream.
-        entries = [(slot, frame0, q, time0, frame_no0), ...]: frame0 a dense CUDA uint8 [H, W] tensor, q the clicked plate corners [4, 2]; settings: a
-        Frame0Settings whose .cap is this session's track capacity.  ONE frame-0 batch call for all entries, in the given order, then one
-        vh_session_init_dev per entry, fed by the batch's device outputs (count included: nothing is read back).  The session keeps each slot's frame
+        entries = [(slot, frame0, q, time0, frame_no0[, K]), ...]: frame0 a dense CUDA uint8 [H, W] tensor (the slot takes its size: at most the
+        session's), q the clicked plate corners [4, 2], K the clip's intrinsics (absent / None: the session's); settings: a Frame0Settings whose .cap
+        is this session's track capacity.  ONE frame-0 batch call for all entries, in the given order (vh_frame0_init_batch3 when their cameras differ
+        from the session's), then per entry vh_session_set_camera (only for a slot whose camera changes) and one vh_session_init_dev, fed by the batch's device outputs (count included: nothing is read back).  The session keeps each slot's frame
         and its rows of those outputs alive until the slot is initialised again.  Returns one Admitted per entry: the frame-0 facts a result needs and
         the stream's state does not hold."""
         assert settings.cap == self.n0, "the session's track capacity must be 4 + max_corners"
-        assert all(e[1].is_cuda and e[1].dtype == self.torch.uint8 and e[1].shape == (self.h, self.w) and e[1].is_contiguous() for e in entries)
+        assert all(e[1].is_cuda and e[1].dtype == self.torch.uint8 and e[1].dim() == 2 and e[1].is_contiguous() for e in entries)
+        Ks = [e[5] if len(e) > 5 else None for e in entries]
+        for (slot, f0, *_), _K in zip(entries, Ks):
+            if f0.shape[1] > self.w or f0.shape[0] > self.h:
+                raise ValueError(f"admit: slot {slot}: a {f0.shape[1]} x {f0.shape[0]} frame does not fit the session's {self.w} x {self.h}")
         bufs = settings.outputs(len(entries))
-        rois = _frame0_batch_call(self.ws, [e[1] for e in entries], [e[2] for e in entries], self.K64, settings, bufs)
+        if all(K is None and e[1].shape == (self.h, self.w) for e, K in zip(entries, Ks)):  # the session's own camera throughout
+            rois = _frame0_batch_call(self.ws, [e[1] for e in entries], [e[2] for e in entries], self.K64, settings, bufs)
+        else:
+            rois = _frame0_batch3_call(self.ws, [e[1] for e in entries], [e[2] for e in entries], [self.K64 if K is None else K for K in Ks], settings, bufs)
         out = []
-        for a, (slot, f0, _, time0, frame_no0) in enumerate(entries):
+        for a, ((slot, f0, _, time0, frame_no0, *_), K) in enumerate(zip(entries, Ks)):
             p, p3, vp, t0, R0, res0, n0 = rows = tuple(x[a:a + 1] for x in bufs)
-            L.check(self.lib.vh_session_init_dev(self.handle, slot, L.dptr(f0), self.w, L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
+            self._set_camera(slot, f0.shape[1], f0.shape[0], K)
+            L.check(self.lib.vh_session_init_dev(self.handle, slot, L.dptr(f0), f0.shape[1], L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
                                                  float(time0), float(frame_no0), L.stream_ptr()), "vh_session_init_dev")
             self._keep[slot], self._init_keep[slot] = f0, rows
             out.append(Admitted(tuple(rois[8 * a:8 * a + 4]), tuple(rois[8 * a + 4:8 * a + 8]), R0[0], res0))
         return out
 
     def set_frames(self, frames):
-        """frames: list of `batch` CUDA uint8 [H,W] tensors (kept alive until the next call replaces them); a None entry is a stream that sits the step
+        """frames: list of `batch` CUDA uint8 [H,W] tensors, each of its slot's size (kept alive until the next call replaces them); a None entry is a stream that sits the step
         out: its table entry is a null pointer and the frame of its last active step stays alive (it is the im0 of its next active one).
         -> None when every stream has a frame, else the host mask uint8 [batch] of the active streams."""
         torch = self.torch
         assert len(frames) == self.batch
         ptrs = []
-        for f in frames:
+        for b, f in enumerate(frames):
             if f is None:
                 ptrs.append(0)
                 continue
-            assert f.is_cuda and f.dtype == torch.uint8 and f.shape == (self.h, self.w) and f.is_contiguous()
+            assert f.is_cuda and f.dtype == torch.uint8 and f.shape == self.slot_size(b) and f.is_contiguous()
             ptrs.append(f.data_ptr())
         self._prev_keep = self._keep
         self._keep = [k if f is None else f for f, k in zip(frames, self._keep)]
@@ -134,10 +166,10 @@ class TrackerSession:
     def step_bgr(self, frames_bgr, time_s=0.0, frame_no=0.0):
         """One frame for every stream straight from BGR frames (the decoder's output, vidExample.py:89-91): the fused ingest writes the gray frames
         and the quarter-scale images in one pass (vh_session_ingest_bgr), then the step runs on them.  frames_bgr: list of `batch` CUDA uint8 [H,W,3]
-        tensors.  The session owns two sets of gray buffers (a frame is read by two steps: as `im`, then as `im0`).
+        tensors, each of its slot's size.  The session owns two sets of gray buffers (a frame is read by two steps: as `im`, then as `im0`).
         A None entry is a stream that sits the step out, as in step(): nothing of it is ingested, and its gray frame of its last active step is kept (each
         stream alternates between its two buffers on its own active steps).  Returns the gray frames of the step: the [batch, H, W] buffer, or with idle
-        streams a list with None in their places."""
+        streams -- or with slots of other sizes than the session's -- a list (None for an idle stream, else the slot's [H_b, W_b] gray frame)."""
         torch = self.torch
         assert len(frames_bgr) == self.batch
         if getattr(self, "_gray", None) is None:
@@ -146,21 +178,24 @@ class TrackerSession:
             self._gray_i = 0
             self._gray_k = [0] * self.batch  # per stream: the buffer its next active step writes
         ptrs = []
-        for f in frames_bgr:
+        for b, f in enumerate(frames_bgr):
             if f is None:
                 ptrs.append(0)
                 continue
-            assert f.is_cuda and f.dtype == torch.uint8 and f.shape == (self.h, self.w, 3) and f.is_contiguous()
+            assert f.is_cuda and f.dtype == torch.uint8 and f.shape == self.slot_size(b) + (3,) and f.is_contiguous()
             ptrs.append(f.data_ptr())
+        sizes = [self.slot_size(b) for b in range(self.batch)]
+        mixed = any(sz != (self.h, self.w) for sz in sizes)  # a slot's dense gray frame is the front of its (maximum-sized) buffer
+        bgr_stride = 0 if mixed else 3 * self.w  # 0: dense rows of every stream's own width
         self._bgr_keep = list(frames_bgr)
         bgr_tab = torch.tensor(ptrs, dtype=torch.int64).cuda()
         self._bgr_tab_keep = bgr_tab
-        if not all(ptrs) or len(set(self._gray_k)) > 1:  # some stream is idle now, or was: the streams no longer alternate in step
+        if mixed or not all(ptrs) or len(set(self._gray_k)) > 1:  # some stream is idle now, or was: the streams no longer alternate in step
             ks = self._gray_k
-            gray = [None if not q else self._gray[ks[b]][b] for b, q in enumerate(ptrs)]
+            gray = [None if not q else self._gray[ks[b]][b].reshape(-1)[: sizes[b][0] * sizes[b][1]].view(sizes[b]) for b, q in enumerate(ptrs)]
             gtab = torch.tensor([0 if g is None else g.data_ptr() for g in gray], dtype=torch.int64).cuda()
             self._gray_k = [k ^ 1 if q else k for k, q in zip(ks, ptrs)]
-            L.check(self.lib.vh_session_ingest_bgr(self.handle, L.dptr(bgr_tab), 3 * self.w, L.dptr(gtab), L.stream_ptr()), "vh_session_ingest_bgr")
+            L.check(self.lib.vh_session_ingest_bgr(self.handle, L.dptr(bgr_tab), bgr_stride, L.dptr(gtab), L.stream_ptr()), "vh_session_ingest_bgr")
             self._gray_tab_keep = gtab
             self.step(frames_table=gtab, time_s=time_s, frame_no=frame_no, active=np.array([1 if q else 0 for q in ptrs], np.uint8))
             return gray
@@ -459,6 +494,22 @@ def _frame0_batch_call(ws, frames0, qs, K64, settings, bufs):
     return list(rois)
 
 
+def _frame0_batch3_call(ws, frames0, qs, Ks, settings, bufs):
+    """vh_frame0_init_batch3 on the current stream: dense CUDA [H_b, W_b] frames of any sizes, their plate corners and their intrinsics (one K per clip).
+    -> host list of nb x 8 ROIs (boxa, boxb)."""
+    s, lib, nb = settings, ws.lib, len(frames0)
+    q = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 2) for x in qs]))
+    ptrs = (C.c_void_p * nb)(*[f.data_ptr() for f in frames0])
+    cams = (L.ClipCamera * nb)(*[L.clip_camera(f.shape[1], f.shape[0], K) for f, K in zip(frames0, Ks)])
+    rois = (C.c_int * (8 * nb))()
+    win, it, eps = s.subpix
+    L.check(lib.vh_frame0_init_batch3(ws.handle, nb, C.cast(ptrs, C.c_void_p), cams, q.ctypes.data_as(L.f32p), s.plate_w.ctypes.data_as(L.f64p),
+                                      int(s.roi_border[0]), int(s.roi_border[1]), int(s.max_corners), float(s.quality), int(s.block), float(s.harris_k),
+                                      1 if s.use_harris else 0, float(s.min_distance), int(win), int(it), float(eps), *[L.dptr(x) for x in bufs], rois,
+                                      L.stream_ptr()), "vh_frame0_init_batch3")
+    return list(rois)
+
+
 def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
                  use_harris=True, min_distance=0.0):
     """Frame 0 of many clips at once (vidExample.py:105-127 for each): `frames` = the clips' first frames (numpy / torch uint8 [H, W] of one size, or one
@@ -636,8 +687,10 @@ class _SessionSet:
 
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
                   msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
-    """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name]) of ONE frame size and
-    length; every clip is a stream of a device-resident TrackerSession, so a frame step is one launch sequence for all the clips of a session
+    """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name, K]) of ONE length -- the
+    frame size and the intrinsics are each clip's own ("K": that clip's camera, default the K argument); the sessions are created at the elementwise
+    maximum of the sizes and a frame step is sized for it, so clips of one camera type batch best.  One length stays required: a step advances every
+    stream, and clips of other lengths belong to run_queue.  Every clip is a stream of a device-resident TrackerSession, so a frame step is one launch sequence for all the clips of a session
     (vh_session_step_v: each stream has its own clock).  `sessions`: the clips are split into this many sessions, each on its own HIP stream (0 = auto,
     session_groups(len(clips)): their one-workgroup-per-stream stages overlap the others' LK launches); results do not depend on it.  Frame 0 of the clips
     of a session is ONE TrackerSession.admit (one frame-0 batch call on the device, its outputs feed vh_session_init_dev directly); nothing is read back
@@ -652,8 +705,9 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     assert nclip >= 1
     n = len(clips[0]["frames"])
     dev = [_to_device(c["frames"]) for c in clips]
-    H, W = dev[0][0].shape
-    assert all(len(d) == n and d[0].shape == (H, W) for d in dev), "clips must share frame size and length"
+    assert all(len(d) == n for d in dev), "clips must share one length (run_queue takes clips of any length)"
+    assert all(f.shape == d[0].shape for d in dev for f in d), "the frames of a clip must share one size"
+    H, W = max(d[0].shape[0] for d in dev), max(d[0].shape[1] for d in dev)
     group = _SessionSet(nclip, sessions, max_corners)
     for hs in group.hip_streams[1:]:
         hs.wait_stream(group.hip_streams[0])  # the frame uploads above ran on the current stream
@@ -667,7 +721,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
         with torch.cuda.stream(hs):
             f0_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
             f0_events[-1][0].record()
-            f0 += ses.admit([(j, dev[b][0], clips[b]["q"], times[b, 0], fnos[b, 0]) for j, b in enumerate(mem)], settings)
+            f0 += ses.admit([(j, dev[b][0], clips[b]["q"], times[b, 0], fnos[b, 0], clips[b].get("K")) for j, b in enumerate(mem)], settings)
             f0_events[-1][1].record()
     t_loop = _time.perf_counter()
     for i in range(1, n):
@@ -729,6 +783,16 @@ def _queue_steps(next_length, sizes):
         yield dict(admit=admit, frames=frames, done=done)
 
 
+def queue_clip_fits(index, shape, max_size):
+    """run_queue's size rule (a pure function: no device): clip `index` with frames of `shape` = (H, W) fits sessions created for max_size = (H, W) iff
+    each side does -- a portrait frame does not fit a landscape session of the same area.  Raises the ValueError run_queue raises, else returns shape."""
+    h, w = int(shape[0]), int(shape[1])
+    mh, mw = int(max_size[0]), int(max_size[1])
+    if h > mh or w > mw:
+        raise ValueError(f"run_queue: clip {index} has {w} x {h} frames, larger than max_size = {mw} x {mh} (W x H)")
+    return h, w
+
+
 def queue_plan(lengths, streams, sessions=1):
     """The whole schedule run_queue follows for clips of these lengths (a pure function: no device): the list of the steps of _queue_steps.  Greedy and
     FIFO: at every global step each free slot takes the next waiting clip, in (session, slot) order; a clip of n frames is admitted (frame 0) and tracked
@@ -738,13 +802,16 @@ def queue_plan(lengths, streams, sessions=1):
     return list(_queue_steps(lambda: next(it, None), _slot_split(int(streams), sessions)))
 
 
-def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
+def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, max_size=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
               harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=None, use_harris=True, min_distance=0.0, fallback=False,
               fallback_params=None):
     """A queue of clips of ANY length on `streams` resident streams: what run_sequences is for clips of one length.  `clips` = any iterable of
-    dict(frames, q, times[, frame_numbers, name]) of ONE frame size, each of >= 2 frames; it is consumed lazily -- a clip is pulled when a slot is free
+    dict(frames, q, times[, frame_numbers, name, K]), each of >= 2 frames and with its own frame size and intrinsics ("K": default the K argument); it is consumed lazily -- a clip is pulled when a slot is free
     for it and its frames go up then, so at most `streams` clips are resident -- and may hold more clips than fit on the device at once.
     max_frames   the sessions' history length: no clip may be longer (ValueError when it is admitted); required unless `clips` is a list.
+    max_size     (H, W) of the largest frame a clip may have: the size the sessions (and the frame-0 scratch) are created for.  Without it they take the
+                 size of the first clip pulled.  A later clip that does not fit (queue_clip_fits) raises ValueError naming the clip and both sizes --
+                 before any of its frames goes up or anything is queued for it; the clips already resident run to their end and are delivered first.
     sessions     the slots are split over this many TrackerSessions, each on its own HIP stream (0 = auto, session_groups(streams)); results do not
                  depend on it.
     The schedule is queue_plan's: one shared FIFO; at every global step each free slot takes the next clip, all admissions of a session are ONE
@@ -770,7 +837,8 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
     main, upload = group.hip_streams[0], _upload_stream()
     source = iter(clips)
     pulled = {}          # clip index -> the clip as its slot uses it (dropped when the clip is done)
-    size = [None]
+    size = [None if max_size is None else (int(max_size[0]), int(max_size[1]))]  # (H, W) the sessions are created for
+    misfit = []          # the ValueError of a clip that does not fit: the queue ends there, the resident clips are finished and delivered, then it is raised
 
     def next_length():
         c = next(source, None)
@@ -781,12 +849,18 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
         if n > nhist:
             raise ValueError(f"run_queue: clip {k} has {n} frames, more than max_frames = {nhist}")
         if n >= 2:
+            shape = tuple(c["frames"][0].shape)
+            size[0] = size[0] or shape
+            try:
+                queue_clip_fits(k, shape, size[0])
+            except ValueError as e:
+                misfit.append(e)
+                return None
             host = [f for f in c["frames"] if not (isinstance(f, torch.Tensor) and f.is_cuda)]
             with torch.cuda.stream(upload if host else main):  # (host frames: an upload that waits for nothing the sessions have queued)
                 dev = _to_device(c["frames"], non_blocking=True)
-            size[0] = size[0] or tuple(dev[0].shape)
-            assert all(d.shape == size[0] and d.dtype == torch.uint8 for d in dev), "clips must share one frame size"
-            pulled[k] = dict(dev=dev, uploaded=bool(host), q=c["q"], times=np.asarray(c["times"], np.float32),
+            assert all(d.shape == shape and d.dtype == torch.uint8 for d in dev), "the frames of a clip must share one size"
+            pulled[k] = dict(dev=dev, uploaded=bool(host), q=c["q"], K=c.get("K"), times=np.asarray(c["times"], np.float32),
                              fnos=np.asarray(c.get("frame_numbers", np.arange(n)), np.float32), frame_numbers=c.get("frame_numbers", list(range(n))),
                              name=c.get("name", f"clip {k}"), n=n)
         next_length.count += 1
@@ -819,7 +893,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
     idle_slots = steps = 0
     for step in _queue_steps(next_length, group.sizes):
         poll()
-        if not sess:  # the first clips have been pulled: the frame size is known
+        if not sess:  # the first clips have been pulled: the (largest) frame size is known
             H, W = size[0]
             group.create(K, W, H, settings, nhist, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params)
             for ses, hs in zip(sess, group.hip_streams):
@@ -842,7 +916,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
                     ev0 = torch.cuda.Event(enable_timing=True)
                     ev1 = torch.cuda.Event(enable_timing=True)
                     ev0.record()
-                    f0s = ses.admit([(j, c["dev"][0], c["q"], c["times"][0], c["fnos"][0]) for j, c in adm], settings)
+                    f0s = ses.admit([(j, c["dev"][0], c["q"], c["times"][0], c["fnos"][0], c["K"]) for j, c in adm], settings)
                     for (j, _), f0 in zip(adm, f0s):
                         held[g][j] = (f0, _time.perf_counter())
                     ev1.record()
@@ -884,6 +958,8 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, pl
     seconds = _time.perf_counter() - t_begin
     run_queue.last_stats = dict(steps=steps, sessions=G, mean_idle_slots=idle_slots / max(steps, 1), seconds=seconds,
                                 admission_ms=float(sum(a.elapsed_time(b) for a, b in t_admit)), admissions=len(t_admit))
+    if misfit:
+        raise misfit[0]
     return [results[k] for k in range(next_length.count)]
 
 
