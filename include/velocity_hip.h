@@ -176,6 +176,19 @@ VH_API int vh_nls_batch(vh_ctx* ctx, const double* K_host, const double* z, doub
 VH_API int vh_nls_batch_multi(vh_ctx* ctx, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, int max_iter,
                               double* trace, int* info, void* workspace, size_t workspace_bytes_per_window, void* stream);
 
+/* vh_nls_batch_multi for windows that keep DIFFERENT numbers of full-length tracks (NLS.py:190: tracks die on each stream's own gates) and have
+ * different cameras, still one launch sequence.  nt_win_dev: device int[nwin], 0 <= nt_w <= nt (NULL: nt for every window);  K_win_dev: device
+ * double[nwin][9], row-major (NULL: K_host for every window).  Both tables are read on the device when the kernels run: no count comes back to
+ * the host, so a kernel queued earlier on the stream may write them.  Every window is laid out for the common nt (the strides of the multi call);
+ * rows i >= nt_w of a window are padding, for which the caller gives NaN measurements (z) and any finite point (x).  An unobserved point has zero
+ * residual and zero Jacobian rows, so its block of the normal equations is the bare +I damping: it adds exact zeros to the window's reduced camera
+ * system, its own step is zero (its rows of x come back byte for byte), and only the two rms divisors nx = 3 nt_w + 6 nc, nz = 2 nt_w (nc + 1) are
+ * taken from the true count.  Window w therefore takes the steps vh_nls_batch takes on its first nt_w tracks with its own K, up to the order of
+ * the partial sums.  A window with nt_w = 0 is not solved: info {0, 0}, x untouched.  With both tables NULL this is vh_nls_batch_multi, bit for bit. */
+VH_API int vh_nls_batch_windows(vh_ctx* ctx, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
+                                const double* K_win_dev, int max_iter, double* trace, int* info, void* workspace,
+                                size_t workspace_bytes_per_window, void* stream);
+
 /* fcnNLS_batch2(K, P, pw, cw), utils/NLS.py:253-328: the constrained sibling -- tie points, ONE joint rotation applied to the
  * points and a straight-line camera trajectory (elevation, azimuth, one range per camera 1..nc; camera 0 at the origin).
  * Same z packing, damping (+I), step (0.9) and stop rule (rms(delta) < 1e-7); the reference runs at most 20 iterations.
@@ -447,6 +460,37 @@ typedef struct {
 VH_API size_t vh_session_export_size(const vh_session* s, vh_session_record* layout_host);
 /* packs stream `slot` into rec_dev (device memory, vh_session_export_size bytes, 8-byte aligned) on `stream`: one launch, no scratch, no wait */
 VH_API int vh_session_export(vh_session* s, int slot, void* rec_dev, void* stream);
+
+/* Bundle adjustment of finished clips, straight from the session (default OFF: nothing calls it unless asked).  The refinement the reference's author
+ * sketched at vidExample.py:157 -- fcnNLS_batch(K, P[:, :, 0:i], p3, B[0:i, 3:6]), utils/NLS.py:186-250 -- for slots whose clips have had all their nf
+ * frames (frame counter nf - 1): tracks = the slot's surviving tracks (vh_session_view::ids, the tracks NLS.py:190 keeps: ascending id), z from the
+ * float32 history (NLS.py:198-199), x0 = [p3[ids] | B[1:nf, 3:6] | 0] (NLS.py:202-203), K the slot's own.  The slots of one call are the windows of ONE
+ * vh_nls_batch_windows launch sequence (nt = n0, nc = nf - 1): their track counts and cameras may differ, their nf may not (other lengths: another
+ * call).  One record per slot, byte offsets as in vh_session_record: */
+typedef struct {
+    size_t bytes;                               /* size of a record (a multiple of 8)                                         */
+    size_t nt, iterations, converged;           /* int32 each: tracks solved, LM iterations taken, rms(delta) < 1e-7 reached   */
+    size_t ids;                                 /* int32[n0]        rows [0, nt) global track ids, -1 behind them             */
+    size_t pw;                                  /* float64[n0][3]   rows [0, nt) refined world points, NaN behind them        */
+    size_t cw;                                  /* float64[nhist][3] refined camera positions: row 0 zero, rows >= nf NaN     */
+    size_t dr, speed;                           /* float64[nhist]   dr_i = |cw_i - cw_(i-1)|, speed_i = dr_i / (B[i,12] - B[i-1,12]) * 3.6 with the float32
+                                                                    time difference of vidExample.py:142; entry 0 and entries >= nf NaN */
+    size_t speed_mean, speed_std;               /* float64: mean and (population) std of speed[1:nf] (vidExample.py:177)      */
+    size_t f_first, f_last;                     /* float64: rms residual (pixels) of the first and of the last iteration, NaN when none ran */
+    size_t trace;                               /* float64[max_iter][2] rms(z - zhat), rms(delta) per iteration, 0 behind them */
+    int n0, nhist, max_iter;
+} vh_refine_record;
+/* size in bytes of a record for max_iter iterations (0 and vh_last_error on bad arguments); layout_host (may be NULL) receives the offsets */
+VH_API size_t vh_session_refine_size(const vh_session* s, int max_iter, vh_refine_record* layout_host);
+/* bytes of device scratch a vh_session_refine call of nslots slots and nf frames needs (0 and vh_last_error on bad arguments) */
+VH_API size_t vh_session_refine_workspace(const vh_session* s, int nslots, int nf);
+/* Queues kernels only -- pack, the BA launch sequence, unpack -- on `stream`: no allocation, no host wait, legal between two steps.  It reads the
+ * session and writes nothing of it: every stream steps on as if the call had not happened.  recs_dev: nslots records (8-byte aligned), in the order
+ * of slots_host.  A slot without a surviving track is not solved: iterations 0, converged 0, cw = B[0:nf, 3:6].  Returns -1 with vh_last_error
+ * naming the slot and the limit, and nothing queued, for: a slot outside the session or given twice, nf < 2, nf - 1 > 255 (the BA's camera limit),
+ * nf > nhist, a slot whose frame counter is not nf - 1, max_iter < 1, a workspace below vh_session_refine_workspace(s, nslots, nf). */
+VH_API int vh_session_refine(vh_session* s, const int* slots_host, int nslots, int nf, int max_iter, void* recs_dev, void* workspace,
+                             size_t workspace_bytes, void* stream);
 VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
 /* (vh_version >= 109) the recovery branch of KLTmain (utils/KLT.py:130-133) inside the session; default OFF: a step then queues exactly the launches it
  * always did and a stream whose coarse stage fails reports klt_flags & 1 and goes on with what the blind fine stage kept.

@@ -124,43 +124,72 @@ def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False):
     return cw_out, pw_out
 
 
-def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False):
-    """fcnNLS_batch (utils/NLS.py:186-250) for several independent windows of the SAME shape (one sliding window per video stream)
-    in one launch sequence (vh_nls_batch_multi, grid.y = window).  Ps / pws / cws: sequences of the reference's P, pw, cw arguments;
-    every window must keep the same number of full-length tracks and frames.  Returns [(cw, pw), ...] (with return_info: also x, trace)."""
-    torch = L.torch_cuda()
-    zs, xs, shape = [], [], None
+def pack_windows(Ps, pws, cws):
+    """Track filter and packing of fcnNLS_batch (utils/NLS.py:190-203) for several windows of one number of frames, laid out for the largest track
+    count nt: z [nw, 2 nt nf] and x0 [nw, 3 nt + 6 nc] in the layout of vh_nls_batch_multi, counts int32[nw].  Rows behind a window's own count
+    are padding: NaN measurements (no observation, see k_ba_jac) and the point (0, 0, 1).  Host only."""
+    zs, pts, cams, nf0 = [], [], [], None
     for P, pw, cw in zip(Ps, pws, cws):
         P, pw, cw = np.asarray(P), np.asarray(pw, np.float64), np.asarray(cw, np.float64)
         keep = np.isfinite(P[4]).sum(1) == P.shape[2]  # NLS.py:190
         P, pw = P[:, keep], pw[keep]
-        _, nt, nf = P.shape
-        if shape is None:
-            shape = (nt, nf)
-        elif shape != (nt, nf):
-            raise ValueError(f"fcnNLS_batch_windows: window shapes differ ({shape} vs {(nt, nf)})")
-        z = np.concatenate([P[0].T.reshape(-1), P[1].T.reshape(-1)]).astype(np.float64)  # NLS.py:198-199 (NaN = no observation: kept, see k_ba_jac)
-        zs.append(z)
-        xs.append(np.concatenate((pw, cw[1:], np.zeros((nf - 1, 3)))).reshape(-1))  # NLS.py:202-203
-    nt, nf = shape
-    nc, nw = nf - 1, len(zs)
-    K64 = L.host_K(K)
-    zd = L.to_dev(np.stack(zs), torch.float64)
-    xd = L.to_dev(np.stack(xs), torch.float64).clone()
+        nf = P.shape[2]
+        if nf0 is None:
+            nf0 = nf
+        elif nf0 != nf:
+            raise ValueError(f"fcnNLS_batch_windows: window shapes differ ({nf0} vs {nf} frames)")
+        zs.append(P[0:2].astype(np.float64))  # [2, nt_w, nf] (NaN = no observation: kept)
+        pts.append(pw)
+        cams.append(np.concatenate((cw[1:], np.zeros((nf - 1, 3)))).reshape(-1))  # NLS.py:202-203
+    nf, nw = nf0, len(zs)
+    nc = nf - 1
+    counts = np.array([len(p) for p in pts], np.int32)
+    nt = max(1, int(counts.max()))
+    z = np.full((nw, 2, nf, nt), np.nan)  # NLS.py:198-199: [all u | all v], camera-major / track-minor
+    x0 = np.empty((nw, 3 * nt + 6 * nc))
+    for w in range(nw):
+        z[w, :, :, : counts[w]] = zs[w].transpose(0, 2, 1)
+        x0[w] = np.concatenate((pts[w].reshape(-1), np.tile([0.0, 0.0, 1.0], nt - counts[w]), cams[w]))
+    return z.reshape(nw, -1), x0, counts, nt, nc
+
+
+def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False):
+    """fcnNLS_batch (utils/NLS.py:186-250) for several independent windows of the same number of frames (one finished clip or sliding window per
+    video stream) in one launch sequence (grid.y = window).  Ps / pws / cws: sequences of the reference's P, pw, cw arguments.  K: one 3x3 matrix
+    for all windows, or one per window ([nw, 3, 3]).  The windows may keep different numbers of full-length tracks: pack_windows lays them out for
+    the largest count and pads with unobserved points, which take no part in the solve (vh_nls_batch_windows); windows of equal counts and one K
+    go through vh_nls_batch_multi unchanged.  A window without a full-length track is not solved (cw comes back as given).  Returns
+    [(cw, pw), ...], pw cut to the window's own tracks (with return_info: also the padded x and the trace)."""
+    torch = L.torch_cuda()
+    z, x0, counts, nt, nc = pack_windows(Ps, pws, cws)
+    nw = len(counts)
+    K64 = np.asarray(K, np.float64)
+    per_window_K = K64.ndim == 3
+    if per_window_K and len(K64) != nw:
+        raise ValueError(f"fcnNLS_batch_windows: {len(K64)} intrinsics for {nw} windows")
+    zd = L.to_dev(z, torch.float64)
+    xd = L.to_dev(x0, torch.float64).clone()
     trace = torch.zeros((nw, max_iter, 2), dtype=torch.float64, device="cuda")
     info = torch.zeros((nw, 2), dtype=torch.int32, device="cuda")
     ws = L.workspace()
     nbytes = int(ws.lib.vh_nls_batch_workspace(nt, nc))
     scratch = _scratch(torch, (nw, nbytes))
-    L.check(ws.lib.vh_nls_batch_multi(ws.handle, K64.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, nw, int(max_iter), L.dptr(trace),
-                                      L.dptr(info), L.dptr(scratch), nbytes, L.stream_ptr()), "vh_nls_batch_multi")
+    K_host = L.host_K(K64[0] if per_window_K else K64)
+    if per_window_K or (counts != nt).any():
+        ntd = L.to_dev(counts, torch.int32)
+        Kd = L.to_dev(K64.reshape(nw, 9), torch.float64) if per_window_K else None
+        L.check(ws.lib.vh_nls_batch_windows(ws.handle, K_host.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, nw, L.dptr(ntd), L.dptr(Kd),
+                                            int(max_iter), L.dptr(trace), L.dptr(info), L.dptr(scratch), nbytes, L.stream_ptr()), "vh_nls_batch_windows")
+    else:
+        L.check(ws.lib.vh_nls_batch_multi(ws.handle, K_host.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, nw, int(max_iter), L.dptr(trace),
+                                          L.dptr(info), L.dptr(scratch), nbytes, L.stream_ptr()), "vh_nls_batch_multi")
     info, x, tr = info.cpu().numpy(), xd.cpu().numpy(), trace.cpu().numpy()
     out = []
     for w in range(nw):
-        if not info[w, 1]:
+        if not info[w, 1] and counts[w]:
             print("WARNING: fcnNLS_batch() reaching max iterations!")  # NLS.py:242
         j = nt * 3
-        pw_out = x[w, :j].reshape(nt, 3)
+        pw_out = x[w, : 3 * counts[w]].reshape(-1, 3)
         cw_out = np.concatenate((np.zeros((1, 3)), x[w, j : j + nc * 3].reshape(nc, 3)), 0)
         out.append((cw_out, pw_out, x[w], tr[w, : info[w, 0]]) if return_info else (cw_out, pw_out))
     return out

@@ -41,6 +41,13 @@ class SessionRecord(C.Structure):
                                           "P")] + [("n0", C.c_int), ("nhist", C.c_int)]
 
 
+class RefineRecord(C.Structure):
+    """vh_refine_record: byte offsets of the fields of a refined clip's record (vh_session_refine)."""
+
+    _fields_ = [(k, C.c_size_t) for k in ("bytes", "nt", "iterations", "converged", "ids", "pw", "cw", "dr", "speed", "speed_mean", "speed_std", "f_first",
+                                          "f_last", "trace")] + [("n0", C.c_int), ("nhist", C.c_int), ("max_iter", C.c_int)]
+
+
 class MatchParams(C.Structure):
     """vh_match_params (defaults: MATCH_DEFAULTS)."""
 
@@ -98,6 +105,7 @@ _SIGS = {
     "vh_ba_graph_replay": (C.c_int, [vp, C.c_int]),
     "vh_nls_batch": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_nls_batch_multi": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]),
+    "vh_nls_batch_windows": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_nls_batch2": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_good_features": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, vp, vp, vp]),
     "vh_corner_subpix": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp]),
@@ -112,6 +120,9 @@ _SIGS = {
     "vh_session_step_some": (C.c_int, [vp, vp, vp, vp, vp, vp]),
     "vh_session_export_size": (C.c_size_t, [vp, C.POINTER(SessionRecord)]),
     "vh_session_export": (C.c_int, [vp, C.c_int, vp, vp]),
+    "vh_session_refine_size": (C.c_size_t, [vp, C.c_int, C.POINTER(RefineRecord)]),
+    "vh_session_refine_workspace": (C.c_size_t, [vp, C.c_int, C.c_int]),
+    "vh_session_refine": (C.c_int, [vp, i32p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),
     "vh_session_ptrs": (C.c_int, [vp, C.c_int, C.POINTER(SessionView)]),
     "vh_session_pack_state": (C.c_int, [vp, vp, vp]),
     "vh_debug_force_generic_lk": (None, [C.c_int]),

@@ -926,11 +926,30 @@ extern "C" VH_API int vh_nls_batch(vh_ctx* c, const double* K_host, const double
 extern "C" VH_API int vh_nls_batch_multi(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, int max_iter,
                                          double* trace, int* info, void* workspace, size_t workspace_bytes_per_window, void* stream)
 {
+    return vh_nls_batch_windows(c, K_host, z, x, nt, nc, nwin, nullptr, nullptr, max_iter, trace, info, workspace, workspace_bytes_per_window, stream);
+}
+
+// the same launch sequence for windows that keep different numbers of tracks and have different cameras: every window is laid out for nt tracks and
+// padded with unobserved points, which add exact zeros to its reduced system (vh_ba.hpp); both tables stay on the device
+extern "C" VH_API int vh_nls_batch_windows(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
+                                           const double* K_win_dev, int max_iter, double* trace, int* info, void* workspace,
+                                           size_t workspace_bytes_per_window, void* stream)
+{
+    return vh_ba_windows(c, K_host, z, x, nt, nc, nwin, nt_win_dev, K_win_dev, max_iter, trace, (size_t)2 * (max_iter > 0 ? max_iter : 0), info, 2, workspace,
+                         workspace_bytes_per_window, stream);
+}
+
+// ... with the windows' trace / info records trace_stride doubles / info_stride ints apart (vh_session_refine writes them straight into its records)
+int vh_ba_windows(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev, const double* K_win_dev,
+                  int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride, void* workspace, size_t workspace_bytes_per_window,
+                  void* stream)
+{
     if (!c || !K_host || nt < 1 || nc < 1 || max_iter < 1 || nwin < 1 || nwin > 65535) return vh_fail(-1, "vh_nls_batch_multi: bad arguments");
     if (nc > 255) return vh_fail(-1, "vh_nls_batch_multi: at most 255 free cameras");
     if (workspace_bytes_per_window < vh_ba_workspace_bytes(nt, nc, ba_parts(nt, nc)) || workspace_bytes_per_window % 256)
         return vh_fail(-1, "vh_nls_batch_multi: per-window workspace too small or not a multiple of 256 bytes");
     BaProblem P;
+    P.nt_win = nt_win_dev; P.K_win = K_win_dev;
     P.graph_cache = c->ba_graph_on ? &c->ba_graphs : nullptr;
     P.ctx = c;
     for (int k = 0; k < 9; k++) P.K[k] = (double)K_host[k];
@@ -941,7 +960,7 @@ extern "C" VH_API int vh_nls_batch_multi(vh_ctx* c, const double* K_host, const 
     P.phase = -1; P.it = 0; P.add_identity = 1; P.count_cams = 1; P.defer_finalize = 0; P.model = 0;
     P.nx_total = 3.0 * nt + 6.0 * nc; P.nz_total = 2.0 * nt * (nc + 1);
     P.nwin = nwin; P.ws_stride = workspace_bytes_per_window; P.z_stride = (size_t)2 * nt * (nc + 1); P.x_stride = (size_t)3 * nt + 6 * (size_t)nc;
-    P.trace_stride = (size_t)2 * max_iter; P.info_stride = 2;
+    P.trace_stride = trace_stride; P.info_stride = info_stride;
     int r = vh_ba_run(P, vh_ctx_bind(c, stream));
     if (r) return vh_fail(r, "vh_ba_run failed");
     return 0;

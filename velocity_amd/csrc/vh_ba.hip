@@ -168,7 +168,8 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_jac(BaJob J)
     if (il < npts) {
         const int i = i0 + il, c = threadIdx.x - il * nf;  // POINT-major measurement index m = i (nc+1) + c: a point's Jacobians are contiguous
         double K[9];
-        for (int k = 0; k < 9; k++) K[k] = J.K[k];
+        if (J.K_win) for (int k = 0; k < 9; k++) K[k] = J.K_win[9 * (size_t)blockIdx.y + k];  // the window's own camera (wave-uniform: scalar loads)
+        else for (int k = 0; k < 9; k++) K[k] = J.K[k];
         double w[3] = {J.x[3 * i], J.x[3 * i + 1], J.x[3 * i + 2]};
         if (J.model == 1) {
             // zhat = pscale((pw @ R + offset_c) @ K); columns of the compact Jacobian: point (3) | rpy (3), el, az, range_c
@@ -1690,7 +1691,14 @@ __global__ __launch_bounds__(BA_CB_THREADS) void k_ba_chol_back(BaJob J, int blo
     for (int q = tid; q < nq; q += BA_CB_THREADS) J.dc[q] = sx[q];
 }
 
-// tail of the update kernels: block 0 moves the cameras (and builds the rotation / offset tables of the next iteration from the LDS copy of the new
+// a window's own normalisation of rms(delta) / rms(residual): its padding rows add exact zeros to both sums, the divisors are the true sizes
+__device__ __forceinline__ void ba_window_sizes(const BaJob& J, int w, double& nx, double& nz)
+{
+    const double n = (double)J.nt_win[w];
+    nx = 3.0 * n + 6.0 * J.nc; nz = 2.0 * n * (J.nc + 1);
+}
+
+// tail of the update kernels (all of them launched with blockIdx.y = window): block 0 moves the cameras (and builds the rotation / offset tables of the next iteration from the LDS copy of the new
 // parameters -- saves a launch per iteration); every block adds its sum of squared steps, the last one finishes the iteration record
 template <int NT>
 __device__ __forceinline__ void ba_update_tail(BaJob& J, int it, double ss, double* s_par, double* sh)
@@ -1724,7 +1732,8 @@ __device__ __forceinline__ void ba_update_tail(BaJob& J, int it, double ss, doub
         const unsigned prev = atomicAdd(J.ticket, 1u);
         if (prev == gridDim.x - 1 && J.defer_finalize) *J.ticket = 0u;
         if (prev == gridDim.x - 1 && !J.defer_finalize) {  // last block: finish the iteration record
-            const double nz = J.nz_total, nx = J.nx_total;
+            double nz = J.nz_total, nx = J.nx_total;
+            if (J.nt_win) ba_window_sizes(J, blockIdx.y, nx, nz);
             const double sumr = atomicAdd(J.acc, 0.0), sumd = atomicAdd(J.acc + 1, 0.0);
             const double f = sqrt(sumr / nz), xr = sqrt(sumd / nx);
             J.trace[2 * it] = f;
@@ -1877,7 +1886,9 @@ __global__ void k_ba_finalize(BaJob J, int it)
 {
     ba_select_window(J, blockIdx.y);
     if (threadIdx.x != 0 || *J.done) return;
-    const double f = sqrt(J.acc[0] / J.nz_total), xr = sqrt(J.acc[1] / J.nx_total);
+    double nz = J.nz_total, nx = J.nx_total;
+    if (J.nt_win) ba_window_sizes(J, blockIdx.y, nx, nz);
+    const double f = sqrt(J.acc[0] / nz), xr = sqrt(J.acc[1] / nx);
     J.trace[2 * it] = f;
     J.trace[2 * it + 1] = xr;
     J.info[0] = it + 1;
@@ -1894,6 +1905,7 @@ __global__ void k_ba_init(BaJob J, double* flags0)
     if (t < 4) J.acc[t] = 0.0;
     if (t < 32) flags[t] = 0.0;
     if (t < 2) J.info[t] = 0;
+    if (t == 0 && J.nt_win && J.nt_win[blockIdx.y] == 0) *J.done = 1;  // an empty window is not solved: info stays {0, 0}, x untouched
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1979,6 +1991,7 @@ static void ba_layout(const BaProblem& P, BaJob& J, double*& flags)
     J.add_identity = P.add_identity; J.count_cams = P.count_cams; J.defer_finalize = P.defer_finalize;
     J.nx_total = P.nx_total; J.nz_total = P.nz_total;
     J.nwin = P.nwin < 1 ? 1 : P.nwin;
+    J.nt_win = P.nt_win; J.K_win = P.K_win;
     J.ws_stride = P.ws_stride; J.z_stride = P.z_stride; J.x_stride = P.x_stride; J.trace_stride = P.trace_stride; J.info_stride = P.info_stride;
     char* w = reinterpret_cast<char*>(P.workspace);
     auto take = [&](size_t n) { double* p = reinterpret_cast<double*>(w); w += (n * sizeof(double) + 255) / 256 * 256; return p; };

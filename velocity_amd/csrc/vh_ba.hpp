@@ -39,6 +39,10 @@ struct BaJob {  // passed by value to every BA kernel
     size_t z_stride, x_stride;       // doubles between consecutive windows' z / x
     size_t trace_stride;             // doubles
     size_t info_stride;              // ints
+    // windows of different track counts and cameras (vh_nls_batch_windows): every window is laid out for nt tracks, rows >= nt_win[w] are padding
+    // (NaN measurements: exact zeros everywhere, see k_ba_jac).  Both tables are read on the device; null = nt tracks / K for every window
+    const int* nt_win;               // [nwin] true track counts: the two rms divisors of the iteration record, and the start flag of an empty window
+    const double* K_win;             // [nwin][9] intrinsics of each window
 };
 
 struct BaProblem {
@@ -56,6 +60,8 @@ struct BaProblem {
     int force_valu;  // test hook: 1 = accumulate the reduced camera system on the VALU instead of the matrix cores
     int nwin;        // independent windows solved by the same launches (>= 1); z, x, trace, info and workspace are arrays of nwin
     size_t ws_stride, z_stride, x_stride, trace_stride, info_stride;  // see BaJob (ignored when nwin == 1)
+    const int* nt_win = nullptr;  // see BaJob (device, may be null)
+    const double* K_win = nullptr;
     struct vh_ctx* ctx;  // may be null: per-kernel HIP-event timing when its profiling is on (vh_profile_begin)
     void** graph_cache;  // may be null: where the owner (vh_ctx) keeps the replayable launch sequences of whole solves (vh_ba_graph_cache_free)
 };
@@ -64,3 +70,7 @@ void vh_ba_graph_cache_free(void* cache);
 size_t vh_ba_workspace_bytes(int nt, int nc, int nparts);
 int vh_ba_run(const BaProblem& P, hipStream_t s);
 void vh_ba_exchange_span(const BaProblem& P, size_t* offset_bytes, size_t* n_doubles);
+// vh_nls_batch_windows (include/velocity_hip.h) with the caller's own distances between the windows' trace (doubles) and info (ints) records (vh_api.hip)
+int vh_ba_windows(struct vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
+                  const double* K_win_dev, int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride, void* workspace,
+                  size_t workspace_bytes_per_window, void* stream);

@@ -12,6 +12,7 @@
 #include <stddef.h>
 
 #include "vh_ws.hpp"
+#include "vh_ba.hpp"
 #include "vh_pose_dev.hpp"
 
 // History P (vidExample.py:128-129: [5, N0, n] in the reference) is kept FRAME-MAJOR on the device, [nhist][5][N0]: a frame writes its five rows as five
@@ -725,6 +726,210 @@ extern "C" VH_API int vh_session_export(vh_session* s, int slot, void* rec_dev, 
     sess_record_layout(s->N0, s->nhist, &L);
     const int tiles = (s->N0 + SESS_EXP_TILE - 1) / SESS_EXP_TILE;
     hipLaunchKernelGGL(k_sess_export, dim3(5 * tiles + SESS_EXP_FLAT), dim3(256), 0, (hipStream_t)stream, s->d_ss + slot, L, reinterpret_cast<char*>(rec_dev), tiles);
+    SESS_CHECK();
+    return 0;
+}
+
+// ---- bundle adjustment of finished clips (vh_session_refine; vidExample.py:157, NLS.py:186-250) ----------------------------------------------------------
+// pack: the slot's surviving tracks, its history, world points, per-frame translations and camera -> window w of one vh_nls_batch_windows problem laid out
+// for N0 tracks; unpack: the refined state and the speed derived from it -> record w.  The session is only read.
+#define SESS_REF_CHUNK 256  // slots per pack / unpack launch: their numbers travel in the kernel arguments (no upload, no host wait)
+struct RefSlots {
+    int slot[SESS_REF_CHUNK];
+};
+struct RefWs {  // the scratch of one call, carved by refine_ws_layout
+    double* z;   // [nslots][2][nf][N0]
+    double* x;   // [nslots][3 N0 + 6 nc]
+    double* K;   // [nslots][9]
+    int* nt;     // [nslots]
+    char* ba;    // [nslots] BA workspaces, ba_stride bytes apart
+    size_t z_stride, x_stride, ba_stride;
+};
+
+static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_record* L)
+{
+    size_t off = 0;
+    auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
+    L->nt = put(4 * sizeof(int)); L->iterations = L->nt + 4; L->converged = L->nt + 8;  // (iterations, converged: the int[2] info record of the window's solve)
+    L->ids = put(sizeof(int) * (size_t)N0);
+    L->pw = put(sizeof(double) * 3 * (size_t)N0);
+    L->cw = put(sizeof(double) * 3 * (size_t)nhist);
+    L->dr = put(sizeof(double) * (size_t)nhist); L->speed = put(sizeof(double) * (size_t)nhist);
+    L->speed_mean = put(sizeof(double)); L->speed_std = put(sizeof(double)); L->f_first = put(sizeof(double)); L->f_last = put(sizeof(double));
+    L->trace = put(sizeof(double) * 2 * (size_t)max_iter);
+    L->bytes = off;
+    L->n0 = N0; L->nhist = nhist; L->max_iter = max_iter;
+}
+
+static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* base, RefWs* W)
+{
+    const size_t N0 = s->N0, nc = nf - 1, nw = nslots;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return base + o; };
+    W->z_stride = 2 * N0 * (size_t)nf; W->x_stride = 3 * N0 + 6 * nc;
+    W->ba_stride = align_up(vh_nls_batch_workspace((int)N0, (int)nc), 256);
+    W->z = (double*)carve(sizeof(double) * nw * W->z_stride);
+    W->x = (double*)carve(sizeof(double) * nw * W->x_stride);
+    W->K = (double*)carve(sizeof(double) * 9 * nw);
+    W->nt = (int*)carve(sizeof(int) * nw);
+    W->ba = carve(nw * W->ba_stride);
+    return off;
+}
+
+__global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, RefSlots sl, int w0, int nf, RefWs W, vh_refine_record L, char* recs)
+{
+    const int w = w0 + blockIdx.x, tid = threadIdx.x;
+    const SessStream& S = ss_all[sl.slot[blockIdx.x]];
+    const int N0 = S.N0, n = min(max(S.n_cur, 0), N0), nc = nf - 1;
+    const double nanv = __longlong_as_double(0x7ff8000000000000LL);
+    // z = [all u | all v], camera-major / track-minor (NLS.py:198-199), from the frame-major float32 history; rows behind the n survivors: no observation
+    double* z = W.z + (size_t)w * W.z_stride;
+    const size_t plane = (size_t)nf * N0;
+    for (size_t e = tid; e < 2 * plane; e += 256) {
+        const int row = e >= plane ? 1 : 0;
+        const size_t rem = e - (size_t)row * plane;
+        const int f = (int)(rem / N0), k = (int)(rem - (size_t)f * N0);
+        z[e] = k < n ? (double)S.P[sess_P(row, S.ids[k], f, N0)] : nanv;
+    }
+    // x0 = [p3[ids] | B[1:nf, 3:6] | 0] (NLS.py:202-203); padding points sit at (0, 0, 1)
+    double* x = W.x + (size_t)w * W.x_stride;
+    for (int e = tid; e < 3 * N0; e += 256) {
+        const int k = e / 3, c = e - 3 * k;
+        x[e] = k < n ? S.p3[3 * (size_t)S.ids[k] + c] : (c == 2 ? 1.0 : 0.0);
+    }
+    for (int e = tid; e < 3 * nc; e += 256) {
+        const int i = e / 3 + 1, c = e - 3 * (i - 1);
+        x[3 * (size_t)N0 + e] = (double)S.B[14 * i + 3 + c];
+        x[3 * (size_t)N0 + 3 * nc + e] = 0.0;
+    }
+    if (tid < 9) W.K[9 * (size_t)w + tid] = S.K[tid];
+    if (tid == 0) W.nt[w] = n;
+    // the part of the record the solve writes into (info, trace rows up to the iterations it takes): defined from the start
+    char* rec = recs + (size_t)w * L.bytes;
+    if (tid < 4) reinterpret_cast<int*>(rec + L.nt)[tid] = 0;
+    double* trace = reinterpret_cast<double*>(rec + L.trace);
+    for (int e = tid; e < 2 * L.max_iter; e += 256) trace[e] = 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_refine_unpack(const SessStream* ss_all, RefSlots sl, int w0, int nf, RefWs W, vh_refine_record L, char* recs)
+{
+    const int w = w0 + blockIdx.x, tid = threadIdx.x;
+    const SessStream& S = ss_all[sl.slot[blockIdx.x]];
+    const int N0 = S.N0, nh = S.nhist, n = W.nt[w];
+    const double nanv = __longlong_as_double(0x7ff8000000000000LL);
+    const double* x = W.x + (size_t)w * W.x_stride;
+    const double* cam = x + 3 * (size_t)N0;  // refined positions of cameras 1..nf-1 (camera 0 is the origin)
+    char* rec = recs + (size_t)w * L.bytes;
+    int* hdr = reinterpret_cast<int*>(rec + L.nt);
+    int* ids = reinterpret_cast<int*>(rec + L.ids);
+    double* pw = reinterpret_cast<double*>(rec + L.pw);
+    double* cw = reinterpret_cast<double*>(rec + L.cw);
+    double* dr = reinterpret_cast<double*>(rec + L.dr);
+    double* speed = reinterpret_cast<double*>(rec + L.speed);
+    for (int k = tid; k < ((N0 + 1) & ~1); k += 256) ids[k] = k < n ? S.ids[k] : -1;  // (to the 8-byte boundary the next array starts on: the whole record is defined)
+    for (int e = tid; e < 3 * N0; e += 256) pw[e] = e < 3 * n ? x[e] : nanv;
+    for (int e = tid; e < 3 * nh; e += 256) {
+        const int i = e / 3;
+        cw[e] = i == 0 ? 0.0 : (i < nf ? cam[e - 3] : nanv);
+    }
+    __shared__ double s_speed[256];  // nf <= 256 (the BA's camera limit)
+    for (int i = tid; i < nh; i += 256) {
+        double d = nanv, sp = nanv;
+        if (i >= 1 && i < nf) {
+            double ss = 0.0;
+            for (int c = 0; c < 3; c++) {
+                const double a = cam[3 * (i - 1) + c] - (i == 1 ? 0.0 : cam[3 * (i - 2) + c]);
+                ss += a * a;
+            }
+            d = sqrt(ss);
+            const float dt = __fsub_rn(S.B[14 * i + 12], S.B[14 * (i - 1) + 12]);  // the float32 difference vidExample.py:142 forms
+            sp = d / (double)dt * 3.6;
+            s_speed[i] = sp;
+        }
+        dr[i] = d; speed[i] = sp;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        hdr[0] = n;
+        double m = 0.0, v = 0.0;  // vidExample.py:177: mean and population std over frames 1..nf-1
+        for (int i = 1; i < nf; i++) m += s_speed[i];
+        m /= (double)(nf - 1);
+        for (int i = 1; i < nf; i++) v += (s_speed[i] - m) * (s_speed[i] - m);
+        *reinterpret_cast<double*>(rec + L.speed_mean) = m;
+        *reinterpret_cast<double*>(rec + L.speed_std) = sqrt(v / (double)(nf - 1));
+        const double* trace = reinterpret_cast<const double*>(rec + L.trace);
+        const int it = min(max(hdr[1], 0), L.max_iter);
+        *reinterpret_cast<double*>(rec + L.f_first) = it > 0 ? trace[0] : nanv;
+        *reinterpret_cast<double*>(rec + L.f_last) = it > 0 ? trace[2 * (it - 1)] : nanv;
+    }
+}
+
+extern "C" VH_API size_t vh_session_refine_size(const vh_session* s, int max_iter, vh_refine_record* layout_host)
+{
+    if (!s || max_iter < 1) { vh_fail(-1, "vh_session_refine_size: bad arguments"); return 0; }
+    vh_refine_record L;
+    refine_record_layout(s->N0, s->nhist, max_iter, &L);
+    if (layout_host) *layout_host = L;
+    return L.bytes;
+}
+
+extern "C" VH_API size_t vh_session_refine_workspace(const vh_session* s, int nslots, int nf)
+{
+    if (!s || nslots < 1 || nslots > s->batch || nf < 2 || nf - 1 > 255) { vh_fail(-1, "vh_session_refine_workspace: bad arguments"); return 0; }
+    RefWs W;
+    return refine_ws_layout(s, nslots, nf, nullptr, &W);
+}
+
+extern "C" VH_API int vh_session_refine(vh_session* s, const int* slots_host, int nslots, int nf, int max_iter, void* recs_dev, void* workspace,
+                                        size_t workspace_bytes, void* stream)
+{
+    char msg[240];
+    if (!s || !slots_host || !recs_dev || !workspace || nslots < 1 || max_iter < 1 || (reinterpret_cast<uintptr_t>(recs_dev) & 7) ||
+        (reinterpret_cast<uintptr_t>(workspace) & 255))
+        return vh_fail(-1, "vh_session_refine: bad arguments (records 8-byte, workspace 256-byte aligned; at least one slot and one iteration)");
+    if (nf < 2) { snprintf(msg, sizeof(msg), "vh_session_refine: nf = %d: a clip needs at least two frames", nf); return vh_fail(-1, msg); }
+    if (nf - 1 > 255) { snprintf(msg, sizeof(msg), "vh_session_refine: nf = %d: at most 255 free cameras (256 frames)", nf); return vh_fail(-1, msg); }
+    if (nf > s->nhist) { snprintf(msg, sizeof(msg), "vh_session_refine: nf = %d exceeds the session's history of %d frames", nf, s->nhist); return vh_fail(-1, msg); }
+    if (nslots > s->batch) { snprintf(msg, sizeof(msg), "vh_session_refine: %d slots, the session has %d", nslots, s->batch); return vh_fail(-1, msg); }
+    std::vector<char> seen(s->batch, 0);
+    for (int k = 0; k < nslots; k++) {
+        const int b = slots_host[k];
+        if (b < 0 || b >= s->batch) { snprintf(msg, sizeof(msg), "vh_session_refine: slot %d is outside the session's %d slots", b, s->batch); return vh_fail(-1, msg); }
+        if (seen[b]) { snprintf(msg, sizeof(msg), "vh_session_refine: slot %d is given twice", b); return vh_fail(-1, msg); }
+        seen[b] = 1;
+        if (s->h_frame[b] != nf - 1) {
+            snprintf(msg, sizeof(msg), "vh_session_refine: slot %d is at frame %d, not at the last frame nf - 1 = %d of its clip", b, s->h_frame[b], nf - 1);
+            return vh_fail(-1, msg);
+        }
+    }
+    RefWs W;
+    const size_t need = refine_ws_layout(s, nslots, nf, reinterpret_cast<char*>(workspace), &W);
+    if (workspace_bytes < need) {
+        snprintf(msg, sizeof(msg), "vh_session_refine: workspace of %zu bytes, %d slots of %d frames need %zu", workspace_bytes, nslots, nf, need);
+        return vh_fail(-1, msg);
+    }
+    vh_refine_record L;
+    refine_record_layout(s->N0, s->nhist, max_iter, &L);
+    char* recs = reinterpret_cast<char*>(recs_dev);
+    auto each_chunk = [&](auto kernel, hipStream_t st) {
+        for (int w0 = 0; w0 < nslots; w0 += SESS_REF_CHUNK) {
+            RefSlots sl;
+            const int cnt = nslots - w0 < SESS_REF_CHUNK ? nslots - w0 : SESS_REF_CHUNK;
+            for (int k = 0; k < SESS_REF_CHUNK; k++) sl.slot[k] = slots_host[w0 + (k < cnt ? k : 0)];
+            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, sl, w0, nf, W, L, recs);
+        }
+    };
+    {
+        VH_BIND(s->ctx, stream);
+        each_chunk(k_refine_pack, bound_.s);
+        SESS_CHECK();
+    }
+    // the windows' info = {iterations, converged} and trace go straight into the records
+    int r = vh_ba_windows(s->ctx, s->h_ss[slots_host[0]].K, W.z, W.x, s->N0, nf - 1, nslots, W.nt, W.K, max_iter, reinterpret_cast<double*>(recs + L.trace),
+                          L.bytes / sizeof(double), reinterpret_cast<int*>(recs + L.iterations), L.bytes / sizeof(int), W.ba, W.ba_stride, stream);
+    if (r) return r;
+    VH_BIND(s->ctx, stream);
+    each_chunk(k_refine_unpack, bound_.s);
     SESS_CHECK();
     return 0;
 }

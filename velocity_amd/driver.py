@@ -44,6 +44,7 @@ class TrackerSession:
         # not have run yet) stay alive until the slot is initialised again -- by init_stream or by admit, which both replace the slot's entries here
         self._keep = [None] * batch
         self._init_keep = [None] * batch
+        self._frame_i = [0] * batch  # host mirror of every slot's frame counter (refine: a clip is finished when it has had all its frames)
 
     def slot_size(self, slot):
         """(H, W) of the frames slot `slot` takes."""
@@ -79,7 +80,7 @@ class TrackerSession:
         self._set_camera(slot, fw, fh, K)
         L.check(self.lib.vh_session_init(self.handle, slot, L.dptr(f0), fw, L.dptr(pd), L.dptr(p3d), L.dptr(vpd), t0.ctypes.data_as(L.f32p),
                                          float(time0), float(frame_no), float(res0), L.stream_ptr()), "vh_session_init")
-        self._keep[slot], self._init_keep[slot] = f0, (pd, p3d, vpd)
+        self._keep[slot], self._init_keep[slot], self._frame_i[slot] = f0, (pd, p3d, vpd), 0
 
     def admit(self, entries, settings):
         """THE admission (vidExample.py:105-131 for each clip): frame 0 of every entry computed and installed on the device, on the current stream.
@@ -106,7 +107,7 @@ class TrackerSession:
             self._set_camera(slot, f0.shape[1], f0.shape[0], K)
             L.check(self.lib.vh_session_init_dev(self.handle, slot, L.dptr(f0), f0.shape[1], L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
                                                  float(time0), float(frame_no0), L.stream_ptr()), "vh_session_init_dev")
-            self._keep[slot], self._init_keep[slot] = f0, rows
+            self._keep[slot], self._init_keep[slot], self._frame_i[slot] = f0, rows, 0
             out.append(Admitted(tuple(rois[8 * a:8 * a + 4]), tuple(rois[8 * a + 4:8 * a + 8]), R0[0], res0))
         return out
 
@@ -141,6 +142,7 @@ class TrackerSession:
         if frames is not None:
             active = self.set_frames(frames)
         tab = self._frames if frames_table is None else frames_table
+        self._frame_i = [i + (1 if active is None or active[b] else 0) for b, i in enumerate(self._frame_i)]
         is_t = [hasattr(x, "is_cuda") for x in (time_s, frame_no)]  # torch tensors first: numpy must never see a CUDA tensor
         if active is None and not any(is_t) and np.ndim(time_s) == 0 and np.ndim(frame_no) == 0:
             L.check(self.lib.vh_session_step(self.handle, L.dptr(tab), float(time_s), float(frame_no), L.stream_ptr()), "vh_session_step")
@@ -275,6 +277,50 @@ class TrackerSession:
         ev.record()
         return ExportedState(out, lay, ev, self.recoveries()[slot])
 
+    def refine_layout(self, max_iter=10):
+        """vh_refine_record of this session for max_iter iterations: byte offsets of the fields of a refined clip's record (and `bytes`, its size)."""
+        lays = self.__dict__.setdefault("_refine_layouts", {})
+        if max_iter not in lays:
+            lay = L.RefineRecord()
+            if not self.lib.vh_session_refine_size(self.handle, int(max_iter), C.byref(lay)):
+                L.check(-1, "vh_session_refine_size")
+            lays[max_iter] = lay
+        return lays[max_iter]
+
+    def refine(self, slots, max_iter=10, out=None):
+        """Bundle adjustment of the finished clips in `slots` (vidExample.py:157: fcnNLS_batch(K, P[:, :, 0:i], p3, B[0:i, 3:6]), NLS.py:186-250), without
+        leaving the device: ONE vh_session_refine -- pack, one BA launch sequence for all the slots (their track counts and cameras may differ), unpack --
+        then one asynchronous copy per pinned buffer and an event.  The slots must have had the same number of frames, all of their clips' (clips of other
+        lengths: another call).  The session's state is only read: its streams step on as if nothing had happened.  The scratch and the device records
+        belong to the session and are reused.  out: None (a new pinned buffer), ONE pinned uint8 tensor for all the records, or one per slot.
+        Returns a handle like export()'s: .done() polls, .result() waits and returns one dict per slot (unpack_refine)."""
+        torch = self.torch
+        slots = [int(b) for b in slots]
+        if not slots:
+            raise ValueError("refine: no slot given")
+        lay = self.refine_layout(max_iter)
+        nf = self._frame_i[slots[0]] + 1 if 0 <= slots[0] < self.batch else 0  # (a slot outside the session: the library names it)
+        need = int(self.lib.vh_session_refine_workspace(self.handle, len(slots), nf)) if nf >= 2 and len(slots) <= self.batch else 0
+        nbytes = lay.bytes * len(slots)
+        if getattr(self, "_refine_ws", None) is None or self._refine_ws.numel() < need:
+            self._refine_ws = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
+        if getattr(self, "_refine_dev", None) is None or self._refine_dev.numel() < nbytes:
+            self._refine_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        bufs = [out[k * lay.bytes:(k + 1) * lay.bytes] for k in range(len(slots))] if isinstance(out, torch.Tensor) else list(out)
+        assert len(bufs) == len(slots) and all(b.dtype == torch.uint8 and b.numel() >= lay.bytes and b.is_pinned() and b.is_contiguous() for b in bufs)
+        L.check(self.lib.vh_session_refine(self.handle, (C.c_int * len(slots))(*slots), len(slots), nf, int(max_iter), L.dptr(self._refine_dev),
+                                           L.dptr(self._refine_ws), self._refine_ws.numel(), L.stream_ptr()), "vh_session_refine")
+        if isinstance(out, torch.Tensor):
+            out[:nbytes].copy_(self._refine_dev[:nbytes], non_blocking=True)
+        else:
+            for k, b in enumerate(bufs):
+                b[: lay.bytes].copy_(self._refine_dev[k * lay.bytes:(k + 1) * lay.bytes], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return RefinedClips(bufs, lay, ev, nf)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -301,6 +347,53 @@ class ExportedState:
             self.event.synchronize()
             self._res = unpack_record(self.buf.numpy(), self.layout)
         return self._res
+
+
+class RefinedClips:
+    """The refined clips of one TrackerSession.refine on their way to the host: one pinned record per slot."""
+
+    def __init__(self, bufs, layout, event, nf):
+        self.bufs, self.layout, self.event, self.nf = bufs, layout, event, nf
+        self._res = None
+
+    def done(self):
+        """True once the records have arrived (never waits)."""
+        return self._res is not None or self.event.query()
+
+    def result(self):
+        if self._res is None:
+            self.event.synchronize()
+            self._res = [unpack_refine(b.numpy(), self.layout, self.nf) for b in self.bufs]
+        return self._res
+
+
+def unpack_refine(raw, lay, nf=None):
+    """A vh_refine_record (uint8 array `raw`, offsets `lay`) as a dict: nt, ids [nt], pw [nt, 3], cw [nf, 3], dr [nf], speed [nf] (entry 0 NaN),
+    speed_mean, speed_std, iterations, converged, trace [iterations, 2], f_first, f_last; every array is a copy.  nf: the clip's frames (None: the
+    rows of cw the record defines)."""
+
+    def rd(off, count, dtype):
+        return np.frombuffer(raw, dtype, count, off).copy()
+
+    nt, iterations, converged = (int(rd(off, 1, np.int32)[0]) for off in (lay.nt, lay.iterations, lay.converged))
+    cw = rd(lay.cw, 3 * lay.nhist, np.float64).reshape(lay.nhist, 3)
+    if nf is None:
+        nf = int(np.isfinite(cw[:, 0]).sum())
+    one = {k: float(rd(getattr(lay, k), 1, np.float64)[0]) for k in ("speed_mean", "speed_std", "f_first", "f_last")}
+    return dict(nt=nt, ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3), cw=cw[:nf].copy(), dr=rd(lay.dr, nf, np.float64),
+                speed=rd(lay.speed, nf, np.float64), iterations=iterations, converged=converged,
+                trace=rd(lay.trace, 2 * iterations, np.float64).reshape(iterations, 2), **one)
+
+
+def ba_line(ba):
+    """The line a refined clip adds behind the reference's summary."""
+    return f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({ba['nt']:g} tracks, f = {ba['f_last']:.3f} pixels)"
+
+
+def _check_refine(refine):
+    if refine not in (None, "ba"):
+        raise ValueError(f"refine must be None or 'ba', got {refine!r}")
+    return refine == "ba"
 
 
 def unpack_record(raw, lay):
@@ -532,7 +625,7 @@ def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corner
     return out
 
 
-def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=None):
+def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=None, ba=None):
     """THE result of a clip, whichever driver ran it (a pure function: numpy in, fresh arrays out, no device).
     st       the stream's state after the clip's last frame (TrackerSession.state / ExportedState.result).  Its session may have been sized for longer
              clips and has room for 4 + max_corners tracks: the history is cut to the clip's n frames and to the k tracks frame 0 found (S[0, 2]:
@@ -540,6 +633,7 @@ def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=
     clip     dict(n, name, frame_numbers); f0: the clip's Admitted with host values
     seconds  the wall time the `Processed ...` line reports; step_seconds: the mean time of a frame step, which rows 1.. of the procTime column carry
              (row 0: 0) unless `proc` gives the column frame by frame (run_sequence's live table)
+    ba       the clip's refinement (unpack_refine's dict; None: not asked for): the result gains the key "ba" and the lines gain ba_line(ba) at the end
     `lines` = the start line, TABLE_HEADER, one table_row per frame and the two summary_lines."""
     n, k = clip["n"], int(st["S"][0, 2])
     S = st["S"][:n].copy()
@@ -550,15 +644,19 @@ def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=
     B = st["B"][:n].copy()
     lines = [f"Starting image processing on {clip['name']} ...", TABLE_HEADER] + [table_row(S[i]) for i in range(n)]  # vidExample.py:50
     lines += summary_lines(S, n, clip["frame_numbers"], seconds)
+    extra = {}
+    if ba is not None:
+        lines.append(ba_line(ba))
+        extra["ba"] = ba
     return dict(S=S, B=B, P=st["P"][:, :k, :n].copy(), vg=st["vg"][:k].copy(), vp=st["vp"][:k].copy(), p=st["p"].copy(), p3=st["p3"][:k].copy(),
                 ids=st["ids"].copy(), n_tracks0=k, t0=B[0, 0:3].copy(), R0=np.array(f0.R0, np.float64).reshape(3, 3), res0=float(f0.res0), boxa=tuple(f0.boxa),
                 boxb=tuple(f0.boxb), klt_flags=st["klt_flags"], recoveries=recoveries, lines=lines, seconds=seconds, ms_per_frame=1e3 * step_seconds,
-                sessions=sessions)
+                sessions=sessions, **extra)
 
 
 def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01,
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
-                 out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
+                 out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None):
     """The packaged counterpart of vidExample.py:52-178 (minus video decode and plots) on one clip.
 
     frames  sequence of n uint8 [H, W] gray frames (numpy arrays or CUDA tensors): what `cv2.cvtColor(cap.read(), BGR2GRAY)` / `cv2.imread(.., 0)` hands
@@ -575,6 +673,8 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             other setting goes through vh_frame0_init_batch2).
     fallback   True: a frame whose coarse KLT stage fails recovers the motion by feature matching (TrackerSession(fallback=True): one host read per
             frame step; default off).  The result then carries `recoveries` = [the recovery ran, it found a model] counts.
+    refine  None (default: nothing new is queued), or "ba": after the last frame the clip is bundle-adjusted on the device (TrackerSession.refine:
+            vidExample.py:157's fcnNLS_batch over all frames and surviving tracks); the result gains "ba" and one line follows the summary (ba_line).
     out     line sink (default print); clock: time source for the procTime column / fps line (default time.perf_counter).
 
     Prints the reference's header, one 9-column row per frame (vidExample.py:165) and the `Speed = ... +/- ... km/h / Res = ...` summary (:177-178).
@@ -582,6 +682,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     import time as _time
 
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
+    refine = _check_refine(refine)
     if route != "session":
         raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
     clock = clock or _time.perf_counter
@@ -619,9 +720,10 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             row(i)
     ses.torch.cuda.synchronize()
     step_seconds = (clock() - t_loop) / (n - 1)
+    ba = ses.refine([0]).result()[0] if refine else None
     st, recoveries, f0 = ses.state(0), ses.recoveries()[0], f0.host()
-    res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None)
-    for line in res["lines"][-2 if live else 2:]:  # (not live: the whole clip ran first, and every row carries the mean time per frame)
+    res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None, ba)
+    for line in res["lines"][-(3 if refine else 2) if live else 2:]:  # (not live: the whole clip ran first, and every row carries the mean time per frame)
         emit(line)
     return res
 
@@ -686,7 +788,7 @@ class _SessionSet:
 
 
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
-                  msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None):
+                  msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name, K]) of ONE length -- the
     frame size and the intrinsics are each clip's own ("K": that clip's camera, default the K argument); the sessions are created at the elementwise
     maximum of the sizes and a frame step is sized for it, so clips of one camera type batch best.  One length stays required: a step advances every
@@ -696,9 +798,11 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     of a session is ONE TrackerSession.admit (one frame-0 batch call on the device, its outputs feed vh_session_init_dev directly); nothing is read back
     before the last frame.  use_harris / min_distance: the frame-0 detector, as in run_sequence.  fallback: the recovery by feature matching, as in
     run_sequence (the failed streams of a session share one vh_match_affine_batch call per step).  Returns one result dict per clip (clip_result's;
-    `lines` = that clip's table and summary, printed through `out` if given), each equal to what run_sequence returns for the clip alone."""
+    `lines` = that clip's table and summary, printed through `out` if given), each equal to what run_sequence returns for the clip alone.  refine="ba": as in
+    run_sequence; all the clips of a session are refined by ONE TrackerSession.refine after the last frame."""
     import time as _time
 
+    refine = _check_refine(refine)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
     nclip = len(clips)
@@ -730,14 +834,22 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
                 ses.step([dev[b][i] for b in mem], time_s=times[mem, i], frame_no=fnos[mem, i])
     torch.cuda.synchronize()
     step_seconds = (_time.perf_counter() - t_loop) / (n - 1)  # every row carries the mean time of a frame step (of ALL clips)
+    refined = None
+    if refine:
+        refined = []
+        for ses, hs, mem in zip(sess, group.hip_streams, members):
+            with torch.cuda.stream(hs):
+                refined.append(ses.refine(list(range(len(mem)))))
+        refined = [h.result() for h in refined]
     seconds = _time.perf_counter() - t_begin
     # what tools/exp/queue_timing.py reads: device time of the frame-0 block of every session (events on its stream), to set beside run_queue's
     run_sequences.last_stats = dict(sessions=len(sess), steps=n - 1, admission_ms=float(sum(a.elapsed_time(b) for a, b in f0_events)), admissions=len(sess))
     results = []
-    for ses, mem in zip(sess, members):
+    for g, (ses, mem) in enumerate(zip(sess, members)):
         for j, b in enumerate(mem):
             meta = dict(n=n, name=clips[b].get("name", f"clip {b}"), frame_numbers=clips[b].get("frame_numbers", list(range(n))))
-            results.append(clip_result(ses.state(j), meta, f0[b].host(), seconds, step_seconds, len(sess), ses.recoveries()[j]))
+            results.append(clip_result(ses.state(j), meta, f0[b].host(), seconds, step_seconds, len(sess), ses.recoveries()[j],
+                                       ba=refined[g][j] if refine else None))
             if out is not None:
                 for ln in results[-1]["lines"]:
                     out(ln)
@@ -804,7 +916,7 @@ def queue_plan(lengths, streams, sessions=1):
 
 def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, max_size=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
               harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=None, use_harris=True, min_distance=0.0, fallback=False,
-              fallback_params=None):
+              fallback_params=None, refine=None):
     """A queue of clips of ANY length on `streams` resident streams: what run_sequences is for clips of one length.  `clips` = any iterable of
     dict(frames, q, times[, frame_numbers, name, K]), each of >= 2 frames and with its own frame size and intrinsics ("K": default the K argument); it is consumed lazily -- a clip is pulled when a slot is free
     for it and its frames go up then, so at most `streams` clips are resident -- and may hold more clips than fit on the device at once.
@@ -821,9 +933,12 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
     With fallback=False the loop never waits for the device except for a result whose pinned buffer is needed again (a ring of 2 x streams) and at
     the end of the run; frames given as CUDA tensors are used in place, host frames are uploaded on a side stream.
     on_result(index, result) is called as results land (polled at every step, never waited for); returns the results in input order.  A result is
-    clip_result's: P / B / S cut to the clip's own length and the track rows to n_tracks0; `lines` = the clip's table and summary."""
+    clip_result's: P / B / S cut to the clip's own length and the track rows to n_tracks0; `lines` = the clip's table and summary.
+    refine="ba": as in run_sequence.  The clips of a session that finish at the same step are refined on the session's stream right behind their
+    exports, one TrackerSession.refine per clip length among them; the records travel with the exports and the slots are free at the next step as ever."""
     import time as _time
 
+    refine = _check_refine(refine)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
     if max_frames is None:
@@ -872,11 +987,13 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
     t_begin = _time.perf_counter()
 
     def deliver(entry):
-        handle, index, clip, f0, t0 = entry[2]
+        handle, index, clip, f0, t0, ba = entry[2]
         st = handle.result()
+        if ba is not None:
+            ba = ba[0].result()[ba[1]]
         x = entry[1].numpy().copy()
         seconds = _time.perf_counter() - t0  # the clip's time in the queue: every row carries the mean over its frame steps
-        res = results[index] = clip_result(st, clip, f0._replace(R0=x[0:9], res0=x[9]), seconds, seconds / (clip["n"] - 1), G, handle.recoveries)
+        res = results[index] = clip_result(st, clip, f0._replace(R0=x[0:9], res0=x[9]), seconds, seconds / (clip["n"] - 1), G, handle.recoveries, ba=ba)
         entry[2] = None
         pending[:] = [e for e in pending if e is not entry]
         if out is not None:
@@ -886,7 +1003,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
             on_result(index, res)
 
     def poll():
-        for entry in [e for e in pending if e[2][0].done()]:
+        for entry in [e for e in pending if e[2][0].done() and (e[2][5] is None or e[2][5][0].done())]:
             deliver(entry)
 
     held = [[None] * n for n in group.sizes]  # per slot: (the resident clip's Admitted, its admission time)
@@ -900,7 +1017,9 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                 with torch.cuda.stream(hs):  # the frame-0 scratch for a full house, so that no later admission grows it (growing waits for the stream)
                     L.check(ses.lib.vh_init_reserve_batch(ses.ws.handle, ses.batch, W, H, L.stream_ptr()), "vh_init_reserve_batch")
             rec_bytes = sess[0].record_layout().bytes
-            ring = [[torch.empty(rec_bytes, dtype=torch.uint8).pin_memory(), torch.empty(10, dtype=torch.float64).pin_memory(), None] for _ in range(2 * streams)]
+            ba_bytes = sess[0].refine_layout().bytes if refine else 0
+            ring = [[torch.empty(rec_bytes, dtype=torch.uint8).pin_memory(), torch.empty(10, dtype=torch.float64).pin_memory(), None,
+                     torch.empty(ba_bytes, dtype=torch.uint8).pin_memory() if refine else None] for _ in range(2 * streams)]
         for g, (ses, hs) in enumerate(zip(sess, group.hip_streams)):
             adm = [(j, pulled[k]) for gg, j, k in step["admit"] if gg == g]
             with torch.cuda.stream(hs):
@@ -933,6 +1052,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                 clk = torch.from_numpy(clk).pin_memory().cuda(non_blocking=True)
                 ses._queue_keep = (tab, clk)
                 ses.step(frames_table=tab, time_s=clk[0], frame_no=clk[1], active=(ptrs != 0).astype(np.uint8))
+                finished = []  # (slot, clip length, ring entry) of the clips of this session that end here
                 for gg, j, k in step["done"]:
                     if gg != g:
                         continue
@@ -946,9 +1066,15 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                     entry[1].copy_(torch.cat([f0.R0, f0.res0]), non_blocking=True)
                     handle.event.record()
                     c = pulled.pop(k)
-                    entry[2] = (handle, k, dict(n=c["n"], name=c["name"], frame_numbers=c["frame_numbers"]), f0, t0)
+                    entry[2] = [handle, k, dict(n=c["n"], name=c["name"], frame_numbers=c["frame_numbers"]), f0, t0, None]
                     pending.append(entry)
                     held[g][j] = None
+                    finished.append((j, c["n"], entry))
+                for n_clip in sorted({n for _, n, _ in finished}) if refine else ():
+                    same = [(j, e) for j, n, e in finished if n == n_clip]
+                    rh = ses.refine([j for j, _ in same], out=[e[3] for _, e in same])
+                    for idx, (_, e) in enumerate(same):
+                        e[2][5] = (rh, idx)
         steps += 1
         poll()
     for hs in group.hip_streams:
@@ -988,13 +1114,14 @@ def main(argv=None):
     ap.add_argument("--msv-frame", type=int, default=5)
     ap.add_argument("--min-distance", type=float, default=0.0, help="minimum distance between the frame-0 corners (vidExample.py:110 uses 0)")
     ap.add_argument("--fallback", action="store_true", help="recover the motion by feature matching when the coarse KLT stage fails (one host read per frame)")
+    ap.add_argument("--refine", choices=["ba"], default=None, help="bundle-adjust the finished clip on the device and print the refined speed (vidExample.py:157)")
     ap.add_argument("--shi-tomasi", action="store_true", help="frame-0 corners by the minimum-eigenvalue detector instead of Harris")
     a = ap.parse_args(argv)
     d = np.load(a.clip)
     fr = d[f"{a.seq}_frames"]
     border = tuple(a.border) if a.border else ((700, 500) if fr.shape[2] >= 1900 else (180, 140))
     run_sequence(fr, d[f"{a.seq}_q"], d[f"{a.seq}_K"], times=d[f"{a.seq}_times"], roi_border=border, msv_frame=a.msv_frame,
-                 name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback)
+                 name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback, refine=a.refine)
 
 
 if __name__ == "__main__":
