@@ -17,6 +17,23 @@ def _scratch(torch, shape):
     return t
 
 
+def _ba_solve(fn, K_host, z, x0, nt, nc, max_iter, nw=None, extra=()):
+    """The device part of every fcnNLS_batch* shim: upload z and x0, allocate trace / info / workspace (one of each per window when nw is given), call
+    the entry point `fn` (its arguments between nc and max_iter: `extra`), read back -> info, x, trace as numpy arrays."""
+    torch = L.torch_cuda()
+    lead = () if nw is None else (nw,)
+    zd = L.to_dev(z, torch.float64)
+    xd = L.to_dev(x0, torch.float64).clone()
+    trace = torch.zeros(lead + (max_iter, 2), dtype=torch.float64, device="cuda")
+    info = torch.zeros(lead + (2,), dtype=torch.int32, device="cuda")
+    ws = L.workspace()
+    nbytes = int(ws.lib.vh_nls_batch_workspace(nt, nc))
+    scratch = _scratch(torch, lead + (nbytes,))
+    L.check(getattr(ws.lib, fn)(ws.handle, K_host.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, *extra, int(max_iter), L.dptr(trace), L.dptr(info),
+                                L.dptr(scratch), nbytes, L.stream_ptr()), fn)
+    return info.cpu().numpy(), xd.cpu().numpy(), trace.cpu().numpy()
+
+
 def _pose(K, p, pw, x0, R, findR, want_proj=True):
     """vh_pose with ONE upload (p and pw packed into one host buffer when both are host arrays) and ONE download (R | res | proj | t | info packed into one
     device record): the drop-in call costs two PCIe transfers and one host synchronisation, not seven."""
@@ -89,7 +106,6 @@ def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False):
     The track filter, the measurement ordering and the state layout are the reference's (NLS.py:190-203); the
     iterations (forward-difference Jacobian, damped normal equations, x += 0.9 delta) run on the device.
     """
-    torch = L.torch_cuda()
     P = np.asarray(P)
     pw = np.asarray(pw, np.float64)
     cw = np.asarray(cw, np.float64)
@@ -99,19 +115,8 @@ def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False):
     nc = nf - 1
     z = np.concatenate([P[0].T.reshape(-1), P[1].T.reshape(-1)]).astype(np.float64)  # NLS.py:198-199
     x0 = np.concatenate((pw, cw[1:], np.zeros((nc, 3)))).reshape(-1)  # NLS.py:202-203
-    K64 = L.host_K(K)
-    zd = L.to_dev(z, torch.float64)
-    xd = L.to_dev(x0, torch.float64).clone()
-    trace = torch.zeros((max_iter, 2), dtype=torch.float64, device="cuda")
-    info = torch.zeros(2, dtype=torch.int32, device="cuda")
-    ws = L.workspace()
-    nbytes = int(ws.lib.vh_nls_batch_workspace(nt, nc))
-    scratch = _scratch(torch, nbytes)
-    L.check(ws.lib.vh_nls_batch(ws.handle, K64.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, int(max_iter), L.dptr(trace), L.dptr(info),
-                                L.dptr(scratch), nbytes, L.stream_ptr()), "vh_nls_batch")
-    info = info.cpu().numpy()
-    x = xd.cpu().numpy()
-    tr = trace.cpu().numpy()[: info[0]]
+    info, x, tr = _ba_solve("vh_nls_batch", L.host_K(K), z, x0, nt, nc, max_iter)
+    tr = tr[: info[0]]
     for i, (f, xr) in enumerate(tr):
         print(f"{i:g}: f={f:g}, x={xr}")  # NLS.py:238 (without the wall-time column)
     if not info[1]:
@@ -167,23 +172,13 @@ def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False):
     per_window_K = K64.ndim == 3
     if per_window_K and len(K64) != nw:
         raise ValueError(f"fcnNLS_batch_windows: {len(K64)} intrinsics for {nw} windows")
-    zd = L.to_dev(z, torch.float64)
-    xd = L.to_dev(x0, torch.float64).clone()
-    trace = torch.zeros((nw, max_iter, 2), dtype=torch.float64, device="cuda")
-    info = torch.zeros((nw, 2), dtype=torch.int32, device="cuda")
-    ws = L.workspace()
-    nbytes = int(ws.lib.vh_nls_batch_workspace(nt, nc))
-    scratch = _scratch(torch, (nw, nbytes))
     K_host = L.host_K(K64[0] if per_window_K else K64)
     if per_window_K or (counts != nt).any():
         ntd = L.to_dev(counts, torch.int32)
         Kd = L.to_dev(K64.reshape(nw, 9), torch.float64) if per_window_K else None
-        L.check(ws.lib.vh_nls_batch_windows(ws.handle, K_host.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, nw, L.dptr(ntd), L.dptr(Kd),
-                                            int(max_iter), L.dptr(trace), L.dptr(info), L.dptr(scratch), nbytes, L.stream_ptr()), "vh_nls_batch_windows")
+        info, x, tr = _ba_solve("vh_nls_batch_windows", K_host, z, x0, nt, nc, max_iter, nw, (nw, L.dptr(ntd), L.dptr(Kd)))
     else:
-        L.check(ws.lib.vh_nls_batch_multi(ws.handle, K_host.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, nw, int(max_iter), L.dptr(trace),
-                                          L.dptr(info), L.dptr(scratch), nbytes, L.stream_ptr()), "vh_nls_batch_multi")
-    info, x, tr = info.cpu().numpy(), xd.cpu().numpy(), trace.cpu().numpy()
+        info, x, tr = _ba_solve("vh_nls_batch_multi", K_host, z, x0, nt, nc, max_iter, nw, (nw,))
     out = []
     for w in range(nw):
         if not info[w, 1] and counts[w]:
@@ -207,7 +202,6 @@ def fcnNLS_batch2(K, P, pw, cw, max_iter=20, return_info=False):
     device (vh_nls_batch2).  Reference defect resolved by intent: `sc2cc` switches to its column branch when exactly 3
     cameras are fitted (shape ambiguity, common.py:100); here the ranges / el / az are always read row-wise.
     """
-    torch = L.torch_cuda()
     P = np.asarray(P)
     pw = np.asarray(pw, np.float64)
     cw = np.asarray(cw, np.float64)
@@ -222,19 +216,8 @@ def fcnNLS_batch2(K, P, pw, cw, max_iter=20, return_info=False):
     el, az = np.arcsin(-d[2] / r), np.arctan2(d[1], d[0])
     ranges = np.arange(1, nc + 1) * r
     x0 = np.concatenate((pw.ravel(), np.zeros(3), [el, az], ranges))  # NLS.py:274
-    K64 = L.host_K(K)
-    zd = L.to_dev(z, torch.float64)
-    xd = L.to_dev(x0, torch.float64).clone()
-    trace = torch.zeros((max_iter, 2), dtype=torch.float64, device="cuda")
-    info = torch.zeros(2, dtype=torch.int32, device="cuda")
-    ws = L.workspace()
-    nbytes = int(ws.lib.vh_nls_batch_workspace(nt, nc))
-    scratch = _scratch(torch, nbytes)
-    L.check(ws.lib.vh_nls_batch2(ws.handle, K64.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, int(max_iter), L.dptr(trace), L.dptr(info),
-                                 L.dptr(scratch), nbytes, L.stream_ptr()), "vh_nls_batch2")
-    info = info.cpu().numpy()
-    x = xd.cpu().numpy()
-    tr = trace.cpu().numpy()[: info[0]]
+    info, x, tr = _ba_solve("vh_nls_batch2", L.host_K(K), z, x0, nt, nc, max_iter)
+    tr = tr[: info[0]]
     if not info[1]:
         print("WARNING: fcnNLS_batch() reaching max iterations!")  # NLS.py:314 (sic)
     print(f"fcnNLS_batch2 done in {info[0] - 1:g} steps, f={tr[-1, 0]:g}")  # NLS.py:315 (without the wall-time column)

@@ -12,6 +12,7 @@
 #include <new>
 
 #include "vh_ba.hpp"
+#include "vh_ba_plan.hpp"
 #include "vh_ws.hpp"
 #include "vh_glue_dev.hpp"
 
@@ -884,17 +885,11 @@ extern "C" VH_API int vh_msv1_t(vh_ctx* c, const double* K, const float* P, cons
 // ---------------------------------------------------------------------------------------------------------------
 // bundle adjustment entry points
 // ---------------------------------------------------------------------------------------------------------------
-// partials of the reduced system: one workgroup per ~16 points, at most 256 (512 / 1024 measured 20 % slower at C5: the reduction grows); with many
-// cameras fewer, so that the partial systems of one window stay below 256 MB
-static int ba_parts(int nt, int nc)
+// partial systems of nwin windows (ba_nparts, vh_ba_plan.hpp) under the VH_BA_PARTS experiment switch, which is read once per process
+static int ba_parts(int nt, int nc, int nwin = 1)
 {
-    static const int cap_env = [] { const char* e = getenv("VH_BA_PARTS"); return e ? atoi(e) : 0; }();  // experiment switch
-    const int pmax = cap_env > 0 ? cap_env : 256;
-    int p = nt / 16;
-    p = p < 1 ? 1 : (p > pmax ? pmax : p);
-    const long long per = 8ll * (6ll * nc) * (6ll * nc), cap = per > 0 ? (256ll << 20) / per : 256;
-    if (cap < p) p = cap < 1 ? 1 : (int)cap;
-    return p;
+    static const int cap_env = [] { const char* e = getenv("VH_BA_PARTS"); return e ? atoi(e) : 0; }();
+    return ba_nparts(nt, nc, nwin, cap_env);
 }
 static std::atomic<int> g_ba_force_valu{0};  // PROCESS-WIDE test hook (include/velocity_hip.h)
 extern "C" VH_API void vh_debug_ba_force_valu(int on) { g_ba_force_valu.store(on, std::memory_order_relaxed); }
@@ -902,23 +897,44 @@ extern "C" VH_API void vh_debug_pyr_rows(int rows) { vh_pyr_force_rows(rows == 2
 
 extern "C" VH_API size_t vh_nls_batch_workspace(int nt, int nc) { return vh_ba_workspace_bytes(nt, nc, ba_parts(nt, nc)); }
 
-extern "C" VH_API int vh_nls_batch(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int max_iter, double* trace,
-                                   int* info, void* workspace, size_t workspace_bytes, void* stream)
+// The checks every BA entry point makes, in their order, and the problem of fcnNLS_batch: ONE window, the whole solve, free cameras (model 0), this
+// context's graph cache and profiling, the process-wide VALU hook.  An entry point then sets only what makes it different.  The workspace (of one
+// window) is always sized for ba_parts(nt, nc) of a single window; ws_what: the entry point's wording of that refusal.
+static int ba_problem(BaProblem& P, vh_ctx* c, const char* fn, const double* K_host, const double* z, double* x, int nt, int nc, int max_iter,
+                      double* trace, int* info, void* workspace, size_t bytes, const char* ws_what = "workspace too small")
 {
-    if (!c || !K_host || nt < 1 || nc < 1 || max_iter < 1) return vh_fail(-1, "vh_nls_batch: bad arguments");
-    if (nc > 255) return vh_fail(-1, "vh_nls_batch: at most 255 free cameras");
-    if (workspace_bytes < vh_ba_workspace_bytes(nt, nc, ba_parts(nt, nc))) return vh_fail(-1, "vh_nls_batch: workspace too small");
-    BaProblem P;
+    auto refuse = [fn](const char* what) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+        return vh_fail(-1, msg);
+    };
+    if (!c || !K_host || nt < 1 || nc < 1 || max_iter < 1) return refuse("bad arguments");
+    if (nc > 255) return refuse("at most 255 free cameras");
+    if (bytes < vh_ba_workspace_bytes(nt, nc, ba_parts(nt, nc))) return refuse(ws_what);
+    P = BaProblem();
     P.graph_cache = c->ba_graph_on ? &c->ba_graphs : nullptr;
     P.ctx = c;
     for (int k = 0; k < 9; k++) P.K[k] = (double)K_host[k];
-    P.z = z; P.x = x; P.trace = trace; P.info = info; P.workspace = workspace; P.nt = nt; P.nc = nc; P.max_iter = max_iter; P.nparts = ba_parts(nt, nc); P.force_valu = g_ba_force_valu.load(std::memory_order_relaxed);
-    P.phase = -1; P.it = 0; P.add_identity = 1; P.count_cams = 1; P.defer_finalize = 0; P.model = 0;
-    P.nwin = 1; P.ws_stride = P.z_stride = P.x_stride = P.trace_stride = P.info_stride = 0;
+    P.z = z; P.x = x; P.trace = trace; P.info = info; P.workspace = workspace;
+    P.nt = nt; P.nc = nc; P.max_iter = max_iter; P.nparts = ba_parts(nt, nc);
+    P.force_valu = g_ba_force_valu.load(std::memory_order_relaxed);
+    P.phase = -1; P.add_identity = 1; P.count_cams = 1; P.nwin = 1;
     P.nx_total = 3.0 * nt + 6.0 * nc; P.nz_total = 2.0 * nt * (nc + 1);
+    return 0;
+}
+static int ba_run_checked(const BaProblem& P, vh_ctx* c, void* stream)
+{
     int r = vh_ba_run(P, vh_ctx_bind(c, stream));
     if (r) return vh_fail(r, "vh_ba_run failed");
     return 0;
+}
+
+extern "C" VH_API int vh_nls_batch(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int max_iter, double* trace,
+                                   int* info, void* workspace, size_t workspace_bytes, void* stream)
+{
+    BaProblem P;
+    if (int r = ba_problem(P, c, "vh_nls_batch", K_host, z, x, nt, nc, max_iter, trace, info, workspace, workspace_bytes)) return r;
+    return ba_run_checked(P, c, stream);
 }
 
 // nwin independent windows of the same shape through ONE launch sequence (grid.y = window): a sliding-window tracker has one window per
@@ -944,46 +960,28 @@ int vh_ba_windows(vh_ctx* c, const double* K_host, const double* z, double* x, i
                   int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride, void* workspace, size_t workspace_bytes_per_window,
                   void* stream)
 {
-    if (!c || !K_host || nt < 1 || nc < 1 || max_iter < 1 || nwin < 1 || nwin > 65535) return vh_fail(-1, "vh_nls_batch_multi: bad arguments");
-    if (nc > 255) return vh_fail(-1, "vh_nls_batch_multi: at most 255 free cameras");
-    if (workspace_bytes_per_window < vh_ba_workspace_bytes(nt, nc, ba_parts(nt, nc)) || workspace_bytes_per_window % 256)
-        return vh_fail(-1, "vh_nls_batch_multi: per-window workspace too small or not a multiple of 256 bytes");
+    if (nwin < 1 || nwin > 65535) return vh_fail(-1, "vh_nls_batch_multi: bad arguments");
     BaProblem P;
+    if (int r = ba_problem(P, c, "vh_nls_batch_multi", K_host, z, x, nt, nc, max_iter, trace, info, workspace,
+                           workspace_bytes_per_window % 256 ? 0 : workspace_bytes_per_window,  // a stride that would misalign the next window counts as too small
+                           "per-window workspace too small or not a multiple of 256 bytes"))
+        return r;
     P.nt_win = nt_win_dev; P.K_win = K_win_dev;
-    P.graph_cache = c->ba_graph_on ? &c->ba_graphs : nullptr;
-    P.ctx = c;
-    for (int k = 0; k < 9; k++) P.K[k] = (double)K_host[k];
-    P.z = z; P.x = x; P.trace = trace; P.info = info; P.workspace = workspace; P.nt = nt; P.nc = nc; P.max_iter = max_iter; P.force_valu = g_ba_force_valu.load(std::memory_order_relaxed);
-    // fewer partial systems per window when many windows fill the chip anyway (the partials are reduced through HBM)
-    int parts = ba_parts(nt, nc), cap = 512 / nwin < 16 ? 16 : 512 / nwin;
-    P.nparts = nwin > 1 && parts > cap ? cap : parts;
-    P.phase = -1; P.it = 0; P.add_identity = 1; P.count_cams = 1; P.defer_finalize = 0; P.model = 0;
-    P.nx_total = 3.0 * nt + 6.0 * nc; P.nz_total = 2.0 * nt * (nc + 1);
+    P.nparts = ba_parts(nt, nc, nwin);
     P.nwin = nwin; P.ws_stride = workspace_bytes_per_window; P.z_stride = (size_t)2 * nt * (nc + 1); P.x_stride = (size_t)3 * nt + 6 * (size_t)nc;
     P.trace_stride = trace_stride; P.info_stride = info_stride;
-    int r = vh_ba_run(P, vh_ctx_bind(c, stream));
-    if (r) return vh_fail(r, "vh_ba_run failed");
-    return 0;
+    return ba_run_checked(P, c, stream);
 }
 
 // fcnNLS_batch2 (NLS.py:253-328): tie points + ONE joint rotation + a straight-line camera trajectory (el, az, one range per camera)
 extern "C" VH_API int vh_nls_batch2(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int max_iter, double* trace,
                                     int* info, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!c || !K_host || nt < 1 || nc < 1 || max_iter < 1) return vh_fail(-1, "vh_nls_batch2: bad arguments");
-    if (nc > 255) return vh_fail(-1, "vh_nls_batch2: at most 255 free cameras");
-    if (workspace_bytes < vh_ba_workspace_bytes(nt, nc, ba_parts(nt, nc))) return vh_fail(-1, "vh_nls_batch2: workspace too small");
     BaProblem P;
-    P.graph_cache = c->ba_graph_on ? &c->ba_graphs : nullptr;
-    P.ctx = c;
-    for (int k = 0; k < 9; k++) P.K[k] = (double)K_host[k];
-    P.z = z; P.x = x; P.trace = trace; P.info = info; P.workspace = workspace; P.nt = nt; P.nc = nc; P.max_iter = max_iter; P.nparts = ba_parts(nt, nc); P.force_valu = 1;
-    P.phase = -1; P.it = 0; P.add_identity = 1; P.count_cams = 1; P.defer_finalize = 0; P.model = 1;
-    P.nwin = 1; P.ws_stride = P.z_stride = P.x_stride = P.trace_stride = P.info_stride = 0;
-    P.nx_total = 3.0 * nt + nc + 5.0; P.nz_total = 2.0 * nt * (nc + 1);
-    int r = vh_ba_run(P, vh_ctx_bind(c, stream));
-    if (r) return vh_fail(r, "vh_ba_run failed");
-    return 0;
+    if (int r = ba_problem(P, c, "vh_nls_batch2", K_host, z, x, nt, nc, max_iter, trace, info, workspace, workspace_bytes)) return r;
+    P.model = 1; P.force_valu = 1;
+    P.nx_total = 3.0 * nt + nc + 5.0;
+    return ba_run_checked(P, c, stream);
 }
 
 // One phase of a point-sharded BA iteration: this rank owns nt tie points, all nc cameras are replicated.
@@ -995,21 +993,12 @@ extern "C" VH_API int vh_nls_batch_phase(vh_ctx* c, const double* K_host, const 
                                          int phase, int it, double* trace, int* info, void* workspace, size_t workspace_bytes,
                                          size_t* span_offset, size_t* span_doubles, void* stream)
 {
-    if (!c || !K_host || nt < 1 || nc < 1 || nt_total < nt) return vh_fail(-1, "vh_nls_batch_phase: bad arguments");
-    if (nc > 255) return vh_fail(-1, "vh_nls_batch_phase: at most 255 free cameras");
-    if (workspace_bytes < vh_ba_workspace_bytes(nt, nc, ba_parts(nt, nc))) return vh_fail(-1, "vh_nls_batch_phase: workspace too small");
+    if (nt_total < nt) return vh_fail(-1, "vh_nls_batch_phase: bad arguments");
     BaProblem P;
-    P.graph_cache = c->ba_graph_on ? &c->ba_graphs : nullptr;
-    P.ctx = c;
-    for (int k = 0; k < 9; k++) P.K[k] = (double)K_host[k];
-    P.z = z; P.x = x; P.trace = trace; P.info = info; P.workspace = workspace; P.nt = nt; P.nc = nc; P.max_iter = 1; P.nparts = ba_parts(nt, nc);
-    P.force_valu = g_ba_force_valu.load(std::memory_order_relaxed);
-    P.phase = phase; P.it = it; P.add_identity = rank0 ? 1 : 0; P.count_cams = rank0 ? 1 : 0; P.defer_finalize = 1; P.model = 0;
-    P.nwin = 1; P.ws_stride = P.z_stride = P.x_stride = P.trace_stride = P.info_stride = 0;
+    if (int r = ba_problem(P, c, "vh_nls_batch_phase", K_host, z, x, nt, nc, 1, trace, info, workspace, workspace_bytes)) return r;
+    P.phase = phase; P.it = it; P.add_identity = rank0 ? 1 : 0; P.count_cams = rank0 ? 1 : 0; P.defer_finalize = 1;
     P.nx_total = 3.0 * nt_total + 6.0 * nc; P.nz_total = 2.0 * nt_total * (nc + 1);
     if (span_offset && span_doubles) vh_ba_exchange_span(P, span_offset, span_doubles);
     if (phase < 0 || phase > 3) return vh_fail(-1, "vh_nls_batch_phase: phase must be 0..3");
-    int r = vh_ba_run(P, vh_ctx_bind(c, stream));
-    if (r) return vh_fail(r, "vh_ba_run failed");
-    return 0;
+    return ba_run_checked(P, c, stream);
 }

@@ -9,6 +9,7 @@
 // Everything stays on the device for all iterations (the convergence test only sets a device flag).
 #include <atomic>
 #include "vh_ba.hpp"
+#include "vh_ba_plan.hpp"
 #include <type_traits>
 #include "vh_ws.hpp"
 #include <algorithm>
@@ -17,11 +18,6 @@
 #include <new>
 
 #define BA_FD 1e-6
-#define BA_THREADS 256
-#define BA_EPT 64  // Schur entries owned by one thread per pass
-#define BA_MAX_NC 255                       // free cameras: a k_ba_jac workgroup (256 threads) owns whole points, one thread per frame (the reference has no limit)
-#define BA_MAX_NC_VALU 128                  // ... of the VALU Schur kernel (test hook / fcnNLS_batch2's trajectory model excepted: nc + 5 unknowns)
-#define BA_ZB_MAX 256                        // workgroups of k_ba_zbuild (43+ cameras): one partial right-hand side / set of diagonal blocks each
 #define BA_RQ ((6 * BA_MAX_NC_VALU + BA_THREADS - 1) / BA_THREADS)  // reduced right-hand-side entries owned by one thread of the VALU Schur kernel
 
 // batched windows: shift every pointer of the job to window w (the job travels by value, so this edits the kernel's own copy)
@@ -465,7 +461,6 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_points(BaJob J, int pass)
 //     registers), so two workgroups fit a CU and one's global-load latency hides behind the other's matrix-core time.
 //     Z is also what the back-substitution needs: dp_i = tp_i - L_i (Z_i dc).
 typedef double double4v __attribute__((ext_vector_type(4)));
-#define BA_NPAD 128
 
 // ---- k_ba_schur_mfma: data flow --------------------------------------------------------------------------------------------------------
 // The inputs of one tie point ("raw record": its camera Jacobians Jc [nc][12], point Jacobians Jp [nc][6], residuals r [nc][2], L (6), tp (3);
@@ -643,7 +638,6 @@ __device__ __forceinline__ void ba_lds_barrier() { asm volatile("s_waitcnt lgkmc
 // wavefront issues in order and serialised the two (measured: MFMA, VALU and memory time simply added up).  One workgroup barrier per group.
 // `pass` (NP = 256 only): consumer jobs 4 pass .. 4 pass + 3 of the NT / 2 = 8.  The diagonal blocks V_c and the right-hand side are accumulated and added by
 // the LAST pass: by then every tile they touch is final (the earlier pass is a finished launch, this block's own tiles are stored before barrier (C)).
-#define BA_SCHUR_THREADS 512
 template <int NP, int PASS>
 __global__ __launch_bounds__(BA_SCHUR_THREADS) void k_ba_schur_mfma(BaJob J)
 {
@@ -781,7 +775,6 @@ __global__ __launch_bounds__(BA_SCHUR_THREADS) void k_ba_schur_mfma(BaJob J)
 //                    16 tiles of a wavefront are 128 accumulator registers), so the launch is sized to ONE resident round: npairs x nsplit <= 256.
 //                    Z is read from L2 / the infinity cache 2 x (number of macro-tile columns) times.
 // The partial systems are summed by k_ba_reduce exactly as for the smaller kernels (upper-triangle 16 x 16 tiles, mirrored there).
-#define BA_ZB_PL 4  // points a k_ba_zbuild block works on at a time (threadIdx.y)
 __global__ __launch_bounds__(256 * BA_ZB_PL) void k_ba_zbuild(BaJob J)
 {
     ba_select_window(J, blockIdx.z);
@@ -1180,9 +1173,6 @@ __device__ __forceinline__ void ba_inv4_col(const double (&P)[4][4], int col, do
 }
 
 #define BA_GJ_N 128
-#define BA_GJ_MAXQ 124  // the last pivot block must end before the rhs column (127)
-#define BA_GJ_WAVES 8   // one 16-row tile row per wavefront, two wavefronts per SIMD: the per-round hand-over (accumulator read-back, LDS publish, waits) is
-                        // per-wavefront serial work, so halving each wavefront's share and letting two of them interleave on a SIMD shortens the round
 __global__ __launch_bounds__(64 * BA_GJ_WAVES) void k_ba_solve_mfma(BaJob J)
 {
     ba_select_window(J, blockIdx.y);
@@ -1296,7 +1286,6 @@ __global__ __launch_bounds__(64 * BA_GJ_WAVES) void k_ba_solve_mfma(BaJob J)
 // and at the end k_ba_chol_back: L^T dc = y, panel by panel from the last (a matrix-vector product over the rows below, then a 32-step triangular solve).
 // Measured at 252 unknowns (8 panels): panel kernel 17-32 us (4.6 us the register Cholesky of the diagonal block, up to 9 us the rows below, the rest
 // launch + three dependent L2 round trips), update 6.7 us, back-substitution 28 us: 265 us per solve against 1331 us (the spilling elimination kernel).  Same result as the elimination kernels to rounding (no pivoting needed or done in either).
-#define BA_CH_NB 32
 // wave-uniform copy of lane `l`'s double (l is a constant after unrolling: two v_readlane_b32 with an immediate lane)
 __device__ __forceinline__ double ba_readlane_f64(double v, int l)
 {
@@ -1458,10 +1447,6 @@ __global__ __launch_bounds__(256) void k_ba_chol_update(BaJob J, int k0)
 // workgroup forms the diagonal block redundantly: 32 x 32 x k0 flops buy the absence of a grid-wide dependency) -- then factors the diagonal block (one
 // wavefront, registers, as above) and forward-substitutes its rows.  Only workgroup 0 writes the diagonal factor back.
 // At 768 unknowns (24 panels): 1115 + 175 us for k_ba_chol_panel + k_ba_chol_update per solve before.
-#define BA_CL_RB 32
-#define BA_CL_KC 128                          // columns of L per LDS stage
-#define BA_CL_XP (BA_CL_KC + 2)               // pitch = 4 banks mod 64: the 16 rows x 4 columns of an MFMA operand read hit 64 different banks
-#define BA_CL_LDS ((BA_CH_NB + BA_CL_RB) * BA_CL_XP * 8)
 __global__ __launch_bounds__(256) void k_ba_chol_left(BaJob J, int k0)
 {
     ba_select_window(J, blockIdx.y);
@@ -1626,7 +1611,6 @@ __global__ __launch_bounds__(256) void k_ba_chol_left(BaJob J, int k0)
 
 // L^T dc = y, from the last panel to the first (one workgroup of 1024 threads: the product over the rows below a panel is split 32 ways -- with 8 slices of
 // 256 threads a thread walked up to 92 rows of dependent loads, 160 us per solve at 768 unknowns)
-#define BA_CB_THREADS 1024
 __global__ __launch_bounds__(BA_CB_THREADS) void k_ba_chol_back(BaJob J, int blocks_apart)
 {
     ba_select_window(J, blockIdx.y);
@@ -1786,7 +1770,6 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_update(BaJob J, int it)
 // measurement arrive as nine 16-byte loads issued together -- one memory round trip per point instead of the five dependent ones of the 4-lanes-per-point
 // loop (round 5: 20 -> ~9 us for one C5 window, whose Jacobians were written by other XCDs in the previous launch and come from the infinity cache / HBM)
 // Up to 20 000 points per launch (latency regime); more take k_ba_update_z4.
-#define BA_UZ_LPP 32  // lanes per point
 template <int BA_UZ_THREADS>
 __global__ __launch_bounds__(BA_UZ_THREADS) void k_ba_update_z(BaJob J, int it)
 {
@@ -1912,8 +1895,8 @@ __global__ void k_ba_init(BaJob J, double* flags0)
 // replayable launch sequences (hipGraph) of whole solves, owned by the vh_ctx that issues them
 struct BaGraphKey {
     BaJob J;
-    double* flags0;
-    int max_iter, nparts, use_mfma, pad_;
+    BaPlan plan;  // nparts, routes and grids
+    int max_iter, pad_;
 };
 struct BaGraphEntry {
     BaGraphKey key;
@@ -1969,23 +1952,12 @@ void vh_ba_graph_cache_free(void* cache)
     delete c;
 }
 
-size_t vh_ba_workspace_bytes(int nt, int nc, int nparts)
-{
-    const size_t nf = nc + 1, nq = 6 * (size_t)nc, m = (size_t)nt * nf;
-    size_t b = 0;
-    auto add = [&](size_t n) { b += (n * sizeof(double) + 255) / 256 * 256; };
-    const bool big = nq > 252;  // 43+ cameras: per-workgroup partials of k_ba_zbuild (see there)
-    add(36 * nf); add(2 * m); add(6 * m); add(12 * m); add(3 * (size_t)nt); add(6 * (size_t)nt); add(3 * nq * nt); add(nparts * nq * nq);
-    add((big ? std::max((size_t)nparts, (size_t)BA_ZB_MAX) : (size_t)nparts) * nq); add(big ? (size_t)BA_ZB_MAX * 36 * nc : 0);
-    add(nq * (nq + 1) + 4); add(nq); add(32);
-    return b + 1024;
-}
+size_t vh_ba_workspace_bytes(int nt, int nc, int nparts) { return ba_workspace_bytes(nt, nc, nparts); }
 
-static void ba_layout(const BaProblem& P, BaJob& J, double*& flags)
+static void ba_layout(const BaProblem& P, BaJob& J)
 {
-    const int nt = P.nt, nc = P.nc, nq = 6 * nc, nparts = P.nparts;
-    J.nt = nt; J.nc = nc;
-    J.model = P.model; J.nq = P.model == 1 ? nc + 5 : 6 * nc;  // buffers are sized for 6 nc >= nc + 5
+    J.nt = P.nt; J.nc = P.nc;
+    J.model = P.model; J.nq = P.model == 1 ? P.nc + 5 : 6 * P.nc;
     for (int k = 0; k < 9; k++) J.K[k] = P.K[k];
     J.z = P.z; J.x = P.x; J.trace = P.trace; J.info = P.info;
     J.add_identity = P.add_identity; J.count_cams = P.count_cams; J.defer_finalize = P.defer_finalize;
@@ -1993,81 +1965,60 @@ static void ba_layout(const BaProblem& P, BaJob& J, double*& flags)
     J.nwin = P.nwin < 1 ? 1 : P.nwin;
     J.nt_win = P.nt_win; J.K_win = P.K_win;
     J.ws_stride = P.ws_stride; J.z_stride = P.z_stride; J.x_stride = P.x_stride; J.trace_stride = P.trace_stride; J.info_stride = P.info_stride;
-    char* w = reinterpret_cast<char*>(P.workspace);
-    auto take = [&](size_t n) { double* p = reinterpret_cast<double*>(w); w += (n * sizeof(double) + 255) / 256 * 256; return p; };
-    const size_t nf = nc + 1, m = (size_t)nt * nf;
-    J.camR = take(36 * nf); J.r = take(2 * m); J.Jp = take(6 * m); J.Jc = take(12 * m); J.tp = take(3 * (size_t)nt); J.Lc = take(6 * (size_t)nt); J.Y = take(3 * (size_t)nq * nt);
-    const bool big = nq > 252;
-    J.Spart = take((size_t)nparts * nq * nq); J.Rpart = take((big ? std::max((size_t)nparts, (size_t)BA_ZB_MAX) : (size_t)nparts) * nq);
-    J.Dpart = take(big ? (size_t)BA_ZB_MAX * 36 * nc : 0);
-    J.Sfull = take((size_t)nq * (nq + 1) + 4);     // augmented system followed by the 4 accumulators: ONE all-reduce span
-    J.acc = J.Sfull + (size_t)nq * (nq + 1);
-    J.dc = take(nq);
-    flags = take(32);
-    J.done = reinterpret_cast<int*>(flags);
-    J.ticket = reinterpret_cast<unsigned*>(flags) + 4;
-    J.rslot = flags + 8;  // doubles 8..23 of the 32-double flag block
+    ba_workspace_walk(P.nt, P.nc, P.nparts, P.workspace, &J);
 }
 
 // byte offset / length (in doubles) of the all-reduce span [Sfull | acc] inside the workspace
 void vh_ba_exchange_span(const BaProblem& P, size_t* offset_bytes, size_t* n_doubles)
 {
-    BaJob J;
-    double* flags;
-    ba_layout(P, J, flags);
-    *offset_bytes = (size_t)(reinterpret_cast<char*>(J.Sfull) - reinterpret_cast<char*>(P.workspace));
+    BaFields f;
+    ba_workspace_walk(P.nt, P.nc, P.nparts, P.workspace, &f);
+    *offset_bytes = (size_t)(reinterpret_cast<char*>(f.Sfull) - reinterpret_cast<char*>(P.workspace));
     *n_doubles = (size_t)(6 * P.nc) * (6 * P.nc + 1) + 4;
+}
+
+// Instantiated kernels land in the code object in the order of their first mention in the host code.  This list mentions them first, in the order
+// they have always had, so that a rewrite of the launch code below leaves the device code byte for byte as it was (profiles/ba_host/resources.md).
+[[maybe_unused]] static void (*const ba_kernel_order[])(BaJob) = {k_ba_schur_mfma<256, 0>, k_ba_schur_mfma<256, 1>, k_ba_jac<true>, k_ba_schur_mfma<128, 0>,
+                                                                 k_ba_jac<false>};
+
+// k_ba_schur_mfma<256, *> and k_ba_chol_left use more dynamic LDS than a kernel gets by default (BaPlan::needs_big_lds).  The attribute is per
+// function AND per device: one bit per device ordinal, set with an atomic OR (two host threads, or a process that drives a second GPU, each set it
+// for their device; setting it twice is harmless)
+static hipError_t ba_raise_lds_limits()
+{
+    static std::atomic<unsigned long long> attr_devs{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (attr_devs.load(std::memory_order_acquire) & bit) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_schur_mfma<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_schur_mfma<256, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_chol_left), hipFuncAttributeMaxDynamicSharedMemorySize, BA_CL_LDS);
+    if (e == hipSuccess) attr_devs.fetch_or(bit, std::memory_order_release);
+    return e;
 }
 
 // phase -1: the whole solve on one rank.  Sharded runs (velocity_amd/dist.py): 0 = init, 1 = local normal equations ->
 // [Sfull | acc] (then all-reduced by the caller), 2 = solve + update (then acc all-reduced), 3 = iteration record.
+// What runs is decided by ba_plan (vh_ba_plan.hpp); this function launches it.
 int vh_ba_run(const BaProblem& P, hipStream_t s)
 {
-    const int nt = P.nt, nc = P.nc, nq = P.model == 1 ? nc + 5 : 6 * nc;
-    if (nc > BA_MAX_NC) return -3;
-    const int nparts = P.nparts;
+    const char* dbg_env = getenv("VH_BA_DBG");  // experiment switches, read on every call (the tests change it between solves of one process)
+    const int dbg = dbg_env ? atoi(dbg_env) : 0;
+    BaPlan plan;
+    if (int r = ba_plan(P.nt, P.nc, P.nparts, P.nwin, P.model, P.force_valu, dbg, &plan)) return r;
+    if (plan.needs_big_lds)
+        if (hipError_t e = ba_raise_lds_limits()) return (int)e;
     BaJob J;
     memset(&J, 0, sizeof(J));  // padding included: whole solves are recognised by the bytes of their descriptor (graph replay below)
-    double* flags;
-    ba_layout(P, J, flags);
+    ba_layout(P, J);
+    J.zmode = plan.zmode;
+    J.dbg = dbg;
+    double* flags = reinterpret_cast<double*>(J.done);  // the 32-double flag block of window 0
+    const int nt = P.nt, nc = P.nc, nq = plan.nq, nparts = plan.nparts;
     const long long nent = (long long)nq * nq;
-    const int npass = (int)((nent + (long long)BA_THREADS * BA_EPT - 1) / ((long long)BA_THREADS * BA_EPT));
-    const size_t lds = sizeof(double) * (size_t)(6 * nq + 12 * (nc + 1) + 16);
-    const int npad = nq <= BA_NPAD ? BA_NPAD : 2 * BA_NPAD;  // matrix-core Schur kernel: 128-wide (<= 21 cameras) or 256-wide in two passes (<= 42)
-    const size_t lds_mfma = sizeof(double) * (size_t)(24 * npad + 2 * 4 * (20 * nc + 10) + 4 * npad);
-    // the VALU test hook (vh_debug_ba_force_valu) is honoured where the VALU Schur kernel exists (<= BA_MAX_NC_VALU cameras) and ignored above: a flag
-    // left set by another test or thread must not turn a valid call into a failure
-    const bool force_valu = P.force_valu && nq <= 6 * BA_MAX_NC_VALU;
-    const bool use_mfma = nq <= 252 && !force_valu && P.model == 0;  // model 1 has nc + 5 unknowns: nothing for the matrix cores to do
-    // 43..128 cameras: Z materialised + K-split SYRK on the matrix cores (k_ba_zbuild / k_ba_syrk_mfma).  nm macro tiles of 128 per dimension; the
-    // first `nsplit` partial systems are used: about one resident round of workgroups (2 per CU), every split at least one LDS stage of points
-    const bool use_syrk = nq > 252 && !force_valu && P.model == 0;
-    if (!use_syrk && !use_mfma && nq > 6 * BA_MAX_NC_VALU) return -3;  // the VALU Schur kernel keeps 6 nc / 256 right-hand-side entries per thread and 3 x 6 nc doubles of LDS
-    const int nm = (nq + 127) / 128, npairs = nm * (nm + 1) / 2;
-    const int nsplit = use_syrk ? std::max(1, std::min(std::min(nparts, std::max(1, 512 / (npairs * (int)std::min(J.nwin < 1 ? 1 : J.nwin, 512)))), (nt + 10) / 11)) : nparts;
-    const int nzb = use_syrk ? std::max(1, std::min(BA_ZB_MAX, (nt + 2 * BA_ZB_PL - 1) / (2 * BA_ZB_PL))) : 0;  // workgroups of k_ba_zbuild: at least two rounds of points each
-    if ((use_mfma && lds_mfma > 64 * 1024) || nq > BA_GJ_MAXQ) {
-        // the attribute is per function AND per device: one bit per device ordinal, set with an atomic OR (two host threads, or a process that drives
-        // a second GPU, each set it for their device; setting it twice is harmless)
-        static std::atomic<unsigned long long> attr_devs{0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(attr_devs.load(std::memory_order_acquire) & bit)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_schur_mfma<256, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_schur_mfma<256, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_chol_left), hipFuncAttributeMaxDynamicSharedMemorySize, BA_CL_LDS);
-            if (e != hipSuccess) return (int)e;
-            attr_devs.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    J.zmode = (use_mfma || use_syrk) ? 1 : 0;
-    { const char* e = getenv("VH_BA_DBG"); J.dbg = e ? atoi(e) : 0; }
-    // one wavefront per point, grid-strided: every block ends with an atomic on one address, so keep the block count low
-    const int upd_cap = J.nwin > 1 ? std::max(16, 1024 / J.nwin) : 256;
-    const bool uz_latency = (long long)J.nwin * nt <= 20000;  // few points in flight: the 32-lanes-per-point kernel (one memory round trip); else every lane busy
-    const int uz_ppb = uz_latency ? 1024 / BA_UZ_LPP : BA_THREADS / 4;  // points per block and pass of k_ba_update_z / k_ba_update_z4
-    const int upd_blocks = std::min((use_mfma || use_syrk) ? (nt + uz_ppb - 1) / uz_ppb : (nt + BA_THREADS / 64 - 1) / (BA_THREADS / 64), upd_cap);
+    const bool syrk = plan.schur == BA_SCHUR_SYRK;
     const unsigned nw = (unsigned)J.nwin;
     auto init = [&]() -> int {
         hipLaunchKernelGGL(k_ba_init, dim3(1, nw), dim3(64), 0, s, J, flags);
@@ -2078,61 +2029,64 @@ int vh_ba_run(const BaProblem& P, hipStream_t s)
     auto normal_equations = [&](int it) {
         if (it == 0) hipLaunchKernelGGL(k_ba_cams, dim3((nc + 1 + 63) / 64, nw), dim3(64), 0, s, J);
         const int ppb = BA_THREADS / (nc + 1);  // k_ba_jac: whole points per block
-        if (use_mfma) {
-            int rec = vh_prof_start(pc, s);
-            hipLaunchKernelGGL(k_ba_jac<true>, dim3((nt + ppb - 1) / ppb, nw), dim3(BA_THREADS), 0, s, J);
-            vh_prof_stop(pc, rec, VH_PROF_BA_JAC, s);
-            rec = vh_prof_start(pc, s);
-            if (npad == BA_NPAD) hipLaunchKernelGGL((k_ba_schur_mfma<128, 0>), dim3(nparts, nw), dim3(BA_SCHUR_THREADS), lds_mfma, s, J);
-            else {
-                hipLaunchKernelGGL((k_ba_schur_mfma<256, 0>), dim3(nparts, nw), dim3(BA_SCHUR_THREADS), lds_mfma, s, J);
-                hipLaunchKernelGGL((k_ba_schur_mfma<256, 1>), dim3(nparts, nw), dim3(BA_SCHUR_THREADS), lds_mfma, s, J);
-            }
-            vh_prof_stop(pc, rec, VH_PROF_BA_SCHUR, s);
-        } else if (use_syrk) {
-            int rec = vh_prof_start(pc, s);
-            hipLaunchKernelGGL(k_ba_jac<true>, dim3((nt + ppb - 1) / ppb, nw), dim3(BA_THREADS), 0, s, J);
-            vh_prof_stop(pc, rec, VH_PROF_BA_JAC, s);
-            rec = vh_prof_start(pc, s);
-            hipLaunchKernelGGL(k_ba_zbuild, dim3(nzb, (nq + 255) / 256, nw), dim3(256, BA_ZB_PL), 0, s, J);
-            hipLaunchKernelGGL(k_ba_syrk_mfma, dim3(npairs, nsplit, nw), dim3(256), 0, s, J, nm);
-            vh_prof_stop(pc, rec, VH_PROF_BA_SCHUR, s);
-        } else {
-            int rec = vh_prof_start(pc, s);
-            hipLaunchKernelGGL(k_ba_jac<false>, dim3((nt + ppb - 1) / ppb, nw), dim3(BA_THREADS), 0, s, J);
-            vh_prof_stop(pc, rec, VH_PROF_BA_JAC, s);
-            rec = vh_prof_start(pc, s);
-            for (int pass = 0; pass < npass; pass++)  // later passes overwrite Spart entries of their own range only
-                hipLaunchKernelGGL(k_ba_points, dim3(nparts, nw), dim3(BA_THREADS), lds, s, J, pass);
-            vh_prof_stop(pc, rec, VH_PROF_BA_SCHUR, s);
+        int rec = vh_prof_start(pc, s);
+        if (plan.zmode) hipLaunchKernelGGL(k_ba_jac<true>, dim3((nt + ppb - 1) / ppb, nw), dim3(BA_THREADS), 0, s, J);
+        else hipLaunchKernelGGL(k_ba_jac<false>, dim3((nt + ppb - 1) / ppb, nw), dim3(BA_THREADS), 0, s, J);
+        vh_prof_stop(pc, rec, VH_PROF_BA_JAC, s);
+        rec = vh_prof_start(pc, s);
+        switch (plan.schur) {
+        case BA_SCHUR_MFMA128:
+            hipLaunchKernelGGL((k_ba_schur_mfma<128, 0>), dim3(nparts, nw), dim3(BA_SCHUR_THREADS), plan.lds_mfma, s, J);
+            break;
+        case BA_SCHUR_MFMA256:
+            hipLaunchKernelGGL((k_ba_schur_mfma<256, 0>), dim3(nparts, nw), dim3(BA_SCHUR_THREADS), plan.lds_mfma, s, J);
+            hipLaunchKernelGGL((k_ba_schur_mfma<256, 1>), dim3(nparts, nw), dim3(BA_SCHUR_THREADS), plan.lds_mfma, s, J);
+            break;
+        case BA_SCHUR_SYRK:
+            hipLaunchKernelGGL(k_ba_zbuild, dim3(plan.nzb, (nq + 255) / 256, nw), dim3(256, BA_ZB_PL), 0, s, J);
+            hipLaunchKernelGGL(k_ba_syrk_mfma, dim3(plan.npairs, plan.nsplit, nw), dim3(256), 0, s, J, plan.nm);
+            break;
+        case BA_SCHUR_VALU:
+            for (int pass = 0; pass < plan.npass; pass++)  // later passes overwrite Spart entries of their own range only
+                hipLaunchKernelGGL(k_ba_points, dim3(nparts, nw), dim3(BA_THREADS), plan.lds_valu, s, J, pass);
+            break;
         }
-        const int rec = vh_prof_start(pc, s);
-        if (nsplit >= 128) hipLaunchKernelGGL(k_ba_reduce<16>, dim3((unsigned)((nent + nq + 63) / 64), nw), dim3(1024), 0, s, J, nsplit, use_syrk ? nzb : nsplit, use_syrk ? nzb : 0);
-        else hipLaunchKernelGGL(k_ba_reduce<4>, dim3((unsigned)((nent + nq + 63) / 64), nw), dim3(256), 0, s, J, nsplit, use_syrk ? nzb : nsplit, use_syrk ? nzb : 0);
+        vh_prof_stop(pc, rec, VH_PROF_BA_SCHUR, s);
+        rec = vh_prof_start(pc, s);
+        const dim3 rgrid((unsigned)((nent + nq + 63) / 64), nw);
+        const int nparts_r = syrk ? plan.nzb : plan.nsplit, ndpart = syrk ? plan.nzb : 0;
+        if (plan.reduce_ns == 16) hipLaunchKernelGGL(k_ba_reduce<16>, rgrid, dim3(1024), 0, s, J, plan.nsplit, nparts_r, ndpart);
+        else hipLaunchKernelGGL(k_ba_reduce<4>, rgrid, dim3(256), 0, s, J, plan.nsplit, nparts_r, ndpart);
         vh_prof_stop(pc, rec, VH_PROF_BA_REDUCE, s);
     };
     auto solve_update = [&](int it) {
         int rec = vh_prof_start(pc, s);
-        // up to 124 unknowns (20 cameras): block Gauss-Jordan on the matrix cores; 125..127 (21 cameras: 126): the register-resident VALU Gauss-Jordan
-        if (nq <= BA_GJ_MAXQ && !(J.dbg & 64)) hipLaunchKernelGGL(k_ba_solve_mfma, dim3(1, nw), dim3(64 * BA_GJ_WAVES), 0, s, J);
-        else if (nq + 1 <= 128) hipLaunchKernelGGL((k_ba_solve<8, 8, 16>), dim3(1, nw), dim3(256), 0, s, J, nparts);
-        else {  // 128+ unknowns (22+ cameras): left-looking blocked Cholesky, ONE launch per 32-column panel, + the back-substitution
-            for (int k0 = 0; k0 < nq && !(J.dbg & 256); k0 += BA_CH_NB) {  // left-looking: one launch per panel, rows spread over workgroups
+        switch (plan.solve) {
+        case BA_SOLVE_GJ_MFMA: hipLaunchKernelGGL(k_ba_solve_mfma, dim3(1, nw), dim3(64 * BA_GJ_WAVES), 0, s, J); break;
+        case BA_SOLVE_GJ_VALU: hipLaunchKernelGGL((k_ba_solve<8, 8, 16>), dim3(1, nw), dim3(256), 0, s, J, nparts); break;
+        case BA_SOLVE_CHOL_LEFT:
+            for (int k0 = 0; k0 < nq; k0 += BA_CH_NB) {  // one launch per panel, rows spread over workgroups
                 const int rows = nq - std::min(nq, k0 + BA_CH_NB) + 1;
                 hipLaunchKernelGGL(k_ba_chol_left, dim3((rows + BA_CL_RB - 1) / BA_CL_RB, nw), dim3(256), BA_CL_LDS, s, J, k0);
             }
-            for (int k0 = 0; k0 < nq && (J.dbg & 256); k0 += BA_CH_NB) {  // right-looking kernels of round 4 (VH_BA_DBG=256: second implementation for the tests)
+            hipLaunchKernelGGL(k_ba_chol_back, dim3(1, nw), dim3(BA_CB_THREADS), sizeof(double) * (size_t)nq, s, J, 1);
+            break;
+        case BA_SOLVE_CHOL_RIGHT:
+            for (int k0 = 0; k0 < nq; k0 += BA_CH_NB) {
                 hipLaunchKernelGGL(k_ba_chol_panel, dim3(1, nw), dim3(256), 0, s, J, k0);
                 const int r0 = std::min(nq, k0 + BA_CH_NB), ntile = (nq - r0 + BA_CH_NB - 1) / BA_CH_NB;
                 if (ntile > 0) hipLaunchKernelGGL(k_ba_chol_update, dim3(ntile + 1, ntile, nw), dim3(256), 0, s, J, k0);
             }
-            hipLaunchKernelGGL(k_ba_chol_back, dim3(1, nw), dim3(BA_CB_THREADS), sizeof(double) * (size_t)nq, s, J, (J.dbg & 256) ? 0 : 1);
+            hipLaunchKernelGGL(k_ba_chol_back, dim3(1, nw), dim3(BA_CB_THREADS), sizeof(double) * (size_t)nq, s, J, 0);
+            break;
         }
         vh_prof_stop(pc, rec, VH_PROF_BA_SOLVE, s);
         rec = vh_prof_start(pc, s);
-        if (J.zmode && uz_latency) hipLaunchKernelGGL(k_ba_update_z<1024>, dim3(upd_blocks + 1, nw), dim3(1024), 0, s, J, it);  // (+ 1: the camera block)
-        else if (J.zmode) hipLaunchKernelGGL(k_ba_update_z4, dim3(upd_blocks, nw), dim3(BA_THREADS), 0, s, J, it);
-        else hipLaunchKernelGGL(k_ba_update, dim3(upd_blocks, nw), dim3(BA_THREADS), 0, s, J, it);
+        switch (plan.update) {
+        case BA_UPDATE_Z_LATENCY: hipLaunchKernelGGL(k_ba_update_z<1024>, dim3(plan.upd_blocks + 1, nw), dim3(1024), 0, s, J, it); break;  // (+ 1: the camera block)
+        case BA_UPDATE_Z4: hipLaunchKernelGGL(k_ba_update_z4, dim3(plan.upd_blocks, nw), dim3(BA_THREADS), 0, s, J, it); break;
+        case BA_UPDATE_POINTS: hipLaunchKernelGGL(k_ba_update, dim3(plan.upd_blocks, nw), dim3(BA_THREADS), 0, s, J, it); break;
+        }
         vh_prof_stop(pc, rec, VH_PROF_BA_UPDATE, s);
     };
     switch (P.phase) {
@@ -2142,7 +2096,7 @@ int vh_ba_run(const BaProblem& P, hipStream_t s)
         // throttled host otherwise shows up as idle gaps between the 10-60 us kernels of a single window).  The second sighting builds the graph.
         BaGraphKey key;
         memset(&key, 0, sizeof(key));
-        memcpy(&key.J, &J, sizeof(J)); key.flags0 = flags; key.max_iter = P.max_iter; key.nparts = nparts; key.use_mfma = use_mfma ? 1 : (use_syrk ? 2 : 0);
+        memcpy(&key.J, &J, sizeof(J)); memcpy(&key.plan, &plan, sizeof(plan)); key.max_iter = P.max_iter;
         BaGraphCache* gc = profiling ? nullptr : ba_graph_cache(P.graph_cache);
         BaGraphEntry* e = gc ? gc->find(key, s) : nullptr;
         if (e && e->exec && !gc->disabled) {

@@ -31,7 +31,8 @@ struct BaJob {  // passed by value to every BA kernel
     int nq;     // reduced unknowns: 6 nc (model 0) or nc + 5 (model 1)
     int model;  // 0: fcnNLS_batch (free cameras, NLS.py:186-250); 1: fcnNLS_batch2 (joint rotation + straight-line trajectory, NLS.py:253-328)
     int add_identity, count_cams, defer_finalize;
-    int dbg;    // experiment switches (VH_BA_DBG): 1 skip MFMA, 2 skip Z / diag VALU, 4 skip global fetch, 8 skip barrier, 64 VALU Gauss-Jordan solve, 128 elimination kernels above 128 unknowns, 256 right-looking Cholesky (two launches per panel)
+    int dbg;    // experiment switches (VH_BA_DBG, tools/ba_dbg.sh).  Read by k_ba_schur_mfma: 1 skip MFMA, 2 skip the diagonal blocks (VALU), 4 skip global fetch, 8 skip barrier,
+                // 16 skip parking the raw records in LDS, 32 skip forming Z.  Read by ba_plan (vh_ba_plan.hpp), ignored on the device: 64 VALU Gauss-Jordan solve, 256 right-looking Cholesky (two launches per panel)
     int zmode;  // 1: Y holds Z = L^T W and Spart holds only the upper-triangle 16x16 tiles (k_ba_schur_mfma); 0: Y = (U+I)^-1 W, full Spart
     // batched independent windows (vh_nls_batch_multi): blockIdx.y selects the window; every pointer above is window 0's
     int nwin;
@@ -45,25 +46,25 @@ struct BaJob {  // passed by value to every BA kernel
     const double* K_win;             // [nwin][9] intrinsics of each window
 };
 
-struct BaProblem {
-    double K[9];
-    const double* z;
-    double* x;
-    double* trace;
-    int* info;
-    void* workspace;
-    int nt, nc, max_iter, nparts;
-    int phase, it;   // phase -1: whole solve; 0..3: the pieces of one sharded iteration (see vh_ba_run)
-    int add_identity, count_cams, defer_finalize;
-    double nx_total, nz_total;
-    int model;       // see BaJob::model
-    int force_valu;  // test hook: 1 = accumulate the reduced camera system on the VALU instead of the matrix cores
-    int nwin;        // independent windows solved by the same launches (>= 1); z, x, trace, info and workspace are arrays of nwin
-    size_t ws_stride, z_stride, x_stride, trace_stride, info_stride;  // see BaJob (ignored when nwin == 1)
+struct BaProblem {  // every field defaults to zero / null: an entry point sets what it uses (ba_problem in vh_api.hip fills the single-window defaults)
+    double K[9] = {};
+    const double* z = nullptr;
+    double* x = nullptr;
+    double* trace = nullptr;
+    int* info = nullptr;
+    void* workspace = nullptr;
+    int nt = 0, nc = 0, max_iter = 0, nparts = 0;
+    int phase = 0, it = 0;   // phase -1: whole solve; 0..3: the pieces of one sharded iteration (see vh_ba_run)
+    int add_identity = 0, count_cams = 0, defer_finalize = 0;
+    double nx_total = 0, nz_total = 0;
+    int model = 0;       // see BaJob::model
+    int force_valu = 0;  // test hook: 1 = accumulate the reduced camera system on the VALU instead of the matrix cores
+    int nwin = 0;        // independent windows solved by the same launches (>= 1); z, x, trace, info and workspace are arrays of nwin
+    size_t ws_stride = 0, z_stride = 0, x_stride = 0, trace_stride = 0, info_stride = 0;  // see BaJob (ignored when nwin == 1)
     const int* nt_win = nullptr;  // see BaJob (device, may be null)
     const double* K_win = nullptr;
-    struct vh_ctx* ctx;  // may be null: per-kernel HIP-event timing when its profiling is on (vh_profile_begin)
-    void** graph_cache;  // may be null: where the owner (vh_ctx) keeps the replayable launch sequences of whole solves (vh_ba_graph_cache_free)
+    struct vh_ctx* ctx = nullptr;  // may be null: per-kernel HIP-event timing when its profiling is on (vh_profile_begin)
+    void** graph_cache = nullptr;  // may be null: where the owner (vh_ctx) keeps the replayable launch sequences of whole solves (vh_ba_graph_cache_free)
 };
 void vh_ba_graph_cache_free(void* cache);
 
