@@ -527,9 +527,13 @@ VH_API void vh_debug_force_generic_lk(int on);
 /* test hook (vh_version >= 105): launch slots one workgroup of the one-wavefront LDS-staged LK kernel (k_lk3<.., 1, ..>, routes 3 and 5) solves one after the
  * other -- 0: chosen by load (1 below 49 152 tracks in flight, 2 from there, 4 from 98 304), n > 0: n (clamped to 8).  Bit-identical results. */
 VH_API void vh_debug_lk3_tpw(int n);
+/* test hook: 1 (the default): an LK job with max_level = 0 takes the single-level form of the LDS-staged kernel k_lk3 (routes 3, 5, 6, 7), 0: it takes
+ * the general form, whose level loop then runs once.  Bit-identical results. */
+VH_API void vh_debug_lk3_one_level(int on);
 /* test hook (vh_version >= 111): residency of the one-wavefront 51x51 LDS-staged kernel (k_lk3<51, 1, 4>, route 5) as the runtime sees it, at the dynamic
  * LDS size its launches pass -- out[0]: workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor), out[1]: registers per lane, out[2]: scratch bytes
- * per lane, out[3]: LDS bytes per workgroup (hipFuncGetAttributes + the dynamic size).  Launches no kernel. */
+ * per lane, out[3]: LDS bytes per workgroup (hipFuncGetAttributes + the dynamic size).  Launches no kernel.  The kernel has a general and a single-level
+ * form (vh_debug_lk3_one_level): of each figure the worse of the two is reported. */
 VH_API int vh_debug_lk3_residency(int out[4]);
 
 /* test hook: estimateAffine2D stand-in -- 1: always the three-kernel path (hypotheses spread over the chip), 2: the fused

@@ -131,6 +131,7 @@ _SIGS = {
     "vh_debug_pyr_rows": (None, [C.c_int]),
     "vh_debug_klt_order": (None, [C.c_int]),
     "vh_debug_lk3_tpw": (None, [C.c_int]),
+    "vh_debug_lk3_one_level": (None, [C.c_int]),
     "vh_debug_lk3_residency": (C.c_int, [i32p]),
     "vh_profile_lk_tpw": (C.c_int, [vp, i32p]),
     "vh_profile_begin": (C.c_int, [vp, C.c_int]),

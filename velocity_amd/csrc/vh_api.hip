@@ -272,11 +272,12 @@ __device__ void klt_setup_descriptors(StreamWS& ws, const SessStream* ss_all, co
 __global__ __launch_bounds__(256) void k_klt_glue1(StreamWS* ws_all) { klt_glue1_body<256>(ws_all[blockIdx.x]); }
 __global__ void k_klt_glue2(StreamWS* ws_all) { klt_glue2_body(ws_all[blockIdx.x]); }
 
-static int launch_lk_profiled(vh_ctx* c, int stage, const void* tab, size_t st, int count, int win, hipStream_t s, int mn)
+static int launch_lk_profiled(vh_ctx* c, int stage, const void* tab, size_t st, int count, const vh_lk_params& lk, hipStream_t s, int mn)
 {
     const int rec = vh_prof_start(c, s, 1);
     int route = 0, tpw = 1;
-    const int r = vh_launch_lk(tab, st, count, mn, win, s, &route, &tpw);
+    const int win = lk.win;
+    const int r = vh_launch_lk(tab, st, count, mn, win, s, &route, &tpw, lk.max_level);
     if (c && stage >= 0 && stage < 3) { c->lk_route[stage] = route; c->lk_win[stage] = win; c->lk_tpw[stage] = tpw; }
     vh_prof_stop(c, rec, stage, s);
     return r;
@@ -304,7 +305,7 @@ int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_p
     hipLaunchKernelGGL(k_klt_setup, dim3(count), dim3(use_order ? KO_THREADS : 64), 0, s, ws, sess ? sess + slot : nullptr, frames, coarse, fine, use_order);
     VH_PROFILED(c, VH_PROF_RESIZE, s, vh_launch_resize_quarter(&ws->rs_src[0], &ws->rs_dst[0], st, 2, count, c->sw, c->sh, s));
     VH_PROFILED(c, VH_PROF_PYR, s, for (int l = 0; l < lvl_c; l++) vh_launch_pyr_down_ws(&ws->pb[0], st, count, l, c->sw, c->sh, s));
-    int r = launch_lk_profiled(c, 0, &ws->lk, st, count, coarse.win, s, mn);
+    int r = launch_lk_profiled(c, 0, &ws->lk, st, count, coarse, s, mn);
     if (r) return vh_fail(r, "vh_launch_lk failed (window too large for LDS?)");
     // RANSAC + the glue that follows it: ONE launch when the fused one-workgroup-per-stream kernel serves the problem (it runs the glue as its epilogue),
     // else the three RANSAC launches and the glue kernel (which does the zero-padded shifted crop itself when one is needed)
@@ -312,13 +313,13 @@ int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_p
     VH_PROFILED(c, VH_PROF_RANSAC, s, glued = vh_launch_ransac(&ws->ransac, st, count, mn, s, ws, 1));
     if (!glued) hipLaunchKernelGGL(k_klt_glue1, dim3(count), dim3(256), 0, s, ws);
     VH_PROFILED(c, VH_PROF_PYR, s, for (int l = 0; l < lvl_c; l++) vh_launch_pyr_down_ws(&ws->pb[0], st, count, l, c->max_w, c->max_h, s));
-    r = launch_lk_profiled(c, 1, &ws->lk, st, count, coarse.win, s, mn);
+    r = launch_lk_profiled(c, 1, &ws->lk, st, count, coarse, s, mn);
     if (r) return vh_fail(r, "vh_launch_lk failed");
     VH_PROFILED(c, VH_PROF_RANSAC, s, glued = vh_launch_ransac(&ws->ransac, st, count, mn, s, ws, 2));
     if (!glued) hipLaunchKernelGGL(k_klt_glue2, dim3(count), dim3(64), 0, s, ws);
     VH_PROFILED(c, VH_PROF_WARP, s, vh_launch_roi_warp(&ws->warp, st, count, c->max_w, c->max_h, s));
     if (lvl_f > 0) VH_PROFILED(c, VH_PROF_PYR, s, for (int l = 0; l < lvl_f; l++) vh_launch_pyr_down_ws(&ws->pb[0], st, count, l, c->max_w, c->max_h, s));
-    r = launch_lk_profiled(c, 2, &ws->lk, st, count, fine.win, s, mn);
+    r = launch_lk_profiled(c, 2, &ws->lk, st, count, fine, s, mn);
     if (r) return vh_fail(r, "vh_launch_lk failed");
     VH_LAUNCH_CHECK();
     return 0;
@@ -425,6 +426,8 @@ extern "C" VH_API int vh_profile_lk_tpw(vh_ctx* c, int* tpw_host)
 
 void vh_lk3_set_tpw(int n);
 extern "C" VH_API void vh_debug_lk3_tpw(int n) { vh_lk3_set_tpw(n); }
+void vh_lk3_set_one_level(int on);
+extern "C" VH_API void vh_debug_lk3_one_level(int on) { vh_lk3_set_one_level(on); }
 
 int vh_lk3_residency(int out[4]);
 extern "C" VH_API int vh_debug_lk3_residency(int out[4])
@@ -658,7 +661,7 @@ extern "C" VH_API int vh_pyr_lk(vh_ctx* c, const uint8_t* im1, const uint8_t* im
     VH_CHECK(vh_store(&ws->pb[1], PyrBuild{&ws->lk.J, 1, 0}, s));
     const int lv = lk->max_level < VH_MAX_LEVELS - 1 ? lk->max_level : VH_MAX_LEVELS - 1;
     for (int l = 0; l < lv; l++) vh_launch_pyr_down_ws(&ws->pb[0], sizeof(StreamWS), 1, l, w, h, s);
-    int r = vh_launch_lk(&ws->lk, sizeof(StreamWS), 1, n, lk->win, s, &c->lk_route[0], &c->lk_tpw[0]);
+    int r = vh_launch_lk(&ws->lk, sizeof(StreamWS), 1, n, lk->win, s, &c->lk_route[0], &c->lk_tpw[0], lk->max_level);
     c->lk_win[0] = lk->win;
     if (r) return vh_fail(r, "vh_launch_lk failed (window too large for LDS?)");
     VH_LAUNCH_CHECK();
@@ -762,7 +765,7 @@ extern "C" VH_API int vh_klt_regional(vh_ctx* c, const uint8_t* im0, const uint8
     vh_launch_roi_warp(&ws->warp, sizeof(StreamWS), 1, w, h, s);
     const int lv = lk->max_level < VH_MAX_LEVELS - 1 ? lk->max_level : VH_MAX_LEVELS - 1;
     for (int l = 0; l < lv; l++) vh_launch_pyr_down_ws(&ws->pb[0], sizeof(StreamWS), 1, l, w, h, s);
-    int r = vh_launch_lk(&ws->lk, sizeof(StreamWS), 1, n, lk->win, s);
+    int r = vh_launch_lk(&ws->lk, sizeof(StreamWS), 1, n, lk->win, s, nullptr, nullptr, lk->max_level);
     if (r) return vh_fail(r, "vh_launch_lk failed (window too large for LDS?)");
     VH_LAUNCH_CHECK();
     return 0;

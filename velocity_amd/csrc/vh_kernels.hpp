@@ -56,7 +56,9 @@ struct IngestJob {
 void vh_launch_ingest_bgr(const IngestJob* jobs_dev, int count, int max_w, int max_h, hipStream_t s);
 void vh_pyr_force_rows(int rb);
 void vh_launch_roi_warp(const void* job_tab, size_t tab_stride, int batch, int max_w, int max_h, hipStream_t s);
-int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, int win, hipStream_t s, int* route_out = nullptr, int* tpw_out = nullptr);
+// max_level: LKJob::max_level of every job of the launch where the caller knows it (0 selects the single-level form of k_lk3), -1 = not stated
+int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, int win, hipStream_t s, int* route_out = nullptr, int* tpw_out = nullptr,
+                 int max_level = -1);
 bool vh_lk_window_fits(int win);  // false: no LK kernel holds a win x win window in LDS (vh_launch_lk would return -2)
 int vh_lk_max_window();           // the largest window that fits
 int vh_lk_route(int batch, int max_n, int win);           // the kernel such a launch takes (ids of vh_debug_force_generic_lk)

@@ -885,6 +885,8 @@ typedef const uint2 __attribute__((address_space(1)))* gptr_u32x2;
 typedef int __attribute__((address_space(3)))* lds_i32;
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef u32x4_t __attribute__((address_space(3)))* lds_u32x4;
+typedef unsigned u32x4_dw_t __attribute__((ext_vector_type(4), aligned(4)));  // a 16-byte global load needs dword alignment only
+typedef const u32x4_dw_t __attribute__((address_space(1)))* gptr_u32x4;
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned __attribute__((address_space(3)))* lds_u32;
 
@@ -900,36 +902,51 @@ template <int T, int ROWS, int WIDTH, int PITCH = WIDTH>  // WIDTH bytes of ever
 __device__ __forceinline__ void stage_region(const ImgDesc& im, int rx, int ry, unsigned* dst, int tid)
 {
     constexpr int DPR = WIDTH >> 2, LP = PITCH >> 2;
-    // LPR lanes per region row, T / LPR rows per batch of loads: a lane keeps its dword column, so the address of batch `it` is the first one
-    // plus the wave-uniform it * RPI * stride (no per-element division, one 32-bit add per load; hipcc's form of the flat index q / DPR cost
-    // ~12 VALU instructions per element)
-    constexpr int LPR = DPR <= 4 ? 4 : DPR <= 8 ? 8 : DPR <= 16 ? 16 : 32;
-    static_assert(DPR <= 32 && T % LPR == 0, "region rows wider than 32 dwords are not staged by this layout");
+    // LPR lanes per region row, FOUR dwords of it each, T / LPR rows per batch of loads: a lane keeps its dword columns, so the address of batch `it` is
+    // the first one plus the wave-uniform it * RPI * stride (no per-element division, one 32-bit add per batch; hipcc's form of the flat index q / DPR
+    // cost ~12 VALU instructions per element).  A lane reads the five aligned dwords that hold its 16 bytes -- one 16-byte load and the dword behind it --
+    // and stores four: a 51 x 51 region is 4 batches of 16 rows (one dword per lane, 16 lanes per row: 14 / 15 batches, an address add each).
+    // Where a row is no multiple of 4 dwords, its last lane starts at dword DPR - 4 and stores some dwords a second time (the same values), so that
+    // no lane reads past byte WIDTH + 4 of a row: what `fast` vouches for.
+    constexpr int LPR = DPR <= 4 ? 1 : DPR <= 8 ? 2 : DPR <= 16 ? 4 : 8;
+    static_assert(DPR >= 4 && DPR <= 32 && T % LPR == 0, "region rows narrower than 4 or wider than 32 dwords are not staged by this layout");
     constexpr int RPI = T / LPR, NIT = (ROWS + RPI - 1) / RPI;
     const bool fast = rx >= 0 && ry >= 0 && rx + WIDTH + 4 <= im.w && ry + ROWS <= im.h;
     if (fast) {
         const int l = tid & (LPR - 1), r0 = tid / LPR;
-        const int d = min(l, DPR - 1);
+        const int d = min(4 * l, DPR - 4);
+        // A region of fewer rows than one batch (the 15 x 15 regions, the patch of four wavefronts per track): the lanes below its last row take the
+        // place of a lane inside it whose row differs by a multiple of 4 -- the same byte phase -- and do that lane's work a second time.  (No lane
+        // may address a row >= ROWS: the row may lie outside the image, and the LDS behind the region is somebody else's.)
+        static_assert(ROWS >= 4, "a region has at least four rows");
+        const int rh = RPI <= ROWS || r0 < ROWS ? r0 : (r0 & 3);
         const unsigned bsh = (unsigned)(reinterpret_cast<uintptr_t>(im.p) & 3);
         const uint8_t* bp = im.p - bsh;  // dword aligned, wave uniform
-        const unsigned off0 = (unsigned)(__mul24(ry + r0, im.stride) + rx + 4 * d) + bsh;
+        const unsigned off0 = (unsigned)(__mul24(ry + rh, im.stride) + rx + 4 * d) + bsh;
         // A batch steps RPI rows = a multiple of 4 bytes whatever the stride is, so a lane keeps its byte phase and its dword-aligned offset over the
-        // whole staging: one 32-bit add of a wave-uniform step per load pair (was: add + 2 and)
+        // whole staging: one 32-bit add of a wave-uniform step per batch (was: add + 2 and)
         static_assert(RPI % 4 == 0, "a batch of rows must keep the byte phase of a lane");
         const unsigned sh = off0 & 3u, aoff = off0 & ~3u;
-        unsigned d0[NIT], d1[NIT];
+        // The last batch may hang over the region's last row.  A branch around its loads or its stores would split the staging into two memory round
+        // trips (and a branch around a load makes hipcc wait vmcnt(0) per element), so every lane loads and stores in every batch: a lane whose row
+        // of the last batch lies below the region does batch 0 a second time instead -- same address, same byte phase, same values to the same place
+        // (batch 0 of a lane is row rh, which is inside the region for every lane)
+        const auto row_step = [&](int it) { return (it + 1) * RPI <= ROWS || r0 + it * RPI < ROWS ? it * RPI : 0; };
+        u32x4_t q[NIT];
+        unsigned q4[NIT];
 #pragma unroll
         for (int it = 0; it < NIT; it++) {
-            // unconditional loads (row clamped in the last batch): a branch around a load makes hipcc wait vmcnt(0) per element
-            gptr_u32 ap;
-            if ((it + 1) * RPI <= ROWS) ap = (gptr_u32)(bp + (aoff + (unsigned)(it * RPI) * (unsigned)im.stride));  // scalar base + 32-bit lane offset
-            else ap = (gptr_u32)(bp + ((off0 + (unsigned)__mul24(min(it * RPI, ROWS - 1 - r0), im.stride)) & ~3u));  // clamped lanes are not stored
-            d0[it] = ap[0]; d1[it] = ap[1];
+            const uint8_t* ap = bp + (aoff + (unsigned)row_step(it) * (unsigned)im.stride);  // scalar base + 32-bit lane offset
+            q[it] = *(gptr_u32x4)ap; q4[it] = ((gptr_u32)ap)[4];  // (dword aligned: a 16-byte global load asks no more)
         }
-        if (l < DPR) {
+        unsigned* out = dst + rh * LP + d;
 #pragma unroll
-            for (int it = 0; it < NIT; it++)
-                if ((it + 1) * RPI <= ROWS || r0 + it * RPI < ROWS) dst[(r0 + it * RPI) * LP + l] = __builtin_amdgcn_alignbyte(d1[it], d0[it], sh);
+        for (int it = 0; it < NIT; it++) {
+            unsigned* o = out + row_step(it) * LP;
+            o[0] = __builtin_amdgcn_alignbyte(q[it].y, q[it].x, sh);
+            o[1] = __builtin_amdgcn_alignbyte(q[it].z, q[it].y, sh);
+            o[2] = __builtin_amdgcn_alignbyte(q[it].w, q[it].z, sh);
+            o[3] = __builtin_amdgcn_alignbyte(q4[it], q[it].w, sh);
         }
     } else {
         constexpr int TOTAL = ROWS * DPR;
@@ -1185,16 +1202,24 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
     const int max_count = job.max_count;
     const double eps2 = job.eps2;
     for (int it = 0; it < max_count; it++) {
-        int inx, iny, in = 0;
-        if constexpr (PAIR) { in = vh_floor(n); inx = pair_x(in); iny = pair_y(in); }
-        else { inx = vh_floor(nx); iny = vh_floor(ny); }
+        // iteration 0 of a top level (the only level of the fine stage) stands on the template origin: its integer origin and its weights are the set-up's,
+        // and the region was staged around it (lk_iter_at_template_origin; wave uniform, a scalar branch)
+        const bool moved = !lk_iter_at_template_origin(it, level, top_level);
+        int inx = ipx, iny = ipy, in = 0;
+        if (moved) {
+            if constexpr (PAIR) { in = vh_floor(n); inx = pair_x(in); iny = pair_y(in); }
+            else { inx = vh_floor(nx); iny = vh_floor(ny); }
+        }
         if (lk_outside(inx, iny, WIN, J)) {
             if (level == 0) status = 0;
             break;
         }
-        if (!region_holds(inx, iny)) restage(inx, iny);
-        const StripWeights w = strip_weights(PAIR ? bilinear_weights_pair(__fsub_rn(n, (float)in))
-                                                  : bilinear_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny)));
+        Win wn = w0;
+        if (moved) {
+            if (!region_holds(inx, iny)) restage(inx, iny);
+            wn = PAIR ? bilinear_weights_pair(__fsub_rn(n, (float)in)) : bilinear_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny));
+        }
+        const StripWeights w = strip_weights(wn);
         n_iter++;
         int b[2] = {ncI[0], ncI[1]};  // (lanes without strips keep -c: the first strip of the others starts from it without a copy)
         if (lane_on) {
@@ -1306,11 +1331,13 @@ __device__ __forceinline__ void LK3Level<WIN, NW, M>::operator()(const ImgDesc I
 // are resident without a spilled register (tests/test_gpu_lk3_residency.py asks the runtime).  A/B on one box against the same code held at three
 // wavefronts: fine launch 1741 -> 1646 us, the headline +1.6 % (profiles/lk3_residency/ab.json).  (-DLK3_FINE_WAVES=3: experiments only.)
 // (With the per-track arithmetic on pairs, profiles/lk3_pair/: 121 VGPRs.)
+// (profiles/lk3_setup/: 124 VGPRs, and 120 in the single-level form the fine stage runs.)
 #ifndef LK3_FINE_WAVES
 #define LK3_FINE_WAVES 4
 #endif
 #define LK3_WAVES (NW == 1 ? (WIN == 51 ? LK3_FINE_WAVES : 3) : 4)
-template <int WIN, int NW, int M>
+// ONE_LEVEL: jobs with max_level = 0 (the fine stage), see lk_track
+template <int WIN, int NW, int M, bool ONE_LEVEL = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LK3_WAVES))) void k_lk3(const void* job_tab, size_t tab_stride, unsigned grp, unsigned tpw)
 {
     unsigned blk_x0, blk_y0;
@@ -1359,7 +1386,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LK3_WAV
             const PyrDesc& PB = dir ? job.I : job.J;
             float ox, oy, e;
             int s;
-            lk_track(PA, PB, dir ? fx : px, dir ? fy : py, ox, oy, s, e, dir == 0, lf);
+            lk_track<ONE_LEVEL>(PA, PB, dir ? fx : px, dir ? fy : py, ox, oy, s, e, dir == 0, lf);
             if (dir == 0) { fx = ox; fy = oy; st = s; err = e; }
             else { bx = ox; by = oy; st2 = s; }
         }
@@ -2055,6 +2082,10 @@ static int launch_lkq(const void* job_tab, size_t tab_stride, int batch, int max
 // PROCESS-WIDE atomic like the other hooks; every value gives bit-identical results (VH_LK3_TPW: experiments only, the initial value).
 static std::atomic<int> g_lk3_tpw{getenv("VH_LK3_TPW") ? atoi(getenv("VH_LK3_TPW")) : 0};
 void vh_lk3_set_tpw(int n) { g_lk3_tpw.store(n < 0 ? 0 : n, std::memory_order_relaxed); }
+// test hook (vh_debug_lk3_one_level): 1 = jobs with max_level = 0 take the single-level form of k_lk3 (the default), 0 = they take the general form, whose
+// level loop then runs once.  Bit-identical results.  PROCESS-WIDE, as the hook above.
+static std::atomic<int> g_lk3_one_level{getenv("VH_LK3_ONE_LEVEL") ? atoi(getenv("VH_LK3_ONE_LEVEL")) : 1};  // (environment: experiments only)
+void vh_lk3_set_one_level(int on) { g_lk3_one_level.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 // dynamic LDS of a k_lk3 launch
 template <int WIN, int NW, int M>
@@ -2066,23 +2097,27 @@ static int lk3_lds_bytes()
 }
 
 // test hook (vh_debug_lk3_residency): what the runtime makes of k_lk3<51, 1, 4> at the dynamic LDS size launch_lk3 passes -- workgroups per CU, registers,
-// scratch bytes per lane, LDS bytes per workgroup.  Launches nothing.
+// scratch bytes per lane, LDS bytes per workgroup.  Launches nothing.  The kernel has two forms (general and single-level, see lk_track): of each figure
+// the WORSE of the two is reported (fewest workgroups, most registers, scratch and LDS).
 int vh_lk3_residency(int out[4])
 {
-    const void* fn = reinterpret_cast<const void*>(k_lk3<51, 1, 4>);
+    const void* fns[2] = {reinterpret_cast<const void*>(k_lk3<51, 1, 4, false>), reinterpret_cast<const void*>(k_lk3<51, 1, 4, true>)};
     const int lds = lk3_lds_bytes<51, 1, 4>();
-    int blocks = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 64, (size_t)lds);
-    if (e != hipSuccess) return (int)e;
-    hipFuncAttributes a;
-    e = hipFuncGetAttributes(&a, fn);
-    if (e != hipSuccess) return (int)e;
-    out[0] = blocks; out[1] = a.numRegs; out[2] = (int)a.localSizeBytes; out[3] = (int)a.sharedSizeBytes + lds;
+    for (int f = 0; f < 2; f++) {
+        int blocks = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fns[f], 64, (size_t)lds);
+        if (e != hipSuccess) return (int)e;
+        hipFuncAttributes a;
+        e = hipFuncGetAttributes(&a, fns[f]);
+        if (e != hipSuccess) return (int)e;
+        const int v[4] = {blocks, a.numRegs, (int)a.localSizeBytes, (int)a.sharedSizeBytes + lds};
+        for (int k = 0; k < 4; k++) out[k] = f == 0 ? v[k] : (k == 0 ? std::min(out[k], v[k]) : std::max(out[k], v[k]));
+    }
     return 0;
 }
 
 template <int WIN, int NW, int M>
-static int launch_lk3(const void* job_tab, size_t tab_stride, int batch, int max_n, hipStream_t s, int* tpw_out)
+static int launch_lk3(const void* job_tab, size_t tab_stride, int batch, int max_n, int max_level, hipStream_t s, int* tpw_out)
 {
     const int lds = lk3_lds_bytes<WIN, NW, M>();
     static const unsigned grp = getenv("VH_LK3_G") ? (unsigned)atoi(getenv("VH_LK3_G")) : 16u;  // (environment: experiments only)
@@ -2094,7 +2129,12 @@ static int launch_lk3(const void* job_tab, size_t tab_stride, int batch, int max
     const int tpw_auto = NW != 1 ? 1 : tracks >= 98304 ? 4 : tracks >= 49152 ? 2 : 1;
     const unsigned tpw = (unsigned)std::min(NW == 1 && tpw_env > 0 ? tpw_env : tpw_auto, LK3<WIN, NW, M>::MAX_TPW);
     if (tpw_out) *tpw_out = (int)tpw;
-    hipLaunchKernelGGL((k_lk3<WIN, NW, M>), dim3((max_n + tpw - 1) / tpw, batch), dim3(64 * NW), lds, s, job_tab, tab_stride, lk_group_arg(grp, batch), tpw);
+    // max_level = 0 is one level whatever the frame size is (fill_pyramid): the single-level form of the kernel.  A caller that does not say takes the general one.
+    const dim3 grid((max_n + tpw - 1) / tpw, batch);
+    if (max_level == 0 && g_lk3_one_level.load(std::memory_order_relaxed))
+        hipLaunchKernelGGL((k_lk3<WIN, NW, M, true>), grid, dim3(64 * NW), lds, s, job_tab, tab_stride, lk_group_arg(grp, batch), tpw);
+    else
+        hipLaunchKernelGGL((k_lk3<WIN, NW, M, false>), grid, dim3(64 * NW), lds, s, job_tab, tab_stride, lk_group_arg(grp, batch), tpw);
     return 0;
 }
 
@@ -2175,7 +2215,7 @@ int vh_lk_max_window()
     return win;
 }
 
-int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, int win, hipStream_t s, int* route_out, int* tpw_out)
+int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, int win, hipStream_t s, int* route_out, int* tpw_out, int max_level)
 {
     if (route_out) *route_out = 0;
     if (tpw_out) *tpw_out = 1;
@@ -2183,10 +2223,10 @@ int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, i
     const int route = vh_lk_route(batch, max_n, win);
     if (route_out) *route_out = route;
     switch (route) {
-    case 3: return launch_lk3<15, 1, 6>(job_tab, tab_stride, batch, max_n, s, tpw_out);
-    case 5: return launch_lk3<51, 1, 4>(job_tab, tab_stride, batch, max_n, s, tpw_out);
-    case 6: return launch_lk3<51, 2, 4>(job_tab, tab_stride, batch, max_n, s, tpw_out);
-    case 7: return launch_lk3<51, 4, 4>(job_tab, tab_stride, batch, max_n, s, tpw_out);
+    case 3: return launch_lk3<15, 1, 6>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
+    case 5: return launch_lk3<51, 1, 4>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
+    case 6: return launch_lk3<51, 2, 4>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
+    case 7: return launch_lk3<51, 4, 4>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
     case 8: return launch_lko<15>(job_tab, tab_stride, batch, max_n, s);
     case 4: return launch_lkq<15>(job_tab, tab_stride, batch, max_n, s);
     case 2:

@@ -83,6 +83,13 @@ __device__ __forceinline__ bool lk_level_start(float p0x, float p0y, int level, 
     return true;
 }
 
+// The first Newton iteration of the TOP level samples J where the template was sampled in I.  There lk_level_start sets nxo = cx (no = c), so
+// s.nx = cx - half is the same subtraction of the same operands as s.px: s.nx == s.px and s.ny == s.py (s.n == s.p) bit for bit.  Iteration 0 then has
+// floor(nx) = ipx, floor(ny) = ipy, the fractions nx - ipx = px - ipx, and with them the four bilinear weights (and their packed pairs) of the template
+// origin: a level functor may take all of them from its set-up instead of computing the chain again, and a region staged around floor(s.n) holds this
+// window by construction.  (A stage with max_level = 0 has nothing but top levels.)  From iteration 1 on, and on every lower level, n has moved.
+__device__ __forceinline__ bool lk_iter_at_template_origin(int it, int level, int top_level) { return it == 0 && level == top_level; }
+
 // The 2x2 system of a level from the three window sums of Ix Ix, Ix Iy, Iy Iy (exact integers, converted once to float32): false when the
 // min-eigenvalue / determinant gate rejects the window.  iD = 1 / determinant.
 struct LKSys {
@@ -247,7 +254,10 @@ __device__ __forceinline__ bool lk_final_origin_pair(float no, float half, int w
 
 // All levels of one track, coarse to fine.  `lf` is a kernel's level functor: lf(I, J, level, top_level, px, py, ox, oy, status, err, want_err) solves one
 // level and keeps what the kernel needs from level to level (its lanes' place in the window, LDS pointers, the statistics counts) as its state.
-template <class LevelFn>
+// ONE_LEVEL: the launcher vouches that the job has max_level = 0, hence one level (fill_pyramid).  The level functor is then entered with level =
+// top_level = 0 as CONSTANTS: the level loop, the per-level descriptor addressing, 2^-level and every `level != top_level` / `level == 0` test fold away
+// in the ONE copy of the functor's body, and with them the scalars a kernel otherwise carries (or parks) through the track for them.
+template <bool ONE_LEVEL = false, class LevelFn>
 __device__ __forceinline__ void lk_track(const PyrDesc& PI, const PyrDesc& PJ, float px, float py, float& ox, float& oy, int& status, float& err,
                                          bool want_err, LevelFn& lf)
 {
@@ -255,6 +265,10 @@ __device__ __forceinline__ void lk_track(const PyrDesc& PI, const PyrDesc& PJ, f
     status = 1;
     err = 0.f;
     ox = 0.f; oy = 0.f;
+    if constexpr (ONE_LEVEL) {
+        lf(PI.lv[0], PJ.lv[0], 0, 0, px, py, ox, oy, status, err, want_err);
+        return;
+    }
     for (int level = nl - 1; level >= 0; level--) lf(PI.lv[level], PJ.lv[level], level, nl - 1, px, py, ox, oy, status, err, want_err);
 }
 
