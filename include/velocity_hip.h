@@ -466,7 +466,7 @@ VH_API int vh_session_export(vh_session* s, int slot, void* rec_dev, void* strea
  * frames (frame counter nf - 1): tracks = the slot's surviving tracks (vh_session_view::ids, the tracks NLS.py:190 keeps: ascending id), z from the
  * float32 history (NLS.py:198-199), x0 = [p3[ids] | B[1:nf, 3:6] | 0] (NLS.py:202-203), K the slot's own.  The slots of one call are the windows of ONE
  * vh_nls_batch_windows launch sequence (nt = n0, nc = nf - 1): their track counts and cameras may differ, their nf may not (other lengths: another
- * call).  One record per slot, byte offsets as in vh_session_record: */
+ * call, or windows of one length through vh_session_refine_windows below).  One record per slot, byte offsets as in vh_session_record: */
 typedef struct {
     size_t bytes;                               /* size of a record (a multiple of 8)                                         */
     size_t nt, iterations, converged;           /* int32 each: tracks solved, LM iterations taken, rms(delta) < 1e-7 reached   */
@@ -491,6 +491,49 @@ VH_API size_t vh_session_refine_workspace(const vh_session* s, int nslots, int n
  * nf > nhist, a slot whose frame counter is not nf - 1, max_iter < 1, a workspace below vh_session_refine_workspace(s, nslots, nf). */
 VH_API int vh_session_refine(vh_session* s, const int* slots_host, int nslots, int nf, int max_iter, void* recs_dev, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* Bundle adjustment of ANY frame window of a clip, many windows per call (default OFF, like vh_session_refine, which is the window first = 0 of a clip
+ * that has just ended.  vh_version stays 111: a consumer tests for the symbols).  Window (slot, first) with the call's common length nf is frames
+ * [first, first + nf) of the slot's clip: the reference's fcnNLS_batch(K, P[:, :, first:first+nf], pw, cw) in the coordinates of the window's first camera.
+ *   tracks  the ids with isfinite(P[4, id, f]) for EVERY f of the window (NLS.py:190 on the slice), ascending -- selected from the history, not the
+ *           slot's current survivors: a track that died after the window belongs to it
+ *   z       the float32 history of the window's frames (NLS.py:198-199)
+ *   x0      the session's points satisfy proj(K (p3 + B[i, 3:6])) and the BA fixes its camera 0 at the origin with R = I: points p3[id] + B[first, 3:6],
+ *           camera positions B[first + c, 3:6] - B[first, 3:6] for c = 1 .. nf-1, rpy 0; float32 values widened to double first, arithmetic in double
+ *   K       the slot's own
+ * All windows of a call -- of any slots, of clips of any lengths, finished or still running -- are the windows of ONE vh_nls_batch_windows launch
+ * sequence (nt = n0, nc = nf - 1).  Clips of more than 256 frames are refined this way: the BA's 255-camera limit is per window.  What windows do NOT
+ * do: each window's scale gauge is still held only by the +I damping, and windows are independent solves (no shared points, no global adjustment). */
+typedef struct { int slot; int first; } vh_refine_window;   /* frames [first, first + nf) of the slot's clip */
+/* One record per window, byte offsets as in vh_refine_record; sized by nf, not by nhist (a long clip has many windows).  Every byte is defined. */
+typedef struct {
+    size_t bytes;                               /* size of a record (a multiple of 8)                                         */
+    size_t slot, first;                         /* int32 each: the window as given                                            */
+    size_t nt, iterations, converged;           /* int32 each: tracks solved, LM iterations taken, rms(delta) < 1e-7 reached   */
+    size_t cw;                                  /* float64[nf][3]  refined camera positions RELATIVE TO THE WINDOW'S FIRST CAMERA: row 0 zero */
+    size_t dr, speed;                           /* float64[nf]     dr_j = |cw_j - cw_(j-1)|, speed_j = dr_j / (B[first+j,12] - B[first+j-1,12]) * 3.6 with
+                                                                   the float32 time difference of vidExample.py:142; entry 0 NaN */
+    size_t speed_mean, speed_std;               /* float64: mean and (population) std of speed[1:nf] (vidExample.py:177)      */
+    size_t f_first, f_last;                     /* float64: rms residual (pixels) of the first and of the last iteration, NaN when none ran */
+    size_t trace;                               /* float64[max_iter][2] rms(z - zhat), rms(delta) per iteration, 0 behind them */
+    size_t ids;                                 /* with_points only (else 0): int32[n0] rows [0, nt) global track ids, -1 behind them */
+    size_t pw;                                  /* with_points only (else 0): float64[n0][3] rows [0, nt) refined points IN THE WINDOW'S COORDINATES
+                                                   (subtract B[first, 3:6] for the session's), NaN behind them                 */
+    int n0, nf, max_iter, with_points;
+} vh_refine_window_record;
+/* size in bytes of a record of a window of nf frames (0 and vh_last_error on bad arguments); layout_host (may be NULL) receives the offsets */
+VH_API size_t vh_session_refine_windows_size(const vh_session* s, int nf, int max_iter, int with_points, vh_refine_window_record* layout_host);
+/* bytes of device scratch a call of nwin windows of nf frames needs: it grows with nwin (0 and vh_last_error on bad arguments) */
+VH_API size_t vh_session_refine_windows_workspace(const vh_session* s, int nwin, int nf);
+/* Queues kernels only -- select + pack, the BA launch sequence, unpack -- on `stream`: no allocation, no host wait, legal between two steps; it reads
+ * the session and writes nothing of it.  recs_dev: nwin records (8-byte aligned) in the order of wins_host; workspace 256-byte aligned.  A slot may
+ * appear in many windows and need not be finished: a window must lie within the frames the slot has had, first >= 0 and first + nf - 1 <= the slot's
+ * frame counter.  A window without a track is not solved: iterations 0, converged 0, cw = the tracker's relative positions.  Returns -1 with
+ * vh_last_error naming the window and the limit, and nothing queued, for: a slot outside the session, first < 0, a window past the slot's frame
+ * counter, the same (slot, first) given twice, nf < 2, nf - 1 > 255 (the BA's camera limit, per window), nf > nhist, max_iter < 1, nwin < 1 (or above
+ * the 65535 windows of one launch sequence), misaligned buffers, a workspace below vh_session_refine_windows_workspace(s, nwin, nf). */
+VH_API int vh_session_refine_windows(vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, int max_iter, int with_points, void* recs_dev,
+                                     void* workspace, size_t workspace_bytes, void* stream);
 VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
 /* (vh_version >= 109) the recovery branch of KLTmain (utils/KLT.py:130-133) inside the session; default OFF: a step then queues exactly the launches it
  * always did and a stream whose coarse stage fails reports klt_flags & 1 and goes on with what the blind fine stage kept.

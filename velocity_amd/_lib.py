@@ -48,6 +48,19 @@ class RefineRecord(C.Structure):
                                           "f_last", "trace")] + [("n0", C.c_int), ("nhist", C.c_int), ("max_iter", C.c_int)]
 
 
+class RefineWindow(C.Structure):
+    """vh_refine_window: frames [first, first + nf) of the slot's clip."""
+
+    _fields_ = [("slot", C.c_int), ("first", C.c_int)]
+
+
+class RefineWindowRecord(C.Structure):
+    """vh_refine_window_record: byte offsets of the fields of a refined window's record (vh_session_refine_windows)."""
+
+    _fields_ = [(k, C.c_size_t) for k in ("bytes", "slot", "first", "nt", "iterations", "converged", "cw", "dr", "speed", "speed_mean", "speed_std", "f_first",
+                                          "f_last", "trace", "ids", "pw")] + [("n0", C.c_int), ("nf", C.c_int), ("max_iter", C.c_int), ("with_points", C.c_int)]
+
+
 class MatchParams(C.Structure):
     """vh_match_params (defaults: MATCH_DEFAULTS)."""
 
@@ -123,6 +136,9 @@ _SIGS = {
     "vh_session_refine_size": (C.c_size_t, [vp, C.c_int, C.POINTER(RefineRecord)]),
     "vh_session_refine_workspace": (C.c_size_t, [vp, C.c_int, C.c_int]),
     "vh_session_refine": (C.c_int, [vp, i32p, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),
+    "vh_session_refine_windows_size": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(RefineWindowRecord)]),
+    "vh_session_refine_windows_workspace": (C.c_size_t, [vp, C.c_int, C.c_int]),
+    "vh_session_refine_windows": (C.c_int, [vp, C.POINTER(RefineWindow), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),
     "vh_session_ptrs": (C.c_int, [vp, C.c_int, C.POINTER(SessionView)]),
     "vh_session_pack_state": (C.c_int, [vp, vp, vp]),
     "vh_debug_force_generic_lk": (None, [C.c_int]),

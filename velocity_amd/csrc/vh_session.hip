@@ -742,6 +742,7 @@ struct RefWs {  // the scratch of one call, carved by refine_ws_layout
     double* x;   // [nslots][3 N0 + 6 nc]
     double* K;   // [nslots][9]
     int* nt;     // [nslots]
+    int* ids;    // [nslots][N0] the tracks of each window, ascending (vh_session_refine_windows only: a whole clip's are the slot's survivors)
     char* ba;    // [nslots] BA workspaces, ba_stride bytes apart
     size_t z_stride, x_stride, ba_stride;
 };
@@ -761,7 +762,7 @@ static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_reco
     L->n0 = N0; L->nhist = nhist; L->max_iter = max_iter;
 }
 
-static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* base, RefWs* W)
+static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* base, RefWs* W, bool with_ids = false)
 {
     const size_t N0 = s->N0, nc = nf - 1, nw = nslots;
     size_t off = 0;
@@ -772,37 +773,105 @@ static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* ba
     W->x = (double*)carve(sizeof(double) * nw * W->x_stride);
     W->K = (double*)carve(sizeof(double) * 9 * nw);
     W->nt = (int*)carve(sizeof(int) * nw);
+    W->ids = with_ids ? (int*)carve(sizeof(int) * nw * N0) : nullptr;
     W->ba = carve(nw * W->ba_stride);
     return off;
+}
+
+// THE packing arithmetic of a refinement window (one copy: the whole clip is the window first = 0): frames [first, first + nf) of stream S and the n tracks
+// ids[0..n) -> z, x0 and K of one window of a vh_ba_windows problem laid out for N0 tracks.  The session's points satisfy proj(K (p3 + B[i, 3:6])) and the
+// BA fixes its camera 0 at the origin, so the window's points are p3 + B[first, 3:6] and its cameras B[first + c, 3:6] - B[first, 3:6]: float32 values
+// widened to double first, the arithmetic in double (first = 0: B[0, 3:6] is 0, both are the session's own values).
+__device__ __forceinline__ void refine_pack_window(const SessStream& S, const int* ids, int n, int first, int nf, double* z, double* x, double* Kw, int tid)
+{
+    const int N0 = S.N0, nc = nf - 1;
+    const double nanv = __longlong_as_double(0x7ff8000000000000LL);
+    // z = [all u | all v], camera-major / track-minor (NLS.py:198-199), from the frame-major float32 history; rows behind the n tracks: no observation
+    const size_t plane = (size_t)nf * N0;
+    for (size_t e = tid; e < 2 * plane; e += 256) {
+        const int row = e >= plane ? 1 : 0;
+        const size_t rem = e - (size_t)row * plane;
+        const int f = (int)(rem / N0), k = (int)(rem - (size_t)f * N0);
+        z[e] = k < n ? (double)S.P[sess_P(row, ids[k], first + f, N0)] : nanv;
+    }
+    // x0 = [p3[ids] + B[first, 3:6] | B[first + 1 : first + nf, 3:6] - B[first, 3:6] | 0] (NLS.py:202-203); padding points sit at (0, 0, 1)
+    const float* B0 = S.B + 14 * (size_t)first + 3;
+    for (int e = tid; e < 3 * N0; e += 256) {
+        const int k = e / 3, c = e - 3 * k;
+        x[e] = k < n ? S.p3[3 * (size_t)ids[k] + c] + (double)B0[c] : (c == 2 ? 1.0 : 0.0);
+    }
+    for (int e = tid; e < 3 * nc; e += 256) {
+        const int i = e / 3 + 1, c = e - 3 * (i - 1);
+        x[3 * (size_t)N0 + e] = (double)B0[14 * i + c] - (double)B0[c];
+        x[3 * (size_t)N0 + 3 * nc + e] = 0.0;
+    }
+    if (tid < 9) Kw[tid] = S.K[tid];
+}
+
+// where the derived quantities of one solved window go (both record types)
+struct RefOut {
+    int* nt;        // tracks solved
+    const int* info;  // {iterations, converged} the solve wrote
+    int* ids;       // [N0] or null
+    double* pw;     // [N0][3] or null
+    double *cw, *dr, *speed;  // [rows][3], [rows], [rows]
+    double *speed_mean, *speed_std, *f_first, *f_last;
+    const double* trace;
+    int rows, max_iter;
+};
+
+// THE unpacking of a solved window: refined points, camera positions (row 0 zero, rows >= nf NaN) and the speed derived from them
+__device__ __forceinline__ void refine_unpack_window(const SessStream& S, const int* ids_in, int n, int first, int nf, const double* x, const RefOut& o,
+                                                     double* s_speed, int tid)
+{
+    const int N0 = S.N0;
+    const double nanv = __longlong_as_double(0x7ff8000000000000LL);
+    const double* cam = x + 3 * (size_t)N0;  // refined positions of cameras 1..nf-1 (camera 0 is the origin)
+    if (o.ids)
+        for (int k = tid; k < ((N0 + 1) & ~1); k += 256) o.ids[k] = k < n ? ids_in[k] : -1;  // (to the 8-byte boundary the next array starts on: the whole record is defined)
+    if (o.pw)
+        for (int e = tid; e < 3 * N0; e += 256) o.pw[e] = e < 3 * n ? x[e] : nanv;
+    for (int e = tid; e < 3 * o.rows; e += 256) {
+        const int i = e / 3;
+        o.cw[e] = i == 0 ? 0.0 : (i < nf ? cam[e - 3] : nanv);
+    }
+    for (int i = tid; i < o.rows; i += 256) {
+        double d = nanv, sp = nanv;
+        if (i >= 1 && i < nf) {
+            double ss = 0.0;
+            for (int c = 0; c < 3; c++) {
+                const double a = cam[3 * (i - 1) + c] - (i == 1 ? 0.0 : cam[3 * (i - 2) + c]);
+                ss += a * a;
+            }
+            d = sqrt(ss);
+            const float dt = __fsub_rn(S.B[14 * (first + i) + 12], S.B[14 * (first + i - 1) + 12]);  // the float32 difference vidExample.py:142 forms
+            sp = d / (double)dt * 3.6;
+            s_speed[i] = sp;
+        }
+        o.dr[i] = d; o.speed[i] = sp;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        *o.nt = n;
+        double m = 0.0, v = 0.0;  // vidExample.py:177: mean and population std over frames 1..nf-1
+        for (int i = 1; i < nf; i++) m += s_speed[i];
+        m /= (double)(nf - 1);
+        for (int i = 1; i < nf; i++) v += (s_speed[i] - m) * (s_speed[i] - m);
+        *o.speed_mean = m;
+        *o.speed_std = sqrt(v / (double)(nf - 1));
+        const int it = min(max(o.info[0], 0), o.max_iter);
+        *o.f_first = it > 0 ? o.trace[0] : nanv;
+        *o.f_last = it > 0 ? o.trace[2 * (it - 1)] : nanv;
+    }
 }
 
 __global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, RefSlots sl, int w0, int nf, RefWs W, vh_refine_record L, char* recs)
 {
     const int w = w0 + blockIdx.x, tid = threadIdx.x;
     const SessStream& S = ss_all[sl.slot[blockIdx.x]];
-    const int N0 = S.N0, n = min(max(S.n_cur, 0), N0), nc = nf - 1;
-    const double nanv = __longlong_as_double(0x7ff8000000000000LL);
-    // z = [all u | all v], camera-major / track-minor (NLS.py:198-199), from the frame-major float32 history; rows behind the n survivors: no observation
-    double* z = W.z + (size_t)w * W.z_stride;
-    const size_t plane = (size_t)nf * N0;
-    for (size_t e = tid; e < 2 * plane; e += 256) {
-        const int row = e >= plane ? 1 : 0;
-        const size_t rem = e - (size_t)row * plane;
-        const int f = (int)(rem / N0), k = (int)(rem - (size_t)f * N0);
-        z[e] = k < n ? (double)S.P[sess_P(row, S.ids[k], f, N0)] : nanv;
-    }
-    // x0 = [p3[ids] | B[1:nf, 3:6] | 0] (NLS.py:202-203); padding points sit at (0, 0, 1)
-    double* x = W.x + (size_t)w * W.x_stride;
-    for (int e = tid; e < 3 * N0; e += 256) {
-        const int k = e / 3, c = e - 3 * k;
-        x[e] = k < n ? S.p3[3 * (size_t)S.ids[k] + c] : (c == 2 ? 1.0 : 0.0);
-    }
-    for (int e = tid; e < 3 * nc; e += 256) {
-        const int i = e / 3 + 1, c = e - 3 * (i - 1);
-        x[3 * (size_t)N0 + e] = (double)S.B[14 * i + 3 + c];
-        x[3 * (size_t)N0 + 3 * nc + e] = 0.0;
-    }
-    if (tid < 9) W.K[9 * (size_t)w + tid] = S.K[tid];
+    const int N0 = S.N0, n = min(max(S.n_cur, 0), N0);
+    // the slot's survivors are the tracks NLS.py:190 keeps of a clip that has just had its last frame
+    refine_pack_window(S, S.ids, n, 0, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid);
     if (tid == 0) W.nt[w] = n;
     // the part of the record the solve writes into (info, trace rows up to the iterations it takes): defined from the start
     char* rec = recs + (size_t)w * L.bytes;
@@ -815,53 +884,91 @@ __global__ __launch_bounds__(256) void k_refine_unpack(const SessStream* ss_all,
 {
     const int w = w0 + blockIdx.x, tid = threadIdx.x;
     const SessStream& S = ss_all[sl.slot[blockIdx.x]];
-    const int N0 = S.N0, nh = S.nhist, n = W.nt[w];
-    const double nanv = __longlong_as_double(0x7ff8000000000000LL);
-    const double* x = W.x + (size_t)w * W.x_stride;
-    const double* cam = x + 3 * (size_t)N0;  // refined positions of cameras 1..nf-1 (camera 0 is the origin)
     char* rec = recs + (size_t)w * L.bytes;
-    int* hdr = reinterpret_cast<int*>(rec + L.nt);
-    int* ids = reinterpret_cast<int*>(rec + L.ids);
-    double* pw = reinterpret_cast<double*>(rec + L.pw);
-    double* cw = reinterpret_cast<double*>(rec + L.cw);
-    double* dr = reinterpret_cast<double*>(rec + L.dr);
-    double* speed = reinterpret_cast<double*>(rec + L.speed);
-    for (int k = tid; k < ((N0 + 1) & ~1); k += 256) ids[k] = k < n ? S.ids[k] : -1;  // (to the 8-byte boundary the next array starts on: the whole record is defined)
-    for (int e = tid; e < 3 * N0; e += 256) pw[e] = e < 3 * n ? x[e] : nanv;
-    for (int e = tid; e < 3 * nh; e += 256) {
-        const int i = e / 3;
-        cw[e] = i == 0 ? 0.0 : (i < nf ? cam[e - 3] : nanv);
-    }
     __shared__ double s_speed[256];  // nf <= 256 (the BA's camera limit)
-    for (int i = tid; i < nh; i += 256) {
-        double d = nanv, sp = nanv;
-        if (i >= 1 && i < nf) {
-            double ss = 0.0;
-            for (int c = 0; c < 3; c++) {
-                const double a = cam[3 * (i - 1) + c] - (i == 1 ? 0.0 : cam[3 * (i - 2) + c]);
-                ss += a * a;
-            }
-            d = sqrt(ss);
-            const float dt = __fsub_rn(S.B[14 * i + 12], S.B[14 * (i - 1) + 12]);  // the float32 difference vidExample.py:142 forms
-            sp = d / (double)dt * 3.6;
-            s_speed[i] = sp;
-        }
-        dr[i] = d; speed[i] = sp;
-    }
+    RefOut o;
+    o.nt = reinterpret_cast<int*>(rec + L.nt); o.info = reinterpret_cast<const int*>(rec + L.iterations);
+    o.ids = reinterpret_cast<int*>(rec + L.ids); o.pw = reinterpret_cast<double*>(rec + L.pw);
+    o.cw = reinterpret_cast<double*>(rec + L.cw); o.dr = reinterpret_cast<double*>(rec + L.dr); o.speed = reinterpret_cast<double*>(rec + L.speed);
+    o.speed_mean = reinterpret_cast<double*>(rec + L.speed_mean); o.speed_std = reinterpret_cast<double*>(rec + L.speed_std);
+    o.f_first = reinterpret_cast<double*>(rec + L.f_first); o.f_last = reinterpret_cast<double*>(rec + L.f_last);
+    o.trace = reinterpret_cast<const double*>(rec + L.trace); o.rows = S.nhist; o.max_iter = L.max_iter;
+    refine_unpack_window(S, S.ids, W.nt[w], 0, nf, W.x + (size_t)w * W.x_stride, o, s_speed, tid);
+}
+
+// ---- any frame window of a clip (vh_session_refine_windows): window (slot, first) = frames [first, first + nf) of the slot's clip ---------------------------
+struct RefWins {  // the windows of one pack / unpack launch travel in the kernel arguments, as RefSlots
+    int slot[SESS_REF_CHUNK];
+    int first[SESS_REF_CHUNK];
+};
+
+static void refine_window_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_window_record* L)
+{
+    size_t off = 0;
+    auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
+    L->slot = put(6 * sizeof(int)); L->first = L->slot + 4; L->nt = L->slot + 8;
+    L->iterations = L->slot + 12; L->converged = L->slot + 16;  // (iterations, converged: the int[2] info record of the window's solve; one pad word)
+    L->cw = put(sizeof(double) * 3 * (size_t)nf);
+    L->dr = put(sizeof(double) * (size_t)nf); L->speed = put(sizeof(double) * (size_t)nf);
+    L->speed_mean = put(sizeof(double)); L->speed_std = put(sizeof(double)); L->f_first = put(sizeof(double)); L->f_last = put(sizeof(double));
+    L->trace = put(sizeof(double) * 2 * (size_t)max_iter);
+    L->ids = with_points ? put(sizeof(int) * (size_t)N0) : 0;
+    L->pw = with_points ? put(sizeof(double) * 3 * (size_t)N0) : 0;
+    L->bytes = off;
+    L->n0 = N0; L->nf = nf; L->max_iter = max_iter; L->with_points = with_points ? 1 : 0;
+}
+
+// select + pack: the window's tracks are the ids whose history row 4 is finite in EVERY frame of the window (NLS.py:190 on the slice) -- not the slot's
+// current survivors: a track that died after the window belongs to it.  One workgroup per window: 256 ids at a time read row 4 of the frame-major
+// history (coalesced over tracks), a ballot + the four wavefronts' counts give each kept id its place, so the ids come out ascending.
+__global__ __launch_bounds__(256) void k_refine_win_pack(const SessStream* ss_all, RefWins wn, int w0, int nf, RefWs W, vh_refine_window_record L, char* recs)
+{
+    const int w = w0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int slot = wn.slot[blockIdx.x], first = wn.first[blockIdx.x];
+    const SessStream& S = ss_all[slot];
+    const int N0 = S.N0;
+    int* ids = W.ids + (size_t)w * N0;
+    __shared__ int s_cnt[4], s_base;
+    if (tid == 0) s_base = 0;
     __syncthreads();
-    if (tid == 0) {
-        hdr[0] = n;
-        double m = 0.0, v = 0.0;  // vidExample.py:177: mean and population std over frames 1..nf-1
-        for (int i = 1; i < nf; i++) m += s_speed[i];
-        m /= (double)(nf - 1);
-        for (int i = 1; i < nf; i++) v += (s_speed[i] - m) * (s_speed[i] - m);
-        *reinterpret_cast<double*>(rec + L.speed_mean) = m;
-        *reinterpret_cast<double*>(rec + L.speed_std) = sqrt(v / (double)(nf - 1));
-        const double* trace = reinterpret_cast<const double*>(rec + L.trace);
-        const int it = min(max(hdr[1], 0), L.max_iter);
-        *reinterpret_cast<double*>(rec + L.f_first) = it > 0 ? trace[0] : nanv;
-        *reinterpret_cast<double*>(rec + L.f_last) = it > 0 ? trace[2 * (it - 1)] : nanv;
+    for (int g0 = 0; g0 < N0; g0 += 256) {  // (uniform trip count: every lane of every wavefront reaches the ballot and the barriers)
+        const int g = g0 + tid;
+        bool alive = g < N0;
+        for (int f = 0; alive && f < nf; f++) alive = isfinite(S.P[sess_P(4, g, first + f, N0)]);
+        const unsigned long long bal = __ballot(alive);
+        if (lane == 0) s_cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int at = s_base;
+        for (int k = 0; k < wave; k++) at += s_cnt[k];
+        if (alive) ids[at + __popcll(bal & ((1ull << lane) - 1ull))] = g;
+        __syncthreads();
+        if (tid == 0) s_base += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        __syncthreads();
     }
+    const int n = s_base;  // (the ids written above are visible to the whole workgroup: barriers since)
+    refine_pack_window(S, ids, n, first, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid);
+    if (tid == 0) W.nt[w] = n;
+    // the part of the record the solve writes into (info, trace rows up to the iterations it takes) and the header: defined from the start
+    char* rec = recs + (size_t)w * L.bytes;
+    if (tid < 6) reinterpret_cast<int*>(rec + L.slot)[tid] = tid == 0 ? slot : (tid == 1 ? first : 0);
+    double* trace = reinterpret_cast<double*>(rec + L.trace);
+    for (int e = tid; e < 2 * L.max_iter; e += 256) trace[e] = 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_refine_win_unpack(const SessStream* ss_all, RefWins wn, int w0, int nf, RefWs W, vh_refine_window_record L, char* recs)
+{
+    const int w = w0 + blockIdx.x, tid = threadIdx.x;
+    const SessStream& S = ss_all[wn.slot[blockIdx.x]];
+    char* rec = recs + (size_t)w * L.bytes;
+    __shared__ double s_speed[256];  // nf <= 256 (the BA's camera limit)
+    RefOut o;
+    o.nt = reinterpret_cast<int*>(rec + L.nt); o.info = reinterpret_cast<const int*>(rec + L.iterations);
+    o.ids = L.with_points ? reinterpret_cast<int*>(rec + L.ids) : nullptr; o.pw = L.with_points ? reinterpret_cast<double*>(rec + L.pw) : nullptr;
+    o.cw = reinterpret_cast<double*>(rec + L.cw); o.dr = reinterpret_cast<double*>(rec + L.dr); o.speed = reinterpret_cast<double*>(rec + L.speed);
+    o.speed_mean = reinterpret_cast<double*>(rec + L.speed_mean); o.speed_std = reinterpret_cast<double*>(rec + L.speed_std);
+    o.f_first = reinterpret_cast<double*>(rec + L.f_first); o.f_last = reinterpret_cast<double*>(rec + L.f_last);
+    o.trace = reinterpret_cast<const double*>(rec + L.trace); o.rows = nf; o.max_iter = L.max_iter;
+    refine_unpack_window(S, W.ids + (size_t)w * S.N0, W.nt[w], wn.first[blockIdx.x], nf, W.x + (size_t)w * W.x_stride, o, s_speed, tid);
 }
 
 extern "C" VH_API size_t vh_session_refine_size(const vh_session* s, int max_iter, vh_refine_record* layout_host)
@@ -930,6 +1037,89 @@ extern "C" VH_API int vh_session_refine(vh_session* s, const int* slots_host, in
     if (r) return r;
     VH_BIND(s->ctx, stream);
     each_chunk(k_refine_unpack, bound_.s);
+    SESS_CHECK();
+    return 0;
+}
+
+extern "C" VH_API size_t vh_session_refine_windows_size(const vh_session* s, int nf, int max_iter, int with_points, vh_refine_window_record* layout_host)
+{
+    if (!s || nf < 2 || max_iter < 1) { vh_fail(-1, "vh_session_refine_windows_size: bad arguments"); return 0; }
+    vh_refine_window_record L;
+    refine_window_record_layout(s->N0, nf, max_iter, with_points, &L);
+    if (layout_host) *layout_host = L;
+    return L.bytes;
+}
+
+extern "C" VH_API size_t vh_session_refine_windows_workspace(const vh_session* s, int nwin, int nf)
+{
+    if (!s || nwin < 1 || nf < 2 || nf - 1 > 255) { vh_fail(-1, "vh_session_refine_windows_workspace: bad arguments"); return 0; }
+    RefWs W;
+    return refine_ws_layout(s, nwin, nf, nullptr, &W, true);
+}
+
+extern "C" VH_API int vh_session_refine_windows(vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, int max_iter, int with_points,
+                                                void* recs_dev, void* workspace, size_t workspace_bytes, void* stream)
+{
+    char msg[240];
+    if (!s || !wins_host || !recs_dev || !workspace)
+        return vh_fail(-1, "vh_session_refine_windows: bad arguments (a null session, window table, record buffer or workspace)");
+    if ((reinterpret_cast<uintptr_t>(recs_dev) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 255))
+        return vh_fail(-1, "vh_session_refine_windows: misaligned buffers (records 8-byte, workspace 256-byte aligned)");
+    if (nwin < 1) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nwin = %d: at least one window", nwin); return vh_fail(-1, msg); }
+    if (nwin > 65535) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nwin = %d: at most 65535 windows in one launch sequence", nwin); return vh_fail(-1, msg); }
+    if (max_iter < 1) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: max_iter = %d: at least one iteration", max_iter); return vh_fail(-1, msg); }
+    if (nf < 2) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nf = %d: a window needs at least two frames", nf); return vh_fail(-1, msg); }
+    if (nf - 1 > 255) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nf = %d: at most 255 free cameras (256 frames) per window", nf); return vh_fail(-1, msg); }
+    if (nf > s->nhist) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nf = %d exceeds the session's history of %d frames", nf, s->nhist); return vh_fail(-1, msg); }
+    std::vector<std::vector<int>> seen(s->batch);  // per slot: the window starts given so far
+    for (int k = 0; k < nwin; k++) {
+        const int b = wins_host[k].slot, first = wins_host[k].first;
+        if (b < 0 || b >= s->batch) {
+            snprintf(msg, sizeof(msg), "vh_session_refine_windows: window %d: slot %d is outside the session's %d slots", k, b, s->batch);
+            return vh_fail(-1, msg);
+        }
+        if (first < 0) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: window %d (slot %d): first = %d is negative", k, b, first); return vh_fail(-1, msg); }
+        const int last_have = s->h_frame[b] < s->nhist - 1 ? s->h_frame[b] : s->nhist - 1;  // (the history holds nhist frames)
+        if (first > last_have || nf - 1 > last_have - first) {
+            snprintf(msg, sizeof(msg), "vh_session_refine_windows: window %d (slot %d, first %d) ends at frame %lld, the slot is at frame %d", k, b, first,
+                     (long long)first + nf - 1, last_have);
+            return vh_fail(-1, msg);
+        }
+        for (int f : seen[b])
+            if (f == first) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: window (slot %d, first %d) is given twice", b, first); return vh_fail(-1, msg); }
+        seen[b].push_back(first);
+    }
+    RefWs W;
+    const size_t need = refine_ws_layout(s, nwin, nf, reinterpret_cast<char*>(workspace), &W, true);
+    if (workspace_bytes < need) {
+        snprintf(msg, sizeof(msg), "vh_session_refine_windows: workspace of %zu bytes, %d windows of %d frames need %zu", workspace_bytes, nwin, nf, need);
+        return vh_fail(-1, msg);
+    }
+    vh_refine_window_record L;
+    refine_window_record_layout(s->N0, nf, max_iter, with_points, &L);
+    char* recs = reinterpret_cast<char*>(recs_dev);
+    auto each_chunk = [&](auto kernel, hipStream_t st) {
+        for (int w0 = 0; w0 < nwin; w0 += SESS_REF_CHUNK) {
+            RefWins wn;
+            const int cnt = nwin - w0 < SESS_REF_CHUNK ? nwin - w0 : SESS_REF_CHUNK;
+            for (int k = 0; k < SESS_REF_CHUNK; k++) {
+                wn.slot[k] = wins_host[w0 + (k < cnt ? k : 0)].slot;
+                wn.first[k] = wins_host[w0 + (k < cnt ? k : 0)].first;
+            }
+            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, wn, w0, nf, W, L, recs);
+        }
+    };
+    {
+        VH_BIND(s->ctx, stream);
+        each_chunk(k_refine_win_pack, bound_.s);
+        SESS_CHECK();
+    }
+    // the windows' info = {iterations, converged} and trace go straight into the records
+    int r = vh_ba_windows(s->ctx, s->h_ss[wins_host[0].slot].K, W.z, W.x, s->N0, nf - 1, nwin, W.nt, W.K, max_iter, reinterpret_cast<double*>(recs + L.trace),
+                          L.bytes / sizeof(double), reinterpret_cast<int*>(recs + L.iterations), L.bytes / sizeof(int), W.ba, W.ba_stride, stream);
+    if (r) return r;
+    VH_BIND(s->ctx, stream);
+    each_chunk(k_refine_win_unpack, bound_.s);
     SESS_CHECK();
     return 0;
 }

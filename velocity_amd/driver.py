@@ -321,6 +321,68 @@ class TrackerSession:
         ev.record()
         return RefinedClips(bufs, lay, ev, nf)
 
+    def refine_window_layout(self, nf, max_iter=10, with_points=False):
+        """vh_refine_window_record of this session for windows of nf frames: byte offsets of the fields of a refined window's record (and `bytes`)."""
+        lays = self.__dict__.setdefault("_refine_window_layouts", {})
+        key = (int(nf), int(max_iter), bool(with_points))
+        if key not in lays:
+            lay = L.RefineWindowRecord()
+            if not self.lib.vh_session_refine_windows_size(self.handle, key[0], key[1], int(key[2]), C.byref(lay)):
+                L.check(-1, "vh_session_refine_windows_size")
+            lays[key] = lay
+        return lays[key]
+
+    def refine_windows(self, windows, nf, max_iter=10, with_points=False, out=None, workspace_budget=None):
+        """Bundle adjustment of frame windows of the slots' clips without leaving the device (vh_session_refine_windows): `windows` = [(slot, first), ...],
+        each the frames [first, first + nf) of its slot's clip -- fcnNLS_batch(K, P[:, :, first:first+nf], ...) in the coordinates of the window's first
+        camera, on the tracks alive through the window.  A slot may appear in many windows and need not be finished (first + nf - 1 <= its frame
+        counter); the clips may have any lengths.  The session is only read.  The windows go through ONE BA launch sequence per chunk: the scratch grows
+        with the number of windows, so a request is issued in chunks of as many windows as keep it under `workspace_budget` bytes (default
+        REFINE_WINDOWS_BUDGET; always at least one window).  The scratch and the device records belong to the session and are reused.
+        out: None (a new pinned buffer), ONE pinned uint8 tensor for all the records, or a list of (pinned uint8 tensor, count): consecutive records,
+        `count` of them into each tensor.  with_points: the records also carry ids and pw (in the window's coordinates).
+        Returns a handle like refine()'s: .done() polls, .result() waits and returns one dict per window (unpack_refine_window), in the order given."""
+        torch = self.torch
+        wins = [(int(b), int(f)) for b, f in windows]
+        if not wins:
+            raise ValueError("refine_windows: no window given")
+        nf, max_iter = int(nf), int(max_iter)
+        lay = self.refine_window_layout(nf, max_iter, with_points)
+        budget = REFINE_WINDOWS_BUDGET if workspace_budget is None else int(workspace_budget)
+        one = int(self.lib.vh_session_refine_windows_workspace(self.handle, 1, nf))
+        if not one:
+            L.check(-1, "vh_session_refine_windows_workspace")
+        chunk = max(1, min(budget // one, REFINE_WINDOWS_MOST, len(wins)))
+        if chunk < len(wins):  # several calls: what the library would refuse in a later one is refused here, before the first is queued
+            if len(set(wins)) != len(wins):
+                raise ValueError("refine_windows: a window is given twice")
+            for b, f in wins:
+                if not 0 <= b < self.batch or f < 0 or f + nf - 1 > self._frame_i[b]:
+                    raise ValueError(f"refine_windows: window (slot {b}, first {f}) of {nf} frames is outside the session's {self.batch} slots or the frames its slot has had")
+        need = int(self.lib.vh_session_refine_windows_workspace(self.handle, chunk, nf))
+        nbytes = lay.bytes * len(wins)
+        if getattr(self, "_refine_ws", None) is None or self._refine_ws.numel() < need:
+            self._refine_ws = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
+        if getattr(self, "_refine_dev", None) is None or self._refine_dev.numel() < nbytes:
+            self._refine_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        parts = [(out, len(wins))] if isinstance(out, torch.Tensor) else [(b, int(k)) for b, k in out]
+        assert sum(k for _, k in parts) == len(wins)
+        assert all(b.dtype == torch.uint8 and b.numel() >= k * lay.bytes and b.is_pinned() and b.is_contiguous() for b, k in parts)
+        for w0 in range(0, len(wins), chunk):  # the chunks share the scratch: they are ordered by the stream
+            part = wins[w0:w0 + chunk]
+            tab = (L.RefineWindow * len(part))(*[L.RefineWindow(b, f) for b, f in part])
+            L.check(self.lib.vh_session_refine_windows(self.handle, tab, len(part), nf, max_iter, int(bool(with_points)), C.c_void_p(self._refine_dev.data_ptr() + w0 * lay.bytes),
+                                                       L.dptr(self._refine_ws), self._refine_ws.numel(), L.stream_ptr()), "vh_session_refine_windows")
+        at = 0
+        for b, k in parts:
+            b[: k * lay.bytes].copy_(self._refine_dev[at:at + k * lay.bytes], non_blocking=True)
+            at += k * lay.bytes
+        ev = torch.cuda.Event()
+        ev.record()
+        return RefinedWindows(parts, lay, ev, chunk)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -385,15 +447,122 @@ def unpack_refine(raw, lay, nf=None):
                 trace=rd(lay.trace, 2 * iterations, np.float64).reshape(iterations, 2), **one)
 
 
+# Device scratch one refine_windows chunk may take, in bytes (the keyword workspace_budget overrides it).  A window's share is its z, x0 and BA workspace
+# (vh_session_refine_windows_workspace(s, 1, nf): about 1.3 MB at 1004 tracks and 8 frames), so the default holds several hundred such windows per BA
+# launch sequence -- enough to fill the chip -- while a request of thousands of windows of a long clip does not grow the scratch without bound.
+REFINE_WINDOWS_BUDGET = 1 << 30
+REFINE_WINDOWS_MOST = 65535  # windows of one BA launch sequence (vh_nls_batch_windows)
+
+
+class RefinedWindows:
+    """The refined windows of one TrackerSession.refine_windows on their way to the host: the records of all its chunks, gathered in the order given."""
+
+    def __init__(self, parts, layout, event, chunk):
+        self.parts, self.layout, self.event, self.chunk = parts, layout, event, chunk
+        self._res = None
+
+    def done(self):
+        """True once the records have arrived (never waits)."""
+        return self._res is not None or self.event.query()
+
+    def result(self):
+        if self._res is None:
+            self.event.synchronize()
+            nb = self.layout.bytes
+            self._res = [unpack_refine_window(b.numpy()[k * nb:(k + 1) * nb], self.layout) for b, cnt in self.parts for k in range(cnt)]
+        return self._res
+
+
+def unpack_refine_window(raw, lay):
+    """A vh_refine_window_record (uint8 array `raw`, offsets `lay`) as a dict: slot, first, nt, iterations, converged, cw [nf, 3] (relative to the window's
+    first camera), dr [nf], speed [nf] (entry 0 NaN), speed_mean, speed_std, f_first, f_last, trace [iterations, 2] and, when the record carries them,
+    ids [nt] and pw [nt, 3] (in the window's coordinates: subtract B[first, 3:6] for the session's); every array is a copy."""
+
+    def rd(off, count, dtype):
+        return np.frombuffer(raw, dtype, count, off).copy()
+
+    head = {k: int(rd(getattr(lay, k), 1, np.int32)[0]) for k in ("slot", "first", "nt", "iterations", "converged")}
+    nf, nt = lay.nf, head["nt"]
+    one = {k: float(rd(getattr(lay, k), 1, np.float64)[0]) for k in ("speed_mean", "speed_std", "f_first", "f_last")}
+    pts = dict(ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3)) if lay.with_points else {}
+    return dict(cw=rd(lay.cw, 3 * nf, np.float64).reshape(nf, 3), dr=rd(lay.dr, nf, np.float64), speed=rd(lay.speed, nf, np.float64),
+                trace=rd(lay.trace, 2 * head["iterations"], np.float64).reshape(head["iterations"], 2), **head, **one, **pts)
+
+
+def refine_window_starts(n, window, stride=None):
+    """The first frames of the windows of `window` frames that cover a clip of n frames: range(0, n - window + 1, stride) plus the end-aligned n - window when
+    that is not already last, so every frame is in a window.  1 <= stride <= window - 1 (default window - 1): consecutive windows share at least one
+    frame, so every frame-to-frame step i-1 -> i lies inside a window -- with the default exactly one, except where the end-aligned window overlaps."""
+    n, window = int(n), int(window)
+    stride = window - 1 if stride is None else int(stride)
+    if window < 2:
+        raise ValueError(f"refine_window_starts: window = {window}: a window needs at least two frames")
+    if n < window:
+        raise ValueError(f"refine_window_starts: a clip of n = {n} frames is shorter than window = {window}")
+    if not 1 <= stride <= window - 1:
+        raise ValueError(f"refine_window_starts: stride = {stride} is outside 1 .. window - 1 = {window - 1}")
+    starts = list(range(0, n - window + 1, stride))
+    if starts[-1] != n - window:
+        starts.append(n - window)
+    return starts
+
+
+def merge_window_speeds(n, windows):
+    """The speed of a clip of n frames from its refined windows (pure NumPy).  windows: dicts with `first`, `speed` [W] (entry 0 NaN: speed[j] is the
+    estimate of the step first+j-1 -> first+j), nt, iterations, converged, f_last (unpack_refine_window's).  speed[i] (i >= 1) is the mean of the
+    estimates of the windows that cover step i, cover[i] how many did (a step nobody covers: NaN); speed_mean / speed_std are over speed[1:n]
+    (vidExample.py:177).  An average of independent estimates, not one global adjustment.  Also returns the per-window arrays first, nt, iterations,
+    converged, f_last."""
+    n = int(n)
+    tot, cover = np.zeros(n), np.zeros(n, np.int64)
+    for w in windows:
+        sp = np.asarray(w["speed"], np.float64)
+        lo = int(w["first"])
+        assert lo >= 0 and lo + len(sp) <= n, "merge_window_speeds: a window outside the clip"
+        tot[lo + 1:lo + len(sp)] += sp[1:]
+        cover[lo + 1:lo + len(sp)] += 1
+    speed = np.full(n, np.nan)
+    hit = cover > 0
+    speed[hit] = tot[hit] / cover[hit]
+    return dict(speed=speed, cover=cover, speed_mean=float(speed[1:].mean()), speed_std=float(speed[1:].std()),
+                first=np.array([w["first"] for w in windows], np.int64), nt=np.array([w["nt"] for w in windows], np.int64),
+                iterations=np.array([w["iterations"] for w in windows], np.int64), converged=np.array([w["converged"] for w in windows], np.int64),
+                f_last=np.array([w["f_last"] for w in windows], np.float64))
+
+
+def _merged_ba(n, wins, window, stride):
+    """result["ba"] of a clip refined in windows: merge_window_speeds' dict with `window` and `stride`."""
+    return dict(merge_window_speeds(n, wins), window=window, stride=stride)
+
+
 def ba_line(ba):
-    """The line a refined clip adds behind the reference's summary."""
+    """The line a refined clip adds behind the reference's summary (a clip refined in windows: their count and length, the fewest and the most tracks of a
+    window, the largest last rms residual among them)."""
+    if "window" in ba:
+        return (f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({len(ba['first'])} windows of {ba['window']} frames, "
+                f"{ba['nt'].min()}-{ba['nt'].max()} tracks, f = {np.nanmax(ba['f_last']) if np.isfinite(ba['f_last']).any() else np.nan:.3f} pixels)")
     return f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({ba['nt']:g} tracks, f = {ba['f_last']:.3f} pixels)"
 
 
-def _check_refine(refine):
+def _check_refine(refine, refine_window=None, refine_stride=None):
+    """-> (refine is on, the window length or None, the stride or None); raises ValueError by name before anything is queued."""
     if refine not in (None, "ba"):
         raise ValueError(f"refine must be None or 'ba', got {refine!r}")
-    return refine == "ba"
+    if refine_window is None:
+        if refine_stride is not None:
+            raise ValueError("refine_stride needs refine_window")
+        return refine == "ba", None, None
+    if refine != "ba":
+        raise ValueError("refine_window needs refine='ba'")
+    window = int(refine_window)
+    if window < 2:
+        raise ValueError(f"refine_window = {window}: a window needs at least two frames")
+    if window > 256:
+        raise ValueError(f"refine_window = {window}: at most 256 frames (the bundle adjustment's 255 free cameras)")
+    stride = window - 1 if refine_stride is None else int(refine_stride)
+    if not 1 <= stride <= window - 1:
+        raise ValueError(f"refine_stride = {stride} is outside 1 .. refine_window - 1 = {window - 1}")
+    return True, window, stride
 
 
 def unpack_record(raw, lay):
@@ -656,7 +825,8 @@ def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=
 
 def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01,
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
-                 out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None):
+                 out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
+                 refine_window=None, refine_stride=None):
     """The packaged counterpart of vidExample.py:52-178 (minus video decode and plots) on one clip.
 
     frames  sequence of n uint8 [H, W] gray frames (numpy arrays or CUDA tensors): what `cv2.cvtColor(cap.read(), BGR2GRAY)` / `cv2.imread(.., 0)` hands
@@ -675,6 +845,12 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             frame step; default off).  The result then carries `recoveries` = [the recovery ran, it found a model] counts.
     refine  None (default: nothing new is queued), or "ba": after the last frame the clip is bundle-adjusted on the device (TrackerSession.refine:
             vidExample.py:157's fcnNLS_batch over all frames and surviving tracks); the result gains "ba" and one line follows the summary (ba_line).
+    refine_window, refine_stride   None (default): the whole clip, as above -- at most 256 frames.  refine_window=W (2 .. 256; needs refine="ba"): a clip of
+            at least W frames, of ANY length, is refined in windows of W frames starting at refine_window_starts(n, W, refine_stride) (default stride
+            W - 1), all in one TrackerSession.refine_windows request, each on the tracks alive through it; "ba" is then merge_window_speeds' dict
+            (speed, cover, speed_mean, speed_std and the per-window first, nt, iterations, converged, f_last) plus `window` and `stride`.  A clip
+            shorter than W is refined whole.  The windows are independent solves and the merged speed an average of their estimates, not one global
+            adjustment; each window's scale is still held only by the damping.
     out     line sink (default print); clock: time source for the procTime column / fps line (default time.perf_counter).
 
     Prints the reference's header, one 9-column row per frame (vidExample.py:165) and the `Speed = ... +/- ... km/h / Res = ...` summary (:177-178).
@@ -682,7 +858,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     import time as _time
 
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
-    refine = _check_refine(refine)
+    refine, win, stride = _check_refine(refine, refine_window, refine_stride)
     if route != "session":
         raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
     clock = clock or _time.perf_counter
@@ -720,7 +896,10 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             row(i)
     ses.torch.cuda.synchronize()
     step_seconds = (clock() - t_loop) / (n - 1)
-    ba = ses.refine([0]).result()[0] if refine else None
+    if refine and win and n >= win:
+        ba = _merged_ba(n, ses.refine_windows([(0, f) for f in refine_window_starts(n, win, stride)], win).result(), win, stride)
+    else:
+        ba = ses.refine([0]).result()[0] if refine else None
     st, recoveries, f0 = ses.state(0), ses.recoveries()[0], f0.host()
     res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None, ba)
     for line in res["lines"][-(3 if refine else 2) if live else 2:]:  # (not live: the whole clip ran first, and every row carries the mean time per frame)
@@ -788,7 +967,8 @@ class _SessionSet:
 
 
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
-                  msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None):
+                  msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
+                  refine_window=None, refine_stride=None):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name, K]) of ONE length -- the
     frame size and the intrinsics are each clip's own ("K": that clip's camera, default the K argument); the sessions are created at the elementwise
     maximum of the sizes and a frame step is sized for it, so clips of one camera type batch best.  One length stays required: a step advances every
@@ -799,10 +979,11 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     before the last frame.  use_harris / min_distance: the frame-0 detector, as in run_sequence.  fallback: the recovery by feature matching, as in
     run_sequence (the failed streams of a session share one vh_match_affine_batch call per step).  Returns one result dict per clip (clip_result's;
     `lines` = that clip's table and summary, printed through `out` if given), each equal to what run_sequence returns for the clip alone.  refine="ba": as in
-    run_sequence; all the clips of a session are refined by ONE TrackerSession.refine after the last frame."""
+    run_sequence; all the clips of a session are refined by ONE TrackerSession.refine after the last frame -- with refine_window=W (and clips of at least
+    W frames) all the windows of all the clips of a session by ONE TrackerSession.refine_windows request."""
     import time as _time
 
-    refine = _check_refine(refine)
+    refine, win, stride = _check_refine(refine, refine_window, refine_stride)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
     nclip = len(clips)
@@ -837,10 +1018,16 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     refined = None
     if refine:
         refined = []
+        starts = refine_window_starts(n, win, stride) if win and n >= win else None
         for ses, hs, mem in zip(sess, group.hip_streams, members):
             with torch.cuda.stream(hs):
-                refined.append(ses.refine(list(range(len(mem)))))
+                if win and n >= win:
+                    refined.append(ses.refine_windows([(j, f) for j in range(len(mem)) for f in starts], win))
+                else:
+                    refined.append(ses.refine(list(range(len(mem)))))
         refined = [h.result() for h in refined]
+        if win and n >= win:  # a clip's windows are consecutive in its session's request
+            refined = [[_merged_ba(n, r[j * len(starts):(j + 1) * len(starts)], win, stride) for j in range(len(r) // len(starts))] for r in refined]
     seconds = _time.perf_counter() - t_begin
     # what tools/exp/queue_timing.py reads: device time of the frame-0 block of every session (events on its stream), to set beside run_queue's
     run_sequences.last_stats = dict(sessions=len(sess), steps=n - 1, admission_ms=float(sum(a.elapsed_time(b) for a, b in f0_events)), admissions=len(sess))
@@ -916,7 +1103,7 @@ def queue_plan(lengths, streams, sessions=1):
 
 def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, max_size=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
               harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=None, use_harris=True, min_distance=0.0, fallback=False,
-              fallback_params=None, refine=None):
+              fallback_params=None, refine=None, refine_window=None, refine_stride=None):
     """A queue of clips of ANY length on `streams` resident streams: what run_sequences is for clips of one length.  `clips` = any iterable of
     dict(frames, q, times[, frame_numbers, name, K]), each of >= 2 frames and with its own frame size and intrinsics ("K": default the K argument); it is consumed lazily -- a clip is pulled when a slot is free
     for it and its frames go up then, so at most `streams` clips are resident -- and may hold more clips than fit on the device at once.
@@ -935,10 +1122,12 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
     on_result(index, result) is called as results land (polled at every step, never waited for); returns the results in input order.  A result is
     clip_result's: P / B / S cut to the clip's own length and the track rows to n_tracks0; `lines` = the clip's table and summary.
     refine="ba": as in run_sequence.  The clips of a session that finish at the same step are refined on the session's stream right behind their
-    exports, one TrackerSession.refine per clip length among them; the records travel with the exports and the slots are free at the next step as ever."""
+    exports, one TrackerSession.refine per clip length among them; the records travel with the exports and the slots are free at the next step as ever.
+    refine_window=W (refine_stride: as in run_sequence): the clips of at least W frames that finish at a step go through ONE TrackerSession.refine_windows
+    request of their session, whatever their lengths (their "ba" is the merged dict); the per-length calls remain for clips shorter than W."""
     import time as _time
 
-    refine = _check_refine(refine)
+    refine, win, stride = _check_refine(refine, refine_window, refine_stride)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
     if max_frames is None:
@@ -990,7 +1179,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
         handle, index, clip, f0, t0, ba = entry[2]
         st = handle.result()
         if ba is not None:
-            ba = ba[0].result()[ba[1]]
+            ba = ba[1](ba[0].result())
         x = entry[1].numpy().copy()
         seconds = _time.perf_counter() - t0  # the clip's time in the queue: every row carries the mean over its frame steps
         res = results[index] = clip_result(st, clip, f0._replace(R0=x[0:9], res0=x[9]), seconds, seconds / (clip["n"] - 1), G, handle.recoveries, ba=ba)
@@ -1018,6 +1207,9 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                     L.check(ses.lib.vh_init_reserve_batch(ses.ws.handle, ses.batch, W, H, L.stream_ptr()), "vh_init_reserve_batch")
             rec_bytes = sess[0].record_layout().bytes
             ba_bytes = sess[0].refine_layout().bytes if refine else 0
+            if win and nhist >= win:  # room for the most windows a clip of nhist frames can have (a clip shorter than W: the whole-clip record)
+                win_bytes = sess[0].refine_window_layout(win).bytes
+                ba_bytes = max(ba_bytes, len(refine_window_starts(nhist, win, stride)) * win_bytes)
             ring = [[torch.empty(rec_bytes, dtype=torch.uint8).pin_memory(), torch.empty(10, dtype=torch.float64).pin_memory(), None,
                      torch.empty(ba_bytes, dtype=torch.uint8).pin_memory() if refine else None] for _ in range(2 * streams)]
         for g, (ses, hs) in enumerate(zip(sess, group.hip_streams)):
@@ -1070,11 +1262,19 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                     pending.append(entry)
                     held[g][j] = None
                     finished.append((j, c["n"], entry))
+                windowed = [(j, n, e, refine_window_starts(n, win, stride)) for j, n, e in finished if refine and win and n >= win]
+                if windowed:  # ONE request for all of them, whatever their lengths; a clip's records land in its own pinned buffer
+                    rh = ses.refine_windows([(j, f) for j, _, _, st in windowed for f in st], win, out=[(e[3], len(st)) for _, _, e, st in windowed])
+                    at = 0
+                    for _, n, e, st in windowed:
+                        e[2][5] = (rh, lambda r, at=at, k=len(st), n=n: _merged_ba(n, r[at:at + k], win, stride))
+                        at += len(st)
+                    finished = [x for x in finished if not (win and x[1] >= win)]
                 for n_clip in sorted({n for _, n, _ in finished}) if refine else ():
                     same = [(j, e) for j, n, e in finished if n == n_clip]
                     rh = ses.refine([j for j, _ in same], out=[e[3] for _, e in same])
                     for idx, (_, e) in enumerate(same):
-                        e[2][5] = (rh, idx)
+                        e[2][5] = (rh, lambda r, idx=idx: r[idx])
         steps += 1
         poll()
     for hs in group.hip_streams:
@@ -1115,13 +1315,16 @@ def main(argv=None):
     ap.add_argument("--min-distance", type=float, default=0.0, help="minimum distance between the frame-0 corners (vidExample.py:110 uses 0)")
     ap.add_argument("--fallback", action="store_true", help="recover the motion by feature matching when the coarse KLT stage fails (one host read per frame)")
     ap.add_argument("--refine", choices=["ba"], default=None, help="bundle-adjust the finished clip on the device and print the refined speed (vidExample.py:157)")
+    ap.add_argument("--refine-window", type=int, default=None, metavar="W", help="with --refine ba: refine the clip in windows of W frames (2 .. 256); clips of any length")
+    ap.add_argument("--refine-stride", type=int, default=None, metavar="S", help="frames between the starts of consecutive windows (1 .. W-1; default W-1)")
     ap.add_argument("--shi-tomasi", action="store_true", help="frame-0 corners by the minimum-eigenvalue detector instead of Harris")
     a = ap.parse_args(argv)
     d = np.load(a.clip)
     fr = d[f"{a.seq}_frames"]
     border = tuple(a.border) if a.border else ((700, 500) if fr.shape[2] >= 1900 else (180, 140))
     run_sequence(fr, d[f"{a.seq}_q"], d[f"{a.seq}_K"], times=d[f"{a.seq}_times"], roi_border=border, msv_frame=a.msv_frame,
-                 name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback, refine=a.refine)
+                 name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback, refine=a.refine,
+                 refine_window=a.refine_window, refine_stride=a.refine_stride)
 
 
 if __name__ == "__main__":
