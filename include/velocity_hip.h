@@ -189,6 +189,17 @@ VH_API int vh_nls_batch_windows(vh_ctx* ctx, const double* K_host, const double*
                                 const double* K_win_dev, int max_iter, double* trace, int* info, void* workspace,
                                 size_t workspace_bytes_per_window, void* stream);
 
+/* vh_nls_batch_windows with ANCHORED points: the scale gauge of fcnNLS_batch is held only by the +I damping (camera 0 is fixed and nothing else, and
+ * scaling every point and camera position by one factor leaves every reprojection unchanged), so a solve returns the scale its start had.  Points whose
+ * coordinates are known -- the licence-plate corners, vidExample.py:116-119 -- pin it.  fixed_dev: device uint8[nwin][nt], non-zero = row i of the
+ * window is anchored (NULL: none).  An anchored point's three Jacobian columns are exact zeros: it takes no step (its rows of x come back byte for
+ * byte) while its measurements still constrain the cameras that see it.  Nothing else changes: damping, the 0.9 gain, the stop rule and the divisors
+ * nx = 3 nt_w + 6 nc, nz of the iteration record (an anchored point still counts as rows of x; its delta is 0).  Flags of padding rows are ignored
+ * (their Jacobian is zero already).  The table is read on the device when the kernels run.  With fixed_dev == NULL this is vh_nls_batch_windows. */
+VH_API int vh_nls_batch_windows_fixed(vh_ctx* ctx, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
+                                      const double* K_win_dev, const uint8_t* fixed_dev, int max_iter, double* trace, int* info, void* workspace,
+                                      size_t workspace_bytes_per_window, void* stream);
+
 /* fcnNLS_batch2(K, P, pw, cw), utils/NLS.py:253-328: the constrained sibling -- tie points, ONE joint rotation applied to the
  * points and a straight-line camera trajectory (elevation, azimuth, one range per camera 1..nc; camera 0 at the origin).
  * Same z packing, damping (+I), step (0.9) and stop rule (rms(delta) < 1e-7); the reference runs at most 20 iterations.
@@ -461,6 +472,23 @@ VH_API size_t vh_session_export_size(const vh_session* s, vh_session_record* lay
 /* packs stream `slot` into rec_dev (device memory, vh_session_export_size bytes, 8-byte aligned) on `stream`: one launch, no scratch, no wait */
 VH_API int vh_session_export(vh_session* s, int slot, void* rec_dev, void* stream);
 
+/* Anchored points of a slot's clip: world points whose coordinates are known -- the licence-plate corners, tracks 0..3 of every clip, whose frame-0
+ * coordinates come from the plate's size (vidExample.py:116-119) -- and which vh_session_refine / vh_session_refine_windows therefore hold fixed
+ * (vh_nls_batch_windows_fixed): they pin the scale of the adjustment, which is otherwise held only by the +I damping.  A step neither reads nor writes them.
+ *   ids_host  n distinct track ids in [0, n0);  n = 0 clears the slot's anchors
+ *   xyz_host  their coordinates, float64[n][3], in the frame of the clip's camera 0;  NULL: the slot's current p3 rows of those ids, taken in stream
+ *             order (after a device-side frame-0 batch, and BEFORE the re-triangulation frame: fcnMSV1_t overwrites p3 of the surviving tracks)
+ * Queues one clear and one small launch per 96 anchors on `stream`: no upload, no host wait.  A refined window starts an anchored track at the
+ * anchor's coordinates + B[first, 3:6] in place of p3 and flags its row; an anchored track that is not alive in a window is simply not among its
+ * tracks, and a window with nfix = 0 is solved free and says so.  What anchoring does NOT do: for first > 0 the anchors are placed by the tracker's
+ * own B[first, 3:6]; windows are still separate solves; the plate's frame-0 pose error is inherited.  vh_session_init / vh_session_init_dev clear
+ * the slot's anchors: a new clip is a new plate.  Returns -1 with vh_last_error naming the cause, and nothing queued, for: a slot outside the session
+ * or not initialised, n < 0 or n > n0, an id outside [0, n0), an id given twice. */
+VH_API int vh_session_set_anchors(vh_session* s, int slot, const int* ids_host, int n, const double* xyz_host, void* stream);
+/* the slot's anchors read back, ascending id: ids_host int[n0], xyz_host float64[n0][3] (either may be NULL).  Returns their number (-1 on bad
+ * arguments).  Waits for the device: an accessor for tests. */
+VH_API int vh_session_anchors(vh_session* s, int slot, int* ids_host, double* xyz_host);
+
 /* Bundle adjustment of finished clips, straight from the session (default OFF: nothing calls it unless asked).  The refinement the reference's author
  * sketched at vidExample.py:157 -- fcnNLS_batch(K, P[:, :, 0:i], p3, B[0:i, 3:6]), utils/NLS.py:186-250 -- for slots whose clips have had all their nf
  * frames (frame counter nf - 1): tracks = the slot's surviving tracks (vh_session_view::ids, the tracks NLS.py:190 keeps: ascending id), z from the
@@ -479,6 +507,9 @@ typedef struct {
     size_t f_first, f_last;                     /* float64: rms residual (pixels) of the first and of the last iteration, NaN when none ran */
     size_t trace;                               /* float64[max_iter][2] rms(z - zhat), rms(delta) per iteration, 0 behind them */
     int n0, nhist, max_iter;
+    size_t nfix;                                /* int32: anchored points among the nt tracks (vh_session_set_anchors); 0: solved free.  In the record it is
+                                                   the word behind `converged`, which was padding: no offset moved.  Appended HERE, behind every older
+                                                   member, so a caller compiled against the older header reads what it always read */
 } vh_refine_record;
 /* size in bytes of a record for max_iter iterations (0 and vh_last_error on bad arguments); layout_host (may be NULL) receives the offsets */
 VH_API size_t vh_session_refine_size(const vh_session* s, int max_iter, vh_refine_record* layout_host);
@@ -503,7 +534,8 @@ VH_API int vh_session_refine(vh_session* s, const int* slots_host, int nslots, i
  *   K       the slot's own
  * All windows of a call -- of any slots, of clips of any lengths, finished or still running -- are the windows of ONE vh_nls_batch_windows launch
  * sequence (nt = n0, nc = nf - 1).  Clips of more than 256 frames are refined this way: the BA's 255-camera limit is per window.  What windows do NOT
- * do: each window's scale gauge is still held only by the +I damping, and windows are independent solves (no shared points, no global adjustment). */
+ * do: without anchors (vh_session_set_anchors) each window's scale gauge is held only by the +I damping, and windows are independent solves (no shared
+ * points, no global adjustment). */
 typedef struct { int slot; int first; } vh_refine_window;   /* frames [first, first + nf) of the slot's clip */
 /* One record per window, byte offsets as in vh_refine_record; sized by nf, not by nhist (a long clip has many windows).  Every byte is defined. */
 typedef struct {
@@ -519,6 +551,8 @@ typedef struct {
     size_t ids;                                 /* with_points only (else 0): int32[n0] rows [0, nt) global track ids, -1 behind them */
     size_t pw;                                  /* with_points only (else 0): float64[n0][3] rows [0, nt) refined points IN THE WINDOW'S COORDINATES
                                                    (subtract B[first, 3:6] for the session's), NaN behind them                 */
+    size_t nfix;                                /* int32: anchored points among the window's nt tracks; 0: solved free (the record header's spare word:
+                                                   no offset moved).  The last of the offsets: none of the older ones changed place in this struct */
     int n0, nf, max_iter, with_points;
 } vh_refine_window_record;
 /* size in bytes of a record of a window of nf frames (0 and vh_last_error on bad arguments); layout_host (may be NULL) receives the offsets */

@@ -100,22 +100,32 @@ def fzK(a, K):
     return world2image(K, np.eye(3), np.zeros(3), a)
 
 
-def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False):
+def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None):
     """Dense full bundle adjustment over tie points and cameras 1..nc (utils/NLS.py:186-250) -> (cw [nc+1,3], pw [nt,3]).
 
     The track filter, the measurement ordering and the state layout are the reference's (NLS.py:190-203); the
     iterations (forward-difference Jacobian, damped normal equations, x += 0.9 delta) run on the device.
+
+    fixed: None (the reference's solve: its scale is whatever the start had), or a bool mask over the rows of pw: those points are ANCHORED -- they take
+    no step (their rows come back as given) while their measurements still constrain the cameras, which pins the scale to them
+    (vh_nls_batch_windows_fixed).  The mask is filtered like the tracks.
     """
     P = np.asarray(P)
     pw = np.asarray(pw, np.float64)
     cw = np.asarray(cw, np.float64)
     keep = np.isfinite(P[4]).sum(1) == P.shape[2]  # NLS.py:190
+    if fixed is not None:
+        fixed = _fixed_mask(fixed, len(pw), "fcnNLS_batch")[keep]
     P, pw = P[:, keep], pw[keep]
     _, nt, nf = P.shape
     nc = nf - 1
     z = np.concatenate([P[0].T.reshape(-1), P[1].T.reshape(-1)]).astype(np.float64)  # NLS.py:198-199
     x0 = np.concatenate((pw, cw[1:], np.zeros((nc, 3)))).reshape(-1)  # NLS.py:202-203
-    info, x, tr = _ba_solve("vh_nls_batch", L.host_K(K), z, x0, nt, nc, max_iter)
+    if fixed is None:
+        info, x, tr = _ba_solve("vh_nls_batch", L.host_K(K), z, x0, nt, nc, max_iter)
+    else:  # one window of the windows entry: the same launches, the same record
+        fd = L.to_dev(fixed.astype(np.uint8), L.torch_cuda().uint8)
+        info, x, tr = (a[0] for a in _ba_solve("vh_nls_batch_windows_fixed", L.host_K(K), z[None], x0[None], nt, nc, max_iter, 1, (1, L.dptr(None), L.dptr(None), L.dptr(fd))))
     tr = tr[: info[0]]
     for i, (f, xr) in enumerate(tr):
         print(f"{i:g}: f={f:g}, x={xr}")  # NLS.py:238 (without the wall-time column)
@@ -129,14 +139,27 @@ def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False):
     return cw_out, pw_out
 
 
-def pack_windows(Ps, pws, cws):
+def _fixed_mask(fixed, n, who):
+    m = np.asarray(fixed)
+    if m.dtype != np.bool_ or m.shape != (n,):
+        raise ValueError(f"{who}: fixed must be a bool mask over the {n} rows of pw, got {m.dtype} {m.shape}")
+    return m
+
+
+def pack_windows(Ps, pws, cws, fixed=None):
     """Track filter and packing of fcnNLS_batch (utils/NLS.py:190-203) for several windows of one number of frames, laid out for the largest track
     count nt: z [nw, 2 nt nf] and x0 [nw, 3 nt + 6 nc] in the layout of vh_nls_batch_multi, counts int32[nw].  Rows behind a window's own count
-    are padding: NaN measurements (no observation, see k_ba_jac) and the point (0, 0, 1).  Host only."""
-    zs, pts, cams, nf0 = [], [], [], None
-    for P, pw, cw in zip(Ps, pws, cws):
+    are padding: NaN measurements (no observation, see k_ba_jac) and the point (0, 0, 1).  Host only.  fixed: None, or one bool mask per window over
+    the rows of its pw (None inside the list: no anchors in that window); the result then gains a sixth item, the flags uint8 [nw, nt] of the kept
+    tracks (padding rows 0)."""
+    zs, pts, cams, flags, nf0 = [], [], [], [], None
+    if fixed is not None and len(fixed) != len(Ps):
+        raise ValueError(f"fcnNLS_batch_windows: {len(fixed)} masks for {len(Ps)} windows")
+    for w, (P, pw, cw) in enumerate(zip(Ps, pws, cws)):
         P, pw, cw = np.asarray(P), np.asarray(pw, np.float64), np.asarray(cw, np.float64)
         keep = np.isfinite(P[4]).sum(1) == P.shape[2]  # NLS.py:190
+        if fixed is not None:
+            flags.append(np.zeros(int(keep.sum()), bool) if fixed[w] is None else _fixed_mask(fixed[w], len(pw), "fcnNLS_batch_windows")[keep])
         P, pw = P[:, keep], pw[keep]
         nf = P.shape[2]
         if nf0 is None:
@@ -155,25 +178,39 @@ def pack_windows(Ps, pws, cws):
     for w in range(nw):
         z[w, :, :, : counts[w]] = zs[w].transpose(0, 2, 1)
         x0[w] = np.concatenate((pts[w].reshape(-1), np.tile([0.0, 0.0, 1.0], nt - counts[w]), cams[w]))
-    return z.reshape(nw, -1), x0, counts, nt, nc
+    if fixed is None:
+        return z.reshape(nw, -1), x0, counts, nt, nc
+    fx = np.zeros((nw, nt), np.uint8)
+    for w in range(nw):
+        fx[w, : counts[w]] = flags[w]
+    return z.reshape(nw, -1), x0, counts, nt, nc, fx
 
 
-def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False):
+def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=None):
     """fcnNLS_batch (utils/NLS.py:186-250) for several independent windows of the same number of frames (one finished clip or sliding window per
     video stream) in one launch sequence (grid.y = window).  Ps / pws / cws: sequences of the reference's P, pw, cw arguments.  K: one 3x3 matrix
     for all windows, or one per window ([nw, 3, 3]).  The windows may keep different numbers of full-length tracks: pack_windows lays them out for
     the largest count and pads with unobserved points, which take no part in the solve (vh_nls_batch_windows); windows of equal counts and one K
     go through vh_nls_batch_multi unchanged.  A window without a full-length track is not solved (cw comes back as given).  Returns
-    [(cw, pw), ...], pw cut to the window's own tracks (with return_info: also the padded x and the trace)."""
+    [(cw, pw), ...], pw cut to the window's own tracks (with return_info: also the padded x and the trace).  fixed: None, or a list of bool masks, one per
+    window over the rows of its pw (see fcnNLS_batch; None inside the list: that window is solved free)."""
     torch = L.torch_cuda()
-    z, x0, counts, nt, nc = pack_windows(Ps, pws, cws)
+    fx = None
+    if fixed is None:
+        z, x0, counts, nt, nc = pack_windows(Ps, pws, cws)
+    else:
+        z, x0, counts, nt, nc, fx = pack_windows(Ps, pws, cws, fixed)
     nw = len(counts)
     K64 = np.asarray(K, np.float64)
     per_window_K = K64.ndim == 3
     if per_window_K and len(K64) != nw:
         raise ValueError(f"fcnNLS_batch_windows: {len(K64)} intrinsics for {nw} windows")
     K_host = L.host_K(K64[0] if per_window_K else K64)
-    if per_window_K or (counts != nt).any():
+    if fx is not None:
+        ntd, fd = L.to_dev(counts, torch.int32), L.to_dev(fx, torch.uint8)
+        Kd = L.to_dev(K64.reshape(nw, 9), torch.float64) if per_window_K else None
+        info, x, tr = _ba_solve("vh_nls_batch_windows_fixed", K_host, z, x0, nt, nc, max_iter, nw, (nw, L.dptr(ntd), L.dptr(Kd), L.dptr(fd)))
+    elif per_window_K or (counts != nt).any():
         ntd = L.to_dev(counts, torch.int32)
         Kd = L.to_dev(K64.reshape(nw, 9), torch.float64) if per_window_K else None
         info, x, tr = _ba_solve("vh_nls_batch_windows", K_host, z, x0, nt, nc, max_iter, nw, (nw, L.dptr(ntd), L.dptr(Kd)))

@@ -45,7 +45,7 @@ class RefineRecord(C.Structure):
     """vh_refine_record: byte offsets of the fields of a refined clip's record (vh_session_refine)."""
 
     _fields_ = [(k, C.c_size_t) for k in ("bytes", "nt", "iterations", "converged", "ids", "pw", "cw", "dr", "speed", "speed_mean", "speed_std", "f_first",
-                                          "f_last", "trace")] + [("n0", C.c_int), ("nhist", C.c_int), ("max_iter", C.c_int)]
+                                          "f_last", "trace")] + [("n0", C.c_int), ("nhist", C.c_int), ("max_iter", C.c_int), ("nfix", C.c_size_t)]
 
 
 class RefineWindow(C.Structure):
@@ -58,7 +58,7 @@ class RefineWindowRecord(C.Structure):
     """vh_refine_window_record: byte offsets of the fields of a refined window's record (vh_session_refine_windows)."""
 
     _fields_ = [(k, C.c_size_t) for k in ("bytes", "slot", "first", "nt", "iterations", "converged", "cw", "dr", "speed", "speed_mean", "speed_std", "f_first",
-                                          "f_last", "trace", "ids", "pw")] + [("n0", C.c_int), ("nf", C.c_int), ("max_iter", C.c_int), ("with_points", C.c_int)]
+                                          "f_last", "trace", "ids", "pw", "nfix")] + [("n0", C.c_int), ("nf", C.c_int), ("max_iter", C.c_int), ("with_points", C.c_int)]
 
 
 class MatchParams(C.Structure):
@@ -119,6 +119,7 @@ _SIGS = {
     "vh_nls_batch": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_nls_batch_multi": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_nls_batch_windows": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
+    "vh_nls_batch_windows_fixed": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_nls_batch2": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_good_features": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, vp, vp, vp]),
     "vh_corner_subpix": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp]),
@@ -139,6 +140,8 @@ _SIGS = {
     "vh_session_refine_windows_size": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(RefineWindowRecord)]),
     "vh_session_refine_windows_workspace": (C.c_size_t, [vp, C.c_int, C.c_int]),
     "vh_session_refine_windows": (C.c_int, [vp, C.POINTER(RefineWindow), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),
+    "vh_session_set_anchors": (C.c_int, [vp, C.c_int, i32p, C.c_int, f64p, vp]),
+    "vh_session_anchors": (C.c_int, [vp, C.c_int, i32p, f64p]),
     "vh_session_ptrs": (C.c_int, [vp, C.c_int, C.POINTER(SessionView)]),
     "vh_session_pack_state": (C.c_int, [vp, vp, vp]),
     "vh_debug_force_generic_lk": (None, [C.c_int]),

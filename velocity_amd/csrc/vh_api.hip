@@ -954,13 +954,22 @@ extern "C" VH_API int vh_nls_batch_windows(vh_ctx* c, const double* K_host, cons
                                            const double* K_win_dev, int max_iter, double* trace, int* info, void* workspace,
                                            size_t workspace_bytes_per_window, void* stream)
 {
-    return vh_ba_windows(c, K_host, z, x, nt, nc, nwin, nt_win_dev, K_win_dev, max_iter, trace, (size_t)2 * (max_iter > 0 ? max_iter : 0), info, 2, workspace,
-                         workspace_bytes_per_window, stream);
+    return vh_nls_batch_windows_fixed(c, K_host, z, x, nt, nc, nwin, nt_win_dev, K_win_dev, nullptr, max_iter, trace, info, workspace, workspace_bytes_per_window,
+                                      stream);
+}
+
+// ... with anchored points: fixed_dev [nwin][nt], non-zero = the row takes no step (vh_ba.hpp); null = none, which is vh_nls_batch_windows
+extern "C" VH_API int vh_nls_batch_windows_fixed(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
+                                                 const double* K_win_dev, const uint8_t* fixed_dev, int max_iter, double* trace, int* info, void* workspace,
+                                                 size_t workspace_bytes_per_window, void* stream)
+{
+    return vh_ba_windows(c, K_host, z, x, nt, nc, nwin, nt_win_dev, K_win_dev, fixed_dev, max_iter, trace, (size_t)2 * (max_iter > 0 ? max_iter : 0), info, 2,
+                         workspace, workspace_bytes_per_window, stream);
 }
 
 // ... with the windows' trace / info records trace_stride doubles / info_stride ints apart (vh_session_refine writes them straight into its records)
 int vh_ba_windows(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev, const double* K_win_dev,
-                  int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride, void* workspace, size_t workspace_bytes_per_window,
+                  const uint8_t* fixed_dev, int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride, void* workspace, size_t workspace_bytes_per_window,
                   void* stream)
 {
     if (nwin < 1 || nwin > 65535) return vh_fail(-1, "vh_nls_batch_multi: bad arguments");
@@ -969,7 +978,7 @@ int vh_ba_windows(vh_ctx* c, const double* K_host, const double* z, double* x, i
                            workspace_bytes_per_window % 256 ? 0 : workspace_bytes_per_window,  // a stride that would misalign the next window counts as too small
                            "per-window workspace too small or not a multiple of 256 bytes"))
         return r;
-    P.nt_win = nt_win_dev; P.K_win = K_win_dev;
+    P.nt_win = nt_win_dev; P.K_win = K_win_dev; P.fixed = fixed_dev;
     P.nparts = ba_parts(nt, nc, nwin);
     P.nwin = nwin; P.ws_stride = workspace_bytes_per_window; P.z_stride = (size_t)2 * nt * (nc + 1); P.x_stride = (size_t)3 * nt + 6 * (size_t)nc;
     P.trace_stride = trace_stride; P.info_stride = info_stride;

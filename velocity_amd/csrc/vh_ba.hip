@@ -29,6 +29,7 @@ __device__ __forceinline__ void ba_select_window(BaJob& J, int w)
     J.done = reinterpret_cast<int*>(reinterpret_cast<char*>(J.done) + (size_t)w * J.ws_stride);
     J.ticket = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(J.ticket) + (size_t)w * J.ws_stride);
     J.z += (size_t)w * J.z_stride; J.x += (size_t)w * J.x_stride; J.trace += (size_t)w * J.trace_stride; J.info += (size_t)w * J.info_stride;
+    if (J.fixed) J.fixed += (size_t)w * J.nt;
 }
 
 __device__ void ba_rpy2dcm(const double* rpy, double* C)
@@ -161,8 +162,10 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_jac(BaJob J)
     double o[20];  // r (2) | Jp (6) | Jc (12)
 #pragma unroll
     for (int k = 0; k < 20; k++) o[k] = 0.0;
+    bool anchored = false;
     if (il < npts) {
         const int i = i0 + il, c = threadIdx.x - il * nf;  // POINT-major measurement index m = i (nc+1) + c: a point's Jacobians are contiguous
+        if (J.fixed) anchored = J.fixed[i] != 0;  // (a null table is wave-uniform: no lane takes the load; issued first, used last)
         double K[9];
         if (J.K_win) for (int k = 0; k < 9; k++) K[k] = J.K_win[9 * (size_t)blockIdx.y + k];  // the window's own camera (wave-uniform: scalar loads)
         else for (int k = 0; k < 9; k++) K[k] = J.K[k];
@@ -236,6 +239,12 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_jac(BaJob J)
         ss = 0.0;
 #pragma unroll
         for (int k = 0; k < 20; k++) o[k] = 0.0;
+    }
+    // an anchored point keeps its residual and its camera columns and has exact zeros for its own three: U_i + I = I, tp_i = 0, W_i = 0 on every route
+    // of vh_ba_plan.hpp -- it takes no step, and its measurements still constrain the cameras that see it (vh_ba.hpp)
+    if (anchored) {
+#pragma unroll
+        for (int k = 2; k < 8; k++) o[k] = 0.0;
     }
 #pragma unroll
     for (int k = 0; k < 20; k++) s_out[k][threadIdx.x] = o[k];
@@ -1963,7 +1972,7 @@ static void ba_layout(const BaProblem& P, BaJob& J)
     J.add_identity = P.add_identity; J.count_cams = P.count_cams; J.defer_finalize = P.defer_finalize;
     J.nx_total = P.nx_total; J.nz_total = P.nz_total;
     J.nwin = P.nwin < 1 ? 1 : P.nwin;
-    J.nt_win = P.nt_win; J.K_win = P.K_win;
+    J.nt_win = P.nt_win; J.K_win = P.K_win; J.fixed = P.fixed;
     J.ws_stride = P.ws_stride; J.z_stride = P.z_stride; J.x_stride = P.x_stride; J.trace_stride = P.trace_stride; J.info_stride = P.info_stride;
     ba_workspace_walk(P.nt, P.nc, P.nparts, P.workspace, &J);
 }

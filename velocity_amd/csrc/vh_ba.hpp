@@ -44,6 +44,10 @@ struct BaJob {  // passed by value to every BA kernel
     // (NaN measurements: exact zeros everywhere, see k_ba_jac).  Both tables are read on the device; null = nt tracks / K for every window
     const int* nt_win;               // [nwin] true track counts: the two rms divisors of the iteration record, and the start flag of an empty window
     const double* K_win;             // [nwin][9] intrinsics of each window
+    // anchored (fixed) points (vh_nls_batch_windows_fixed): a flagged row has exact zeros for its three Jacobian columns (k_ba_jac), so U_i + I = I,
+    // tp_i = 0, W_i = 0: it takes no step and subtracts nothing from the reduced system, while its measurements still add Jc^T Jc and Jc^T r to its
+    // cameras.  It still counts as rows of x (nx, nz are unchanged).  Null = no anchors
+    const uint8_t* fixed;            // [nwin][nt] non-zero = anchored
 };
 
 struct BaProblem {  // every field defaults to zero / null: an entry point sets what it uses (ba_problem in vh_api.hip fills the single-window defaults)
@@ -63,6 +67,7 @@ struct BaProblem {  // every field defaults to zero / null: an entry point sets 
     size_t ws_stride = 0, z_stride = 0, x_stride = 0, trace_stride = 0, info_stride = 0;  // see BaJob (ignored when nwin == 1)
     const int* nt_win = nullptr;  // see BaJob (device, may be null)
     const double* K_win = nullptr;
+    const uint8_t* fixed = nullptr;
     struct vh_ctx* ctx = nullptr;  // may be null: per-kernel HIP-event timing when its profiling is on (vh_profile_begin)
     void** graph_cache = nullptr;  // may be null: where the owner (vh_ctx) keeps the replayable launch sequences of whole solves (vh_ba_graph_cache_free)
 };
@@ -71,7 +76,7 @@ void vh_ba_graph_cache_free(void* cache);
 size_t vh_ba_workspace_bytes(int nt, int nc, int nparts);
 int vh_ba_run(const BaProblem& P, hipStream_t s);
 void vh_ba_exchange_span(const BaProblem& P, size_t* offset_bytes, size_t* n_doubles);
-// vh_nls_batch_windows (include/velocity_hip.h) with the caller's own distances between the windows' trace (doubles) and info (ints) records (vh_api.hip)
+// vh_nls_batch_windows_fixed (include/velocity_hip.h) with the caller's own distances between the windows' trace (doubles) and info (ints) records (vh_api.hip)
 int vh_ba_windows(struct vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
-                  const double* K_win_dev, int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride, void* workspace,
-                  size_t workspace_bytes_per_window, void* stream);
+                  const double* K_win_dev, const uint8_t* fixed_dev, int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride,
+                  void* workspace, size_t workspace_bytes_per_window, void* stream);

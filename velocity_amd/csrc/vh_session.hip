@@ -57,6 +57,12 @@ struct vh_session {
     int* h_frame;      // per stream: frames stepped since its vh_session_init (host mirror of SessStream::frame_i; the
                        // reference fires fcnMSV1_t at `i == msvFrame` of EACH video, vidExample.py:155)
     SessFallback fb;
+    // anchored points of each slot's clip (vh_session_set_anchors): world points the refinement holds fixed.  Kept beside the streams, not in them:
+    // a step neither reads nor writes them
+    uint8_t* d_anc_mask;  // [batch][N0] non-zero = track id is anchored
+    double* d_anc_xyz;    // [batch][N0][3] its coordinates, in the frame of the clip's camera 0 (rows of unanchored ids: undefined)
+    int* h_nanchor;       // per slot: anchors set (host)
+    char* h_inited;       // per slot: vh_session_init has run
 };
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -328,12 +334,14 @@ extern "C" VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, i
     s->h_ss = new SessStream[s->batch];
     memset(s->h_ss, 0, sizeof(SessStream) * s->batch);
     s->h_frame = new int[s->batch]();
+    s->h_nanchor = new int[s->batch]();
+    s->h_inited = new char[s->batch]();
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
     for (int pass = 0; pass < 2; pass++) {
         if (pass == 1) {
             hipError_t e = hipMalloc((void**)&s->arena, off);
-            if (e != hipSuccess) { delete[] s->h_ss; delete[] s->h_frame; delete s; vh_set_error("hipMalloc(session)", e, __FILE__, __LINE__); return (int)e; }
+            if (e != hipSuccess) { delete[] s->h_ss; delete[] s->h_frame; delete[] s->h_nanchor; delete[] s->h_inited; delete s; vh_set_error("hipMalloc(session)", e, __FILE__, __LINE__); return (int)e; }
             (void)hipMemset(s->arena, 0, off);
             off = 0;
         }
@@ -353,6 +361,8 @@ extern "C" VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, i
             S.msv_U = (double*)(base + carve(sizeof(double) * 3 * (size_t)(sess_msv_fires(msv_frame, nhist) ? msv_frame + 1 : 1) * n0));  /* one row when fcnMSV1_t can never fire (a 'never' sentinel must not size the buffer) */ S.msv_b0 = (double*)(base + carve(sizeof(double) * 3 * n0));
             S.small[0] = (uint8_t*)(base + carve((size_t)dw * dh)); S.small[1] = (uint8_t*)(base + carve((size_t)dw * dh));
         }
+        s->d_anc_mask = (uint8_t*)(base + carve((size_t)s->batch * n0));  // (zero = no anchors: the arena is cleared)
+        s->d_anc_xyz = (double*)(base + carve(sizeof(double) * 3 * (size_t)s->batch * n0));
     }
     for (int b = 0; b < s->batch; b++) {
         SessStream& S = s->h_ss[b];
@@ -373,7 +383,7 @@ extern "C" VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, i
         M.U = S.msv_U; M.b0 = S.msv_b0; M.x_out = d->msv_x; M.info_out = d->msv_info;
     }
     hipError_t e = hipMemcpy(s->d_ss, s->h_ss, sizeof(SessStream) * s->batch, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(s->arena); delete[] s->h_ss; delete[] s->h_frame; delete s; vh_set_error("hipMemcpy(session)", e, __FILE__, __LINE__); return (int)e; }
+    if (e != hipSuccess) { (void)hipFree(s->arena); delete[] s->h_ss; delete[] s->h_frame; delete[] s->h_nanchor; delete[] s->h_inited; delete s; vh_set_error("hipMemcpy(session)", e, __FILE__, __LINE__); return (int)e; }
     *out = s;
     return 0;
 }
@@ -501,6 +511,8 @@ extern "C" VH_API void vh_session_destroy(vh_session* s)
     (void)hipFree(s->arena);
     delete[] s->h_ss;
     delete[] s->h_frame;
+    delete[] s->h_nanchor;
+    delete[] s->h_inited;
     delete s;
 }
 
@@ -553,6 +565,11 @@ static int session_init(vh_session* s, int slot, const uint8_t* frame0, int stri
     H.stride = stride;
     if (r) return r;
     s->h_frame[slot] = 0;  // a (re-)initialised slot starts a new clip: its MSV frame counts from here
+    s->h_inited[slot] = 1;
+    if (s->h_nanchor[slot] > 0) {  // ... and a new clip is a new plate (a slot that had no anchors queues nothing here)
+        s->h_nanchor[slot] = 0;
+        VH_CHECK(hipMemsetAsync(s->d_anc_mask + (size_t)slot * s->N0, 0, (size_t)s->N0, st));
+    }
     if (s->fb.counts) s->fb.counts[2 * slot] = s->fb.counts[2 * slot + 1] = 0;
     SESS_CHECK();
     return 0;
@@ -730,6 +747,80 @@ extern "C" VH_API int vh_session_export(vh_session* s, int slot, void* rec_dev, 
     return 0;
 }
 
+// ---- anchored points of a slot's clip (vh_session_set_anchors): what the refinements below hold fixed ----------------------------------------------------
+#define SESS_ANC_CHUNK 96  // anchors per launch: ids and coordinates travel in the kernel arguments (no upload, no host wait), 2688 bytes of them
+struct AnchorChunk {
+    int id[SESS_ANC_CHUNK];
+    double xyz[SESS_ANC_CHUNK][3];
+};
+// snapshot: the slot's current p3 rows (what frame 0 gave them, when taken before fcnMSV1_t overwrites p3[vg] at the MSV frame)
+__global__ __launch_bounds__(128) void k_sess_anchors(const SessStream* ss, uint8_t* mask, double* xyz, AnchorChunk ch, int cnt, int snapshot)
+{
+    const int t = threadIdx.x;
+    if (t >= cnt) return;
+    const int id = ch.id[t];
+    mask[id] = 1;
+    for (int c = 0; c < 3; c++) xyz[3 * (size_t)id + c] = snapshot ? ss->p3[3 * (size_t)id + c] : ch.xyz[t][c];
+}
+
+extern "C" VH_API int vh_session_set_anchors(vh_session* s, int slot, const int* ids_host, int n, const double* xyz_host, void* stream)
+{
+    char msg[200];
+    if (!s) return vh_fail(-1, "vh_session_set_anchors: null session");
+    if (slot < 0 || slot >= s->batch) {
+        snprintf(msg, sizeof(msg), "vh_session_set_anchors: slot %d is outside the session's %d slots", slot, s->batch);
+        return vh_fail(-1, msg);
+    }
+    if (!s->h_inited[slot]) { snprintf(msg, sizeof(msg), "vh_session_set_anchors: slot %d is not initialised (vh_session_init)", slot); return vh_fail(-1, msg); }
+    if (n < 0 || n > s->N0) { snprintf(msg, sizeof(msg), "vh_session_set_anchors: slot %d: n = %d anchors, the session has %d tracks", slot, n, s->N0); return vh_fail(-1, msg); }
+    if (n > 0 && !ids_host) { snprintf(msg, sizeof(msg), "vh_session_set_anchors: slot %d: null ids for %d anchors", slot, n); return vh_fail(-1, msg); }
+    std::vector<char> seen(s->N0, 0);
+    for (int k = 0; k < n; k++) {
+        const int id = ids_host[k];
+        if (id < 0 || id >= s->N0) { snprintf(msg, sizeof(msg), "vh_session_set_anchors: slot %d: id %d is outside [0, %d)", slot, id, s->N0); return vh_fail(-1, msg); }
+        if (seen[id]) { snprintf(msg, sizeof(msg), "vh_session_set_anchors: slot %d: id %d is given twice", slot, id); return vh_fail(-1, msg); }
+        seen[id] = 1;
+    }
+    VH_BIND(s->ctx, stream);
+    uint8_t* mask = s->d_anc_mask + (size_t)slot * s->N0;
+    double* xyz = s->d_anc_xyz + 3 * (size_t)slot * s->N0;
+    const int had = s->h_nanchor[slot];
+    s->h_nanchor[slot] = n;  // before anything is queued: should a launch below fail, the host count still says what the (partly written) table was asked to hold
+    if (had > 0 || n > 0) VH_CHECK(hipMemsetAsync(mask, 0, (size_t)s->N0, bound_.s));
+    for (int k0 = 0; k0 < n; k0 += SESS_ANC_CHUNK) {
+        AnchorChunk ch;
+        memset(&ch, 0, sizeof(ch));
+        const int cnt = n - k0 < SESS_ANC_CHUNK ? n - k0 : SESS_ANC_CHUNK;
+        for (int k = 0; k < cnt; k++) {
+            ch.id[k] = ids_host[k0 + k];
+            if (xyz_host) for (int c = 0; c < 3; c++) ch.xyz[k][c] = xyz_host[3 * (size_t)(k0 + k) + c];
+        }
+        hipLaunchKernelGGL(k_sess_anchors, dim3(1), dim3(128), 0, bound_.s, s->d_ss + slot, mask, xyz, ch, cnt, xyz_host ? 0 : 1);
+    }
+    SESS_CHECK();
+    return 0;
+}
+
+// the slot's anchors read back, ascending id (a test accessor: it waits for the device).  Returns their number, -1 on bad arguments
+extern "C" VH_API int vh_session_anchors(vh_session* s, int slot, int* ids_host, double* xyz_host)
+{
+    if (!s || slot < 0 || slot >= s->batch) return vh_fail(-1, "vh_session_anchors: bad arguments");
+    std::vector<uint8_t> mask(s->N0);
+    std::vector<double> xyz(3 * (size_t)s->N0);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(mask.data(), s->d_anc_mask + (size_t)slot * s->N0, (size_t)s->N0, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(xyz.data(), s->d_anc_xyz + 3 * (size_t)slot * s->N0, sizeof(double) * 3 * (size_t)s->N0, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { vh_set_error("vh_session_anchors: reading the table back", e, __FILE__, __LINE__); return -1; }  // (a count is never negative)
+    int n = 0;
+    for (int id = 0; id < s->N0; id++) {
+        if (!mask[id]) continue;
+        if (ids_host) ids_host[n] = id;
+        if (xyz_host) for (int c = 0; c < 3; c++) xyz_host[3 * (size_t)n + c] = xyz[3 * (size_t)id + c];
+        n++;
+    }
+    return n;
+}
+
 // ---- bundle adjustment of finished clips (vh_session_refine; vidExample.py:157, NLS.py:186-250) ----------------------------------------------------------
 // pack: the slot's surviving tracks, its history, world points, per-frame translations and camera -> window w of one vh_nls_batch_windows problem laid out
 // for N0 tracks; unpack: the refined state and the speed derived from it -> record w.  The session is only read.
@@ -744,6 +835,7 @@ struct RefWs {  // the scratch of one call, carved by refine_ws_layout
     int* nt;     // [nslots]
     int* ids;    // [nslots][N0] the tracks of each window, ascending (vh_session_refine_windows only: a whole clip's are the slot's survivors)
     char* ba;    // [nslots] BA workspaces, ba_stride bytes apart
+    uint8_t* fixed;  // [nslots][N0] anchored rows of each window (read by the solve only when a slot of the request has anchors)
     size_t z_stride, x_stride, ba_stride;
 };
 
@@ -752,6 +844,7 @@ static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_reco
     size_t off = 0;
     auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
     L->nt = put(4 * sizeof(int)); L->iterations = L->nt + 4; L->converged = L->nt + 8;  // (iterations, converged: the int[2] info record of the window's solve)
+    L->nfix = L->nt + 12;                                                               // (the header's fourth word)
     L->ids = put(sizeof(int) * (size_t)N0);
     L->pw = put(sizeof(double) * 3 * (size_t)N0);
     L->cw = put(sizeof(double) * 3 * (size_t)nhist);
@@ -775,6 +868,7 @@ static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* ba
     W->nt = (int*)carve(sizeof(int) * nw);
     W->ids = with_ids ? (int*)carve(sizeof(int) * nw * N0) : nullptr;
     W->ba = carve(nw * W->ba_stride);
+    W->fixed = (uint8_t*)carve(nw * N0);  // (behind everything else: no other offset moves)
     return off;
 }
 
@@ -782,7 +876,11 @@ static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* ba
 // ids[0..n) -> z, x0 and K of one window of a vh_ba_windows problem laid out for N0 tracks.  The session's points satisfy proj(K (p3 + B[i, 3:6])) and the
 // BA fixes its camera 0 at the origin, so the window's points are p3 + B[first, 3:6] and its cameras B[first + c, 3:6] - B[first, 3:6]: float32 values
 // widened to double first, the arithmetic in double (first = 0: B[0, 3:6] is 0, both are the session's own values).
-__device__ __forceinline__ void refine_pack_window(const SessStream& S, const int* ids, int n, int first, int nf, double* z, double* x, double* Kw, int tid)
+// Anchors (am, ax: the slot's mask and coordinates over its N0 ids, null = none; fx: the window's row flags for the solve): a kept track that is anchored
+// starts at its anchor's coordinates in place of p3, still + B[first, 3:6], and its row is flagged; padding rows never are.  Returns the anchors among the
+// window's tracks (every thread of the workgroup calls this, every thread gets the count).
+__device__ __forceinline__ int refine_pack_window(const SessStream& S, const int* ids, int n, int first, int nf, double* z, double* x, double* Kw, int tid,
+                                                  const uint8_t* am, const double* ax, uint8_t* fx)
 {
     const int N0 = S.N0, nc = nf - 1;
     const double nanv = __longlong_as_double(0x7ff8000000000000LL);
@@ -798,7 +896,15 @@ __device__ __forceinline__ void refine_pack_window(const SessStream& S, const in
     const float* B0 = S.B + 14 * (size_t)first + 3;
     for (int e = tid; e < 3 * N0; e += 256) {
         const int k = e / 3, c = e - 3 * k;
-        x[e] = k < n ? S.p3[3 * (size_t)ids[k] + c] + (double)B0[c] : (c == 2 ? 1.0 : 0.0);
+        if (k < n) {
+            const int id = ids[k];
+            const bool anchored = am && am[id];
+            x[e] = (anchored ? ax[3 * (size_t)id + c] : S.p3[3 * (size_t)id + c]) + (double)B0[c];
+            if (am && c == 0) fx[k] = anchored ? 1 : 0;
+        } else {
+            x[e] = c == 2 ? 1.0 : 0.0;
+            if (am && c == 0) fx[k] = 0;
+        }
     }
     for (int e = tid; e < 3 * nc; e += 256) {
         const int i = e / 3 + 1, c = e - 3 * (i - 1);
@@ -806,6 +912,15 @@ __device__ __forceinline__ void refine_pack_window(const SessStream& S, const in
         x[3 * (size_t)N0 + 3 * nc + e] = 0.0;
     }
     if (tid < 9) Kw[tid] = S.K[tid];
+    if (!am) return 0;
+    __shared__ int s_nfix;
+    if (tid == 0) s_nfix = 0;
+    __syncthreads();
+    int cnt = 0;
+    for (int k = tid; k < n; k += 256) cnt += am[ids[k]] ? 1 : 0;
+    if (cnt) atomicAdd(&s_nfix, cnt);
+    __syncthreads();
+    return s_nfix;
 }
 
 // where the derived quantities of one solved window go (both record types)
@@ -865,17 +980,22 @@ __device__ __forceinline__ void refine_unpack_window(const SessStream& S, const 
     }
 }
 
-__global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, RefSlots sl, int w0, int nf, RefWs W, vh_refine_record L, char* recs)
+// anc_mask / anc_xyz: the session's anchor tables over all slots, null when no slot of the request has anchors
+__global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, RefSlots sl, int w0, int nf, RefWs W, vh_refine_record L, char* recs,
+                                                     const uint8_t* anc_mask, const double* anc_xyz)
 {
     const int w = w0 + blockIdx.x, tid = threadIdx.x;
-    const SessStream& S = ss_all[sl.slot[blockIdx.x]];
+    const int slot = sl.slot[blockIdx.x];
+    const SessStream& S = ss_all[slot];
     const int N0 = S.N0, n = min(max(S.n_cur, 0), N0);
     // the slot's survivors are the tracks NLS.py:190 keeps of a clip that has just had its last frame
-    refine_pack_window(S, S.ids, n, 0, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid);
+    const int nfix = refine_pack_window(S, S.ids, n, 0, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid,
+                                        anc_mask ? anc_mask + (size_t)slot * N0 : nullptr, anc_mask ? anc_xyz + 3 * (size_t)slot * N0 : nullptr,
+                                        W.fixed + (size_t)w * N0);
     if (tid == 0) W.nt[w] = n;
-    // the part of the record the solve writes into (info, trace rows up to the iterations it takes): defined from the start
+    // the part of the record the solve writes into (info, trace rows up to the iterations it takes): defined from the start; the fourth header word: nfix
     char* rec = recs + (size_t)w * L.bytes;
-    if (tid < 4) reinterpret_cast<int*>(rec + L.nt)[tid] = 0;
+    if (tid < 4) reinterpret_cast<int*>(rec + L.nt)[tid] = tid == 3 ? nfix : 0;
     double* trace = reinterpret_cast<double*>(rec + L.trace);
     for (int e = tid; e < 2 * L.max_iter; e += 256) trace[e] = 0.0;
 }
@@ -907,7 +1027,8 @@ static void refine_window_record_layout(int N0, int nf, int max_iter, int with_p
     size_t off = 0;
     auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
     L->slot = put(6 * sizeof(int)); L->first = L->slot + 4; L->nt = L->slot + 8;
-    L->iterations = L->slot + 12; L->converged = L->slot + 16;  // (iterations, converged: the int[2] info record of the window's solve; one pad word)
+    L->iterations = L->slot + 12; L->converged = L->slot + 16;  // (iterations, converged: the int[2] info record of the window's solve)
+    L->nfix = L->slot + 20;                                      // (the header's sixth word)
     L->cw = put(sizeof(double) * 3 * (size_t)nf);
     L->dr = put(sizeof(double) * (size_t)nf); L->speed = put(sizeof(double) * (size_t)nf);
     L->speed_mean = put(sizeof(double)); L->speed_std = put(sizeof(double)); L->f_first = put(sizeof(double)); L->f_last = put(sizeof(double));
@@ -921,7 +1042,8 @@ static void refine_window_record_layout(int N0, int nf, int max_iter, int with_p
 // select + pack: the window's tracks are the ids whose history row 4 is finite in EVERY frame of the window (NLS.py:190 on the slice) -- not the slot's
 // current survivors: a track that died after the window belongs to it.  One workgroup per window: 256 ids at a time read row 4 of the frame-major
 // history (coalesced over tracks), a ballot + the four wavefronts' counts give each kept id its place, so the ids come out ascending.
-__global__ __launch_bounds__(256) void k_refine_win_pack(const SessStream* ss_all, RefWins wn, int w0, int nf, RefWs W, vh_refine_window_record L, char* recs)
+__global__ __launch_bounds__(256) void k_refine_win_pack(const SessStream* ss_all, RefWins wn, int w0, int nf, RefWs W, vh_refine_window_record L, char* recs,
+                                                         const uint8_t* anc_mask, const double* anc_xyz)
 {
     const int w = w0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int slot = wn.slot[blockIdx.x], first = wn.first[blockIdx.x];
@@ -946,11 +1068,13 @@ __global__ __launch_bounds__(256) void k_refine_win_pack(const SessStream* ss_al
         __syncthreads();
     }
     const int n = s_base;  // (the ids written above are visible to the whole workgroup: barriers since)
-    refine_pack_window(S, ids, n, first, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid);
+    const int nfix = refine_pack_window(S, ids, n, first, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid,
+                                        anc_mask ? anc_mask + (size_t)slot * N0 : nullptr, anc_mask ? anc_xyz + 3 * (size_t)slot * N0 : nullptr,
+                                        W.fixed + (size_t)w * N0);
     if (tid == 0) W.nt[w] = n;
-    // the part of the record the solve writes into (info, trace rows up to the iterations it takes) and the header: defined from the start
+    // the part of the record the solve writes into (info, trace rows up to the iterations it takes) and the header (sixth word: nfix): defined from the start
     char* rec = recs + (size_t)w * L.bytes;
-    if (tid < 6) reinterpret_cast<int*>(rec + L.slot)[tid] = tid == 0 ? slot : (tid == 1 ? first : 0);
+    if (tid < 6) reinterpret_cast<int*>(rec + L.slot)[tid] = tid == 0 ? slot : (tid == 1 ? first : (tid == 5 ? nfix : 0));
     double* trace = reinterpret_cast<double*>(rec + L.trace);
     for (int e = tid; e < 2 * L.max_iter; e += 256) trace[e] = 0.0;
 }
@@ -1018,21 +1142,23 @@ extern "C" VH_API int vh_session_refine(vh_session* s, const int* slots_host, in
     vh_refine_record L;
     refine_record_layout(s->N0, s->nhist, max_iter, &L);
     char* recs = reinterpret_cast<char*>(recs_dev);
-    auto each_chunk = [&](auto kernel, hipStream_t st) {
+    bool anchored = false;  // the tables travel only when a slot of the request has anchors: otherwise the solve is queued as ever, with no table
+    for (int k = 0; k < nslots; k++) anchored = anchored || s->h_nanchor[slots_host[k]] > 0;
+    auto each_chunk = [&](auto kernel, hipStream_t st, auto... more) {
         for (int w0 = 0; w0 < nslots; w0 += SESS_REF_CHUNK) {
             RefSlots sl;
             const int cnt = nslots - w0 < SESS_REF_CHUNK ? nslots - w0 : SESS_REF_CHUNK;
             for (int k = 0; k < SESS_REF_CHUNK; k++) sl.slot[k] = slots_host[w0 + (k < cnt ? k : 0)];
-            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, sl, w0, nf, W, L, recs);
+            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, sl, w0, nf, W, L, recs, more...);
         }
     };
     {
         VH_BIND(s->ctx, stream);
-        each_chunk(k_refine_pack, bound_.s);
+        each_chunk(k_refine_pack, bound_.s, anchored ? (const uint8_t*)s->d_anc_mask : nullptr, anchored ? (const double*)s->d_anc_xyz : nullptr);
         SESS_CHECK();
     }
     // the windows' info = {iterations, converged} and trace go straight into the records
-    int r = vh_ba_windows(s->ctx, s->h_ss[slots_host[0]].K, W.z, W.x, s->N0, nf - 1, nslots, W.nt, W.K, max_iter, reinterpret_cast<double*>(recs + L.trace),
+    int r = vh_ba_windows(s->ctx, s->h_ss[slots_host[0]].K, W.z, W.x, s->N0, nf - 1, nslots, W.nt, W.K, anchored ? W.fixed : nullptr, max_iter, reinterpret_cast<double*>(recs + L.trace),
                           L.bytes / sizeof(double), reinterpret_cast<int*>(recs + L.iterations), L.bytes / sizeof(int), W.ba, W.ba_stride, stream);
     if (r) return r;
     VH_BIND(s->ctx, stream);
@@ -1098,7 +1224,9 @@ extern "C" VH_API int vh_session_refine_windows(vh_session* s, const vh_refine_w
     vh_refine_window_record L;
     refine_window_record_layout(s->N0, nf, max_iter, with_points, &L);
     char* recs = reinterpret_cast<char*>(recs_dev);
-    auto each_chunk = [&](auto kernel, hipStream_t st) {
+    bool anchored = false;  // as vh_session_refine
+    for (int k = 0; k < nwin; k++) anchored = anchored || s->h_nanchor[wins_host[k].slot] > 0;
+    auto each_chunk = [&](auto kernel, hipStream_t st, auto... more) {
         for (int w0 = 0; w0 < nwin; w0 += SESS_REF_CHUNK) {
             RefWins wn;
             const int cnt = nwin - w0 < SESS_REF_CHUNK ? nwin - w0 : SESS_REF_CHUNK;
@@ -1106,16 +1234,16 @@ extern "C" VH_API int vh_session_refine_windows(vh_session* s, const vh_refine_w
                 wn.slot[k] = wins_host[w0 + (k < cnt ? k : 0)].slot;
                 wn.first[k] = wins_host[w0 + (k < cnt ? k : 0)].first;
             }
-            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, wn, w0, nf, W, L, recs);
+            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, wn, w0, nf, W, L, recs, more...);
         }
     };
     {
         VH_BIND(s->ctx, stream);
-        each_chunk(k_refine_win_pack, bound_.s);
+        each_chunk(k_refine_win_pack, bound_.s, anchored ? (const uint8_t*)s->d_anc_mask : nullptr, anchored ? (const double*)s->d_anc_xyz : nullptr);
         SESS_CHECK();
     }
     // the windows' info = {iterations, converged} and trace go straight into the records
-    int r = vh_ba_windows(s->ctx, s->h_ss[wins_host[0].slot].K, W.z, W.x, s->N0, nf - 1, nwin, W.nt, W.K, max_iter, reinterpret_cast<double*>(recs + L.trace),
+    int r = vh_ba_windows(s->ctx, s->h_ss[wins_host[0].slot].K, W.z, W.x, s->N0, nf - 1, nwin, W.nt, W.K, anchored ? W.fixed : nullptr, max_iter, reinterpret_cast<double*>(recs + L.trace),
                           L.bytes / sizeof(double), reinterpret_cast<int*>(recs + L.iterations), L.bytes / sizeof(int), W.ba, W.ba_stride, stream);
     if (r) return r;
     VH_BIND(s->ctx, stream);

@@ -82,14 +82,16 @@ class TrackerSession:
                                          float(time0), float(frame_no), float(res0), L.stream_ptr()), "vh_session_init")
         self._keep[slot], self._init_keep[slot], self._frame_i[slot] = f0, (pd, p3d, vpd), 0
 
-    def admit(self, entries, settings):
+    def admit(self, entries, settings, anchor=None):
         """THE admission (vidExample.py:105-131 for each clip): frame 0 of every entry computed and installed on the device, on the current stream.
         entries = [(slot, frame0, q, time0, frame_no0[, K]), ...]: frame0 a dense CUDA uint8 [H, W] tensor (the slot takes its size: at most the
         session's), q the clicked plate corners [4, 2], K the clip's intrinsics (absent / None: the session's); settings: a Frame0Settings whose .cap
         is this session's track capacity.  ONE frame-0 batch call for all entries, in the given order (vh_frame0_init_batch3 when their cameras differ
         from the session's), then per entry vh_session_set_camera (only for a slot whose camera changes) and one vh_session_init_dev, fed by the batch's device outputs (count included: nothing is read back).  The session keeps each slot's frame
         and its rows of those outputs alive until the slot is initialised again.  Returns one Admitted per entry: the frame-0 facts a result needs and
-        the stream's state does not hold."""
+        the stream's state does not hold.  anchor="plate": every admitted clip's tracks 0..3 -- the plate corners, whose frame-0 coordinates come from the
+        plate's known size -- become the anchors of its slot (set_anchors as a snapshot, right behind the initialisation)."""
+        assert anchor in (None, "plate"), anchor
         assert settings.cap == self.n0, "the session's track capacity must be 4 + max_corners"
         assert all(e[1].is_cuda and e[1].dtype == self.torch.uint8 and e[1].dim() == 2 and e[1].is_contiguous() for e in entries)
         Ks = [e[5] if len(e) > 5 else None for e in entries]
@@ -108,8 +110,32 @@ class TrackerSession:
             L.check(self.lib.vh_session_init_dev(self.handle, slot, L.dptr(f0), f0.shape[1], L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t0), L.dptr(res0), L.dptr(n0),
                                                  float(time0), float(frame_no0), L.stream_ptr()), "vh_session_init_dev")
             self._keep[slot], self._init_keep[slot], self._frame_i[slot] = f0, rows, 0
+            if anchor == "plate":
+                self.set_anchors(slot, [0, 1, 2, 3])
             out.append(Admitted(tuple(rois[8 * a:8 * a + 4]), tuple(rois[8 * a + 4:8 * a + 8]), R0[0], res0))
         return out
+
+    def set_anchors(self, slot, ids, xyz=None):
+        """The anchored points of the slot's clip (vh_session_set_anchors): track ids whose world coordinates are known, which refine() and
+        refine_windows() hold fixed -- they pin the scale of the adjustment.  xyz [n, 3] in the coordinates of the clip's camera 0, or None: the slot's
+        current p3 rows of those ids, taken on the current stream (take them before the re-triangulation frame, which overwrites p3 of the surviving
+        tracks).  ids = []: no anchors.  Initialising the slot again clears them.  Stream-ordered: nothing is uploaded, nothing waits."""
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+        xp = None
+        if xyz is not None:
+            xyz = np.ascontiguousarray(np.asarray(xyz, np.float64))
+            if xyz.shape != (len(ids), 3):
+                raise ValueError(f"set_anchors: xyz must be [{len(ids)}, 3], got {xyz.shape}")
+            xp = xyz.ctypes.data_as(L.f64p)
+        L.check(self.lib.vh_session_set_anchors(self.handle, int(slot), ids.ctypes.data_as(L.i32p), len(ids), xp, L.stream_ptr()), "vh_session_set_anchors")
+
+    def anchors(self, slot):
+        """(ids int32 [n] ascending, xyz float64 [n, 3]) of the slot's anchors, read back from the device (waits for it: for tests)."""
+        ids, xyz = np.zeros(self.n0, np.int32), np.zeros((self.n0, 3), np.float64)
+        n = self.lib.vh_session_anchors(self.handle, int(slot), ids.ctypes.data_as(L.i32p), xyz.ctypes.data_as(L.f64p))
+        if n < 0:
+            L.check(n, "vh_session_anchors")
+        return ids[:n].copy(), xyz[:n].copy()
 
     def set_frames(self, frames):
         """frames: list of `batch` CUDA uint8 [H,W] tensors, each of its slot's size (kept alive until the next call replaces them); a None entry is a stream that sits the step
@@ -430,19 +456,19 @@ class RefinedClips:
 
 
 def unpack_refine(raw, lay, nf=None):
-    """A vh_refine_record (uint8 array `raw`, offsets `lay`) as a dict: nt, ids [nt], pw [nt, 3], cw [nf, 3], dr [nf], speed [nf] (entry 0 NaN),
-    speed_mean, speed_std, iterations, converged, trace [iterations, 2], f_first, f_last; every array is a copy.  nf: the clip's frames (None: the
+    """A vh_refine_record (uint8 array `raw`, offsets `lay`) as a dict: nt, nfix (anchored points among the nt), ids [nt], pw [nt, 3], cw [nf, 3], dr [nf],
+    speed [nf] (entry 0 NaN), speed_mean, speed_std, iterations, converged, trace [iterations, 2], f_first, f_last; every array is a copy.  nf: the clip's frames (None: the
     rows of cw the record defines)."""
 
     def rd(off, count, dtype):
         return np.frombuffer(raw, dtype, count, off).copy()
 
-    nt, iterations, converged = (int(rd(off, 1, np.int32)[0]) for off in (lay.nt, lay.iterations, lay.converged))
+    nt, iterations, converged, nfix = (int(rd(off, 1, np.int32)[0]) for off in (lay.nt, lay.iterations, lay.converged, lay.nfix))
     cw = rd(lay.cw, 3 * lay.nhist, np.float64).reshape(lay.nhist, 3)
     if nf is None:
         nf = int(np.isfinite(cw[:, 0]).sum())
     one = {k: float(rd(getattr(lay, k), 1, np.float64)[0]) for k in ("speed_mean", "speed_std", "f_first", "f_last")}
-    return dict(nt=nt, ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3), cw=cw[:nf].copy(), dr=rd(lay.dr, nf, np.float64),
+    return dict(nt=nt, nfix=nfix, ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3), cw=cw[:nf].copy(), dr=rd(lay.dr, nf, np.float64),
                 speed=rd(lay.speed, nf, np.float64), iterations=iterations, converged=converged,
                 trace=rd(lay.trace, 2 * iterations, np.float64).reshape(iterations, 2), **one)
 
@@ -474,14 +500,15 @@ class RefinedWindows:
 
 
 def unpack_refine_window(raw, lay):
-    """A vh_refine_window_record (uint8 array `raw`, offsets `lay`) as a dict: slot, first, nt, iterations, converged, cw [nf, 3] (relative to the window's
+    """A vh_refine_window_record (uint8 array `raw`, offsets `lay`) as a dict: slot, first, nt, nfix (anchored points among the nt; 0: solved free),
+    iterations, converged, cw [nf, 3] (relative to the window's
     first camera), dr [nf], speed [nf] (entry 0 NaN), speed_mean, speed_std, f_first, f_last, trace [iterations, 2] and, when the record carries them,
     ids [nt] and pw [nt, 3] (in the window's coordinates: subtract B[first, 3:6] for the session's); every array is a copy."""
 
     def rd(off, count, dtype):
         return np.frombuffer(raw, dtype, count, off).copy()
 
-    head = {k: int(rd(getattr(lay, k), 1, np.int32)[0]) for k in ("slot", "first", "nt", "iterations", "converged")}
+    head = {k: int(rd(getattr(lay, k), 1, np.int32)[0]) for k in ("slot", "first", "nt", "iterations", "converged", "nfix")}
     nf, nt = lay.nf, head["nt"]
     one = {k: float(rd(getattr(lay, k), 1, np.float64)[0]) for k in ("speed_mean", "speed_std", "f_first", "f_last")}
     pts = dict(ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3)) if lay.with_points else {}
@@ -511,8 +538,8 @@ def merge_window_speeds(n, windows):
     """The speed of a clip of n frames from its refined windows (pure NumPy).  windows: dicts with `first`, `speed` [W] (entry 0 NaN: speed[j] is the
     estimate of the step first+j-1 -> first+j), nt, iterations, converged, f_last (unpack_refine_window's).  speed[i] (i >= 1) is the mean of the
     estimates of the windows that cover step i, cover[i] how many did (a step nobody covers: NaN); speed_mean / speed_std are over speed[1:n]
-    (vidExample.py:177).  An average of independent estimates, not one global adjustment.  Also returns the per-window arrays first, nt, iterations,
-    converged, f_last."""
+    (vidExample.py:177).  An average of independent estimates, not one global adjustment.  Also returns the per-window arrays first, nt, nfix (0 where a
+    window has no such field), iterations, converged, f_last."""
     n = int(n)
     tot, cover = np.zeros(n), np.zeros(n, np.int64)
     for w in windows:
@@ -526,6 +553,7 @@ def merge_window_speeds(n, windows):
     speed[hit] = tot[hit] / cover[hit]
     return dict(speed=speed, cover=cover, speed_mean=float(speed[1:].mean()), speed_std=float(speed[1:].std()),
                 first=np.array([w["first"] for w in windows], np.int64), nt=np.array([w["nt"] for w in windows], np.int64),
+                nfix=np.array([w.get("nfix", 0) for w in windows], np.int64),
                 iterations=np.array([w["iterations"] for w in windows], np.int64), converged=np.array([w["converged"] for w in windows], np.int64),
                 f_last=np.array([w["f_last"] for w in windows], np.float64))
 
@@ -537,17 +565,29 @@ def _merged_ba(n, wins, window, stride):
 
 def ba_line(ba):
     """The line a refined clip adds behind the reference's summary (a clip refined in windows: their count and length, the fewest and the most tracks of a
-    window, the largest last rms residual among them)."""
+    window, the largest last rms residual among them).  A refinement that was asked to anchor (ba["anchor"], set by the drivers' refine_anchor) also says
+    how many of its tracks were anchored -- the fewest and the most of a window -- since 0 means the solve ran free; otherwise the line is what it was."""
     if "window" in ba:
+        anchors = f", {np.min(ba['nfix'])}-{np.max(ba['nfix'])} anchors" if "anchor" in ba else ""
         return (f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({len(ba['first'])} windows of {ba['window']} frames, "
-                f"{ba['nt'].min()}-{ba['nt'].max()} tracks, f = {np.nanmax(ba['f_last']) if np.isfinite(ba['f_last']).any() else np.nan:.3f} pixels)")
-    return f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({ba['nt']:g} tracks, f = {ba['f_last']:.3f} pixels)"
+                f"{ba['nt'].min()}-{ba['nt'].max()} tracks{anchors}, f = {np.nanmax(ba['f_last']) if np.isfinite(ba['f_last']).any() else np.nan:.3f} pixels)")
+    anchors = f", {ba['nfix']} anchors" if "anchor" in ba else ""
+    return f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({ba['nt']:g} tracks{anchors}, f = {ba['f_last']:.3f} pixels)"
 
 
-def _check_refine(refine, refine_window=None, refine_stride=None):
+def _tag_anchor(ba, refine_anchor):
+    """A clip's refinement (either form) marked with what it was asked to anchor; None: untouched."""
+    return ba if refine_anchor is None or ba is None else dict(ba, anchor=refine_anchor)
+
+
+def _check_refine(refine, refine_window=None, refine_stride=None, refine_anchor=None):
     """-> (refine is on, the window length or None, the stride or None); raises ValueError by name before anything is queued."""
     if refine not in (None, "ba"):
         raise ValueError(f"refine must be None or 'ba', got {refine!r}")
+    if refine_anchor not in (None, "plate"):
+        raise ValueError(f"refine_anchor must be None or 'plate', got {refine_anchor!r}")
+    if refine_anchor is not None and refine != "ba":
+        raise ValueError("refine_anchor needs refine='ba'")
     if refine_window is None:
         if refine_stride is not None:
             raise ValueError("refine_stride needs refine_window")
@@ -826,7 +866,7 @@ def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=
 def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01,
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
                  out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
-                 refine_window=None, refine_stride=None):
+                 refine_window=None, refine_stride=None, refine_anchor=None):
     """The packaged counterpart of vidExample.py:52-178 (minus video decode and plots) on one clip.
 
     frames  sequence of n uint8 [H, W] gray frames (numpy arrays or CUDA tensors): what `cv2.cvtColor(cap.read(), BGR2GRAY)` / `cv2.imread(.., 0)` hands
@@ -850,7 +890,12 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             W - 1), all in one TrackerSession.refine_windows request, each on the tracks alive through it; "ba" is then merge_window_speeds' dict
             (speed, cover, speed_mean, speed_std and the per-window first, nt, iterations, converged, f_last) plus `window` and `stride`.  A clip
             shorter than W is refined whole.  The windows are independent solves and the merged speed an average of their estimates, not one global
-            adjustment; each window's scale is still held only by the damping.
+            adjustment; without refine_anchor each window's scale is still held only by the damping.
+    refine_anchor   None (default), or "plate" (needs refine="ba"): the clip's tracks 0..3 -- the plate corners, whose frame-0 world coordinates come from
+            the plate's known size -- are held fixed in the adjustment (TrackerSession.set_anchors right after frame 0), which pins its scale to the
+            plate.  "ba" gains nothing but `anchor`; its `nfix` says how many anchors were alive (per window in the windowed form: 0 = that window ran
+            free), and the BA line says so too.  What it does not do: a window with first > 0 places its anchors by the tracker's own B[first, 3:6],
+            windows stay separate solves, and the plate's frame-0 pose error is inherited.
     out     line sink (default print); clock: time source for the procTime column / fps line (default time.perf_counter).
 
     Prints the reference's header, one 9-column row per frame (vidExample.py:165) and the `Speed = ... +/- ... km/h / Res = ...` summary (:177-178).
@@ -858,7 +903,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     import time as _time
 
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
-    refine, win, stride = _check_refine(refine, refine_window, refine_stride)
+    refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     if route != "session":
         raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
     clock = clock or _time.perf_counter
@@ -877,7 +922,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     H, W = dev[0].shape
     ses = _SessionSet(1, 1, max_corners).create(K, W, H, settings, n, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback,
                                                  fallback_params=fallback_params)[0]
-    f0 = ses.admit([(0, dev[0], q, times[0], frame_numbers[0])], settings)[0]
+    f0 = ses.admit([(0, dev[0], q, times[0], frame_numbers[0])], settings, anchor=refine_anchor)[0]
     view = ses.view(0)
     proc = np.zeros(n)
 
@@ -900,6 +945,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
         ba = _merged_ba(n, ses.refine_windows([(0, f) for f in refine_window_starts(n, win, stride)], win).result(), win, stride)
     else:
         ba = ses.refine([0]).result()[0] if refine else None
+    ba = _tag_anchor(ba, refine_anchor)
     st, recoveries, f0 = ses.state(0), ses.recoveries()[0], f0.host()
     res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None, ba)
     for line in res["lines"][-(3 if refine else 2) if live else 2:]:  # (not live: the whole clip ran first, and every row carries the mean time per frame)
@@ -968,7 +1014,7 @@ class _SessionSet:
 
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
                   msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
-                  refine_window=None, refine_stride=None):
+                  refine_window=None, refine_stride=None, refine_anchor=None):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name, K]) of ONE length -- the
     frame size and the intrinsics are each clip's own ("K": that clip's camera, default the K argument); the sessions are created at the elementwise
     maximum of the sizes and a frame step is sized for it, so clips of one camera type batch best.  One length stays required: a step advances every
@@ -980,10 +1026,11 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     run_sequence (the failed streams of a session share one vh_match_affine_batch call per step).  Returns one result dict per clip (clip_result's;
     `lines` = that clip's table and summary, printed through `out` if given), each equal to what run_sequence returns for the clip alone.  refine="ba": as in
     run_sequence; all the clips of a session are refined by ONE TrackerSession.refine after the last frame -- with refine_window=W (and clips of at least
-    W frames) all the windows of all the clips of a session by ONE TrackerSession.refine_windows request."""
+    W frames) all the windows of all the clips of a session by ONE TrackerSession.refine_windows request.  refine_anchor="plate": as in run_sequence,
+    for every clip."""
     import time as _time
 
-    refine, win, stride = _check_refine(refine, refine_window, refine_stride)
+    refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
     nclip = len(clips)
@@ -1006,7 +1053,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
         with torch.cuda.stream(hs):
             f0_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
             f0_events[-1][0].record()
-            f0 += ses.admit([(j, dev[b][0], clips[b]["q"], times[b, 0], fnos[b, 0], clips[b].get("K")) for j, b in enumerate(mem)], settings)
+            f0 += ses.admit([(j, dev[b][0], clips[b]["q"], times[b, 0], fnos[b, 0], clips[b].get("K")) for j, b in enumerate(mem)], settings, anchor=refine_anchor)
             f0_events[-1][1].record()
     t_loop = _time.perf_counter()
     for i in range(1, n):
@@ -1036,7 +1083,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
         for j, b in enumerate(mem):
             meta = dict(n=n, name=clips[b].get("name", f"clip {b}"), frame_numbers=clips[b].get("frame_numbers", list(range(n))))
             results.append(clip_result(ses.state(j), meta, f0[b].host(), seconds, step_seconds, len(sess), ses.recoveries()[j],
-                                       ba=refined[g][j] if refine else None))
+                                       ba=_tag_anchor(refined[g][j], refine_anchor) if refine else None))
             if out is not None:
                 for ln in results[-1]["lines"]:
                     out(ln)
@@ -1103,7 +1150,7 @@ def queue_plan(lengths, streams, sessions=1):
 
 def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, max_size=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
               harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=None, use_harris=True, min_distance=0.0, fallback=False,
-              fallback_params=None, refine=None, refine_window=None, refine_stride=None):
+              fallback_params=None, refine=None, refine_window=None, refine_stride=None, refine_anchor=None):
     """A queue of clips of ANY length on `streams` resident streams: what run_sequences is for clips of one length.  `clips` = any iterable of
     dict(frames, q, times[, frame_numbers, name, K]), each of >= 2 frames and with its own frame size and intrinsics ("K": default the K argument); it is consumed lazily -- a clip is pulled when a slot is free
     for it and its frames go up then, so at most `streams` clips are resident -- and may hold more clips than fit on the device at once.
@@ -1124,10 +1171,11 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
     refine="ba": as in run_sequence.  The clips of a session that finish at the same step are refined on the session's stream right behind their
     exports, one TrackerSession.refine per clip length among them; the records travel with the exports and the slots are free at the next step as ever.
     refine_window=W (refine_stride: as in run_sequence): the clips of at least W frames that finish at a step go through ONE TrackerSession.refine_windows
-    request of their session, whatever their lengths (their "ba" is the merged dict); the per-length calls remain for clips shorter than W."""
+    request of their session, whatever their lengths (their "ba" is the merged dict); the per-length calls remain for clips shorter than W.
+    refine_anchor="plate": as in run_sequence, for every clip (a slot's anchors are set at its clip's admission and cleared by the next one)."""
     import time as _time
 
-    refine, win, stride = _check_refine(refine, refine_window, refine_stride)
+    refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
     if max_frames is None:
@@ -1179,7 +1227,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
         handle, index, clip, f0, t0, ba = entry[2]
         st = handle.result()
         if ba is not None:
-            ba = ba[1](ba[0].result())
+            ba = _tag_anchor(ba[1](ba[0].result()), refine_anchor)
         x = entry[1].numpy().copy()
         seconds = _time.perf_counter() - t0  # the clip's time in the queue: every row carries the mean over its frame steps
         res = results[index] = clip_result(st, clip, f0._replace(R0=x[0:9], res0=x[9]), seconds, seconds / (clip["n"] - 1), G, handle.recoveries, ba=ba)
@@ -1227,7 +1275,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                     ev0 = torch.cuda.Event(enable_timing=True)
                     ev1 = torch.cuda.Event(enable_timing=True)
                     ev0.record()
-                    f0s = ses.admit([(j, c["dev"][0], c["q"], c["times"][0], c["fnos"][0], c["K"]) for j, c in adm], settings)
+                    f0s = ses.admit([(j, c["dev"][0], c["q"], c["times"][0], c["fnos"][0], c["K"]) for j, c in adm], settings, anchor=refine_anchor)
                     for (j, _), f0 in zip(adm, f0s):
                         held[g][j] = (f0, _time.perf_counter())
                     ev1.record()
@@ -1317,6 +1365,7 @@ def main(argv=None):
     ap.add_argument("--refine", choices=["ba"], default=None, help="bundle-adjust the finished clip on the device and print the refined speed (vidExample.py:157)")
     ap.add_argument("--refine-window", type=int, default=None, metavar="W", help="with --refine ba: refine the clip in windows of W frames (2 .. 256); clips of any length")
     ap.add_argument("--refine-stride", type=int, default=None, metavar="S", help="frames between the starts of consecutive windows (1 .. W-1; default W-1)")
+    ap.add_argument("--refine-anchor", choices=["plate"], default=None, help="with --refine ba: hold the four plate corners fixed in the adjustment (a metric scale from the plate)")
     ap.add_argument("--shi-tomasi", action="store_true", help="frame-0 corners by the minimum-eigenvalue detector instead of Harris")
     a = ap.parse_args(argv)
     d = np.load(a.clip)
@@ -1324,7 +1373,7 @@ def main(argv=None):
     border = tuple(a.border) if a.border else ((700, 500) if fr.shape[2] >= 1900 else (180, 140))
     run_sequence(fr, d[f"{a.seq}_q"], d[f"{a.seq}_K"], times=d[f"{a.seq}_times"], roi_border=border, msv_frame=a.msv_frame,
                  name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback, refine=a.refine,
-                 refine_window=a.refine_window, refine_stride=a.refine_stride)
+                 refine_window=a.refine_window, refine_stride=a.refine_stride, refine_anchor=a.refine_anchor)
 
 
 if __name__ == "__main__":
