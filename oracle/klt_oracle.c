@@ -13,7 +13,8 @@
  * the Newton iteration with its two stop rules, remap's 5-bit fixed-point bilinear, nearest resize.
  *
  * PARITY UNPINNED: the reference holds no KLT test, golden vector or fixture and cv2 cannot run here, so this
- * restatement is pinned only by analytic-flow ground truth (tests/test_oracle_klt.py) and by self-consistency.
+ * restatement is pinned by analytic-flow ground truth (tests/test_oracle_klt.py) and, bit for bit, by the exact NumPy models of
+ * tests/image_ref.py and tests/lk_ref.py (tests/test_klt_model_cpu.py: image stages, pyramidal LK, KLTregional, KLTmain's stages), not by OpenCV itself.
  * Deliberate, documented choices where OpenCV is build/SIMD dependent or not reproducible:
  *   - window sums (A11,A12,A22,b1,b2,err) are accumulated EXACTLY in int64 and converted once to float
  *     (OpenCV: float or int32-lane accumulation depending on the SIMD path) -> order independent;

@@ -1,10 +1,19 @@
-"""Exact-integer NumPy model of the single-level Lucas-Kanade solve (cv2.calcOpticalFlowPyrLK with maxLevel = 0), and
-the worst-case-contrast scenes and track sets its tests share (tests/test_lk_ref_cpu.py, tests/test_gpu_lk_extremes.py).
+"""Exact-integer NumPy model of Lucas-Kanade tracking as the reference uses it: one pyramid level (lk_level), the
+pyramidal descent of cv2.calcOpticalFlowPyrLK (pyr_lk), the forward-backward gate of cv2calcOpticalFlowPyrLK (lk_fb, utils/KLT.py:37-51) and
+KLTregional (klt_regional, utils/KLT.py:55-95) on top of the image stages of tests/image_ref.py; and the worst-case-contrast scenes and track sets
+that the single-level tests share (tests/test_lk_ref_cpu.py, tests/test_gpu_lk_extremes.py).  tests/test_klt_model_cpu.py holds the oracle to the whole
+call, tests/test_gpu_klt_model.py the kernels.
 
 The oracle (oracle/klt_oracle.c) keeps every window sum in int64 and the HIP kernels (velocity_amd/csrc/vh_lk.hip) reproduce it bit for bit with int32
 per-lane partials, 16-bit halves and 24-bit multiply-adds, each on the argument that 8-bit images cannot produce larger operands.  This module restates
 the level independently of both -- all tracks at once, whole windows as arrays -- and reports the largest window sums it met, so a test can assert how
 close to those operand limits its scenes really come.
+
+The descent.  A level's positions are the full-resolution ones times float32(1 / 2^level), a power of two, so the scaling is exact.  The top level
+starts at the scaled point, every lower one at twice the level above's result (exact again).  Status and err belong to level 0 alone: an upper level
+that cannot start (window origin further out than a window) or that fails the min-eigenvalue test hands its guess down unchanged and says nothing.
+The backward pass of lk_fb starts from the forward result; the error sqrt(dx dx + dy dy) and its comparison with the threshold are float32, and a NaN
+compares false.  klt_regional subtracts and adds the ROI origin and maps back through T in float32, (ax T0 + ay T2) + T4, one rounding per operation.
 
 Number formats.  Pixels, gradients, bilinear samples and the products of two samples are int32 arrays, and none of them can wrap: the weights are
 non-negative and add up to 2^14, so a weighted sample is at most 4080 * 2^14 + 2^13 < 2^27, and a product of two samples is at most
@@ -14,6 +23,8 @@ eps^2 test is float64.  int64 -> float32 conversions round to nearest even, as t
 import functools
 
 import numpy as np
+
+import image_ref as IM
 
 F32 = np.float32
 W_BITS = 14
@@ -30,7 +41,7 @@ W, H = 192, 160  # every scene below
 # ---------------------------------------------------------------------------------------------------------------------
 def scharr(img):
     """(Ix, Iy) int32 of a uint8 image: smoothing [3 10 3], difference [-1 0 1], no normalisation, REFLECT_101 support."""
-    p = np.pad(img.astype(np.int32), 1, mode="reflect")  # numpy's 'reflect' does not repeat the edge sample: REFLECT_101
+    p = IM.pad101(img.astype(np.int32), 1)  # by index, so a dimension of 1 works too
     sm = 3 * (p[:-2, :] + p[2:, :]) + 10 * p[1:-1, :]  # vertical smoothing, all columns
     dv = p[2:, :] - p[:-2, :]  # vertical difference, all columns
     return sm[:, 2:] - sm[:, :-2], 3 * (dv[:, 2:] + dv[:, :-2]) + 10 * dv[:, 1:-1]
@@ -83,35 +94,48 @@ def _f32_of(s):
     return s.astype(F32) * FLT_SCALE
 
 
-def lk_level0(prev, nxt, pts, win, max_count, eps):
-    """(next (n, 2) float32, status (n,) bool, err (n,) float32, peaks) of calcOpticalFlowPyrLK(prev, nxt, pts, winSize=(win, win), maxLevel=0,
-    criteria=(COUNT | EPS, max_count, eps)).  peaks: the largest |A11|, |A12|, |A22|, |b1|, |b2| integer window sums over every track and
-    iteration, the largest single |Ix|, |Iy| and |diff| sample, and the most negative b1 and b2 sums (b1_min, b2_min), as Python ints."""
+def _criteria(max_count, eps):
+    """OpenCV's clamp of the termination criteria -> (max_count, eps^2)."""
+    return min(max(int(max_count), 0), 100), min(max(float(eps), 0.0), 10.0) ** 2
+
+
+def _new_peaks():
+    return dict(A11=0, A12=0, A22=0, b1=0, b2=0, Ix=0, Iy=0, diff=0, b1_min=0, b2_min=0)
+
+
+def lk_level(prev, nxt, pts, guess, level, top_level, win, max_count, eps2, status, err, peaks=None):
+    """One level of calcOpticalFlowPyrLK for every track: prev / nxt are that level's images, pts (n, 2) float32 the FULL-resolution points, guess
+    (n, 2) float32 the level above's result (ignored on the top level), max_count and eps2 already clamped (_criteria).  Returns this level's
+    positions (n, 2) float32.  status (n,) bool and err (n,) float32 are updated in place, and only when level == 0; a track that cannot start or
+    fails the min-eigenvalue test on an upper level keeps its starting guess.  peaks: a _new_peaks() dict to update (see lk_level0), or None."""
     assert prev.shape == nxt.shape and prev.dtype == np.uint8 and nxt.dtype == np.uint8 and 3 <= win <= 128
     h, w = prev.shape
     pts = np.ascontiguousarray(pts, F32).reshape(-1, 2)
-    n = len(pts)
-    max_count = min(max(int(max_count), 0), 100)
-    eps2 = min(max(float(eps), 0.0), 10.0) ** 2
+    base = level == 0
+    peaks = _new_peaks() if peaks is None else peaks
 
     gx, gy = scharr(prev)
-    pI = np.pad(prev.astype(np.int32), win, mode="reflect")
-    pJ = np.pad(nxt.astype(np.int32), win, mode="reflect")
+    pI = IM.pad101(prev.astype(np.int32), win)
+    pJ = IM.pad101(nxt.astype(np.int32), win)
     pGx, pGy = np.pad(gx, win), np.pad(gy, win)  # gradients: zero outside the image
 
     half = F32((win - 1) * F32(0.5))
-    nxt_pt = pts.copy()
-    status = np.ones(n, bool)
-    err = np.zeros(n, F32)
-    peaks = dict(A11=0, A12=0, A22=0, b1=0, b2=0, Ix=0, Iy=0, diff=0, b1_min=0, b2_min=0)
+    lpts = pts * F32(1.0 / (1 << level))
+    nxt_pt = lpts.copy() if level == top_level else np.ascontiguousarray(guess, F32).reshape(-1, 2) * F32(2.0)
 
     def peak(name, s):
         if s.size:
             peaks[name] = max(peaks[name], int(np.abs(s).max()))
 
+    def drop(idx):
+        if base:
+            status[idx] = False
+
     # template: the window of prev at the track, its gradients, the structure tensor
-    ok, ipx, ipy, a, b = _origin(pts[:, 0] - half, pts[:, 1] - half, win, w, h)
-    status &= ok
+    ok, ipx, ipy, a, b = _origin(lpts[:, 0] - half, lpts[:, 1] - half, win, w, h)
+    drop(~ok)
+    if base:
+        err[~ok] = F32(0.0)
     live = np.flatnonzero(ok)
     Iw, Ix, Iy = _sample((pI, pGx, pGy), ipx[live], ipy[live], a[live], b[live], win, (W_BITS - 5, W_BITS, W_BITS))
     s11, s12, s22 = _wsum(Ix * Ix), _wsum(Ix * Iy), _wsum(Iy * Iy)
@@ -120,7 +144,7 @@ def lk_level0(prev, nxt, pts, win, max_count, eps):
     D = A11 * A22 - A12 * A12
     min_eig = (A22 + A11 - np.sqrt((A11 - A22) * (A11 - A22) + F32(4.0) * A12 * A12)) / F32(2 * win * win)
     good = ~((min_eig < MIN_EIG_THR) | (D < FLT_EPSILON))
-    status[live[~good]] = False
+    drop(live[~good])
     live, Iw, Ix, Iy, A11, A12, A22 = live[good], Iw[good], Ix[good], Iy[good], A11[good], A12[good], A22[good]
     D = F32(1.0) / D[good]
 
@@ -131,7 +155,7 @@ def lk_level0(prev, nxt, pts, win, max_count, eps):
     cur = np.arange(m)
     for j in range(max_count):
         ok, inx, iny, a, b = _origin(nx[cur], ny[cur], win, w, h)
-        status[live[cur[~ok]]] = False
+        drop(live[cur[~ok]])
         cur, inx, iny, a, b = cur[ok], inx[ok], iny[ok], a[ok], b[ok]
         if not len(cur):
             break
@@ -154,6 +178,9 @@ def lk_level0(prev, nxt, pts, win, max_count, eps):
         pdx[cur], pdy[cur] = dx, dy
         cur = cur[~(small | osc)]
 
+    if not base:
+        return nxt_pt
+
     # err of the tracks still alive: mean |diff| of the final window, in intensity units
     fin = np.flatnonzero(status[live])
     ok, inx, iny, a, b = _origin(nxt_pt[live[fin], 0] - half, nxt_pt[live[fin], 1] - half, win, w, h)
@@ -162,7 +189,70 @@ def lk_level0(prev, nxt, pts, win, max_count, eps):
     if len(fin):
         diff = _sample((pJ,), inx, iny, a, b, win, (W_BITS - 5,))[0] - Iw[fin]
         err[live[fin]] = _wsum(np.abs(diff)).astype(F32) * (F32(1.0) / F32(32 * win * win))
+    return nxt_pt
+
+
+def lk_level0(prev, nxt, pts, win, max_count, eps):
+    """(next (n, 2) float32, status (n,) bool, err (n,) float32, peaks) of calcOpticalFlowPyrLK(prev, nxt, pts, winSize=(win, win), maxLevel=0,
+    criteria=(COUNT | EPS, max_count, eps)): the one-level call of lk_level.  peaks: the largest |A11|, |A12|, |A22|, |b1|, |b2| integer window sums
+    over every track and iteration, the largest single |Ix|, |Iy| and |diff| sample, and the most negative b1 and b2 sums (b1_min, b2_min), as
+    Python ints."""
+    pts = np.ascontiguousarray(pts, F32).reshape(-1, 2)
+    max_count, eps2 = _criteria(max_count, eps)
+    status, err, peaks = np.ones(len(pts), bool), np.zeros(len(pts), F32), _new_peaks()
+    nxt_pt = lk_level(prev, nxt, pts, None, 0, 0, win, max_count, eps2, status, err, peaks)
     return nxt_pt, status, err, peaks
+
+
+def pyr_lk(prev, nxt, pts, win, max_level, max_count, eps):
+    """(next (n, 2) float32, status (n,) bool, err (n,) float32) of calcOpticalFlowPyrLK(prev, nxt, pts, winSize=(win, win), maxLevel=max_level,
+    criteria=(COUNT | EPS, max_count, eps)): the pyramids of image_ref.pyramid, lk_level from the top level down."""
+    pts = np.ascontiguousarray(pts, F32).reshape(-1, 2)
+    max_count, eps2 = _criteria(max_count, eps)
+    pI, pJ = IM.pyramid(prev, win, max_level), IM.pyramid(nxt, win, max_level)
+    top = len(pI) - 1
+    status, err = np.ones(len(pts), bool), np.zeros(len(pts), F32)
+    guess = np.zeros_like(pts)
+    for level in range(top, -1, -1):
+        guess = lk_level(pI[level], pJ[level], pts, guess, level, top, win, max_count, eps2, status, err)
+    return guess, status, err
+
+
+def lk_fb(im1, im2, p1, fbt=None, win=15, max_level=4, max_count=10, eps=0.1):
+    """cv2calcOpticalFlowPyrLK (utils/KLT.py:37-51) -> (p2, v, err, fbe): forward pyr_lk; with a threshold (fbt neither None nor negative) a backward
+    pyr_lk from p2, fbe = |p1 - p1'| in float32 and v = v & v2 & (fbe < fbt), where a NaN compares false.  Without one fbe is zero."""
+    p1 = np.ascontiguousarray(p1, F32).reshape(-1, 2)
+    p2, v, err = pyr_lk(im1, im2, p1, win, max_level, max_count, eps)
+    fbe = np.zeros(len(p1), F32)
+    if fbt is not None and F32(fbt) >= 0:
+        p1b, v2, _ = pyr_lk(im2, im1, p2, win, max_level, max_count, eps)
+        with np.errstate(over="ignore", invalid="ignore"):
+            dx, dy = p1[:, 0] - p1b[:, 0], p1[:, 1] - p1b[:, 1]
+            fbe = np.sqrt(dx * dx + dy * dy)
+            v = v & v2 & (fbe < F32(fbt))
+    return p2, v, err, fbe
+
+
+def klt_regional(im0, im, p0, T, lk, fbt=1.0, translate=False):
+    """KLTregional (utils/KLT.py:55-95) -> (p (n, 2) float32, v (n,) bool, roi (x0, x1, y0, y1), warped): the ROI is boundingRect(p0, border 50);
+    `im` is cropped at the integer shift int(T[4]), int(T[5]) (truncated towards zero; translate) or remapped through the float32 T (3 x 2) over it;
+    lk_fb tracks p0 - origin from im0's ROI into that; the origin is added back and the result shifted or mapped through T.  lk: dict(win,
+    max_level, max_count, eps).  At least one point."""
+    p0 = np.ascontiguousarray(p0, F32).reshape(-1, 2)
+    T = np.asarray(T, F32).reshape(6)
+    roi = IM.bounding_rect(p0, im0.shape, (50, 50))
+    x0, x1, y0, y1 = roi
+    org = np.array([x0, y0], F32)
+    dx, dy = int(T[4]), int(T[5])
+    warped = IM.crop_shift(im, roi, dx, dy) if translate else IM.remap_affine(im, T, roi)
+    pa, v, _, _ = lk_fb(np.ascontiguousarray(im0[y0:y1, x0:x1]), warped, p0 - org, fbt, **lk)
+    with np.errstate(over="ignore", invalid="ignore"):
+        a = pa + org
+        if translate:
+            p = a + np.array([dx, dy], F32)
+        else:
+            p = np.stack([(a[:, 0] * T[0] + a[:, 1] * T[2]) + T[4], (a[:, 0] * T[1] + a[:, 1] * T[3]) + T[5]], 1)
+    return p.astype(F32), v, roi, warped
 
 
 # ---------------------------------------------------------------------------------------------------------------------
