@@ -239,6 +239,48 @@ def test_refusals_queue_nothing():
         assert (a["slot"], a["first"], a["nt"]) == (b["slot"], b["first"], b["nt"]) and np.array_equal(a["cw"], b["cw"]) and np.array_equal(a["pw"], b["pw"])
 
 
+def test_a_request_past_the_launch_chunk_of_one_call():
+    """The library launches pack and unpack 256 windows at a time (their table travels in the kernel arguments).  30 slots -- the three scenes, ten times
+    -- at their last frame hold 30 x 9 = 270 distinct windows of W4 frames: ONE vh_session_refine_windows call of two launches, the second of 14 windows
+    behind 242 padding entries.  The windows are given start-major, so entries 255 and 256 sit in two slots of two cameras."""
+    import torch
+
+    from velocity_amd.driver import TrackerSession
+
+    scenes = _scenes3()
+    B, last = 30, NHIST - 1
+    ses = TrackerSession(scenes[0][4], 320, 240, N0, nhist=NHIST, batch=B, msv_frame=5)
+    for b in range(B):
+        frames, p, p3, vp, Kb = scenes[b % 3]
+        ses.init_stream(b, frames[0], p, p3, vp, T0, time0=10.0 * b, K=Kb)
+    dev = [[torch.from_numpy(f).cuda() for f in sc[0]] for sc in scenes]
+    for k in range(1, last + 1):
+        ses.step([dev[b % 3][k] for b in range(B)], time_s=[np.float32(10.0 * b + k / (25.0 + b % 3)) for b in range(B)], frame_no=[k] * B)
+    wins = [(b, f) for f in range(last - W4 + 2) for b in range(B)]
+    assert len(wins) == len(set(wins)) == 270 and wins[255] == (15, 8) and wins[256] == (16, 8)
+    one = int(ses.lib.vh_session_refine_windows_workspace(ses.handle, 1, W4))
+    h = ses.refine_windows(wins, W4, with_points=True, workspace_budget=2 * len(wins) * one)
+    assert h.chunk == len(wins) >= 257  # Python did not split the request
+    got = h.result()
+    probe = [0, 254, 255, 256, 257, len(wins) - 1]
+    for k in probe:
+        assert (got[k]["slot"], got[k]["first"]) == wins[k], k
+    assert all((g["slot"], g["first"]) == w for g, w in zip(got, wins))
+    small = ses.refine_windows([wins[k] for k in probe], W4, with_points=True)
+    assert small.chunk == len(probe) < 256
+    for k, s in zip(probe, small.result()):
+        g = got[k]
+        for key in ("slot", "first", "nt", "nfix", "iterations", "converged"):
+            assert g[key] == s[key], (k, key)
+        assert g["nt"] > 0 and g["iterations"] > 0, k
+        for key in ("ids", "cw", "pw", "speed"):
+            assert np.array_equal(g[key], s[key], equal_nan=True), (k, key)
+        np.testing.assert_allclose(g["trace"], s["trace"], rtol=1e-12)  # (sums of squares accumulated with atomics)
+    for k in (255, 256):
+        b, f = wins[k]
+        _window_equals_model(got[k], scenes[b % 3][4], ses.state(b), f, W4, f"entry {k}: window ({b}, {f})")
+
+
 # ---- the drivers ---------------------------------------------------------------------------------------------------------------------------------
 def _plate_quad(K, X, Y, Z):
     from velocity_amd.common import worldPointsLicensePlate

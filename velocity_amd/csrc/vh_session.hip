@@ -821,23 +821,36 @@ extern "C" VH_API int vh_session_anchors(vh_session* s, int slot, int* ids_host,
     return n;
 }
 
-// ---- bundle adjustment of finished clips (vh_session_refine; vidExample.py:157, NLS.py:186-250) ----------------------------------------------------------
-// pack: the slot's surviving tracks, its history, world points, per-frame translations and camera -> window w of one vh_nls_batch_windows problem laid out
-// for N0 tracks; unpack: the refined state and the speed derived from it -> record w.  The session is only read.
-#define SESS_REF_CHUNK 256  // slots per pack / unpack launch: their numbers travel in the kernel arguments (no upload, no host wait)
-struct RefSlots {
+// ---- bundle adjustment of frame windows of the slots' clips (vidExample.py:157, NLS.py:186-250) -----------------------------------------------------------
+// ONE request path behind both entries: window (slot, first) = frames [first, first + nf) of the slot's clip; vh_session_refine asks for the window
+// first = 0 of clips that have just ended, vh_session_refine_windows for any.  pack: the window's tracks, their history, world points, per-frame
+// translations and camera -> window w of one vh_nls_batch_windows problem laid out for N0 tracks; unpack: the refined state and the speed derived from it
+// -> record w.  The session is only read.
+#define SESS_REF_CHUNK 256  // windows per pack / unpack launch: they travel in the kernel arguments (no upload, no host wait)
+struct RefReq {  // the windows of one launch (a whole clip: first = 0)
     int slot[SESS_REF_CHUNK];
+    int first[SESS_REF_CHUNK];
 };
 struct RefWs {  // the scratch of one call, carved by refine_ws_layout
-    double* z;   // [nslots][2][nf][N0]
-    double* x;   // [nslots][3 N0 + 6 nc]
-    double* K;   // [nslots][9]
-    int* nt;     // [nslots]
-    int* ids;    // [nslots][N0] the tracks of each window, ascending (vh_session_refine_windows only: a whole clip's are the slot's survivors)
-    char* ba;    // [nslots] BA workspaces, ba_stride bytes apart
-    uint8_t* fixed;  // [nslots][N0] anchored rows of each window (read by the solve only when a slot of the request has anchors)
+    double* z;   // [nwin][2][nf][N0]
+    double* x;   // [nwin][3 N0 + 6 nc]
+    double* K;   // [nwin][9]
+    int* nt;     // [nwin]
+    int* ids;    // [nwin][N0] the tracks of each window, ascending (null for vh_session_refine: a whole clip's are the slot's survivors)
+    char* ba;    // [nwin] BA workspaces, ba_stride bytes apart
+    uint8_t* fixed;  // [nwin][N0] anchored rows of each window (read by the solve only when a slot of the request has anchors)
     size_t z_stride, x_stride, ba_stride;
 };
+// a record of either public layout as the kernels see it: byte offsets taken from vh_refine_record or vh_refine_window_record (refine_view)
+struct RefView {
+    size_t bytes, head, nt, info, nfix, ids, pw, cw, dr, speed, speed_mean, speed_std, f_first, f_last, trace;
+    int rows;         // of cw, dr and speed: nhist | nf
+    int head_words;   // int32 words from `head` on: 4 {nt, iterations, converged, nfix} | 6 {slot, first, nt, iterations, converged, nfix}
+    int max_iter;
+    int with_points;  // ids and pw are in the record
+};
+// (table + workspace + view + the other arguments of the pack kernel: 2304 bytes of the 4 KB a launch may carry)
+static_assert(sizeof(RefReq) + sizeof(RefWs) + sizeof(RefView) + 5 * sizeof(void*) == 2304, "the refinement request travels in the kernel arguments");
 
 static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_record* L)
 {
@@ -853,6 +866,34 @@ static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_reco
     L->trace = put(sizeof(double) * 2 * (size_t)max_iter);
     L->bytes = off;
     L->n0 = N0; L->nhist = nhist; L->max_iter = max_iter;
+}
+
+static void refine_window_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_window_record* L)
+{
+    size_t off = 0;
+    auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
+    L->slot = put(6 * sizeof(int)); L->first = L->slot + 4; L->nt = L->slot + 8;
+    L->iterations = L->slot + 12; L->converged = L->slot + 16;  // (iterations, converged: the int[2] info record of the window's solve)
+    L->nfix = L->slot + 20;                                      // (the header's sixth word)
+    L->cw = put(sizeof(double) * 3 * (size_t)nf);
+    L->dr = put(sizeof(double) * (size_t)nf); L->speed = put(sizeof(double) * (size_t)nf);
+    L->speed_mean = put(sizeof(double)); L->speed_std = put(sizeof(double)); L->f_first = put(sizeof(double)); L->f_last = put(sizeof(double));
+    L->trace = put(sizeof(double) * 2 * (size_t)max_iter);
+    L->ids = with_points ? put(sizeof(int) * (size_t)N0) : 0;
+    L->pw = with_points ? put(sizeof(double) * 3 * (size_t)N0) : 0;
+    L->bytes = off;
+    L->n0 = N0; L->nf = nf; L->max_iter = max_iter; L->with_points = with_points ? 1 : 0;
+}
+
+// the kernels' view of a public layout (the two functions above stay the one source of every offset): head = the record's first header word
+template <class Layout>
+static RefView refine_view(const Layout& L, size_t head, int rows, int with_points)
+{
+    RefView V;
+    V.bytes = L.bytes; V.head = head; V.nt = L.nt; V.info = L.iterations; V.nfix = L.nfix; V.ids = L.ids; V.pw = L.pw; V.cw = L.cw; V.dr = L.dr;
+    V.speed = L.speed; V.speed_mean = L.speed_mean; V.speed_std = L.speed_std; V.f_first = L.f_first; V.f_last = L.f_last; V.trace = L.trace;
+    V.rows = rows; V.head_words = (int)((L.nfix - head) / sizeof(int)) + 1; V.max_iter = L.max_iter; V.with_points = with_points;
+    return V;
 }
 
 static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* base, RefWs* W, bool with_ids = false)
@@ -981,118 +1022,155 @@ __device__ __forceinline__ void refine_unpack_window(const SessStream& S, const 
 }
 
 // anc_mask / anc_xyz: the session's anchor tables over all slots, null when no slot of the request has anchors
-__global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, RefSlots sl, int w0, int nf, RefWs W, vh_refine_record L, char* recs,
+// pack.  SELECT: the window's tracks are the ids whose history row 4 is finite in EVERY frame of the window (NLS.py:190 on the slice) -- not the slot's
+// current survivors: a track that died after the window belongs to it.  256 ids at a time read row 4 of the frame-major history (coalesced over
+// tracks), a ballot + the four wavefronts' counts give each kept id its place, so the ids come out ascending (into W.ids).  !SELECT (first = 0 of a
+// clip that has just had its last frame): the slot's survivors ARE those tracks -- no pass, no scratch.  One workgroup per window.
+template <bool SELECT>
+__global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, RefReq rq, int w0, int nf, RefWs W, RefView V, char* recs,
                                                      const uint8_t* anc_mask, const double* anc_xyz)
 {
     const int w = w0 + blockIdx.x, tid = threadIdx.x;
-    const int slot = sl.slot[blockIdx.x];
-    const SessStream& S = ss_all[slot];
-    const int N0 = S.N0, n = min(max(S.n_cur, 0), N0);
-    // the slot's survivors are the tracks NLS.py:190 keeps of a clip that has just had its last frame
-    const int nfix = refine_pack_window(S, S.ids, n, 0, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid,
-                                        anc_mask ? anc_mask + (size_t)slot * N0 : nullptr, anc_mask ? anc_xyz + 3 * (size_t)slot * N0 : nullptr,
-                                        W.fixed + (size_t)w * N0);
-    if (tid == 0) W.nt[w] = n;
-    // the part of the record the solve writes into (info, trace rows up to the iterations it takes): defined from the start; the fourth header word: nfix
-    char* rec = recs + (size_t)w * L.bytes;
-    if (tid < 4) reinterpret_cast<int*>(rec + L.nt)[tid] = tid == 3 ? nfix : 0;
-    double* trace = reinterpret_cast<double*>(rec + L.trace);
-    for (int e = tid; e < 2 * L.max_iter; e += 256) trace[e] = 0.0;
-}
-
-__global__ __launch_bounds__(256) void k_refine_unpack(const SessStream* ss_all, RefSlots sl, int w0, int nf, RefWs W, vh_refine_record L, char* recs)
-{
-    const int w = w0 + blockIdx.x, tid = threadIdx.x;
-    const SessStream& S = ss_all[sl.slot[blockIdx.x]];
-    char* rec = recs + (size_t)w * L.bytes;
-    __shared__ double s_speed[256];  // nf <= 256 (the BA's camera limit)
-    RefOut o;
-    o.nt = reinterpret_cast<int*>(rec + L.nt); o.info = reinterpret_cast<const int*>(rec + L.iterations);
-    o.ids = reinterpret_cast<int*>(rec + L.ids); o.pw = reinterpret_cast<double*>(rec + L.pw);
-    o.cw = reinterpret_cast<double*>(rec + L.cw); o.dr = reinterpret_cast<double*>(rec + L.dr); o.speed = reinterpret_cast<double*>(rec + L.speed);
-    o.speed_mean = reinterpret_cast<double*>(rec + L.speed_mean); o.speed_std = reinterpret_cast<double*>(rec + L.speed_std);
-    o.f_first = reinterpret_cast<double*>(rec + L.f_first); o.f_last = reinterpret_cast<double*>(rec + L.f_last);
-    o.trace = reinterpret_cast<const double*>(rec + L.trace); o.rows = S.nhist; o.max_iter = L.max_iter;
-    refine_unpack_window(S, S.ids, W.nt[w], 0, nf, W.x + (size_t)w * W.x_stride, o, s_speed, tid);
-}
-
-// ---- any frame window of a clip (vh_session_refine_windows): window (slot, first) = frames [first, first + nf) of the slot's clip ---------------------------
-struct RefWins {  // the windows of one pack / unpack launch travel in the kernel arguments, as RefSlots
-    int slot[SESS_REF_CHUNK];
-    int first[SESS_REF_CHUNK];
-};
-
-static void refine_window_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_window_record* L)
-{
-    size_t off = 0;
-    auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
-    L->slot = put(6 * sizeof(int)); L->first = L->slot + 4; L->nt = L->slot + 8;
-    L->iterations = L->slot + 12; L->converged = L->slot + 16;  // (iterations, converged: the int[2] info record of the window's solve)
-    L->nfix = L->slot + 20;                                      // (the header's sixth word)
-    L->cw = put(sizeof(double) * 3 * (size_t)nf);
-    L->dr = put(sizeof(double) * (size_t)nf); L->speed = put(sizeof(double) * (size_t)nf);
-    L->speed_mean = put(sizeof(double)); L->speed_std = put(sizeof(double)); L->f_first = put(sizeof(double)); L->f_last = put(sizeof(double));
-    L->trace = put(sizeof(double) * 2 * (size_t)max_iter);
-    L->ids = with_points ? put(sizeof(int) * (size_t)N0) : 0;
-    L->pw = with_points ? put(sizeof(double) * 3 * (size_t)N0) : 0;
-    L->bytes = off;
-    L->n0 = N0; L->nf = nf; L->max_iter = max_iter; L->with_points = with_points ? 1 : 0;
-}
-
-// select + pack: the window's tracks are the ids whose history row 4 is finite in EVERY frame of the window (NLS.py:190 on the slice) -- not the slot's
-// current survivors: a track that died after the window belongs to it.  One workgroup per window: 256 ids at a time read row 4 of the frame-major
-// history (coalesced over tracks), a ballot + the four wavefronts' counts give each kept id its place, so the ids come out ascending.
-__global__ __launch_bounds__(256) void k_refine_win_pack(const SessStream* ss_all, RefWins wn, int w0, int nf, RefWs W, vh_refine_window_record L, char* recs,
-                                                         const uint8_t* anc_mask, const double* anc_xyz)
-{
-    const int w = w0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int slot = wn.slot[blockIdx.x], first = wn.first[blockIdx.x];
+    const int slot = rq.slot[blockIdx.x], first = rq.first[blockIdx.x];
     const SessStream& S = ss_all[slot];
     const int N0 = S.N0;
-    int* ids = W.ids + (size_t)w * N0;
-    __shared__ int s_cnt[4], s_base;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int g0 = 0; g0 < N0; g0 += 256) {  // (uniform trip count: every lane of every wavefront reaches the ballot and the barriers)
-        const int g = g0 + tid;
-        bool alive = g < N0;
-        for (int f = 0; alive && f < nf; f++) alive = isfinite(S.P[sess_P(4, g, first + f, N0)]);
-        const unsigned long long bal = __ballot(alive);
-        if (lane == 0) s_cnt[wave] = __popcll(bal);
+    const int* ids = S.ids;
+    int n = min(max(S.n_cur, 0), N0);
+    if (SELECT) {
+        const int lane = tid & 63, wave = tid >> 6;
+        int* sel = W.ids + (size_t)w * N0;
+        __shared__ int s_cnt[4], s_base;
+        if (tid == 0) s_base = 0;
         __syncthreads();
-        int at = s_base;
-        for (int k = 0; k < wave; k++) at += s_cnt[k];
-        if (alive) ids[at + __popcll(bal & ((1ull << lane) - 1ull))] = g;
-        __syncthreads();
-        if (tid == 0) s_base += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        __syncthreads();
+        for (int g0 = 0; g0 < N0; g0 += 256) {  // (uniform trip count: every lane of every wavefront reaches the ballot and the barriers)
+            const int g = g0 + tid;
+            bool alive = g < N0;
+            for (int f = 0; alive && f < nf; f++) alive = isfinite(S.P[sess_P(4, g, first + f, N0)]);
+            const unsigned long long bal = __ballot(alive);
+            if (lane == 0) s_cnt[wave] = __popcll(bal);
+            __syncthreads();
+            int at = s_base;
+            for (int k = 0; k < wave; k++) at += s_cnt[k];
+            if (alive) sel[at + __popcll(bal & ((1ull << lane) - 1ull))] = g;
+            __syncthreads();
+            if (tid == 0) s_base += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            __syncthreads();
+        }
+        ids = sel; n = s_base;  // (the ids written above are visible to the whole workgroup: barriers since)
     }
-    const int n = s_base;  // (the ids written above are visible to the whole workgroup: barriers since)
     const int nfix = refine_pack_window(S, ids, n, first, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid,
                                         anc_mask ? anc_mask + (size_t)slot * N0 : nullptr, anc_mask ? anc_xyz + 3 * (size_t)slot * N0 : nullptr,
                                         W.fixed + (size_t)w * N0);
     if (tid == 0) W.nt[w] = n;
-    // the part of the record the solve writes into (info, trace rows up to the iterations it takes) and the header (sixth word: nfix): defined from the start
-    char* rec = recs + (size_t)w * L.bytes;
-    if (tid < 6) reinterpret_cast<int*>(rec + L.slot)[tid] = tid == 0 ? slot : (tid == 1 ? first : (tid == 5 ? nfix : 0));
-    double* trace = reinterpret_cast<double*>(rec + L.trace);
-    for (int e = tid; e < 2 * L.max_iter; e += 256) trace[e] = 0.0;
+    // the part of the record the solve writes into (info, trace rows up to the iterations it takes) and the header -- {slot, first} where the record
+    // has them, then {nt, iterations, converged} = 0 and nfix, its last word: defined from the start
+    char* rec = recs + (size_t)w * V.bytes;
+    const int lead = V.head_words - 4;
+    if (tid < V.head_words)
+        reinterpret_cast<int*>(rec + V.head)[tid] = tid < lead ? (tid == lead - 2 ? slot : first) : (tid == V.head_words - 1 ? nfix : 0);
+    double* trace = reinterpret_cast<double*>(rec + V.trace);
+    for (int e = tid; e < 2 * V.max_iter; e += 256) trace[e] = 0.0;
 }
 
-__global__ __launch_bounds__(256) void k_refine_win_unpack(const SessStream* ss_all, RefWins wn, int w0, int nf, RefWs W, vh_refine_window_record L, char* recs)
+// unpack: W.ids is null when the windows are whole clips (the slot's survivors, as packed)
+__global__ __launch_bounds__(256) void k_refine_unpack(const SessStream* ss_all, RefReq rq, int w0, int nf, RefWs W, RefView V, char* recs)
 {
     const int w = w0 + blockIdx.x, tid = threadIdx.x;
-    const SessStream& S = ss_all[wn.slot[blockIdx.x]];
-    char* rec = recs + (size_t)w * L.bytes;
+    const SessStream& S = ss_all[rq.slot[blockIdx.x]];
+    char* rec = recs + (size_t)w * V.bytes;
     __shared__ double s_speed[256];  // nf <= 256 (the BA's camera limit)
     RefOut o;
-    o.nt = reinterpret_cast<int*>(rec + L.nt); o.info = reinterpret_cast<const int*>(rec + L.iterations);
-    o.ids = L.with_points ? reinterpret_cast<int*>(rec + L.ids) : nullptr; o.pw = L.with_points ? reinterpret_cast<double*>(rec + L.pw) : nullptr;
-    o.cw = reinterpret_cast<double*>(rec + L.cw); o.dr = reinterpret_cast<double*>(rec + L.dr); o.speed = reinterpret_cast<double*>(rec + L.speed);
-    o.speed_mean = reinterpret_cast<double*>(rec + L.speed_mean); o.speed_std = reinterpret_cast<double*>(rec + L.speed_std);
-    o.f_first = reinterpret_cast<double*>(rec + L.f_first); o.f_last = reinterpret_cast<double*>(rec + L.f_last);
-    o.trace = reinterpret_cast<const double*>(rec + L.trace); o.rows = nf; o.max_iter = L.max_iter;
-    refine_unpack_window(S, W.ids + (size_t)w * S.N0, W.nt[w], wn.first[blockIdx.x], nf, W.x + (size_t)w * W.x_stride, o, s_speed, tid);
+    o.nt = reinterpret_cast<int*>(rec + V.nt); o.info = reinterpret_cast<const int*>(rec + V.info);
+    o.ids = V.with_points ? reinterpret_cast<int*>(rec + V.ids) : nullptr; o.pw = V.with_points ? reinterpret_cast<double*>(rec + V.pw) : nullptr;
+    o.cw = reinterpret_cast<double*>(rec + V.cw); o.dr = reinterpret_cast<double*>(rec + V.dr); o.speed = reinterpret_cast<double*>(rec + V.speed);
+    o.speed_mean = reinterpret_cast<double*>(rec + V.speed_mean); o.speed_std = reinterpret_cast<double*>(rec + V.speed_std);
+    o.f_first = reinterpret_cast<double*>(rec + V.f_first); o.f_last = reinterpret_cast<double*>(rec + V.f_last);
+    o.trace = reinterpret_cast<const double*>(rec + V.trace); o.rows = V.rows; o.max_iter = V.max_iter;
+    refine_unpack_window(S, W.ids ? W.ids + (size_t)w * S.N0 : S.ids, W.nt[w], rq.first[blockIdx.x], nf, W.x + (size_t)w * W.x_stride, o, s_speed, tid);
+}
+
+struct RefEntry {  // how a public entry words the refusals both share
+    const char* name;
+    bool windows;            // vh_session_refine_windows: selected tracks, its record; else whole clips
+    const char* bad_args;    // null arguments (vh_session_refine: its one message for those, misaligned buffers, no slot and no iteration)
+    const char* misaligned;
+    const char* unit;        // what nf frames are: "a clip" | "a window"
+    const char* per;         // behind the camera limit: "" | " per window"
+    const char* noun;        // "slots" | "windows"
+};
+static const char REF_CLIPS_BAD[] = "vh_session_refine: bad arguments (records 8-byte, workspace 256-byte aligned; at least one slot and one iteration)";
+static const RefEntry REF_CLIPS = {"vh_session_refine", false, REF_CLIPS_BAD, REF_CLIPS_BAD, "a clip", "", "slots"};
+static const RefEntry REF_WINDOWS = {"vh_session_refine_windows", true,
+                                     "vh_session_refine_windows: bad arguments (a null session, window table, record buffer or workspace)",
+                                     "vh_session_refine_windows: misaligned buffers (records 8-byte, workspace 256-byte aligned)", "a window", " per window",
+                                     "windows"};
+
+// THE refinement request: n windows of nf frames -> n records at recs_dev.  The checks both entries share, worded as E's; own(fail, req): the entry's
+// own checks of its table, which leaves the windows in req (or returns what fail returned); then the workspace, pack, ONE vh_ba_windows launch
+// sequence, unpack.  Every refusal returns before anything is queued.
+template <class Own>
+static int refine_request(const RefEntry& E, vh_session* s, const void* table, int n, int nf, int max_iter, int with_points, void* recs_dev, void* workspace,
+                          size_t workspace_bytes, void* stream, Own own)
+{
+    char msg[240];
+    auto fail = [&](const char* fmt, auto... a) {
+        const int at = snprintf(msg, sizeof(msg), "%s: ", E.name);
+        snprintf(msg + at, sizeof(msg) - at, fmt, a...);
+        return vh_fail(-1, msg);
+    };
+    if (!s || !table || !recs_dev || !workspace) return vh_fail(-1, E.bad_args);
+    if ((reinterpret_cast<uintptr_t>(recs_dev) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return vh_fail(-1, E.misaligned);
+    if (n < 1) return E.windows ? fail("nwin = %d: at least one window", n) : vh_fail(-1, E.bad_args);
+    if (E.windows && n > 65535) return fail("nwin = %d: at most 65535 windows in one launch sequence", n);
+    if (max_iter < 1) return E.windows ? fail("max_iter = %d: at least one iteration", max_iter) : vh_fail(-1, E.bad_args);
+    if (nf < 2) return fail("nf = %d: %s needs at least two frames", nf, E.unit);
+    if (nf - 1 > 255) return fail("nf = %d: at most 255 free cameras (256 frames)%s", nf, E.per);
+    if (nf > s->nhist) return fail("nf = %d exceeds the session's history of %d frames", nf, s->nhist);
+    std::vector<vh_refine_window> req;
+    if (int r = own(fail, req)) return r;
+    RefWs W;
+    const size_t need = refine_ws_layout(s, n, nf, reinterpret_cast<char*>(workspace), &W, E.windows);
+    if (workspace_bytes < need) return fail("workspace of %zu bytes, %d %s of %d frames need %zu", workspace_bytes, n, E.noun, nf, need);
+    RefView V;
+    if (E.windows) {
+        vh_refine_window_record L;
+        refine_window_record_layout(s->N0, nf, max_iter, with_points, &L);
+        V = refine_view(L, L.slot, nf, L.with_points);
+    } else {
+        vh_refine_record L;
+        refine_record_layout(s->N0, s->nhist, max_iter, &L);
+        V = refine_view(L, L.nt, s->nhist, 1);
+    }
+    char* recs = reinterpret_cast<char*>(recs_dev);
+    bool anchored = false;  // the tables travel only when a slot of the request has anchors: otherwise the solve is queued as ever, with no table
+    for (int k = 0; k < n; k++) anchored = anchored || s->h_nanchor[req[k].slot] > 0;
+    auto each_chunk = [&](auto kernel, hipStream_t st, auto... more) {
+        for (int w0 = 0; w0 < n; w0 += SESS_REF_CHUNK) {
+            RefReq rq;
+            const int cnt = n - w0 < SESS_REF_CHUNK ? n - w0 : SESS_REF_CHUNK;
+            for (int k = 0; k < SESS_REF_CHUNK; k++) {  // (behind the last window: window w0 again, which no workgroup reads)
+                rq.slot[k] = req[w0 + (k < cnt ? k : 0)].slot;
+                rq.first[k] = req[w0 + (k < cnt ? k : 0)].first;
+            }
+            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, rq, w0, nf, W, V, recs, more...);
+        }
+    };
+    {
+        VH_BIND(s->ctx, stream);
+        const uint8_t* mask = anchored ? s->d_anc_mask : nullptr;
+        const double* xyz = anchored ? s->d_anc_xyz : nullptr;
+        if (E.windows) each_chunk(k_refine_pack<true>, bound_.s, mask, xyz);
+        else each_chunk(k_refine_pack<false>, bound_.s, mask, xyz);
+        SESS_CHECK();
+    }
+    // the windows' info = {iterations, converged} and trace go straight into the records
+    int r = vh_ba_windows(s->ctx, s->h_ss[req[0].slot].K, W.z, W.x, s->N0, nf - 1, n, W.nt, W.K, anchored ? W.fixed : nullptr, max_iter, reinterpret_cast<double*>(recs + V.trace),
+                          V.bytes / sizeof(double), reinterpret_cast<int*>(recs + V.info), V.bytes / sizeof(int), W.ba, W.ba_stride, stream);
+    if (r) return r;
+    VH_BIND(s->ctx, stream);
+    each_chunk(k_refine_unpack, bound_.s);
+    SESS_CHECK();
+    return 0;
 }
 
 extern "C" VH_API size_t vh_session_refine_size(const vh_session* s, int max_iter, vh_refine_record* layout_host)
@@ -1114,57 +1192,19 @@ extern "C" VH_API size_t vh_session_refine_workspace(const vh_session* s, int ns
 extern "C" VH_API int vh_session_refine(vh_session* s, const int* slots_host, int nslots, int nf, int max_iter, void* recs_dev, void* workspace,
                                         size_t workspace_bytes, void* stream)
 {
-    char msg[240];
-    if (!s || !slots_host || !recs_dev || !workspace || nslots < 1 || max_iter < 1 || (reinterpret_cast<uintptr_t>(recs_dev) & 7) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 255))
-        return vh_fail(-1, "vh_session_refine: bad arguments (records 8-byte, workspace 256-byte aligned; at least one slot and one iteration)");
-    if (nf < 2) { snprintf(msg, sizeof(msg), "vh_session_refine: nf = %d: a clip needs at least two frames", nf); return vh_fail(-1, msg); }
-    if (nf - 1 > 255) { snprintf(msg, sizeof(msg), "vh_session_refine: nf = %d: at most 255 free cameras (256 frames)", nf); return vh_fail(-1, msg); }
-    if (nf > s->nhist) { snprintf(msg, sizeof(msg), "vh_session_refine: nf = %d exceeds the session's history of %d frames", nf, s->nhist); return vh_fail(-1, msg); }
-    if (nslots > s->batch) { snprintf(msg, sizeof(msg), "vh_session_refine: %d slots, the session has %d", nslots, s->batch); return vh_fail(-1, msg); }
-    std::vector<char> seen(s->batch, 0);
-    for (int k = 0; k < nslots; k++) {
-        const int b = slots_host[k];
-        if (b < 0 || b >= s->batch) { snprintf(msg, sizeof(msg), "vh_session_refine: slot %d is outside the session's %d slots", b, s->batch); return vh_fail(-1, msg); }
-        if (seen[b]) { snprintf(msg, sizeof(msg), "vh_session_refine: slot %d is given twice", b); return vh_fail(-1, msg); }
-        seen[b] = 1;
-        if (s->h_frame[b] != nf - 1) {
-            snprintf(msg, sizeof(msg), "vh_session_refine: slot %d is at frame %d, not at the last frame nf - 1 = %d of its clip", b, s->h_frame[b], nf - 1);
-            return vh_fail(-1, msg);
+    return refine_request(REF_CLIPS, s, slots_host, nslots, nf, max_iter, 1, recs_dev, workspace, workspace_bytes, stream, [&](auto fail, auto& req) {
+        if (nslots > s->batch) return fail("%d slots, the session has %d", nslots, s->batch);
+        std::vector<char> seen(s->batch, 0);
+        for (int k = 0; k < nslots; k++) {
+            const int b = slots_host[k];
+            if (b < 0 || b >= s->batch) return fail("slot %d is outside the session's %d slots", b, s->batch);
+            if (seen[b]) return fail("slot %d is given twice", b);
+            seen[b] = 1;
+            if (s->h_frame[b] != nf - 1) return fail("slot %d is at frame %d, not at the last frame nf - 1 = %d of its clip", b, s->h_frame[b], nf - 1);
+            req.push_back({b, 0});
         }
-    }
-    RefWs W;
-    const size_t need = refine_ws_layout(s, nslots, nf, reinterpret_cast<char*>(workspace), &W);
-    if (workspace_bytes < need) {
-        snprintf(msg, sizeof(msg), "vh_session_refine: workspace of %zu bytes, %d slots of %d frames need %zu", workspace_bytes, nslots, nf, need);
-        return vh_fail(-1, msg);
-    }
-    vh_refine_record L;
-    refine_record_layout(s->N0, s->nhist, max_iter, &L);
-    char* recs = reinterpret_cast<char*>(recs_dev);
-    bool anchored = false;  // the tables travel only when a slot of the request has anchors: otherwise the solve is queued as ever, with no table
-    for (int k = 0; k < nslots; k++) anchored = anchored || s->h_nanchor[slots_host[k]] > 0;
-    auto each_chunk = [&](auto kernel, hipStream_t st, auto... more) {
-        for (int w0 = 0; w0 < nslots; w0 += SESS_REF_CHUNK) {
-            RefSlots sl;
-            const int cnt = nslots - w0 < SESS_REF_CHUNK ? nslots - w0 : SESS_REF_CHUNK;
-            for (int k = 0; k < SESS_REF_CHUNK; k++) sl.slot[k] = slots_host[w0 + (k < cnt ? k : 0)];
-            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, sl, w0, nf, W, L, recs, more...);
-        }
-    };
-    {
-        VH_BIND(s->ctx, stream);
-        each_chunk(k_refine_pack, bound_.s, anchored ? (const uint8_t*)s->d_anc_mask : nullptr, anchored ? (const double*)s->d_anc_xyz : nullptr);
-        SESS_CHECK();
-    }
-    // the windows' info = {iterations, converged} and trace go straight into the records
-    int r = vh_ba_windows(s->ctx, s->h_ss[slots_host[0]].K, W.z, W.x, s->N0, nf - 1, nslots, W.nt, W.K, anchored ? W.fixed : nullptr, max_iter, reinterpret_cast<double*>(recs + L.trace),
-                          L.bytes / sizeof(double), reinterpret_cast<int*>(recs + L.iterations), L.bytes / sizeof(int), W.ba, W.ba_stride, stream);
-    if (r) return r;
-    VH_BIND(s->ctx, stream);
-    each_chunk(k_refine_unpack, bound_.s);
-    SESS_CHECK();
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" VH_API size_t vh_session_refine_windows_size(const vh_session* s, int nf, int max_iter, int with_points, vh_refine_window_record* layout_host)
@@ -1186,70 +1226,22 @@ extern "C" VH_API size_t vh_session_refine_windows_workspace(const vh_session* s
 extern "C" VH_API int vh_session_refine_windows(vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, int max_iter, int with_points,
                                                 void* recs_dev, void* workspace, size_t workspace_bytes, void* stream)
 {
-    char msg[240];
-    if (!s || !wins_host || !recs_dev || !workspace)
-        return vh_fail(-1, "vh_session_refine_windows: bad arguments (a null session, window table, record buffer or workspace)");
-    if ((reinterpret_cast<uintptr_t>(recs_dev) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 255))
-        return vh_fail(-1, "vh_session_refine_windows: misaligned buffers (records 8-byte, workspace 256-byte aligned)");
-    if (nwin < 1) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nwin = %d: at least one window", nwin); return vh_fail(-1, msg); }
-    if (nwin > 65535) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nwin = %d: at most 65535 windows in one launch sequence", nwin); return vh_fail(-1, msg); }
-    if (max_iter < 1) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: max_iter = %d: at least one iteration", max_iter); return vh_fail(-1, msg); }
-    if (nf < 2) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nf = %d: a window needs at least two frames", nf); return vh_fail(-1, msg); }
-    if (nf - 1 > 255) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nf = %d: at most 255 free cameras (256 frames) per window", nf); return vh_fail(-1, msg); }
-    if (nf > s->nhist) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: nf = %d exceeds the session's history of %d frames", nf, s->nhist); return vh_fail(-1, msg); }
-    std::vector<std::vector<int>> seen(s->batch);  // per slot: the window starts given so far
-    for (int k = 0; k < nwin; k++) {
-        const int b = wins_host[k].slot, first = wins_host[k].first;
-        if (b < 0 || b >= s->batch) {
-            snprintf(msg, sizeof(msg), "vh_session_refine_windows: window %d: slot %d is outside the session's %d slots", k, b, s->batch);
-            return vh_fail(-1, msg);
+    return refine_request(REF_WINDOWS, s, wins_host, nwin, nf, max_iter, with_points, recs_dev, workspace, workspace_bytes, stream, [&](auto fail, auto& req) {
+        std::vector<std::vector<int>> seen(s->batch);  // per slot: the window starts given so far
+        for (int k = 0; k < nwin; k++) {
+            const int b = wins_host[k].slot, first = wins_host[k].first;
+            if (b < 0 || b >= s->batch) return fail("window %d: slot %d is outside the session's %d slots", k, b, s->batch);
+            if (first < 0) return fail("window %d (slot %d): first = %d is negative", k, b, first);
+            const int last_have = s->h_frame[b] < s->nhist - 1 ? s->h_frame[b] : s->nhist - 1;  // (the history holds nhist frames)
+            if (first > last_have || nf - 1 > last_have - first)
+                return fail("window %d (slot %d, first %d) ends at frame %lld, the slot is at frame %d", k, b, first, (long long)first + nf - 1, last_have);
+            for (int f : seen[b])
+                if (f == first) return fail("window (slot %d, first %d) is given twice", b, first);
+            seen[b].push_back(first);
         }
-        if (first < 0) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: window %d (slot %d): first = %d is negative", k, b, first); return vh_fail(-1, msg); }
-        const int last_have = s->h_frame[b] < s->nhist - 1 ? s->h_frame[b] : s->nhist - 1;  // (the history holds nhist frames)
-        if (first > last_have || nf - 1 > last_have - first) {
-            snprintf(msg, sizeof(msg), "vh_session_refine_windows: window %d (slot %d, first %d) ends at frame %lld, the slot is at frame %d", k, b, first,
-                     (long long)first + nf - 1, last_have);
-            return vh_fail(-1, msg);
-        }
-        for (int f : seen[b])
-            if (f == first) { snprintf(msg, sizeof(msg), "vh_session_refine_windows: window (slot %d, first %d) is given twice", b, first); return vh_fail(-1, msg); }
-        seen[b].push_back(first);
-    }
-    RefWs W;
-    const size_t need = refine_ws_layout(s, nwin, nf, reinterpret_cast<char*>(workspace), &W, true);
-    if (workspace_bytes < need) {
-        snprintf(msg, sizeof(msg), "vh_session_refine_windows: workspace of %zu bytes, %d windows of %d frames need %zu", workspace_bytes, nwin, nf, need);
-        return vh_fail(-1, msg);
-    }
-    vh_refine_window_record L;
-    refine_window_record_layout(s->N0, nf, max_iter, with_points, &L);
-    char* recs = reinterpret_cast<char*>(recs_dev);
-    bool anchored = false;  // as vh_session_refine
-    for (int k = 0; k < nwin; k++) anchored = anchored || s->h_nanchor[wins_host[k].slot] > 0;
-    auto each_chunk = [&](auto kernel, hipStream_t st, auto... more) {
-        for (int w0 = 0; w0 < nwin; w0 += SESS_REF_CHUNK) {
-            RefWins wn;
-            const int cnt = nwin - w0 < SESS_REF_CHUNK ? nwin - w0 : SESS_REF_CHUNK;
-            for (int k = 0; k < SESS_REF_CHUNK; k++) {
-                wn.slot[k] = wins_host[w0 + (k < cnt ? k : 0)].slot;
-                wn.first[k] = wins_host[w0 + (k < cnt ? k : 0)].first;
-            }
-            hipLaunchKernelGGL(kernel, dim3(cnt), dim3(256), 0, st, s->d_ss, wn, w0, nf, W, L, recs, more...);
-        }
-    };
-    {
-        VH_BIND(s->ctx, stream);
-        each_chunk(k_refine_win_pack, bound_.s, anchored ? (const uint8_t*)s->d_anc_mask : nullptr, anchored ? (const double*)s->d_anc_xyz : nullptr);
-        SESS_CHECK();
-    }
-    // the windows' info = {iterations, converged} and trace go straight into the records
-    int r = vh_ba_windows(s->ctx, s->h_ss[wins_host[0].slot].K, W.z, W.x, s->N0, nf - 1, nwin, W.nt, W.K, anchored ? W.fixed : nullptr, max_iter, reinterpret_cast<double*>(recs + L.trace),
-                          L.bytes / sizeof(double), reinterpret_cast<int*>(recs + L.iterations), L.bytes / sizeof(int), W.ba, W.ba_stride, stream);
-    if (r) return r;
-    VH_BIND(s->ctx, stream);
-    each_chunk(k_refine_win_unpack, bound_.s);
-    SESS_CHECK();
-    return 0;
+        req.assign(wins_host, wins_host + nwin);
+        return 0;
+    });
 }
 
 // packed track state of every stream for the cross-GPU exchange (K20): per stream a record of 8 + 3*N0 float32 words

@@ -313,6 +313,33 @@ class TrackerSession:
             lays[max_iter] = lay
         return lays[max_iter]
 
+    def _refine_request(self, call, items, lay, nf, out, chunk, need):
+        """THE refinement request behind refine() and refine_windows(): `items` (slots or windows) go to the library `chunk` at a time -- call(part, recs)
+        queues one part with its records at device address `recs`, on a scratch of `need` bytes -- then one asynchronous copy per pinned buffer and an
+        event.  The scratch and the device records belong to the session and are reused (the chunks share the scratch: they are ordered by the stream).
+        out: None (a new pinned buffer), ONE pinned uint8 tensor for all the records, or a list whose entries are a pinned tensor (one record) or
+        (pinned tensor, count): consecutive records, `count` of them into that tensor."""
+        torch = self.torch
+        nbytes = lay.bytes * len(items)
+        if getattr(self, "_refine_ws", None) is None or self._refine_ws.numel() < need:
+            self._refine_ws = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
+        if getattr(self, "_refine_dev", None) is None or self._refine_dev.numel() < nbytes:
+            self._refine_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        parts = [(out, len(items))] if isinstance(out, torch.Tensor) else [(b, 1) if isinstance(b, torch.Tensor) else (b[0], int(b[1])) for b in out]
+        assert sum(k for _, k in parts) == len(items)
+        assert all(b.dtype == torch.uint8 and b.numel() >= k * lay.bytes and b.is_pinned() and b.is_contiguous() for b, k in parts)
+        for w0 in range(0, len(items), chunk):
+            call(items[w0:w0 + chunk], C.c_void_p(self._refine_dev.data_ptr() + w0 * lay.bytes))
+        at = 0
+        for b, k in parts:
+            b[: k * lay.bytes].copy_(self._refine_dev[at:at + k * lay.bytes], non_blocking=True)
+            at += k * lay.bytes
+        ev = torch.cuda.Event()
+        ev.record()
+        return Refined(parts, lay, ev, chunk, nf)
+
     def refine(self, slots, max_iter=10, out=None):
         """Bundle adjustment of the finished clips in `slots` (vidExample.py:157: fcnNLS_batch(K, P[:, :, 0:i], p3, B[0:i, 3:6]), NLS.py:186-250), without
         leaving the device: ONE vh_session_refine -- pack, one BA launch sequence for all the slots (their track counts and cameras may differ), unpack --
@@ -320,33 +347,17 @@ class TrackerSession:
         lengths: another call).  The session's state is only read: its streams step on as if nothing had happened.  The scratch and the device records
         belong to the session and are reused.  out: None (a new pinned buffer), ONE pinned uint8 tensor for all the records, or one per slot.
         Returns a handle like export()'s: .done() polls, .result() waits and returns one dict per slot (unpack_refine)."""
-        torch = self.torch
         slots = [int(b) for b in slots]
         if not slots:
             raise ValueError("refine: no slot given")
-        lay = self.refine_layout(max_iter)
         nf = self._frame_i[slots[0]] + 1 if 0 <= slots[0] < self.batch else 0  # (a slot outside the session: the library names it)
         need = int(self.lib.vh_session_refine_workspace(self.handle, len(slots), nf)) if nf >= 2 and len(slots) <= self.batch else 0
-        nbytes = lay.bytes * len(slots)
-        if getattr(self, "_refine_ws", None) is None or self._refine_ws.numel() < need:
-            self._refine_ws = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
-        if getattr(self, "_refine_dev", None) is None or self._refine_dev.numel() < nbytes:
-            self._refine_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-        if out is None:
-            out = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-        bufs = [out[k * lay.bytes:(k + 1) * lay.bytes] for k in range(len(slots))] if isinstance(out, torch.Tensor) else list(out)
-        assert len(bufs) == len(slots) and all(b.dtype == torch.uint8 and b.numel() >= lay.bytes and b.is_pinned() and b.is_contiguous() for b in bufs)
-        L.check(self.lib.vh_session_refine(self.handle, (C.c_int * len(slots))(*slots), len(slots), nf, int(max_iter), L.dptr(self._refine_dev),
-                                           L.dptr(self._refine_ws), self._refine_ws.numel(), L.stream_ptr()), "vh_session_refine")
-        if isinstance(out, torch.Tensor):
-            out[:nbytes].copy_(self._refine_dev[:nbytes], non_blocking=True)
-        else:
-            for k, b in enumerate(bufs):
-                b[: lay.bytes].copy_(self._refine_dev[k * lay.bytes:(k + 1) * lay.bytes], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return RefinedClips(bufs, lay, ev, nf)
 
+        def call(part, recs):
+            L.check(self.lib.vh_session_refine(self.handle, (C.c_int * len(part))(*part), len(part), nf, int(max_iter), recs, L.dptr(self._refine_ws),
+                                               self._refine_ws.numel(), L.stream_ptr()), "vh_session_refine")
+
+        return self._refine_request(call, slots, self.refine_layout(max_iter), nf, out, len(slots), need)
     def refine_window_layout(self, nf, max_iter=10, with_points=False):
         """vh_refine_window_record of this session for windows of nf frames: byte offsets of the fields of a refined window's record (and `bytes`)."""
         lays = self.__dict__.setdefault("_refine_window_layouts", {})
@@ -368,7 +379,6 @@ class TrackerSession:
         out: None (a new pinned buffer), ONE pinned uint8 tensor for all the records, or a list of (pinned uint8 tensor, count): consecutive records,
         `count` of them into each tensor.  with_points: the records also carry ids and pw (in the window's coordinates).
         Returns a handle like refine()'s: .done() polls, .result() waits and returns one dict per window (unpack_refine_window), in the order given."""
-        torch = self.torch
         wins = [(int(b), int(f)) for b, f in windows]
         if not wins:
             raise ValueError("refine_windows: no window given")
@@ -385,29 +395,13 @@ class TrackerSession:
             for b, f in wins:
                 if not 0 <= b < self.batch or f < 0 or f + nf - 1 > self._frame_i[b]:
                     raise ValueError(f"refine_windows: window (slot {b}, first {f}) of {nf} frames is outside the session's {self.batch} slots or the frames its slot has had")
-        need = int(self.lib.vh_session_refine_windows_workspace(self.handle, chunk, nf))
-        nbytes = lay.bytes * len(wins)
-        if getattr(self, "_refine_ws", None) is None or self._refine_ws.numel() < need:
-            self._refine_ws = torch.empty(max(need, 256), dtype=torch.uint8, device="cuda")
-        if getattr(self, "_refine_dev", None) is None or self._refine_dev.numel() < nbytes:
-            self._refine_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-        if out is None:
-            out = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-        parts = [(out, len(wins))] if isinstance(out, torch.Tensor) else [(b, int(k)) for b, k in out]
-        assert sum(k for _, k in parts) == len(wins)
-        assert all(b.dtype == torch.uint8 and b.numel() >= k * lay.bytes and b.is_pinned() and b.is_contiguous() for b, k in parts)
-        for w0 in range(0, len(wins), chunk):  # the chunks share the scratch: they are ordered by the stream
-            part = wins[w0:w0 + chunk]
+
+        def call(part, recs):
             tab = (L.RefineWindow * len(part))(*[L.RefineWindow(b, f) for b, f in part])
-            L.check(self.lib.vh_session_refine_windows(self.handle, tab, len(part), nf, max_iter, int(bool(with_points)), C.c_void_p(self._refine_dev.data_ptr() + w0 * lay.bytes),
-                                                       L.dptr(self._refine_ws), self._refine_ws.numel(), L.stream_ptr()), "vh_session_refine_windows")
-        at = 0
-        for b, k in parts:
-            b[: k * lay.bytes].copy_(self._refine_dev[at:at + k * lay.bytes], non_blocking=True)
-            at += k * lay.bytes
-        ev = torch.cuda.Event()
-        ev.record()
-        return RefinedWindows(parts, lay, ev, chunk)
+            L.check(self.lib.vh_session_refine_windows(self.handle, tab, len(part), nf, max_iter, int(bool(with_points)), recs, L.dptr(self._refine_ws),
+                                                       self._refine_ws.numel(), L.stream_ptr()), "vh_session_refine_windows")
+
+        return self._refine_request(call, wins, lay, nf, out, chunk, int(self.lib.vh_session_refine_windows_workspace(self.handle, chunk, nf)))
 
     def __del__(self):
         try:
@@ -437,11 +431,14 @@ class ExportedState:
         return self._res
 
 
-class RefinedClips:
-    """The refined clips of one TrackerSession.refine on their way to the host: one pinned record per slot."""
+class Refined:
+    """The records of one TrackerSession.refine or refine_windows request on their way to the host, in the order given.  parts: [(pinned buffer, the
+    consecutive records it holds)]; bufs: one view per record; chunk: the slots or windows per library call; nf: the frames of a clip or window."""
 
-    def __init__(self, bufs, layout, event, nf):
-        self.bufs, self.layout, self.event, self.nf = bufs, layout, event, nf
+    def __init__(self, parts, layout, event, chunk, nf):
+        self.parts, self.layout, self.event, self.chunk, self.nf = parts, layout, event, chunk, nf
+        nb = layout.bytes
+        self.bufs = [b[k * nb:(k + 1) * nb] for b, cnt in parts for k in range(cnt)]
         self._res = None
 
     def done(self):
@@ -451,26 +448,11 @@ class RefinedClips:
     def result(self):
         if self._res is None:
             self.event.synchronize()
-            self._res = [unpack_refine(b.numpy(), self.layout, self.nf) for b in self.bufs]
+            self._res = [_unpack_refined(b.numpy(), self.layout, self.nf) for b in self.bufs]
         return self._res
 
 
-def unpack_refine(raw, lay, nf=None):
-    """A vh_refine_record (uint8 array `raw`, offsets `lay`) as a dict: nt, nfix (anchored points among the nt), ids [nt], pw [nt, 3], cw [nf, 3], dr [nf],
-    speed [nf] (entry 0 NaN), speed_mean, speed_std, iterations, converged, trace [iterations, 2], f_first, f_last; every array is a copy.  nf: the clip's frames (None: the
-    rows of cw the record defines)."""
-
-    def rd(off, count, dtype):
-        return np.frombuffer(raw, dtype, count, off).copy()
-
-    nt, iterations, converged, nfix = (int(rd(off, 1, np.int32)[0]) for off in (lay.nt, lay.iterations, lay.converged, lay.nfix))
-    cw = rd(lay.cw, 3 * lay.nhist, np.float64).reshape(lay.nhist, 3)
-    if nf is None:
-        nf = int(np.isfinite(cw[:, 0]).sum())
-    one = {k: float(rd(getattr(lay, k), 1, np.float64)[0]) for k in ("speed_mean", "speed_std", "f_first", "f_last")}
-    return dict(nt=nt, nfix=nfix, ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3), cw=cw[:nf].copy(), dr=rd(lay.dr, nf, np.float64),
-                speed=rd(lay.speed, nf, np.float64), iterations=iterations, converged=converged,
-                trace=rd(lay.trace, 2 * iterations, np.float64).reshape(iterations, 2), **one)
+RefinedClips = RefinedWindows = Refined
 
 
 # Device scratch one refine_windows chunk may take, in bytes (the keyword workspace_budget overrides it).  A window's share is its z, x0 and BA workspace
@@ -480,23 +462,32 @@ REFINE_WINDOWS_BUDGET = 1 << 30
 REFINE_WINDOWS_MOST = 65535  # windows of one BA launch sequence (vh_nls_batch_windows)
 
 
-class RefinedWindows:
-    """The refined windows of one TrackerSession.refine_windows on their way to the host: the records of all its chunks, gathered in the order given."""
+def _unpack_refined(raw, lay, nf=None):
+    """THE reader of a refinement record of either layout (uint8 array `raw`, offsets `lay`): the header words, the first nf of the record's rows of cw, dr
+    and speed, the scalars, the trace and -- where the record carries them -- ids and pw; every array is a copy."""
+    window = isinstance(lay, L.RefineWindowRecord)
 
-    def __init__(self, parts, layout, event, chunk):
-        self.parts, self.layout, self.event, self.chunk = parts, layout, event, chunk
-        self._res = None
+    def rd(off, count, dtype):
+        return np.frombuffer(raw, dtype, count, off).copy()
 
-    def done(self):
-        """True once the records have arrived (never waits)."""
-        return self._res is not None or self.event.query()
+    head = {k: int(rd(getattr(lay, k), 1, np.int32)[0]) for k in (("slot", "first") if window else ()) + ("nt", "iterations", "converged", "nfix")}
+    rows, nt = lay.nf if window else lay.nhist, head["nt"]
+    cw = rd(lay.cw, 3 * rows, np.float64).reshape(rows, 3)
+    if window:
+        nf = rows
+    elif nf is None:
+        nf = int(np.isfinite(cw[:, 0]).sum())
+    one = {k: float(rd(getattr(lay, k), 1, np.float64)[0]) for k in ("speed_mean", "speed_std", "f_first", "f_last")}
+    pts = dict(ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3)) if not window or lay.with_points else {}
+    return dict(cw=cw[:nf].copy(), dr=rd(lay.dr, nf, np.float64), speed=rd(lay.speed, nf, np.float64),
+                trace=rd(lay.trace, 2 * head["iterations"], np.float64).reshape(head["iterations"], 2), **head, **one, **pts)
 
-    def result(self):
-        if self._res is None:
-            self.event.synchronize()
-            nb = self.layout.bytes
-            self._res = [unpack_refine_window(b.numpy()[k * nb:(k + 1) * nb], self.layout) for b, cnt in self.parts for k in range(cnt)]
-        return self._res
+
+def unpack_refine(raw, lay, nf=None):
+    """A vh_refine_record (uint8 array `raw`, offsets `lay`) as a dict: nt, nfix (anchored points among the nt), ids [nt], pw [nt, 3], cw [nf, 3], dr [nf],
+    speed [nf] (entry 0 NaN), speed_mean, speed_std, iterations, converged, trace [iterations, 2], f_first, f_last; every array is a copy.  nf: the clip's frames (None: the
+    rows of cw the record defines)."""
+    return _unpack_refined(raw, lay, nf)
 
 
 def unpack_refine_window(raw, lay):
@@ -504,16 +495,7 @@ def unpack_refine_window(raw, lay):
     iterations, converged, cw [nf, 3] (relative to the window's
     first camera), dr [nf], speed [nf] (entry 0 NaN), speed_mean, speed_std, f_first, f_last, trace [iterations, 2] and, when the record carries them,
     ids [nt] and pw [nt, 3] (in the window's coordinates: subtract B[first, 3:6] for the session's); every array is a copy."""
-
-    def rd(off, count, dtype):
-        return np.frombuffer(raw, dtype, count, off).copy()
-
-    head = {k: int(rd(getattr(lay, k), 1, np.int32)[0]) for k in ("slot", "first", "nt", "iterations", "converged", "nfix")}
-    nf, nt = lay.nf, head["nt"]
-    one = {k: float(rd(getattr(lay, k), 1, np.float64)[0]) for k in ("speed_mean", "speed_std", "f_first", "f_last")}
-    pts = dict(ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3)) if lay.with_points else {}
-    return dict(cw=rd(lay.cw, 3 * nf, np.float64).reshape(nf, 3), dr=rd(lay.dr, nf, np.float64), speed=rd(lay.speed, nf, np.float64),
-                trace=rd(lay.trace, 2 * head["iterations"], np.float64).reshape(head["iterations"], 2), **head, **one, **pts)
+    return _unpack_refined(raw, lay)
 
 
 def refine_window_starts(n, window, stride=None):
@@ -561,6 +543,28 @@ def merge_window_speeds(n, windows):
 def _merged_ba(n, wins, window, stride):
     """result["ba"] of a clip refined in windows: merge_window_speeds' dict with `window` and `stride`."""
     return dict(merge_window_speeds(n, wins), window=window, stride=stride)
+
+
+def _refine_finished(ses, clips, win, stride):
+    """The refinement of the clips of session `ses` that have just ended, for all three drivers.  clips = [(slot, clip length, pinned buffer for the
+    clip's records or None: for all of them or for none)]; win, stride: _check_refine's.  The clips of at least `win` frames go through ONE
+    refine_windows request -- the windows refine_window_starts gives each, a clip's consecutive -- and the others through one refine per clip length,
+    shortest first.  Returns per clip (the handle of its request, the function that turns the handle's result into the clip's "ba" dict)."""
+    done = [None] * len(clips)
+    starts = {i: refine_window_starts(n, win, stride) for i, (_, n, _) in enumerate(clips) if win and n >= win}
+    if starts:
+        rh = ses.refine_windows([(clips[i][0], f) for i, st in starts.items() for f in st], win,
+                                out=None if clips[0][2] is None else [(clips[i][2], len(st)) for i, st in starts.items()])
+        at = 0
+        for i, st in starts.items():
+            done[i] = (rh, lambda r, at=at, k=len(st), n=clips[i][1]: _merged_ba(n, r[at:at + k], win, stride))
+            at += len(st)
+    for n_clip in sorted({n for i, (_, n, _) in enumerate(clips) if i not in starts}):
+        same = [i for i, (_, n, _) in enumerate(clips) if i not in starts and n == n_clip]
+        rh = ses.refine([clips[i][0] for i in same], out=None if clips[0][2] is None else [clips[i][2] for i in same])
+        for idx, i in enumerate(same):
+            done[i] = (rh, lambda r, idx=idx: r[idx])
+    return done
 
 
 def ba_line(ba):
@@ -941,11 +945,10 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             row(i)
     ses.torch.cuda.synchronize()
     step_seconds = (clock() - t_loop) / (n - 1)
-    if refine and win and n >= win:
-        ba = _merged_ba(n, ses.refine_windows([(0, f) for f in refine_window_starts(n, win, stride)], win).result(), win, stride)
-    else:
-        ba = ses.refine([0]).result()[0] if refine else None
-    ba = _tag_anchor(ba, refine_anchor)
+    ba = None
+    if refine:
+        (rh, ba_of), = _refine_finished(ses, [(0, n, None)], win, stride)
+        ba = _tag_anchor(ba_of(rh.result()), refine_anchor)
     st, recoveries, f0 = ses.state(0), ses.recoveries()[0], f0.host()
     res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None, ba)
     for line in res["lines"][-(3 if refine else 2) if live else 2:]:  # (not live: the whole clip ran first, and every row carries the mean time per frame)
@@ -1062,19 +1065,12 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
                 ses.step([dev[b][i] for b in mem], time_s=times[mem, i], frame_no=fnos[mem, i])
     torch.cuda.synchronize()
     step_seconds = (_time.perf_counter() - t_loop) / (n - 1)  # every row carries the mean time of a frame step (of ALL clips)
-    refined = None
+    refined = []
     if refine:
-        refined = []
-        starts = refine_window_starts(n, win, stride) if win and n >= win else None
         for ses, hs, mem in zip(sess, group.hip_streams, members):
-            with torch.cuda.stream(hs):
-                if win and n >= win:
-                    refined.append(ses.refine_windows([(j, f) for j in range(len(mem)) for f in starts], win))
-                else:
-                    refined.append(ses.refine(list(range(len(mem)))))
-        refined = [h.result() for h in refined]
-        if win and n >= win:  # a clip's windows are consecutive in its session's request
-            refined = [[_merged_ba(n, r[j * len(starts):(j + 1) * len(starts)], win, stride) for j in range(len(r) // len(starts))] for r in refined]
+            with torch.cuda.stream(hs):  # (one length: ONE request per session)
+                refined.append(_refine_finished(ses, [(j, n, None) for j in range(len(mem))], win, stride))
+        refined = [[ba_of(rh.result()) for rh, ba_of in per] for per in refined]
     seconds = _time.perf_counter() - t_begin
     # what tools/exp/queue_timing.py reads: device time of the frame-0 block of every session (events on its stream), to set beside run_queue's
     run_sequences.last_stats = dict(sessions=len(sess), steps=n - 1, admission_ms=float(sum(a.elapsed_time(b) for a, b in f0_events)), admissions=len(sess))
@@ -1310,19 +1306,9 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                     pending.append(entry)
                     held[g][j] = None
                     finished.append((j, c["n"], entry))
-                windowed = [(j, n, e, refine_window_starts(n, win, stride)) for j, n, e in finished if refine and win and n >= win]
-                if windowed:  # ONE request for all of them, whatever their lengths; a clip's records land in its own pinned buffer
-                    rh = ses.refine_windows([(j, f) for j, _, _, st in windowed for f in st], win, out=[(e[3], len(st)) for _, _, e, st in windowed])
-                    at = 0
-                    for _, n, e, st in windowed:
-                        e[2][5] = (rh, lambda r, at=at, k=len(st), n=n: _merged_ba(n, r[at:at + k], win, stride))
-                        at += len(st)
-                    finished = [x for x in finished if not (win and x[1] >= win)]
-                for n_clip in sorted({n for _, n, _ in finished}) if refine else ():
-                    same = [(j, e) for j, n, e in finished if n == n_clip]
-                    rh = ses.refine([j for j, _ in same], out=[e[3] for _, e in same])
-                    for idx, (_, e) in enumerate(same):
-                        e[2][5] = (rh, lambda r, idx=idx: r[idx])
+                if refine and finished:  # right behind the exports; a clip's records land in its own pinned buffer
+                    for (_, _, e), ba in zip(finished, _refine_finished(ses, [(j, n, e[3]) for j, n, e in finished], win, stride)):
+                        e[2][5] = ba
         steps += 1
         poll()
     for hs in group.hip_streams:
