@@ -232,12 +232,12 @@ VH_API int vh_good_features(vh_ctx* ctx, const uint8_t* im, int w, int h, int st
 VH_API int vh_corner_subpix(vh_ctx* ctx, const uint8_t* im, int w, int h, int stride, float* pts, int n, int win, int max_iter,
                             double eps, void* stream);
 
-/* The detector scratch of this context (response planes, candidate keys, counters, descriptors) for the one-image entries: created by the first
+/* The detector scratch of this context (a block: response planes, candidate keys, counters, descriptors) for the one-image entries: created by the first
  * frame-0 call for the image at hand, or explicitly here -- e.g. before a stream capture, inside which it can be neither allocated nor grown (-6;
  * vh_last_error names this call).  After it, vh_good_features, vh_good_features2, vh_corner_subpix and vh_frame0_init on an image (ROI) of up to
  * max(w x h, the context's max_w x max_h) pixels only queue kernels.  It keeps the chunk size the context has (at least one clip) and does not fix it:
  * the chunking of vh_frame0_init_batch is vh_init_reserve_batch's to set.
- * One case it does not cover: max_corners > 2048 (with min_distance < 1) sorts through a second scratch sized by the budget, which exists only after
+ * One case it does not cover: max_corners > 2048 (with min_distance < 1) sorts through a second block sized by the budget, which exists only after
  * one eager call with that budget; inside a capture such a call returns -6 until then.  (The first-generation detector, a full sort of every pixel,
  * had no such case.) */
 VH_API int vh_init_reserve(vh_ctx* ctx, int w, int h, void* stream);
@@ -572,7 +572,7 @@ VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
 /* (vh_version >= 109) the recovery branch of KLTmain (utils/KLT.py:130-133) inside the session; default OFF: a step then queues exactly the launches it
  * always did and a stream whose coarse stage fails reports klt_flags & 1 and goes on with what the blind fine stage kept.
  * on != 0 (params_host: the matcher's parameters, NULL = defaults) creates everything the branch needs -- a private context of the session's (maximum) frame
- * size, the matcher's scratch for up to 16 pairs, a pinned host record -- so no step allocates.  Every step then, between KLTmain and the bookkeeping:
+ * size, the matcher's scratch for up to 16 pairs, a pinned host block and a device block -- so no step allocates.  Every step then, between KLTmain and the bookkeeping:
  *   - reads {klt_flags, n_cur} of every stream back: ONE small device-to-host copy and ONE hipStreamSynchronize PER STEP, whether a stream failed or not.
  *     The host therefore no longer runs ahead of the device; leave the option off for clips that do not need it.
  *   - for the streams with klt_flags & 1 and n_cur > 0: vh_match_affine_batch(im0, frame, p, n_cur) (at most 16 pairs per call, one call per distinct frame size among them), a second

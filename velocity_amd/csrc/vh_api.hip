@@ -45,7 +45,36 @@ extern "C" VH_API int vh_copy_to_host(void* dst_host, const void* src_dev, size_
 }
 extern "C" VH_API const char* vh_last_error(void) { return g_err; }
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// The device side of a context as ONE walk: sizes only when base is null.  hb: the batch buffer tables (host copies of StreamWS::bufs).
+static size_t ctx_carve(char* base, vh_ctx* c, StreamBufs* hb)
+{
+    VhCarver A(base);
+    // levels >= 1 of a w x h image: a level buffer holds either layout of any level up to its size, dense or bordered (small levels, see VH_LV_PAD)
+    auto levels = [&A](int w, int h, uint8_t** lv) {
+        lv[0] = nullptr;
+        for (int l = 1; l < VH_MAX_LEVELS; l++) {
+            w = (w + 1) / 2; h = (h + 1) / 2;
+            lv[l] = A.take<uint8_t>((size_t)VH_LV_STRIDE(w) * (size_t)(h + 2 * VH_LV_PAD));
+        }
+    };
+    const size_t max_pts = c->max_pts;
+    c->d_ws = A.take<StreamWS>(c->batch); c->d_small = A.take<double>(64);
+    for (int b = 0; b < c->batch; b++) {
+        StreamBufs& B = hb[b];
+        for (int k = 0; k < 2; k++) {
+            B.small0[k] = A.take<uint8_t>((size_t)c->sw * c->sh);
+            levels(c->sw, c->sh, B.small_lv[k]);
+            levels(c->max_w, c->max_h, B.roi_lv[k]);
+        }
+        B.warp = A.take<uint8_t>((size_t)((c->max_w + 3) & ~3) * c->max_h);
+        B.p_small = A.take<float>(2 * max_pts); B.p_coarse = A.take<float>(2 * max_pts);
+        B.v_small = A.take<uint8_t>(max_pts); B.v_coarse = A.take<uint8_t>(max_pts);
+        B.v_all = A.take<uint8_t>(max_pts); B.inl = A.take<uint8_t>(max_pts);
+        B.idx = A.take<int>(max_pts); B.pairs = A.take<float4>(max_pts);
+        B.counts = A.take<int>(VH_RANSAC_ITERS); B.order = A.take<int>(max_pts);
+    }
+    return A.bytes();
+}
 
 extern "C" VH_API int vh_ctx_create(vh_ctx** out, int batch, int max_w, int max_h, int max_pts)
 {
@@ -54,67 +83,17 @@ extern "C" VH_API int vh_ctx_create(vh_ctx** out, int batch, int max_w, int max_
     if (!c) return vh_fail(-1, "vh_ctx_create: out of host memory");
     c->batch = batch; c->max_w = max_w; c->max_h = max_h; c->max_pts = max_pts;
     c->sw = (int)lrint(max_w * 0.25); c->sh = (int)lrint(max_h * 0.25);
-    // carve plan (computed twice: size, then pointers)
-    StreamBufs* hb = new StreamBufs[batch];
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    // a level buffer holds either layout of any level up to w x h: dense, or bordered (small levels, see VH_LV_PAD)
-    auto lv_bytes = [](int w, int h) { return (size_t)VH_LV_STRIDE(w) * (size_t)(h + 2 * VH_LV_PAD); };
-    size_t ws_off = carve(sizeof(StreamWS) * batch);
-    size_t small_off = carve(sizeof(double) * 64);
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 1) {
-            c->arena_bytes = off;
-            hipError_t e = hipMalloc((void**)&c->arena, off);
-            if (e != hipSuccess) { delete[] hb; delete c; vh_set_error("hipMalloc(arena)", e, __FILE__, __LINE__); return (int)e; }
-            e = hipMemset(c->arena, 0, off);
-            if (e != hipSuccess) { (void)hipFree(c->arena); delete[] hb; delete c; vh_set_error("hipMemset(arena)", e, __FILE__, __LINE__); return (int)e; }
-            off = 0;
-            carve(sizeof(StreamWS) * batch);
-            carve(sizeof(double) * 64);
-        }
-        char* base = pass ? c->arena : nullptr;
-        for (int b = 0; b < batch; b++) {
-            StreamBufs& B = hb[b];
-            for (int k = 0; k < 2; k++) {
-                B.small0[k] = (uint8_t*)(base + carve((size_t)c->sw * c->sh));
-                int w = c->sw, h = c->sh;
-                for (int l = 1; l < VH_MAX_LEVELS; l++) {
-                    w = (w + 1) / 2; h = (h + 1) / 2;
-                    B.small_lv[k][l] = (uint8_t*)(base + carve(lv_bytes(w, h)));
-                }
-                B.small_lv[k][0] = nullptr;
-                w = max_w; h = max_h;
-                for (int l = 1; l < VH_MAX_LEVELS; l++) {
-                    w = (w + 1) / 2; h = (h + 1) / 2;
-                    B.roi_lv[k][l] = (uint8_t*)(base + carve(lv_bytes(w, h)));
-                }
-                B.roi_lv[k][0] = nullptr;
-            }
-            B.warp = (uint8_t*)(base + carve((size_t)((max_w + 3) & ~3) * max_h));
-            B.p_small = (float*)(base + carve(sizeof(float) * 2 * max_pts));
-            B.p_coarse = (float*)(base + carve(sizeof(float) * 2 * max_pts));
-            B.v_small = (uint8_t*)(base + carve(max_pts));
-            B.v_coarse = (uint8_t*)(base + carve(max_pts));
-            B.v_all = (uint8_t*)(base + carve(max_pts));
-            B.inl = (uint8_t*)(base + carve(max_pts));
-            B.idx = (int*)(base + carve(sizeof(int) * max_pts));
-            B.pairs = (float4*)(base + carve(sizeof(float4) * max_pts));
-            B.counts = (int*)(base + carve(sizeof(int) * VH_RANSAC_ITERS));
-            B.order = (int*)(base + carve(sizeof(int) * max_pts));
-        }
-    }
-    c->d_ws = (StreamWS*)(c->arena + ws_off);
-    c->d_small = (double*)(c->arena + small_off);
+    c->h_bufs = new StreamBufs[batch];  // (from here on a failure goes through vh_ctx_destroy, which releases whatever the context holds by then)
+    int r = c->arena.reserve(ctx_carve(nullptr, c, c->h_bufs), nullptr, "arena", "create the context before capturing", true);
+    if (r) { vh_ctx_destroy(c); return r; }
+    ctx_carve(c->arena.p, c, c->h_bufs);
     hipError_t e = hipSuccess;
     for (int b = 0; b < batch && e == hipSuccess; b++) {
-        e = hipMemcpy(&c->d_ws[b].bufs, &hb[b], sizeof(StreamBufs), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(hb[b].v_all, 1, max_pts);
+        e = hipMemcpy(&c->d_ws[b].bufs, &c->h_bufs[b], sizeof(StreamBufs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(c->h_bufs[b].v_all, 1, max_pts);
     }
-    if (e != hipSuccess) { (void)hipFree(c->arena); delete[] hb; delete c; vh_set_error("hipMemcpy(bufs)", e, __FILE__, __LINE__); return (int)e; }
-    const int mr = vh_subpix_masks_create(&c->subpix_mask);
-    if (mr) { (void)hipFree(c->arena); delete[] hb; delete c; return mr; }
-    c->h_bufs = hb;
+    if (e != hipSuccess) { vh_set_error("hipMemcpy(bufs)", e, __FILE__, __LINE__); vh_ctx_destroy(c); return (int)e; }
+    if ((r = vh_subpix_masks_create(&c->subpix_mask))) { vh_ctx_destroy(c); return r; }
     *out = c;
     return 0;
 }
@@ -125,7 +104,7 @@ extern "C" VH_API void vh_ctx_destroy(vh_ctx* c)
     vh_ba_graph_cache_free(c->ba_graphs);
     vh_init_scratch_free(c);
     vh_match_scratch_free(c);
-    (void)hipFree(c->arena);
+    c->arena.release();
     if (c->bound_ev) (void)hipEventDestroy(c->bound_ev);
     for (int k = 0; k < 2 * c->prof_cap; k++) (void)hipEventDestroy(c->prof_ev[k]);
     delete[] c->prof_ev;

@@ -204,7 +204,7 @@ static void host_bounding_rect(const float* q, int n, int imw, int imh, int bx, 
 #define F0B_SEL_MAX 2048 // max_corners up to this: selected keys sorted in LDS; above: rocPRIM segmented sort
 #define F0B_WIN 2048     // k_f0b_spread: candidates per window (sorted in LDS)
 #define F0B_EMPTY 0xffffffffu
-static const size_t F0B_BUDGET = (size_t)1 << 30;  // scratch of a context sized by the first call (include/velocity_hip.h)
+static const size_t F0B_BUDGET = (size_t)1 << 30;  // the scratch block of a context sized by the first call (include/velocity_hip.h)
 
 struct F0Clip {
     const uint8_t* roi;        // frame + boxb[2] * stride + boxb[0]
@@ -616,91 +616,76 @@ __global__ __launch_bounds__(256) void k_f0b_world(const F0Clip* tab, const F0Ca
     frame0_world_row(i, n, cam[clip].K, tab[clip].boxa, R_out + 9 * b, t_out + 3 * b, p_out + b * cap * 2, p3_out + b * cap * 3, vp_out + b * cap);
 }
 
-static void batch_sel_release(InitBatchScratch& B)
-{
-    (void)hipFree(B.sel); (void)hipFree(B.sorted); (void)hipFree(B.seg); (void)hipFree(B.sort_tmp);
-    B.sel = B.sorted = nullptr; B.seg = nullptr; B.sort_tmp = nullptr; B.sort_bytes = B.sel_cap = 0;
-}
-static void batch_release(InitBatchScratch& B)
-{
-    batch_sel_release(B);
-    (void)hipFree(B.resp); (void)hipFree(B.keys); (void)hipFree(B.cnt); (void)hipFree(B.info); (void)hipFree(B.tab); (void)hipFree(B.cam); (void)hipFree(B.shared);
-    (void)hipFree(B.pose);
-    memset(&B, 0, sizeof(B));
-}
-
 // what a caller does ahead of a capture so that the entry it called finds its scratch (the -6 message names it)
 static const char* const F0B_RESERVE_ONE = "call vh_init_reserve(ctx, w, h) before capturing";
 static const char* const F0B_RESERVE_BATCH = "call vh_init_reserve_batch(ctx, nb, w, h) before capturing";
 static const char* const F0B_RESERVE_MATCH = "call vh_match_reserve(ctx, w, h, params) or vh_match_reserve_batch before capturing";
 static const char* const F0B_RESERVE_SORT = "make one eager call with this max_corners before capturing";
 
-// allocation or growth of the scratch: never inside a capture; when kernels queued earlier may still use it (had), after a stream synchronisation
-static int batch_grow_guard(bool had, hipStream_t s, const char* remedy)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "frame-0 scratch must grow inside a stream capture: %s", remedy);
-        return vh_fail(-6, msg);
-    }
-    if (had) VH_CHECK(hipStreamSynchronize(s));
-    return 0;
-}
-
 static size_t batch_clip_bytes(size_t px) { return 12 * px + 24 + sizeof(F0Clip) + sizeof(F0Cam) + sizeof(PoseJob); }
 
-// scratch for chunks of up to `clips` clips and `pix` ROI pixels in all (never shrinks)
+// the two blocks of the scratch as one walk each (sizes only when base is null)
+static size_t batch_carve(char* base, int clips, size_t pix, InitBatchScratch& B)
+{
+    VhCarver A(base);
+    const size_t tab_n = (size_t)(clips + F0B_PIECE - 1) / F0B_PIECE * F0B_PIECE;
+    B.resp = A.take<float>(pix); B.keys = A.take<unsigned long long>(pix);
+    B.cnt = A.take<unsigned>((size_t)4 * clips); B.info = A.take<int>((size_t)2 * clips);
+    B.tab = A.take<F0Clip>(tab_n); B.cam = A.take<F0Cam>(tab_n);
+    B.shared = A.take<F0Shared>(1); B.pose = A.take<PoseJob>(clips);
+    return A.bytes();
+}
+static size_t batch_sel_carve(char* base, int clips, size_t keys, size_t sort_bytes, InitBatchScratch& B)
+{
+    VhCarver A(base);
+    B.sel = A.take<unsigned long long>(keys); B.sorted = A.take<unsigned long long>(keys);
+    B.seg = A.take<int>((size_t)2 * clips); B.sort_tmp = A.take<char>(sort_bytes);  // rocPRIM's temporary storage, last
+    B.sort_bytes = sort_bytes; B.sel_cap = keys;
+    return A.bytes();
+}
+
+// scratch for chunks of up to `clips` (>= 1) clips and `pix` ROI pixels in all (never shrinks): a refused growth leaves it as it was, a failed one empty (explicit_size kept)
 static int batch_reserve(vh_ctx* c, int clips, size_t pix, hipStream_t s, const char* remedy)
 {
     InitBatchScratch& B = c->init_batch;
     if (B.clips_cap >= clips && B.pix_cap >= pix) return 0;
-    int r = batch_grow_guard(B.clips_cap > 0, s, remedy);
-    if (r) return r;
     clips = clips > B.clips_cap ? clips : B.clips_cap;
     pix = pix > B.pix_cap ? pix : B.pix_cap;
-    const int expl = B.explicit_size;
-    batch_release(B);
-    const int tab_n = (clips + F0B_PIECE - 1) / F0B_PIECE * F0B_PIECE;
-    VH_CHECK(hipMalloc((void**)&B.resp, pix * 4));
-    VH_CHECK(hipMalloc((void**)&B.keys, pix * 8));
-    VH_CHECK(hipMalloc((void**)&B.cnt, sizeof(unsigned) * 4 * clips));
-    VH_CHECK(hipMalloc((void**)&B.info, sizeof(int) * 2 * clips));
-    VH_CHECK(hipMalloc(&B.tab, sizeof(F0Clip) * tab_n));
-    VH_CHECK(hipMalloc(&B.cam, sizeof(F0Cam) * tab_n));
-    VH_CHECK(hipMalloc(&B.shared, sizeof(F0Shared)));
-    VH_CHECK(hipMalloc((void**)&B.pose, sizeof(PoseJob) * clips));
-    B.clips_cap = clips;
-    B.pix_cap = pix;
-    B.explicit_size = expl;
-    return 0;
+    InitBatchScratch sized;
+    const size_t had = B.main.bytes;
+    const int r = B.main.reserve(batch_carve(nullptr, clips, pix, sized), s, "frame-0 scratch", remedy);
+    if (r && B.main.p) return r;
+    if (r) clips = 0, pix = 0;
+    // The sort block (its segment table is sized by clips_cap) goes only with a main block that reserve() replaced: capture check made, stream waited for.  Where the
+    // rounded size still fitted, reserve() did nothing and no offset moved: the sort block stays, and a new clips_cap makes batch_sel_reserve lay it out again.
+    if (B.main.bytes != had) { B.sort.release(); batch_sel_carve(nullptr, 0, 0, 0, B); }
+    if (clips != B.clips_cap) B.sel_cap = 0;
+    B.clips_cap = clips; B.pix_cap = pix;
+    batch_carve(B.main.p, clips, pix, B);
+    return r;
 }
 
-// the segmented-sort route's buffers for max_corners above F0B_SEL_MAX
+// the segmented-sort route's block for max_corners above F0B_SEL_MAX
 static int batch_sel_reserve(vh_ctx* c, int max_corners, hipStream_t s)
 {
     InitBatchScratch& B = c->init_batch;
     const size_t need = (size_t)B.clips_cap * max_corners;
     if (B.sel_cap >= need) return 0;
     if (need > 0x7fffffffu) return vh_fail(-1, "frame-0 detector: clips x max_corners exceeds the segmented sort's range");
-    int r = batch_grow_guard(B.sel_cap > 0, s, F0B_RESERVE_SORT);
-    if (r) return r;
-    batch_sel_release(B);
-    VH_CHECK(hipMalloc((void**)&B.sel, need * 8));
-    VH_CHECK(hipMalloc((void**)&B.sorted, need * 8));
-    VH_CHECK(hipMalloc((void**)&B.seg, sizeof(int) * 2 * B.clips_cap));
-    size_t bytes = 0;
-    VH_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, B.sel, B.sorted, (unsigned)need, (unsigned)B.clips_cap, B.seg, B.seg + B.clips_cap, 0, 64, 0));
-    VH_CHECK(hipMalloc(&B.sort_tmp, bytes));
-    B.sort_bytes = bytes;
-    B.sel_cap = need;
-    return 0;
+    size_t bytes = 0;  // (a size query reads none of its pointers)
+    VH_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned)need,
+                                                     (unsigned)B.clips_cap, (int*)nullptr, (int*)nullptr, 0, 64, 0));
+    InitBatchScratch sized;
+    const int r = B.sort.reserve(batch_sel_carve(nullptr, B.clips_cap, need, bytes, sized), s, "frame-0 scratch", F0B_RESERVE_SORT);
+    if (r && B.sort.p) return r;  // (refused; a block that already held the rounded size was kept and is laid out again: it holds nothing between calls)
+    batch_sel_carve(B.sort.p, B.clips_cap, r ? 0 : need, r ? 0 : bytes, B);
+    return r;
 }
 
 void vh_init_scratch_free(vh_ctx* c)
 {
     if (!c) return;
-    batch_release(c->init_batch);
+    c->init_batch.main.release(); c->init_batch.sort.release();
     (void)hipFree(c->subpix_mask);
     c->subpix_mask = nullptr;
 }
@@ -885,7 +870,7 @@ static int frame0_batch_run(vh_ctx* c, int nb, const uint8_t* const* frames_host
     hipStream_t s = bound_.s;
     InitBatchScratch& B = c->init_batch;
     // (the spacing stage needs no scratch of its own: its occupancy grid reuses the clip's response plane)
-    if (B.explicit_size) {  // chunks of the reserved size; grown only for a ROI larger than the whole scratch
+    if (B.explicit_size && B.clips_cap > 0) {  // chunks of the reserved size; grown only for a ROI larger than the whole scratch (a scratch lost to a failed growth is sized like a first call's)
         r = batch_reserve(c, B.clips_cap, max_px, s, remedy);
     } else {                // as many clips per chunk as the budget holds
         const size_t fit = F0B_BUDGET / batch_clip_bytes(max_px);

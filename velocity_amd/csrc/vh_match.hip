@@ -261,15 +261,13 @@ __global__ __launch_bounds__(256) void k_match_info(const MatchJob* tab)
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 struct MatchScratch {
-    char* base;
-    size_t bytes;
+    VhDeviceBlock block;  // laid out by match_carve
     vh_match_stages last;  // what vh_match_stage_ptrs hands out
     int have_last;
 };
 
 static const vh_match_params MATCH_DEFAULTS = {5, 500, 1000, 5, 50, 50, 4, 5, 10, 0.01};
 
-static inline size_t match_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static double match_scale(int l) { return pow(2.0, -l / 4.0); }
 static void match_dims(int w, int h, int l, int* wl, int* hl)
 {
@@ -320,18 +318,17 @@ struct MatchLayout {
 // Lays the scratch of nb pairs out (base may be null: sizes only) and fills the jobs' pointers (J, X: nb entries each, may be null).
 static MatchLayout match_carve(char* base, int nb, int w, int h, const vh_match_params& P, MatchJob* J, MatchPairBufs* X)
 {
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { char* p = base ? base + off : nullptr; off = match_align(off + bytes); return p; };
+    VhCarver A(base);
     const int qcap = P.levels * P.query_per_level, tcap = P.levels * P.train_per_level;
     MatchLayout Y;
     Y.level_px = 0;
-    Y.cnt = (int*)carve(sizeof(int) * 2 * VH_MATCH_MAX_LEVELS * nb);
-    Y.jobs = (MatchJob*)carve(sizeof(MatchJob) * nb);
-    Y.rjobs = (RansacJob*)carve(sizeof(RansacJob) * nb);
+    Y.cnt = A.take<int>((size_t)2 * VH_MATCH_MAX_LEVELS * nb);
+    Y.jobs = A.take<MatchJob>(nb);
+    Y.rjobs = A.take<RansacJob>(nb);
     for (int b = 0; b < nb; b++) {
         int* cnt = Y.cnt + (size_t)b * 2 * VH_MATCH_MAX_LEVELS;
-        int* roi = (int*)carve(sizeof(int) * 4);
-        int* small = (int*)carve(sizeof(int) * 4);
+        int* roi = A.take<int>(4);
+        int* small = A.take<int>(4);
         for (int img = 0; img < 2; img++) {
             const int budget = img ? P.train_per_level : P.query_per_level;
             for (int l = 0; l < P.levels; l++) {
@@ -339,10 +336,10 @@ static MatchLayout match_carve(char* base, int nb, int w, int h, const vh_match_
                 match_dims(w, h, l, &wl, &hl);
                 const size_t px = (size_t)wl * hl;
                 if (b == 0) Y.level_px += px;
-                uint8_t* image = (uint8_t*)carve(l ? px : 0);
-                uint8_t* mask = (uint8_t*)carve(px);
-                unsigned short* box = (unsigned short*)carve(2 * px);
-                float* kp = (float*)carve(sizeof(float) * 2 * budget);
+                uint8_t* image = A.take<uint8_t>(l ? px : 0);  // (level 0 is the caller's frame: a take of 0 moves nothing)
+                uint8_t* mask = A.take<uint8_t>(px);
+                unsigned short* box = A.take<unsigned short>(px);
+                float* kp = A.take<float>((size_t)2 * budget);
                 if (J) {
                     MatchLevel& L = J[b].lv[img][l];
                     if (l) { L.img = image; L.stride = wl; }
@@ -352,17 +349,14 @@ static MatchLayout match_carve(char* base, int nb, int w, int h, const vh_match_
                 }
             }
         }
-        float* pos0 = (float*)carve(sizeof(float) * 2 * qcap);
-        float* pos1 = (float*)carve(sizeof(float) * 2 * tcap);
-        uint8_t* desc0 = (uint8_t*)carve((size_t)32 * qcap);
-        uint8_t* desc1 = (uint8_t*)carve((size_t)32 * tcap);
-        int* nn = (int*)carve(sizeof(int) * 4 * qcap);
-        uint8_t* good = (uint8_t*)carve(qcap);
-        float* from = (float*)carve(sizeof(float) * 2 * qcap);
-        float* to = (float*)carve(sizeof(float) * 2 * qcap);
-        int* idx = (int*)carve(sizeof(int) * qcap);
-        float4* rpairs = (float4*)carve(sizeof(float4) * qcap);
-        int* counts = (int*)carve(sizeof(int) * VH_RANSAC_ITERS);
+        float *pos0 = A.take<float>((size_t)2 * qcap), *pos1 = A.take<float>((size_t)2 * tcap);
+        uint8_t *desc0 = A.take<uint8_t>((size_t)32 * qcap), *desc1 = A.take<uint8_t>((size_t)32 * tcap);
+        int* nn = A.take<int>((size_t)4 * qcap);
+        uint8_t* good = A.take<uint8_t>(qcap);
+        float *from = A.take<float>((size_t)2 * qcap), *to = A.take<float>((size_t)2 * qcap);
+        int* idx = A.take<int>(qcap);
+        float4* rpairs = A.take<float4>(qcap);
+        int* counts = A.take<int>(VH_RANSAC_ITERS);
         if (J) {
             MatchJob& Q = J[b];
             Q.levels = P.levels; Q.budget[0] = P.query_per_level; Q.budget[1] = P.train_per_level;
@@ -371,7 +365,7 @@ static MatchLayout match_carve(char* base, int nb, int w, int h, const vh_match_
         }
         if (X) { X[b].status = small + 1; X[b].m = small + 2; X[b].bound = small + 3; X[b].idx = idx; X[b].rpairs = rpairs; X[b].counts = counts; }
     }
-    Y.bytes = off;
+    Y.bytes = A.bytes();
     return Y;
 }
 
@@ -379,7 +373,7 @@ void vh_match_scratch_free(vh_ctx* c)
 {
     if (!c || !c->match) return;
     MatchScratch* S = static_cast<MatchScratch*>(c->match);
-    (void)hipFree(S->base);
+    S->block.release();
     delete S;
     c->match = nullptr;
 }
@@ -390,29 +384,12 @@ static int match_reserve(vh_ctx* c, int nb, int w, int h, const vh_match_params&
     const MatchLayout Y = match_carve(nullptr, nb, w, h, P, nullptr, nullptr);
     int r = vh_detect_reserve(c, 2 * P.levels * nb, Y.level_px * nb, s);  // the detector's own scratch: one pass over every level image
     if (r) return r;
-    if (!c->match) {
-        MatchScratch* S = new (std::nothrow) MatchScratch();
-        if (!S) return vh_fail(-1, "vh_match: out of host memory");
-        memset(S, 0, sizeof(*S));
-        c->match = S;
-    }
+    if (!c->match && !(c->match = new (std::nothrow) MatchScratch())) return vh_fail(-1, "vh_match: out of host memory");
     MatchScratch* S = static_cast<MatchScratch*>(c->match);
-    const size_t need = Y.bytes;
-    if (need <= S->bytes) return 0;
-    if (S->base) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return vh_fail(-6, "the matching scratch must grow inside a stream capture: call vh_match_reserve(ctx, w, h, params) or vh_match_reserve_batch "
-                               "before capturing");
-        VH_CHECK(hipStreamSynchronize(s));
-        (void)hipFree(S->base);
-        S->base = nullptr;
-        S->bytes = 0;
-        S->have_last = 0;
-    }
-    VH_CHECK(hipMalloc((void**)&S->base, need));
-    S->bytes = need;
-    return 0;
+    const size_t had = S->block.bytes;
+    r = S->block.reserve(Y.bytes, s, "the matching scratch", "call vh_match_reserve(ctx, w, h, params) or vh_match_reserve_batch before capturing");
+    if (S->block.bytes != had) S->have_last = 0;  // (the stage pointers of the last call died with the old block)
+    return r;
 }
 
 extern "C" VH_API int vh_match_reserve_batch(vh_ctx* c, int nb, int w, int h, const vh_match_params* params_host, void* stream)
@@ -470,7 +447,7 @@ static int match_run(vh_ctx* c, int nb, const uint8_t* const* im1, const uint8_t
     std::vector<RansacJob> R((size_t)nb);
     memset(J.data(), 0, sizeof(MatchJob) * nb);
     memset(R.data(), 0, sizeof(RansacJob) * nb);
-    const MatchLayout Y = match_carve(S->base, nb, w, h, P, J.data(), X.data());
+    const MatchLayout Y = match_carve(S->block.p, nb, w, h, P, J.data(), X.data());
     const StreamBufs& B = c->h_bufs[0];
     for (int b = 0; b < nb; b++) {
         MatchJob& Q = J[b];

@@ -35,14 +35,12 @@ struct SessFallback {
     int on, chunk;
     vh_match_params params;
     vh_ctx* ctx;        // batch 1, the session's (maximum) frame size, max_pts >= max(N0, levels x query_per_level)
-    SessFbRec* h_rec;   // pinned [batch]
-    SessFbRec* d_rec;   // [batch]
-    double* d_M;        // [chunk][6]
-    int* d_info;        // [chunk][4]
-    uint8_t* d_inl;     // [chunk][levels x query_per_level]
-    double* h_M;        // pinned, as d_M
-    int* h_info;        // pinned, as d_info
-    int inl_cap;        // bytes of d_inl
+    VhPinnedBlock host;  // h_rec, h_M, h_info
+    VhDeviceBlock dev;   // d_rec, d_M, d_info, d_inl: both laid out by sess_fb_carve for (batch, chunk, qcap) and regrown whole when qcap grows
+    SessFbRec *h_rec, *d_rec;  // [batch]
+    double *h_M, *d_M;         // [chunk][6]
+    int *h_info, *d_info;      // [chunk][4]
+    uint8_t* d_inl;            // [chunk][levels x query_per_level]
     int* counts;        // host [batch][2]: the recovery ran, it found a model
 };
 
@@ -50,7 +48,7 @@ struct vh_session {
     vh_ctx* ctx;
     int batch, N0, nhist, w, h, msv_frame, k_is_f32;
     vh_lk_params coarse, fine;
-    char* arena;
+    VhDeviceBlock arena;  // laid out by sess_carve
     SessStream* d_ss;
     SessStream* h_ss;  // host mirror of the pointer fields and of every slot's camera (w, h, K: vh_session_set_camera) and row stride
     IngestJob* d_ingest;  // [batch] descriptors of the fused BGR ingest
@@ -65,7 +63,6 @@ struct vh_session {
     char* h_inited;       // per slot: vh_session_init has run
 };
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 #define SESS_CHECK() VH_CHECK(hipGetLastError())
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -316,6 +313,30 @@ __global__ void k_sess_camera(SessStream* ss, SessCamera cam)
 // fcnMSV1_t (vidExample.py:155-160) can fire for this session: the predicate that both sizes its scratch and gates its launch
 static inline bool sess_msv_fires(int msv_frame, int nhist) { return msv_frame >= 1 && msv_frame + 1 <= 2048 && msv_frame < nhist; }
 
+// The device side of a session as ONE walk (sizes only when base is null): the pointer fields of the host mirror h_ss and of the session itself.
+static size_t sess_carve(char* base, vh_session* s)
+{
+    VhCarver A(base);
+    const size_t n0 = s->N0, nhist = s->nhist, small = (size_t)lrint(s->w * 0.25) * (size_t)lrint(s->h * 0.25);
+    const size_t msv_rows = sess_msv_fires(s->msv_frame, s->nhist) ? s->msv_frame + 1 : 1;  // one row when fcnMSV1_t can never fire (a 'never' sentinel sizes nothing)
+    s->d_ss = A.take<SessStream>(s->batch); s->d_ingest = A.take<IngestJob>(s->batch);
+    for (int b = 0; b < s->batch; b++) {
+        SessStream& S = s->h_ss[b];
+        S.vg = A.take<uint8_t>(n0); S.vp = A.take<uint8_t>(n0);
+        S.p_cur = A.take<float>(2 * n0); S.ids = A.take<int>(n0);
+        S.p3 = A.take<double>(3 * n0); S.P = A.take<float>(5 * n0 * nhist);
+        S.B = A.take<float>(14 * nhist); S.S = A.take<float>(9 * nhist);
+        S.p_all = A.take<float>(2 * n0); S.v = A.take<uint8_t>(n0);
+        S.sel_p = A.take<int>(n0); S.sel_pw = A.take<int>(n0);
+        S.p_proj = A.take<double>(2 * n0);
+        S.msv_U = A.take<double>(3 * msv_rows * n0); S.msv_b0 = A.take<double>(3 * n0);
+        S.small[0] = A.take<uint8_t>(small); S.small[1] = A.take<uint8_t>(small);
+    }
+    s->d_anc_mask = A.take<uint8_t>(s->batch * n0);  // (zero = no anchors: the arena is cleared, and the clear is checked)
+    s->d_anc_xyz = A.take<double>(3 * s->batch * n0);
+    return A.bytes();
+}
+
 extern "C" VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, int nhist, int w, int h, const double* K_host,
                                         int k_is_float32, const vh_lk_params* coarse, const vh_lk_params* fine, int msv_frame)
 {
@@ -329,41 +350,11 @@ extern "C" VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, i
     if (!s) return vh_fail(-1, "out of host memory");
     s->ctx = ctx; s->batch = ctx->batch; s->N0 = n0; s->nhist = nhist; s->w = w; s->h = h; s->msv_frame = msv_frame; s->k_is_f32 = k_is_float32 ? 1 : 0;
     s->coarse = *coarse; s->fine = *fine;
-    memset(&s->fb, 0, sizeof(s->fb));
-    const int dw = (int)lrint(w * 0.25), dh = (int)lrint(h * 0.25);
-    s->h_ss = new SessStream[s->batch];
-    memset(s->h_ss, 0, sizeof(SessStream) * s->batch);
-    s->h_frame = new int[s->batch]();
-    s->h_nanchor = new int[s->batch]();
-    s->h_inited = new char[s->batch]();
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 1) {
-            hipError_t e = hipMalloc((void**)&s->arena, off);
-            if (e != hipSuccess) { delete[] s->h_ss; delete[] s->h_frame; delete[] s->h_nanchor; delete[] s->h_inited; delete s; vh_set_error("hipMalloc(session)", e, __FILE__, __LINE__); return (int)e; }
-            (void)hipMemset(s->arena, 0, off);
-            off = 0;
-        }
-        char* base = pass ? s->arena : nullptr;
-        s->d_ss = (SessStream*)(base + carve(sizeof(SessStream) * s->batch));
-        s->d_ingest = (IngestJob*)(base + carve(sizeof(IngestJob) * s->batch));
-        for (int b = 0; b < s->batch; b++) {
-            SessStream& S = s->h_ss[b];
-            S.vg = (uint8_t*)(base + carve(n0)); S.vp = (uint8_t*)(base + carve(n0));
-            S.p_cur = (float*)(base + carve(sizeof(float) * 2 * n0)); S.ids = (int*)(base + carve(sizeof(int) * n0));
-            S.p3 = (double*)(base + carve(sizeof(double) * 3 * n0));
-            S.P = (float*)(base + carve(sizeof(float) * 5 * (size_t)n0 * nhist));
-            S.B = (float*)(base + carve(sizeof(float) * 14 * nhist)); S.S = (float*)(base + carve(sizeof(float) * 9 * nhist));
-            S.p_all = (float*)(base + carve(sizeof(float) * 2 * n0)); S.v = (uint8_t*)(base + carve(n0));
-            S.sel_p = (int*)(base + carve(sizeof(int) * n0)); S.sel_pw = (int*)(base + carve(sizeof(int) * n0));
-            S.p_proj = (double*)(base + carve(sizeof(double) * 2 * n0));
-            S.msv_U = (double*)(base + carve(sizeof(double) * 3 * (size_t)(sess_msv_fires(msv_frame, nhist) ? msv_frame + 1 : 1) * n0));  /* one row when fcnMSV1_t can never fire (a 'never' sentinel must not size the buffer) */ S.msv_b0 = (double*)(base + carve(sizeof(double) * 3 * n0));
-            S.small[0] = (uint8_t*)(base + carve((size_t)dw * dh)); S.small[1] = (uint8_t*)(base + carve((size_t)dw * dh));
-        }
-        s->d_anc_mask = (uint8_t*)(base + carve((size_t)s->batch * n0));  // (zero = no anchors: the arena is cleared)
-        s->d_anc_xyz = (double*)(base + carve(sizeof(double) * 3 * (size_t)s->batch * n0));
-    }
+    s->h_ss = new SessStream[s->batch]();
+    s->h_frame = new int[s->batch](); s->h_nanchor = new int[s->batch](); s->h_inited = new char[s->batch]();  // (from here on a failure goes through vh_session_destroy)
+    const int r = s->arena.reserve(sess_carve(nullptr, s), nullptr, "session", "create the session before capturing", true);
+    if (r) { vh_session_destroy(s); return r; }
+    sess_carve(s->arena.p, s);
     for (int b = 0; b < s->batch; b++) {
         SessStream& S = s->h_ss[b];
         SessStream* d = s->d_ss + b;
@@ -382,16 +373,23 @@ extern "C" VH_API int vh_session_create(vh_session** out, vh_ctx* ctx, int n0, i
         M.nf = msv_frame + 1; M.max_iter = 1000; M.f32_rays = s->k_is_f32;  // P is float32 always; K as the caller holds it
         M.U = S.msv_U; M.b0 = S.msv_b0; M.x_out = d->msv_x; M.info_out = d->msv_info;
     }
-    hipError_t e = hipMemcpy(s->d_ss, s->h_ss, sizeof(SessStream) * s->batch, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(s->arena); delete[] s->h_ss; delete[] s->h_frame; delete[] s->h_nanchor; delete[] s->h_inited; delete s; vh_set_error("hipMemcpy(session)", e, __FILE__, __LINE__); return (int)e; }
+    const hipError_t e = hipMemcpy(s->d_ss, s->h_ss, sizeof(SessStream) * s->batch, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { vh_set_error("hipMemcpy(session)", e, __FILE__, __LINE__); vh_session_destroy(s); return (int)e; }
     *out = s;
     return 0;
 }
 
+// The recovery's two blocks for `chunk` failed streams per matcher call and qcap query keypoints per pair: sizes only when the carvers have no base.
+static void sess_fb_carve(VhCarver& H, VhCarver& D, SessFallback& F, int batch, int chunk, int qcap)
+{
+    F.h_rec = H.take<SessFbRec>(batch); F.h_M = H.take<double>(6 * (size_t)chunk); F.h_info = H.take<int>(4 * (size_t)chunk);
+    F.d_rec = D.take<SessFbRec>(batch); F.d_M = D.take<double>(6 * (size_t)chunk); F.d_info = D.take<int>(4 * (size_t)chunk);
+    F.d_inl = D.take<uint8_t>((size_t)qcap * chunk);
+}
+
 static void sess_fb_release(SessFallback& F)
 {
-    (void)hipFree(F.d_rec); (void)hipFree(F.d_M); (void)hipFree(F.d_info); (void)hipFree(F.d_inl);
-    (void)hipHostFree(F.h_rec); (void)hipHostFree(F.h_M); (void)hipHostFree(F.h_info);
+    F.dev.release(); F.host.release();
     if (F.ctx) vh_ctx_destroy(F.ctx);
     delete[] F.counts;
     memset(&F, 0, sizeof(F));
@@ -410,6 +408,7 @@ extern "C" VH_API int vh_session_set_fallback(vh_session* s, int on, const vh_ma
     if (params_host) P = *params_host;
     if (P.levels < 1 || P.levels > 8 || P.query_per_level < 1 || P.query_per_level > 2048) return vh_fail(-1, "vh_session_set_fallback: bad matcher parameters");
     const int qcap = P.levels * P.query_per_level, pts = s->N0 > qcap ? s->N0 : qcap;
+    F.on = 0;  // off until everything below is there: a call that fails on the way leaves the recovery off and nothing half-made
     if (F.ctx && F.ctx->max_pts < pts) {  // a larger query budget than the context was made for
         VH_CHECK(hipDeviceSynchronize());
         vh_ctx_destroy(F.ctx);
@@ -418,23 +417,15 @@ extern "C" VH_API int vh_session_set_fallback(vh_session* s, int on, const vh_ma
     int r = 0;
     if (!F.ctx && (r = vh_ctx_create(&F.ctx, 1, s->w, s->h, pts))) return r;
     if ((r = vh_match_reserve_batch(F.ctx, chunk, s->w, s->h, &P, nullptr))) return r;
-    if (!F.h_rec) {
-        F.counts = new int[2 * (size_t)s->batch]();
-        VH_CHECK(hipHostMalloc((void**)&F.h_rec, sizeof(SessFbRec) * s->batch, hipHostMallocDefault));
-        VH_CHECK(hipHostMalloc((void**)&F.h_M, sizeof(double) * 6 * chunk, hipHostMallocDefault));
-        VH_CHECK(hipHostMalloc((void**)&F.h_info, sizeof(int) * 4 * chunk, hipHostMallocDefault));
-        VH_CHECK(hipMalloc((void**)&F.d_rec, sizeof(SessFbRec) * s->batch));
-        VH_CHECK(hipMalloc((void**)&F.d_M, sizeof(double) * 6 * chunk));
-        VH_CHECK(hipMalloc((void**)&F.d_info, sizeof(int) * 4 * chunk));
-    }
-    if (F.inl_cap < qcap * chunk) {
-        if (F.d_inl) { VH_CHECK(hipDeviceSynchronize()); (void)hipFree(F.d_inl); F.d_inl = nullptr; F.inl_cap = 0; }
-        VH_CHECK(hipMalloc((void**)&F.d_inl, (size_t)qcap * chunk));
-        F.inl_cap = qcap * chunk;
-    }
-    F.params = P;
-    F.chunk = chunk;
-    F.on = 1;
+    if (!F.counts) F.counts = new int[2 * (size_t)s->batch]();
+    VhCarver hs(nullptr), ds(nullptr);
+    sess_fb_carve(hs, ds, F, s->batch, chunk, qcap);  // sizes; the pointers stay null unless both blocks are there (the recovery is off)
+    if (F.dev.p && ds.bytes() > F.dev.bytes) VH_CHECK(hipDeviceSynchronize());
+    static const char* const remedy = "call vh_session_set_fallback before capturing";
+    if ((r = F.host.reserve(hs.bytes(), nullptr, "the recovery scratch", remedy)) || (r = F.dev.reserve(ds.bytes(), nullptr, "the recovery scratch", remedy))) return r;
+    VhCarver hp(F.host.p), dp(F.dev.p);
+    sess_fb_carve(hp, dp, F, s->batch, chunk, qcap);
+    F.params = P; F.chunk = chunk; F.on = 1;
     return 0;
 }
 
@@ -508,7 +499,7 @@ extern "C" VH_API void vh_session_destroy(vh_session* s)
     if (!s) return;
     (void)hipDeviceSynchronize();
     sess_fb_release(s->fb);
-    (void)hipFree(s->arena);
+    s->arena.release();
     delete[] s->h_ss;
     delete[] s->h_frame;
     delete[] s->h_nanchor;
@@ -659,7 +650,7 @@ extern "C" VH_API int vh_session_step_some(vh_session* s, const uint8_t* const* 
 static void sess_record_layout(int N0, int nhist, vh_session_record* L)
 {
     size_t off = 0;
-    auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
+    auto put = [&](size_t bytes) { const size_t o = off; off = vh_align_up(off + bytes, 8); return o; };
     L->n_cur = put(4 * sizeof(int)) + 0; L->n_pose = L->n_cur + 4; L->frame_i = L->n_cur + 8; L->klt_flags = L->n_cur + 12;
     L->pose_info = put(2 * sizeof(int));
     L->t = put(3 * sizeof(float));
@@ -855,7 +846,7 @@ static_assert(sizeof(RefReq) + sizeof(RefWs) + sizeof(RefView) + 5 * sizeof(void
 static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_record* L)
 {
     size_t off = 0;
-    auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
+    auto put = [&](size_t bytes) { const size_t o = off; off = vh_align_up(off + bytes, 8); return o; };
     L->nt = put(4 * sizeof(int)); L->iterations = L->nt + 4; L->converged = L->nt + 8;  // (iterations, converged: the int[2] info record of the window's solve)
     L->nfix = L->nt + 12;                                                               // (the header's fourth word)
     L->ids = put(sizeof(int) * (size_t)N0);
@@ -871,7 +862,7 @@ static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_reco
 static void refine_window_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_window_record* L)
 {
     size_t off = 0;
-    auto put = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 8); return o; };
+    auto put = [&](size_t bytes) { const size_t o = off; off = vh_align_up(off + bytes, 8); return o; };
     L->slot = put(6 * sizeof(int)); L->first = L->slot + 4; L->nt = L->slot + 8;
     L->iterations = L->slot + 12; L->converged = L->slot + 16;  // (iterations, converged: the int[2] info record of the window's solve)
     L->nfix = L->slot + 20;                                      // (the header's sixth word)
@@ -899,18 +890,17 @@ static RefView refine_view(const Layout& L, size_t head, int rows, int with_poin
 static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* base, RefWs* W, bool with_ids = false)
 {
     const size_t N0 = s->N0, nc = nf - 1, nw = nslots;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return base + o; };
+    VhCarver A(base);
     W->z_stride = 2 * N0 * (size_t)nf; W->x_stride = 3 * N0 + 6 * nc;
-    W->ba_stride = align_up(vh_nls_batch_workspace((int)N0, (int)nc), 256);
-    W->z = (double*)carve(sizeof(double) * nw * W->z_stride);
-    W->x = (double*)carve(sizeof(double) * nw * W->x_stride);
-    W->K = (double*)carve(sizeof(double) * 9 * nw);
-    W->nt = (int*)carve(sizeof(int) * nw);
-    W->ids = with_ids ? (int*)carve(sizeof(int) * nw * N0) : nullptr;
-    W->ba = carve(nw * W->ba_stride);
-    W->fixed = (uint8_t*)carve(nw * N0);  // (behind everything else: no other offset moves)
-    return off;
+    W->ba_stride = vh_align_up(vh_nls_batch_workspace((int)N0, (int)nc), 256);
+    W->z = A.take<double>(nw * W->z_stride);
+    W->x = A.take<double>(nw * W->x_stride);
+    W->K = A.take<double>(9 * nw);
+    W->nt = A.take<int>(nw);
+    W->ids = with_ids ? A.take<int>(nw * N0) : nullptr;
+    W->ba = A.take<char>(nw * W->ba_stride);
+    W->fixed = A.take<uint8_t>(nw * N0);  // (behind everything else: no other offset moves)
+    return A.bytes();
 }
 
 // THE packing arithmetic of a refinement window (one copy: the whole clip is the window first = 0): frames [first, first + nf) of stream S and the n tracks

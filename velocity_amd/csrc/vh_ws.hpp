@@ -3,6 +3,7 @@
 #include "../../include/velocity_hip.h"
 #include "vh_kernels.hpp"
 #include "vh_nls.hpp"
+#include "vh_arena.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------
 // per-stream device workspace
@@ -63,6 +64,7 @@ struct StreamWS {
 
 // scratch of the frame-0 detector and initialisation (vh_init.hip: every goodFeaturesToTrack / frame-0 entry), owned by the context; one chunk of clips at a time
 struct InitBatchScratch {
+    VhDeviceBlock main, sort;    // the two blocks every pointer below points into (batch_carve, batch_sel_carve): sort only for max_corners above the in-LDS selection
     float* resp;                 // Harris response planes of a chunk's ROIs, back to back (pix_cap floats)
     unsigned long long* keys;    // candidate keys, one segment per clip at the offset of its plane (pix_cap)
     unsigned* cnt;               // per clip: [0] max response (ordered bits), [1] candidate count, [2] corners kept, [3] unused
@@ -83,8 +85,7 @@ struct InitBatchScratch {
 
 struct vh_ctx {
     int batch, max_w, max_h, max_pts, sw, sh;
-    char* arena;
-    size_t arena_bytes;
+    VhDeviceBlock arena;  // everything below that lives on the device, laid out by ctx_carve (vh_api.hip)
     StreamWS* d_ws;
     StreamBufs* h_bufs;  // host copy of every stream's buffer table
     // optional per-stage HIP-event timing of the LK launches (bench.py roofline leg)
