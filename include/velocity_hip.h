@@ -598,7 +598,8 @@ VH_API int vh_session_pack_state(vh_session* s, float* out, void* stream);
  * for anything but a test.
  * test hook: route every LK window through one implementation -- 1: per-sample kernel, 2: strip kernel, 3: LDS-staged
  * kernel, 4: 4-tracks-per-wavefront kernel (15x15 windows; others as in 2), 5 / 6 / 7: LDS-staged 51x51 kernel with 1 / 2 / 4
- * wavefronts per track (other windows: default routing), 0: default routing per window and load.  All are bit-identical. */
+ * wavefronts per track (other windows: default routing), 8: 8-tracks-per-wavefront kernel k_lk_o (15x15 windows; others as in 2),
+ * 9: 16-tracks-per-wavefront kernel k_lk_h (15x15 windows; others as in 2), 0: default routing per window and load.  All are bit-identical. */
 VH_API void vh_debug_force_generic_lk(int on);
 
 /* test hook (vh_version >= 105): launch slots one workgroup of the one-wavefront LDS-staged LK kernel (k_lk3<.., 1, ..>, routes 3 and 5) solves one after the

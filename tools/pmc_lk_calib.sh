@@ -9,7 +9,7 @@
 S=${1:-256}
 R=/root/repo; OUT=$R/gpurun_out/pmc_calib; rm -rf $OUT $R/gpurun_out/lk_valu_model.json; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 run() {  # tag, extra bench flags
-  timeout -k 10 ${PMC_TIMEOUT:-240} rocprofv3 --kernel-trace --kernel-include-regex "k_lk3|k_lk_o|k_lk_q" --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/$1 -- \
+  timeout -k 10 ${PMC_TIMEOUT:-240} rocprofv3 --kernel-trace --kernel-include-regex "k_lk3|k_lk_o|k_lk_q|k_lk_h" --pmc SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/$1 -- \
     python $R/bench.py --streams $S --groups 1 --steps 4 --warmup 2 --cpu-seconds 0 --no-ba --no-extras --min-seconds 0 --detail $OUT/$1.json --verify-frames 0 $2 > $OUT/$1.log 2>&1 \
     || { echo "pmc_lk_calib: run $1 failed: stopping"; tail -5 $OUT/$1.log; exit 1; }
 }

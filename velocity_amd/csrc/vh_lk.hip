@@ -10,6 +10,7 @@
 //   k_lk3<W,NW,M>   LDS-staged patch + search region, NW wavefronts per track, vertical strip runs (the 51x51 fine stage)
 //   k_lk_q<W>       4 tracks per wavefront, one 16-lane DPP row per track, template in registers (the 15x15 coarse stages)
 //   k_lk_o<W>       8 tracks per wavefront, half a DPP row per track, two window rows per lane (the 15x15 coarse stages at full load)
+//   k_lk_h<W>       16 tracks per wavefront, a DPP quad per track, four window rows per lane (the 15x15 coarse stages from 128 000 tracks in flight)
 // An implementation is its window sampling and its window-sum reduction: a level functor (LK*Level below).  What a track computes from the
 // reduced sums (level start, 2x2 system and its gate, Newton update and stop rules, final in-level check), the loop over the levels, the
 // forward-backward gate, and a kernel's prologue (job row, launch slot -> point, start point) and epilogue (map-back, output stores, statistics)
@@ -2078,6 +2079,348 @@ static int launch_lkq(const void* job_tab, size_t tab_stride, int batch, int max
     return 0;
 }
 
+#ifndef VH_LKH_WAVES
+#define VH_LKH_WAVES 3  // wavefronts per SIMD k_lk_h is compiled for (profiles/lkh/resources.md)
+#endif
+// =================================================================================================================
+// v6: sixteenth-wave kernel for the 15x15 coarse stages at the largest loads.
+// 16 tracks per wavefront: a track owns 4 consecutive lanes (one DPP quad), lane r owns window rows 4r .. 4r+3 (row 15 of lane 3 is the dummy that
+// carries zero gradients).  The per-track chain of k_lk_o -- weights, window tests, row addresses, selectors, the window sums, the 2x2 solve and the
+// stop rules -- serves 16 tracks here, and the template set-up shares more V rows inside a lane: a lane builds V rows 4r .. 4r+4 from six patch rows
+// (5 per 4 window rows where k_lk_o builds 3 per 2) and takes V row 4r+5 from lane r+1.  In the Newton iterations a lane loads its own four search
+// rows; the row below its fourth row is the first row of lane r+1 (v_dot2c_i32_i16_dpp).  Window sums are 4-lane DPP reductions (two quad_perm
+// steps).  Lane 3 of a track reads lane 0 of the next track through DPP only for its dummy row.  Same integers, same float sequence per track:
+// bit-identical results.
+// =================================================================================================================
+__device__ __forceinline__ int dpp_quad_sum(int v)
+{
+    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);  // quad_perm [1,0,3,2]
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);  // quad_perm [2,3,0,1]
+    return v;
+}
+// exact 4-lane sum of int32 partials as the float32 the int64 -> float32 conversion gives (the conversion of oct_sum_f32): the 16-bit halves are
+// summed apart -- |hi| < 2^17, lo < 2^18 over four lanes -- hi * 2^16 + lo is exact in float64, the final conversion rounds once.
+// A lane holds 4 rows x 15 columns = 60 samples of at most 8160 x 4080 each (operand bounds): the int32 partial cannot wrap.
+static_assert(60ll * 8160 * 4080 < (1ll << 31), "a lane's 60-sample partial sum must fit int32");
+__device__ __forceinline__ float quad_sum_f32(int v)
+{
+    const int lo = dpp_quad_sum(v & 0xffff), hi = dpp_quad_sum(v >> 16);
+    return (float)__fma_rn((double)hi, 65536.0, (double)lo);
+}
+// The !fast form of load_rows_words for ONE row (REFLECT_101 byte loads packed at phase 0, the same addressing), four bytes in flight at a time: beside
+// the sixteen template registers per row kind that is all this kernel has room for.  Border windows of levels without a border ring only.
+template <int NWORDS, int ROW>
+__device__ __forceinline__ void lkh_row_bytes(const ImgDesc& im, int gx, int gy, unsigned* d)
+{
+    // every row computes its own column indices (the empty asm hides that they are the same, see load_rows_words): kept from row to row they cost 16 VGPRs
+    asm("; row %1" : "+v"(gx) : "n"(ROW));
+    const uint8_t* corner = im.p - (ptrdiff_t)im.pad * (im.stride + 1);
+    const unsigned bsh = (unsigned)(reinterpret_cast<uintptr_t>(corner) & 3);
+    const uint8_t* bp = corner - bsh;
+    const unsigned org = (unsigned)(im.pad * (im.stride + 1)) + bsh;
+    const uint8_t* row = bp + (org + (unsigned)vh_reflect101_near(gy, im.h) * (unsigned)im.stride);
+#pragma unroll
+    for (int i = 0; i < NWORDS; i++) {
+        unsigned b[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) b[k] = row[vh_reflect101_near(gx + 4 * i + k, im.w)];
+        unsigned w = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        asm volatile("; word %1" : "+v"(w) : "n"(i));  // packed HERE: hipcc otherwise sinks the packing to the first use and keeps every byte in a register of its own
+        d[i] = w;
+    }
+    d[NWORDS] = 0;
+}
+// bilinear x32 samples of window rows 4r .. 4r+3 (NS strips each) at (x0, y0) of image im: the lane holds image rows y0 + 4r .. y0 + 4r + 3, the row
+// below them is the first row of lane r + 1.  f(k, j, p01, p23) takes strip j of the lane's row k as two packed int16 pairs.
+template <int NS, int WIN, class F>
+__device__ __forceinline__ void lkh_sample_rows(const ImgDesc& im, int x0, int y0, int r, bool fast, unsigned wt, unsigned wb, F&& f)
+{
+    static_assert(WIN <= 4 * NS, "pairs up to (WIN - 1, WIN): NS dwords from the pixel");
+    unsigned rows[4][NS + 1];
+    unsigned sh = 0;
+    if (fast) sh = load_rows_words<NS, 4>(im, x0, y0 + 4 * r, true, rows);
+    else {
+        // byte loads, a dword of one row at a time: with the 64 bytes of the four rows in flight together the kernel does not fit its registers
+        lkh_row_bytes<NS, 0>(im, x0, y0 + 4 * r, rows[0]);
+        lkh_row_bytes<NS, 1>(im, x0, y0 + 4 * r + 1, rows[1]);
+        lkh_row_bytes<NS, 2>(im, x0, y0 + 4 * r + 2, rows[2]);
+        lkh_row_bytes<NS, 3>(im, x0, y0 + 4 * r + 3, rows[3]);
+    }
+    const PairSel sel = pair_selectors(sh);
+    constexpr int SH = 16 - (W_BITS - 5), RND = 1 << (W_BITS - 5 - 1 + 16 - (W_BITS - 5));
+#pragma unroll
+    for (int j = 0; j < NS; j++) {
+        int v[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};  // columns >= WIN are never used (zero template gradients there): not computed
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            if (4 * j + c >= WIN) continue;
+            unsigned p[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) p[k] = row_pair(rows[k], sel, 4 * j + c);
+#pragma unroll
+            for (int k = 0; k < 3; k++) v[k][c] = (dot2(p[k + 1], wb, dot2_first(p[k], wt)) << SH) + RND;
+            v[3][c] = (dot2c_next_lane(dot2_first(p[3], wt), p[0], wb) << SH) + RND;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) f(k, j, pack_hi16(v[k][0], v[k][1]), pack_hi16(v[k][2], v[k][3]));
+    }
+}
+
+template <int WIN>
+struct LKHLevel {  // the level functor of k_lk_h (see lk_track); r: this lane's place in its track's lanes
+    int max_count;
+    double eps2;
+    int r, n_iter, n_setup;
+    __device__ __forceinline__ void operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo, float& nyo,
+                                               int& status, float& err, bool want_err);
+};
+template <int WIN>
+__device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo,
+                                                          float& nyo, int& status, float& err, bool want_err)
+{
+    constexpr int NS = (WIN + 3) >> 2;  // strips per row
+    constexpr int reach = WIN + 9;      // bytes from the first one that the aligned row reads of a lane may touch (lk_block_inside)
+    LKStart s;
+    if (!lk_level_start(p0x, p0y, level, top_level, WIN, I, nxo, nyo, status, err, s)) return;
+    const float half = s.half;
+    const int ipx = s.ipx, ipy = s.ipy;
+    float nx = s.nx, ny = s.ny;
+    const Win w0 = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
+    n_setup++;
+
+    int a11 = 0, a12 = 0, a22 = 0;
+    uint2 tX[4][NS], tY[4][NS];  // template gradients of window rows 4r .. 4r + 3
+    int cI[2] = {0, 0};
+    const bool fast_I = lk_block_inside(I, ipx - 1, ipy - 1, WIN + 3, reach);
+    const unsigned w0t = pack16(w0.w00, w0.w01), w0b = pack16(w0.w10, w0.w11);
+    const bool rowd = 4 * r + 3 < WIN;  // (rows 4r .. 4r + 2 are always window rows)
+    // accumulate one strip of one window row: template samples vI, gradients vX / vY (already masked)
+    auto accumulate = [&](uint2 vI, uint2 vX, uint2 vY) {
+        a11 = dot2(vX.y, vX.y, dot2(vX.x, vX.x, a11));
+        a12 = dot2(vX.y, vY.y, dot2(vX.x, vY.x, a12));
+        a22 = dot2(vY.y, vY.y, dot2(vY.x, vY.x, a22));
+        cI[0] = dot2(vI.y, vX.y, dot2(vI.x, vX.x, cI[0]));
+        cI[1] = dot2(vI.y, vY.y, dot2(vI.x, vY.x, cI[1]));
+    };
+    if (fast_I) {
+        // Lane r reads patch rows 4r .. 4r+5 (patch row 0 = image row ipy - 1) and builds V rows 4r .. 4r+4 over the NC columns its strips share
+        // (V = bilinear weights . patch, no rounding); V row 4r+5 is the neighbour's second V row (DPP).  Window row w uses V rows w, w+1, w+2:
+        //   S = 3 (V_w + V_w+2) + 10 V_w+1,  dV = V_w+2 - V_w,  Ix = S[c+2] - S[c],  Iy = 3 (dV[c] + dV[c+2]) + 10 dV[c+1]   (see LKQLevel)
+        constexpr int NC = 4 * NS + 2;
+        unsigned a[6][NS + 2];  // (pairs up to (NC - 1, NC): NS + 1 dwords from the pixel)
+        const PairSel sel = pair_selectors(load_rows_words<NS + 1, 6>(I, ipx - 1, ipy - 1 + 4 * r, true, a));
+        int Sv[4][NC], dV[4][NC], Cv[4][NC];
+        auto column = [&](int c) {
+            unsigned q[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) q[k] = row_pair(a[k], sel, c);
+            int V[6];
+#pragma unroll
+            for (int k = 0; k < 5; k++) V[k] = dot2(q[k + 1], w0b, dot2_first(q[k], w0t));
+            V[5] = (int)dpp_from_next_lane((unsigned)V[1]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                Cv[k][c] = V[k + 1];
+                Sv[k][c] = mad24_v<40>(V[k + 1], mad24_s<12>(V[k] + V[k + 2], c << W_BITS));
+                dV[k][c] = V[k + 2] - V[k];
+            }
+        };
+        column(0); column(1);
+        // a strip in two halves of two columns, so that no more than three columns of S / dV / C per row are live
+#pragma unroll
+        for (int j = 0; j < NS; j++) {
+            const int cnt = WIN - 4 * j < 4 ? WIN - 4 * j : 4;
+            const unsigned s01 = cnt >= 2 ? 0x07060302u : 0x0c0c0302u, s23 = cnt >= 4 ? 0x07060302u : (cnt == 3 ? 0x0c0c0302u : 0x0c0c0c0cu);
+            unsigned hI[4][2], hX[4][2], hY[4][2];
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+#pragma unroll
+                for (int c = 2 * h; c < 2 * h + 2; c++)
+                    if (c < cnt) column(4 * j + 2 + c);  // (window column k uses V columns k .. k+2)
+                const unsigned sh = h ? s23 : s01, sdh = rowd ? sh : 0x0c0c0c0cu;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    int iv[2] = {0, 0}, ix[2] = {0, 0}, iy[2] = {0, 0};
+#pragma unroll
+                    for (int c = 2 * h; c < 2 * h + 2; c++) {
+                        if (c >= cnt) continue;
+                        const int col = 4 * j + c;
+                        iv[c & 1] = (Cv[k][col + 1] << (16 - (W_BITS - 5))) + (1 << (W_BITS - 5 - 1 + 16 - (W_BITS - 5)));
+                        ix[c & 1] = Sv[k][col + 2] - Sv[k][col];
+                        iy[c & 1] = mad24_v<40>(dV[k][col + 1], mad24_s<12>(dV[k][col] + dV[k][col + 2], 4 << (W_BITS - 1)));
+                    }
+                    const unsigned m = k == 3 ? sdh : sh;
+                    hI[k][h] = pack_hi16(iv[0], iv[1]);
+                    hX[k][h] = __builtin_amdgcn_perm((unsigned)ix[1], (unsigned)ix[0], m);
+                    hY[k][h] = __builtin_amdgcn_perm((unsigned)iy[1], (unsigned)iy[0], m);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint2 vX = make_uint2(hX[k][0], hX[k][1]), vY = make_uint2(hY[k][0], hY[k][1]);
+                tX[k][j] = vX; tY[k][j] = vY;
+                accumulate(make_uint2(hI[k][0], hI[k][1]), vX, vY);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+        // Window at the image border: the derivative image is 0 OUTSIDE the level, so the Scharr gradients of the integer pixels are built (packed
+        // int16 pairs (k, k+1), see LKQLevel), zeroed outside, then interpolated like any other image.  Lane r holds pixel rows 4r-1 .. 4r+4 of the
+        // window (image rows ipy + 4r - 1 ..) and gradient rows 4r .. 4r+3; gradient / pixel row 4r+4 is lane r+1's first row (DPP).
+        unsigned a[6][NS + 1];
+#pragma unroll
+        for (int rr = 0; rr < 6; rr++) {
+            load_row_words<NS + 1>(I, ipx - 1, ipy - 1 + 4 * r + rr, I.pad >= VH_LV_PAD, a[rr]);
+            __builtin_amdgcn_sched_barrier(0);  // (a row's byte loads at a time: six rows of them in flight do not fit the registers)
+        }
+        const int ay = ipy + 4 * r, cs = max(0, -ipx), ce = min(4 * NS, I.w - 1 - ipx);
+        const unsigned Mc = ce >= cs ? (((2u << ce) - 1u) & ~((1u << cs) - 1u)) : 0u;
+        unsigned Mr[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) Mr[k] = (ay + k >= 0 && ay + k < I.h) ? Mc : 0u;
+        short2v Sp[4][4 * NS + 2], Dp[4][4 * NS + 2];
+        unsigned Pp[4][4 * NS + 2];
+        const short2v k3 = {3, 3}, k10 = {10, 10};
+        auto colb = [&](int c) {
+            unsigned p[6];
+#pragma unroll
+            for (int k = 0; k < 6; k++) p[k] = row_pair(a[k], c);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                Pp[k][c] = p[k + 1];
+                Sp[k][c] = (as_s2(p[k]) + as_s2(p[k + 2])) * k3 + as_s2(p[k + 1]) * k10;
+                Dp[k][c] = as_s2(p[k + 2]) - as_s2(p[k]);
+            }
+        };
+        colb(0); colb(1);
+        constexpr int SH = 16 - (W_BITS - 5), RND = 1 << (W_BITS - 5 - 1 + 16 - (W_BITS - 5));
+#pragma unroll
+        for (int j = 0; j < NS; j++) {
+            const int cnt = WIN - 4 * j < 4 ? WIN - 4 * j : 4;
+            const unsigned s01 = cnt >= 2 ? 0x07060302u : 0x0c0c0302u, s23 = cnt >= 4 ? 0x07060302u : (cnt == 3 ? 0x0c0c0302u : 0x0c0c0c0cu);
+            unsigned hI[4][2], hX[4][2], hY[4][2];
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+#pragma unroll
+                for (int c = 2 * h; c < 2 * h + 2; c++)
+                    if (c < cnt) colb(4 * j + 2 + c);
+                const unsigned sh = h ? s23 : s01, sdh = rowd ? sh : 0x0c0c0c0cu;
+                int iv[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}, ix[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}, iy[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+#pragma unroll
+                for (int c = 2 * h; c < 2 * h + 2; c++) {
+                    if (c >= cnt) continue;
+                    const int col = 4 * j + c, e = c & 1;
+                    unsigned gx[4], gy[4];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const unsigned m = ((unsigned)__builtin_amdgcn_sbfe((int)Mr[k], col, 1) & 0xffffu) | ((unsigned)__builtin_amdgcn_sbfe((int)Mr[k], col + 1, 1) << 16);
+                        gx[k] = __builtin_bit_cast(unsigned, Sp[k][col + 2] - Sp[k][col]) & m;
+                        gy[k] = __builtin_bit_cast(unsigned, (Dp[k][col] + Dp[k][col + 2]) * k3 + Dp[k][col + 1] * k10) & m;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        ix[k][e] = (dot2(gx[k + 1], w0b, dot2_first(gx[k], w0t)) << 2) + (4 << (W_BITS - 1));
+                        iy[k][e] = (dot2(gy[k + 1], w0b, dot2_first(gy[k], w0t)) << 2) + (4 << (W_BITS - 1));
+                        iv[k][e] = (dot2(Pp[k + 1][col + 1], w0b, dot2_first(Pp[k][col + 1], w0t)) << SH) + RND;
+                    }
+                    ix[3][e] = (dot2c_next_lane(dot2_first(gx[3], w0t), gx[0], w0b) << 2) + (4 << (W_BITS - 1));
+                    iy[3][e] = (dot2c_next_lane(dot2_first(gy[3], w0t), gy[0], w0b) << 2) + (4 << (W_BITS - 1));
+                    iv[3][e] = (dot2c_next_lane(dot2_first(Pp[3][col + 1], w0t), Pp[0][col + 1], w0b) << SH) + RND;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const unsigned m = k == 3 ? sdh : sh;
+                    hI[k][h] = pack_hi16(iv[k][0], iv[k][1]);
+                    hX[k][h] = __builtin_amdgcn_perm((unsigned)ix[k][1], (unsigned)ix[k][0], m);
+                    hY[k][h] = __builtin_amdgcn_perm((unsigned)iy[k][1], (unsigned)iy[k][0], m);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint2 vX = make_uint2(hX[k][0], hX[k][1]), vY = make_uint2(hY[k][0], hY[k][1]);
+                tX[k][j] = vX; tY[k][j] = vY;
+                accumulate(make_uint2(hI[k][0], hI[k][1]), vX, vY);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    LKSys S;
+    if (!lk_system(quad_sum_f32(a11), quad_sum_f32(a12), quad_sum_f32(a22), WIN, S)) {
+        if (level == 0) status = 0;
+        return;
+    }
+
+    float pdx = 0.f, pdy = 0.f;
+    for (int it = 0; it < max_count; it++) {
+        const int inx = vh_floor(nx), iny = vh_floor(ny);
+        if (lk_outside(inx, iny, WIN, J)) {
+            if (level == 0) status = 0;
+            break;
+        }
+        const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(nx, (float)inx), __fsub_rn(ny, (float)iny)));
+        const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);
+        n_iter++;
+        int b1 = -cI[0], b2 = -cI[1];
+        lkh_sample_rows<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, [&](int k, int j, unsigned p01, unsigned p23) {
+            b1 = dot2(p23, tX[k][j].y, dot2(p01, tX[k][j].x, b1));
+            b2 = dot2(p23, tY[k][j].y, dot2(p01, tY[k][j].x, b2));
+        });
+        if (lk_step(S, quad_sum_f32(b1), quad_sum_f32(b2), half, it, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
+    }
+
+    if (status && level == 0) {
+        float fx, fy;
+        int inx, iny;
+        if (!lk_final_origin(nxo, nyo, half, WIN, J, fx, fy, inx, iny)) { status = 0; return; }
+        if (!want_err) return;
+        const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
+        const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);
+        unsigned i01[4][NS], i23[4][NS];
+        lkh_sample_rows<NS, WIN>(I, ipx, ipy, r, fast_I || I.pad >= VH_LV_PAD, w0t, w0b, [&](int k, int j, unsigned p01, unsigned p23) {
+            i01[k][j] = p01; i23[k][j] = p23;
+        });
+        int se = 0;
+        lkh_sample_rows<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, [&](int k, int j, unsigned p01, unsigned p23) {
+            const short2v d01 = as_s2(p01) - as_s2(i01[k][j]), d23 = as_s2(p23) - as_s2(i23[k][j]);
+            const int d[4] = {d01.x, d01.y, d23.x, d23.y};
+            const int cnt = WIN - 4 * j < 4 ? WIN - 4 * j : 4;
+#pragma unroll
+            for (int c = 0; c < 4; c++) se += (c < cnt && (k < 3 || rowd)) ? (d[c] < 0 ? -d[c] : d[c]) : 0;
+        });
+        err = lk_err_of(quad_sum_f32(se), WIN);
+    }
+}
+
+template <int WIN>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VH_LKH_WAVES))) void k_lk_h(const void* job_tab, size_t tab_stride, unsigned grp)
+{
+    static_assert(WIN == 15, "4 lanes x 4 rows: row 15 is the dummy that feeds nothing");
+    unsigned blk_x, blk_y;
+    lk_block_xy<true>(blk_x, blk_y, grp);
+    const LKJob& job = lk_job_row(job_tab, tab_stride, blk_y);
+    const int slot = (int)blk_x * 16 + (threadIdx.x >> 2);
+    int pt;
+    float px, py;
+    if (!lk_slot_start(job, slot, pt, px, py)) return;  // whole quads leave together
+    LKHLevel<WIN> lf{job.max_count, job.eps2, (int)(threadIdx.x & 3), 0, 0};
+    LKResult R;
+    lk_solve(job, px, py, lf, R);
+    if (lf.r == 0) {
+        lk_store_track(job, pt, R.fx, R.fy, R.st, R.err, R.fbe);
+        lk_add_stats(job, (unsigned)slot, lf.n_iter, lf.n_setup);
+    }
+}
+
+template <int WIN>
+static int launch_lkh(const void* job_tab, size_t tab_stride, int batch, int max_n, hipStream_t s)
+{
+    static const unsigned grp = getenv("VH_LKO_G") ? (unsigned)atoi(getenv("VH_LKO_G")) : 64u;  // (the group argument of launch_lko)
+    hipLaunchKernelGGL(k_lk_h<WIN>, dim3((max_n + 15) / 16, batch), dim3(64), 0, s, job_tab, tab_stride, lk_group_arg(grp, batch));
+    return 0;
+}
+
 // test hook (vh_debug_lk3_tpw): launch slots per workgroup of the one-wavefront LDS-staged kernel -- 0 = chosen by load, n > 0 = n (clamped to MAX_TPW).
 // PROCESS-WIDE atomic like the other hooks; every value gives bit-identical results (VH_LK3_TPW: experiments only, the initial value).
 static std::atomic<int> g_lk3_tpw{getenv("VH_LK3_TPW") ? atoi(getenv("VH_LK3_TPW")) : 0};
@@ -2152,12 +2495,13 @@ static int launch_strip(const void* job_tab, size_t tab_stride, int batch, int m
 }
 
 // test hook: 1 = per-sample kernel, 2 = strip kernel, 3 = LDS-staged kernel, 4 = 4-tracks-per-wave kernel (15x15), 5 / 6 / 7 = LDS-staged 51x51 kernel with
-// 1 / 2 / 4 wavefronts per track, 8 = 8-tracks-per-wave kernel (15x15), 0 = default routing.
+// 1 / 2 / 4 wavefronts per track, 8 = 8-tracks-per-wave kernel (15x15), 9 = 16-tracks-per-wave kernel (15x15), 0 = default routing.
 // PROCESS-WIDE (every context of the process is re-routed; an atomic, so a flip while another thread launches is a clean switch between two
 // bit-identical implementations, never a torn value) -- a test / experiment switch, not a per-stream control.
 static std::atomic<int> g_lk_force_generic{getenv("VH_LK_FORCE") ? atoi(getenv("VH_LK_FORCE")) : 0};  // (environment: experiments only)
 void vh_lk_force_generic(int on) { g_lk_force_generic.store(on, std::memory_order_relaxed); }
 static const long long g_lko_min_tracks = getenv("VH_LKO_MIN") ? atoll(getenv("VH_LKO_MIN")) : 10000;  // (environment: experiments only)
+static const long long g_lkh_min_tracks = getenv("VH_LKH_MIN") ? atoll(getenv("VH_LKH_MIN")) : 128000;  // (environment: experiments only)
 
 // Which kernel a launch of `batch` streams x `max_n` track slots with window `win` takes (the ids of the test hook above; 2 = the strip kernel of any
 // window <= 63, 1 = the per-sample kernel).  vh_launch_lk follows exactly this decision, and the profiling records report it (vh_profile_lk_routes), so
@@ -2168,7 +2512,11 @@ static const long long g_lko_min_tracks = getenv("VH_LKO_MIN") ? atoll(getenv("V
 // wavefront per track from 640 tracks in flight (2000 tracks: 28.8 us against 33.2 / 43.2 with 2 / 4 wavefronts per track; 768: 37.1 / 39.7 / 41.1 for
 // the whole vh_pyr_lk call), 4 wavefronts per track below (128 tracks: 30.8 against 35.3); 2 per track is never the fastest and is kept for the tests.
 // 15x15 coarse stages: the one-wave-per-track strip kernel up to 3000 tracks (2000: 20.2 / 27.9 us against 22.2 / 29.4 for 4 tracks per wavefront; 4000:
-// 25.6 / 36.6 against 23.1 / 29.2), 4 tracks per wavefront up to 10 000, 8 per wavefront above (12 000: 33.6 / 50.2 against 35.4 / 55.9 us; 8000: a tie).
+// 25.6 / 36.6 against 23.1 / 29.2), 4 tracks per wavefront up to 10 000, 8 per wavefront above (12 000: 33.6 / 50.2 against 35.4 / 55.9 us; 8000: a tie),
+// 16 per wavefront (k_lk_h, three wavefronts per SIMD) from 128 000: both launches of sessions of 64 / 96 / 128 / 256 streams x 2000 tracks, routes 8 and 9 forced
+// in one call on one box (profiles/lkh/threshold.json): 147.9 / 242.5 -> 143.6 / 235.0 us at 128 000 tracks, 208.5 / 351.4 -> 202.1 / 336.3 at 192 000, 267.0 / 456.6 ->
+// 254.5 / 432.9 at 256 000, 496.8 / 927.1 -> 460.2 / 897.9 at 512 000, shorter in every run.  128 000 is the smallest load measured, not a crossover: below it the
+// route is unmeasured, and the threshold may not go below 102 401, where a test pins k_lk_o<15> as the headline's route of its time.
 int vh_lk_route(int batch, int max_n, int win)
 {
     const int force = g_lk_force_generic.load(std::memory_order_relaxed);
@@ -2181,6 +2529,7 @@ int vh_lk_route(int batch, int max_n, int win)
             return nw == 1 ? 5 : nw == 2 ? 6 : 7;
         }
     }
+    if (win == 15 && (force == 9 || ((force == 0 || force_nw) && tracks >= g_lkh_min_tracks))) return 9;
     if (win == 15 && (force == 8 || ((force == 0 || force_nw) && tracks >= g_lko_min_tracks))) return 8;
     if (win == 15 && (force == 4 || ((force == 0 || force_nw) && tracks >= 3000))) return 4;
     if (force != 1 && win <= 63) return 2;  // (modes 5..7 with another window than 51: default routing); int32 per-lane partial sums are exact up to 16 strips per lane
@@ -2198,6 +2547,7 @@ const char* vh_lk_route_name(int route, int win)
     case 6: return "k_lk3<51, 2, 4>";
     case 7: return "k_lk3<51, 4, 4>";
     case 8: return "k_lk_o<15>";
+    case 9: return "k_lk_h<15>";
     default: return "none";
     }
 }
@@ -2228,6 +2578,7 @@ int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, i
     case 6: return launch_lk3<51, 2, 4>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
     case 7: return launch_lk3<51, 4, 4>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
     case 8: return launch_lko<15>(job_tab, tab_stride, batch, max_n, s);
+    case 9: return launch_lkh<15>(job_tab, tab_stride, batch, max_n, s);
     case 4: return launch_lkq<15>(job_tab, tab_stride, batch, max_n, s);
     case 2:
         if (win == 15) return launch_strip<15>(job_tab, tab_stride, batch, max_n, win, s);
