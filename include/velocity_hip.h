@@ -599,7 +599,7 @@ VH_API int vh_session_pack_state(vh_session* s, float* out, void* stream);
  * test hook: route every LK window through one implementation -- 1: per-sample kernel, 2: strip kernel, 3: LDS-staged
  * kernel, 4: 4-tracks-per-wavefront kernel (15x15 windows; others as in 2), 5 / 6 / 7: LDS-staged 51x51 kernel with 1 / 2 / 4
  * wavefronts per track (other windows: default routing), 8: 8-tracks-per-wavefront kernel k_lk_o (15x15 windows; others as in 2),
- * 9: 16-tracks-per-wavefront kernel k_lk_h (15x15 windows; others as in 2), 0: default routing per window and load.  All are bit-identical. */
+ * 9: 16-tracks-per-wavefront kernel k_lk_h, four wavefronts per SIMD with 40 dwords per lane in LDS (15x15 windows; others as in 2), 0: default routing per window and load.  All are bit-identical. */
 VH_API void vh_debug_force_generic_lk(int on);
 
 /* test hook (vh_version >= 105): launch slots one workgroup of the one-wavefront LDS-staged LK kernel (k_lk3<.., 1, ..>, routes 3 and 5) solves one after the
@@ -613,6 +613,9 @@ VH_API void vh_debug_lk3_one_level(int on);
  * per lane, out[3]: LDS bytes per workgroup (hipFuncGetAttributes + the dynamic size).  Launches no kernel.  The kernel has a general and a single-level
  * form (vh_debug_lk3_one_level): of each figure the worse of the two is reported. */
 VH_API int vh_debug_lk3_residency(int out[4]);
+/* test hook: the same four figures for the 16-tracks-per-wavefront 15x15 kernel (k_lk_h<15>, route 9), whose LDS is static: out[3] is
+ * hipFuncGetAttributes' sharedSizeBytes.  Launches no kernel. */
+VH_API int vh_debug_lkh_residency(int out[4]);
 
 /* test hook: estimateAffine2D stand-in -- 1: always the three-kernel path (hypotheses spread over the chip), 2: the fused
  * one-workgroup-per-stream kernel whenever the problem fits it (latency path), 0: default routing by batch size.  Bit-identical results. */

@@ -152,6 +152,7 @@ _SIGS = {
     "vh_debug_lk3_tpw": (None, [C.c_int]),
     "vh_debug_lk3_one_level": (None, [C.c_int]),
     "vh_debug_lk3_residency": (C.c_int, [i32p]),
+    "vh_debug_lkh_residency": (C.c_int, [i32p]),
     "vh_profile_lk_tpw": (C.c_int, [vp, i32p]),
     "vh_profile_begin": (C.c_int, [vp, C.c_int]),
     "vh_profile_end": (C.c_int, [vp, f64p, i32p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),

@@ -416,6 +416,14 @@ extern "C" VH_API int vh_debug_lk3_residency(int out[4])
     return rc ? vh_fail(rc, "vh_debug_lk3_residency: the runtime refused the occupancy / attribute query") : 0;
 }
 
+int vh_lkh_residency(int out[4]);
+extern "C" VH_API int vh_debug_lkh_residency(int out[4])
+{
+    if (!out) return vh_fail(-1, "vh_debug_lkh_residency: bad arguments");
+    const int rc = vh_lkh_residency(out);
+    return rc ? vh_fail(rc, "vh_debug_lkh_residency: the runtime refused the occupancy / attribute query") : 0;
+}
+
 extern "C" VH_API int vh_profile_lk_routes(vh_ctx* c, int* routes_host, char* names_host)
 {
     if (!c || !routes_host) return vh_fail(-1, "vh_profile_lk_routes: bad arguments");

@@ -10,7 +10,7 @@
 //   k_lk3<W,NW,M>   LDS-staged patch + search region, NW wavefronts per track, vertical strip runs (the 51x51 fine stage)
 //   k_lk_q<W>       4 tracks per wavefront, one 16-lane DPP row per track, template in registers (the 15x15 coarse stages)
 //   k_lk_o<W>       8 tracks per wavefront, half a DPP row per track, two window rows per lane (the 15x15 coarse stages at full load)
-//   k_lk_h<W>       16 tracks per wavefront, a DPP quad per track, four window rows per lane (the 15x15 coarse stages from 128 000 tracks in flight)
+//   k_lk_h<W>       16 tracks per wavefront, a DPP quad per track, four window rows per lane, part of the template in LDS (the 15x15 coarse stages from 128 000 tracks in flight)
 // An implementation is its window sampling and its window-sum reduction: a level functor (LK*Level below).  What a track computes from the
 // reduced sums (level start, 2x2 system and its gate, Newton update and stop rules, final in-level check), the loop over the levels, the
 // forward-backward gate, and a kernel's prologue (job row, launch slot -> point, start point) and epilogue (map-back, output stores, statistics)
@@ -2080,7 +2080,7 @@ static int launch_lkq(const void* job_tab, size_t tab_stride, int batch, int max
 }
 
 #ifndef VH_LKH_WAVES
-#define VH_LKH_WAVES 3  // wavefronts per SIMD k_lk_h is compiled for (profiles/lkh/resources.md)
+#define VH_LKH_WAVES 4  // wavefronts per SIMD k_lk_h is compiled for (profiles/lkh_lds/resources.md; 3: experiments)
 #endif
 // =================================================================================================================
 // v6: sixteenth-wave kernel for the 15x15 coarse stages at the largest loads.
@@ -2091,6 +2091,8 @@ static int launch_lkq(const void* job_tab, size_t tab_stride, int batch, int max
 // rows; the row below its fourth row is the first row of lane r+1 (v_dot2c_i32_i16_dpp).  Window sums are 4-lane DPP reductions (two quad_perm
 // steps).  Lane 3 of a track reads lane 0 of the next track through DPP only for its dummy row.  Same integers, same float sequence per track:
 // bit-identical results.
+// Four wavefronts per SIMD (128 VGPRs, no scratch): 40 dwords per lane -- the y gradients and the last strip of the x gradients of the template, and
+// what a track carries from level to level -- live in 10 240 bytes of LDS per wavefront, see LKHLevel.
 // =================================================================================================================
 __device__ __forceinline__ int dpp_quad_sum(int v)
 {
@@ -2131,9 +2133,11 @@ __device__ __forceinline__ void lkh_row_bytes(const ImgDesc& im, int gx, int gy,
     d[NWORDS] = 0;
 }
 // bilinear x32 samples of window rows 4r .. 4r+3 (NS strips each) at (x0, y0) of image im: the lane holds image rows y0 + 4r .. y0 + 4r + 3, the row
-// below them is the first row of lane r + 1.  f(k, j, p01, p23) takes strip j of the lane's row k as two packed int16 pairs.
-template <int NS, int WIN, class F>
-__device__ __forceinline__ void lkh_sample_rows(const ImgDesc& im, int x0, int y0, int r, bool fast, unsigned wt, unsigned wb, F&& f)
+// below them is the first row of lane r + 1.  f(k, j, h, p) takes columns 2h, 2h + 1 of strip j of the lane's row k as a packed int16 pair.  pre(j)
+// runs ahead of strip j's arithmetic, half a strip of it before the first f(., j, ...) call: where the consumer issues the LDS reads of what it pairs strip j with (the
+// sched_barrier keeps them there: hipcc would sink them to their use, or hoist all of them above the first strip).
+template <int NS, int WIN, class P, class F>
+__device__ __forceinline__ void lkh_sample_rows(const ImgDesc& im, int x0, int y0, int r, bool fast, unsigned wt, unsigned wb, P&& pre, F&& f)
 {
     static_assert(WIN <= 4 * NS, "pairs up to (WIN - 1, WIN): NS dwords from the pixel");
     unsigned rows[4][NS + 1];
@@ -2150,19 +2154,25 @@ __device__ __forceinline__ void lkh_sample_rows(const ImgDesc& im, int x0, int y
     constexpr int SH = 16 - (W_BITS - 5), RND = 1 << (W_BITS - 5 - 1 + 16 - (W_BITS - 5));
 #pragma unroll
     for (int j = 0; j < NS; j++) {
-        int v[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};  // columns >= WIN are never used (zero template gradients there): not computed
+        pre(j);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-            if (4 * j + c >= WIN) continue;
-            unsigned p[4];
+        for (int h = 0; h < 2; h++) {  // a pair of columns at a time: no more than eight samples live
+            int v[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};  // columns >= WIN are never used (zero template gradients there): not computed
 #pragma unroll
-            for (int k = 0; k < 4; k++) p[k] = row_pair(rows[k], sel, 4 * j + c);
+            for (int e = 0; e < 2; e++) {
+                const int c = 4 * j + 2 * h + e;
+                if (c >= WIN) continue;
+                unsigned p[4];
 #pragma unroll
-            for (int k = 0; k < 3; k++) v[k][c] = (dot2(p[k + 1], wb, dot2_first(p[k], wt)) << SH) + RND;
-            v[3][c] = (dot2c_next_lane(dot2_first(p[3], wt), p[0], wb) << SH) + RND;
+                for (int k = 0; k < 4; k++) p[k] = row_pair(rows[k], sel, c);
+#pragma unroll
+                for (int k = 0; k < 3; k++) v[k][e] = (dot2(p[k + 1], wb, dot2_first(p[k], wt)) << SH) + RND;
+                v[3][e] = (dot2c_next_lane(dot2_first(p[3], wt), p[0], wb) << SH) + RND;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) f(k, j, h, pack_hi16(v[k][0], v[k][1]));
         }
-#pragma unroll
-        for (int k = 0; k < 4; k++) f(k, j, pack_hi16(v[k][0], v[k][1]), pack_hi16(v[k][2], v[k][3]));
     }
 }
 
@@ -2171,36 +2181,74 @@ struct LKHLevel {  // the level functor of k_lk_h (see lk_track); r: this lane's
     int max_count;
     double eps2;
     int r, n_iter, n_setup;
+    // The template gradients of a lane are 4 rows x NS strips x 2 dwords each of Ix and Iy: 64 registers, which do not fit beside the rest at four
+    // wavefronts per SIMD.  LDS_CHUNKS x 16 bytes of them per lane live in LDS instead: all of Iy (chunk 2j + h: columns 2h, 2h + 1 of strip j, one dword
+    // for each of the four rows) and the first half of the last strip of Ix (chunk 2 NS).  The last strip has ONE column in its second half (the other is
+    // masked to zero), so Ix and Iy of that column share a dword: chunk 2 NS - 1 holds (Ix | Iy << 16) of column WIN - 1 for each row.  Chunk c of lane l
+    // is the 16 bytes at 1024 c + 16 l of the workgroup's (= wavefront's) LDS: every access a ds_write_b128 / ds_read_b128 off one base register `tl`
+    // with the chunk in the offset field, no bank conflict.  A lane reads only what it wrote: no barrier.  Every level of both passes reuses the slots,
+    // and so does the err pass once the template is dead.
+    // The chunk this frees (PARK) holds what a track keeps from its first level to its epilogue and a level reads once: the start point of the pass,
+    // the point index and the launch slot -- four registers that the set-ups, which are what the kernel's register count is, do not carry.
+    static constexpr int NS = (WIN + 3) >> 2, LDS_CHUNKS = 2 * NS + 2, LDS_BYTES = LDS_CHUNKS * 1024, PARK = 2 * NS + 1;
+    static_assert(LDS_BYTES <= 160 * 1024 / 16, "16 one-wavefront workgroups per CU (4 wavefronts per SIMD) must fit in LDS");
+    static_assert(WIN - 4 * (NS - 1) == 3, "the last strip must have exactly one column in its second half");
+    lds_u32x4 tl;  // chunk 0 of this lane
+    __device__ __forceinline__ void put(int chunk, const unsigned (&d)[4]) const { tl[64 * chunk] = u32x4_t{d[0], d[1], d[2], d[3]}; }
+    __device__ __forceinline__ void park(float sx, float sy, int pt, int slot) const
+    {
+        tl[64 * PARK] = u32x4_t{__float_as_uint(sx), __float_as_uint(sy), (unsigned)pt, (unsigned)slot};
+    }
+    __device__ __forceinline__ u32x4_t parked() const { return tl[64 * PARK]; }
+    // (p0x, p0y): NOT read -- the pass starts at the parked point
     __device__ __forceinline__ void operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo, float& nyo,
                                                int& status, float& err, bool want_err);
 };
 template <int WIN>
-__device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float p0x, float p0y, float& nxo,
+__device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const ImgDesc J, int level, int top_level, float, float, float& nxo,
                                                           float& nyo, int& status, float& err, bool want_err)
 {
-    constexpr int NS = (WIN + 3) >> 2;  // strips per row
-    constexpr int reach = WIN + 9;      // bytes from the first one that the aligned row reads of a lane may touch (lk_block_inside)
+    constexpr int reach = WIN + 9;  // bytes from the first one that the aligned row reads of a lane may touch (lk_block_inside)
+    const u32x4_t start = parked();
+    const float p0x = __uint_as_float(start[0]), p0y = __uint_as_float(start[1]);
     LKStart s;
     if (!lk_level_start(p0x, p0y, level, top_level, WIN, I, nxo, nyo, status, err, s)) return;
     const float half = s.half;
     const int ipx = s.ipx, ipy = s.ipy;
-    float nx = s.nx, ny = s.ny;
     const Win w0 = bilinear_weights(__fsub_rn(s.px, (float)ipx), __fsub_rn(s.py, (float)ipy));
     n_setup++;
 
     int a11 = 0, a12 = 0, a22 = 0;
-    uint2 tX[4][NS], tY[4][NS];  // template gradients of window rows 4r .. 4r + 3
+    uint2 tX[4][NS - 1];  // x template gradients of window rows 4r .. 4r + 3, all strips but the last; the last one and the y gradients: LDS (see `tl`)
     int cI[2] = {0, 0};
     const bool fast_I = lk_block_inside(I, ipx - 1, ipy - 1, WIN + 3, reach);
     const unsigned w0t = pack16(w0.w00, w0.w01), w0b = pack16(w0.w10, w0.w11);
     const bool rowd = 4 * r + 3 < WIN;  // (rows 4r .. 4r + 2 are always window rows)
-    // accumulate one strip of one window row: template samples vI, gradients vX / vY (already masked)
-    auto accumulate = [&](uint2 vI, uint2 vX, uint2 vY) {
-        a11 = dot2(vX.y, vX.y, dot2(vX.x, vX.x, a11));
-        a12 = dot2(vX.y, vY.y, dot2(vX.x, vY.x, a12));
-        a22 = dot2(vY.y, vY.y, dot2(vY.x, vY.x, a22));
-        cI[0] = dot2(vI.y, vX.y, dot2(vI.x, vX.x, cI[0]));
-        cI[1] = dot2(vI.y, vY.y, dot2(vI.x, vY.x, cI[1]));
+    // Half h (columns 2h, 2h + 1) of strip j of the lane's four rows, as either set-up has just produced it -- template samples gI, gradients gX / gY,
+    // already masked: into the window sums (integer sums: the order does not matter), and kept for the iterations HERE, in registers or in LDS, so that
+    // the set-up holds neither a whole strip nor more of the template than the iterations do
+    auto keep_half = [&](int j, int h, const unsigned (&gI)[4], const unsigned (&gX)[4], const unsigned (&gY)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {  // (one chain per sum: a second one each is five registers the set-up does not have, see profiles/lkh_lds/resources.md)
+            a11 = dot2(gX[k], gX[k], a11);
+            a12 = dot2(gX[k], gY[k], a12);
+            a22 = dot2(gY[k], gY[k], a22);
+            cI[0] = dot2(gI[k], gX[k], cI[0]);
+            cI[1] = dot2(gI[k], gY[k], cI[1]);
+        }
+        if (j < NS - 1) {
+            put(2 * j + h, gY);
+#pragma unroll
+            for (int k = 0; k < 4; k++) (h ? tX[k][j].y : tX[k][j].x) = gX[k];
+        } else if (h == 0) {
+            put(2 * j, gY);
+            put(2 * NS, gX);
+        } else {
+            unsigned q[4];  // (the upper halves of gX and gY are the masked column)
+#pragma unroll
+            for (int k = 0; k < 4; k++) q[k] = gX[k] | gY[k] << 16;
+            put(2 * j + 1, q);
+        }
     };
     if (fast_I) {
         // Lane r reads patch rows 4r .. 4r+5 (patch row 0 = image row ipy - 1) and builds V rows 4r .. 4r+4 over the NC columns its strips share
@@ -2231,13 +2279,13 @@ __device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const
         for (int j = 0; j < NS; j++) {
             const int cnt = WIN - 4 * j < 4 ? WIN - 4 * j : 4;
             const unsigned s01 = cnt >= 2 ? 0x07060302u : 0x0c0c0302u, s23 = cnt >= 4 ? 0x07060302u : (cnt == 3 ? 0x0c0c0302u : 0x0c0c0c0cu);
-            unsigned hI[4][2], hX[4][2], hY[4][2];
 #pragma unroll
             for (int h = 0; h < 2; h++) {
 #pragma unroll
                 for (int c = 2 * h; c < 2 * h + 2; c++)
                     if (c < cnt) column(4 * j + 2 + c);  // (window column k uses V columns k .. k+2)
                 const unsigned sh = h ? s23 : s01, sdh = rowd ? sh : 0x0c0c0c0cu;
+                unsigned gI[4], gX[4], gY[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     int iv[2] = {0, 0}, ix[2] = {0, 0}, iy[2] = {0, 0};
@@ -2250,19 +2298,13 @@ __device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const
                         iy[c & 1] = mad24_v<40>(dV[k][col + 1], mad24_s<12>(dV[k][col] + dV[k][col + 2], 4 << (W_BITS - 1)));
                     }
                     const unsigned m = k == 3 ? sdh : sh;
-                    hI[k][h] = pack_hi16(iv[0], iv[1]);
-                    hX[k][h] = __builtin_amdgcn_perm((unsigned)ix[1], (unsigned)ix[0], m);
-                    hY[k][h] = __builtin_amdgcn_perm((unsigned)iy[1], (unsigned)iy[0], m);
+                    gI[k] = pack_hi16(iv[0], iv[1]);
+                    gX[k] = __builtin_amdgcn_perm((unsigned)ix[1], (unsigned)ix[0], m);
+                    gY[k] = __builtin_amdgcn_perm((unsigned)iy[1], (unsigned)iy[0], m);
                 }
+                keep_half(j, h, gI, gX, gY);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint2 vX = make_uint2(hX[k][0], hX[k][1]), vY = make_uint2(hY[k][0], hY[k][1]);
-                tX[k][j] = vX; tY[k][j] = vY;
-                accumulate(make_uint2(hI[k][0], hI[k][1]), vX, vY);
-            }
-            __builtin_amdgcn_sched_barrier(0);
         }
     } else {
         // Window at the image border: the derivative image is 0 OUTSIDE the level, so the Scharr gradients of the integer pixels are built (packed
@@ -2299,7 +2341,6 @@ __device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const
         for (int j = 0; j < NS; j++) {
             const int cnt = WIN - 4 * j < 4 ? WIN - 4 * j : 4;
             const unsigned s01 = cnt >= 2 ? 0x07060302u : 0x0c0c0302u, s23 = cnt >= 4 ? 0x07060302u : (cnt == 3 ? 0x0c0c0302u : 0x0c0c0c0cu);
-            unsigned hI[4][2], hX[4][2], hY[4][2];
 #pragma unroll
             for (int h = 0; h < 2; h++) {
 #pragma unroll
@@ -2328,22 +2369,17 @@ __device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const
                     iy[3][e] = (dot2c_next_lane(dot2_first(gy[3], w0t), gy[0], w0b) << 2) + (4 << (W_BITS - 1));
                     iv[3][e] = (dot2c_next_lane(dot2_first(Pp[3][col + 1], w0t), Pp[0][col + 1], w0b) << SH) + RND;
                 }
+                unsigned gI[4], gX[4], gY[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const unsigned m = k == 3 ? sdh : sh;
-                    hI[k][h] = pack_hi16(iv[k][0], iv[k][1]);
-                    hX[k][h] = __builtin_amdgcn_perm((unsigned)ix[k][1], (unsigned)ix[k][0], m);
-                    hY[k][h] = __builtin_amdgcn_perm((unsigned)iy[k][1], (unsigned)iy[k][0], m);
+                    gI[k] = pack_hi16(iv[k][0], iv[k][1]);
+                    gX[k] = __builtin_amdgcn_perm((unsigned)ix[k][1], (unsigned)ix[k][0], m);
+                    gY[k] = __builtin_amdgcn_perm((unsigned)iy[k][1], (unsigned)iy[k][0], m);
                 }
+                keep_half(j, h, gI, gX, gY);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint2 vX = make_uint2(hX[k][0], hX[k][1]), vY = make_uint2(hY[k][0], hY[k][1]);
-                tX[k][j] = vX; tY[k][j] = vY;
-                accumulate(make_uint2(hI[k][0], hI[k][1]), vX, vY);
-            }
-            __builtin_amdgcn_sched_barrier(0);
         }
     }
     LKSys S;
@@ -2352,6 +2388,7 @@ __device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const
         return;
     }
 
+    float nx = __fsub_rn(nxo, half), ny = __fsub_rn(nyo, half);  // (LKStart::nx, ny, taken here: two registers fewer across the set-up)
     float pdx = 0.f, pdy = 0.f;
     for (int it = 0; it < max_count; it++) {
         const int inx = vh_floor(nx), iny = vh_floor(ny);
@@ -2363,9 +2400,23 @@ __device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const
         const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);
         n_iter++;
         int b1 = -cI[0], b2 = -cI[1];
-        lkh_sample_rows<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, [&](int k, int j, unsigned p01, unsigned p23) {
-            b1 = dot2(p23, tX[k][j].y, dot2(p01, tX[k][j].x, b1));
-            b2 = dot2(p23, tY[k][j].y, dot2(p01, tY[k][j].x, b2));
+        // the LDS part of strip j is read ahead of the strip's own arithmetic (pre), one strip of it before the sums below use it
+        u32x4_t yA = {0, 0, 0, 0}, yB = yA, xA = yA;  // Iy of columns 0, 1 | 2, 3 of the strip, a dword per row; Ix of columns 0, 1 of the last strip
+        lkh_sample_rows<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, [&](int j) {
+            yA = tl[64 * (2 * j)]; yB = tl[64 * (2 * j + 1)];
+            if (j == NS - 1) xA = tl[64 * (2 * NS)];
+        }, [&](int k, int j, int h, unsigned p) {
+            // (one chain per sum: two independent ones each fit the registers but measure no shorter, profiles/lkh_lds/resources.md)
+            if (j < NS - 1) {
+                b1 = dot2(p, h ? tX[k][j].y : tX[k][j].x, b1);
+                b2 = dot2(p, h ? yB[k] : yA[k], b2);
+            } else if (h == 0) {
+                b1 = dot2(p, xA[k], b1);
+                b2 = dot2(p, yA[k], b2);
+            } else {  // p = (sample of column WIN - 1 | 0), yB = (Ix | Iy) of that column
+                b1 = dot2(p, yB[k], b1);
+                b2 = dot2(p << 16, yB[k], b2);
+            }
         });
         if (lk_step(S, quad_sum_f32(b1), quad_sum_f32(b2), half, it, eps2, nx, ny, nxo, nyo, pdx, pdy)) break;
     }
@@ -2377,17 +2428,22 @@ __device__ __forceinline__ void LKHLevel<WIN>::operator()(const ImgDesc I, const
         if (!want_err) return;
         const StripWeights w = strip_weights(bilinear_weights(__fsub_rn(fx, (float)inx), __fsub_rn(fy, (float)iny)));
         const bool fast = J.pad >= VH_LV_PAD || lk_block_inside(J, inx, iny, WIN + 1, reach);
-        unsigned i01[4][NS], i23[4][NS];
-        lkh_sample_rows<NS, WIN>(I, ipx, ipy, r, fast_I || I.pad >= VH_LV_PAD, w0t, w0b, [&](int k, int j, unsigned p01, unsigned p23) {
-            i01[k][j] = p01; i23[k][j] = p23;
+        // the template is dead by now: its slots (chunks 2j + h) hold the samples of I while J is sampled -- 32 registers beside the byte rows of a
+        // border window were what four wavefronts per SIMD spilled
+        unsigned si[4];
+        lkh_sample_rows<NS, WIN>(I, ipx, ipy, r, fast_I || I.pad >= VH_LV_PAD, w0t, w0b, [](int) {}, [&](int k, int j, int h, unsigned p) {
+            si[k] = p;
+            if (k == 3) put(2 * j + h, si);
         });
         int se = 0;
-        lkh_sample_rows<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, [&](int k, int j, unsigned p01, unsigned p23) {
-            const short2v d01 = as_s2(p01) - as_s2(i01[k][j]), d23 = as_s2(p23) - as_s2(i23[k][j]);
-            const int d[4] = {d01.x, d01.y, d23.x, d23.y};
+        u32x4_t iA = {0, 0, 0, 0}, iB = iA;
+        lkh_sample_rows<NS, WIN>(J, inx, iny, r, fast, w.wt, w.wb, [&](int j) { iA = tl[64 * (2 * j)]; iB = tl[64 * (2 * j + 1)]; },
+                                 [&](int k, int j, int h, unsigned p) {
+            const short2v d2 = as_s2(p) - as_s2(h ? iB[k] : iA[k]);
+            const int d[2] = {d2.x, d2.y};
             const int cnt = WIN - 4 * j < 4 ? WIN - 4 * j : 4;
 #pragma unroll
-            for (int c = 0; c < 4; c++) se += (c < cnt && (k < 3 || rowd)) ? (d[c] < 0 ? -d[c] : d[c]) : 0;
+            for (int e = 0; e < 2; e++) se += (2 * h + e < cnt && (k < 3 || rowd)) ? (d[e] < 0 ? -d[e] : d[e]) : 0;
         });
         err = lk_err_of(quad_sum_f32(se), WIN);
     }
@@ -2404,12 +2460,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VH_LKH_WAVES
     int pt;
     float px, py;
     if (!lk_slot_start(job, slot, pt, px, py)) return;  // whole quads leave together
-    LKHLevel<WIN> lf{job.max_count, job.eps2, (int)(threadIdx.x & 3), 0, 0};
+    __shared__ __attribute__((aligned(16))) u32x4_t tmpl[LKHLevel<WIN>::LDS_CHUNKS * 64];  // (explicitly LDS pointers from here on: a generic-pointer store in
+    // the track code would turn the descriptor's scalar loads into per-lane vector loads, see k_lk3)
+    LKHLevel<WIN> lf{job.max_count, job.eps2, (int)(threadIdx.x & 3), 0, 0, (lds_u32x4)tmpl + threadIdx.x};
+    // lk_solve with the start point of each pass, the point index and the slot parked in LDS (LKHLevel::PARK) instead of carried in registers: the
+    // forward start point, which the gate needs again, is read a second time from the parked point index
+    // The slot is parked as 4 slot + r, the lane's index in the launch: r is read back with it after each pass and is not carried either.
+    lf.park(px, py, pt, 4 * slot + lf.r);
     LKResult R;
-    lk_solve(job, px, py, lf, R);
-    if (lf.r == 0) {
-        lk_store_track(job, pt, R.fx, R.fy, R.st, R.err, R.fbe);
-        lk_add_stats(job, (unsigned)slot, lf.n_iter, lf.n_setup);
+    lk_track(job.I, job.J, 0.f, 0.f, R.fx, R.fy, R.st, R.err, job.err_out != nullptr, lf);
+    R.fbe = 0.f;
+    u32x4_t id = lf.parked();
+    if (job.fbt >= 0.f) {
+        float bx = 0.f, by = 0.f, e2, sx, sy;
+        int st2 = 0;
+        if (R.st || job.fbe_out) {
+            lf.r = (int)(id[3] & 3);
+            lf.park(R.fx, R.fy, (int)id[2], (int)id[3]);
+            lk_track(job.J, job.I, 0.f, 0.f, bx, by, st2, e2, false, lf);
+            id = lf.parked();
+            R.fx = __uint_as_float(id[0]); R.fy = __uint_as_float(id[1]);  // (the same bits, not carried through the pass)
+        }
+        lk_point_start(job, (int)id[2], sx, sy);
+        R.fbe = lk_fb_gate(sx, sy, bx, by, job.fbt, st2, R.st);
+    }
+    if ((id[3] & 3) == 0) {
+        lk_store_track(job, (int)id[2], R.fx, R.fy, R.st, R.err, R.fbe);
+        lk_add_stats(job, id[3] >> 2, lf.n_iter, lf.n_setup);
     }
 }
 
@@ -2418,6 +2495,21 @@ static int launch_lkh(const void* job_tab, size_t tab_stride, int batch, int max
 {
     static const unsigned grp = getenv("VH_LKO_G") ? (unsigned)atoi(getenv("VH_LKO_G")) : 64u;  // (the group argument of launch_lko)
     hipLaunchKernelGGL(k_lk_h<WIN>, dim3((max_n + 15) / 16, batch), dim3(64), 0, s, job_tab, tab_stride, lk_group_arg(grp, batch));
+    return 0;
+}
+
+// test hook (vh_debug_lkh_residency): what the runtime makes of k_lk_h<15> -- workgroups per CU, registers, scratch bytes per lane, LDS bytes per
+// workgroup (static: the kernel is launched without dynamic LDS).  Launches nothing.
+int vh_lkh_residency(int out[4])
+{
+    const void* fn = reinterpret_cast<const void*>(k_lk_h<15>);
+    int blocks = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 64, 0);
+    if (e != hipSuccess) return (int)e;
+    hipFuncAttributes a;
+    e = hipFuncGetAttributes(&a, fn);
+    if (e != hipSuccess) return (int)e;
+    out[0] = blocks; out[1] = a.numRegs; out[2] = (int)a.localSizeBytes; out[3] = (int)a.sharedSizeBytes;
     return 0;
 }
 
@@ -2513,10 +2605,11 @@ static const long long g_lkh_min_tracks = getenv("VH_LKH_MIN") ? atoll(getenv("V
 // the whole vh_pyr_lk call), 4 wavefronts per track below (128 tracks: 30.8 against 35.3); 2 per track is never the fastest and is kept for the tests.
 // 15x15 coarse stages: the one-wave-per-track strip kernel up to 3000 tracks (2000: 20.2 / 27.9 us against 22.2 / 29.4 for 4 tracks per wavefront; 4000:
 // 25.6 / 36.6 against 23.1 / 29.2), 4 tracks per wavefront up to 10 000, 8 per wavefront above (12 000: 33.6 / 50.2 against 35.4 / 55.9 us; 8000: a tie),
-// 16 per wavefront (k_lk_h, three wavefronts per SIMD) from 128 000: both launches of sessions of 64 / 96 / 128 / 256 streams x 2000 tracks, routes 8 and 9 forced
+// 16 per wavefront (k_lk_h) from 128 000.  Measured with three wavefronts per SIMD: both launches of sessions of 64 / 96 / 128 / 256 streams x 2000 tracks, routes 8 and 9 forced
 // in one call on one box (profiles/lkh/threshold.json): 147.9 / 242.5 -> 143.6 / 235.0 us at 128 000 tracks, 208.5 / 351.4 -> 202.1 / 336.3 at 192 000, 267.0 / 456.6 ->
 // 254.5 / 432.9 at 256 000, 496.8 / 927.1 -> 460.2 / 897.9 at 512 000, shorter in every run.  128 000 is the smallest load measured, not a crossover: below it the
-// route is unmeasured, and the threshold may not go below 102 401, where a test pins k_lk_o<15> as the headline's route of its time.
+// route is unmeasured, and the threshold may not go below 102 401, where a test pins k_lk_o<15> as the headline's route of its time.  The protocol was
+// repeated with the build for four wavefronts per SIMD (profiles/lkh_lds/threshold.json, same loads, nothing below 128 000): the threshold stays.
 int vh_lk_route(int batch, int max_n, int win)
 {
     const int force = g_lk_force_generic.load(std::memory_order_relaxed);

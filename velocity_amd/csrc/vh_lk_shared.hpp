@@ -312,15 +312,20 @@ __device__ __forceinline__ const LKJob& lk_job_row(const void* job_tab, size_t t
 
 // Launch slot -> point (LKJob::order) and its start point in LK image coordinates; false: the slot is beyond the job's tracks.
 // UNIFORM: the slot is the same for the whole workgroup, and the point index and the start position come back as SCALARS (readfirstlane).
+// the start point of point `pt` in LK image coordinates
+__device__ __forceinline__ void lk_point_start(const LKJob& job, int pt, float& px, float& py)
+{
+    const float qx = ((gptr_f32)job.p_in)[2 * pt], qy = ((gptr_f32)job.p_in)[2 * pt + 1];
+    px = __fsub_rn(__fmul_rn(qx, job.in_scale), job.in_off[0]);
+    py = __fsub_rn(__fmul_rn(qy, job.in_scale), job.in_off[1]);
+}
 template <bool UNIFORM = false>
 __device__ __forceinline__ bool lk_slot_start(const LKJob& job, int slot, int& pt, float& px, float& py)
 {
     if (slot >= LK_N_OF(job)) return false;
     pt = job.order ? ((gptr_i32)job.order)[slot] : slot;
     if (UNIFORM) pt = __builtin_amdgcn_readfirstlane(pt);
-    const float qx = ((gptr_f32)job.p_in)[2 * pt], qy = ((gptr_f32)job.p_in)[2 * pt + 1];
-    px = __fsub_rn(__fmul_rn(qx, job.in_scale), job.in_off[0]);
-    py = __fsub_rn(__fmul_rn(qy, job.in_scale), job.in_off[1]);
+    lk_point_start(job, pt, px, py);
     if (UNIFORM) {
         px = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(px)));
         py = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(py)));
