@@ -583,6 +583,45 @@ VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
 VH_API int vh_session_set_fallback(vh_session* s, int on, const vh_match_params* params_host);
 /* counts_host int[batch][2]: steps of each stream (since its vh_session_init) in which the recovery ran / in which it found a model */
 VH_API int vh_session_recoveries(vh_session* s, int* counts_host);
+/* ---- replacing lost tracks with new corners (an extension beyond the reference; vh_version stays 111: a consumer tests for the symbols) --------------
+ * Default OFF: a step then queues exactly the launches it always did.  With the option on a session's rows are the frame-0 tracks of a slot's clip
+ * (vh_session_init_dev with *n_dev < n0) plus spare TAIL rows, which births fill in ascending order -- ids stays ascending and a history row never holds
+ * two tracks.  Per slot the session keeps born int32[n0] (the frame at which row g entered: 0 for frame-0 tracks, -1 for a row never used), tri uint8[n0]
+ * (p3[g] is defined: 1 for frame-0 tracks) and n_rows (rows used so far).  m0 = max(msv_frame, 0).
+ *   birth      at a stream's own frame f, behind that frame's bookkeeping and fcnMSV1_t, when f > m0, (f - m0) % every == 0 and f + baseline < nhist;
+ *              not when n_cur == 0, n_cur >= target, n_rows == n0, or the bounding rectangle of the live tracks (+ border, clipped like
+ *              boundingRect) is below 3 x 3 or below block.  goodFeaturesToTrack(frame[roi], max_new, quality, min_distance, mask, block, use_harris,
+ *              harris_k) + the ROI origin, mask = 0 where abs(x - rint(px)) < min_distance and abs(y - rint(py)) < min_distance for a live track
+ *              (px, py), then cornerSubPix on the whole frame; the first min(count, target - n_cur, n0 - n_rows) corners enter as rows n_rows.. with
+ *              vg = 1, vp = 0, tri = 0, born = f and history rows 0, 1, 4 of frame f.  S[f, 2] keeps the count from before the birth.
+ *   promotion  at frame born + baseline every live row with tri == 0 born then is triangulated: fcn2vintercept over its baseline + 1 rays (built as
+ *              fcnMSV1_t builds them) with origins float32(B[0, 0:3] - B[born + j, 0:3]).  p3[g] = C0, tri = 1, vp = 1 iff C0 is finite, lies in front
+ *              of every camera (C0_z + B[born + j, 5] > 0) and reprojects within max_reproj pixels in every frame of the baseline; otherwise the row
+ *              stays tracked with vp = 0.
+ * No step reads anything back: a step with a birth or promotion due queues a fixed launch sequence over all streams, in which the workgroup of a stream
+ * that is idle, not due or in need of nothing leaves at once.  Everything is created by vh_session_set_replenish (the detector's scratch of the
+ * session's context for 16 streams at a time, the mask planes, the state), so no step allocates and a step may be captured; the set call itself may not
+ * (-6, "call vh_session_set_replenish before capturing").  Refinement on a session with the option on selects, for whole clips too, the tracks alive
+ * through the window that are triangulated (tri). */
+typedef struct vh_replenish_params {
+    int every, baseline;        /* >= 1; baseline <= 63 */
+    int target;                 /* live tracks a birth refills to; <= 0: the slot's frame-0 track count */
+    int max_new;                /* corner budget of one birth, 1 .. 2048 */
+    double min_distance;        /* pixels, finite */
+    int border_x, border_y;     /* >= 0 */
+    double max_reproj;          /* pixels */
+    /* the detector and cornerSubPix settings (the clip's frame-0 settings) */
+    double quality, harris_k;
+    int block, use_harris;      /* block 1 .. 15 */
+    int subpix_win, subpix_iter; /* win 1 .. 7 */
+    double subpix_eps;
+} vh_replenish_params;
+/* params_host NULL: off (what was created is kept).  Otherwise on, with these parameters.  Call it before the slots are initialised: a slot initialised
+ * earlier counts as full (no births) until its next vh_session_init / vh_session_init_dev.  -1 for parameters outside the ranges above. */
+VH_API int vh_session_set_replenish(vh_session* s, const vh_replenish_params* params_host, void* stream);
+/* born_host int32[n0], tri_host uint8[n0] (either may be NULL), counts_host int[4] = {n_rows, rows born, promoted, rejected} since the slot's
+ * initialisation.  Waits for the device: for tests and for the results of a finished clip.  -1 when the option was never on. */
+VH_API int vh_session_replenish_state(vh_session* s, int slot, int* born_host, uint8_t* tri_host, int* counts_host);
 /* Packed track state of every stream for the cross-GPU exchange (RCCL all-gather, DESIGN.md "multi-GPU"):
  * out = device float32 [batch][8 + 3*n0]: {n_cur, n_pose, frame_i, klt_flags, t[3], res | p (n0 x 2) | ids (n0, int32 bits)} */
 /* Fused frame ingest for every stream of the session (vidExample.py:91 + KLT.py:111-113 in ONE pass over the BGR frames): bgr_frames_dev / gray_frames_dev =

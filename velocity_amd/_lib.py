@@ -68,6 +68,14 @@ class MatchParams(C.Structure):
                                        "min_good")] + [("quality", C.c_double)]
 
 
+class ReplenishParams(C.Structure):
+    """vh_replenish_params: the schedule, budget and gate of the replenishment, then the detector and cornerSubPix settings (replenish_params)."""
+
+    _fields_ = [("every", C.c_int), ("baseline", C.c_int), ("target", C.c_int), ("max_new", C.c_int), ("min_distance", C.c_double), ("border_x", C.c_int),
+                ("border_y", C.c_int), ("max_reproj", C.c_double), ("quality", C.c_double), ("harris_k", C.c_double), ("block", C.c_int), ("use_harris", C.c_int),
+                ("subpix_win", C.c_int), ("subpix_iter", C.c_int), ("subpix_eps", C.c_double)]
+
+
 class ClipCamera(C.Structure):
     """vh_clip_camera: the camera of one clip of vh_frame0_init_batch3 (frame size, row stride of its frame, how the caller holds K, K as host_K gives it)."""
 
@@ -179,6 +187,8 @@ _SIGS = {
     "vh_match_reserve_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(MatchParams), vp]),
     "vh_session_set_fallback": (C.c_int, [vp, C.c_int, C.POINTER(MatchParams)]),
     "vh_session_recoveries": (C.c_int, [vp, i32p]),
+    "vh_session_set_replenish": (C.c_int, [vp, C.POINTER(ReplenishParams), vp]),
+    "vh_session_replenish_state": (C.c_int, [vp, C.c_int, i32p, vp, i32p]),
     "vh_match_stage_ptrs": (C.c_int, [vp, C.POINTER(MatchStages)]),
     "vh_match_pairs": (C.c_int, [i32p]),
     "vh_match_launch_count": (C.c_longlong, []),
@@ -390,6 +400,14 @@ def match_params(d=None):
         raise TypeError(f"unknown matching parameters {sorted(bad)} (known: {sorted(MATCH_DEFAULTS)})")
     m = dict(MATCH_DEFAULTS, **d)
     return MatchParams(*[int(m[k]) for k, _ in MatchParams._fields_[:-1]], float(m["quality"]))
+
+
+def replenish_params(rep, det):
+    """rep: a driver.Replenish; det: the clip's driver.Frame0Settings (quality, block, harris_k, use_harris, subpix) -> ReplenishParams."""
+    win, it, eps = det.subpix
+    return ReplenishParams(int(rep.every), int(rep.baseline), 0 if rep.target is None else int(rep.target), int(rep.max_new), float(rep.min_distance),
+                           int(rep.border[0]), int(rep.border[1]), float(rep.max_reproj), float(det.quality), float(det.harris_k), int(det.block),
+                           1 if det.use_harris else 0, int(win), int(it), float(eps))
 
 
 def lk_params(d):

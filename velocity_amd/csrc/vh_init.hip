@@ -206,33 +206,12 @@ static void host_bounding_rect(const float* q, int n, int imw, int imh, int bx, 
 #define F0B_EMPTY 0xffffffffu
 static const size_t F0B_BUDGET = (size_t)1 << 30;  // the scratch block of a context sized by the first call (include/velocity_hip.h)
 
-struct F0Clip {
-    const uint8_t* roi;        // frame + boxb[2] * stride + boxb[0]
-    const uint8_t* im;         // the frame (cornerSubPix samples the whole frame)
-    unsigned long long seg;    // offset of the clip's response plane and key segment in the chunk's scratch
-    int rw, rh;                // ROI size (boxb)
-    float offx, offy;          // ROI origin
-    int boxa[4];
-    float q[8];
-    const uint8_t* mask;       // ROI-relative detection mask (NULL: none): pixels where it is 0 neither set the maximum nor become corners
-    int mstride;
-    int stride;                // row stride of the clip's frame
-    float* out;                // the clip's corner row (vh_frame0_init_batch: the 4 plate corners q go first)
-    int* n_out;                // the clip's corner count (NULL: only cnt[4 * clip + 2])
-    int max_corners, pad_;     // the clip's corner budget (the spacing and segmented-sort routes need one budget for the whole chunk)
-};
-static_assert(sizeof(F0Clip) == 128, "F0ClipPiece is sized by hand");
+// (F0Clip, the descriptor of one clip, and F0Cam, its camera: vh_ws.hpp -- the session's replenishment writes them on the device)
 struct F0ClipPiece {
     F0Clip c[F0B_PIECE];
 };
 struct F0Shared {
     double plate[12];
-};
-// A clip's camera (vh_clip_camera: frame size and intrinsics; the row stride is F0Clip's), in a table of its own beside the descriptors and uploaded the
-// same way: F0Clip stays at its 128 bytes.
-struct F0Cam {
-    double K[9];
-    int w, h;
 };
 struct F0CamPiece {
     F0Cam c[F0B_PIECE];
@@ -991,6 +970,44 @@ static int f0b_run_clips(vh_ctx* c, F0Clip* clips, int n, const F0Detect& D, hip
     if (r) return r;
     VH_CHECK(hipMemsetAsync(B.cnt, 0, sizeof(unsigned) * 4 * n, s));
     return f0b_detect(B, d_tab, clips, n, D, 0, s);
+}
+
+// ---- the detector on device-written ROI descriptors (vh_ws.hpp: VhRoiDetect; the session's replenishment) -----------------------------------------------
+int vh_roi_detect_reserve(vh_ctx* c, int clips, int w, int h, hipStream_t s, const char* remedy)
+{
+    return batch_reserve(c, clips, (size_t)clips * (size_t)w * (size_t)h, s, remedy);
+}
+
+int vh_roi_detect_scratch(vh_ctx* c, int clips, int w, int h, VhRoiScratch* out)
+{
+    InitBatchScratch& B = c->init_batch;
+    const size_t plane = (size_t)w * (size_t)h;
+    if (!B.main.p || B.clips_cap < clips || B.pix_cap < (size_t)clips * plane) return vh_fail(-1, "batched detector: the ROI scratch was not reserved");
+    out->tab = reinterpret_cast<F0Clip*>(B.tab); out->cam = reinterpret_cast<F0Cam*>(B.cam); out->cnt = B.cnt; out->plane = plane;
+    return 0;
+}
+
+int vh_roi_detect_run(vh_ctx* c, int clips, int w, int h, const VhRoiDetect& D, float* rows, int cap, hipStream_t s)
+{
+    if (clips < 1 || clips > 65535 || D.max_corners < 1 || D.max_corners > F0B_SEL_MAX || D.max_corners + 4 > cap || D.block < 1 || D.block > 15 || D.win < 1 ||
+        D.win > SUBPIX_MAXWIN)
+        return vh_fail(-1, "batched detector on device ROIs: bad arguments");
+    const F0Detect F = {D.max_corners, D.block, D.use_harris, D.quality, D.k, D.min_distance};
+    int r = f0b_detect_check(F, w, h, "batched detector on device ROIs");
+    if (r) return r;
+    VhRoiScratch R;
+    if ((r = vh_roi_detect_scratch(c, clips, w, h, &R))) return r;
+    // what f0b_detect reads of the host descriptors: the largest ROI (the grid) and the budgets
+    std::vector<F0Clip> sized((size_t)clips);
+    memset(sized.data(), 0, sizeof(F0Clip) * (size_t)clips);
+    for (int i = 0; i < clips; i++) { sized[i].rw = w; sized[i].rh = h; sized[i].max_corners = D.max_corners; }
+    if ((r = f0b_detect(c->init_batch, R.tab, sized.data(), clips, F, 0, s))) return r;
+    const int iters = D.max_iter < 1 ? 1 : (D.max_iter > 100 ? 100 : D.max_iter);
+    const double eps = D.eps < 0 ? 0 : D.eps;
+    hipLaunchKernelGGL(k_f0b_subpix, dim3((D.max_corners + 63) / 64, clips), dim3(64), 0, s, R.tab, R.cam, 0, cap, R.cnt, D.max_corners, D.win, iters, eps * eps,
+                       c->subpix_mask + subpix_mask_offset(D.win), rows);
+    VH_CHECK(hipGetLastError());
+    return 0;
 }
 
 int vh_detect_reserve(vh_ctx* c, int clips, size_t pixels, hipStream_t s) { return batch_reserve(c, clips, pixels, s, F0B_RESERVE_MATCH); }

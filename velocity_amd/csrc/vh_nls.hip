@@ -71,29 +71,7 @@ __global__ void k_pixel2uvec_f32(float cx, float cy, float f, const float* p, in
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void two_view_point(const double* A, const double* U, int nf, int nv, int i, double* c)
 {
-    double sx = 0, sy = 0, sz = 0, Bx = 0, By = 0, Bz = 0;
-    int npairs = 0;
-    for (int j = 0; j < nf; j++) { Bx += A[3 * j]; By += A[3 * j + 1]; Bz += A[3 * j + 2]; }
-    for (int j = 0; j < nf; j++) {
-        const double ux = U[(0 * nf + j) * nv + i], uy = U[(1 * nf + j) * nv + i], uz = U[(2 * nf + j) * nv + i];
-        for (int k = j + 1; k < nf; k++) {
-            const double vx = U[(0 * nf + k) * nv + i], vy = U[(1 * nf + k) * nv + i], vz = U[(2 * nf + k) * nv + i];
-            const double dAx = A[3 * j] - A[3 * k], dAy = A[3 * j + 1] - A[3 * k + 1], dAz = A[3 * j + 2] - A[3 * k + 2];
-            const double d = ux * vx + uy * vy + uz * vz;
-            const double e = ux * dAx + uy * dAy + uz * dAz;
-            const double f = vx * dAx + vy * dAy + vz * dAz;
-            const double g = 1 - d * d;
-            const double s1 = (d * f - e) / g, t1 = (f - d * e) / g;
-            sx += t1 * vx + s1 * ux;
-            sy += t1 * vy + s1 * uy;
-            sz += t1 * vz + s1 * uz;
-            npairs++;
-        }
-    }
-    const double den = 2.0 * npairs, m = (double)(nf - 1);
-    c[0] = (sx + Bx * m) / den;
-    c[1] = (sy + By * m) / den;
-    c[2] = (sz + Bz * m) / den;
+    two_view_rays(A, nf, [&](int j, double* u) { u[0] = U[(0 * nf + j) * nv + i]; u[1] = U[(1 * nf + j) * nv + i]; u[2] = U[(2 * nf + j) * nv + i]; }, c);
 }
 
 __global__ void k_two_view(const double* A, const double* U, int nf, int nv, double* out)

@@ -132,6 +132,41 @@ __device__ __forceinline__ void uvec_f32(float pu, float pv, float cx, float cy,
 }
 
 
+// fcn2vintercept (MSV.py:98-142) of ONE track: the mean of the pairwise closest-approach points over all C(nf, 2) frame pairs.  A: [nf][3] ray origins;
+// ray(j, u): the track's unit ray of frame j.  THE arithmetic of the triangulation: fcnMSV1_t reads its rays from a table (vh_nls.hip: two_view_point),
+// a newborn track's promotion builds them on the fly (vh_session.hip: k_replenish_promote).
+template <class Ray>
+__device__ __forceinline__ void two_view_rays(const double* A, int nf, Ray ray, double* c)
+{
+    double sx = 0, sy = 0, sz = 0, Bx = 0, By = 0, Bz = 0;
+    int npairs = 0;
+    for (int j = 0; j < nf; j++) { Bx += A[3 * j]; By += A[3 * j + 1]; Bz += A[3 * j + 2]; }
+    for (int j = 0; j < nf; j++) {
+        double u[3];
+        ray(j, u);
+        const double ux = u[0], uy = u[1], uz = u[2];
+        for (int k = j + 1; k < nf; k++) {
+            double v[3];
+            ray(k, v);
+            const double vx = v[0], vy = v[1], vz = v[2];
+            const double dAx = A[3 * j] - A[3 * k], dAy = A[3 * j + 1] - A[3 * k + 1], dAz = A[3 * j + 2] - A[3 * k + 2];
+            const double d = ux * vx + uy * vy + uz * vz;
+            const double e = ux * dAx + uy * dAy + uz * dAz;
+            const double f = vx * dAx + vy * dAy + vz * dAz;
+            const double g = 1 - d * d;
+            const double s1 = (d * f - e) / g, t1 = (f - d * e) / g;
+            sx += t1 * vx + s1 * ux;
+            sy += t1 * vy + s1 * uy;
+            sz += t1 * vz + s1 * uz;
+            npairs++;
+        }
+    }
+    const double den = 2.0 * npairs, m = (double)(nf - 1);
+    c[0] = (sx + Bx * m) / den;
+    c[1] = (sy + By * m) / den;
+    c[2] = (sz + Bz * m) / den;
+}
+
 // Residual point + forward-difference rows of the translation Jacobian (fcnNLS_t / fcnMSV1_t: b0 + dx e_k re-projected,
 // NLS.py:119-120).  (b + dx e_k) @ K = q + dx K[k,:], so the three perturbed projections reuse q; one reciprocal per
 // projection.  Same forward-difference values as the reference up to float64 rounding (~1e-16 rel).

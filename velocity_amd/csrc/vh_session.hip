@@ -44,6 +44,28 @@ struct SessFallback {
     int* counts;        // host [batch][2]: the recovery ran, it found a model
 };
 
+// Replenishment (vh_session_set_replenish; off unless asked for): lost tracks are replaced by new corners, which are triangulated on the device once they
+// have a baseline.  The state lives BESIDE the streams, not in them: SessStream keeps its layout and a step with the option off touches none of it.
+#define SESS_RP_CHUNK 16     // streams per detector pass (bounds the mask planes and the detector's response planes and key segments: they are per stream)
+#define SESS_RP_MAXBASE 63   // baseline + 1 ray origins and translations of a stream sit in LDS
+struct SessRepl {  // device resident, one per stream
+    int* born;     // [N0] the frame at which row g entered (0: a frame-0 track, -1: never used)
+    uint8_t* tri;  // [N0] p3[g] is defined
+    int n_rows;    // rows used so far: a birth takes rows n_rows.. (tail rows only)
+    int n_new;     // corners the detector found in the birth under way
+    int due;       // the birth under way got as far as the detector (k_replenish_setup -> k_replenish_append)
+    int cnt[3];    // since the slot's initialisation: rows born, promoted, rejected
+};
+struct SessReplenish {
+    int on, chunk;
+    vh_replenish_params P;
+    VhDeviceBlock dev;  // laid out by sess_rp_carve
+    SessRepl* d_rp;     // [batch]
+    SessRepl* h_rp;     // host mirror of the pointer fields
+    uint8_t* d_mask;    // [chunk] exclusion masks, w x h each (a stream's is ROI-relative: rows rw apart)
+    float* d_rows;      // [chunk][max_new + 4][2] corner rows of the detector pass
+};
+
 struct vh_session {
     vh_ctx* ctx;
     int batch, N0, nhist, w, h, msv_frame, k_is_f32;
@@ -55,6 +77,7 @@ struct vh_session {
     int* h_frame;      // per stream: frames stepped since its vh_session_init (host mirror of SessStream::frame_i; the
                        // reference fires fcnMSV1_t at `i == msvFrame` of EACH video, vidExample.py:155)
     SessFallback fb;
+    SessReplenish rp;
     // anchored points of each slot's clip (vh_session_set_anchors): world points the refinement holds fixed.  Kept beside the streams, not in them:
     // a step neither reads nor writes them
     uint8_t* d_anc_mask;  // [batch][N0] non-zero = track id is anchored
@@ -293,6 +316,211 @@ __global__ __launch_bounds__(256) void k_sess_init(SessStream* ss, const float* 
     }
 }
 
+// ---- replenishment ------------------------------------------------------------------------------------------------------------------------------
+// All four kernels are one workgroup per stream and latency-bound (a few hundred tracks, a chain of dependent loads); a workgroup whose stream is idle,
+// not due or in need of nothing leaves at once, so a step never has to know on the host which streams act.
+__host__ __device__ __forceinline__ bool repl_birth_due(int f, int msv_frame, int every, int baseline, int nhist)
+{
+    const int m0 = msv_frame > 0 ? msv_frame : 0;
+    return f > m0 && (f - m0) % every == 0 && f + baseline < nhist;
+}
+
+// rows of a slot that has just been initialised (k_sess_init ran): the frame-0 tracks are born at 0 and triangulated, the tail rows are free
+__global__ __launch_bounds__(256) void k_replenish_init(SessStream* ss, SessRepl* rp, int full)
+{
+    SessStream& S = *ss;
+    SessRepl& R = *rp;
+    const int N0 = S.N0, n = full ? N0 : S.n_cur;
+    for (int g = threadIdx.x; g < N0; g += 256) {
+        R.born[g] = g < n ? 0 : -1;
+        R.tri[g] = g < n ? 1 : 0;
+        if (g >= n && !full) { S.p3[3 * g] = 0.0; S.p3[3 * g + 1] = 0.0; S.p3[3 * g + 2] = 0.0; }  // (a slot's earlier clip may have left points there)
+    }
+    if (threadIdx.x == 0) { R.n_rows = n; R.n_new = 0; R.due = 0; R.cnt[0] = R.cnt[1] = R.cnt[2] = 0; }
+}
+
+// Promotion: one thread per candidate row.  Rays as fcnMSV1_t builds them, origins float32(B[0, 0:3] - B[born + j, 0:3]) widened (MSV.py:18), the point
+// by fcn2vintercept; the gate: finite, in front of every camera of the baseline, reprojected within max_reproj pixels in each of its frames.
+__global__ __launch_bounds__(256) void k_replenish_promote(SessStream* ss_all, SessRepl* rp_all, const uint8_t* const* frames, int msv_frame, int every,
+                                                           int baseline, double max_reproj)
+{
+    if (frames[blockIdx.x] == nullptr) return;
+    SessStream& S = ss_all[blockIdx.x];
+    SessRepl& R = rp_all[blockIdx.x];
+    const int f = S.frame_i, born = f - baseline, N0 = S.N0, nf = baseline + 1, tid = threadIdx.x;
+    if (f >= S.nhist || !repl_birth_due(born, msv_frame, every, baseline, S.nhist)) return;  // no birth ran `baseline` frames ago
+    __shared__ double s_A[3 * (SESS_RP_MAXBASE + 1)], s_T[3 * (SESS_RP_MAXBASE + 1)];
+    if (tid < nf)
+        for (int c = 0; c < 3; c++) {
+            s_A[3 * tid + c] = (double)__fsub_rn(S.B[c], S.B[14 * (born + tid) + c]);
+            s_T[3 * tid + c] = (double)S.B[14 * (born + tid) + 3 + c];
+        }
+    __syncthreads();
+    double K[9];
+    for (int k = 0; k < 9; k++) K[k] = S.K[k];
+    const int f32 = S.msv.f32_rays, n_rows = R.n_rows;
+    int good = 0, bad = 0;
+    for (int g = tid; g < n_rows; g += 256) {
+        if (!S.vg[g] || R.tri[g] || R.born[g] != born) continue;
+        auto pix = [&](int j, int row) { return S.P[sess_P(row, g, born + j, N0)]; };
+        double c[3];
+        two_view_rays(s_A, nf, [&](int j, double* u) {
+            if (f32) uvec_f32(pix(j, 0), pix(j, 1), (float)K[6], (float)K[7], (float)K[0], u);
+            else uvec_f64((double)pix(j, 0), (double)pix(j, 1), K[6], K[7], K[0], u);
+        }, c);
+        bool ok = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]);
+        double worst = 0.0;
+        for (int j = 0; j < nf && ok; j++) {
+            const double b0 = c[0] + s_T[3 * j], b1 = c[1] + s_T[3 * j + 1], b2 = c[2] + s_T[3 * j + 2];
+            ok = b2 > 0.0;
+            double u, v;
+            project_cam(K, b0, b1, b2, u, v);
+            const double du = u - (double)pix(j, 0), dv = v - (double)pix(j, 1);
+            const double e = sqrt(du * du + dv * dv);
+            ok = ok && isfinite(e);
+            worst = fmax(worst, e);
+        }
+        if (ok && worst < max_reproj) {
+            S.p3[3 * g] = c[0]; S.p3[3 * g + 1] = c[1]; S.p3[3 * g + 2] = c[2];
+            R.tri[g] = 1;
+            S.vp[g] = 1;
+            good++;
+        } else {
+            bad++;
+        }
+    }
+    if (good) atomicAdd(&R.cnt[1], good);
+    if (bad) atomicAdd(&R.cnt[2], bad);
+}
+
+// Birth, part 1: per stream of the chunk, the bounding rectangle of the live tracks (boundingRect, images.py:9-19), the exclusion mask and the stream's
+// detector descriptor -- written HERE, on the device, so that no step reads a ROI back.  A stream with nothing to do gets empty extents: every detector
+// tile of it leaves at once and its corner count comes out 0.
+struct ReplSetup {
+    F0Clip* tab;
+    F0Cam* cam;
+    unsigned* cnt;
+    uint8_t* mask;
+    float* rows;
+    size_t plane;
+    int cap, c0;
+};
+__global__ __launch_bounds__(256) void k_replenish_setup(SessStream* ss_all, SessRepl* rp_all, const uint8_t* const* frames, ReplSetup Q, int msv_frame,
+                                                         vh_replenish_params P)
+{
+    const int clip = blockIdx.x, b = Q.c0 + clip, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    SessStream& S = ss_all[b];
+    SessRepl& R = rp_all[b];
+    __shared__ float s_box[4][4];
+    __shared__ int s_roi[4];
+    const int n = S.n_cur, target = P.target > 0 ? P.target : (int)S.S[2];
+    bool go = frames[b] != nullptr && repl_birth_due(S.frame_i, msv_frame, P.every, P.baseline, S.nhist) && n > 0 && n < target && R.n_rows < S.N0;
+    uint8_t* mask = Q.mask + (size_t)clip * Q.plane;
+    if (go) {  // (uniform over the workgroup)
+        float mnx = 3.0e38f, mny = 3.0e38f, mxx = -3.0e38f, mxy = -3.0e38f;
+        for (int i = tid; i < n; i += 256) {
+            const float x = S.p_cur[2 * i], y = S.p_cur[2 * i + 1];
+            mnx = fminf(mnx, x); mxx = fmaxf(mxx, x); mny = fminf(mny, y); mxy = fmaxf(mxy, y);
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            mnx = fminf(mnx, __shfl_xor(mnx, o, 64)); mny = fminf(mny, __shfl_xor(mny, o, 64));
+            mxx = fmaxf(mxx, __shfl_xor(mxx, o, 64)); mxy = fmaxf(mxy, __shfl_xor(mxy, o, 64));
+        }
+        if (lane == 0) { s_box[wave][0] = mnx; s_box[wave][1] = mny; s_box[wave][2] = mxx; s_box[wave][3] = mxy; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 4; w++) {
+                mnx = fminf(mnx, s_box[w][0]); mny = fminf(mny, s_box[w][1]); mxx = fmaxf(mxx, s_box[w][2]); mxy = fmaxf(mxy, s_box[w][3]);
+            }
+            // (live tracks lie within a window of the frame: the clamps only keep the integer arithmetic below defined)
+            mnx = fminf(fmaxf(mnx, -1.0e6f), 1.0e6f); mny = fminf(fmaxf(mny, -1.0e6f), 1.0e6f);
+            mxx = fminf(fmaxf(mxx, -1.0e6f), 1.0e6f); mxy = fminf(fmaxf(mxy, -1.0e6f), 1.0e6f);
+            int x0 = vh_floor(mnx), y0 = vh_floor(mny);
+            const int bw = vh_floor(mxx) - x0 + 1, bh = vh_floor(mxy) - y0 + 1;
+            int x1 = x0 + bw + P.border_x, y1 = y0 + bh + P.border_y;
+            x0 -= P.border_x; y0 -= P.border_y;
+            s_roi[0] = max(x0, 1); s_roi[1] = min(x1, S.w); s_roi[2] = max(y0, 1); s_roi[3] = min(y1, S.h);
+        }
+        __syncthreads();
+    }
+    const int x0 = go ? s_roi[0] : 0, y0 = go ? s_roi[2] : 0;
+    const int rw = go ? s_roi[1] - x0 : 0, rh = go ? s_roi[3] - y0 : 0;
+    go = go && rw >= 3 && rh >= 3 && rw >= P.block && rh >= P.block;
+    if (go) {
+        // the mask: 255, and 0 in the square abs(x - rint(px)) < min_distance, abs(y - rint(py)) < min_distance around every live track
+        const size_t px = (size_t)rw * rh;  // (<= the plane: the ROI lies inside the slot's frame, which is at most the session's)
+        for (size_t i = tid; i < px; i += 256) mask[i] = 255;
+        __syncthreads();
+        const int r = (int)ceil(P.min_distance) - 1;  // the integer offsets d with abs(d) < min_distance
+        if (r >= 0)
+            for (int i = wave; i < n; i += 4) {  // one wavefront per track, its lanes over the cells of the square
+                const float fx = S.p_cur[2 * i], fy = S.p_cur[2 * i + 1];
+                if (!(fabsf(fx) < 1.0e6f && fabsf(fy) < 1.0e6f)) continue;
+                const int cx = (int)rintf(fx) - x0, cy = (int)rintf(fy) - y0;
+                const int xa = max(cx - r, 0), xb = min(cx + r + 1, rw), ya = max(cy - r, 0), yb = min(cy + r + 1, rh);
+                if (xa >= xb || ya >= yb) continue;
+                const int cw = xb - xa, cells = cw * (yb - ya);
+                for (int e = lane; e < cells; e += 64) {
+                    const int yy = ya + e / cw, xx = xa + e % cw;
+                    mask[(size_t)yy * rw + xx] = 0;
+                }
+            }
+    }
+    if (tid == 0) {
+        F0Clip C;
+        C.roi = go ? S.im0 + (size_t)y0 * S.stride + x0 : S.im0;
+        C.im = S.im0;
+        C.seg = (unsigned long long)clip * Q.plane;
+        C.rw = go ? rw : 0; C.rh = go ? rh : 0;
+        C.offx = (float)x0; C.offy = (float)y0;
+        for (int k = 0; k < 4; k++) C.boxa[k] = 0;
+        for (int k = 0; k < 8; k++) C.q[k] = 0.f;
+        C.mask = mask; C.mstride = rw;
+        C.stride = S.stride;
+        C.out = Q.rows + ((size_t)clip * Q.cap + 4) * 2;
+        C.n_out = &R.n_new;
+        C.max_corners = P.max_new; C.pad_ = 0;
+        Q.tab[clip] = C;
+        F0Cam M;
+        for (int k = 0; k < 9; k++) M.K[k] = S.K[k];
+        M.w = S.w; M.h = S.h;
+        Q.cam[clip] = M;
+        for (int k = 0; k < 4; k++) Q.cnt[4 * clip + k] = 0;
+        R.due = go ? 1 : 0;
+        R.n_new = 0;
+    }
+}
+
+// Birth, part 2: the first m = min(corners, target - n_cur, N0 - n_rows) refined corners enter as rows n_rows.. (the list is response-ordered, so a prefix
+// equals a smaller budget): tracked, not yet used for the pose (vg = 1, vp = 0), history rows 0, 1, 4 of the frame.  S[f, 2] keeps the count from before.
+__global__ __launch_bounds__(256) void k_replenish_append(SessStream* ss_all, SessRepl* rp_all, ReplSetup Q, vh_replenish_params P)
+{
+    const int clip = blockIdx.x, b = Q.c0 + clip, tid = threadIdx.x;
+    SessRepl& R = rp_all[b];
+    if (!R.due) return;
+    SessStream& S = ss_all[b];
+    const int N0 = S.N0, n = S.n_cur, n_rows = R.n_rows, f = S.frame_i, target = P.target > 0 ? P.target : (int)S.S[2];
+    const int found = min((int)Q.cnt[4 * clip + 2], P.max_new);
+    const int m = min(found, min(target - n, N0 - n_rows));
+    const float* row = Q.rows + ((size_t)clip * Q.cap + 4) * 2;
+    for (int k = tid; k < m; k += 256) {
+        const int g = n_rows + k;
+        const float x = row[2 * k], y = row[2 * k + 1];
+        S.p_cur[2 * (n + k)] = x; S.p_cur[2 * (n + k) + 1] = y;
+        S.ids[n + k] = g;
+        S.vg[g] = 1; S.vp[g] = 0;
+        R.tri[g] = 0; R.born[g] = f;
+        S.P[sess_P(0, g, f, N0)] = x;
+        S.P[sess_P(1, g, f, N0)] = y;
+        S.P[sess_P(4, g, f, N0)] = (float)f;
+    }
+    __syncthreads();  // every thread has read n, n_rows and due
+    if (tid == 0) {
+        if (m > 0) { S.n_cur = n + m; R.n_rows = n_rows + m; R.cnt[0] += m; }
+        R.due = 0;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------
@@ -494,11 +722,121 @@ static int session_recover(vh_session* s, const uint8_t* const* frames_dev, hipS
     return 0;
 }
 
+// The replenishment's device block as one walk (sizes only when base is null): the per-stream state, then the scratch of one chunk of streams
+static size_t sess_rp_carve(char* base, vh_session* s, int chunk, int max_new)
+{
+    VhCarver A(base);
+    SessReplenish& R = s->rp;
+    const size_t n0 = s->N0, plane = (size_t)s->w * (size_t)s->h;
+    R.d_rp = A.take<SessRepl>(s->batch);
+    for (int b = 0; b < s->batch; b++) {
+        int* born = A.take<int>(n0);
+        uint8_t* tri = A.take<uint8_t>(n0);
+        if (base) { R.h_rp[b].born = born; R.h_rp[b].tri = tri; }
+    }
+    R.d_mask = A.take<uint8_t>((size_t)chunk * plane);
+    R.d_rows = A.take<float>((size_t)chunk * (size_t)(max_new + 4) * 2);
+    return A.bytes();
+}
+
+extern "C" VH_API int vh_session_set_replenish(vh_session* s, const vh_replenish_params* params_host, void* stream)
+{
+    if (!s) return vh_fail(-1, "vh_session_set_replenish: null session");
+    SessReplenish& R = s->rp;
+    if (!params_host) { R.on = 0; return 0; }
+    const vh_replenish_params P = *params_host;
+    char msg[240];
+    if (P.every < 1 || P.baseline < 1 || P.baseline > SESS_RP_MAXBASE) {
+        snprintf(msg, sizeof(msg), "vh_session_set_replenish: every = %d, baseline = %d: every >= 1 and 1 <= baseline <= %d", P.every, P.baseline, SESS_RP_MAXBASE);
+        return vh_fail(-1, msg);
+    }
+    if (P.max_new < 1 || P.max_new > 2048) {
+        snprintf(msg, sizeof(msg), "vh_session_set_replenish: max_new = %d: 1 .. 2048 corners per birth", P.max_new);
+        return vh_fail(-1, msg);
+    }
+    if (!std::isfinite(P.min_distance) || !std::isfinite(P.max_reproj) || !std::isfinite(P.quality) || !std::isfinite(P.harris_k) || P.border_x < 0 || P.border_y < 0 ||
+        P.block < 1 || P.block > 15 || P.subpix_win < 1 || P.subpix_win > 7)
+        return vh_fail(-1, "vh_session_set_replenish: bad parameters (finite distances and thresholds, border >= 0, block 1 .. 15, subpix_win 1 .. 7)");
+    if (s->w < 3 || s->h < 3 || (P.min_distance >= 1 && (s->w > 32767 || s->h > 32767)))
+        return vh_fail(-1, "vh_session_set_replenish: frames of 3 x 3 up to 32767 x 32767");
+    static const char* const remedy = "call vh_session_set_replenish before capturing";
+    VH_BIND(s->ctx, stream);
+    hipStream_t st = bound_.s;
+    R.on = 0;  // off until everything below is there
+    const int chunk = s->batch < SESS_RP_CHUNK ? s->batch : SESS_RP_CHUNK;
+    int r = vh_roi_detect_reserve(s->ctx, chunk, s->w, s->h, st, remedy);
+    if (r) return r;
+    if (!R.h_rp) R.h_rp = new SessRepl[s->batch]();
+    const size_t need = sess_rp_carve(nullptr, s, chunk, P.max_new);
+    const bool fresh = need > R.dev.bytes;  // (a block that grows is a new block: the slots' rows start over as full)
+    if ((r = R.dev.reserve(need, st, "the replenishment's state and scratch", remedy, true))) return r;
+    sess_rp_carve(R.dev.p, s, chunk, P.max_new);
+    if (fresh) {
+        VH_CHECK(hipMemcpyAsync(R.d_rp, R.h_rp, sizeof(SessRepl) * s->batch, hipMemcpyHostToDevice, st));
+        VH_CHECK(hipStreamSynchronize(st));  // (h_rp is pageable: the copy has left it)
+        // a slot initialised before the option was on counts as full until its next initialisation
+        for (int b = 0; b < s->batch; b++) hipLaunchKernelGGL(k_replenish_init, dim3(1), dim3(256), 0, st, s->d_ss + b, R.d_rp + b, 1);
+        SESS_CHECK();
+    }
+    R.P = P; R.chunk = chunk; R.on = 1;
+    return 0;
+}
+
+extern "C" VH_API int vh_session_replenish_state(vh_session* s, int slot, int* born_host, uint8_t* tri_host, int* counts_host)
+{
+    if (!s || slot < 0 || slot >= s->batch) return vh_fail(-1, "vh_session_replenish_state: bad arguments");
+    const SessReplenish& R = s->rp;
+    if (!R.dev.p) return vh_fail(-1, "vh_session_replenish_state: the option was never on (vh_session_set_replenish)");
+    SessRepl rec;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&rec, R.d_rp + slot, sizeof(rec), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && born_host) e = hipMemcpy(born_host, R.h_rp[slot].born, sizeof(int) * (size_t)s->N0, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && tri_host) e = hipMemcpy(tri_host, R.h_rp[slot].tri, (size_t)s->N0, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { vh_set_error("vh_session_replenish_state: reading the state back", e, __FILE__, __LINE__); return (int)e; }
+    if (counts_host) { counts_host[0] = rec.n_rows; counts_host[1] = rec.cnt[0]; counts_host[2] = rec.cnt[1]; counts_host[3] = rec.cnt[2]; }
+    return 0;
+}
+
+// The replenishment of one step, behind the bookkeeping and fcnMSV1_t: promotions, then births.  The host knows from its frame counters whether ANY
+// stream is due, the way it knows the MSV frame; which streams act is decided on the device.
+static int session_replenish(vh_session* s, const uint8_t* const* frames_dev, const uint8_t* active, hipStream_t st)
+{
+    SessReplenish& R = s->rp;
+    const vh_replenish_params& P = R.P;
+    const int nb = s->batch;
+    bool promote = false, birth = false;
+    for (int b = 0; b < nb; b++) {
+        if (active && !active[b]) continue;
+        const int f = s->h_frame[b];
+        promote = promote || (f < s->nhist && repl_birth_due(f - P.baseline, s->msv_frame, P.every, P.baseline, s->nhist));
+        birth = birth || repl_birth_due(f, s->msv_frame, P.every, P.baseline, s->nhist);
+    }
+    if (promote)
+        hipLaunchKernelGGL(k_replenish_promote, dim3(nb), dim3(256), 0, st, s->d_ss, R.d_rp, frames_dev, s->msv_frame, P.every, P.baseline, P.max_reproj);
+    if (birth) {
+        VhRoiScratch D;
+        int r = vh_roi_detect_scratch(s->ctx, R.chunk, s->w, s->h, &D);
+        if (r) return r;
+        const VhRoiDetect det = {P.max_new, P.block, P.use_harris ? 1 : 0, P.quality, P.harris_k, P.min_distance, P.subpix_win, P.subpix_iter, P.subpix_eps};
+        for (int c0 = 0; c0 < nb; c0 += R.chunk) {
+            const int n = nb - c0 < R.chunk ? nb - c0 : R.chunk;
+            const ReplSetup Q = {D.tab, D.cam, D.cnt, R.d_mask, R.d_rows, D.plane, P.max_new + 4, c0};
+            hipLaunchKernelGGL(k_replenish_setup, dim3(n), dim3(256), 0, st, s->d_ss, R.d_rp, frames_dev, Q, s->msv_frame, P);
+            if ((r = vh_roi_detect_run(s->ctx, n, s->w, s->h, det, R.d_rows, P.max_new + 4, st))) return r;
+            hipLaunchKernelGGL(k_replenish_append, dim3(n), dim3(256), 0, st, s->d_ss, R.d_rp, Q, P);
+        }
+    }
+    SESS_CHECK();
+    return 0;
+}
+
 extern "C" VH_API void vh_session_destroy(vh_session* s)
 {
     if (!s) return;
     (void)hipDeviceSynchronize();
     sess_fb_release(s->fb);
+    s->rp.dev.release();
+    delete[] s->rp.h_rp;
     s->arena.release();
     delete[] s->h_ss;
     delete[] s->h_frame;
@@ -562,6 +900,7 @@ static int session_init(vh_session* s, int slot, const uint8_t* frame0, int stri
         VH_CHECK(hipMemsetAsync(s->d_anc_mask + (size_t)slot * s->N0, 0, (size_t)s->N0, st));
     }
     if (s->fb.counts) s->fb.counts[2 * slot] = s->fb.counts[2 * slot + 1] = 0;
+    if (s->rp.on) hipLaunchKernelGGL(k_replenish_init, dim3(1), dim3(256), 0, st, s->d_ss + slot, s->rp.d_rp + slot, 0);  // a new clip: its spare rows are free again
     SESS_CHECK();
     return 0;
 }
@@ -621,6 +960,7 @@ static int session_step(vh_session* s, const uint8_t* const* frames_dev, float t
     if (any) vh_launch_msv1_tab(&s->d_ss[0].msv, sizeof(SessStream), (ptrdiff_t)offsetof(SessStream, frame_i) - (ptrdiff_t)offsetof(SessStream, msv),
                                 s->msv_frame, s->msv_frame + 1, nb, st, reinterpret_cast<const void* const*>(frames_dev));
     if (any) hipLaunchKernelGGL(k_sess_after_msv, dim3(nb), dim3(256), 0, st, s->d_ss, frames_dev, s->msv_frame);
+    if (s->rp.on && (r = session_replenish(s, frames_dev, active, st))) return r;
     SESS_CHECK();
     return 0;
 }
@@ -841,7 +1181,7 @@ struct RefView {
     int with_points;  // ids and pw are in the record
 };
 // (table + workspace + view + the other arguments of the pack kernel: 2304 bytes of the 4 KB a launch may carry)
-static_assert(sizeof(RefReq) + sizeof(RefWs) + sizeof(RefView) + 5 * sizeof(void*) == 2304, "the refinement request travels in the kernel arguments");
+static_assert(sizeof(RefReq) + sizeof(RefWs) + sizeof(RefView) + 6 * sizeof(void*) == 2312, "the refinement request travels in the kernel arguments");
 
 static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_record* L)
 {
@@ -1016,9 +1356,11 @@ __device__ __forceinline__ void refine_unpack_window(const SessStream& S, const 
 // current survivors: a track that died after the window belongs to it.  256 ids at a time read row 4 of the frame-major history (coalesced over
 // tracks), a ballot + the four wavefronts' counts give each kept id its place, so the ids come out ascending (into W.ids).  !SELECT (first = 0 of a
 // clip that has just had its last frame): the slot's survivors ARE those tracks -- no pass, no scratch.  One workgroup per window.
+// rp_all (a session with the replenishment on, else null): every request is SELECTed -- the shortcut assumes that survivors were alive at frame 0 -- and
+// a selected track must also be triangulated (tri).
 template <bool SELECT>
 __global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, RefReq rq, int w0, int nf, RefWs W, RefView V, char* recs,
-                                                     const uint8_t* anc_mask, const double* anc_xyz)
+                                                     const uint8_t* anc_mask, const double* anc_xyz, const SessRepl* rp_all)
 {
     const int w = w0 + blockIdx.x, tid = threadIdx.x;
     const int slot = rq.slot[blockIdx.x], first = rq.first[blockIdx.x];
@@ -1034,7 +1376,7 @@ __global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, R
         __syncthreads();
         for (int g0 = 0; g0 < N0; g0 += 256) {  // (uniform trip count: every lane of every wavefront reaches the ballot and the barriers)
             const int g = g0 + tid;
-            bool alive = g < N0;
+            bool alive = g < N0 && (!rp_all || rp_all[slot].tri[g]);  // (replenished session: a row not yet triangulated has no world point)
             for (int f = 0; alive && f < nf; f++) alive = isfinite(S.P[sess_P(4, g, first + f, N0)]);
             const unsigned long long bal = __ballot(alive);
             if (lane == 0) s_cnt[wave] = __popcll(bal);
@@ -1119,7 +1461,8 @@ static int refine_request(const RefEntry& E, vh_session* s, const void* table, i
     std::vector<vh_refine_window> req;
     if (int r = own(fail, req)) return r;
     RefWs W;
-    const size_t need = refine_ws_layout(s, n, nf, reinterpret_cast<char*>(workspace), &W, E.windows);
+    const bool select = E.windows || s->rp.on;  // (replenished session: survivors need not have been alive at frame 0)
+    const size_t need = refine_ws_layout(s, n, nf, reinterpret_cast<char*>(workspace), &W, select);
     if (workspace_bytes < need) return fail("workspace of %zu bytes, %d %s of %d frames need %zu", workspace_bytes, n, E.noun, nf, need);
     RefView V;
     if (E.windows) {
@@ -1149,8 +1492,9 @@ static int refine_request(const RefEntry& E, vh_session* s, const void* table, i
         VH_BIND(s->ctx, stream);
         const uint8_t* mask = anchored ? s->d_anc_mask : nullptr;
         const double* xyz = anchored ? s->d_anc_xyz : nullptr;
-        if (E.windows) each_chunk(k_refine_pack<true>, bound_.s, mask, xyz);
-        else each_chunk(k_refine_pack<false>, bound_.s, mask, xyz);
+        const SessRepl* rp = s->rp.on ? s->rp.d_rp : nullptr;
+        if (select) each_chunk(k_refine_pack<true>, bound_.s, mask, xyz, rp);
+        else each_chunk(k_refine_pack<false>, bound_.s, mask, xyz, rp);
         SESS_CHECK();
     }
     // the windows' info = {iterations, converged} and trace go straight into the records
@@ -1176,7 +1520,7 @@ extern "C" VH_API size_t vh_session_refine_workspace(const vh_session* s, int ns
 {
     if (!s || nslots < 1 || nslots > s->batch || nf < 2 || nf - 1 > 255) { vh_fail(-1, "vh_session_refine_workspace: bad arguments"); return 0; }
     RefWs W;
-    return refine_ws_layout(s, nslots, nf, nullptr, &W);
+    return refine_ws_layout(s, nslots, nf, nullptr, &W, s->rp.on != 0);
 }
 
 extern "C" VH_API int vh_session_refine(vh_session* s, const int* slots_host, int nslots, int nf, int max_iter, void* recs_dev, void* workspace,

@@ -83,6 +83,30 @@ struct InitBatchScratch {
     int explicit_size;           // sized by vh_init_reserve_batch: calls run in chunks of that size instead of growing it
 };
 
+// the descriptor of one clip of the batched detector (vh_init.hip: the k_f0b_* kernels find a clip's ROI, frame, mask and scratch segment here)
+struct F0Clip {
+    const uint8_t* roi;        // frame + boxb[2] * stride + boxb[0]
+    const uint8_t* im;         // the frame (cornerSubPix samples the whole frame)
+    unsigned long long seg;    // offset of the clip's response plane and key segment in the chunk's scratch
+    int rw, rh;                // ROI size (boxb)
+    float offx, offy;          // ROI origin
+    int boxa[4];
+    float q[8];
+    const uint8_t* mask;       // ROI-relative detection mask (NULL: none): pixels where it is 0 neither set the maximum nor become corners
+    int mstride;
+    int stride;                // row stride of the clip's frame
+    float* out;                // the clip's corner row (vh_frame0_init_batch: the 4 plate corners q go first)
+    int* n_out;                // the clip's corner count (NULL: only cnt[4 * clip + 2])
+    int max_corners, pad_;     // the clip's corner budget (the spacing and segmented-sort routes need one budget for the whole chunk)
+};
+static_assert(sizeof(F0Clip) == 128, "F0ClipPiece is sized by hand");
+// A clip's camera (vh_clip_camera: frame size and intrinsics; the row stride is F0Clip's), in a table of its own beside the descriptors and uploaded the
+// same way: F0Clip stays at its 128 bytes.
+struct F0Cam {
+    double K[9];
+    int w, h;
+};
+
 struct vh_ctx {
     int batch, max_w, max_h, max_pts, sw, sh;
     VhDeviceBlock arena;  // everything below that lives on the device, laid out by ctx_carve (vh_api.hip)
@@ -218,6 +242,24 @@ int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_p
 int vh_fail(int code, const char* msg);
 int vh_subpix_masks_create(float** out);     // the cornerSubPix mask table of a new context (vh_init.hip; synchronous upload)
 void vh_init_scratch_free(vh_ctx* c);        // the frame-0 scratch and the mask table (vh_init.hip)
+// the batched detector + cornerSubPix on ROIs whose descriptors a kernel of the CALLER writes on the device (the session's replenishment, vh_session.hip):
+// nothing about a ROI is known on the host, so the tile grid is sized for a w x h frame and the tiles outside a clip's ROI leave at once
+struct VhRoiDetect {
+    int max_corners, block, use_harris;  // one corner budget for the chunk, 1 .. 2048
+    double quality, k, min_distance;
+    int win, max_iter;                   // cornerSubPix
+    double eps;
+};
+struct VhRoiScratch {
+    F0Clip* tab;     // [clips] descriptors, to be written by the caller's kernel (rw = rh = 0: nothing to do)
+    F0Cam* cam;      // [clips] w, h of each clip's frame (cornerSubPix clamps to them)
+    unsigned* cnt;   // [clips][4], to be zeroed by the caller's kernel; [2] = corners found
+    size_t plane;    // w x h: clip i owns segment seg = i * plane of the response planes and key segments
+};
+int vh_roi_detect_reserve(vh_ctx* c, int clips, int w, int h, hipStream_t s, const char* remedy);  // never shrinks; -6 inside a capture when it must grow
+int vh_roi_detect_scratch(vh_ctx* c, int clips, int w, int h, VhRoiScratch* out);                   // the pointers as they are now (-1: not reserved)
+// corners of clip i: rows + (i * cap + 4) * 2 (a row laid out like a frame-0 row: 4 unused entries in front), to be named by the descriptor's `out`
+int vh_roi_detect_run(vh_ctx* c, int clips, int w, int h, const VhRoiDetect& D, float* rows, int cap, hipStream_t s);
 // the batched frame-0 detector on whole images of different sizes, strides and corner budgets (vh_init.hip; the level images of vh_match_affine_batch)
 struct vh_detect_image {
     const uint8_t* im;

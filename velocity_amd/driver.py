@@ -14,14 +14,24 @@ from . import _lib as L
 
 
 class TrackerSession:
-    def __init__(self, K, width, height, n0, nhist=20, batch=1, lk_coarse=None, lk_fine=None, msv_frame=5, fallback=False, fallback_params=None):
+    def __init__(self, K, width, height, n0, nhist=20, batch=1, lk_coarse=None, lk_fine=None, msv_frame=5, fallback=False, fallback_params=None,
+                 replenish=None, spare=0, replenish_settings=None):
         """width x height: the LARGEST frame a slot can hold; K: the camera a slot has until init_stream / admit gives it another (vh_session_set_camera).
         fallback=True (default off: a step queues exactly what it always did): the recovery branch of KLTmain (KLT.py:130-133) for a stream whose coarse
         stage fails -- the affine from feature matching (vh_match_affine_batch over the failed streams; `fallback_params`: _lib.MATCH_DEFAULTS keys)
         drives the fine stage.  It costs ONE host read per step (the failure flags), so the host no longer runs ahead of the device, and such a step cannot
-        be captured into a graph: leave it off for clips that do not need it (include/velocity_hip.h, vh_session_set_fallback)."""
+        be captured into a graph: leave it off for clips that do not need it (include/velocity_hip.h, vh_session_set_fallback).
+        spare: rows behind the n0 a slot's frame 0 may fill -- the session has n0 + spare rows (self.n0), and a slot's clip may start with fewer tracks
+        than rows (init_stream with fewer points, admit with settings.cap below the rows).  replenish: None (default: a step queues exactly what it always
+        did), or a Replenish: lost tracks are replaced by new corners in the spare rows and triangulated on the device (vh_session_set_replenish);
+        replenish_settings: the Frame0Settings whose detector and sub-pixel settings the births use (default: the reference's).  state() then gains
+        born, tri and n_rows."""
         torch = L.torch_cuda()
         self.torch = torch
+        self.spare = int(spare)
+        if self.spare < 0:
+            raise ValueError(f"spare must be at least 0, got {spare}")
+        n0 = int(n0) + self.spare
         self.batch, self.w, self.h, self.n0, self.nhist = batch, width, height, n0, nhist
         self.ws = L.Workspace(batch, width, height, n0)
         self.lib = self.ws.lib
@@ -39,6 +49,10 @@ class TrackerSession:
         if self.fallback:
             mp = L.match_params(fallback_params)
             L.check(self.lib.vh_session_set_fallback(h, 1, C.byref(mp)), "vh_session_set_fallback")
+        self.replenish = replenish
+        if replenish is not None:
+            rp = L.replenish_params(replenish, replenish_settings or Frame0Settings())
+            L.check(self.lib.vh_session_set_replenish(h, C.byref(rp), L.stream_ptr()), "vh_session_set_replenish")
         self._frames = torch.zeros(batch, dtype=torch.int64, device="cuda")  # device table of frame pointers
         # the lifetime rule of a slot: its current frame (the im0 of its next step) and the device inputs of its initialisation (read by a kernel that may
         # not have run yet) stay alive until the slot is initialised again -- by init_stream or by admit, which both replace the slot's entries here
@@ -61,7 +75,8 @@ class TrackerSession:
             self._cam[slot] = cam
 
     def init_stream(self, slot, frame0, p, p3, vp, t0, time0=0.0, frame_no=0.0, res0=0.0, K=None):
-        """Frame-0 state (vidExample.py:116-131): points p [n0,2], world points p3 [n0,3], pose mask vp, plate pose t0.  numpy arrays or CUDA tensors
+        """Frame-0 state (vidExample.py:116-131): points p [n,2], world points p3 [n,3], pose mask vp, plate pose t0; n = the session's rows, or fewer:
+        the rows behind them are tracks that never existed (spare rows).  numpy arrays or CUDA tensors
         (tensors of the right dtype are used in place: a stream can be re-initialised without touching the host).  The slot takes its frame size from
         frame0.shape (at most the session's) and its intrinsics from K (None: the session's)."""
         torch = self.torch
@@ -75,9 +90,16 @@ class TrackerSession:
             return L.to_dev(a if isinstance(a, torch.Tensor) else np.asarray(a).astype(np_dtype), t_dtype)
 
         pd, p3d, vpd = dev(p, np.float32, torch.float32), dev(p3, np.float64, torch.float64), dev(vp, np.uint8, torch.uint8)
-        assert pd.shape == (self.n0, 2) and p3d.shape == (self.n0, 3) and vpd.shape == (self.n0,)
+        n = pd.shape[0]
+        assert 1 <= n <= self.n0 and pd.shape == (n, 2) and p3d.shape == (n, 3) and vpd.shape == (n,)
         t0 = np.ascontiguousarray(np.asarray(t0, np.float32).reshape(3))
         self._set_camera(slot, fw, fh, K)
+        if n < self.n0:  # fewer tracks than rows: the count travels as a device value, like admit's (vh_session_init_dev)
+            t0d, r0d, nd = L.to_dev(t0, torch.float32), L.to_dev(np.array([res0], np.float64), torch.float64), L.to_dev(np.array([n], np.int32), torch.int32)
+            L.check(self.lib.vh_session_init_dev(self.handle, slot, L.dptr(f0), fw, L.dptr(pd), L.dptr(p3d), L.dptr(vpd), L.dptr(t0d), L.dptr(r0d), L.dptr(nd),
+                                                 float(time0), float(frame_no), L.stream_ptr()), "vh_session_init_dev")
+            self._keep[slot], self._init_keep[slot], self._frame_i[slot] = f0, (pd, p3d, vpd, t0d, r0d, nd), 0
+            return
         L.check(self.lib.vh_session_init(self.handle, slot, L.dptr(f0), fw, L.dptr(pd), L.dptr(p3d), L.dptr(vpd), t0.ctypes.data_as(L.f32p),
                                          float(time0), float(frame_no), float(res0), L.stream_ptr()), "vh_session_init")
         self._keep[slot], self._init_keep[slot], self._frame_i[slot] = f0, (pd, p3d, vpd), 0
@@ -92,7 +114,10 @@ class TrackerSession:
         the stream's state does not hold.  anchor="plate": every admitted clip's tracks 0..3 -- the plate corners, whose frame-0 coordinates come from the
         plate's known size -- become the anchors of its slot (set_anchors as a snapshot, right behind the initialisation)."""
         assert anchor in (None, "plate"), anchor
-        assert settings.cap == self.n0, "the session's track capacity must be 4 + max_corners"
+        if self.spare or self.replenish is not None:
+            assert settings.cap <= self.n0, "the session's rows must hold 4 + max_corners tracks"
+        else:
+            assert settings.cap == self.n0, "the session's track capacity must be 4 + max_corners"
         assert all(e[1].is_cuda and e[1].dtype == self.torch.uint8 and e[1].dim() == 2 and e[1].is_contiguous() for e in entries)
         Ks = [e[5] if len(e) > 5 else None for e in entries]
         for (slot, f0, *_), _K in zip(entries, Ks):
@@ -240,6 +265,14 @@ class TrackerSession:
         L.check(self.lib.vh_session_recoveries(self.handle, out.ctypes.data_as(L.i32p)), "vh_session_recoveries")
         return out
 
+    def replenish_state(self, slot=0):
+        """(born int32 [N0], tri uint8 [N0], counts int32 [4] = n_rows, rows born, promoted, rejected) of the slot (vh_session_replenish_state: waits for
+        the device; for tests and for the results of a finished clip)."""
+        born, tri, counts = np.zeros(self.n0, np.int32), np.zeros(self.n0, np.uint8), np.zeros(4, np.int32)
+        L.check(self.lib.vh_session_replenish_state(self.handle, int(slot), born.ctypes.data_as(L.i32p), tri.ctypes.data, counts.ctypes.data_as(L.i32p)),
+                "vh_session_replenish_state")
+        return born, tri, counts
+
     def view(self, slot=0):
         v = L.SessionView()
         L.check(self.lib.vh_session_ptrs(self.handle, slot, C.byref(v)), "vh_session_ptrs")
@@ -261,12 +294,18 @@ class TrackerSession:
 
     def state(self, slot=0):
         """Host copy of the stream state: dict(vg, vp, p, P, B, S, p3, t, res, n_cur, n_pose, frame_i, klt_flags).
-        P comes back in the reference's [5, N0, nhist] layout (the device keeps it frame-major, [nhist, 5, N0]: include/velocity_hip.h)."""
+        P comes back in the reference's [5, N0, nhist] layout (the device keeps it frame-major, [nhist, 5, N0]: include/velocity_hip.h).
+        With replenish on also born int32 [N0], tri uint8 [N0] and n_rows (replenish_state)."""
         v = self.view(slot)
         n0, nh = self.n0, self.nhist
         n_cur = int(self._rd(v.n_cur, 1, np.int32)[0])
         n_pose = int(self._rd(v.n_pose, 1, np.int32)[0])
+        extra = {}
+        if self.replenish is not None:
+            born, tri, counts = self.replenish_state(slot)
+            extra = dict(born=born, tri=tri, n_rows=int(counts[0]))
         return dict(
+            **extra,
             vg=self._rd(v.vg, n0, np.uint8).astype(bool), vp=self._rd(v.vp, n0, np.uint8).astype(bool),
             p=self._rd(v.p, 2 * n_cur, np.float32).reshape(n_cur, 2), ids=self._rd(v.ids, n_cur, np.int32),
             P=np.ascontiguousarray(self._rd(v.P, 5 * n0 * nh, np.float32).reshape(nh, 5, n0).transpose(1, 2, 0)), B=self._rd(v.B, nh * 14, np.float32).reshape(nh, 14),
@@ -762,6 +801,36 @@ class Frame0Settings:
         return tuple(torch.empty(shape, dtype=dtype, device="cuda") for shape, dtype in layout)
 
 
+@dataclasses.dataclass(frozen=True)
+class Replenish:
+    """Replacing lost tracks with new corners (TrackerSession(replenish=...), vh_session_set_replenish; an extension beyond the reference, default off).
+    every      a birth runs at a stream's own frame f when f > max(msv_frame, 0), (f - max(msv_frame, 0)) % every == 0 and f + baseline < nhist
+    baseline   a newborn is triangulated from frames born .. born + baseline and joins the pose tracks at frame born + baseline if its point passes
+    target     births refill a stream up to this many live tracks (None: the slot's frame-0 track count)
+    max_new    corner budget of one birth (at most 2048)
+    min_distance   new corners keep this distance (pixels) from each other and, as a square of that half-size, from every live track
+    border     (x, y) pixels added around the bounding rectangle of the live tracks: the region searched
+    max_reproj a newborn's point must reproject within this many pixels in every frame of its baseline (the reference's coarse forward-backward threshold)
+    The detector and sub-pixel settings are the clip's Frame0Settings (quality, block, harris_k, use_harris, subpix)."""
+    every: int = 5
+    baseline: int = 5
+    target: typing.Optional[int] = None
+    max_new: int = 256
+    min_distance: float = 10.0
+    border: tuple = (0, 0)
+    max_reproj: float = 1.0
+
+    def __post_init__(self):
+        if int(self.every) < 1 or int(self.baseline) < 1:
+            raise ValueError(f"every and baseline must be at least 1, got {self.every}, {self.baseline}")
+        if not 1 <= int(self.max_new) <= 2048:
+            raise ValueError(f"max_new must be 1 .. 2048, got {self.max_new}")
+        if self.target is not None and int(self.target) < 1:
+            raise ValueError(f"target must be None or at least 1, got {self.target}")
+        if not (math.isfinite(float(self.min_distance)) and math.isfinite(float(self.max_reproj))):
+            raise ValueError("min_distance and max_reproj must be finite")
+
+
 class Admitted(typing.NamedTuple):
     """What frame 0 of a clip leaves besides the stream's state: the ROIs (host ints) and the plate pose -- R0 [9] float64, res0 [1] float64: device
     views out of TrackerSession.admit, host values (R0 [3, 3], res0 a float) into clip_result."""
@@ -838,7 +907,27 @@ def frame0_batch(frames, qs, K, plate="Chile", roi_border=(700, 500), max_corner
     return out
 
 
-def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=None, ba=None):
+def replenish_result(st, n, baseline):
+    """What the replenishment did in a clip of n frames, from the stream's state with born / tri / n_rows (a pure function): per-frame counts of the rows
+    born, promoted (at born + baseline) and rejected there (alive at that frame, not triangulated), the rows left, and per row its birth frame and tri."""
+    k = int(st["n_rows"])
+    born, tri = np.asarray(st["born"][:k], np.int32), np.asarray(st["tri"][:k], np.uint8)
+    new = born > 0
+    due = np.minimum(born + int(baseline), n - 1)
+    judged = new & (born + int(baseline) <= n - 1) & np.isfinite(st["P"][4, np.arange(k), due])
+
+    def per_frame(rows):
+        return np.bincount(born[rows] + int(baseline), minlength=n)[:n].astype(np.int64)
+
+    return dict(born=np.bincount(born[new], minlength=n)[:n].astype(np.int64), promoted=per_frame(new & (tri == 1)), rejected=per_frame(judged & (tri == 0)),
+                rows_left=int(len(st["vg"]) - k), born_frame=born.copy(), tri=tri.copy())
+
+
+def replenish_line(r):
+    return f"Replenish: {int(r['born'].sum())} tracks born, {int(r['promoted'].sum())} promoted, {int(r['rejected'].sum())} rejected, {r['rows_left']} rows left"
+
+
+def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=None, ba=None, replenish=None):
     """THE result of a clip, whichever driver ran it (a pure function: numpy in, fresh arrays out, no device).
     st       the stream's state after the clip's last frame (TrackerSession.state / ExportedState.result).  Its session may have been sized for longer
              clips and has room for 4 + max_corners tracks: the history is cut to the clip's n frames and to the k tracks frame 0 found (S[0, 2]:
@@ -847,8 +936,13 @@ def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=
     seconds  the wall time the `Processed ...` line reports; step_seconds: the mean time of a frame step, which rows 1.. of the procTime column carry
              (row 0: 0) unless `proc` gives the column frame by frame (run_sequence's live table)
     ba       the clip's refinement (unpack_refine's dict; None: not asked for): the result gains the key "ba" and the lines gain ba_line(ba) at the end
+    replenish  the clip's Replenish (None: the option was off): st then carries born / tri / n_rows, the track rows are cut to the n_rows the births
+             used instead of to the k of frame 0, and the result gains "replenish" (replenish_result) and one line behind the summary
     `lines` = the start line, TABLE_HEADER, one table_row per frame and the two summary_lines."""
     n, k = clip["n"], int(st["S"][0, 2])
+    k0 = k
+    if replenish is not None:
+        k = int(st["n_rows"])
     S = st["S"][:n].copy()
     S[0, 1] = 0.0
     S[1:, 1] = step_seconds
@@ -858,11 +952,14 @@ def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=
     lines = [f"Starting image processing on {clip['name']} ...", TABLE_HEADER] + [table_row(S[i]) for i in range(n)]  # vidExample.py:50
     lines += summary_lines(S, n, clip["frame_numbers"], seconds)
     extra = {}
+    if replenish is not None:
+        extra["replenish"] = replenish_result(st, n, replenish.baseline)
+        lines.append(replenish_line(extra["replenish"]))
     if ba is not None:
         lines.append(ba_line(ba))
         extra["ba"] = ba
     return dict(S=S, B=B, P=st["P"][:, :k, :n].copy(), vg=st["vg"][:k].copy(), vp=st["vp"][:k].copy(), p=st["p"].copy(), p3=st["p3"][:k].copy(),
-                ids=st["ids"].copy(), n_tracks0=k, t0=B[0, 0:3].copy(), R0=np.array(f0.R0, np.float64).reshape(3, 3), res0=float(f0.res0), boxa=tuple(f0.boxa),
+                ids=st["ids"].copy(), n_tracks0=k0, t0=B[0, 0:3].copy(), R0=np.array(f0.R0, np.float64).reshape(3, 3), res0=float(f0.res0), boxa=tuple(f0.boxa),
                 boxb=tuple(f0.boxb), klt_flags=st["klt_flags"], recoveries=recoveries, lines=lines, seconds=seconds, ms_per_frame=1e3 * step_seconds,
                 sessions=sessions, **extra)
 
@@ -870,7 +967,7 @@ def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=
 def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01,
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
                  out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
-                 refine_window=None, refine_stride=None, refine_anchor=None):
+                 refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0):
     """The packaged counterpart of vidExample.py:52-178 (minus video decode and plots) on one clip.
 
     frames  sequence of n uint8 [H, W] gray frames (numpy arrays or CUDA tensors): what `cv2.cvtColor(cap.read(), BGR2GRAY)` / `cv2.imread(.., 0)` hands
@@ -900,6 +997,9 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             plate.  "ba" gains nothing but `anchor`; its `nfix` says how many anchors were alive (per window in the windowed form: 0 = that window ran
             free), and the BA line says so too.  What it does not do: a window with first > 0 places its anchors by the tracker's own B[first, 3:6],
             windows stay separate solves, and the plate's frame-0 pose error is inherited.
+    replenish, spare   None (default: nothing new is queued), or a Replenish: the session gets `spare` rows behind the 4 + max_corners of frame 0, lost
+            tracks are replaced by new corners there and triangulated on the device (TrackerSession(replenish=...); detector and sub-pixel settings: the
+            frame-0 ones).  The result's track rows are then the rows used, it gains "replenish" (replenish_result) and one line follows the summary.
     out     line sink (default print); clock: time source for the procTime column / fps line (default time.perf_counter).
 
     Prints the reference's header, one 9-column row per frame (vidExample.py:165) and the `Speed = ... +/- ... km/h / Res = ...` summary (:177-178).
@@ -925,7 +1025,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     dev = _to_device(frames, non_blocking=True)
     H, W = dev[0].shape
     ses = _SessionSet(1, 1, max_corners).create(K, W, H, settings, n, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback,
-                                                 fallback_params=fallback_params)[0]
+                                                 fallback_params=fallback_params, **_replenish_kw(replenish, spare, settings))[0]
     f0 = ses.admit([(0, dev[0], q, times[0], frame_numbers[0])], settings, anchor=refine_anchor)[0]
     view = ses.view(0)
     proc = np.zeros(n)
@@ -950,10 +1050,19 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
         (rh, ba_of), = _refine_finished(ses, [(0, n, None)], win, stride)
         ba = _tag_anchor(ba_of(rh.result()), refine_anchor)
     st, recoveries, f0 = ses.state(0), ses.recoveries()[0], f0.host()
-    res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None, ba)
-    for line in res["lines"][-(3 if refine else 2) if live else 2:]:  # (not live: the whole clip ran first, and every row carries the mean time per frame)
+    res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None, ba,
+                      replenish=replenish)
+    tail = 2 + (1 if refine else 0) + (1 if replenish is not None else 0)
+    for line in res["lines"][-tail if live else 2:]:  # (not live: the whole clip ran first, and every row carries the mean time per frame)
         emit(line)
     return res
+
+
+def _replenish_kw(replenish, spare, settings):
+    """The TrackerSession keywords of a driver's replenish / spare arguments (none when the option is off and no spare rows are asked for)."""
+    if replenish is None and not spare:
+        return {}
+    return dict(replenish=replenish, spare=int(spare), replenish_settings=settings)
 
 
 def session_groups(streams, tracks=2000):
@@ -1017,7 +1126,7 @@ class _SessionSet:
 
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
                   msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
-                  refine_window=None, refine_stride=None, refine_anchor=None):
+                  refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name, K]) of ONE length -- the
     frame size and the intrinsics are each clip's own ("K": that clip's camera, default the K argument); the sessions are created at the elementwise
     maximum of the sizes and a frame step is sized for it, so clips of one camera type batch best.  One length stays required: a step advances every
@@ -1030,7 +1139,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     `lines` = that clip's table and summary, printed through `out` if given), each equal to what run_sequence returns for the clip alone.  refine="ba": as in
     run_sequence; all the clips of a session are refined by ONE TrackerSession.refine after the last frame -- with refine_window=W (and clips of at least
     W frames) all the windows of all the clips of a session by ONE TrackerSession.refine_windows request.  refine_anchor="plate": as in run_sequence,
-    for every clip."""
+    for every clip.  replenish, spare: as in run_sequence, for every clip (the births of all the streams of a session are one launch sequence)."""
     import time as _time
 
     refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
@@ -1046,7 +1155,8 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     group = _SessionSet(nclip, sessions, max_corners)
     for hs in group.hip_streams[1:]:
         hs.wait_stream(group.hip_streams[0])  # the frame uploads above ran on the current stream
-    sess = group.create(K, W, H, settings, n, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params)
+    sess = group.create(K, W, H, settings, n, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params,
+                        **_replenish_kw(replenish, spare, settings))
     members = [list(range(a, a + size)) for a, size in zip(group.first, group.sizes)]  # session -> its clips, in slot order
     times = np.stack([np.asarray(c["times"], np.float32) for c in clips])  # [clip, frame]
     fnos = np.stack([np.asarray(c.get("frame_numbers", np.arange(n)), np.float32) for c in clips])
@@ -1079,7 +1189,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
         for j, b in enumerate(mem):
             meta = dict(n=n, name=clips[b].get("name", f"clip {b}"), frame_numbers=clips[b].get("frame_numbers", list(range(n))))
             results.append(clip_result(ses.state(j), meta, f0[b].host(), seconds, step_seconds, len(sess), ses.recoveries()[j],
-                                       ba=_tag_anchor(refined[g][j], refine_anchor) if refine else None))
+                                       ba=_tag_anchor(refined[g][j], refine_anchor) if refine else None, replenish=replenish))
             if out is not None:
                 for ln in results[-1]["lines"]:
                     out(ln)
@@ -1146,7 +1256,7 @@ def queue_plan(lengths, streams, sessions=1):
 
 def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, max_size=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
               harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=None, use_harris=True, min_distance=0.0, fallback=False,
-              fallback_params=None, refine=None, refine_window=None, refine_stride=None, refine_anchor=None):
+              fallback_params=None, refine=None, refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0):
     """A queue of clips of ANY length on `streams` resident streams: what run_sequences is for clips of one length.  `clips` = any iterable of
     dict(frames, q, times[, frame_numbers, name, K]), each of >= 2 frames and with its own frame size and intrinsics ("K": default the K argument); it is consumed lazily -- a clip is pulled when a slot is free
     for it and its frames go up then, so at most `streams` clips are resident -- and may hold more clips than fit on the device at once.
@@ -1168,7 +1278,9 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
     exports, one TrackerSession.refine per clip length among them; the records travel with the exports and the slots are free at the next step as ever.
     refine_window=W (refine_stride: as in run_sequence): the clips of at least W frames that finish at a step go through ONE TrackerSession.refine_windows
     request of their session, whatever their lengths (their "ba" is the merged dict); the per-length calls remain for clips shorter than W.
-    refine_anchor="plate": as in run_sequence, for every clip (a slot's anchors are set at its clip's admission and cleared by the next one)."""
+    refine_anchor="plate": as in run_sequence, for every clip (a slot's anchors are set at its clip's admission and cleared by the next one).
+    replenish, spare: as in run_sequence, for every clip.  A finished clip's born / tri are read right behind its export (vh_session_replenish_state
+    waits for the device: with the option on the loop waits once per finished clip)."""
     import time as _time
 
     refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
@@ -1220,13 +1332,15 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
     t_begin = _time.perf_counter()
 
     def deliver(entry):
-        handle, index, clip, f0, t0, ba = entry[2]
+        handle, index, clip, f0, t0, ba = entry[2][:6]
         st = handle.result()
+        if replenish is not None:
+            st.update(entry[2][6])
         if ba is not None:
             ba = _tag_anchor(ba[1](ba[0].result()), refine_anchor)
         x = entry[1].numpy().copy()
         seconds = _time.perf_counter() - t0  # the clip's time in the queue: every row carries the mean over its frame steps
-        res = results[index] = clip_result(st, clip, f0._replace(R0=x[0:9], res0=x[9]), seconds, seconds / (clip["n"] - 1), G, handle.recoveries, ba=ba)
+        res = results[index] = clip_result(st, clip, f0._replace(R0=x[0:9], res0=x[9]), seconds, seconds / (clip["n"] - 1), G, handle.recoveries, ba=ba, replenish=replenish)
         entry[2] = None
         pending[:] = [e for e in pending if e is not entry]
         if out is not None:
@@ -1245,7 +1359,8 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
         poll()
         if not sess:  # the first clips have been pulled: the (largest) frame size is known
             H, W = size[0]
-            group.create(K, W, H, settings, nhist, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params)
+            group.create(K, W, H, settings, nhist, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params,
+                         **_replenish_kw(replenish, spare, settings))
             for ses, hs in zip(sess, group.hip_streams):
                 with torch.cuda.stream(hs):  # the frame-0 scratch for a full house, so that no later admission grows it (growing waits for the stream)
                     L.check(ses.lib.vh_init_reserve_batch(ses.ws.handle, ses.batch, W, H, L.stream_ptr()), "vh_init_reserve_batch")
@@ -1302,7 +1417,11 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                     entry[1].copy_(torch.cat([f0.R0, f0.res0]), non_blocking=True)
                     handle.event.record()
                     c = pulled.pop(k)
-                    entry[2] = [handle, k, dict(n=c["n"], name=c["name"], frame_numbers=c["frame_numbers"]), f0, t0, None]
+                    extra = None
+                    if replenish is not None:
+                        born, tri, counts = ses.replenish_state(j)
+                        extra = dict(born=born, tri=tri, n_rows=int(counts[0]))
+                    entry[2] = [handle, k, dict(n=c["n"], name=c["name"], frame_numbers=c["frame_numbers"]), f0, t0, None, extra]
                     pending.append(entry)
                     held[g][j] = None
                     finished.append((j, c["n"], entry))
@@ -1352,6 +1471,9 @@ def main(argv=None):
     ap.add_argument("--refine-window", type=int, default=None, metavar="W", help="with --refine ba: refine the clip in windows of W frames (2 .. 256); clips of any length")
     ap.add_argument("--refine-stride", type=int, default=None, metavar="S", help="frames between the starts of consecutive windows (1 .. W-1; default W-1)")
     ap.add_argument("--refine-anchor", choices=["plate"], default=None, help="with --refine ba: hold the four plate corners fixed in the adjustment (a metric scale from the plate)")
+    ap.add_argument("--replenish", type=int, nargs="?", const=5, default=None, metavar="EVERY",
+                    help="replace lost tracks with new corners every EVERY frames (default 5) and triangulate them on the device")
+    ap.add_argument("--spare", type=int, default=256, metavar="ROWS", help="with --replenish: rows for new tracks behind the frame-0 ones")
     ap.add_argument("--shi-tomasi", action="store_true", help="frame-0 corners by the minimum-eigenvalue detector instead of Harris")
     a = ap.parse_args(argv)
     d = np.load(a.clip)
@@ -1359,7 +1481,8 @@ def main(argv=None):
     border = tuple(a.border) if a.border else ((700, 500) if fr.shape[2] >= 1900 else (180, 140))
     run_sequence(fr, d[f"{a.seq}_q"], d[f"{a.seq}_K"], times=d[f"{a.seq}_times"], roi_border=border, msv_frame=a.msv_frame,
                  name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback, refine=a.refine,
-                 refine_window=a.refine_window, refine_stride=a.refine_stride, refine_anchor=a.refine_anchor)
+                 refine_window=a.refine_window, refine_stride=a.refine_stride, refine_anchor=a.refine_anchor,
+                 replenish=None if a.replenish is None else Replenish(every=a.replenish), spare=a.spare if a.replenish is not None else 0)
 
 
 if __name__ == "__main__":
