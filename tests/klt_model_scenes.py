@@ -8,17 +8,12 @@ import numpy as np
 
 import image_ref as IM
 import lk_ref as R
+from _helpers import frozen
 from velocity_amd import synth
 
 F32 = np.float32
 LK_COARSE = dict(win=15, max_level=4, max_count=10, eps=0.1)  # utils/KLT.py:106
 LK_FINE = dict(win=51, max_level=0, max_count=30, eps=0.001)  # utils/KLT.py:107
-
-
-def frozen(*arrays):
-    for a in arrays:
-        a.setflags(write=False)
-    return arrays
 
 
 def rot_T(theta, scale, tx, ty):

@@ -25,6 +25,7 @@ import functools
 import numpy as np
 
 import image_ref as IM
+from _helpers import frozen
 
 F32 = np.float32
 W_BITS = 14
@@ -258,12 +259,6 @@ def klt_regional(im0, im, p0, T, lk, fbt=1.0, translate=False):
 # ---------------------------------------------------------------------------------------------------------------------
 # scenes: 192 x 160 binary frame pairs at the largest gradients and differences 8-bit images can hold
 # ---------------------------------------------------------------------------------------------------------------------
-def _frozen(*arrays):
-    for a in arrays:
-        a.setflags(write=False)
-    return arrays
-
-
 def sign_pair(I, axis=1, negate=False):
     """J = 255 where the Scharr gradient of I along `axis` (1: x, 0: y) is positive, 0 where it is negative, I elsewhere: |J - I| = 255 with the
     gradient's sign on as many edge pixels as a binary pair allows (about half of them: the others already hold the value the rule asks for).
@@ -277,7 +272,7 @@ def bars(k, negate=False):
     """Vertical bars 0, 0, 255, 255 (|Ix| = 4080 at every pixel of a uniform column run), shifted by 2 px every k rows so that Iy is not zero."""
     y, x = np.mgrid[0:H, 0:W]
     I = (255 * (((x + 2 * ((y // k) % 2)) // 2) % 2)).astype(np.uint8)
-    return _frozen(I, sign_pair(I, 1, negate))
+    return frozen(I, sign_pair(I, 1, negate))
 
 
 @functools.lru_cache(maxsize=None)
@@ -285,7 +280,7 @@ def bars_t(k):
     """bars(k) with x and y exchanged: loads Iy, A22 and b2."""
     y, x = np.mgrid[0:H, 0:W]
     I = (255 * (((y + 2 * ((x // k) % 2)) // 2) % 2)).astype(np.uint8)
-    return _frozen(I, sign_pair(I, 0))
+    return frozen(I, sign_pair(I, 0))
 
 
 @functools.lru_cache(maxsize=None)
@@ -297,7 +292,7 @@ def checker(cell, inverse=False):
     cy, cx = y // cell, x // cell
     flip = rng.random((H // cell + 1, W // cell + 1)) < 0.25
     I = (255 * ((cx + cy + flip[cy, cx]) % 2)).astype(np.uint8)
-    return _frozen(I, (255 - I).astype(np.uint8) if inverse else sign_pair(I, 1))
+    return frozen(I, (255 - I).astype(np.uint8) if inverse else sign_pair(I, 1))
 
 
 SCENES = {f"bars{k}": functools.partial(bars, k) for k in (8, 16)}
@@ -326,7 +321,7 @@ def tracks(win, offset):
     along = rng.random(48)
     side = np.arange(48) % 4
     ring = np.where((side < 2)[:, None], np.stack([np.where(side == 0, d, W - 1 - d), along * H], 1), np.stack([along * W, np.where(side == 2, d, H - 1 - d)], 1))
-    return _frozen(np.concatenate([grid, ring]).astype(F32))[0]
+    return frozen(np.concatenate([grid, ring]).astype(F32))[0]
 
 
 CRITERIA = ((1, 0.0), (10, 0.03), (30, 0.001))  # (max_count, eps): one Newton step, the coarse stage's kind, the fine stage's kind
@@ -338,4 +333,4 @@ def model(scene, win, offset, max_count, eps):
     """lk_level0 of a named scene and track set: computed once, shared by every test, never written to."""
     I, J = SCENES[scene]()
     p, s, e, peaks = lk_level0(I, J, tracks(win, offset), win, max_count, eps)
-    return _frozen(p, s, e) + (peaks,)
+    return frozen(p, s, e) + (peaks,)

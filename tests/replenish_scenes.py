@@ -7,6 +7,7 @@ import functools
 import numpy as np
 
 import gftt_ref as G
+import scenes as S
 from oracle import klt_oracle as KO
 from velocity_amd import synth
 from velocity_amd.driver import Frame0Settings, Replenish
@@ -20,10 +21,7 @@ SPARE = 64
 
 
 def camera(w=W, h=H, f=700.0):
-    K = synth.K_1080P.copy()
-    K[0, 0] = K[1, 1] = f
-    K[2, 0], K[2, 1] = w / 2 + 0.5, h / 2 + 0.5
-    return K
+    return S.camera(w, h, f)
 
 
 def motion(K, dx=0.085, dy=0.004, dz=0.02):
@@ -53,10 +51,7 @@ REP_STRICT = Replenish(every=2, baseline=3, target=None, max_new=64, min_distanc
 def plate_clip(seed=2024, n=12):
     """A clip for the drivers: the same sliding plane with a licence plate clicked right of the centre of frame 0 (the ROI around it reaches the right
     edge, where the plane slides out), so that frame 0 goes through admit() and the clip has lost tracks by its first birth frame."""
-    from velocity_amd.common import worldPointsLicensePlate
-
     K = camera()
     m = motion(K)
     frames = np.stack([synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(n)])
-    uvw = (worldPointsLicensePlate("Chile").astype(np.float64) + np.array([0.2, 0.1, 3.6])) @ np.asarray(K, np.float64)
-    return dict(frames=frames, q=(uvw[:, :2] / uvw[:, 2:]).astype(np.float32), times=np.arange(n, dtype=np.float32) / np.float32(25.0), name="sliding plane", K=K)
+    return dict(frames=frames, q=S.plate_quad(K, 0.2, 0.1, 3.6), times=np.arange(n, dtype=np.float32) / np.float32(25.0), name="sliding plane", K=K)

@@ -6,18 +6,19 @@ Tolerances are the project's own for "GPU against the NumPy model, another parti
 atol 1e-8, trace[:, 0] rtol 1e-8, info equal.  What anchoring promises beyond them is exact: an anchored row comes back np.array_equal to its start,
 padding rows byte for byte, an empty window untouched, and a NULL or all-zero table gives the bytes of vh_nls_batch_windows."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import anchor_ref as AR
+import scenes as S
+from scenes import T0
+from session_support import raw_export, session_at, step_to
 from velocity_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 MAX_ITER = 10
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _solve(K, z, x0, nt, nc, counts=None, Ks=None, fixed="absent"):
@@ -207,36 +208,12 @@ def test_python_shims_and_torch_op_take_the_mask(capsys):
 
 
 # ---- the session's anchor table ---------------------------------------------------------------------------------------------------------------------------
-T0 = np.float32([1.5, 0.45, 3.6])
 N0, NF, NHIST = 150, 8, 10
-_SCENES = {}
-
-
-def _camera(W, H, f):
-    K = synth.K_1080P.copy()
-    K[0, 0] = K[1, 1] = f
-    K[2, 0], K[2, 1] = W / 2 + 0.5, H / 2 + 0.5
-    return K
-
-
+# The world points of scenes.scenes3 carry N(0, P3_SIGMA^2) of error here, as points measured from a plate do.  With exact points these rendered clips are
+# tracked to f = 0.002 - 0.003 pixels, and rtol 1e-8 of that is 2e-11 pixels, which the forward-difference Jacobian (1e-6 steps on coordinates of hundreds
+# of pixels: 7e-8 of absolute error per entry) does not give the NumPy model itself; with 2 cm of error f is of the size it has on real footage (0.195
+# pixels on the stills), where the bound means what it says.  Every `hopeless`-th track of a stream -- track 0 among them -- dies at once.
 P3_SIGMA = 0.02  # metres
-
-
-def _scene(W, H, n0, nframes, seed, f=700.0, hopeless=37):
-    """The scene recipe of test_gpu_refine.py (a test module imports no other test module): (frames, p, p3, vp, K); every `hopeless`-th track -- track
-    0 among them -- dies at once.  One thing differs: the world points carry N(0, P3_SIGMA^2) of error, as points measured from a plate do.  With exact
-    points these rendered clips are tracked to f = 0.002 - 0.003 pixels, and rtol 1e-8 of that is 2e-11 pixels, which the forward-difference Jacobian
-    (1e-6 steps on coordinates of hundreds of pixels: 7e-8 of absolute error per entry) does not give the NumPy model itself; with 2 cm of error f is of
-    the size it has on real footage (0.195 pixels on the stills), where the bound means what it says."""
-    K = _camera(W, H, f)
-    m = synth.PlaneMotion(K, z0=3.6)
-    frames = [synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(nframes)]
-    p = synth.grid_tracks(n0, W, H, seed=seed & 0xFF)
-    p[::hopeless] = np.float32([-40.0, -40.0])
-    p3 = m.world_points(p) + np.random.default_rng(seed).normal(0.0, P3_SIGMA, (n0, 3))
-    vp = (p[:, 0] > W * 0.3) & (p[:, 0] < W * 0.7) & (p[:, 1] > H * 0.3) & (p[:, 1] < H * 0.7)
-    return frames, p, p3, vp, K
-
 
 # The scene of the slot WITHOUT anchors and the start of its free window.  A free solve drifts along its scale gauge, and on the states this tracker reaches the
 # NumPy model reproduces its own free traces (tracks in reverse order; the reference's dense form, NLS.py:235) only to 1e-9 .. 4e-8 for the whole clip and
@@ -246,18 +223,8 @@ def _scene(W, H, n0, nframes, seed, f=700.0, hopeless=37):
 SLOT2_SEED, SLOT2_FIRST = 439, 3
 
 
-def _scenes3(n0=N0):
-    if n0 not in _SCENES:
-        _SCENES[n0] = [_scene(320, 240, n0, NHIST, 411, 700.0), _scene(256, 192, n0, NHIST, 422, 560.0, hopeless=11),
-                       _scene(320, 240, n0, NHIST, SLOT2_SEED, 700.0, hopeless=7)]
-    return _SCENES[n0]
-
-
-def _step_to(ses, first, last):
-    import torch
-
-    for k in range(first, last + 1):
-        ses.step([torch.from_numpy(sc[0][k]).cuda() for sc in _scenes3(ses.n0)], time_s=[np.float32(10.0 * b + k / (25.0 + b)) for b in range(3)], frame_no=[k] * 3)
+def _noisy3(n0=N0):
+    return S.scenes3(n0, NHIST, SLOT2_SEED, P3_SIGMA)
 
 
 # slot 0: a snapshot of ids 0..3 (track 0 dies at once: every window has lost it); slot 1: explicit coordinates of three tracks that all die at once
@@ -266,21 +233,17 @@ ANCHOR_IDS = ([0, 1, 2, 3], [0, 11, 22, 5], [])
 
 
 def _explicit_xyz(b, n0=N0):
-    return _scenes3(n0)[b][2][ANCHOR_IDS[b]] + np.array([[0.004, -0.003, 0.01]])
+    return _noisy3(n0)[b][2][ANCHOR_IDS[b]] + np.array([[0.004, -0.003, 0.01]])
 
 
 def _session_with_anchors(frame, anchors=True, n0=N0):
     """Three streams of two cameras in one session, anchors set right after frame 0 (before the re-triangulation frame 5), stepped to `frame`."""
-    from velocity_amd.driver import TrackerSession
-
-    scenes = _scenes3(n0)
-    ses = TrackerSession(scenes[0][4], 320, 240, n0, nhist=NHIST, batch=3, msv_frame=5)
-    for b, (frames, p, p3, vp, Kb) in enumerate(scenes):
-        ses.init_stream(b, frames[0], p, p3, vp, T0, time0=10.0 * b, K=Kb)
+    scenes = _noisy3(n0)
+    ses = session_at(scenes, 0)
     if anchors:
         ses.set_anchors(0, ANCHOR_IDS[0])
         ses.set_anchors(1, ANCHOR_IDS[1], _explicit_xyz(1, n0))
-    _step_to(ses, 1, frame)
+    step_to(ses, scenes, 1, frame)
     return ses
 
 
@@ -295,12 +258,6 @@ def _equals_model(ba, ref, where, window=False, trace=True):
         np.testing.assert_allclose(ba["trace"][:, 0], ref["trace"][:, 0], rtol=1e-8, err_msg=where)
     if window:
         assert ba["first"] == ref["first"], where
-
-
-def _raw_export(ses, b):
-    h = ses.export(b)
-    h.result()
-    return h.buf.numpy()[: h.layout.bytes].tobytes()
 
 
 def _raw_records(handle):
@@ -328,15 +285,15 @@ def _session_case():
     """The anchored session after its last frame, refined whole and in windows, with the models of every record: built once, shared by the tests below."""
     if _SESSION:
         return _SESSION
-    scenes = _scenes3()
+    scenes = _noisy3()
     ses = _session_with_anchors(NF - 1)
     anchors = [ses.anchors(0), ses.anchors(1), None]
-    before = [_raw_export(ses, b) for b in range(3)]
+    before = [raw_export(ses, b) for b in range(3)]
     st = [ses.state(b) for b in range(3)]
     whole = ses.refine([0, 1, 2]).result()
     wins = [(0, 0), (0, 2), (1, 1), (2, SLOT2_FIRST), (1, 3)]
     got = ses.refine_windows(wins, 4, with_points=True).result()
-    after = [_raw_export(ses, b) for b in range(3)]
+    after = [raw_export(ses, b) for b in range(3)]
     whole_ref = [AR.refine_anchored_ref(scenes[b][4], st[b]["P"], st[b]["p3"], st[b]["B"], NF, anchors[b]) for b in range(3)]
     win_ref = [AR.refine_window_anchored_ref(scenes[b][4], st[b]["P"], st[b]["p3"], st[b]["B"], first, 4, anchors[b]) for b, first in wins]
     _SESSION.update(ses=ses, st=st, before=before, after=after, whole=whole, wins=wins, got=got, whole_ref=whole_ref, win_ref=win_ref)
@@ -345,7 +302,7 @@ def _session_case():
 
 def test_session_anchors_refine_and_refine_windows_equal_the_model():
     """Every record of the request -- anchored or not -- against the model: x, info, speeds and trace."""
-    scenes = _scenes3()
+    scenes = _noisy3()
     c = _session_case()
     ses = c["ses"]
     # the table holds the frame-0 values although the clip has passed the re-triangulation frame, which rewrote p3 of the surviving tracks
@@ -449,7 +406,7 @@ def test_reinitialising_a_slot_clears_its_anchors():
     ses = _session_with_anchors(2)
     ses.set_anchors(2, [4, 5, 6])
     assert ses.anchors(2)[0].tolist() == [4, 5, 6] and ses.anchors(0)[0].tolist() == [0, 1, 2, 3]
-    frames, p, p3, vp, Kb = _scenes3()[2]
+    frames, p, p3, vp, Kb = _noisy3()[2]
     ses.init_stream(2, frames[0], p, p3, vp, T0, time0=20.0, K=Kb)  # a new clip is a new plate
     assert ses.anchors(2)[0].size == 0 and ses.anchors(0)[0].tolist() == [0, 1, 2, 3]
 
@@ -459,7 +416,7 @@ def test_set_anchors_refusals_name_their_cause_and_queue_nothing():
     from velocity_amd.driver import TrackerSession
 
     ses = _session_with_anchors(2)
-    before = [_raw_export(ses, b) for b in range(3)]
+    before = [raw_export(ses, b) for b in range(3)]
     table = [ses.anchors(b) for b in range(3)]
     lib = ses.lib
 
@@ -473,14 +430,14 @@ def test_set_anchors_refusals_name_their_cause_and_queue_nothing():
                                ((2, list(range(N0)) + [0]), (f"n = {N0 + 1}", f"{N0} tracks"))):
         rc, msg = call(slot, ids)
         assert rc == -1 and "vh_session_set_anchors" in msg and all(w in msg for w in words), (slot, ids[:4], msg)
-    fresh = TrackerSession(_scenes3()[0][4], 320, 240, N0, nhist=NHIST, batch=2, msv_frame=5)
+    fresh = TrackerSession(_noisy3()[0][4], 320, 240, N0, nhist=NHIST, batch=2, msv_frame=5)
     rc, msg = call(1, [1, 2], fresh.handle)
     assert rc == -1 and "slot 1" in msg and "not initialised" in msg
     with pytest.raises(RuntimeError, match="twice"):
         ses.set_anchors(0, [5, 5])
     with pytest.raises(ValueError, match="xyz"):
         ses.set_anchors(0, [5, 6], np.zeros((3, 3)))
-    assert [_raw_export(ses, b) for b in range(3)] == before
+    assert [raw_export(ses, b) for b in range(3)] == before
     for b in range(3):
         assert all(np.array_equal(a, c) for a, c in zip(ses.anchors(b), table[b]))
     ses.set_anchors(2, [9, 8])  # the next valid call works
@@ -489,21 +446,6 @@ def test_set_anchors_refusals_name_their_cause_and_queue_nothing():
 
 # ---- the drivers' refine_anchor="plate" -------------------------------------------------------------------------------------------------------------------
 KW = dict(roi_border=(60, 40), max_corners=150)
-
-
-def _plate_quad(K, X, Y, Z):
-    from velocity_amd.common import worldPointsLicensePlate
-
-    P = worldPointsLicensePlate("Chile").astype(np.float64) + np.array([X, Y, Z])
-    uvw = P @ np.asarray(K, np.float64)
-    return (uvw[:, :2] / uvw[:, 2:]).astype(np.float32)
-
-
-def _synthetic_clip(W, H, f, n, seed, name):
-    K = _camera(W, H, f)
-    m = synth.PlaneMotion(K, z0=3.6)
-    frames = np.stack([synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(n)])
-    return dict(frames=frames, q=_plate_quad(K, 0.1, -0.05, 3.6), times=np.arange(n, dtype=np.float32) / np.float32(25.0), name=name, K=K)
 
 
 def _plate_anchors(c):
@@ -523,7 +465,7 @@ def _ba_close(g, one, where):
 def test_run_sequence_refine_anchor_plate():
     from velocity_amd import driver as D
 
-    c = _synthetic_clip(320, 240, 700.0, 8, 501, "synthetic 320 x 240")
+    c = S.plate_clip(320, 240, 700.0, 8, 501, "synthetic 320 x 240")
     args = dict(times=c["times"], clock=lambda: 0.0, name=c["name"], **KW)
     free, printed = D.run_sequence(c["frames"], c["q"], c["K"], out=None, refine="ba", **args), []
     got = D.run_sequence(c["frames"], c["q"], c["K"], out=printed.append, refine="ba", refine_anchor="plate", **args)
@@ -557,8 +499,8 @@ def test_run_queue_and_run_sequences_refine_anchor_plate():
     from velocity_amd import driver as D
 
     cams = ((320, 240, 700.0), (256, 192, 560.0))
-    clips = [_synthetic_clip(*cams[k % 2], n, 600 + k, f"clip {k}") for k, n in enumerate((6, 8, 8, 6, 7))]
-    K0 = _camera(320, 240, 650.0)
+    clips = [S.plate_clip(*cams[k % 2], n, 600 + k, f"clip {k}") for k, n in enumerate((6, 8, 8, 6, 7))]
+    K0 = S.camera(320, 240, 650.0)
     alone = [D.run_sequence(c["frames"], c["q"], c["K"], times=c["times"], out=None, live=False, name=c["name"], refine="ba", refine_anchor="plate", **KW)
              for c in clips]
     got = D.run_queue(clips, K0, streams=2, sessions=1, max_size=(240, 320), refine="ba", refine_anchor="plate", **KW)

@@ -6,33 +6,19 @@ the arithmetic.  Every clip of a batch must also be bit-identical to vh_frame0_i
 points, masks, ROIs), whatever the chunking, the stream, a graph capture or a second context running beside it: both run the same kernels, so this
 guards the one-clip wrapper's output layout and the independence of a clip from its neighbours."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
+from _helpers import frame0_host  # noqa: E402
 from oracle import driver_oracle as DO  # noqa: E402 (checker only)
+from scenes import plate_quad, plate_world, stills  # noqa: E402, F401 (stills: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BORDER = (180, 140)
 SENT_F, SENT_I = -7.0, -5
 MIRRORED = 1  # index of the mirrored stills in _mixed_clips
-
-
-@pytest.fixture(scope="module")
-def stills():
-    return np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
-
-
-def _plate_quad(K, X, Y, Z):
-    """worldPointsLicensePlate("Chile") at camera-frame offset (X, Y, Z) metres, projected through K (row-vector layout)."""
-    from velocity_amd.common import worldPointsLicensePlate
-
-    P = worldPointsLicensePlate("Chile").astype(np.float64) + np.array([X, Y, Z])
-    uvw = P @ np.asarray(K, np.float64)
-    return (uvw[:, :2] / uvw[:, 2:]).astype(np.float32)
 
 
 def _mixed_clips(stills):
@@ -45,14 +31,8 @@ def _mixed_clips(stills):
     qm = qb.copy()
     qm[:, 0] = (W - 1) - qm[:, 0]
     syn = synth.render_frame(W, H, synth.AffineMotion(W, H), 0, seed=0x5EED).numpy()
-    return K, [(fb, qb), (np.ascontiguousarray(fb[:, ::-1]), qm[[1, 0, 3, 2]]), (stills["a_frames"][0], stills["a_q"]), (syn, _plate_quad(K, 0.5, -0.97, 6.0)),
+    return K, [(fb, qb), (np.ascontiguousarray(fb[:, ::-1]), qm[[1, 0, 3, 2]]), (stills["a_frames"][0], stills["a_q"]), (syn, plate_quad(K, 0.5, -0.97, 6.0)),
                (np.full((H, W), 128, np.uint8), qb)]
-
-
-def _plate():
-    from velocity_amd.common import worldPointsLicensePlate
-
-    return np.ascontiguousarray(np.asarray(worldPointsLicensePlate("Chile"), np.float64).reshape(12))
 
 
 def _outputs(torch, nb, cap):
@@ -78,14 +58,9 @@ def _batch(ws, frames, qs, K, border=BORDER, max_corners=1000, outs=None, rois=N
     K64 = L.host_K(K)
     p, p3, vp, t, R, res, n = outs
     rc = ws.lib.vh_frame0_init_batch(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), K64.ctypes.data_as(L.f64p),
-                                     _plate().ctypes.data_as(L.f64p), border[0], border[1], max_corners, 0.01, 5, 0.04, 5, 100, 0.001, L.dptr(p), L.dptr(p3),
+                                     plate_world().ctypes.data_as(L.f64p), border[0], border[1], max_corners, 0.01, 5, 0.04, 5, 100, 0.001, L.dptr(p), L.dptr(p3),
                                      L.dptr(vp), L.dptr(t), L.dptr(R), L.dptr(res), L.dptr(n), rois, L.stream_ptr())
     return rc, outs, rois
-
-
-def _host(outs, rois, nb):
-    p, p3, vp, t, R, res, n = (x.cpu().numpy() for x in outs)
-    return dict(p=p[:nb], p3=p3[:nb], vp=vp[:nb], t=t[:nb], R=R[:nb], res=res[:nb], n=n[:nb], rois=np.array(list(rois)[:8 * nb]).reshape(nb, 8))
 
 
 def _single(frame, q, K, border=BORDER, max_corners=1000):
@@ -100,7 +75,7 @@ def _single(frame, q, K, border=BORDER, max_corners=1000):
     rois = (C.c_int * 8)()
     f = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
     q = np.ascontiguousarray(np.asarray(q, np.float32).reshape(4, 2))
-    L.check(ws.lib.vh_frame0_init(ws.handle, L.dptr(f), W, H, W, q.ctypes.data_as(L.f32p), L.host_K(K).ctypes.data_as(L.f64p), _plate().ctypes.data_as(L.f64p),
+    L.check(ws.lib.vh_frame0_init(ws.handle, L.dptr(f), W, H, W, q.ctypes.data_as(L.f32p), L.host_K(K).ctypes.data_as(L.f64p), plate_world().ctypes.data_as(L.f64p),
                                   border[0], border[1], max_corners, 0.01, 5, 0.04, 5, 100, 0.001, L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t), L.dptr(R),
                                   L.dptr(res), L.dptr(n), rois, L.stream_ptr()), "vh_frame0_init")
     return dict(p=p.cpu().numpy(), p3=p3.cpu().numpy(), vp=vp.cpu().numpy(), t=t.cpu().numpy(), R=R.cpu().numpy(), res=res.cpu().numpy(),
@@ -151,7 +126,7 @@ def test_one_call_of_mixed_clips_equals_single_calls_and_the_oracle(stills):
     ws = L.Workspace(1, W, H, 64)
     rc, outs, rois = _batch(ws, _dev([f for f, _ in clips]), [q for _, q in clips], K)
     L.check(rc, "vh_frame0_init_batch")
-    got = _host(outs, rois, len(clips))
+    got = frame0_host(outs, rois, len(clips))
     for b, (f, q) in enumerate(clips):
         _same_as_single(got, b, _single(f, q, K))
         _same_as_oracle(got, b, _oracle(f, q, K), pose=b != MIRRORED)
@@ -174,7 +149,7 @@ def test_chunked_call_equals_one_chunk(stills):
         L.check(ws.lib.vh_init_reserve_batch(ws.handle, nres, W, H, L.stream_ptr()), "vh_init_reserve_batch")
         rc, outs, rois = _batch(ws, frames, qs, K)
         L.check(rc, "vh_frame0_init_batch")
-        res.append(_host(outs, rois, len(clips)))
+        res.append(frame0_host(outs, rois, len(clips)))
     for key in res[0]:
         assert np.array_equal(res[0][key], res[1][key]), key
 
@@ -195,7 +170,7 @@ def test_many_candidates_select_and_large_max_corners(stills):
         ws = L.Workspace(1, W, H, 64)
         rc, outs, rois = _batch(ws, _dev([f, f2]), [q, q], K, border=border, max_corners=mc)
         L.check(rc, "vh_frame0_init_batch")
-        got = _host(outs, rois, 2)
+        got = frame0_host(outs, rois, 2)
         assert got["n"][0] == 4 + mc and got["n"][1] == 4 + mc, got["n"]
         for b, frame in enumerate((f, f2)):
             _same_as_single(got, b, _single(frame, q, K, border=border, max_corners=mc))
@@ -209,7 +184,7 @@ def test_single_call_on_a_tiny_frame_equals_the_oracle():
 
     W, H, border = 96, 64, (8, 5)
     K = np.array([[100.0, 0, 0], [0, 100.0, 0], [48.0, 32.0, 1.0]])
-    q = _plate_quad(K, -0.05, -0.02, 3.0)
+    q = plate_quad(K, -0.05, -0.02, 3.0)
     textured = synth.render_frame(W, H, synth.AffineMotion(W, H), 0, seed=0x5EED).numpy()
     for frame, corners in ((textured, True), (np.full((H, W), 128, np.uint8), False)):
         ref = _oracle(frame, q, K, border=border)
@@ -230,7 +205,7 @@ def test_single_call_refuses_what_it_always_refused():
     W, H = 96, 64
     ws = L.Workspace(1, W, H, 64)
     f = torch.full((H, W), 128, dtype=torch.uint8, device="cuda")
-    K64, plate = L.host_K(np.array([[100.0, 0, 0], [0, 100.0, 0], [48.0, 32.0, 1.0]])), _plate()
+    K64, plate = L.host_K(np.array([[100.0, 0, 0], [0, 100.0, 0], [48.0, 32.0, 1.0]])), plate_world()
     inside = np.float32([[40, 29], [53, 29], [53, 34], [40, 34]])
     outs = _outputs(torch, 1, 54)
 
@@ -263,7 +238,7 @@ def test_graph_capture_replays_the_eager_result(stills):
     L.check(ws.lib.vh_init_reserve_batch(ws.handle, len(clips), W, H, L.stream_ptr()), "vh_init_reserve_batch")
     rc, outs, rois = _batch(ws, frames, qs, K)
     L.check(rc, "vh_frame0_init_batch")
-    eager = _host(outs, rois, len(clips))
+    eager = frame0_host(outs, rois, len(clips))
     cap_outs = _outputs(torch, len(clips), 1004)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
@@ -277,7 +252,7 @@ def test_graph_capture_replays_the_eager_result(stills):
             x.fill_(3)
         g.replay()
         torch.cuda.synchronize()
-        got = _host(cap_outs, rois, len(clips))
+        got = frame0_host(cap_outs, rois, len(clips))
         for key in ("n", "t", "R", "res", "p3", "vp"):
             assert np.array_equal(got[key], eager[key]), key
         for b in range(len(clips)):
@@ -295,7 +270,7 @@ def test_two_contexts_on_two_streams_interleaved(stills):
     K, clips = _mixed_clips(stills)
     A = clips[:3]
     Ws, Hs = 640, 480
-    B = [(synth.render_frame(Ws, Hs, synth.AffineMotion(Ws, Hs), 0, seed=s).numpy(), _plate_quad(K, x, y, 7.0)) for s, x, y in ((3, 0.91, -0.79), (4, 1.01, -0.87))]
+    B = [(synth.render_frame(Ws, Hs, synth.AffineMotion(Ws, Hs), 0, seed=s).numpy(), plate_quad(K, x, y, 7.0)) for s, x, y in ((3, 0.91, -0.79), (4, 1.01, -0.87))]
     refs = [[_oracle(f, q, K) for f, q in A], [_oracle(f, q, K) for f, q in B]]
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     jobs = []
@@ -315,7 +290,7 @@ def test_two_contexts_on_two_streams_interleaved(stills):
     torch.cuda.synchronize()
     for j in range(2):
         for outs, rois in results[j]:
-            got = _host(outs, rois, len(refs[j]))
+            got = frame0_host(outs, rois, len(refs[j]))
             for b, ref in enumerate(refs[j]):
                 _same_as_oracle(got, b, ref, pose=not (j == 0 and b == MIRRORED))
 
@@ -330,7 +305,7 @@ def test_bad_arguments_queue_nothing(stills):
     lib = ws.lib
 
     def untouched(outs, rois, nb):
-        got = _host(outs, rois, nb)
+        got = frame0_host(outs, rois, nb)
         assert np.all(got["p"] == SENT_F) and np.all(got["p3"] == SENT_F) and np.all(got["vp"] == 77) and np.all(got["t"] == SENT_F)
         assert np.all(got["R"] == SENT_F) and np.all(got["res"] == SENT_F) and np.all(got["n"] == SENT_I) and np.all(got["rois"] == SENT_I)
 
@@ -364,12 +339,12 @@ def test_torch_op_equals_the_ctypes_call(stills):
     frames = torch.from_numpy(np.stack([f for f, _ in clips])).cuda()
     qs = np.stack([q for _, q in clips]).astype(np.float32)
     p, p3, vp, t, R, res, n, rois = torch.ops.velocity_hip.frame0_init(frames, torch.from_numpy(qs), torch.from_numpy(np.asarray(K, np.float64)),
-                                                                        torch.from_numpy(_plate().reshape(4, 3)), BORDER[0], BORDER[1])
+                                                                        torch.from_numpy(plate_world().reshape(4, 3)), BORDER[0], BORDER[1])
     assert p.shape == (5, 1004, 2) and p3.shape == (5, 1004, 3) and R.shape == (5, 3, 3) and rois.shape == (5, 8) and not rois.is_cuda
     ws = L.Workspace(1, W, H, 64)
     rc, outs, crois = _batch(ws, [frames[b] for b in range(5)], list(qs), K)
     L.check(rc, "vh_frame0_init_batch")
-    want = _host(outs, crois, 5)
+    want = frame0_host(outs, crois, 5)
     assert np.array_equal(n.cpu().numpy(), want["n"]) and np.array_equal(rois.numpy(), want["rois"])
     for b in range(5):
         k = int(want["n"][b])

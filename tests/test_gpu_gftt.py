@@ -2,26 +2,21 @@
 goodFeaturesToTrack shim, torch.ops.velocity_hip.good_features, driver.run_sequences).  Every comparison is bit-exact: coordinates, order and count
 against tests/gftt_ref.py, which tests/test_gftt_cpu.py pins to the oracle (Harris, minDistance 0) and to OpenCV's spacing grid."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import gftt_ref as G
-from test_gpu_frame0_batch import BORDER, _dev, _host, _mixed_clips, _outputs, _plate
+from _helpers import frame0_host
+from scenes import plate_world, stills  # noqa: F401 (stills: a fixture)
+from test_gpu_frame0_batch import BORDER, _dev, _mixed_clips, _outputs
 
 pytestmark = pytest.mark.gpu
 
 from oracle import klt_oracle as KO  # noqa: E402 (checker only)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MDS = (0, 1, 2.5, 10, 30)
 MCS = (1, 50, 1000, 3000)
-
-
-@pytest.fixture(scope="module")
-def stills():
-    return np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
 
 
 @pytest.fixture(scope="module")
@@ -280,7 +275,7 @@ def _batch2(ws, frames, qs, K, use_harris, md, max_corners=1000, outs=None, bord
     rois = (C.c_int * (8 * nb))()
     p, p3, vp, t, R, res, n = outs
     rc = ws.lib.vh_frame0_init_batch2(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), L.host_K(K).ctypes.data_as(L.f64p),
-                                      _plate().ctypes.data_as(L.f64p), border[0], border[1], max_corners, 0.01, 5, 0.04, 1 if use_harris else 0, float(md), 5,
+                                      plate_world().ctypes.data_as(L.f64p), border[0], border[1], max_corners, 0.01, 5, 0.04, 1 if use_harris else 0, float(md), 5,
                                       100, 0.001, L.dptr(p), L.dptr(p3), L.dptr(vp), L.dptr(t), L.dptr(R), L.dptr(res), L.dptr(n), rois, L.stream_ptr())
     return rc, outs, rois
 
@@ -297,7 +292,7 @@ def _batch1(ws, frames, qs, K, max_corners=1000):
     rois = (C.c_int * (8 * nb))()
     p, p3, vp, t, R, res, n = outs
     L.check(ws.lib.vh_frame0_init_batch(ws.handle, nb, C.cast(ptrs, C.c_void_p), W, H, W, q.ctypes.data_as(L.f32p), L.host_K(K).ctypes.data_as(L.f64p),
-                                        _plate().ctypes.data_as(L.f64p), BORDER[0], BORDER[1], max_corners, 0.01, 5, 0.04, 5, 100, 0.001, L.dptr(p), L.dptr(p3),
+                                        plate_world().ctypes.data_as(L.f64p), BORDER[0], BORDER[1], max_corners, 0.01, 5, 0.04, 5, 100, 0.001, L.dptr(p), L.dptr(p3),
                                         L.dptr(vp), L.dptr(t), L.dptr(R), L.dptr(res), L.dptr(n), rois, L.stream_ptr()), "vh_frame0_init_batch")
     return outs, rois
 
@@ -319,7 +314,7 @@ def test_batch2_shi_tomasi_spaced_equals_reference_and_single_clips(stills):
     ws = L.Workspace(1, W, H, 64)
     rc, outs, rois = _batch2(ws, frames, qs, K, False, 10)
     L.check(rc, "vh_frame0_init_batch2")
-    got = _host(outs, rois, len(clips))
+    got = frame0_host(outs, rois, len(clips))
     assert got["n"][0] > 50 and got["n"][4] == 4, got["n"]
     for b, (f, q) in enumerate(clips):
         x0, x1, y0, y1 = got["rois"][b, 4:8]
@@ -332,7 +327,7 @@ def test_batch2_shi_tomasi_spaced_equals_reference_and_single_clips(stills):
         ws1 = L.Workspace(1, W, H, 64)
         rc, o1, r1 = _batch2(ws1, frames[b:b + 1], qs[b:b + 1], K, False, 10)
         L.check(rc, "vh_frame0_init_batch2")
-        one = _host(o1, r1, 1)
+        one = frame0_host(o1, r1, 1)
         for key in ("n", "t", "R", "res", "p3", "vp", "rois"):
             assert np.array_equal(got[key][b:b + 1], one[key]), (b, key)
         assert np.array_equal(got["p"][b, :n], one["p"][0, :n]), b
@@ -348,7 +343,7 @@ def test_batch2_defaults_equal_batch(stills):
     rc, outs, rois = _batch2(ws, frames, qs, K, True, 0.0)
     L.check(rc, "vh_frame0_init_batch2")
     outs1, rois1 = _batch1(L.Workspace(1, W, H, 64), frames, qs, K)
-    _same(_host(outs, rois, len(clips)), _host(outs1, rois1, len(clips)), len(clips))
+    _same(frame0_host(outs, rois, len(clips)), frame0_host(outs1, rois1, len(clips)), len(clips))
 
 
 def test_batch2_chunked_equals_one_chunk_and_large_max_corners(stills):
@@ -364,7 +359,7 @@ def test_batch2_chunked_equals_one_chunk_and_large_max_corners(stills):
             L.check(ws.lib.vh_init_reserve_batch(ws.handle, nres, W, H, L.stream_ptr()), "vh_init_reserve_batch")
             rc, outs, rois = _batch2(ws, frames, qs, K, False, 10, max_corners=mc)
             L.check(rc, "vh_frame0_init_batch2")
-            res.append(_host(outs, rois, len(clips)))
+            res.append(frame0_host(outs, rois, len(clips)))
         _same(res[0], res[1], len(clips))
     # a textured frame with a full-frame ROI: more than one window of candidates walked, more than 2048 corners kept
     from velocity_amd import synth
@@ -372,7 +367,7 @@ def test_batch2_chunked_equals_one_chunk_and_large_max_corners(stills):
     f = synth.render_frame(W, H, synth.AffineMotion(W, H), 0).numpy()
     rc, outs, rois = _batch2(L.Workspace(1, W, H, 64), _dev([f]), qs[:1], K, False, 2.5, max_corners=3000, border=(2000, 2000))
     L.check(rc, "vh_frame0_init_batch2")
-    got = _host(outs, rois, 1)
+    got = frame0_host(outs, rois, 1)
     x0, x1, y0, y1 = got["rois"][0, 4:8]
     ref = G.good_features(f[y0:y1, x0:x1], 3000, 0.01, 2.5, block=5, use_harris=False) + np.float32([x0, y0])
     assert len(ref) > 2048 and int(got["n"][0]) == 4 + len(ref)
@@ -391,7 +386,7 @@ def test_batch2_graph_capture_replays_the_eager_result(stills):
     L.check(ws.lib.vh_init_reserve_batch(ws.handle, len(clips), W, H, L.stream_ptr()), "vh_init_reserve_batch")
     rc, outs, rois = _batch2(ws, frames, qs, K, False, 10)
     L.check(rc, "vh_frame0_init_batch2")
-    eager = _host(outs, rois, len(clips))
+    eager = frame0_host(outs, rois, len(clips))
     cap_outs = _outputs(torch, len(clips), 1004)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
@@ -402,7 +397,7 @@ def test_batch2_graph_capture_replays_the_eager_result(stills):
         x.fill_(3)
     g.replay()
     torch.cuda.synchronize()
-    _same(_host(cap_outs, rois, len(clips)), eager, len(clips))
+    _same(frame0_host(cap_outs, rois, len(clips)), eager, len(clips))
 
 
 def test_run_sequences_spaced_shi_tomasi_equals_run_sequence(stills):

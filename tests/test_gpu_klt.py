@@ -5,6 +5,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from lk_support import forced_route, klt_order, lk3_slots  # noqa: E402
 from oracle import klt_oracle as KO  # noqa: E402  (checker only)
 from velocity_amd import synth  # noqa: E402
 
@@ -176,21 +177,15 @@ def test_pyr_lk_bit_exact(seq, lk, fbt):
     assert np.array_equal(p2, e2)
     assert np.array_equal(err.ravel(), eerr)
     # the 4-tracks-per-wave kernel (default only for large batches) on the same border / REFLECT_101 cases
-    from velocity_amd import _lib as L
-
     for mode in (4, 8):  # (8: the 8-tracks-per-wave kernel, the default route at full load)
-        L.load().vh_debug_force_generic_lk(mode)
-        try:
+        with forced_route(mode):
             p4, v4, err4 = cv2calcOpticalFlowPyrLK(f0, f1, pts, None, fbt=fbt, **lk)
-        finally:
-            L.load().vh_debug_force_generic_lk(0)
         assert np.array_equal(v4, ev) and np.array_equal(p4, e2) and np.array_equal(err4.ravel(), eerr), mode
     assert v[: len(p0)].mean() > 0.9
 
 
 def test_strip_and_per_sample_lk_kernels_agree(seq):
     """Both device implementations of the track solve (strip kernel, per-sample kernel) are bit-identical."""
-    from velocity_amd import _lib as L
     from velocity_amd.KLT import cv2calcOpticalFlowPyrLK
 
     W, H, m, f0, f1, p0 = seq
@@ -200,11 +195,8 @@ def test_strip_and_per_sample_lk_kernels_agree(seq):
         a = cv2calcOpticalFlowPyrLK(f0, f1, pts, None, fbt=0.5, **lk)
         # 1: per-sample, 2: strip, 3: LDS-staged, 4 / 8: 4 / 8 tracks per wave (15x15 only), 5 / 6 / 7: LDS-staged 51x51 with 1 / 2 / 4 wavefronts per track; default: routed
         for mode in (1, 2, 3, 4, 5, 6, 7, 8):
-            L.load().vh_debug_force_generic_lk(mode)
-            try:
+            with forced_route(mode):
                 b = cv2calcOpticalFlowPyrLK(f0, f1, pts, None, fbt=0.5, **lk)
-            finally:
-                L.load().vh_debug_force_generic_lk(0)
             for x, y in zip(a, b):
                 assert np.array_equal(x, y), (lk, mode)
 
@@ -213,7 +205,6 @@ def test_pyr_lk_interior_border_transition_matches_oracle():
     """Windows sliding across the line where the interior (V-identity, aligned dword loads) path hands over to the border path: a dense set of
     15x15 and 51x51 track positions within 30 px of every side of a small frame (half-pixel steps near the corners), 3 levels, forward +
     backward.  Every kernel route must equal the oracle bit for bit."""
-    from velocity_amd import _lib as L
     from velocity_amd.KLT import cv2calcOpticalFlowPyrLK
 
     W, H = 160, 112
@@ -228,11 +219,8 @@ def test_pyr_lk_interior_border_transition_matches_oracle():
     for win, lvl, modes in ((15, 2, (0, 2, 3, 4, 8)), (51, 1, (0, 2, 5, 6, 7))):
         exp = KO.lk_fb(f0, f1, pts, fbt=1.0, win=win, max_level=lvl, max_count=10, eps=0.03)
         for mode in modes:
-            L.load().vh_debug_force_generic_lk(mode)
-            try:
+            with forced_route(mode):
                 got = cv2calcOpticalFlowPyrLK(f0, f1, pts, None, fbt=1.0, winSize=(win, win), maxLevel=lvl, criteria=(3, 10, 0.03))
-            finally:
-                L.load().vh_debug_force_generic_lk(0)
             assert np.array_equal(got[1], exp[1]), (win, mode)
             assert np.array_equal(got[0], exp[0]), (win, mode)
             assert np.array_equal(got[2].ravel(), exp[2]), (win, mode)
@@ -240,7 +228,6 @@ def test_pyr_lk_interior_border_transition_matches_oracle():
 
 def test_pyr_lk_large_motion_restages_search_region():
     """Displacements far beyond the staged search margin (coarse 6 px, fine 4 px) must still match the oracle."""
-    from velocity_amd import _lib as L
     from velocity_amd.KLT import cv2calcOpticalFlowPyrLK
 
     W, H = 640, 360
@@ -253,11 +240,8 @@ def test_pyr_lk_large_motion_restages_search_region():
                    (dict(winSize=(15, 15), maxLevel=1, criteria=(3, 10, 0.1)), dict(win=15, max_level=1, max_count=10, eps=0.1))):
         e2, ev, eerr = KO.lk_fb(f0, f1, pts, fbt=2.0, **kw)
         for mode in (0, 3, 4, 5, 6, 8):  # (8: 8 tracks per wave for 15x15) default routing, the LDS-staged kernel for both windows, 4 tracks per wave for 15x15, 1 / 2 waves per 51x51 track
-            L.load().vh_debug_force_generic_lk(mode)
-            try:
+            with forced_route(mode):
                 p2, v, err = cv2calcOpticalFlowPyrLK(f0, f1, pts, None, fbt=2.0, **lk)
-            finally:
-                L.load().vh_debug_force_generic_lk(0)
             assert np.array_equal(v, ev) and np.array_equal(p2, e2) and np.array_equal(err.ravel(), eerr)
 
 
@@ -281,7 +265,6 @@ def test_pyr_lk_textureless_and_small_images():
 def test_pyr_lk_images_much_smaller_than_the_window():
     """Level 0 of an image far smaller than the window (OpenCV's level truncation never drops level 0): window columns reach |i| > 4 (n - 1),
     beyond the two-fold branch-free REFLECT_101 -- the looped reflection must take over (an out-of-bounds read otherwise).  Every kernel route."""
-    from velocity_amd import _lib as L
     from velocity_amd.KLT import cv2calcOpticalFlowPyrLK
 
     rng = np.random.default_rng(11)
@@ -291,11 +274,8 @@ def test_pyr_lk_images_much_smaller_than_the_window():
         pts = np.concatenate([rng.uniform([-2, -2], [w + 2, h + 2], (24, 2)), [[w / 2.0, h / 2.0]]]).astype(np.float32)
         exp = KO.lk_fb(a, b, pts, fbt=1.0, win=win, max_level=2, max_count=10, eps=0.03)
         for mode in ((0, 1, 2, 3, 4, 8) if win == 15 else (0, 1, 2, 5, 6, 7)):
-            L.load().vh_debug_force_generic_lk(mode)
-            try:
+            with forced_route(mode):
                 got = cv2calcOpticalFlowPyrLK(a, b, pts, None, fbt=1.0, winSize=(win, win), maxLevel=2, criteria=(3, 10, 0.03))
-            finally:
-                L.load().vh_debug_force_generic_lk(0)
             assert np.array_equal(got[1], exp[1]), ((h, w), win, mode)
             assert np.array_equal(got[0], exp[0]), ((h, w), win, mode)
             assert np.array_equal(got[2].ravel(), exp[2]), ((h, w), win, mode)
@@ -385,13 +365,8 @@ def test_klt_main_bit_exact_all_stages(seq, coarse_levels):
 def spatial_launch_order():
     """LK launches of KLTmain walk the tracks in spatial order (k_klt_setup's counting sort) whatever the load: the default only does above 24000
     tracks in flight, which the full-size tests reach and the small ones do not."""
-    from velocity_amd import _lib as L
-
-    L.load().vh_debug_klt_order(1)
-    try:
+    with klt_order(1):
         yield
-    finally:
-        L.load().vh_debug_klt_order(-1)
 
 
 def test_klt_main_in_spatial_launch_order_is_bit_exact(seq, spatial_launch_order):
@@ -423,7 +398,6 @@ def test_every_lk_route_maps_back_and_records_through_the_shared_epilogue():
     KLTregional and the praw_out record that KLTmain's later stages read must equal the oracle bit for bit -- on a small scene whose border points
     give each case live AND dead tracks (asserted on the oracle alone, before any device call)."""
     from velocity_amd import KLT
-    from velocity_amd import _lib as L
 
     W, H = 320, 240
     m = synth.AffineMotion(W, H, tx=3.5, ty=-1.25)
@@ -444,20 +418,15 @@ def test_every_lk_route_maps_back_and_records_through_the_shared_epilogue():
     for k, v in list((k, v) for k, (_, v) in want.items()) + [("klt_main", ev)]:
         assert v.sum() >= 10 and (~v).sum() >= 10, f"{k}: {int(v.sum())} live / {int((~v).sum())} dead tracks"
 
-    lib = L.load()
     for route in range(9):
-        lib.vh_debug_force_generic_lk(route)
-        try:
+        with forced_route(route):
             for k, (T, cv_lk, _, fbt, tr) in regional.items():
                 p, v = KLT.KLTregional(f0, f1, pts, T, cv_lk, fbt=fbt, translateFlag=tr)
                 assert np.array_equal(v, want[k][1]) and np.array_equal(p, want[k][0]), f"route {route}, {k}"
             for order in (-1, 1):
-                lib.vh_debug_klt_order(order)
-                p, v, _, p_all, flags = KLT.KLTmain(f1, f0, None, pts, lk_coarse=lkc, return_all=True)
+                with klt_order(order):
+                    p, v, _, p_all, flags = KLT.KLTmain(f1, f0, None, pts, lk_coarse=lkc, return_all=True)
                 assert flags == 0 and np.array_equal(v, ev) and np.array_equal(p_all, S["p_all"]) and np.array_equal(p, ep), f"route {route}, order {order}"
-        finally:
-            lib.vh_debug_klt_order(-1)
-            lib.vh_debug_force_generic_lk(0)
 
 
 @pytest.mark.parametrize("coarse_levels", [4, 2])
@@ -505,9 +474,8 @@ def test_backward_pass_is_skipped_for_tracks_whose_forward_status_is_zero(lk, fb
     routes = (1, 2, 3, 4, 8) if lk["win"] == 15 else (1, 2, 5, 6, 7)
     counts = {}
     for mode in routes:
-        ws.lib.vh_debug_force_generic_lk(mode)
         got = {}
-        try:
+        with forced_route(mode):
             for want_fbe in (False, True):
                 p2 = torch.zeros((n, 2), dtype=torch.float32, device="cuda")
                 v = torch.zeros(n, dtype=torch.uint8, device="cuda")
@@ -519,8 +487,6 @@ def test_backward_pass_is_skipped_for_tracks_whose_forward_status_is_zero(lk, fb
                 ms, nl, it, su = (C.c_double * 3)(), (C.c_int * 3)(), (C.c_ulonglong * 3)(), (C.c_ulonglong * 3)()
                 L.check(ws.lib.vh_profile_end(ws.handle, ms, nl, it, su), "vh_profile_end")
                 got[want_fbe] = (p2.cpu().numpy(), v.cpu().numpy().astype(bool), err.cpu().numpy(), int(su[0]), int(it[0]))
-        finally:
-            ws.lib.vh_debug_force_generic_lk(0)
         (pa, va, ea, sua, ita), (pb, vb, eb, sub, itb) = got[False], got[True]
         assert np.array_equal(pa, pb) and np.array_equal(va, vb) and np.array_equal(ea, eb), f"route {mode}: the skip changed a result"
         assert np.array_equal(pa, ep2) and np.array_equal(va, ev) and np.array_equal(ea, eerr), f"route {mode} differs from the oracle"
@@ -715,7 +681,6 @@ def test_frame0_features_inside_a_stream_capture():
 def test_pyr_lk_fuzz_all_kernels_vs_oracle():
     """Randomised configurations (image size, motion, window, pyramid depth, stop rule, FB gate, points in and out of the
     frame) through every LK implementation vs the oracle: bit-exact position / status / err.  Fixed seed."""
-    from velocity_amd import _lib as L
     from velocity_amd.KLT import cv2calcOpticalFlowPyrLK
 
     rng = np.random.default_rng(20260928)
@@ -733,11 +698,8 @@ def test_pyr_lk_fuzz_all_kernels_vs_oracle():
         fbt = [None, 1.0, 0.3][int(rng.integers(0, 3))]
         exp = KO.lk_fb(f0, f1, pts, fbt=fbt, win=win, max_level=lvl, max_count=cnt, eps=eps)
         for mode in (0, 1, 2, 3, 4, 5, 6, 7, 8):
-            L.load().vh_debug_force_generic_lk(mode)
-            try:
+            with forced_route(mode):
                 got = cv2calcOpticalFlowPyrLK(f0, f1, pts, None, fbt=fbt, winSize=(win, win), maxLevel=lvl, criteria=(3, cnt, eps))
-            finally:
-                L.load().vh_debug_force_generic_lk(0)
             ctx = (case, mode, W, H, n, win, lvl, cnt, eps, fbt)
             assert np.array_equal(got[1], exp[1]), ctx
             assert np.array_equal(got[0], exp[0]), ctx
@@ -809,8 +771,7 @@ def test_lk3_slot_loop_is_bit_exact_for_every_slot_count(seq, mode, lk):
     g0, g1, gp = synth.gate_scene()
     cases = [("mixed", f0, f1, mixed), ("three", f0, f1, mixed[:3]), ("one", f0, f1, mixed[:1]), ("seven", f0, f1, mixed[5:12]), ("gate", g0, g1, gp)]
     lib = L.load()
-    try:
-        lib.vh_debug_force_generic_lk(mode)
+    with forced_route(mode), lk3_slots(0):  # (the slot count is set per case below and restored here)
         for name, a_np, b_np, pts in cases:
             h, w = a_np.shape
             ws = L.workspace(w, h, len(pts))
@@ -832,9 +793,6 @@ def test_lk3_slot_loop_is_bit_exact_for_every_slot_count(seq, mode, lk):
                             assert np.array_equal(err, eerr), ctx
                         if want_fbe:  # fbe requested: the backward pass of forward-dead tracks runs too; the gate and the point stay the oracle's
                             assert np.isfinite(fbe[v]).all() and (fbe[v] < fbt).all(), ctx
-    finally:
-        lib.vh_debug_lk3_tpw(0)
-        lib.vh_debug_force_generic_lk(0)
 
 
 def test_lk3_slot_count_hook_is_clamped_and_default_is_one_for_small_launches(seq):
@@ -844,21 +802,17 @@ def test_lk3_slot_count_hook_is_clamped_and_default_is_one_for_small_launches(se
     a, b = torch.from_numpy(f0).cuda(), torch.from_numpy(f1).cuda()
     lk = dict(win=51, max_level=0, max_count=30, eps=0.001)
     lib = L.load()
-    try:
-        lib.vh_debug_force_generic_lk(5)
+    with forced_route(5), lk3_slots(0):  # (the slot count is set step by step below and restored here)
         assert _pyr_lk_raw(ws, a, b, W, H, p0, lk, 0.3)[5] == 1  # 600 tracks in flight: one slot per workgroup
         lib.vh_debug_lk3_tpw(100)
         ref = _pyr_lk_raw(ws, a, b, W, H, p0, lk, 0.3)
         assert ref[5] == 8  # LK3::MAX_TPW
         lib.vh_debug_lk3_tpw(-5)
         assert _pyr_lk_raw(ws, a, b, W, H, p0, lk, 0.3)[5] == 1
-        lib.vh_debug_force_generic_lk(6)  # two wavefronts per track: no slot loop whatever the hook says
-        lib.vh_debug_lk3_tpw(4)
-        two = _pyr_lk_raw(ws, a, b, W, H, p0, lk, 0.3)
+        with forced_route(6):  # two wavefronts per track: no slot loop whatever the hook says
+            lib.vh_debug_lk3_tpw(4)
+            two = _pyr_lk_raw(ws, a, b, W, H, p0, lk, 0.3)
         assert two[4] == 6 and two[5] == 1 and np.array_equal(two[0], ref[0]) and np.array_equal(two[1], ref[1])
-    finally:
-        lib.vh_debug_lk3_tpw(0)
-        lib.vh_debug_force_generic_lk(0)
 
 
 def test_klt_main_reuses_the_previous_upload_and_notices_a_refilled_buffer(seq):

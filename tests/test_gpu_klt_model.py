@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 import image_ref as IM  # noqa: E402
 import klt_model_scenes as S  # noqa: E402
 import lk_ref as R  # noqa: E402
+from lk_support import forced_route  # noqa: E402
 
 F32 = np.float32
 ROUTES = {15: (0, 1, 2, 3, 4, 8), 51: (0, 1, 2, 5, 6, 7)}  # 0: the launcher's own choice; the forced routes that exist for the window (tests/test_gpu_klt.py)
@@ -63,11 +64,8 @@ def test_pyr_lk_equals_the_model_on_every_route(case, fbt):
     want = S.lk_model(case, fbt)
     assert want[1].sum() >= 20 and (~want[1]).sum() >= 20
     for route in ROUTES[lk["win"]]:
-        L.load().vh_debug_force_generic_lk(route)
-        try:
+        with forced_route(route):
             got = _pyr_lk(f0, f1, pts, lk, fbt)
-        finally:
-            L.load().vh_debug_force_generic_lk(0)
         _same_lk(got, want, (case, fbt, route), fbt is not None)
 
 

@@ -19,13 +19,15 @@ import numpy as np
 import pytest
 
 import lk_ref as R
+from lk_support import bits as _bits
+from lk_support import forced_route, lk3_slots
 from oracle import klt_oracle as KO  # (checker only)
 from test_gpu_klt import _lib, _pyr_lk_raw
 from test_gpu_lk3_track_loop import _bilinear
 
 W, H = R.W, R.H  # 192 x 160
 FBT = 0.5
-ROUTES = {51: 5, 15: 3}  # window -> the vh_debug_force_generic_lk mode of its one-wavefront k_lk3 kernel
+ROUTES = {51: 5, 15: 3}  # window -> the forced_route mode of its one-wavefront k_lk3 kernel
 LEVELS = (0, 2)  # max_level: 1 and 3 pyramid levels
 CRITERIA = tuple((mc, eps) for mc in (1, 2, 3, 30) for eps in (0.1, 0.001, 0.0))
 TEXTURES = ("vbars", "hbars", "mix", "vbars_only", "hbars_only")
@@ -92,22 +94,15 @@ def _oracle(texture, shift, win, max_level, max_count, eps):
     return out
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def _check_pair(texture, shift, criteria=CRITERIA, model=None):
     """One frame pair, uploaded once: both windows on their one-wavefront routes x 1 and 3 levels x the criteria."""
     L, C, torch = _lib()
     I, J = _pair(texture, shift)
     a, b = torch.from_numpy(I).cuda(), torch.from_numpy(J).cuda()
-    lib = L.load()
-    try:
-        for win, mode in ROUTES.items():
-            pts = np.array(_tracks(win))
-            ws = L.workspace(W, H, len(pts))
-            lib.vh_debug_force_generic_lk(mode)
-            lib.vh_debug_lk3_tpw(1)
+    for win, mode in ROUTES.items():
+        pts = np.array(_tracks(win))
+        ws = L.workspace(W, H, len(pts))
+        with forced_route(mode), lk3_slots(1):
             for max_level in LEVELS:
                 for max_count, eps in criteria:
                     lk = dict(win=win, max_level=max_level, max_count=max_count, eps=eps)
@@ -127,9 +122,6 @@ def _check_pair(texture, shift, criteria=CRITERIA, model=None):
                         mp, ms, _, _ = model(win, max_count, eps)
                         live = np.asarray(ev, bool)
                         assert (_bits(p[live]) == _bits(mp[live])).all() and ms[live].all(), (ctx, "model")
-    finally:
-        lib.vh_debug_lk3_tpw(0)
-        lib.vh_debug_force_generic_lk(0)
 
 
 def test_the_scenes_do_what_they_are_for():

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import klt_oracle as KO  # (checker only)
+from lk_support import forced_route, lk3_slots
 from test_gpu_klt import _lib, _pyr_lk_raw
 from test_gpu_lk3_track_loop import SCENES, _bilinear
 
@@ -27,7 +28,7 @@ FBT = 0.3
 
 
 @functools.lru_cache(maxsize=None)
-def _scene():
+def _shifted_pair():
     """The frame pair of test_gpu_lk3_track_loop._scene(51) -- same generator, same seed -- displaced by SHIFT instead of (1.3, -0.7), and textured all over:
     without that scene's constant rectangle, which would hold two of the nine tracks in place."""
     rng = np.random.default_rng(SEED)
@@ -46,7 +47,7 @@ def _scene():
 @functools.lru_cache(maxsize=None)
 def _oracle():
     """(p, status, err, fbe) of the nine tracks: computed once, shared, never written to."""
-    f0, f1 = _scene()
+    f0, f1 = _shifted_pair()
     out = KO.lk_fb(f0, f1, PTS, fbt=FBT, return_fbe=True, **LK)
     for a in out:
         a.setflags(write=False)
@@ -86,16 +87,13 @@ def test_restaged_tracks_get_the_oracles_bits_in_every_instantiation():
     """Modes 5 / 6 / 7 (1 / 2 / 4 wavefronts per track) x 1 / 2 / 4 / 8 launch slots per workgroup: p, status, err and fbe of every track, bit for bit."""
     _assert_oracle_restages()
     L, C, torch = _lib()
-    f0, f1 = _scene()
+    f0, f1 = _shifted_pair()
     ep, ev, eerr, efbe = _oracle()
     a, b = torch.from_numpy(f0).cuda(), torch.from_numpy(f1).cuda()
     ws = L.workspace(W, H, len(PTS))
-    lib = L.load()
-    try:
-        for mode in (5, 6, 7):
-            lib.vh_debug_force_generic_lk(mode)
-            for tpw in (1, 2, 4, 8):
-                lib.vh_debug_lk3_tpw(tpw)
+    for mode in (5, 6, 7):
+        for tpw in (1, 2, 4, 8):
+            with forced_route(mode), lk3_slots(tpw):
                 p2, v, err, fbe, route, used = _pyr_lk_raw(ws, a, b, W, H, PTS, LK, FBT, True, True)
                 ctx = (mode, tpw)
                 assert route == mode and used == (tpw if mode == 5 else 1), (ctx, route, used)
@@ -103,6 +101,3 @@ def test_restaged_tracks_get_the_oracles_bits_in_every_instantiation():
                 assert np.array_equal(p2, ep), (ctx, p2, ep)
                 assert np.array_equal(err, eerr), (ctx, err, eerr)
                 assert np.array_equal(fbe, efbe), (ctx, fbe, efbe)
-    finally:
-        lib.vh_debug_lk3_tpw(0)
-        lib.vh_debug_force_generic_lk(0)

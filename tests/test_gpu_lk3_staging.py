@@ -15,9 +15,10 @@ import numpy as np
 import pytest
 
 from oracle import klt_oracle as KO  # (checker only)
+from lk_support import forced_route, lk3_one_level, lk3_slots
 from test_gpu_klt import _lib
 
-# window -> route of vh_debug_force_generic_lk -> search margin M, staged bytes per patch row / per region row (LK3::PI_PITCH, LK3::PJ_WIDTH)
+# window -> modes of forced_route -> search margin M, staged bytes per patch row / per region row (LK3::PI_PITCH, LK3::PJ_WIDTH)
 GEOM = {51: dict(M=4, patch_w=56, region_w=64, modes=(5, 6, 7)), 15: dict(M=6, patch_w=20, region_w=32, modes=(3,))}
 W, H = 130, 100
 PITCHES = (144, 132, 131)  # a multiple of 16, of 4 only, odd
@@ -148,8 +149,7 @@ def test_staging_gives_the_oracles_bits_at_every_pitch_phase_and_limit(mode, win
     L, C, torch = _lib()
     lib = L.load()
     ws = L.workspace(W, H, 32)
-    try:
-        lib.vh_debug_force_generic_lk(mode)
+    with forced_route(mode), lk3_slots(0), lk3_one_level(1):  # (the two inner hooks are set per case below and restored here)
         for motion in ("near", "far"):
             f0, f1, pts, lk, (ep, ev, eerr, efbe) = _staging_case(win, motion)
             for pitch in PITCHES:
@@ -169,10 +169,6 @@ def test_staging_gives_the_oracles_bits_at_every_pitch_phase_and_limit(mode, win
                         assert np.array_equal(err, eerr), (ctx, err, eerr)
                         assert np.array_equal(fbe, efbe), (ctx, fbe, efbe)
                     del ka, kb
-    finally:
-        lib.vh_debug_lk3_one_level(1)
-        lib.vh_debug_lk3_tpw(0)
-        lib.vh_debug_force_generic_lk(0)
 
 
 # (b): 224 x 216 is the smallest frame whose third pyramid level (56 x 54) still holds a 51 x 51 window
@@ -210,8 +206,7 @@ def test_first_iteration_on_the_template_origin_gives_the_oracles_bits(mode, win
     lib = L.load()
     cf = REUSE[win]
     ws = L.workspace(cf["w"], cf["h"], 32)
-    try:
-        lib.vh_debug_force_generic_lk(mode)
+    with forced_route(mode), lk3_one_level(1):  # (set per case below, restored here)
         for max_level in (0, 2):
             for max_count in (1, None):
                 for fb in (False, True):
@@ -227,9 +222,6 @@ def test_first_iteration_on_the_template_origin_gives_the_oracles_bits(mode, win
                         assert np.array_equal(err, eerr), (ctx, err, eerr)
                         if fb:
                             assert np.array_equal(fbe, efbe), (ctx, fbe, efbe)
-    finally:
-        lib.vh_debug_lk3_one_level(1)
-        lib.vh_debug_force_generic_lk(0)
 
 
 def test_the_reuse_scenes_have_live_tracks_and_the_levels_asked_for():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import klt_oracle as KO  # (checker only)
+from lk_support import forced_route, lk3_slots
 from test_gpu_klt import _lib, _pyr_lk_raw
 
 OOF, INT, BRD, FLAT = "out-of-frame", "interior", "border", "textureless"
@@ -107,26 +108,21 @@ def test_every_slot_of_a_workgroup_gets_the_oracles_bits(mode, win, max_level):
     H, W = f0.shape
     a, b = torch.from_numpy(f0).cuda(), torch.from_numpy(f1).cuda()
     ws = L.workspace(W, H, len(pts))
-    lib = L.load()
-    try:
-        lib.vh_debug_force_generic_lk(mode)
+    with forced_route(mode):
         for n in (len(pts), 3):
             for fbt in (None, FBT[win]):
                 ep, ev, eerr, efbe = _oracle(win, max_level, fbt, n)
                 for tpw in ((1, 2, 3, 4, 8) if n == len(pts) else (4, 8)):
-                    lib.vh_debug_lk3_tpw(tpw)
-                    for want_err, want_fbe in ((True, False), (False, False), (True, True), (False, True)):
-                        if want_fbe and fbt is None:
-                            continue
-                        p2, v, err, fbe, route, used = _pyr_lk_raw(ws, a, b, W, H, pts[:n], lk, fbt, want_err, want_fbe)
-                        ctx = (mode, win, max_level, n, fbt, tpw, want_err, want_fbe)
-                        assert route == mode and used == (tpw if mode in (3, 5) else 1), (ctx, route, used)
-                        assert np.array_equal(v, ev), (ctx, v, ev)
-                        assert np.array_equal(p2, ep), (ctx, p2, ep)
-                        if want_err:
-                            assert np.array_equal(err, eerr), (ctx, err, eerr)
-                        if want_fbe:
-                            assert np.array_equal(fbe, efbe), (ctx, fbe, efbe)
-    finally:
-        lib.vh_debug_lk3_tpw(0)
-        lib.vh_debug_force_generic_lk(0)
+                    with lk3_slots(tpw):
+                        for want_err, want_fbe in ((True, False), (False, False), (True, True), (False, True)):
+                            if want_fbe and fbt is None:
+                                continue
+                            p2, v, err, fbe, route, used = _pyr_lk_raw(ws, a, b, W, H, pts[:n], lk, fbt, want_err, want_fbe)
+                            ctx = (mode, win, max_level, n, fbt, tpw, want_err, want_fbe)
+                            assert route == mode and used == (tpw if mode in (3, 5) else 1), (ctx, route, used)
+                            assert np.array_equal(v, ev), (ctx, v, ev)
+                            assert np.array_equal(p2, ep), (ctx, p2, ep)
+                            if want_err:
+                                assert np.array_equal(err, eerr), (ctx, err, eerr)
+                            if want_fbe:
+                                assert np.array_equal(fbe, efbe), (ctx, fbe, efbe)

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 import lk_ref as R
+from lk_support import bits as _bits
+from lk_support import forced_route, lk3_slots
 from oracle import klt_oracle as KO  # (checker only)
 from velocity_amd import synth
 
@@ -22,7 +24,7 @@ SWEEP_EVEN = (4, 8, 16, 20, 64)
 
 
 def _routes(win):
-    """(vh_debug_force_generic_lk mode, vh_debug_lk3_tpw slots, the route the launch must report | None) of every kernel that solves this window.
+    """(forced_route mode, lk3_slots count, the route the launch must report | None) of every kernel that solves this window.
     The slot count only exists in the one-wavefront LDS-staged kernel: the default route and route 5 run with 1 and 4 slots per workgroup."""
     if win == 15:
         return [(0, 0, None), (1, 0, 1), (2, 0, 2), (3, 0, 3), (4, 0, 4), (8, 0, 8)]
@@ -40,25 +42,16 @@ def _run(I, J, pts, win, max_level, max_count, eps, fbt, mode, tpw):
     from velocity_amd.KLT import cv2calcOpticalFlowPyrLK
 
     lib = L.load()
-    try:
-        lib.vh_debug_force_generic_lk(mode)
-        lib.vh_debug_lk3_tpw(tpw)
+    with forced_route(mode), lk3_slots(tpw):
         p2, v, err = cv2calcOpticalFlowPyrLK(I, J, pts, None, fbt=fbt, winSize=(win, win), maxLevel=max_level, criteria=(3, max_count, eps))
         ws = L.workspace(I.shape[1], I.shape[0], len(pts))
         routes, slots = (C.c_int * 3)(), (C.c_int * 3)()
         L.check(lib.vh_profile_lk_routes(ws.handle, routes, None), "vh_profile_lk_routes")
         L.check(lib.vh_profile_lk_tpw(ws.handle, slots), "vh_profile_lk_tpw")
-    finally:
-        lib.vh_debug_lk3_tpw(0)
-        lib.vh_debug_force_generic_lk(0)
     # the launch slots per workgroup the launch reports: the hook's value in the one-wavefront LDS-staged kernels (routes 3 and 5; 1 when the hook is
     # off, far below the loads at which they take more on their own), 1 in every other kernel
     assert int(slots[0]) == ((tpw or 1) if int(routes[0]) in (3, 5) else 1), (win, mode, tpw, int(routes[0]), int(slots[0]))
     return p2, v, err.ravel(), int(routes[0])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _assert_same(got, exp, ctx):

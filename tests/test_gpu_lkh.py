@@ -6,12 +6,12 @@ quad group that is not full, tracks of one wavefront leaving the Newton loop at 
 rows per lane, and the int32 partial sums of a lane that now holds 60 samples (0.93 of 2^31 at worst-case contrast).  The shapes are those of
 tests/test_gpu_lko_alignment.py: 96 x 80 images taken as views with base phase 0..3 and rows 132..135 bytes apart, three levels, 64 tracks of which
 24 touch or cross an edge or a corner."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import lk_ref as R
+from lk_support import assert_same_bits as _assert_same
+from lk_support import SMALL, bits, pyr_lk_forced, small, strided_view, texture_pair, to_dev  # noqa: F401 (small: a fixture)
 from oracle import klt_oracle as KO  # (checker only)
 from oracle.session_oracle import SessionOracle  # (checker only)
 from velocity_amd import synth
@@ -19,102 +19,13 @@ from velocity_amd import synth
 pytestmark = pytest.mark.gpu
 
 WIN, LEVELS, MAX_COUNT, EPS = 15, 2, 10, 0.03
+assert dict(win=WIN, max_level=LEVELS, max_count=MAX_COUNT, eps=EPS) == SMALL  # the `small` fixture's oracle ran with these
 ROUTE = 9
 PITCHES = (132, 133, 134, 135)
 
 
-def _texture(w, h, seed):
-    """Smooth random texture (box-filtered noise, full 8-bit range) and the same texture moved by (+1.5, -1) pixels."""
-    rng = np.random.default_rng(seed)
-    n = rng.integers(0, 256, (h + 12, w + 12)).astype(np.float64)
-    k = np.ones(5) / 5.0
-    n = np.apply_along_axis(lambda r: np.convolve(r, k, "same"), 1, n)
-    n = np.apply_along_axis(lambda c: np.convolve(c, k, "same"), 0, n)
-    n = (n - n.min()) / (n.max() - n.min()) * 255.0
-    a = n[6:6 + h, 6:6 + w]
-    b = 0.5 * (n[7:7 + h, 4:4 + w] + n[7:7 + h, 5:5 + w])
-    return np.rint(a).astype(np.uint8), np.rint(b).astype(np.uint8)
-
-
-def _tracks(w, h):
-    """64 points: 40 interior ones whose integer x runs through every residue mod 4 at several sub-pixel offsets, 24 whose 15 x 15 window touches or
-    crosses the left, right, top and bottom edge and the four corners."""
-    pts = [(20.0 + 1.0 * i + 0.13 * (i % 7), 18.0 + (11 * i) % (h - 36) + 0.29 * (i % 5)) for i in range(40)]
-    for k, e in enumerate((0.5, 3.25, 6.75, 7.5)):
-        y = 20.0 + 9.5 * k
-        pts += [(e, y), (w - 1 - e, y + 3.25), (24.0 + 13.25 * k, e), (30.0 + 11.5 * k, h - 1 - e)]
-    pts += [(1.5, 2.25), (w - 2.25, 1.5), (2.75, h - 3.5), (w - 3.5, h - 2.75), (7.0, 7.0), (w - 8.0, h - 8.0), (8.0, h - 8.5), (w - 8.5, 8.0)]
-    assert len(pts) == 64
-    return np.array(pts, np.float32)
-
-
-def _view(img, pitch, phase):
-    """`img` as a view into a larger device buffer: rows `pitch` bytes apart, base address = `phase` mod 4."""
-    import torch
-
-    h, w = img.shape
-    buf = torch.full((h + 4, pitch), 77, dtype=torch.uint8, device="cuda")
-    x0 = (phase - 2 * pitch - buf.data_ptr()) & 3
-    v = buf[2:2 + h, x0:x0 + w]
-    v.copy_(torch.from_numpy(np.ascontiguousarray(img)).cuda())
-    assert v.data_ptr() & 3 == phase and v.stride(0) == pitch and v.stride(1) == 1
-    return v
-
-
 def _run(I, J, pts, fbt, mode, max_level=LEVELS, max_count=MAX_COUNT, eps=EPS, want_err=True, want_fbe=False):
-    """vh_pyr_lk on one forced route (the hook is process-wide and reset whatever happens) -> (p2, v, err | None, fbe | None); I, J: device views."""
-    import torch
-
-    from velocity_amd import _lib as L
-
-    lib = L.load()
-    n = len(pts)
-    h, w = I.shape
-    ws = L.workspace(w, h, n)
-    p = torch.from_numpy(np.ascontiguousarray(pts, np.float32)).cuda()
-    p2 = torch.zeros((n, 2), dtype=torch.float32, device="cuda")
-    v = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    err = torch.zeros(n, dtype=torch.float32, device="cuda") if want_err else None
-    fbe = torch.zeros(n, dtype=torch.float32, device="cuda") if want_fbe else None
-    prm = L.lk_params(dict(win=WIN, max_level=max_level, max_count=max_count, eps=eps))
-    routes = (C.c_int * 3)()
-    try:
-        lib.vh_debug_force_generic_lk(mode)
-        L.check(lib.vh_pyr_lk(ws.handle, L.dptr(I), L.dptr(J), w, h, I.stride(0), J.stride(0), L.dptr(p), n, C.byref(prm), C.c_float(-1.0 if fbt is None else fbt),
-                              L.dptr(p2), L.dptr(v), L.dptr(err), L.dptr(fbe), L.stream_ptr()), "vh_pyr_lk")
-        L.check(lib.vh_profile_lk_routes(ws.handle, routes, None), "vh_profile_lk_routes")
-    finally:
-        lib.vh_debug_force_generic_lk(0)
-    assert int(routes[0]) == mode, (mode, int(routes[0]))
-    return (p2.cpu().numpy(), v.cpu().numpy().astype(bool), None if err is None else err.cpu().numpy(), None if fbe is None else fbe.cpu().numpy())
-
-
-def _dev(img):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(img)).cuda()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _assert_same(got, exp, ctx):
-    """position, status, err (, fbe) of every track as bit patterns; an output that either side does not have is not compared."""
-    for name, a, b in zip(("position", "status", "err", "fbe"), got, exp):
-        if a is None or b is None:
-            continue
-        same = (a == b) if a.dtype == bool else (_bits(a) == _bits(b))
-        bad = np.flatnonzero(~same.reshape(len(a), -1).all(1))
-        assert not len(bad), (ctx, name, bad[:8], a[bad[:8]], b[bad[:8]])
-
-
-@pytest.fixture(scope="module")
-def small():
-    I, J = _texture(96, 80, 5)
-    pts = _tracks(96, 80)
-    oracle = {fbt: KO.lk_fb(I, J, pts, fbt=fbt, win=WIN, max_level=LEVELS, max_count=MAX_COUNT, eps=EPS) for fbt in (None, 1.0)}
-    return I, J, pts, oracle
+    return pyr_lk_forced(I, J, pts, fbt, mode, WIN, max_level, max_count, eps, want_err, want_fbe)
 
 
 @pytest.mark.parametrize("pitch", PITCHES)
@@ -122,7 +33,7 @@ def test_every_phase_and_pitch(small, pitch):
     """Route 9 against routes 1 and 8 and the oracle at every base phase and row pitch, forward and forward-backward."""
     I, J, pts, oracle = small
     for phase in range(4):
-        a, b = _view(I, pitch, phase), _view(J, pitch + (phase & 1), (phase + 1 + (pitch & 1)) & 3)
+        a, b = strided_view(I, pitch, phase), strided_view(J, pitch + (phase & 1), (phase + 1 + (pitch & 1)) & 3)
         for fbt in (None, 1.0):
             res = {mode: _run(a, b, pts, fbt, mode) for mode in (ROUTE, 8, 1)}
             for mode in (8, 1):
@@ -136,7 +47,7 @@ def test_track_counts(small, n):
     """Partial wavefronts and a last quad group that is not full: the LAST n tracks of the set, so that every count has edge and corner tracks (tracks
     are independent: the oracle's rows of the same tracks)."""
     I, J, pts, oracle = small
-    a, b = _view(I, 133, 1), _view(J, 134, 3)
+    a, b = strided_view(I, 133, 1), strided_view(J, 134, 3)
     for fbt in (None, 1.0):
         got = _run(a, b, pts[-n:], fbt, ROUTE)
         _assert_same(got, tuple(x[-n:] for x in oracle[fbt]), (n, fbt))
@@ -146,7 +57,7 @@ def _spread_scene():
     """192 x 80 pair in four bands of 48 columns: the moved texture, a static copy (J = I: the first Newton step is zero), a flat patch (the
     min-eigenvalue gate rejects it on level 0) and a textured ramp that is 60 grey levels brighter in J (Newton steps of tens of pixels: the window leaves the
     level during the iterations).  Tracks of the four kinds INTERLEAVED, so that every wavefront -- and most quads' neighbours -- hold all of them."""
-    I, J = _texture(192, 80, 9)
+    I, J = texture_pair(192, 80, 9)
     I, J = I.copy(), J.copy()
     J[:, 48:96] = I[:, 48:96]
     I[:, 96:144] = J[:, 96:144] = 128
@@ -180,7 +91,7 @@ def test_spread_inside_one_wavefront(spread):
     assert np.abs(p[kind == 1] - pts[kind == 1]).max() < 0.05  # static copy: done after the first Newton step (the upper levels see a little of the bands beside it)
     assert not v[kind == 2].any()  # flat: rejected on level 0
     assert not v[kind == 3].any() and (np.abs(p[kind == 3] - pts[kind == 3]).max(1) > 50).all()  # the ramp tracks walk out of the level
-    a, b = _dev(I), _dev(J)
+    a, b = to_dev(I), to_dev(J)
     orders = [np.arange(64), np.arange(64)[::-1], np.roll(np.arange(64), 5), np.argsort(kind, kind="stable")]
     fwd = None
     for k, order in enumerate(orders):
@@ -193,14 +104,14 @@ def test_spread_inside_one_wavefront(spread):
             if k == 0 and fbt is not None:
                 dead = ~fwd[1]
                 assert dead.sum() >= 24 and not got[1][dead].any()
-                assert (_bits(got[0][dead]) == _bits(fwd[0][dead])).all()
+                assert (bits(got[0][dead]) == bits(fwd[0][dead])).all()
 
 
 @pytest.mark.parametrize("max_level", (0, 2, 4))
 def test_levels_criteria_and_optional_outputs(small, max_level):
     """max_level 0 / 2 / 4, max_count 1 / 2 / 10, with and without the err and fbe outputs (with fbe the backward pass of dead tracks runs)."""
     I, J, pts, _ = small
-    a, b = _view(I, 135, 2), _view(J, 132, 0)
+    a, b = strided_view(I, 135, 2), strided_view(J, 132, 0)
     for max_count in (1, 2, 10):
         for fbt in (None, 1.0):
             exp = KO.lk_fb(I, J, pts, fbt=fbt, win=WIN, max_level=max_level, max_count=max_count, eps=EPS, return_fbe=True)
@@ -220,7 +131,7 @@ def test_worst_case_contrast(scene):
     pts = np.concatenate(sets)
     lens = np.array([len(s) for s in sets])
     ends = np.cumsum(lens)
-    a, b = _dev(I), _dev(J)
+    a, b = to_dev(I), to_dev(J)
     for fbt in (None, 1.0):
         for lvl in (0, 2):
             for mc, eps in R.CRITERIA:

@@ -11,6 +11,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from lk_support import assert_same_bits as _assert_same
+from lk_support import pyr_lk_forced
 from oracle import klt_oracle as KO  # (checker only)
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +22,7 @@ ROUTE, NMAX = 9, 4096
 FLAT = (150, 100, 44, 40)  # x, y, w, h of a constant patch: the min-eigenvalue gate kills its tracks on level 0 of the forward pass
 
 
-def _scene():
+def _cells_pair():
     """Box-filtered noise whose contrast and grain change from cell to cell of a 16 x 16 px grid (the gradients of two tracks a few pixels apart share
     little), a constant patch, and the same image moved by (+1.5, -1) px."""
     rng = np.random.default_rng(41)
@@ -81,51 +83,14 @@ def _tracks():
 
 
 def _run(I, J, pts, fbt, mode, max_level, want_err=True, want_fbe=True):
-    """vh_pyr_lk on one forced route (the hook is process-wide and reset whatever happens) -> (p2, v, err | None, fbe | None)."""
-    import torch
-
-    from velocity_amd import _lib as L
-
-    lib = L.load()
-    n = len(pts)
-    ws = L.workspace(W, H, n)
-    p = torch.from_numpy(np.ascontiguousarray(pts, np.float32)).cuda()
-    p2 = torch.zeros((n, 2), dtype=torch.float32, device="cuda")
-    v = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    err = torch.zeros(n, dtype=torch.float32, device="cuda") if want_err else None
-    fbe = torch.zeros(n, dtype=torch.float32, device="cuda") if want_fbe else None
-    prm = L.lk_params(dict(win=WIN, max_level=max_level, max_count=MAX_COUNT, eps=EPS))
-    routes = (C.c_int * 3)()
-    try:
-        lib.vh_debug_force_generic_lk(mode)
-        L.check(lib.vh_pyr_lk(ws.handle, L.dptr(I), L.dptr(J), W, H, I.stride(0), J.stride(0), L.dptr(p), n, C.byref(prm), C.c_float(-1.0 if fbt is None else fbt),
-                              L.dptr(p2), L.dptr(v), L.dptr(err), L.dptr(fbe), L.stream_ptr()), "vh_pyr_lk")
-        L.check(lib.vh_profile_lk_routes(ws.handle, routes, None), "vh_profile_lk_routes")
-    finally:
-        lib.vh_debug_force_generic_lk(0)
-    assert int(routes[0]) == mode, (mode, int(routes[0]))
-    return (p2.cpu().numpy(), v.cpu().numpy().astype(bool), None if err is None else err.cpu().numpy(), None if fbe is None else fbe.cpu().numpy())
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _assert_same(got, exp, ctx):
-    """position, status, err, fbe of every track as bit patterns; an output that either side does not have is not compared."""
-    for name, a, b in zip(("position", "status", "err", "fbe"), got, exp):
-        if a is None or b is None:
-            continue
-        same = (a == b) if a.dtype == bool else (_bits(a) == _bits(b))
-        bad = np.flatnonzero(~same.reshape(len(a), -1).all(1))
-        assert not len(bad), (ctx, name, len(bad), bad[:8], a[bad[:8]], b[bad[:8]])
+    return pyr_lk_forced(I, J, pts, fbt, mode, WIN, max_level, MAX_COUNT, EPS, want_err, want_fbe)
 
 
 @pytest.fixture(scope="module")
 def scene():
     import torch
 
-    I, J = _scene()
+    I, J = _cells_pair()
     pts, kinds = _tracks()
     oracle = {(lvl, fbt): KO.lk_fb(I, J, pts, fbt=fbt, win=WIN, max_level=lvl, max_count=MAX_COUNT, eps=EPS, return_fbe=True)
               for lvl in (0, 2) for fbt in (None, FBT)}

@@ -2,7 +2,6 @@
 pinned bit-exact against its checker (remap, detector, RANSAC) -- then the shim, the torch op, KLTmain(fallback=True) and the drop-in loop built on it."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -12,16 +11,11 @@ pytestmark = pytest.mark.gpu
 import match_ref as MR  # noqa: E402
 from oracle import driver_oracle as DO  # noqa: E402 (checker only)
 from oracle import klt_oracle as KO  # noqa: E402 (checker only)
+from scenes import load_stills as stills  # noqa: E402
 from velocity_amd import synth  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 960, 540
 SYNTH = {"shift200": (1.0, 0, 200, 0), "shrink": (0.75, 2, 120, -40), "grow": (1.3, -3, -90, 60)}
-
-
-@functools.lru_cache(maxsize=None)
-def stills():
-    return np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
 
 
 @functools.lru_cache(maxsize=None)

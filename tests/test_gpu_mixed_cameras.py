@@ -3,60 +3,21 @@ TrackerSession.init_stream(K=...) / admit, run_sequences, run_queue(max_size=...
 
 Two yardsticks wherever both can serve: the stream's own SessionOracle (it is per stream and takes its own K and frames), with the comparisons and
 tolerances of test_gpu_session_idle.py, and the same stream ALONE in a session of exactly its size and K, whose state() must be equal field for field,
-bit for bit (every LK route is bit-identical and the pose / MSV solves are per stream).  The helpers are copies of that file's: a test module imports
-no other test module."""
+bit for bit (every LK route is bit-identical and the pose / MSV solves are per stream).  Scenes and comparisons are those of tests/scenes.py and
+tests/session_support.py; _Streams is this module's own (that file's has no per-stream camera and no solo twin)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
+import scenes as S  # noqa: E402
+from _helpers import frame0_host  # noqa: E402
 from oracle.session_oracle import SessionOracle  # noqa: E402 (checker only)
+from scenes import T0  # noqa: E402
+from session_support import equals_oracle, same_dict  # noqa: E402
 from velocity_amd import synth  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-T0 = np.float32([1.5, 0.45, 3.6])
-
-
-def _camera(W, H, f, c=None):
-    K = synth.K_1080P.copy()
-    K[0, 0] = K[1, 1] = f
-    K[2, 0], K[2, 1] = c if c is not None else (W / 2 + 0.5, H / 2 + 0.5)
-    return K
-
-
-def _scene(W, H, n0, nframes, seed, f=700.0, c=None, traj=None):
-    """The scene of test_gpu_session_idle.py for a camera of its own: (frames, p, p3, vp, K).  traj: the camera's path (default: PlaneMotion's, which
-    also recedes, so the tracks drift towards the principal point)."""
-    K = _camera(W, H, f, c)
-    m = synth.PlaneMotion(K, z0=3.6, traj=traj)
-    frames = [synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(nframes)]
-    p = synth.grid_tracks(n0, W, H, seed=seed & 0xFF)
-    # a few hopeless tracks (window far outside the frame) so the masks and the compaction actually change
-    p[::37] = np.float32([-40.0, -40.0])
-    p3 = m.world_points(p)
-    vp = (p[:, 0] > W * 0.3) & (p[:, 0] < W * 0.7) & (p[:, 1] > H * 0.3) & (p[:, 1] < H * 0.7)
-    return frames, p, p3, vp, K
-
-
-def _same_dict(a, b, where):
-    assert a.keys() == b.keys(), where
-    for key in a:
-        assert np.array_equal(np.asarray(a[key]), np.asarray(b[key]), equal_nan=np.asarray(a[key]).dtype.kind == "f"), (where, key)
-
-
-def _equals_oracle(st, orc, where, records=True):
-    assert st["frame_i"] == orc.i, where
-    assert np.array_equal(st["vg"], orc.vg) and np.array_equal(st["vp"], orc.vp), where
-    assert np.array_equal(st["ids"], np.nonzero(orc.vg)[0]) and np.array_equal(st["p"], orc.p), where
-    np.testing.assert_allclose(st["p3"], orc.p3, rtol=1e-4, atol=1e-5)
-    if records:
-        n = orc.i + 1
-        np.testing.assert_allclose(st["B"][:n, 12:14], orc.B[:n, 12:14], rtol=0, atol=0)
-        np.testing.assert_allclose(st["S"][1:n, [0, 2, 4, 5]], orc.S[1:n, [0, 2, 4, 5]], rtol=0, atol=0)
-        np.testing.assert_allclose(st["S"][1:n, [3, 6, 7, 8]], orc.S[1:n, [3, 6, 7, 8]], rtol=1e-4)
 
 
 class _Streams:
@@ -80,8 +41,6 @@ class _Streams:
                 self.solo[b].init_stream(0, frames[0], p, p3, vp, t0, time0=10.0 * b)
 
     def step(self, active, bgr=None):
-        import torch
-
         frames, ts, fn = [], [], []
         for b, a in enumerate(active):
             if not a:
@@ -92,13 +51,13 @@ class _Streams:
             self.k[b] += 1
             k = self.k[b]
             t = np.float32(10.0 * b + k / (25.0 + b))
-            frames.append(torch.from_numpy(self.scenes[b][0][k] if bgr is None else bgr[b][k]).cuda())
+            frames.append(S.to_cuda(self.scenes[b][0][k] if bgr is None else bgr[b][k]))
             ts.append(t)
             fn.append(k)
             if b in self.orc:
                 self.orc[b].step(self.scenes[b][0][k], t, k)
             if b in self.solo:
-                self.solo[b].step([torch.from_numpy(self.scenes[b][0][k]).cuda()], time_s=[t], frame_no=[k])
+                self.solo[b].step([S.to_cuda(self.scenes[b][0][k])], time_s=[t], frame_no=[k])
         if bgr is None:
             self.ses.step(frames, time_s=ts, frame_no=fn)
             return None
@@ -107,9 +66,9 @@ class _Streams:
     def check(self, b, where):
         st = self.ses.state(b)
         if b in self.orc:
-            _equals_oracle(st, self.orc[b], where)
+            equals_oracle(st, self.orc[b], where)
         if b in self.solo:
-            _same_dict(st, self.solo[b].state(0), where)
+            same_dict(st, self.solo[b].state(0), where)
         return st
 
 
@@ -123,7 +82,7 @@ CAMERAS = [(480, 270, 700.0, None), (270, 480, 520.0, (150.5, 222.0)), (414, 233
 
 def test_three_cameras_in_one_session():
     n0 = 220
-    scenes = [_scene(W, H, n0, 6, 555 + 222 * b, f, c) for b, (W, H, f, c) in enumerate(CAMERAS)]
+    scenes = [S.plane_scene(W, H, n0, 6, 555 + 222 * b, f, c) for b, (W, H, f, c) in enumerate(CAMERAS)]
     run = _Streams(scenes, 480, 480, n0, nhist=8, msv_frame=3)
     prev = [run.ses.state(b) for b in range(3)]
     for g, active in enumerate(TABLE, 1):
@@ -132,7 +91,7 @@ def test_three_cameras_in_one_session():
         for b, a in enumerate(active):
             cur.append(run.check(b, (g, b)) if a else run.ses.state(b))
             if not a:
-                _same_dict(cur[b], prev[b], (g, b))  # a slot sits the step out while neighbours of other sizes run
+                same_dict(cur[b], prev[b], (g, b))  # a slot sits the step out while neighbours of other sizes run
         prev = cur
     assert [run.orc[b].i for b in range(3)] == [4, 4, 4]
     assert all(st["n_cur"] > n0 // 4 for st in prev), [st["n_cur"] for st in prev]  # (every camera kept tracking: the comparison is not of empty streams)
@@ -145,7 +104,7 @@ def test_both_level_layouts_side_by_side():
     from velocity_amd import _lib as L
 
     n0 = 220
-    scenes = [_scene(640, 480, n0, 4, 901, 760.0, traj=lambda k: np.array([0.02 * k, 0.005 * k, 0.0])), _scene(480, 270, n0, 4, 902, 700.0)]
+    scenes = [S.plane_scene(640, 480, n0, 4, 901, 760.0, traj=lambda k: np.array([0.02 * k, 0.005 * k, 0.0])), S.plane_scene(480, 270, n0, 4, 902, 700.0)]
     run = _Streams(scenes, 640, 480, n0, nhist=6, msv_frame=0)
     for g in range(1, 4):
         run.step((1, 1))
@@ -159,21 +118,6 @@ def test_both_level_layouts_side_by_side():
 
 
 # ---- frame 0 ------------------------------------------------------------------------------------------------------------------------------------------
-def _plate_quad(K, X, Y, Z):
-    """worldPointsLicensePlate("Chile") at camera-frame offset (X, Y, Z) metres, projected through K (row-vector layout)."""
-    from velocity_amd.common import worldPointsLicensePlate
-
-    P = worldPointsLicensePlate("Chile").astype(np.float64) + np.array([X, Y, Z])
-    uvw = P @ np.asarray(K, np.float64)
-    return (uvw[:, :2] / uvw[:, 2:]).astype(np.float32)
-
-
-def _plate():
-    from velocity_amd.common import worldPointsLicensePlate
-
-    return np.ascontiguousarray(np.asarray(worldPointsLicensePlate("Chile"), np.float64).reshape(12))
-
-
 F0_BORDER, F0_CORNERS = (60, 40), 150
 
 
@@ -183,11 +127,6 @@ def _f0_outputs(torch, nb, cap):
             torch.full((nb, cap), 77, dtype=torch.uint8, device=dev), torch.full((nb, 3), -7.0, dtype=torch.float32, device=dev),
             torch.full((nb, 9), -7.0, dtype=torch.float64, device=dev), torch.full((nb,), -7.0, dtype=torch.float64, device=dev),
             torch.full((nb,), -5, dtype=torch.int32, device=dev))
-
-
-def _f0_host(outs, rois, nb):
-    p, p3, vp, t, R, res, n = (x.cpu().numpy() for x in outs)
-    return dict(p=p[:nb], p3=p3[:nb], vp=vp[:nb], t=t[:nb], R=R[:nb], res=res[:nb], n=n[:nb], rois=np.array(list(rois)[:8 * nb]).reshape(nb, 8))
 
 
 def _batch3(ws, frames, cams, qs, use_harris, min_distance, outs=None):
@@ -200,7 +139,7 @@ def _batch3(ws, frames, cams, qs, use_harris, min_distance, outs=None):
     q = np.ascontiguousarray(np.stack([np.asarray(x, np.float32).reshape(4, 2) for x in qs]))
     ptrs = (C.c_void_p * nb)(*[f.data_ptr() for f in frames])
     rois = (C.c_int * (8 * nb))(*([-5] * 8 * nb))
-    rc = ws.lib.vh_frame0_init_batch3(ws.handle, nb, C.cast(ptrs, C.c_void_p), (L.ClipCamera * nb)(*cams), q.ctypes.data_as(L.f32p), _plate().ctypes.data_as(L.f64p),
+    rc = ws.lib.vh_frame0_init_batch3(ws.handle, nb, C.cast(ptrs, C.c_void_p), (L.ClipCamera * nb)(*cams), q.ctypes.data_as(L.f32p), S.plate_world().ctypes.data_as(L.f64p),
                                       F0_BORDER[0], F0_BORDER[1], F0_CORNERS, 0.01, 5, 0.04, use_harris, min_distance, 5, 100, 0.001,
                                       *[L.dptr(x) for x in outs], rois, L.stream_ptr())
     return rc, outs, rois
@@ -218,23 +157,23 @@ def _f0_single(frame, q, K, use_harris, min_distance):
     rois = (C.c_int * 8)()
     f = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
     q = np.ascontiguousarray(np.asarray(q, np.float32).reshape(4, 2))
-    common = (q.ctypes.data_as(L.f32p), L.host_K(K).ctypes.data_as(L.f64p), _plate().ctypes.data_as(L.f64p), F0_BORDER[0], F0_BORDER[1], F0_CORNERS, 0.01, 5, 0.04)
+    common = (q.ctypes.data_as(L.f32p), L.host_K(K).ctypes.data_as(L.f64p), S.plate_world().ctypes.data_as(L.f64p), F0_BORDER[0], F0_BORDER[1], F0_CORNERS, 0.01, 5, 0.04)
     tail = (5, 100, 0.001, *[L.dptr(x) for x in outs], rois, L.stream_ptr())
     if use_harris and min_distance == 0:
         L.check(ws.lib.vh_frame0_init(ws.handle, L.dptr(f), W, H, W, *common, *tail), "vh_frame0_init")
     else:
         ptrs = (C.c_void_p * 1)(f.data_ptr())
         L.check(ws.lib.vh_frame0_init_batch2(ws.handle, 1, C.cast(ptrs, C.c_void_p), W, H, W, *common, use_harris, float(min_distance), *tail), "vh_frame0_init_batch2")
-    return _f0_host(outs, rois, 1)
+    return frame0_host(outs, rois, 1)
 
 
 def _f0_clips():
     """Three clips of three sizes and three K: (frame, q, K)."""
     out = []
     for b, ((W, H, f, c), (X, Y)) in enumerate(zip(CAMERAS, ((0.1, -0.05), (-0.15, 0.4), (0.3, 0.1)))):
-        K = _camera(W, H, f, c)
+        K = S.camera(W, H, f, c)
         frame = synth.render_frame(W, H, synth.AffineMotion(W, H), 0, seed=0x5EED + b).numpy()
-        out.append((frame, _plate_quad(K, X, Y, 3.6), K))
+        out.append((frame, S.plate_quad(K, X, Y, 3.6), K))
     return out
 
 
@@ -250,7 +189,7 @@ def test_frame0_of_three_cameras_in_one_call(use_harris, min_distance):
     cams = [L.clip_camera(f.shape[1], f.shape[0], K) for f, _, K in clips]
     rc, outs, rois = _batch3(ws, dev, cams, [q for _, q, _ in clips], use_harris, min_distance)
     L.check(rc, "vh_frame0_init_batch3")
-    got = _f0_host(outs, rois, 3)
+    got = frame0_host(outs, rois, 3)
     for b, (frame, q, K) in enumerate(clips):
         one = _f0_single(frame, q, K, use_harris, min_distance)
         n = int(got["n"][b])
@@ -280,13 +219,6 @@ def _same_as_single(g, one, where):
     assert g["lines"][-2] == one["lines"][-2], where  # Speed / Res summary
 
 
-def _synthetic_clip(W, H, f, n, seed, name, plate_xy=(0.1, -0.05)):
-    K = _camera(W, H, f)
-    m = synth.PlaneMotion(K, z0=3.6)
-    frames = np.stack([synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(n)])
-    return dict(frames=frames, q=_plate_quad(K, plate_xy[0], plate_xy[1], 3.6), times=np.arange(n, dtype=np.float32) / np.float32(25.0), name=name, K=K)
-
-
 def _alone(c, K, **kw):
     from velocity_amd.driver import run_sequence
 
@@ -297,9 +229,9 @@ def test_run_sequences_on_clips_of_two_cameras():
     """The reference's stills B (1024 x 768, their own intrinsics and plate corners) beside a synthetic 960 x 540 clip of the same length with its own K."""
     from velocity_amd.driver import run_sequences
 
-    stills = np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
+    stills = S.load_stills()
     a = dict(frames=stills["b_frames"], q=stills["b_q"], times=stills["b_times"], name="stills b")
-    b = _synthetic_clip(960, 540, 1100.0, len(a["frames"]), 77, "synthetic 960 x 540")
+    b = S.plate_clip(960, 540, 1100.0, len(a["frames"]), 77, "synthetic 960 x 540")
     kw = dict(roi_border=(180, 140), max_corners=400)
     lines = []
     got = run_sequences([a, b], stills["b_K"], sessions=1, out=lines.append, **kw)
@@ -314,8 +246,8 @@ def test_run_queue_on_clips_of_two_cameras():
     from velocity_amd.driver import run_queue
 
     cams = ((480, 270, 700.0), (414, 233, 610.0))
-    clips = [_synthetic_clip(*cams[k % 2], n, 300 + k, f"clip {k} {cams[k % 2][0]} x {cams[k % 2][1]}") for k, n in enumerate((3, 6, 4, 5, 6, 3))]
-    K0 = _camera(480, 270, 650.0)  # the default camera: no clip uses it (each brings its own K)
+    clips = [S.plate_clip(*cams[k % 2], n, 300 + k, f"clip {k} {cams[k % 2][0]} x {cams[k % 2][1]}") for k, n in enumerate((3, 6, 4, 5, 6, 3))]
+    K0 = S.camera(480, 270, 650.0)  # the default camera: no clip uses it (each brings its own K)
     kw = dict(roi_border=(60, 40), max_corners=150, msv_frame=3)
     alone = [_alone(c, K0, **kw) for c in clips]
     for ns in (1, 2):
@@ -324,7 +256,7 @@ def test_run_queue_on_clips_of_two_cameras():
         for c, g, one in zip(clips, got, alone):
             _same_as_single(g, one, (ns, c["name"]))
             assert g["P"].shape[2] == len(c["frames"])
-    big = _synthetic_clip(640, 480, 800.0, 3, 999, "too large")
+    big = S.plate_clip(640, 480, 800.0, 3, 999, "too large")
     seen = []
     with pytest.raises(ValueError, match=r"clip 6 .*640 x 480.*480 x 270"):
         run_queue(clips + [big], K0, streams=2, sessions=1, max_size=(270, 480), on_result=lambda i, r: seen.append(i), **kw)
@@ -336,7 +268,7 @@ def test_step_bgr_with_two_frame_sizes_equals_the_gray_path():
 
     n0 = 180
     rng = np.random.default_rng(5)
-    scenes = [_scene(480, 270, n0, 5, 321, 700.0), _scene(414, 233, n0, 5, 332, 610.0)]
+    scenes = [S.plane_scene(480, 270, n0, 5, 321, 700.0), S.plane_scene(414, 233, n0, 5, 332, 610.0)]
     bgr = [[np.clip(np.stack([f.astype(int) + rng.integers(-20, 21, f.shape) * (c - 1) for c in range(3)], -1), 0, 255).astype(np.uint8) for f in sc[0]]
            for sc in scenes]
     gray = [([KO.bgr2gray(f) for f in bgr[b]],) + scenes[b][1:] for b in range(2)]
@@ -354,9 +286,9 @@ def test_step_bgr_with_two_frame_sizes_equals_the_gray_path():
         states.append([run.ses.state(b) for b in range(2)])
         if mode == "gray":
             for b in range(2):
-                _equals_oracle(states[0][b], run.orc[b], b)
+                equals_oracle(states[0][b], run.orc[b], b)
     for b in range(2):
-        _same_dict(states[0][b], states[1][b], b)
+        same_dict(states[0][b], states[1][b], b)
     assert [s["frame_i"] for s in states[1]] == [3, 3]
 
 
@@ -393,7 +325,7 @@ def test_refusals_queue_nothing_and_change_nothing():
 
     torch = L.torch_cuda()
     n0 = 120
-    scenes = [_scene(480, 270, n0, 4, 71, 700.0), _scene(414, 233, n0, 4, 72, 610.0)]
+    scenes = [S.plane_scene(480, 270, n0, 4, 71, 700.0), S.plane_scene(414, 233, n0, 4, 72, 610.0)]
     run = _Streams(scenes, 480, 270, n0, nhist=5, msv_frame=0, solo=False)
     run.step((1, 1))
     before = [run.ses.state(b) for b in range(2)]
@@ -403,7 +335,7 @@ def test_refusals_queue_nothing_and_change_nothing():
     def unchanged(what):
         assert ses.slot_size(1) == (233, 414), what
         for b in range(2):
-            _same_dict(ses.state(b), before[b], (what, b))
+            same_dict(ses.state(b), before[b], (what, b))
 
     assert lib.vh_session_set_camera(ses.handle, 1, 481, 270, K64.ctypes.data_as(L.f64p), 0, L.stream_ptr()) == -1
     msg = lib.vh_last_error()
@@ -415,7 +347,7 @@ def test_refusals_queue_nothing_and_change_nothing():
     assert lib.vh_session_set_camera(ses.handle, 2, 414, 233, K64.ctypes.data_as(L.f64p), 0, L.stream_ptr()) == -1 and b"slot 2" in lib.vh_last_error()
     assert lib.vh_session_set_camera(ses.handle, 1, 414, 233, None, 0, L.stream_ptr()) == -1 and b"K_host" in lib.vh_last_error()
     unchanged("a null K")
-    frames, p, p3, vp, K = _scene(640, 480, n0, 1, 73)
+    frames, p, p3, vp, K = S.plane_scene(640, 480, n0, 1, 73)
     with pytest.raises(ValueError, match="slot 1.*640 x 480.*480 x 270"):
         ses.init_stream(1, frames[0], p, p3, vp, T0, K=K)
     unchanged("a frame larger than the session")
@@ -432,4 +364,4 @@ def test_refusals_queue_nothing_and_change_nothing():
     unchanged("a refused frame-0 call")
     run.step((1, 1))  # and both streams go on as if nothing had been asked
     for b in range(2):
-        _equals_oracle(ses.state(b), run.orc[b], ("after", b))
+        equals_oracle(ses.state(b), run.orc[b], ("after", b))

@@ -1,20 +1,15 @@
 """velocity_amd.driver.run_queue on the real stills: a queue of clips of different lengths on a few resident streams.  Every clip must come out as
 run_sequence gives it alone -- the assertions of test_gpu_stills.py::test_run_sequences_batches_clips_like_single_runs -- whatever slot it lands in,
 whoever its neighbours are and however the slots are split over sessions."""
-import os
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from scenes import stills  # noqa: E402, F401 (a fixture)
+
 BORDER = (180, 140)
-
-
-@pytest.fixture(scope="module")
-def stills():
-    return np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
 
 
 def _clips(stills):

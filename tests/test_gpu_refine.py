@@ -147,64 +147,11 @@ def test_windows_of_different_counts_other_routes(nf, force_valu):
 
 
 # ---- finished clips refined straight from the session (vh_session_refine, TrackerSession.refine, the drivers' refine="ba") --------------------------------
-import os  # noqa: E402
-
 import refine_ref as RR  # noqa: E402
-from velocity_amd import synth  # noqa: E402
+import scenes as S  # noqa: E402
+from session_support import raw_export, same_dict, session_at, step_to  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-T0 = np.float32([1.5, 0.45, 3.6])
-
-
-def _camera(W, H, f):
-    K = synth.K_1080P.copy()
-    K[0, 0] = K[1, 1] = f
-    K[2, 0], K[2, 1] = W / 2 + 0.5, H / 2 + 0.5
-    return K
-
-
-def _scene(W, H, n0, nframes, seed, f=700.0, hopeless=37):
-    """The scene recipe of test_gpu_mixed_cameras.py (a test module imports no other test module): (frames, p, p3, vp, K).  Every `hopeless`-th track
-    (window far outside the frame) dies at once.  In these short clean clips no other track dies (observed: 145 survivors of 150 in every stream with the
-    recipe's 37), so the streams get different strides to keep different numbers of tracks."""
-    K = _camera(W, H, f)
-    m = synth.PlaneMotion(K, z0=3.6)
-    frames = [synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(nframes)]
-    p = synth.grid_tracks(n0, W, H, seed=seed & 0xFF)
-    p[::hopeless] = np.float32([-40.0, -40.0])
-    p3 = m.world_points(p)
-    vp = (p[:, 0] > W * 0.3) & (p[:, 0] < W * 0.7) & (p[:, 1] > H * 0.3) & (p[:, 1] < H * 0.7)
-    return frames, p, p3, vp, K
-
-
-N0, NF, NHIST = 150, 8, 10
-_SCENES = []
-
-
-def _scenes3():
-    if not _SCENES:
-        _SCENES.extend([_scene(320, 240, N0, NHIST, 411, 700.0), _scene(256, 192, N0, NHIST, 422, 560.0, hopeless=11), _scene(320, 240, N0, NHIST, 433, 700.0, hopeless=7)])
-    return _SCENES
-
-
-def _session_at(frame):
-    """Three streams of two cameras in one session, stepped to `frame` (each stream on its own clock)."""
-    from velocity_amd.driver import TrackerSession
-
-    scenes = _scenes3()
-    ses = TrackerSession(scenes[0][4], 320, 240, N0, nhist=NHIST, batch=3, msv_frame=5)
-    for b, (frames, p, p3, vp, Kb) in enumerate(scenes):
-        ses.init_stream(b, frames[0], p, p3, vp, T0, time0=10.0 * b, K=Kb)
-    _step_to(ses, 1, frame)
-    return ses
-
-
-def _step_to(ses, first, last):
-    import torch
-
-    scenes = _scenes3()
-    for k in range(first, last + 1):
-        ses.step([torch.from_numpy(sc[0][k]).cuda() for sc in scenes], time_s=[np.float32(10.0 * b + k / (25.0 + b)) for b in range(3)], frame_no=[k] * 3)
+N0, NF, NHIST = 150, 8, 10  # the three streams of two cameras of scenes.scenes3 (three strides of hopeless tracks: three track counts)
 
 
 def _ba_equals_model(ba, K, P, p3, B, n, where):
@@ -225,26 +172,14 @@ def _ba_equals_model(ba, K, P, p3, B, n, where):
     return ref
 
 
-def _raw_export(ses, b):
-    h = ses.export(b)
-    h.result()
-    return h.buf.numpy()[: h.layout.bytes].tobytes()
-
-
-def _same_state(a, b, where):
-    assert a.keys() == b.keys(), where
-    for key in a:
-        assert np.array_equal(np.asarray(a[key]), np.asarray(b[key]), equal_nan=np.asarray(a[key]).dtype.kind == "f"), (where, key)
-
-
 def test_session_refine_equals_the_model_and_leaves_the_session_alone():
-    scenes = _scenes3()
-    ses, twin = _session_at(NF - 1), _session_at(NF - 1)
-    before = [_raw_export(ses, b) for b in range(3)]
+    scenes = S.scenes3(N0, NHIST)
+    ses, twin = session_at(scenes, NF - 1), session_at(scenes, NF - 1)
+    before = [raw_export(ses, b) for b in range(3)]
     h = ses.refine([0, 1, 2])
     got = h.result()
     assert h.done() and len(got) == 3
-    assert [_raw_export(ses, b) for b in range(3)] == before
+    assert [raw_export(ses, b) for b in range(3)] == before
     counts = []
     for b in range(3):
         st = ses.state(b)
@@ -254,10 +189,10 @@ def test_session_refine_equals_the_model_and_leaves_the_session_alone():
         counts.append(got[b]["nt"])
     assert len(set(counts)) == 3 and min(counts) > 0, counts  # one launch sequence, three track counts, two cameras
     # the refined session steps on as the one that never refined
-    _step_to(ses, NF, NF + 1)
-    _step_to(twin, NF, NF + 1)
+    step_to(ses, scenes, NF, NF + 1)
+    step_to(twin, scenes, NF, NF + 1)
     for b in range(3):
-        _same_state(ses.state(b), twin.state(b), f"stream {b} two frames later")
+        same_dict(ses.state(b), twin.state(b), f"stream {b} two frames later")
 
 
 def test_session_refine_refusals_queue_nothing():
@@ -267,7 +202,7 @@ def test_session_refine_refusals_queue_nothing():
 
     from velocity_amd import _lib as L
 
-    ses = _session_at(NF - 1)
+    ses = session_at(S.scenes3(N0, NHIST), NF - 1)
     first = ses.refine([0, 1, 2]).result()
     lay = ses.refine_layout(10)
     lib = ses.lib
@@ -303,21 +238,6 @@ def test_session_refine_refusals_queue_nothing():
     assert np.array_equal(swapped[0]["cw"], first[2]["cw"]) and np.array_equal(swapped[1]["pw"], first[0]["pw"])
 
 
-def _plate_quad(K, X, Y, Z):
-    from velocity_amd.common import worldPointsLicensePlate
-
-    P = worldPointsLicensePlate("Chile").astype(np.float64) + np.array([X, Y, Z])
-    uvw = P @ np.asarray(K, np.float64)
-    return (uvw[:, :2] / uvw[:, 2:]).astype(np.float32)
-
-
-def _synthetic_clip(W, H, f, n, seed, name):
-    K = _camera(W, H, f)
-    m = synth.PlaneMotion(K, z0=3.6)
-    frames = np.stack([synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(n)])
-    return dict(frames=frames, q=_plate_quad(K, 0.1, -0.05, 3.6), times=np.arange(n, dtype=np.float32) / np.float32(25.0), name=name, K=K)
-
-
 KW = dict(roi_border=(60, 40), max_corners=150)
 _ALONE = {}
 
@@ -339,7 +259,7 @@ def _result_equals_model(res, K, where):
 def test_run_sequence_refine_ba():
     from velocity_amd.driver import ba_line, run_sequence
 
-    c = _synthetic_clip(320, 240, 700.0, 8, 501, "synthetic 320 x 240")
+    c = S.plate_clip(320, 240, 700.0, 8, 501, "synthetic 320 x 240")
     args = dict(times=c["times"], clock=lambda: 0.0, name=c["name"], **KW)
     plain, printed = run_sequence(c["frames"], c["q"], c["K"], out=None, **args), []
     got = run_sequence(c["frames"], c["q"], c["K"], out=printed.append, refine="ba", **args)
@@ -361,8 +281,8 @@ def test_run_queue_and_run_sequences_refine_ba():
     from velocity_amd.driver import run_queue, run_sequences
 
     cams = ((320, 240, 700.0), (256, 192, 560.0))
-    clips = [_synthetic_clip(*cams[k % 2], n, 600 + k, f"clip {k}") for k, n in enumerate((6, 8, 8, 6, 7))]
-    K0 = _camera(320, 240, 650.0)
+    clips = [S.plate_clip(*cams[k % 2], n, 600 + k, f"clip {k}") for k, n in enumerate((6, 8, 8, 6, 7))]
+    K0 = S.camera(320, 240, 650.0)
     plain = run_queue(clips, K0, streams=2, sessions=1, max_size=(240, 320), **KW)
     got = run_queue(clips, K0, streams=2, sessions=1, max_size=(240, 320), refine="ba", **KW)
     assert len(got) == len(plain) == 5
@@ -393,7 +313,7 @@ def test_real_stills_refine_ba():
     +I damping): what is asserted is parity with the model."""
     from velocity_amd.driver import run_sequence
 
-    d = np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
+    d = S.load_stills()
     res = run_sequence(d["b_frames"], d["b_q"], d["b_K"], times=d["b_times"], roi_border=(180, 140), out=None, live=False, refine="ba")
     ba = res["ba"]
     _result_equals_model(res, d["b_K"], "stills b")

@@ -5,82 +5,34 @@ Tolerances: a window against the model is held to what tests/test_gpu_refine.py 
 windows call): nt and ids exact, iterations and converged equal, the rest within rtol 1e-6 / atol 1e-8.  Two device solves of the same window are
 bit-identical except for the trace, whose sums of squares are accumulated with atomics (rtol 1e-12)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import refine_window_ref as RW
+import scenes as S
+from scenes import T0
+from session_support import raw_export, same_dict, session_at, step_to
 from velocity_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-T0 = np.float32([1.5, 0.45, 3.6])
 N0, NHIST, AT, W4 = 150, 12, 8, 4
-PATCH, PATCH_FROM = (0, 0, 120, 240), 4  # (x0, y0, x1, y1) of stream 2 is noise from frame 4 on
+# (x0, y0, x1, y1) of stream 2 is noise from frame 4 on: the tracks inside fail the forward-backward gate THERE -- tracks that die in the middle of the
+# clip (found with oracle/session_oracle.py: 128 tracks live through frames 0..3, 95 of them through 5..8)
+PATCH = (0, 0, 120, 240)
+_SES = {}
 
 
-def _camera(W, H, f):
-    K = synth.K_1080P.copy()
-    K[0, 0] = K[1, 1] = f
-    K[2, 0], K[2, 1] = W / 2 + 0.5, H / 2 + 0.5
-    return K
-
-
-def _scene(W, H, n0, nframes, seed, f=700.0, hopeless=37, patch=None):
-    """The scene recipe of test_gpu_refine.py (a test module imports no other test module): (frames, p, p3, vp, K).  Every `hopeless`-th track dies
-    at once.  patch: that rectangle of every frame from PATCH_FROM on is fresh noise, so the tracks inside fail the forward-backward gate THERE --
-    tracks that die in the middle of the clip (found with oracle/session_oracle.py: 128 tracks live through frames 0..3, 95 of them through 5..8)."""
-    K = _camera(W, H, f)
-    m = synth.PlaneMotion(K, z0=3.6)
-    frames = [synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(nframes)]
-    if patch:
-        x0, y0, x1, y1 = patch
-        for k in range(PATCH_FROM, nframes):
-            frames[k] = frames[k].copy()
-            frames[k][y0:y1, x0:x1] = np.random.default_rng(seed * 1000 + k).integers(0, 256, (y1 - y0, x1 - x0), dtype=np.uint8)
-    p = synth.grid_tracks(n0, W, H, seed=seed & 0xFF)
-    p[::hopeless] = np.float32([-40.0, -40.0])
-    p3 = m.world_points(p)
-    vp = (p[:, 0] > W * 0.3) & (p[:, 0] < W * 0.7) & (p[:, 1] > H * 0.3) & (p[:, 1] < H * 0.7)
-    return frames, p, p3, vp, K
-
-
-_SCENES, _SES = [], {}
-
-
-def _scenes3():
-    if not _SCENES:
-        _SCENES.extend([_scene(320, 240, N0, NHIST, 411, 700.0), _scene(256, 192, N0, NHIST, 422, 560.0, hopeless=11),
-                        _scene(320, 240, N0, NHIST, 433, 700.0, hopeless=7, patch=PATCH)])
-    return _SCENES
-
-
-def _step_to(ses, first, last):
-    import torch
-
-    scenes = _scenes3()
-    for k in range(first, last + 1):
-        ses.step([torch.from_numpy(sc[0][k]).cuda() for sc in scenes], time_s=[np.float32(10.0 * b + k / (25.0 + b)) for b in range(3)], frame_no=[k] * 3)
-
-
-def _session_at(frame):
-    """Three streams of two cameras in one session, stepped to `frame` (each stream on its own clock)."""
-    from velocity_amd.driver import TrackerSession
-
-    scenes = _scenes3()
-    ses = TrackerSession(scenes[0][4], 320, 240, N0, nhist=NHIST, batch=3, msv_frame=5)
-    for b, (frames, p, p3, vp, Kb) in enumerate(scenes):
-        ses.init_stream(b, frames[0], p, p3, vp, T0, time0=10.0 * b, K=Kb)
-    _step_to(ses, 1, frame)
-    return ses
+def _patched3():
+    """scenes.scenes3 with the patch in its third stream."""
+    return S.scenes3(N0, NHIST, patch=PATCH)
 
 
 def _ses8():
     """THE session of the tests that only read it: at frame AT = 8, with its three host states."""
     if not _SES:
-        ses = _session_at(AT)
+        ses = session_at(_patched3(), AT)
         _SES.update(ses=ses, st=[ses.state(b) for b in range(3)])
     return _SES["ses"], _SES["st"]
 
@@ -102,18 +54,6 @@ def _window_equals_model(got, K, st, first, nf, where):
     return ref
 
 
-def _raw_export(ses, b):
-    h = ses.export(b)
-    h.result()
-    return h.buf.numpy()[: h.layout.bytes].tobytes()
-
-
-def _same_state(a, b, where):
-    assert a.keys() == b.keys(), where
-    for key in a:
-        assert np.array_equal(np.asarray(a[key]), np.asarray(b[key]), equal_nan=np.asarray(a[key]).dtype.kind == "f"), (where, key)
-
-
 def test_window_zero_of_a_finished_clip_is_the_whole_clip_entry():
     ses, _ = _ses8()
     NF = AT + 1
@@ -131,7 +71,7 @@ def test_window_zero_of_a_finished_clip_is_the_whole_clip_entry():
 
 def test_windows_that_are_not_the_whole_clip_equal_the_model():
     ses, st = _ses8()
-    scenes = _scenes3()
+    scenes = _patched3()
     wins = [(0, 0), (0, 3), (1, 0), (1, 4), (2, 2)]
     assert all(st[b]["frame_i"] == AT and f + W4 - 1 < AT for b, f in wins)  # none of them ends at the current frame
     h = ses.refine_windows(wins, W4, with_points=True)
@@ -149,7 +89,7 @@ def test_windows_that_are_not_the_whole_clip_equal_the_model():
 
 def test_tracks_that_die_mid_clip_belong_to_the_early_window_only():
     ses, st = _ses8()
-    K = _scenes3()[2][4]
+    K = _patched3()[2][4]
     early, late = ses.refine_windows([(2, 0), (2, 5)], W4, with_points=True).result()
     a, b, cur = set(early["ids"]), set(late["ids"]), set(st[2]["ids"])
     print(f"stream 2: {len(a)} tracks in frames 0..3, {len(b)} in 5..8, {len(a - b)} of the early ones gone, {len(cur)} alive now")
@@ -161,15 +101,15 @@ def test_tracks_that_die_mid_clip_belong_to_the_early_window_only():
 
 
 def test_the_session_is_only_read():
-    ses, twin = _session_at(6), _session_at(6)
+    ses, twin = session_at(_patched3(), 6), session_at(_patched3(), 6)
     wins = [(0, 1), (1, 2), (2, 3), (2, 0)]  # (2, 3) ends at the current frame, the others before it
-    before = [_raw_export(ses, b) for b in range(3)]
+    before = [raw_export(ses, b) for b in range(3)]
     mid = ses.refine_windows(wins, W4, with_points=True).result()
-    assert [_raw_export(ses, b) for b in range(3)] == before
-    _step_to(ses, 7, 8)
-    _step_to(twin, 7, 8)
+    assert [raw_export(ses, b) for b in range(3)] == before
+    step_to(ses, _patched3(), 7, 8)
+    step_to(twin, _patched3(), 7, 8)
     for b in range(3):
-        _same_state(ses.state(b), twin.state(b), f"stream {b} two frames later")
+        same_dict(ses.state(b), twin.state(b), f"stream {b} two frames later")
     after = ses.refine_windows(wins, W4, with_points=True).result()  # the same windows once the clip has run on
     for m, a in zip(mid, after):
         assert m["nt"] == a["nt"] > 0 and np.array_equal(m["ids"], a["ids"])
@@ -243,17 +183,15 @@ def test_a_request_past_the_launch_chunk_of_one_call():
     """The library launches pack and unpack 256 windows at a time (their table travels in the kernel arguments).  30 slots -- the three scenes, ten times
     -- at their last frame hold 30 x 9 = 270 distinct windows of W4 frames: ONE vh_session_refine_windows call of two launches, the second of 14 windows
     behind 242 padding entries.  The windows are given start-major, so entries 255 and 256 sit in two slots of two cameras."""
-    import torch
-
     from velocity_amd.driver import TrackerSession
 
-    scenes = _scenes3()
+    scenes = _patched3()
     B, last = 30, NHIST - 1
     ses = TrackerSession(scenes[0][4], 320, 240, N0, nhist=NHIST, batch=B, msv_frame=5)
     for b in range(B):
         frames, p, p3, vp, Kb = scenes[b % 3]
         ses.init_stream(b, frames[0], p, p3, vp, T0, time0=10.0 * b, K=Kb)
-    dev = [[torch.from_numpy(f).cuda() for f in sc[0]] for sc in scenes]
+    dev = [[S.to_cuda(f) for f in sc[0]] for sc in scenes]
     for k in range(1, last + 1):
         ses.step([dev[b % 3][k] for b in range(B)], time_s=[np.float32(10.0 * b + k / (25.0 + b % 3)) for b in range(B)], frame_no=[k] * B)
     wins = [(b, f) for f in range(last - W4 + 2) for b in range(B)]
@@ -282,21 +220,6 @@ def test_a_request_past_the_launch_chunk_of_one_call():
 
 
 # ---- the drivers ---------------------------------------------------------------------------------------------------------------------------------
-def _plate_quad(K, X, Y, Z):
-    from velocity_amd.common import worldPointsLicensePlate
-
-    P = worldPointsLicensePlate("Chile").astype(np.float64) + np.array([X, Y, Z])
-    uvw = P @ np.asarray(K, np.float64)
-    return (uvw[:, :2] / uvw[:, 2:]).astype(np.float32)
-
-
-def _synthetic_clip(W, H, f, n, seed, name, traj=None):
-    K = _camera(W, H, f)
-    m = synth.PlaneMotion(K, z0=3.6, traj=traj)
-    frames = np.stack([synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(n)])
-    return dict(frames=frames, q=_plate_quad(K, 0.1, -0.05, 3.6), times=np.arange(n, dtype=np.float32) / np.float32(25.0), name=name, K=K)
-
-
 def _merged_equals(got, want, where, exact_ints=True):
     """Two merged dicts (merge_window_speeds'): the per-window integers exact, the floats within the window tolerances."""
     for key in ("first", "nt", "iterations", "converged", "cover"):
@@ -305,14 +228,12 @@ def _merged_equals(got, want, where, exact_ints=True):
         np.testing.assert_allclose(got[key], want[key], rtol=1e-6, atol=1e-8, equal_nan=True, err_msg=f"{where}: {key}")
 
 
-_LONG = {}
+_LONG_TRAJ = synth.oscillating_traj(period=65.0)
 
 
 def _long_clip():
     """260 frames of 160 x 120, rendered once: a bounded, periodic camera path (a straight one would leave the scene)."""
-    if not _LONG:
-        _LONG.update(_synthetic_clip(160, 120, 350.0, 260, 907, "260 frames", traj=synth.oscillating_traj(period=65.0)))
-    return _LONG
+    return S.plate_clip(160, 120, 350.0, 260, 907, "260 frames", traj=_LONG_TRAJ)
 
 
 def test_a_clip_longer_than_the_whole_clip_refinement_takes(monkeypatch):
@@ -354,8 +275,8 @@ def test_the_drivers_refine_in_windows(monkeypatch):
     from velocity_amd import driver as D
 
     cams = ((320, 240, 700.0), (256, 192, 560.0))
-    clips = [_synthetic_clip(*cams[k % 2], n, 700 + k, f"clip {k}") for k, n in enumerate(LENGTHS)]
-    K0 = _camera(320, 240, 650.0)
+    clips = [S.plate_clip(*cams[k % 2], n, 700 + k, f"clip {k}") for k, n in enumerate(LENGTHS)]
+    K0 = S.camera(320, 240, 650.0)
     alone = [D.run_sequence(c["frames"], c["q"], c["K"], times=c["times"], out=None, live=False, name=c["name"], refine="ba", refine_window=W4, **KW) for c in clips]
     for c, one in zip(clips, alone):
         n = len(c["frames"])

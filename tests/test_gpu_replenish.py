@@ -2,7 +2,7 @@
 tests/replenish_ref.py::ReplenishOracle, on the scenes of tests/replenish_scenes.py -- 640 x 360 frames, at most 128 frame-0 tracks and 64 spare rows,
 nhist 16, MSV frame 3, a birth every 2 frames, baseline 3.  tests/test_replenish_cpu.py asserts on the same scenes that no newborn's gate and no prefix
 cut is a near-tie, so every comparison here runs without exclusions: masks, ids, points, born, tri and n_rows exactly, p3, B and S with the tolerances
-of test_gpu_session_idle.py::_equals_oracle."""
+of session_support.equals_oracle."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +14,8 @@ import refine_ref as RR  # noqa: E402
 import refine_window_ref as RW  # noqa: E402
 import replenish_scenes as RS  # noqa: E402
 from replenish_ref import ReplenishOracle  # noqa: E402
+from session_support import same_dict  # noqa: E402
+
 
 def _session(scenes, replenish=RS.REP, spare=RS.SPARE, n0=None, W=RS.W, H=RS.H, first_slot=0, **kw):
     """A session of len(scenes) slots (None: never initialised), every stream on its own clock (time0 = 10 b; first_slot: the b of slot 0)."""
@@ -56,12 +58,6 @@ def _equals_model(st, orc, where):
     np.testing.assert_allclose(st["B"][:n, 12:14], orc.B[:n, 12:14], rtol=0, atol=0)
     np.testing.assert_allclose(st["S"][1:n, [0, 2, 4, 5]], orc.S[1:n, [0, 2, 4, 5]], rtol=0, atol=0)
     np.testing.assert_allclose(st["S"][1:n, [3, 6, 7, 8]], orc.S[1:n, [3, 6, 7, 8]], rtol=1e-4)
-
-
-def _same_dict(a, b, where):
-    assert a.keys() == b.keys(), where
-    for key in a:
-        assert np.array_equal(np.asarray(a[key]), np.asarray(b[key]), equal_nan=np.asarray(a[key]).dtype.kind == "f"), (where, key)
 
 
 def test_device_equals_the_model_after_every_step():
@@ -113,10 +109,10 @@ def test_a_batch_of_three_slots_equals_each_stream_alone():
         _step(ses, scenes, ks)
         for b, k in enumerate(ks):
             if k is None:
-                _same_dict(ses.state(b), idle[b], (g, b, "idle"))
+                same_dict(ses.state(b), idle[b], (g, b, "idle"))
                 continue
             solo[b].step([torch.from_numpy(scenes[b]["frames"][k]).cuda()], time_s=[_clock(b, k)], frame_no=[k])
-            _same_dict(ses.state(b), solo[b].state(0), (g, b))
+            same_dict(ses.state(b), solo[b].state(0), (g, b))
     rows = [ses.state(b)["n_rows"] for b in range(3)]
     assert rows[0] > 128 and rows[1] > 128 and rows[2] > 96, rows  # every stream had births
     assert ses.state(2)["frame_i"] == 9 and ses.state(1)["frame_i"] == 9
@@ -131,7 +127,7 @@ def test_option_off_on_a_session_with_spare_rows_is_a_plain_session():
             _step(s, [sc], [k])
     a, b, c = off.state(0), plain.state(0), small.state(0)
     assert "born" not in a and "tri" not in a and "n_rows" not in a
-    _same_dict(a, b, "spare rows against a plain session of as many rows")
+    same_dict(a, b, "spare rows against a plain session of as many rows")
     for key in c:  # ... and against the plain session of n rows, on the rows that one has
         x = a[key]
         if key in ("vg", "vp", "p3"):
@@ -155,7 +151,7 @@ def test_births_stop_when_the_rows_are_exhausted():
     st = ses.state(0)
     assert st["n_rows"] == ses.n0 == len(sc["p"]) + 10 and orc.counts["born"].sum() == 10
     assert [b["entered"] for b in orc.births] == [10] and st["n_cur"] < len(sc["p"])  # later births were due and had nowhere to go
-    _same_dict(ses.state(1), beside, "the slot beside")
+    same_dict(ses.state(1), beside, "the slot beside")
 
 
 def test_a_stream_without_tracks_has_no_birth():

@@ -6,31 +6,17 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle.session_oracle import SessionOracle  # noqa: E402 (checker only)
+from lk_support import klt_order  # noqa: E402
+from scenes import plane_scene, to_cuda  # noqa: E402
 from velocity_amd import synth  # noqa: E402
-
-
-def _scene(W, H, n0, nframes, seed):
-    K = synth.K_1080P.copy()
-    K[0, 0] = K[1, 1] = 700.0
-    K[2, 0], K[2, 1] = W / 2 + 0.5, H / 2 + 0.5
-    m = synth.PlaneMotion(K, z0=3.6)
-    frames = [synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(nframes)]
-    p = synth.grid_tracks(n0, W, H, seed=seed & 0xFF)
-    # a few hopeless tracks (window far outside the frame) so the masks and the compaction actually change
-    p[::37] = np.float32([-40.0, -40.0])
-    p3 = m.world_points(p)
-    vp = (p[:, 0] > W * 0.3) & (p[:, 0] < W * 0.7) & (p[:, 1] > H * 0.3) & (p[:, 1] < H * 0.7)
-    return frames, p, p3, vp, K
 
 
 @pytest.mark.parametrize("msv_frame", [5, 0])
 def test_session_matches_reference_loop(msv_frame):
-    import torch
-
     from velocity_amd.driver import TrackerSession
 
     W, H, n0, nframes = 640, 360, 400, 9
-    frames, p, p3, vp, K = _scene(W, H, n0, nframes, 0xC0FFEE)
+    frames, p, p3, vp, K = plane_scene(W, H, n0, nframes, 0xC0FFEE)
     t0 = np.float32([1.5, 0.45, 3.6])
     orc = SessionOracle(K, frames[0], p, p3, vp, t0, time0=0.0, frame_no=0, res0=0.5, nhist=nframes, msv_frame=msv_frame)
     ses = TrackerSession(K, W, H, n0, nhist=nframes, batch=1, msv_frame=msv_frame)
@@ -38,7 +24,7 @@ def test_session_matches_reference_loop(msv_frame):
     for i in range(1, nframes):
         ts = np.float32(i / 29.97)
         orc.step(frames[i], ts, i)
-        ses.step([torch.from_numpy(frames[i]).cuda()], time_s=ts, frame_no=i)
+        ses.step([to_cuda(frames[i])], time_s=ts, frame_no=i)
         st = ses.state(0)
         assert np.array_equal(st["vg"], orc.vg), f"vg differs at frame {i}"
         assert np.array_equal(st["vp"], orc.vp), f"vp differs at frame {i}"
@@ -61,12 +47,10 @@ def test_session_matches_reference_loop(msv_frame):
 
 
 def test_session_batch_streams_are_independent():
-    import torch
-
     from velocity_amd.driver import TrackerSession
 
     W, H, n0, nframes, B = 480, 270, 200, 5, 3
-    scenes = [_scene(W, H, n0, nframes, 1000 + 77 * b) for b in range(B)]
+    scenes = [plane_scene(W, H, n0, nframes, 1000 + 77 * b) for b in range(B)]
     t0 = np.float32([1.5, 0.45, 3.6])
     ses = TrackerSession(scenes[0][4], W, H, n0, nhist=nframes, batch=B, msv_frame=0)
     orcs = []
@@ -75,7 +59,7 @@ def test_session_batch_streams_are_independent():
         orcs.append(SessionOracle(K, frames[0], p, p3, vp, t0, nhist=nframes, msv_frame=0))
     for i in range(1, nframes):
         ts = np.float32(i / 30.0)
-        ses.step([torch.from_numpy(scenes[b][0][i]).cuda() for b in range(B)], time_s=ts, frame_no=i)
+        ses.step([to_cuda(scenes[b][0][i]) for b in range(B)], time_s=ts, frame_no=i)
         for b in range(B):
             orcs[b].step(scenes[b][0][i], ts, i)
     for b in range(B):
@@ -91,13 +75,11 @@ def test_session_batches_with_partial_stream_sets(B, n0):
     XCD-pinned from 64 on).  20 streams = a full fine set + a tail of 4, one (rotated) coarse set; 70 streams = a pinned coarse set of 64 + a tail of 6.
     Streams carry different scenes and different track counts (every third stream loses half of its tracks before the first step): each stream must
     still equal its own oracle, bit for bit."""
-    import torch
-
     from velocity_amd.driver import TrackerSession
 
     W, H, nframes = 320, 240, 3
     assert B * n0 >= 3000  # the 4-tracks-per-wavefront coarse kernel (the strip kernel below that is not re-indexed)
-    scenes = [_scene(W, H, n0, nframes, 4000 + 31 * b) for b in range(B)]
+    scenes = [plane_scene(W, H, n0, nframes, 4000 + 31 * b) for b in range(B)]
     t0 = np.float32([1.5, 0.45, 3.6])
     ses = TrackerSession(scenes[0][4], W, H, n0, nhist=nframes, batch=B, msv_frame=0)
     orcs = []
@@ -109,7 +91,7 @@ def test_session_batches_with_partial_stream_sets(B, n0):
         orcs.append(SessionOracle(K, frames[0], p, p3, vp, t0, nhist=nframes, msv_frame=0))
     for i in range(1, nframes):
         ts = np.float32(i / 30.0)
-        ses.step([torch.from_numpy(scenes[b][0][i]).cuda() for b in range(B)], time_s=ts, frame_no=i)
+        ses.step([to_cuda(scenes[b][0][i]) for b in range(B)], time_s=ts, frame_no=i)
         for b in range(B):
             orcs[b].step(scenes[b][0][i], ts, i)
     for b in range(B):
@@ -127,7 +109,7 @@ def test_host_frame_feeder_gives_the_same_tracks(pinned):
     from velocity_amd.driver import HostFrameFeeder, TrackerSession
 
     W, H, n0, nframes, B = 480, 270, 200, 8, 2
-    scenes = [_scene(W, H, n0, nframes, 4242 + 13 * b) for b in range(B)]
+    scenes = [plane_scene(W, H, n0, nframes, 4242 + 13 * b) for b in range(B)]
     t0 = np.float32([1.5, 0.45, 3.6])
     out = []
     for mode in ("device", "host"):
@@ -160,14 +142,14 @@ def test_session_survives_total_track_loss():
     from velocity_amd.driver import TrackerSession
 
     W, H, n0, nframes = 480, 270, 150, 6
-    frames, p, p3, vp, K = _scene(W, H, n0, nframes, 99)
+    frames, p, p3, vp, K = plane_scene(W, H, n0, nframes, 99)
     ses = TrackerSession(K, W, H, n0, nhist=nframes + 2, batch=1, msv_frame=0)
     ses.init_stream(0, frames[0], p, p3, vp, np.float32([1.5, 0.45, 3.6]))
-    ses.step([torch.from_numpy(frames[1]).cuda()], time_s=1 / 30.0, frame_no=1)
+    ses.step([to_cuda(frames[1])], time_s=1 / 30.0, frame_no=1)
     assert ses.state(0)["n_cur"] > 100
     blank = torch.full((H, W), 128, dtype=torch.uint8, device="cuda")
     for i in range(2, nframes):
-        f = blank if i < 4 else torch.from_numpy(frames[i]).cuda()
+        f = blank if i < 4 else to_cuda(frames[i])
         ses.step([f], time_s=i / 30.0, frame_no=i)
         st = ses.state(0)
         assert st["n_cur"] == 0 and st["n_pose"] == 0
@@ -178,15 +160,13 @@ def test_session_survives_total_track_loss():
 def test_streams_started_at_different_times_keep_their_own_clock_and_msv_frame():
     """Two streams in one session; stream 1 is RE-INITIALISED with a new clip after 3 steps and gets its own timestamps.  Each stream must equal
     its own reference loop: fcnMSV1_t fires at frame 5 OF EACH CLIP (vidExample.py:155), dt / time / speed come from the stream's own clock."""
-    import torch
-
     from velocity_amd.driver import TrackerSession
 
     W, H, n0, nfr = 480, 270, 220, 8
     t0 = np.float32([1.5, 0.45, 3.6])
-    A = _scene(W, H, n0, nfr + 3, 555)     # stream 0: runs nfr + 2 steps
-    B1 = _scene(W, H, n0, 4, 777)          # stream 1, first clip (3 steps)
-    B2 = _scene(W, H, n0, nfr, 999)        # stream 1, second clip, started at global step 3
+    A = plane_scene(W, H, n0, nfr + 3, 555)     # stream 0: runs nfr + 2 steps
+    B1 = plane_scene(W, H, n0, 4, 777)          # stream 1, first clip (3 steps)
+    B2 = plane_scene(W, H, n0, nfr, 999)        # stream 1, second clip, started at global step 3
     ses = TrackerSession(A[4], W, H, n0, nhist=nfr + 3, batch=2, msv_frame=5)
     ses.init_stream(0, A[0][0], A[1], A[2], A[3], t0, time0=0.0)
     ses.init_stream(1, B1[0][0], B1[1], B1[2], B1[3], t0, time0=10.0)
@@ -200,7 +180,7 @@ def test_streams_started_at_different_times_keep_their_own_clock_and_msv_frame()
             kB, clipB = 0, B2
         kB += 1
         tA, tB = np.float32(g / 29.97), np.float32((20.0 if clipB is B2 else 10.0) + kB / 25.0)
-        ses.step([torch.from_numpy(A[0][g]).cuda(), torch.from_numpy(clipB[0][kB]).cuda()], time_s=[tA, tB], frame_no=[g, kB])
+        ses.step([to_cuda(A[0][g]), to_cuda(clipB[0][kB])], time_s=[tA, tB], frame_no=[g, kB])
         oA.step(A[0][g], tA, g)
         oB.step(clipB[0][kB], tB, kB)
         for slot, orc in ((0, oA), (1, oB)):
@@ -222,35 +202,28 @@ def test_streams_started_at_different_times_keep_their_own_clock_and_msv_frame()
 def test_session_with_more_than_4096_tracks_takes_the_unfused_path(order):
     """N0 > 4096: the pose fit no longer fits the 256-thread fused frame kernel (bookkeeping, 1024-thread pose, records as three launches).
     order = 1: the LK launches walk the tracks in spatial order (vh_debug_klt_order; the counting sort then takes several passes per thread)."""
-    import torch
-
-    from velocity_amd import _lib as L
     from velocity_amd.driver import TrackerSession
 
-    L.load().vh_debug_klt_order(order)
-
     W, H, n0, nframes = 960, 540, 4500, 4
-    frames, p, p3, vp, K = _scene(W, H, n0, nframes, 31337)
+    frames, p, p3, vp, K = plane_scene(W, H, n0, nframes, 31337)
     t0 = np.float32([1.5, 0.45, 3.6])
     orc = SessionOracle(K, frames[0], p, p3, vp, t0, nhist=nframes, msv_frame=0)
     ses = TrackerSession(K, W, H, n0, nhist=nframes, batch=1, msv_frame=0)
-    ses.init_stream(0, frames[0], p, p3, vp, t0)
-    for i in range(1, nframes):
-        ts = np.float32(i / 30.0)
-        orc.step(frames[i], ts, i)
-        ses.step([torch.from_numpy(frames[i]).cuda()], time_s=ts, frame_no=i)
-        st = ses.state(0)
-        assert np.array_equal(st["vg"], orc.vg) and np.array_equal(st["vp"], orc.vp) and np.array_equal(st["p"], orc.p), i
-        np.testing.assert_allclose(st["t"], orc.t, rtol=1e-5)
-        np.testing.assert_allclose(st["res"], orc.residuals, rtol=1e-6)
-    L.load().vh_debug_klt_order(-1)
+    with klt_order(order):  # (restored whatever happens)
+        ses.init_stream(0, frames[0], p, p3, vp, t0)
+        for i in range(1, nframes):
+            ts = np.float32(i / 30.0)
+            orc.step(frames[i], ts, i)
+            ses.step([to_cuda(frames[i])], time_s=ts, frame_no=i)
+            st = ses.state(0)
+            assert np.array_equal(st["vg"], orc.vg) and np.array_equal(st["vp"], orc.vp) and np.array_equal(st["p"], orc.p), i
+            np.testing.assert_allclose(st["t"], orc.t, rtol=1e-5)
+            np.testing.assert_allclose(st["res"], orc.residuals, rtol=1e-6)
 
 
 def test_session_on_a_rolling_zooming_scene():
     """Camera roll + zoom + translation (SURVEY section 8d's rotation): the stage-3 affine warp leaves its near-identity fast path and gathers;
     tracks, masks and compaction stay bit-identical to the reference loop."""
-    import torch
-
     from velocity_amd.driver import TrackerSession
 
     W, H, n0, nframes = 800, 450, 500, 7
@@ -269,7 +242,7 @@ def test_session_on_a_rolling_zooming_scene():
     for i in range(1, nframes):
         ts = np.float32(i / 30.0)
         orc.step(frames[i], ts, i)
-        ses.step([torch.from_numpy(frames[i]).cuda()], time_s=ts, frame_no=i)
+        ses.step([to_cuda(frames[i])], time_s=ts, frame_no=i)
         st = ses.state(0)
         assert np.array_equal(st["vg"], orc.vg) and np.array_equal(st["p"], orc.p), i
         np.testing.assert_allclose(st["res"], orc.residuals, rtol=1e-6)
@@ -441,7 +414,7 @@ def test_session_step_from_bgr_frames_equals_gray_path():
 
     W, H, n0, nframes, B = 482, 270, 180, 6, 2   # W / 4 = 120.5: the quarter-scale width rounds to even
     rng = np.random.default_rng(5)
-    scenes = [_scene(W, H, n0, nframes, 321 + 11 * b) for b in range(B)]
+    scenes = [plane_scene(W, H, n0, nframes, 321 + 11 * b) for b in range(B)]
     # colour frames whose luma is NOT the synthetic gray frame (random chroma), so the conversion really matters
     bgr = [[np.clip(np.stack([scenes[b][0][i].astype(int) + rng.integers(-20, 21, (H, W)) * (c - 1) for c in range(3)], -1), 0, 255).astype(np.uint8)
             for i in range(nframes)] for b in range(B)]
@@ -473,23 +446,21 @@ def test_profile_table_overflow_is_an_error_not_an_undercount():
     Now the dropped records are counted and vh_profile_end / vh_profile_end_stages fail loudly."""
     import ctypes as C
 
-    import torch
-
     from velocity_amd import _lib as L
     from velocity_amd.driver import TrackerSession
 
     W, H, n0 = 320, 180, 64
-    frames, p, p3, vp, K = _scene(W, H, n0, 3, 5)
+    frames, p, p3, vp, K = plane_scene(W, H, n0, 3, 5)
     ses = TrackerSession(K, W, H, n0, nhist=6, batch=1, msv_frame=0)
     ses.init_stream(0, frames[0], p, p3, vp, np.float32([1.5, 0.45, 3.6]))
     L.check(ses.lib.vh_profile_detail(ses.ws.handle, 1), "detail")
     L.check(ses.lib.vh_profile_begin(ses.ws.handle, 3), "begin")  # three records: a step issues ~20
-    ses.step([torch.from_numpy(frames[1]).cuda()], time_s=1 / 30.0, frame_no=1)
+    ses.step([to_cuda(frames[1])], time_s=1 / 30.0, frame_no=1)
     ms, nl = (C.c_double * 16)(), (C.c_int * 16)()
     rc = ses.lib.vh_profile_end_stages(ses.ws.handle, 16, ms, nl)
     assert rc != 0 and b"too small" in ses.lib.vh_last_error()
     L.check(ses.lib.vh_profile_begin(ses.ws.handle, 64), "begin")  # large enough: fine again
-    ses.step([torch.from_numpy(frames[2]).cuda()], time_s=2 / 30.0, frame_no=2)
+    ses.step([to_cuda(frames[2])], time_s=2 / 30.0, frame_no=2)
     L.check(ses.lib.vh_profile_end_stages(ses.ws.handle, 16, ms, nl), "end_stages")
     assert sum(nl) >= 10
 
@@ -500,7 +471,7 @@ def test_session_with_a_never_msv_sentinel_allocates_no_msv_history():
     from velocity_amd.driver import TrackerSession
 
     W, H, n0 = 320, 180, 512
-    frames, p, p3, vp, K = _scene(W, H, n0, 2, 6)
+    frames, p, p3, vp, K = plane_scene(W, H, n0, 2, 6)
     ses = TrackerSession(K, W, H, n0, nhist=6, batch=2, msv_frame=1 << 24)  # 24 B * 2^24 * 512 = 206 GB per stream if it were carved
     ses.init_stream(0, frames[0], p, p3, vp, np.float32([1.5, 0.45, 3.6]))
     assert ses.state(0)["n_cur"] == n0

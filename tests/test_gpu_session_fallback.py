@@ -2,7 +2,6 @@
 for bit, then TrackerSession / run_sequence / run_sequences with fallback=True against the oracles whose klt_main is wrapped with match_ref.recover (the way
 tests/test_gpu_match.py checks the drop-in loop).  The model of a frame pair costs seconds of CPU, so every pair is computed once and shared."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -13,9 +12,9 @@ import match_ref as MR  # noqa: E402
 from oracle import driver_oracle as DO  # noqa: E402 (checker only)
 from oracle import klt_oracle as KO  # noqa: E402 (checker only)
 from oracle.session_oracle import SessionOracle  # noqa: E402 (checker only)
+from scenes import load_stills as stills  # noqa: E402
 from velocity_amd import synth  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, N0, NH = 480, 270, 100, 8
 T0 = np.float32([0.0, 0.0, 3.6])
 SHIFTS = {"jump": ((0, 100, 103, 106), 0xC0FFEE), "calm": ((0, 3, 6, 9), 0xC0FFEE + 1)}
@@ -51,11 +50,6 @@ def clip(name):
     c, seed = SHIFTS[name]
     m = [synth.AffineMotion(W, H, tx=ck, ty=0) for ck in c]
     return [synth.render_frame(W, H, mk, 1, seed).numpy() for mk in m]
-
-
-@functools.lru_cache(maxsize=None)
-def stills():
-    return np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
 
 
 class Recovering:

@@ -8,41 +8,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle.session_oracle import SessionOracle  # noqa: E402 (checker only)
+from scenes import T0, plane_scene, to_cuda  # noqa: E402
+from session_support import equals_oracle, same_dict  # noqa: E402
 from velocity_amd import synth  # noqa: E402
-
-T0 = np.float32([1.5, 0.45, 3.6])
-
-
-def _scene(W, H, n0, nframes, seed):
-    K = synth.K_1080P.copy()
-    K[0, 0] = K[1, 1] = 700.0
-    K[2, 0], K[2, 1] = W / 2 + 0.5, H / 2 + 0.5
-    m = synth.PlaneMotion(K, z0=3.6)
-    frames = [synth.render_frame(W, H, m, k, seed=seed).numpy() for k in range(nframes)]
-    p = synth.grid_tracks(n0, W, H, seed=seed & 0xFF)
-    # a few hopeless tracks (window far outside the frame) so the masks and the compaction actually change
-    p[::37] = np.float32([-40.0, -40.0])
-    p3 = m.world_points(p)
-    vp = (p[:, 0] > W * 0.3) & (p[:, 0] < W * 0.7) & (p[:, 1] > H * 0.3) & (p[:, 1] < H * 0.7)
-    return frames, p, p3, vp, K
-
-
-def _same_dict(a, b, where):
-    assert a.keys() == b.keys(), where
-    for key in a:
-        assert np.array_equal(np.asarray(a[key]), np.asarray(b[key]), equal_nan=np.asarray(a[key]).dtype.kind == "f"), (where, key)
-
-
-def _equals_oracle(st, orc, where, records=True):
-    assert st["frame_i"] == orc.i, where
-    assert np.array_equal(st["vg"], orc.vg) and np.array_equal(st["vp"], orc.vp), where
-    assert np.array_equal(st["ids"], np.nonzero(orc.vg)[0]) and np.array_equal(st["p"], orc.p), where
-    np.testing.assert_allclose(st["p3"], orc.p3, rtol=1e-4, atol=1e-5)
-    if records:
-        n = orc.i + 1
-        np.testing.assert_allclose(st["B"][:n, 12:14], orc.B[:n, 12:14], rtol=0, atol=0)
-        np.testing.assert_allclose(st["S"][1:n, [0, 2, 4, 5]], orc.S[1:n, [0, 2, 4, 5]], rtol=0, atol=0)
-        np.testing.assert_allclose(st["S"][1:n, [3, 6, 7, 8]], orc.S[1:n, [3, 6, 7, 8]], rtol=1e-4)
 
 
 class _Streams:
@@ -65,8 +33,6 @@ class _Streams:
 
     def step(self, active, bgr=None):
         """active: one flag per stream.  Each active stream gets the next frame of its own clip on its own clock."""
-        import torch
-
         frames, ts, fn = [], [], []
         for b, a in enumerate(active):
             if not a:
@@ -77,7 +43,7 @@ class _Streams:
             self.k[b] += 1
             k = self.k[b]
             t = np.float32(10.0 * b + k / (25.0 + b))
-            frames.append(torch.from_numpy(self.scenes[b][0][k] if bgr is None else bgr[b][k]).cuda())
+            frames.append(to_cuda(self.scenes[b][0][k] if bgr is None else bgr[b][k]))
             ts.append(t)
             fn.append(k)
             if b in self.orc:
@@ -95,7 +61,7 @@ TABLE = [(0, 1, 1), (0, 0, 1), (1, 0, 1), (1, 1, 0), (1, 1, 0), (0, 0, 0), (1, 1
 
 def _table_run(steps, check):
     W, H, n0 = 480, 270, 220
-    run = _Streams([_scene(W, H, n0, 6, 555 + 222 * b) for b in range(3)], W, H, n0, nhist=8, msv_frame=3)
+    run = _Streams([plane_scene(W, H, n0, 6, 555 + 222 * b) for b in range(3)], W, H, n0, nhist=8, msv_frame=3)
     prev = [run.ses.state(b) for b in range(3)]
     for g, active in enumerate(TABLE[:steps], 1):
         run.step(active)
@@ -104,9 +70,9 @@ def _table_run(steps, check):
         cur = [run.ses.state(b) for b in range(3)]
         for b, a in enumerate(active):
             if a:
-                _equals_oracle(cur[b], run.orc[b], (g, b))
+                equals_oracle(cur[b], run.orc[b], (g, b))
             else:
-                _same_dict(cur[b], prev[b], (g, b))
+                same_dict(cur[b], prev[b], (g, b))
         prev = cur
     return run
 
@@ -119,13 +85,13 @@ def test_streams_sit_steps_out_and_keep_their_own_clock_state_and_msv_frame():
 
 def test_a_slot_that_was_never_initialised_is_a_legal_idle_stream():
     W, H, n0 = 480, 270, 220
-    run = _Streams([_scene(W, H, n0, 5, 1000), None, _scene(W, H, n0, 5, 1077)], W, H, n0, nhist=5, msv_frame=0)
+    run = _Streams([plane_scene(W, H, n0, 5, 1000), None, plane_scene(W, H, n0, 5, 1077)], W, H, n0, nhist=5, msv_frame=0)
     empty = run.ses.state(1)
     for g in range(1, 5):
         run.step((1, 0, 1))
         for b in (0, 2):
-            _equals_oracle(run.ses.state(b), run.orc[b], (g, b))
-        _same_dict(run.ses.state(1), empty, g)
+            equals_oracle(run.ses.state(b), run.orc[b], (g, b))
+        same_dict(run.ses.state(1), empty, g)
 
 
 def test_idle_streams_inside_the_lk_stream_sets():
@@ -135,7 +101,7 @@ def test_idle_streams_inside_the_lk_stream_sets():
     W, H, n0, B = 320, 240, 170, 20
     scenes = []
     for b in range(B):
-        frames, p, p3, vp, K = _scene(W, H, n0, 5, 4000 + 31 * b)
+        frames, p, p3, vp, K = plane_scene(W, H, n0, 5, 4000 + 31 * b)
         if b % 3 == 1:
             p = p.copy()
             p[n0 // 2:] = np.float32([-60.0, -60.0])
@@ -146,26 +112,26 @@ def test_idle_streams_inside_the_lk_stream_sets():
         before = {b: run.ses.state(b) for b in range(B) if not active[b]}
         run.step(active)
         for b, st in before.items():
-            _same_dict(run.ses.state(b), st, (g, b))
+            same_dict(run.ses.state(b), st, (g, b))
         for b in (3, 7, 18):
             if active[b]:
-                _equals_oracle(run.ses.state(b), run.orc[b], (g, b))
+                equals_oracle(run.ses.state(b), run.orc[b], (g, b))
     assert [run.orc[b].i for b in (3, 7, 18)] == [2, 4, 2]
 
 
 def test_an_idle_stream_on_the_unfused_bookkeeping_path():
     """N0 = 4500 > 4096: bookkeeping, the 1024-thread pose kernel and the records are three launches, each of which must pass an idle stream by."""
     W, H, n0 = 960, 540, 4500
-    run = _Streams([_scene(W, H, n0, 4, 31337), _scene(W, H, n0, 3, 31338)], W, H, n0, nhist=4, msv_frame=0)
+    run = _Streams([plane_scene(W, H, n0, 4, 31337), plane_scene(W, H, n0, 3, 31338)], W, H, n0, nhist=4, msv_frame=0)
     for g, active in enumerate([(1, 1), (1, 0), (1, 1)], 1):
         before = run.ses.state(1)
         run.step(active)
         for b in (0, 1):
             if active[b]:
-                _equals_oracle(run.ses.state(b), run.orc[b], (g, b))
+                equals_oracle(run.ses.state(b), run.orc[b], (g, b))
                 np.testing.assert_allclose(run.ses.state(b)["t"], run.orc[b].t, rtol=1e-5)
             else:
-                _same_dict(run.ses.state(b), before, (g, b))
+                same_dict(run.ses.state(b), before, (g, b))
 
 
 def test_step_bgr_with_an_idle_stream_equals_the_gray_path():
@@ -175,7 +141,7 @@ def test_step_bgr_with_an_idle_stream_equals_the_gray_path():
 
     W, H, n0, B = 482, 270, 180, 2
     rng = np.random.default_rng(5)
-    scenes = [_scene(W, H, n0, 6, 321 + 11 * b) for b in range(B)]
+    scenes = [plane_scene(W, H, n0, 6, 321 + 11 * b) for b in range(B)]
     bgr = [[np.clip(np.stack([sc[0][i].astype(int) + rng.integers(-20, 21, (H, W)) * (c - 1) for c in range(3)], -1), 0, 255).astype(np.uint8)
             for i in range(6)] for sc in scenes]
     gray = [([KO.bgr2gray(f) for f in bgr[b]],) + scenes[b][1:] for b in range(B)]
@@ -193,9 +159,9 @@ def test_step_bgr_with_an_idle_stream_equals_the_gray_path():
         states.append([run.ses.state(b) for b in range(B)])
         if mode == "gray":
             for b in range(B):
-                _equals_oracle(states[0][b], run.orc[b], b)
+                equals_oracle(states[0][b], run.orc[b], b)
     for b in range(B):
-        _same_dict(states[0][b], states[1][b], b)
+        same_dict(states[0][b], states[1][b], b)
     assert [s["frame_i"] for s in states[1]] == [4, 3]
 
 
@@ -209,7 +175,7 @@ def test_export_is_one_record_equal_to_state():
     handles = [ses.export(b) for b in range(3)]  # three packs and copies in flight before anybody waits
     for b, h in enumerate(handles):
         st, ex = ses.state(b), h.result()
-        _same_dict(ex, st, b)
+        same_dict(ex, st, b)
         assert ex["P"].shape == (5, 220, 8) and ex["P"].flags["C_CONTIGUOUS"]
         assert tuple(h.recoveries) == (0, 0) and h.done()
     assert np.isnan(handles[0].result()["P"][0, :, 3:]).all() and not np.isnan(handles[2].result()["P"][4, :, 0]).any()
@@ -233,7 +199,7 @@ def test_an_idle_stream_with_a_stale_failure_flag_is_not_recovered_again():
     assert st["klt_flags"] & 1 and st["n_cur"] > 0 and tuple(run.ses.recoveries()[0]) == (1, 1) and tuple(run.ses.recoveries()[1]) == (0, 0)
     for g in (2, 3):
         run.step((0, 1))
-        _same_dict(run.ses.state(0), st, g)
+        same_dict(run.ses.state(0), st, g)
         assert run.ses.recoveries().tolist() == [[1, 1], [0, 0]]
     run.step((1, 0))
     assert run.ses.state(0)["frame_i"] == 2 and run.ses.recoveries().tolist() == [[1, 1], [0, 0]]

@@ -7,7 +7,6 @@ then KLTmain + bookkeeping + pose per frame, fcnMSV1_t at frame 5 (vidExample.py
 vg / vp / ids / p on real texture with real failures (profiles/r04_gate_census.json: every status gate fires on these frames, none on the
 synthetic scenes).  KLT parity vs cv2 itself stays unpinned (no OpenCV in this pipeline); what this pins is HIP == oracle on real pixels,
 and that the path measures what the reference says these stills show: a car leaving at 40 km/h (vidExample.py:26)."""
-import os
 
 import numpy as np
 import pytest
@@ -18,13 +17,8 @@ from oracle import klt_oracle as KO  # noqa: E402 (checker only)
 from oracle import nls_oracle as NO  # noqa: E402 (checker only)
 from oracle.session_oracle import SessionOracle  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 from _helpers import same_table as _same_table  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def stills():
-    return np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
+from scenes import stills  # noqa: E402, F401 (a fixture)
 
 
 def _run_both(frames, times, q, K, border, msv_frame=5):

@@ -6,13 +6,10 @@ import numpy as np
 import pytest
 
 import lk_ref as R
+from lk_support import bits as _bits
 from oracle import klt_oracle as KO  # noqa: E402
 
 WINDOWS = (3, 8, 15, 16, 21, 51, 63, 64, 65, 107)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("scene", sorted(R.SCENES))

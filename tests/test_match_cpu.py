@@ -11,15 +11,11 @@ import pytest
 import match_ref as MR
 from oracle import driver_oracle as DO
 from oracle import klt_oracle as KO
+from scenes import load_stills as stills
 from velocity_amd import _lib, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 960, 540
-
-
-@functools.lru_cache(maxsize=None)
-def stills():
-    return np.load(os.path.join(ROOT, "tests", "golden", "stills_gray.npz"))
 
 
 @functools.lru_cache(maxsize=None)
