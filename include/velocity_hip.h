@@ -568,6 +568,42 @@ VH_API size_t vh_session_refine_windows_workspace(const vh_session* s, int nwin,
  * the 65535 windows of one launch sequence), misaligned buffers, a workspace below vh_session_refine_windows_workspace(s, nwin, nf). */
 VH_API int vh_session_refine_windows(vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, int max_iter, int with_points, void* recs_dev,
                                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same windows with tracks that live through PART of a window (default OFF; vh_version stays: a consumer tests for the symbol).  A window takes
+ * the ids observed -- isfinite(P[4, id, f]) -- in at least min_obs of its nf frames for which there is a world point to start from; a missing
+ * measurement is "no observation" to the solve: zero residual, zero Jacobian rows.  With i the slot's frame counter, a track g of the window is
+ *   A  observed in all nf frames (and, in a replenished session, triangulated): the rule of vh_session_refine_windows, unchanged; or
+ *   B  observed in >= min_obs frames and its p3[g] is established: row 2 of its history (the pose solve's projection, written only while g is a pose
+ *      track) is finite in some frame 0..i, or the MSV frame has run (0 <= msv_frame <= i) and g was alive in it, or g is anchored; or
+ *   C  (start_reproj > 0 only) neither, observed in >= min_obs frames: its start is triangulated from its first and its last observed frame of the
+ *      window, by the arithmetic of a replenished row's promotion on that one pair (rays by the slot's float32-rays rule, origins
+ *      float32(B[0, 0:3] - B[f, 0:3])), and it is admitted iff that point is finite, lies in front of both cameras and reprojects within start_reproj
+ *      pixels in both frames; otherwise it counts as rejected.
+ * Tracks ascending; starts p3[g], the anchor or the triangulated point, each + B[first, 3:6]; everything else as vh_session_refine_windows.  The rms
+ * residual f is taken over all 2 nt nf entries, the zeros of the missing ones included (as the reference forms it).  With min_obs = nf and
+ * start_reproj = 0 a window is exactly vh_session_refine_windows's.  What this does NOT do: starts from more than two views, robust weights, a sparse
+ * layout (the solve stays dense over nt x nf: a missing measurement costs what an observed one costs), points shared between windows. */
+typedef struct {
+    int min_obs;          /* 2 <= min_obs <= nf */
+    float start_reproj;   /* pixels, finite, >= 0; 0: no triangulated starts */
+} vh_refine_partial_params;
+/* One record per window: vh_refine_window_record (every shared field at the offset vh_session_refine_windows_size gives it), then four int32 counts.
+ * win.bytes is the size of THIS record (16 more than the window record's).  Every byte is defined. */
+typedef struct {
+    vh_refine_window_record win;
+    size_t nobs;    /* int32: observed measurement pairs among the window's nt x nf */
+    size_t npart;   /* int32: tracks among the nt observed in fewer than nf frames    */
+    size_t ntri;    /* int32: tracks admitted through C (their starts were triangulated) */
+    size_t nrej;    /* int32: C candidates that failed the gate (not among the nt)    */
+} vh_refine_partial_record;
+VH_API size_t vh_session_refine_windows_partial_size(const vh_session* s, int nf, int max_iter, int with_points, vh_refine_partial_record* layout_host);
+/* bytes of device scratch a call of nwin windows needs (vh_session_refine_windows_workspace plus the triangulated starts) */
+VH_API size_t vh_session_refine_windows_partial_workspace(const vh_session* s, int nwin, int nf);
+/* Promises and refusals of vh_session_refine_windows (kernels only, no allocation, no host wait, the session is only read, one BA launch sequence for
+ * all windows, every refusal before anything is queued), and: NULL params_host, min_obs < 2, min_obs > nf, start_reproj < 0 or not finite. */
+VH_API int vh_session_refine_windows_partial(vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, int max_iter, int with_points,
+                                             const vh_refine_partial_params* params_host, void* recs_dev, void* workspace, size_t workspace_bytes,
+                                             void* stream);
 VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
 /* (vh_version >= 109) the recovery branch of KLTmain (utils/KLT.py:130-133) inside the session; default OFF: a step then queues exactly the launches it
  * always did and a stream whose coarse stage fails reports klt_flags & 1 and goes on with what the blind fine stage kept.

@@ -100,7 +100,19 @@ def fzK(a, K):
     return world2image(K, np.eye(3), np.zeros(3), a)
 
 
-def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None):
+def _track_filter(P, min_obs, who):
+    """The tracks a window of history P [5, n, nf] takes, and its measurements [2, n, nf].  min_obs None: the reference's filter, alive in every frame
+    (NLS.py:190), rows 0/1 as they are.  min_obs = M: observed -- row 4 finite -- in at least M of the nf frames, and NaN (no observation: zero
+    residual, zero Jacobian rows in the solve) wherever row 4 is NaN."""
+    seen = np.isfinite(P[4])
+    if min_obs is None:
+        return seen.sum(1) == P.shape[2], P[0:2].astype(np.float64)
+    if not 2 <= int(min_obs) <= P.shape[2]:
+        raise ValueError(f"{who}: min_obs = {min_obs} is outside 2 .. nf = {P.shape[2]}")
+    return seen.sum(1) >= int(min_obs), np.where(seen[None], P[0:2].astype(np.float64), np.nan)
+
+
+def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None, min_obs=None):
     """Dense full bundle adjustment over tie points and cameras 1..nc (utils/NLS.py:186-250) -> (cw [nc+1,3], pw [nt,3]).
 
     The track filter, the measurement ordering and the state layout are the reference's (NLS.py:190-203); the
@@ -109,20 +121,25 @@ def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None):
     fixed: None (the reference's solve: its scale is whatever the start had), or a bool mask over the rows of pw: those points are ANCHORED -- they take
     no step (their rows come back as given) while their measurements still constrain the cameras, which pins the scale to them
     (vh_nls_batch_windows_fixed).  The mask is filtered like the tracks.
+
+    min_obs: None (the reference's filter: alive in every frame), or M with 2 <= M <= nf: the tracks observed in at least M frames take part, a missing
+    measurement being no observation (the windows entry takes it; the rms residual still runs over all 2 nt nf entries, as the reference forms it).
     """
     P = np.asarray(P)
     pw = np.asarray(pw, np.float64)
     cw = np.asarray(cw, np.float64)
-    keep = np.isfinite(P[4]).sum(1) == P.shape[2]  # NLS.py:190
+    keep, uv = _track_filter(P, min_obs, "fcnNLS_batch")  # NLS.py:190
     if fixed is not None:
         fixed = _fixed_mask(fixed, len(pw), "fcnNLS_batch")[keep]
-    P, pw = P[:, keep], pw[keep]
-    _, nt, nf = P.shape
+    uv, pw = uv[:, keep], pw[keep]
+    _, nt, nf = uv.shape
     nc = nf - 1
-    z = np.concatenate([P[0].T.reshape(-1), P[1].T.reshape(-1)]).astype(np.float64)  # NLS.py:198-199
+    z = np.concatenate([uv[0].T.reshape(-1), uv[1].T.reshape(-1)])  # NLS.py:198-199
     x0 = np.concatenate((pw, cw[1:], np.zeros((nc, 3)))).reshape(-1)  # NLS.py:202-203
-    if fixed is None:
+    if fixed is None and min_obs is None:
         info, x, tr = _ba_solve("vh_nls_batch", L.host_K(K), z, x0, nt, nc, max_iter)
+    elif fixed is None:  # one window of the windows entry, which takes missing measurements
+        info, x, tr = (a[0] for a in _ba_solve("vh_nls_batch_windows", L.host_K(K), z[None], x0[None], nt, nc, max_iter, 1, (1, L.dptr(None), L.dptr(None))))
     else:  # one window of the windows entry: the same launches, the same record
         fd = L.to_dev(fixed.astype(np.uint8), L.torch_cuda().uint8)
         info, x, tr = (a[0] for a in _ba_solve("vh_nls_batch_windows_fixed", L.host_K(K), z[None], x0[None], nt, nc, max_iter, 1, (1, L.dptr(None), L.dptr(None), L.dptr(fd))))
@@ -146,27 +163,27 @@ def _fixed_mask(fixed, n, who):
     return m
 
 
-def pack_windows(Ps, pws, cws, fixed=None):
+def pack_windows(Ps, pws, cws, fixed=None, min_obs=None):
     """Track filter and packing of fcnNLS_batch (utils/NLS.py:190-203) for several windows of one number of frames, laid out for the largest track
     count nt: z [nw, 2 nt nf] and x0 [nw, 3 nt + 6 nc] in the layout of vh_nls_batch_multi, counts int32[nw].  Rows behind a window's own count
     are padding: NaN measurements (no observation, see k_ba_jac) and the point (0, 0, 1).  Host only.  fixed: None, or one bool mask per window over
     the rows of its pw (None inside the list: no anchors in that window); the result then gains a sixth item, the flags uint8 [nw, nt] of the kept
-    tracks (padding rows 0)."""
+    tracks (padding rows 0).  min_obs: None, or the least number of observed frames of a kept track (see fcnNLS_batch); z is then NaN wherever row 4 is."""
     zs, pts, cams, flags, nf0 = [], [], [], [], None
     if fixed is not None and len(fixed) != len(Ps):
         raise ValueError(f"fcnNLS_batch_windows: {len(fixed)} masks for {len(Ps)} windows")
     for w, (P, pw, cw) in enumerate(zip(Ps, pws, cws)):
         P, pw, cw = np.asarray(P), np.asarray(pw, np.float64), np.asarray(cw, np.float64)
-        keep = np.isfinite(P[4]).sum(1) == P.shape[2]  # NLS.py:190
+        keep, uv = _track_filter(P, min_obs, "fcnNLS_batch_windows")  # NLS.py:190
         if fixed is not None:
             flags.append(np.zeros(int(keep.sum()), bool) if fixed[w] is None else _fixed_mask(fixed[w], len(pw), "fcnNLS_batch_windows")[keep])
-        P, pw = P[:, keep], pw[keep]
+        uv, pw = uv[:, keep], pw[keep]
         nf = P.shape[2]
         if nf0 is None:
             nf0 = nf
         elif nf0 != nf:
             raise ValueError(f"fcnNLS_batch_windows: window shapes differ ({nf0} vs {nf} frames)")
-        zs.append(P[0:2].astype(np.float64))  # [2, nt_w, nf] (NaN = no observation: kept)
+        zs.append(uv)  # [2, nt_w, nf] (NaN = no observation: kept)
         pts.append(pw)
         cams.append(np.concatenate((cw[1:], np.zeros((nf - 1, 3)))).reshape(-1))  # NLS.py:202-203
     nf, nw = nf0, len(zs)
@@ -186,20 +203,21 @@ def pack_windows(Ps, pws, cws, fixed=None):
     return z.reshape(nw, -1), x0, counts, nt, nc, fx
 
 
-def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=None):
+def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=None, min_obs=None):
     """fcnNLS_batch (utils/NLS.py:186-250) for several independent windows of the same number of frames (one finished clip or sliding window per
     video stream) in one launch sequence (grid.y = window).  Ps / pws / cws: sequences of the reference's P, pw, cw arguments.  K: one 3x3 matrix
     for all windows, or one per window ([nw, 3, 3]).  The windows may keep different numbers of full-length tracks: pack_windows lays them out for
     the largest count and pads with unobserved points, which take no part in the solve (vh_nls_batch_windows); windows of equal counts and one K
     go through vh_nls_batch_multi unchanged.  A window without a full-length track is not solved (cw comes back as given).  Returns
     [(cw, pw), ...], pw cut to the window's own tracks (with return_info: also the padded x and the trace).  fixed: None, or a list of bool masks, one per
-    window over the rows of its pw (see fcnNLS_batch; None inside the list: that window is solved free)."""
+    window over the rows of its pw (see fcnNLS_batch; None inside the list: that window is solved free).  min_obs: None, or the least number of
+    observed frames of a kept track (see fcnNLS_batch); such windows go through vh_nls_batch_windows(_fixed)."""
     torch = L.torch_cuda()
     fx = None
     if fixed is None:
-        z, x0, counts, nt, nc = pack_windows(Ps, pws, cws)
+        z, x0, counts, nt, nc = pack_windows(Ps, pws, cws, min_obs=min_obs)
     else:
-        z, x0, counts, nt, nc, fx = pack_windows(Ps, pws, cws, fixed)
+        z, x0, counts, nt, nc, fx = pack_windows(Ps, pws, cws, fixed, min_obs=min_obs)
     nw = len(counts)
     K64 = np.asarray(K, np.float64)
     per_window_K = K64.ndim == 3
@@ -210,7 +228,7 @@ def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=
         ntd, fd = L.to_dev(counts, torch.int32), L.to_dev(fx, torch.uint8)
         Kd = L.to_dev(K64.reshape(nw, 9), torch.float64) if per_window_K else None
         info, x, tr = _ba_solve("vh_nls_batch_windows_fixed", K_host, z, x0, nt, nc, max_iter, nw, (nw, L.dptr(ntd), L.dptr(Kd), L.dptr(fd)))
-    elif per_window_K or (counts != nt).any():
+    elif per_window_K or (counts != nt).any() or min_obs is not None:
         ntd = L.to_dev(counts, torch.int32)
         Kd = L.to_dev(K64.reshape(nw, 9), torch.float64) if per_window_K else None
         info, x, tr = _ba_solve("vh_nls_batch_windows", K_host, z, x0, nt, nc, max_iter, nw, (nw, L.dptr(ntd), L.dptr(Kd)))

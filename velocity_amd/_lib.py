@@ -61,6 +61,22 @@ class RefineWindowRecord(C.Structure):
                                           "f_last", "trace", "ids", "pw", "nfix")] + [("n0", C.c_int), ("nf", C.c_int), ("max_iter", C.c_int), ("with_points", C.c_int)]
 
 
+class RefinePartialParams(C.Structure):
+    """vh_refine_partial_params: the least number of observed frames of a window's track, the gate of a triangulated start (pixels; 0: none)."""
+
+    _fields_ = [("min_obs", C.c_int), ("start_reproj", C.c_float)]
+
+
+class RefinePartialRecord(C.Structure):
+    """vh_refine_partial_record: the window record's offsets (win; win.bytes is this record's size), then those of the four int32 counts."""
+
+    _fields_ = [("win", RefineWindowRecord)] + [(k, C.c_size_t) for k in ("nobs", "npart", "ntri", "nrej")]
+
+    @property
+    def bytes(self):
+        return self.win.bytes
+
+
 class MatchParams(C.Structure):
     """vh_match_params (defaults: MATCH_DEFAULTS)."""
 
@@ -148,6 +164,10 @@ _SIGS = {
     "vh_session_refine_windows_size": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(RefineWindowRecord)]),
     "vh_session_refine_windows_workspace": (C.c_size_t, [vp, C.c_int, C.c_int]),
     "vh_session_refine_windows": (C.c_int, [vp, C.POINTER(RefineWindow), C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),
+    "vh_session_refine_windows_partial_size": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(RefinePartialRecord)]),
+    "vh_session_refine_windows_partial_workspace": (C.c_size_t, [vp, C.c_int, C.c_int]),
+    "vh_session_refine_windows_partial": (C.c_int, [vp, C.POINTER(RefineWindow), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RefinePartialParams), vp, vp,
+                                                    C.c_size_t, vp]),
     "vh_session_set_anchors": (C.c_int, [vp, C.c_int, i32p, C.c_int, f64p, vp]),
     "vh_session_anchors": (C.c_int, [vp, C.c_int, i32p, f64p]),
     "vh_session_ptrs": (C.c_int, [vp, C.c_int, C.POINTER(SessionView)]),

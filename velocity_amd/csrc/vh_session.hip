@@ -339,6 +339,32 @@ __global__ __launch_bounds__(256) void k_replenish_init(SessStream* ss, SessRepl
     if (threadIdx.x == 0) { R.n_rows = n; R.n_new = 0; R.due = 0; R.cnt[0] = R.cnt[1] = R.cnt[2] = 0; }
 }
 
+// THE triangulation of one track from nf of its own observations, and its gate (one copy: a newborn row's promotion over its baseline, the start of an
+// untrusted track of a partial refinement window over one frame pair).  A, T: [nf][3] ray origins and translations of the frames; pix(j, row): the
+// track's float32 pixel of frame j; rays by the slot's float32-rays rule, the point c by fcn2vintercept.  True iff c is finite, lies in front of every
+// camera and reprojects within max_reproj pixels in each frame.
+template <class Pix>
+__device__ __forceinline__ bool sess_triangulate(const double* A, const double* T, int nf, const double* K, int f32, Pix pix, double max_reproj, double* c)
+{
+    two_view_rays(A, nf, [&](int j, double* u) {
+        if (f32) uvec_f32(pix(j, 0), pix(j, 1), (float)K[6], (float)K[7], (float)K[0], u);
+        else uvec_f64((double)pix(j, 0), (double)pix(j, 1), K[6], K[7], K[0], u);
+    }, c);
+    bool ok = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]);
+    double worst = 0.0;
+    for (int j = 0; j < nf && ok; j++) {
+        const double b0 = c[0] + T[3 * j], b1 = c[1] + T[3 * j + 1], b2 = c[2] + T[3 * j + 2];
+        ok = b2 > 0.0;
+        double u, v;
+        project_cam(K, b0, b1, b2, u, v);
+        const double du = u - (double)pix(j, 0), dv = v - (double)pix(j, 1);
+        const double e = sqrt(du * du + dv * dv);
+        ok = ok && isfinite(e);
+        worst = fmax(worst, e);
+    }
+    return ok && worst < max_reproj;
+}
+
 // Promotion: one thread per candidate row.  Rays as fcnMSV1_t builds them, origins float32(B[0, 0:3] - B[born + j, 0:3]) widened (MSV.py:18), the point
 // by fcn2vintercept; the gate: finite, in front of every camera of the baseline, reprojected within max_reproj pixels in each of its frames.
 __global__ __launch_bounds__(256) void k_replenish_promote(SessStream* ss_all, SessRepl* rp_all, const uint8_t* const* frames, int msv_frame, int every,
@@ -364,23 +390,7 @@ __global__ __launch_bounds__(256) void k_replenish_promote(SessStream* ss_all, S
         if (!S.vg[g] || R.tri[g] || R.born[g] != born) continue;
         auto pix = [&](int j, int row) { return S.P[sess_P(row, g, born + j, N0)]; };
         double c[3];
-        two_view_rays(s_A, nf, [&](int j, double* u) {
-            if (f32) uvec_f32(pix(j, 0), pix(j, 1), (float)K[6], (float)K[7], (float)K[0], u);
-            else uvec_f64((double)pix(j, 0), (double)pix(j, 1), K[6], K[7], K[0], u);
-        }, c);
-        bool ok = isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]);
-        double worst = 0.0;
-        for (int j = 0; j < nf && ok; j++) {
-            const double b0 = c[0] + s_T[3 * j], b1 = c[1] + s_T[3 * j + 1], b2 = c[2] + s_T[3 * j + 2];
-            ok = b2 > 0.0;
-            double u, v;
-            project_cam(K, b0, b1, b2, u, v);
-            const double du = u - (double)pix(j, 0), dv = v - (double)pix(j, 1);
-            const double e = sqrt(du * du + dv * dv);
-            ok = ok && isfinite(e);
-            worst = fmax(worst, e);
-        }
-        if (ok && worst < max_reproj) {
+        if (sess_triangulate(s_A, s_T, nf, K, f32, pix, max_reproj, c)) {
             S.p3[3 * g] = c[0]; S.p3[3 * g + 1] = c[1]; S.p3[3 * g + 2] = c[2];
             R.tri[g] = 1;
             S.vp[g] = 1;
@@ -1171,6 +1181,12 @@ struct RefWs {  // the scratch of one call, carved by refine_ws_layout
     char* ba;    // [nwin] BA workspaces, ba_stride bytes apart
     uint8_t* fixed;  // [nwin][N0] anchored rows of each window (read by the solve only when a slot of the request has anchors)
     size_t z_stride, x_stride, ba_stride;
+    uint8_t* tri_mask;  // [nwin][N0] partial windows only (else null): id g of the window starts at the point triangulated for it, tri_xyz
+    double* tri_xyz;    // [nwin][N0][3] in the session's coordinates (rows of other ids: undefined)
+};
+struct RefPart {  // vh_refine_partial_params as the kernel sees them
+    int min_obs, msv_frame;
+    double start_reproj;
 };
 // a record of either public layout as the kernels see it: byte offsets taken from vh_refine_record or vh_refine_window_record (refine_view)
 struct RefView {
@@ -1180,8 +1196,8 @@ struct RefView {
     int max_iter;
     int with_points;  // ids and pw are in the record
 };
-// (table + workspace + view + the other arguments of the pack kernel: 2304 bytes of the 4 KB a launch may carry)
-static_assert(sizeof(RefReq) + sizeof(RefWs) + sizeof(RefView) + 6 * sizeof(void*) == 2312, "the refinement request travels in the kernel arguments");
+// (table + workspace + view + the other arguments of the pack kernels, the partial one's parameters included: 2344 bytes of the 4 KB a launch may carry)
+static_assert(sizeof(RefReq) + sizeof(RefWs) + sizeof(RefView) + 6 * sizeof(void*) + sizeof(RefPart) == 2344, "the refinement request travels in the kernel arguments");
 
 static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_record* L)
 {
@@ -1216,7 +1232,15 @@ static void refine_window_record_layout(int N0, int nf, int max_iter, int with_p
     L->n0 = N0; L->nf = nf; L->max_iter = max_iter; L->with_points = with_points ? 1 : 0;
 }
 
-// the kernels' view of a public layout (the two functions above stay the one source of every offset): head = the record's first header word
+// a partial window's record: the window record, then the four counts (the shared fields keep the window record's offsets)
+static void refine_partial_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_partial_record* L)
+{
+    refine_window_record_layout(N0, nf, max_iter, with_points, &L->win);
+    L->nobs = L->win.bytes; L->npart = L->nobs + 4; L->ntri = L->nobs + 8; L->nrej = L->nobs + 12;
+    L->win.bytes += 4 * sizeof(int);
+}
+
+// the kernels' view of a public layout (the functions above stay the one source of every offset): head = the record's first header word
 template <class Layout>
 static RefView refine_view(const Layout& L, size_t head, int rows, int with_points)
 {
@@ -1227,7 +1251,7 @@ static RefView refine_view(const Layout& L, size_t head, int rows, int with_poin
     return V;
 }
 
-static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* base, RefWs* W, bool with_ids = false)
+static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* base, RefWs* W, bool with_ids = false, bool partial = false)
 {
     const size_t N0 = s->N0, nc = nf - 1, nw = nslots;
     VhCarver A(base);
@@ -1240,6 +1264,8 @@ static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* ba
     W->ids = with_ids ? A.take<int>(nw * N0) : nullptr;
     W->ba = A.take<char>(nw * W->ba_stride);
     W->fixed = A.take<uint8_t>(nw * N0);  // (behind everything else: no other offset moves)
+    W->tri_mask = partial ? A.take<uint8_t>(nw * N0) : nullptr;
+    W->tri_xyz = partial ? A.take<double>(3 * nw * N0) : nullptr;
     return A.bytes();
 }
 
@@ -1250,8 +1276,9 @@ static size_t refine_ws_layout(const vh_session* s, int nslots, int nf, char* ba
 // Anchors (am, ax: the slot's mask and coordinates over its N0 ids, null = none; fx: the window's row flags for the solve): a kept track that is anchored
 // starts at its anchor's coordinates in place of p3, still + B[first, 3:6], and its row is flagged; padding rows never are.  Returns the anchors among the
 // window's tracks (every thread of the workgroup calls this, every thread gets the count).
+// Triangulated starts (tm, tx: the window's mask and coordinates over the N0 ids, null = none): a kept track with tm set starts at tx in place of p3.
 __device__ __forceinline__ int refine_pack_window(const SessStream& S, const int* ids, int n, int first, int nf, double* z, double* x, double* Kw, int tid,
-                                                  const uint8_t* am, const double* ax, uint8_t* fx)
+                                                  const uint8_t* am, const double* ax, uint8_t* fx, const uint8_t* tm = nullptr, const double* tx = nullptr)
 {
     const int N0 = S.N0, nc = nf - 1;
     const double nanv = __longlong_as_double(0x7ff8000000000000LL);
@@ -1270,7 +1297,8 @@ __device__ __forceinline__ int refine_pack_window(const SessStream& S, const int
         if (k < n) {
             const int id = ids[k];
             const bool anchored = am && am[id];
-            x[e] = (anchored ? ax[3 * (size_t)id + c] : S.p3[3 * (size_t)id + c]) + (double)B0[c];
+            const double* from = anchored ? ax : (tm && tm[id] ? tx : S.p3);
+            x[e] = from[3 * (size_t)id + c] + (double)B0[c];
             if (am && c == 0) fx[k] = anchored ? 1 : 0;
         } else {
             x[e] = c == 2 ? 1.0 : 0.0;
@@ -1351,6 +1379,42 @@ __device__ __forceinline__ void refine_unpack_window(const SessStream& S, const 
     }
 }
 
+// One 256-id block of a selection: the kept ids of the block go behind the *s_base ids kept so far, ascending -- a ballot + the four wavefronts' counts
+// give each its place.  Every thread of the workgroup calls this, once per block (barriers inside).
+__device__ __forceinline__ void refine_keep(bool keep, int g, int* sel, int* s_cnt, int* s_base, int tid)
+{
+    const int lane = tid & 63, wave = tid >> 6;
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) s_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int at = *s_base;
+    for (int k = 0; k < wave; k++) at += s_cnt[k];
+    if (keep) sel[at + __popcll(bal & ((1ull << lane) - 1ull))] = g;
+    __syncthreads();
+    if (tid == 0) *s_base += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    __syncthreads();
+}
+
+// What every pack kernel does once it knows the window's n tracks: refine_pack_window, the count for the solve, and the part of the record the solve
+// writes into (info, trace rows up to the iterations it takes) and the header -- {slot, first} where the record has them, then {nt, iterations,
+// converged} = 0 and nfix, its last word: defined from the start
+__device__ __forceinline__ void refine_pack_rest(const SessStream& S, const int* ids, int n, int slot, int first, int w, int nf, const RefWs& W,
+                                                 const RefView& V, char* recs, const uint8_t* anc_mask, const double* anc_xyz, int tid,
+                                                 const uint8_t* tm = nullptr, const double* tx = nullptr)
+{
+    const int N0 = S.N0;
+    const int nfix = refine_pack_window(S, ids, n, first, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid,
+                                        anc_mask ? anc_mask + (size_t)slot * N0 : nullptr, anc_mask ? anc_xyz + 3 * (size_t)slot * N0 : nullptr,
+                                        W.fixed + (size_t)w * N0, tm, tx);
+    if (tid == 0) W.nt[w] = n;
+    char* rec = recs + (size_t)w * V.bytes;
+    const int lead = V.head_words - 4;
+    if (tid < V.head_words)
+        reinterpret_cast<int*>(rec + V.head)[tid] = tid < lead ? (tid == lead - 2 ? slot : first) : (tid == V.head_words - 1 ? nfix : 0);
+    double* trace = reinterpret_cast<double*>(rec + V.trace);
+    for (int e = tid; e < 2 * V.max_iter; e += 256) trace[e] = 0.0;
+}
+
 // anc_mask / anc_xyz: the session's anchor tables over all slots, null when no slot of the request has anchors
 // pack.  SELECT: the window's tracks are the ids whose history row 4 is finite in EVERY frame of the window (NLS.py:190 on the slice) -- not the slot's
 // current survivors: a track that died after the window belongs to it.  256 ids at a time read row 4 of the frame-major history (coalesced over
@@ -1369,7 +1433,6 @@ __global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, R
     const int* ids = S.ids;
     int n = min(max(S.n_cur, 0), N0);
     if (SELECT) {
-        const int lane = tid & 63, wave = tid >> 6;
         int* sel = W.ids + (size_t)w * N0;
         __shared__ int s_cnt[4], s_base;
         if (tid == 0) s_base = 0;
@@ -1378,30 +1441,83 @@ __global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, R
             const int g = g0 + tid;
             bool alive = g < N0 && (!rp_all || rp_all[slot].tri[g]);  // (replenished session: a row not yet triangulated has no world point)
             for (int f = 0; alive && f < nf; f++) alive = isfinite(S.P[sess_P(4, g, first + f, N0)]);
-            const unsigned long long bal = __ballot(alive);
-            if (lane == 0) s_cnt[wave] = __popcll(bal);
-            __syncthreads();
-            int at = s_base;
-            for (int k = 0; k < wave; k++) at += s_cnt[k];
-            if (alive) sel[at + __popcll(bal & ((1ull << lane) - 1ull))] = g;
-            __syncthreads();
-            if (tid == 0) s_base += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            __syncthreads();
+            refine_keep(alive, g, sel, s_cnt, &s_base, tid);
         }
         ids = sel; n = s_base;  // (the ids written above are visible to the whole workgroup: barriers since)
     }
-    const int nfix = refine_pack_window(S, ids, n, first, nf, W.z + (size_t)w * W.z_stride, W.x + (size_t)w * W.x_stride, W.K + 9 * (size_t)w, tid,
-                                        anc_mask ? anc_mask + (size_t)slot * N0 : nullptr, anc_mask ? anc_xyz + 3 * (size_t)slot * N0 : nullptr,
-                                        W.fixed + (size_t)w * N0);
-    if (tid == 0) W.nt[w] = n;
-    // the part of the record the solve writes into (info, trace rows up to the iterations it takes) and the header -- {slot, first} where the record
-    // has them, then {nt, iterations, converged} = 0 and nfix, its last word: defined from the start
-    char* rec = recs + (size_t)w * V.bytes;
-    const int lead = V.head_words - 4;
-    if (tid < V.head_words)
-        reinterpret_cast<int*>(rec + V.head)[tid] = tid < lead ? (tid == lead - 2 ? slot : first) : (tid == V.head_words - 1 ? nfix : 0);
-    double* trace = reinterpret_cast<double*>(rec + V.trace);
-    for (int e = tid; e < 2 * V.max_iter; e += 256) trace[e] = 0.0;
+    refine_pack_rest(S, ids, n, slot, first, w, nf, W, V, recs, anc_mask, anc_xyz, tid);
+}
+
+// pack, the third selection form (vh_session_refine_windows_partial): the window's tracks are the ids observed in at least min_obs of its nf frames that
+// have a usable world point, ascending.  Per 256-id block one thread per id: row 4 of the window frame by frame (coalesced over tracks) gives obs and the
+// first and last observed frame; then, between two ballots and with no barrier inside,
+//   A  obs == nf (and tri in a replenished session): today's rule;
+//   B  the session has established p3[g]: g is anchored, or alive at the MSV frame once that has run, or row 2 of its history (the pose solve's
+//      projection, written only while g is a pose track) is finite in some frame up to the slot's counter;
+//   C  (start_reproj > 0) neither: the start is triangulated from the first and the last observed frame of the window by sess_triangulate, origins
+//      float32(B[0, 0:3] - B[f, 0:3]) widened (MSV.py:18), and the track is admitted iff it passes that gate; the point goes to W.tri_xyz.
+// The four counts go straight into the record (V.bytes - 16 on: vh_refine_partial_record).
+__global__ __launch_bounds__(256) void k_refine_pack_partial(const SessStream* ss_all, RefReq rq, int w0, int nf, RefWs W, RefView V, char* recs,
+                                                             const uint8_t* anc_mask, const double* anc_xyz, const SessRepl* rp_all, RefPart Q)
+{
+    const int w = w0 + blockIdx.x, tid = threadIdx.x;
+    const int slot = rq.slot[blockIdx.x], first = rq.first[blockIdx.x];
+    const SessStream& S = ss_all[slot];
+    const int N0 = S.N0, last = min(S.frame_i, S.nhist - 1);
+    const uint8_t* am = anc_mask ? anc_mask + (size_t)slot * N0 : nullptr;
+    const bool msv_ran = Q.msv_frame >= 0 && Q.msv_frame <= last;
+    int* sel = W.ids + (size_t)w * N0;
+    uint8_t* tm = W.tri_mask + (size_t)w * N0;
+    double* tx = W.tri_xyz + 3 * (size_t)w * N0;
+    __shared__ int s_cnt[4], s_base, s_tot[4];
+    if (tid == 0) s_base = 0;
+    if (tid < 4) s_tot[tid] = 0;
+    __syncthreads();
+    int nobs = 0, npart = 0, ntri = 0, nrej = 0;
+    for (int g0 = 0; g0 < N0; g0 += 256) {  // (uniform trip count: every lane of every wavefront reaches the ballot and the barriers)
+        const int g = g0 + tid;
+        int obs = 0, fa = 0, fb = 0;
+        if (g < N0)
+            for (int f = 0; f < nf; f++)
+                if (isfinite(S.P[sess_P(4, g, first + f, N0)])) {
+                    if (!obs) fa = f;
+                    fb = f;
+                    obs++;
+                }
+        bool keep = false, tri = false;
+        if (g < N0 && obs >= Q.min_obs) {
+            keep = obs == nf && (!rp_all || rp_all[slot].tri[g]);
+            if (!keep) {
+                bool trusted = (am && am[g]) || (msv_ran && isfinite(S.P[sess_P(4, g, Q.msv_frame, N0)]));
+                for (int f = 0; !trusted && f <= last; f++) trusted = isfinite(S.P[sess_P(2, g, f, N0)]);
+                keep = trusted;
+                if (!trusted && Q.start_reproj > 0.0) {
+                    double A[6], T[6], K[9], c[3];
+                    for (int j = 0; j < 2; j++)
+                        for (int k = 0; k < 3; k++) {
+                            const float* Bf = S.B + 14 * (size_t)(first + (j ? fb : fa));
+                            A[3 * j + k] = (double)__fsub_rn(S.B[k], Bf[k]);
+                            T[3 * j + k] = (double)Bf[3 + k];
+                        }
+                    for (int k = 0; k < 9; k++) K[k] = S.K[k];
+                    keep = tri = sess_triangulate(A, T, 2, K, S.msv.f32_rays, [&](int j, int row) { return S.P[sess_P(row, g, first + (j ? fb : fa), N0)]; },
+                                                  Q.start_reproj, c);
+                    if (tri) for (int k = 0; k < 3; k++) tx[3 * (size_t)g + k] = c[k];
+                    else nrej++;
+                }
+            }
+        }
+        if (g < N0) tm[g] = tri ? 1 : 0;
+        if (keep) { nobs += obs; npart += obs < nf ? 1 : 0; ntri += tri ? 1 : 0; }
+        refine_keep(keep, g, sel, s_cnt, &s_base, tid);
+    }
+    if (nobs) atomicAdd(&s_tot[0], nobs);
+    if (npart) atomicAdd(&s_tot[1], npart);
+    if (ntri) atomicAdd(&s_tot[2], ntri);
+    if (nrej) atomicAdd(&s_tot[3], nrej);
+    __syncthreads();  // (also: the ids, tm and tx written above are visible to the whole workgroup)
+    if (tid < 4) reinterpret_cast<int*>(recs + (size_t)w * V.bytes + V.bytes - 16)[tid] = s_tot[tid];
+    refine_pack_rest(S, sel, s_base, slot, first, w, nf, W, V, recs, anc_mask, anc_xyz, tid, tm, tx);
 }
 
 // unpack: W.ids is null when the windows are whole clips (the slot's survivors, as packed)
@@ -1436,13 +1552,18 @@ static const RefEntry REF_WINDOWS = {"vh_session_refine_windows", true,
                                      "vh_session_refine_windows: bad arguments (a null session, window table, record buffer or workspace)",
                                      "vh_session_refine_windows: misaligned buffers (records 8-byte, workspace 256-byte aligned)", "a window", " per window",
                                      "windows"};
+static const RefEntry REF_PARTIAL = {"vh_session_refine_windows_partial", true,
+                                     "vh_session_refine_windows_partial: bad arguments (a null session, window table, parameters, record buffer or workspace)",
+                                     "vh_session_refine_windows_partial: misaligned buffers (records 8-byte, workspace 256-byte aligned)", "a window",
+                                     " per window", "windows"};
 
 // THE refinement request: n windows of nf frames -> n records at recs_dev.  The checks both entries share, worded as E's; own(fail, req): the entry's
 // own checks of its table, which leaves the windows in req (or returns what fail returned); then the workspace, pack, ONE vh_ba_windows launch
-// sequence, unpack.  Every refusal returns before anything is queued.
+// sequence, unpack.  Every refusal returns before anything is queued.  part (vh_session_refine_windows_partial, else null): the third selection form
+// and its record.
 template <class Own>
 static int refine_request(const RefEntry& E, vh_session* s, const void* table, int n, int nf, int max_iter, int with_points, void* recs_dev, void* workspace,
-                          size_t workspace_bytes, void* stream, Own own)
+                          size_t workspace_bytes, void* stream, Own own, const vh_refine_partial_params* part = nullptr)
 {
     char msg[240];
     auto fail = [&](const char* fmt, auto... a) {
@@ -1462,10 +1583,14 @@ static int refine_request(const RefEntry& E, vh_session* s, const void* table, i
     if (int r = own(fail, req)) return r;
     RefWs W;
     const bool select = E.windows || s->rp.on;  // (replenished session: survivors need not have been alive at frame 0)
-    const size_t need = refine_ws_layout(s, n, nf, reinterpret_cast<char*>(workspace), &W, select);
+    const size_t need = refine_ws_layout(s, n, nf, reinterpret_cast<char*>(workspace), &W, select, part != nullptr);
     if (workspace_bytes < need) return fail("workspace of %zu bytes, %d %s of %d frames need %zu", workspace_bytes, n, E.noun, nf, need);
     RefView V;
-    if (E.windows) {
+    if (part) {
+        vh_refine_partial_record L;
+        refine_partial_record_layout(s->N0, nf, max_iter, with_points, &L);
+        V = refine_view(L.win, L.win.slot, nf, L.win.with_points);
+    } else if (E.windows) {
         vh_refine_window_record L;
         refine_window_record_layout(s->N0, nf, max_iter, with_points, &L);
         V = refine_view(L, L.slot, nf, L.with_points);
@@ -1493,7 +1618,8 @@ static int refine_request(const RefEntry& E, vh_session* s, const void* table, i
         const uint8_t* mask = anchored ? s->d_anc_mask : nullptr;
         const double* xyz = anchored ? s->d_anc_xyz : nullptr;
         const SessRepl* rp = s->rp.on ? s->rp.d_rp : nullptr;
-        if (select) each_chunk(k_refine_pack<true>, bound_.s, mask, xyz, rp);
+        if (part) each_chunk(k_refine_pack_partial, bound_.s, mask, xyz, rp, RefPart{part->min_obs, s->msv_frame, (double)part->start_reproj});
+        else if (select) each_chunk(k_refine_pack<true>, bound_.s, mask, xyz, rp);
         else each_chunk(k_refine_pack<false>, bound_.s, mask, xyz, rp);
         SESS_CHECK();
     }
@@ -1557,25 +1683,63 @@ extern "C" VH_API size_t vh_session_refine_windows_workspace(const vh_session* s
     return refine_ws_layout(s, nwin, nf, nullptr, &W, true);
 }
 
+// the checks of a window table (both window entries)
+template <class Fail>
+static int refine_check_windows(const vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, Fail fail, std::vector<vh_refine_window>& req)
+{
+    std::vector<std::vector<int>> seen(s->batch);  // per slot: the window starts given so far
+    for (int k = 0; k < nwin; k++) {
+        const int b = wins_host[k].slot, first = wins_host[k].first;
+        if (b < 0 || b >= s->batch) return fail("window %d: slot %d is outside the session's %d slots", k, b, s->batch);
+        if (first < 0) return fail("window %d (slot %d): first = %d is negative", k, b, first);
+        const int last_have = s->h_frame[b] < s->nhist - 1 ? s->h_frame[b] : s->nhist - 1;  // (the history holds nhist frames)
+        if (first > last_have || nf - 1 > last_have - first)
+            return fail("window %d (slot %d, first %d) ends at frame %lld, the slot is at frame %d", k, b, first, (long long)first + nf - 1, last_have);
+        for (int f : seen[b])
+            if (f == first) return fail("window (slot %d, first %d) is given twice", b, first);
+        seen[b].push_back(first);
+    }
+    req.assign(wins_host, wins_host + nwin);
+    return 0;
+}
+
 extern "C" VH_API int vh_session_refine_windows(vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, int max_iter, int with_points,
                                                 void* recs_dev, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return refine_request(REF_WINDOWS, s, wins_host, nwin, nf, max_iter, with_points, recs_dev, workspace, workspace_bytes, stream, [&](auto fail, auto& req) {
-        std::vector<std::vector<int>> seen(s->batch);  // per slot: the window starts given so far
-        for (int k = 0; k < nwin; k++) {
-            const int b = wins_host[k].slot, first = wins_host[k].first;
-            if (b < 0 || b >= s->batch) return fail("window %d: slot %d is outside the session's %d slots", k, b, s->batch);
-            if (first < 0) return fail("window %d (slot %d): first = %d is negative", k, b, first);
-            const int last_have = s->h_frame[b] < s->nhist - 1 ? s->h_frame[b] : s->nhist - 1;  // (the history holds nhist frames)
-            if (first > last_have || nf - 1 > last_have - first)
-                return fail("window %d (slot %d, first %d) ends at frame %lld, the slot is at frame %d", k, b, first, (long long)first + nf - 1, last_have);
-            for (int f : seen[b])
-                if (f == first) return fail("window (slot %d, first %d) is given twice", b, first);
-            seen[b].push_back(first);
-        }
-        req.assign(wins_host, wins_host + nwin);
-        return 0;
-    });
+    return refine_request(REF_WINDOWS, s, wins_host, nwin, nf, max_iter, with_points, recs_dev, workspace, workspace_bytes, stream,
+                          [&](auto fail, auto& req) { return refine_check_windows(s, wins_host, nwin, nf, fail, req); });
+}
+
+extern "C" VH_API size_t vh_session_refine_windows_partial_size(const vh_session* s, int nf, int max_iter, int with_points, vh_refine_partial_record* layout_host)
+{
+    if (!s || nf < 2 || max_iter < 1) { vh_fail(-1, "vh_session_refine_windows_partial_size: bad arguments"); return 0; }
+    vh_refine_partial_record L;
+    refine_partial_record_layout(s->N0, nf, max_iter, with_points, &L);
+    if (layout_host) *layout_host = L;
+    return L.win.bytes;
+}
+
+extern "C" VH_API size_t vh_session_refine_windows_partial_workspace(const vh_session* s, int nwin, int nf)
+{
+    if (!s || nwin < 1 || nf < 2 || nf - 1 > 255) { vh_fail(-1, "vh_session_refine_windows_partial_workspace: bad arguments"); return 0; }
+    RefWs W;
+    return refine_ws_layout(s, nwin, nf, nullptr, &W, true, true);
+}
+
+extern "C" VH_API int vh_session_refine_windows_partial(vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, int max_iter, int with_points,
+                                                        const vh_refine_partial_params* params_host, void* recs_dev, void* workspace,
+                                                        size_t workspace_bytes, void* stream)
+{
+    if (!params_host) return vh_fail(-1, REF_PARTIAL.bad_args);
+    const vh_refine_partial_params P = *params_host;
+    return refine_request(REF_PARTIAL, s, wins_host, nwin, nf, max_iter, with_points, recs_dev, workspace, workspace_bytes, stream,
+                          [&](auto fail, auto& req) {
+                              if (P.min_obs < 2) return fail("min_obs = %d: a track needs at least 2 observations in a window of %d frames", P.min_obs, nf);
+                              if (P.min_obs > nf) return fail("min_obs = %d exceeds the window's nf = %d frames", P.min_obs, nf);
+                              if (!(P.start_reproj >= 0.f) || !std::isfinite(P.start_reproj))
+                                  return fail("start_reproj = %g: the gate of a triangulated start is a finite number of pixels >= 0 (0 = no such starts)", (double)P.start_reproj);
+                              return refine_check_windows(s, wins_host, nwin, nf, fail, req);
+                          }, &P);
 }
 
 // packed track state of every stream for the cross-GPU exchange (K20): per stream a record of 8 + 3*N0 float32 words

@@ -397,18 +397,19 @@ class TrackerSession:
                                                self._refine_ws.numel(), L.stream_ptr()), "vh_session_refine")
 
         return self._refine_request(call, slots, self.refine_layout(max_iter), nf, out, len(slots), need)
-    def refine_window_layout(self, nf, max_iter=10, with_points=False):
-        """vh_refine_window_record of this session for windows of nf frames: byte offsets of the fields of a refined window's record (and `bytes`)."""
+    def refine_window_layout(self, nf, max_iter=10, with_points=False, partial=False):
+        """vh_refine_window_record of this session for windows of nf frames: byte offsets of the fields of a refined window's record (and `bytes`).
+        partial: vh_refine_partial_record, the record of a refine_windows(min_obs=...) request (.win: the window record's offsets; then the counts')."""
         lays = self.__dict__.setdefault("_refine_window_layouts", {})
-        key = (int(nf), int(max_iter), bool(with_points))
+        key = (int(nf), int(max_iter), bool(with_points)) + ((True,) if partial else ())
         if key not in lays:
-            lay = L.RefineWindowRecord()
-            if not self.lib.vh_session_refine_windows_size(self.handle, key[0], key[1], int(key[2]), C.byref(lay)):
-                L.check(-1, "vh_session_refine_windows_size")
+            lay, fn = (L.RefinePartialRecord(), "vh_session_refine_windows_partial_size") if partial else (L.RefineWindowRecord(), "vh_session_refine_windows_size")
+            if not getattr(self.lib, fn)(self.handle, key[0], key[1], int(key[2]), C.byref(lay)):
+                L.check(-1, fn)
             lays[key] = lay
         return lays[key]
 
-    def refine_windows(self, windows, nf, max_iter=10, with_points=False, out=None, workspace_budget=None):
+    def refine_windows(self, windows, nf, max_iter=10, with_points=False, out=None, workspace_budget=None, min_obs=None, start_reproj=0.0):
         """Bundle adjustment of frame windows of the slots' clips without leaving the device (vh_session_refine_windows): `windows` = [(slot, first), ...],
         each the frames [first, first + nf) of its slot's clip -- fcnNLS_batch(K, P[:, :, first:first+nf], ...) in the coordinates of the window's first
         camera, on the tracks alive through the window.  A slot may appear in many windows and need not be finished (first + nf - 1 <= its frame
@@ -417,16 +418,24 @@ class TrackerSession:
         REFINE_WINDOWS_BUDGET; always at least one window).  The scratch and the device records belong to the session and are reused.
         out: None (a new pinned buffer), ONE pinned uint8 tensor for all the records, or a list of (pinned uint8 tensor, count): consecutive records,
         `count` of them into each tensor.  with_points: the records also carry ids and pw (in the window's coordinates).
+        min_obs (default None: the call above, unchanged): 2 <= min_obs <= nf -- a window also takes the tracks observed in at least min_obs of its
+        frames that have a world point to start from (vh_session_refine_windows_partial: established by the session or anchored; with start_reproj > 0
+        also those whose start, triangulated from their first and last observed frame of the window, reprojects within start_reproj pixels).  A missing
+        measurement is no observation to the solve.  The dicts then carry nobs, npart, ntri, nrej as well.
         Returns a handle like refine()'s: .done() polls, .result() waits and returns one dict per window (unpack_refine_window), in the order given."""
         wins = [(int(b), int(f)) for b, f in windows]
         if not wins:
             raise ValueError("refine_windows: no window given")
         nf, max_iter = int(nf), int(max_iter)
-        lay = self.refine_window_layout(nf, max_iter, with_points)
+        partial = min_obs is not None
+        if not partial and start_reproj:
+            raise ValueError("refine_windows: start_reproj needs min_obs")
+        ws_fn = "vh_session_refine_windows_partial_workspace" if partial else "vh_session_refine_windows_workspace"
+        lay = self.refine_window_layout(nf, max_iter, with_points, partial)
         budget = REFINE_WINDOWS_BUDGET if workspace_budget is None else int(workspace_budget)
-        one = int(self.lib.vh_session_refine_windows_workspace(self.handle, 1, nf))
+        one = int(getattr(self.lib, ws_fn)(self.handle, 1, nf))
         if not one:
-            L.check(-1, "vh_session_refine_windows_workspace")
+            L.check(-1, ws_fn)
         chunk = max(1, min(budget // one, REFINE_WINDOWS_MOST, len(wins)))
         if chunk < len(wins):  # several calls: what the library would refuse in a later one is refused here, before the first is queued
             if len(set(wins)) != len(wins):
@@ -437,10 +446,16 @@ class TrackerSession:
 
         def call(part, recs):
             tab = (L.RefineWindow * len(part))(*[L.RefineWindow(b, f) for b, f in part])
+            if partial:
+                prm = L.RefinePartialParams(int(min_obs), float(start_reproj))
+                L.check(self.lib.vh_session_refine_windows_partial(self.handle, tab, len(part), nf, max_iter, int(bool(with_points)), C.byref(prm), recs,
+                                                                   L.dptr(self._refine_ws), self._refine_ws.numel(), L.stream_ptr()),
+                        "vh_session_refine_windows_partial")
+                return
             L.check(self.lib.vh_session_refine_windows(self.handle, tab, len(part), nf, max_iter, int(bool(with_points)), recs, L.dptr(self._refine_ws),
                                                        self._refine_ws.numel(), L.stream_ptr()), "vh_session_refine_windows")
 
-        return self._refine_request(call, wins, lay, nf, out, chunk, int(self.lib.vh_session_refine_windows_workspace(self.handle, chunk, nf)))
+        return self._refine_request(call, wins, lay, nf, out, chunk, int(getattr(self.lib, ws_fn)(self.handle, chunk, nf)))
 
     def __del__(self):
         try:
@@ -504,6 +519,10 @@ REFINE_WINDOWS_MOST = 65535  # windows of one BA launch sequence (vh_nls_batch_w
 def _unpack_refined(raw, lay, nf=None):
     """THE reader of a refinement record of either layout (uint8 array `raw`, offsets `lay`): the header words, the first nf of the record's rows of cw, dr
     and speed, the scalars, the trace and -- where the record carries them -- ids and pw; every array is a copy."""
+    counts = {}
+    if isinstance(lay, L.RefinePartialRecord):  # the window record, then the four counts
+        counts = {k: int(np.frombuffer(raw, np.int32, 1, getattr(lay, k))[0]) for k in ("nobs", "npart", "ntri", "nrej")}
+        lay = lay.win
     window = isinstance(lay, L.RefineWindowRecord)
 
     def rd(off, count, dtype):
@@ -519,7 +538,7 @@ def _unpack_refined(raw, lay, nf=None):
     one = {k: float(rd(getattr(lay, k), 1, np.float64)[0]) for k in ("speed_mean", "speed_std", "f_first", "f_last")}
     pts = dict(ids=rd(lay.ids, nt, np.int32), pw=rd(lay.pw, 3 * nt, np.float64).reshape(nt, 3)) if not window or lay.with_points else {}
     return dict(cw=cw[:nf].copy(), dr=rd(lay.dr, nf, np.float64), speed=rd(lay.speed, nf, np.float64),
-                trace=rd(lay.trace, 2 * head["iterations"], np.float64).reshape(head["iterations"], 2), **head, **one, **pts)
+                trace=rd(lay.trace, 2 * head["iterations"], np.float64).reshape(head["iterations"], 2), **head, **one, **pts, **counts)
 
 
 def unpack_refine(raw, lay, nf=None):
@@ -533,7 +552,8 @@ def unpack_refine_window(raw, lay):
     """A vh_refine_window_record (uint8 array `raw`, offsets `lay`) as a dict: slot, first, nt, nfix (anchored points among the nt; 0: solved free),
     iterations, converged, cw [nf, 3] (relative to the window's
     first camera), dr [nf], speed [nf] (entry 0 NaN), speed_mean, speed_std, f_first, f_last, trace [iterations, 2] and, when the record carries them,
-    ids [nt] and pw [nt, 3] (in the window's coordinates: subtract B[first, 3:6] for the session's); every array is a copy."""
+    ids [nt] and pw [nt, 3] (in the window's coordinates: subtract B[first, 3:6] for the session's); every array is a copy.  A vh_refine_partial_record
+    (offsets RefinePartialRecord) gives the same and nobs, npart, ntri, nrej."""
     return _unpack_refined(raw, lay)
 
 
@@ -580,26 +600,56 @@ def merge_window_speeds(n, windows):
 
 
 def _merged_ba(n, wins, window, stride):
-    """result["ba"] of a clip refined in windows: merge_window_speeds' dict with `window` and `stride`."""
-    return dict(merge_window_speeds(n, wins), window=window, stride=stride)
+    """result["ba"] of a clip refined in windows: merge_window_speeds' dict with `window` and `stride`; windows refined with min_obs (their dicts carry
+    the counts) add the per-window arrays nobs, npart, ntri, nrej."""
+    counts = {k: np.array([w[k] for w in wins], np.int64) for k in ("nobs", "npart", "ntri", "nrej") if wins and k in wins[0]}
+    return dict(merge_window_speeds(n, wins), window=window, stride=stride, **counts)
 
 
-def _refine_finished(ses, clips, win, stride):
+def _check_partial(refine, refine_min_obs=None, refine_start_reproj=None):
+    """-> None (the option is absent), or (min_obs, start_reproj); raises ValueError by name before anything is queued."""
+    if refine_min_obs is None:
+        if refine_start_reproj is not None:
+            raise ValueError("refine_start_reproj needs refine_min_obs")
+        return None
+    if refine != "ba":
+        raise ValueError("refine_min_obs needs refine='ba'")
+    m, r = int(refine_min_obs), 0.0 if refine_start_reproj is None else float(refine_start_reproj)
+    if m < 2:
+        raise ValueError(f"refine_min_obs = {m}: a track needs at least two observations")
+    if not (np.isfinite(r) and r >= 0.0):
+        raise ValueError(f"refine_start_reproj = {r}: a finite number of pixels >= 0")
+    return m, r
+
+
+def _refine_finished(ses, clips, win, stride, partial=None):
     """The refinement of the clips of session `ses` that have just ended, for all three drivers.  clips = [(slot, clip length, pinned buffer for the
     clip's records or None: for all of them or for none)]; win, stride: _check_refine's.  The clips of at least `win` frames go through ONE
     refine_windows request -- the windows refine_window_starts gives each, a clip's consecutive -- and the others through one refine per clip length,
-    shortest first.  Returns per clip (the handle of its request, the function that turns the handle's result into the clip's "ba" dict)."""
+    shortest first.  Returns per clip (the handle of its request, the function that turns the handle's result into the clip's "ba" dict).
+    partial = _check_partial's (min_obs, start_reproj): every request goes through refine_windows(min_obs=...) -- min_obs cut to the window's frames --
+    and a clip that is not windowed is ONE window of its own length (one request per clip length, as whole clips have)."""
     done = [None] * len(clips)
     starts = {i: refine_window_starts(n, win, stride) for i, (_, n, _) in enumerate(clips) if win and n >= win}
+
+    def pkw(nf):
+        return {} if partial is None else dict(min_obs=min(partial[0], nf), start_reproj=partial[1])
+
     if starts:
         rh = ses.refine_windows([(clips[i][0], f) for i, st in starts.items() for f in st], win,
-                                out=None if clips[0][2] is None else [(clips[i][2], len(st)) for i, st in starts.items()])
+                                out=None if clips[0][2] is None else [(clips[i][2], len(st)) for i, st in starts.items()], **pkw(win))
         at = 0
         for i, st in starts.items():
             done[i] = (rh, lambda r, at=at, k=len(st), n=clips[i][1]: _merged_ba(n, r[at:at + k], win, stride))
             at += len(st)
     for n_clip in sorted({n for i, (_, n, _) in enumerate(clips) if i not in starts}):
         same = [i for i, (_, n, _) in enumerate(clips) if i not in starts and n == n_clip]
+        if partial is not None:
+            rh = ses.refine_windows([(clips[i][0], 0) for i in same], n_clip, out=None if clips[0][2] is None else [(clips[i][2], 1) for i in same],
+                                    **pkw(n_clip))
+            for idx, i in enumerate(same):
+                done[i] = (rh, lambda r, idx=idx, n=n_clip: _merged_ba(n, r[idx:idx + 1], n, n - 1))
+            continue
         rh = ses.refine([clips[i][0] for i in same], out=None if clips[0][2] is None else [clips[i][2] for i in same])
         for idx, i in enumerate(same):
             done[i] = (rh, lambda r, idx=idx: r[idx])
@@ -612,6 +662,8 @@ def ba_line(ba):
     how many of its tracks were anchored -- the fewest and the most of a window -- since 0 means the solve ran free; otherwise the line is what it was."""
     if "window" in ba:
         anchors = f", {np.min(ba['nfix'])}-{np.max(ba['nfix'])} anchors" if "anchor" in ba else ""
+        if "npart" in ba:  # refined with min_obs: how many of the windows' tracks live through part of their window, how many starts were triangulated
+            anchors += f", {int(ba['npart'].sum())} partial of {int(ba['nt'].sum())}, {int(ba['ntri'].sum())} starts triangulated ({int(ba['nrej'].sum())} rejected)"
         return (f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({len(ba['first'])} windows of {ba['window']} frames, "
                 f"{ba['nt'].min()}-{ba['nt'].max()} tracks{anchors}, f = {np.nanmax(ba['f_last']) if np.isfinite(ba['f_last']).any() else np.nan:.3f} pixels)")
     anchors = f", {ba['nfix']} anchors" if "anchor" in ba else ""
@@ -967,7 +1019,8 @@ def clip_result(st, clip, f0, seconds, step_seconds, sessions, recoveries, proc=
 def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01,
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
                  out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
-                 refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0):
+                 refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0, refine_min_obs=None,
+                 refine_start_reproj=None):
     """The packaged counterpart of vidExample.py:52-178 (minus video decode and plots) on one clip.
 
     frames  sequence of n uint8 [H, W] gray frames (numpy arrays or CUDA tensors): what `cv2.cvtColor(cap.read(), BGR2GRAY)` / `cv2.imread(.., 0)` hands
@@ -997,6 +1050,11 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             plate.  "ba" gains nothing but `anchor`; its `nfix` says how many anchors were alive (per window in the windowed form: 0 = that window ran
             free), and the BA line says so too.  What it does not do: a window with first > 0 places its anchors by the tracker's own B[first, 3:6],
             windows stay separate solves, and the plate's frame-0 pose error is inherited.
+    refine_min_obs, refine_start_reproj   None (default: nothing changes), or M >= 2 (needs refine="ba"): a window also takes the tracks observed in at
+            least M of its frames (cut to the window's length) that have a world point to start from -- and, with refine_start_reproj = R > 0 pixels,
+            those whose two-view start reprojects within R (TrackerSession.refine_windows(min_obs=, start_reproj=)).  Without refine_window the clip is
+            ONE window of its own length (at most 256 frames).  "ba" is then the windowed dict plus, per window, nobs, npart, ntri, nrej, and the BA
+            line says how many tracks are partial and how many starts were triangulated.
     replenish, spare   None (default: nothing new is queued), or a Replenish: the session gets `spare` rows behind the 4 + max_corners of frame 0, lost
             tracks are replaced by new corners there and triangulated on the device (TrackerSession(replenish=...); detector and sub-pixel settings: the
             frame-0 ones).  The result's track rows are then the rows used, it gains "replenish" (replenish_result) and one line follows the summary.
@@ -1007,6 +1065,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     import time as _time
 
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
+    partial = _check_partial(refine, refine_min_obs, refine_start_reproj)
     refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     if route != "session":
         raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
@@ -1047,7 +1106,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     step_seconds = (clock() - t_loop) / (n - 1)
     ba = None
     if refine:
-        (rh, ba_of), = _refine_finished(ses, [(0, n, None)], win, stride)
+        (rh, ba_of), = _refine_finished(ses, [(0, n, None)], win, stride, partial)
         ba = _tag_anchor(ba_of(rh.result()), refine_anchor)
     st, recoveries, f0 = ses.state(0), ses.recoveries()[0], f0.host()
     res = clip_result(st, dict(n=n, name=name, frame_numbers=frame_numbers), f0, clock() - t_begin, step_seconds, 1, recoveries, proc if live else None, ba,
@@ -1126,7 +1185,8 @@ class _SessionSet:
 
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
                   msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
-                  refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0):
+                  refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0, refine_min_obs=None,
+                 refine_start_reproj=None):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name, K]) of ONE length -- the
     frame size and the intrinsics are each clip's own ("K": that clip's camera, default the K argument); the sessions are created at the elementwise
     maximum of the sizes and a frame step is sized for it, so clips of one camera type batch best.  One length stays required: a step advances every
@@ -1139,9 +1199,11 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     `lines` = that clip's table and summary, printed through `out` if given), each equal to what run_sequence returns for the clip alone.  refine="ba": as in
     run_sequence; all the clips of a session are refined by ONE TrackerSession.refine after the last frame -- with refine_window=W (and clips of at least
     W frames) all the windows of all the clips of a session by ONE TrackerSession.refine_windows request.  refine_anchor="plate": as in run_sequence,
-    for every clip.  replenish, spare: as in run_sequence, for every clip (the births of all the streams of a session are one launch sequence)."""
+    for every clip.  refine_min_obs, refine_start_reproj: as in run_sequence (without refine_window: the clips of a session are ONE request of
+    one-window clips).  replenish, spare: as in run_sequence, for every clip (the births of all the streams of a session are one launch sequence)."""
     import time as _time
 
+    partial = _check_partial(refine, refine_min_obs, refine_start_reproj)
     refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
@@ -1179,7 +1241,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     if refine:
         for ses, hs, mem in zip(sess, group.hip_streams, members):
             with torch.cuda.stream(hs):  # (one length: ONE request per session)
-                refined.append(_refine_finished(ses, [(j, n, None) for j in range(len(mem))], win, stride))
+                refined.append(_refine_finished(ses, [(j, n, None) for j in range(len(mem))], win, stride, partial))
         refined = [[ba_of(rh.result()) for rh, ba_of in per] for per in refined]
     seconds = _time.perf_counter() - t_begin
     # what tools/exp/queue_timing.py reads: device time of the frame-0 block of every session (events on its stream), to set beside run_queue's
@@ -1256,7 +1318,8 @@ def queue_plan(lengths, streams, sessions=1):
 
 def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, max_size=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
               harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=None, use_harris=True, min_distance=0.0, fallback=False,
-              fallback_params=None, refine=None, refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0):
+              fallback_params=None, refine=None, refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0, refine_min_obs=None,
+                 refine_start_reproj=None):
     """A queue of clips of ANY length on `streams` resident streams: what run_sequences is for clips of one length.  `clips` = any iterable of
     dict(frames, q, times[, frame_numbers, name, K]), each of >= 2 frames and with its own frame size and intrinsics ("K": default the K argument); it is consumed lazily -- a clip is pulled when a slot is free
     for it and its frames go up then, so at most `streams` clips are resident -- and may hold more clips than fit on the device at once.
@@ -1283,6 +1346,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
     waits for the device: with the option on the loop waits once per finished clip)."""
     import time as _time
 
+    partial = _check_partial(refine, refine_min_obs, refine_start_reproj)
     refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
@@ -1367,8 +1431,10 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
             rec_bytes = sess[0].record_layout().bytes
             ba_bytes = sess[0].refine_layout().bytes if refine else 0
             if win and nhist >= win:  # room for the most windows a clip of nhist frames can have (a clip shorter than W: the whole-clip record)
-                win_bytes = sess[0].refine_window_layout(win).bytes
+                win_bytes = sess[0].refine_window_layout(win, partial=partial is not None).bytes
                 ba_bytes = max(ba_bytes, len(refine_window_starts(nhist, win, stride)) * win_bytes)
+            if partial is not None:  # a clip that is not windowed: one window of its own length
+                ba_bytes = max(ba_bytes, sess[0].refine_window_layout(min(nhist, 256), partial=True).bytes)
             ring = [[torch.empty(rec_bytes, dtype=torch.uint8).pin_memory(), torch.empty(10, dtype=torch.float64).pin_memory(), None,
                      torch.empty(ba_bytes, dtype=torch.uint8).pin_memory() if refine else None] for _ in range(2 * streams)]
         for g, (ses, hs) in enumerate(zip(sess, group.hip_streams)):
@@ -1426,7 +1492,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
                     held[g][j] = None
                     finished.append((j, c["n"], entry))
                 if refine and finished:  # right behind the exports; a clip's records land in its own pinned buffer
-                    for (_, _, e), ba in zip(finished, _refine_finished(ses, [(j, n, e[3]) for j, n, e in finished], win, stride)):
+                    for (_, _, e), ba in zip(finished, _refine_finished(ses, [(j, n, e[3]) for j, n, e in finished], win, stride, partial)):
                         e[2][5] = ba
         steps += 1
         poll()
@@ -1470,6 +1536,10 @@ def main(argv=None):
     ap.add_argument("--refine", choices=["ba"], default=None, help="bundle-adjust the finished clip on the device and print the refined speed (vidExample.py:157)")
     ap.add_argument("--refine-window", type=int, default=None, metavar="W", help="with --refine ba: refine the clip in windows of W frames (2 .. 256); clips of any length")
     ap.add_argument("--refine-stride", type=int, default=None, metavar="S", help="frames between the starts of consecutive windows (1 .. W-1; default W-1)")
+    ap.add_argument("--refine-min-obs", type=int, default=None, metavar="M",
+                    help="with --refine ba: a window also takes the tracks observed in at least M of its frames (a clip without --refine-window: one window)")
+    ap.add_argument("--refine-start-reproj", type=float, default=None, metavar="R",
+                    help="with --refine-min-obs: tracks without a trusted world point start from a two-view triangulation that reprojects within R pixels")
     ap.add_argument("--refine-anchor", choices=["plate"], default=None, help="with --refine ba: hold the four plate corners fixed in the adjustment (a metric scale from the plate)")
     ap.add_argument("--replenish", type=int, nargs="?", const=5, default=None, metavar="EVERY",
                     help="replace lost tracks with new corners every EVERY frames (default 5) and triangulate them on the device")
@@ -1482,6 +1552,7 @@ def main(argv=None):
     run_sequence(fr, d[f"{a.seq}_q"], d[f"{a.seq}_K"], times=d[f"{a.seq}_times"], roi_border=border, msv_frame=a.msv_frame,
                  name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback, refine=a.refine,
                  refine_window=a.refine_window, refine_stride=a.refine_stride, refine_anchor=a.refine_anchor,
+                 refine_min_obs=a.refine_min_obs, refine_start_reproj=a.refine_start_reproj,
                  replenish=None if a.replenish is None else Replenish(every=a.replenish), spare=a.spare if a.replenish is not None else 0)
 
 
