@@ -670,7 +670,19 @@ VH_API int vh_session_pack_state(vh_session* s, float* out, void* stream);
 
 /* The vh_debug_* switches below are PROCESS-WIDE (atomics): they re-route every context of the process, and exist for the parity tests and A/B
  * experiments only -- every route they select is bit-identical to the default one.  Not a per-stream control; do not flip them in a multi-tenant process
- * for anything but a test.
+ * for anything but a test.  They are test hooks, not controls: one record in the library holds them all, and every launch reads one snapshot of it.
+ *
+ *   entry                        values (anything else is stored as given unless noted)                          default   read by
+ *   vh_debug_force_generic_lk    0: by window and load, 1..9: the LK kernel of that id where its window allows     0         every LK launch
+ *   vh_debug_lk3_tpw             0: by load, 1..8: launch slots per workgroup (n < 0 -> 0, n > 8 acts as 8)         0         LK launches of routes 3 and 5
+ *   vh_debug_lk3_one_level       0 / 1 (any non-zero value -> 1)                                                  1         LK launches of routes 3, 5, 6, 7
+ *   vh_debug_ransac_path         0: by size, 1: three kernels, 2: fused kernel where the problem fits (as 0)       0         every RANSAC launch
+ *   vh_debug_pyr_rows            0: by size, 2 / 4 / 8 rows per thread (anything else -> 0)                        0         every pyrDown launch
+ *   vh_debug_klt_order           -1: by load, 0: never, 1: always                                                 -1        vh_klt_main, vh_session_step*
+ *   vh_debug_ba_force_valu       0 / 1                                                                            0         every bundle adjustment entry
+ *   vh_debug_lk3_residency, vh_debug_lkh_residency: queries, they set nothing
+ * (DESIGN.md section 5 lists the environment variables that give four of them another start value, and the experiment switches that have no entry.)
+ *
  * test hook: route every LK window through one implementation -- 1: per-sample kernel, 2: strip kernel, 3: LDS-staged
  * kernel, 4: 4-tracks-per-wavefront kernel (15x15 windows; others as in 2), 5 / 6 / 7: LDS-staged 51x51 kernel with 1 / 2 / 4
  * wavefronts per track (other windows: default routing), 8: 8-tracks-per-wavefront kernel k_lk_o (15x15 windows; others as in 2),

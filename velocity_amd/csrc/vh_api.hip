@@ -32,10 +32,73 @@ int vh_fail(int code, const char* msg)
 #define VH_LAUNCH_CHECK() VH_CHECK(hipGetLastError())
 
 extern "C" VH_API int vh_version(void) { return 111; }
-void vh_lk_force_generic(int on);
-extern "C" VH_API void vh_debug_force_generic_lk(int on) { vh_lk_force_generic(on); }
-void vh_ransac_force_path(int mode);
-extern "C" VH_API void vh_debug_ransac_path(int mode) { vh_ransac_force_path(mode); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The ONE record of the process-wide hooks and switches (VhTuning, vh_step_plan.hpp, says what each means and who reads it).  Built on first use, by
+// whichever comes first, a hook or a launch.  The seven values a vh_debug_* entry sets are atomics -- a flip while another thread launches is a clean
+// switch between two bit-identical implementations, never a torn value -- and start from their environment variable where they have one; the rest
+// is read from the environment once and never changes.  (VH_BA_DBG is no part of it: vh_ba_run reads it on every call.)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+struct VhSwitches {
+    VhTuning env;  // the environment-only values, and the defaults of the rest (first: the atomics below start from it)
+    std::atomic<int> lk_force, lk3_tpw, lk3_one_level, klt_order, ransac_path, pyr_rows, ba_force_valu;
+    static long long env_ll(const char* name, long long dflt)
+    {
+        const char* e = getenv(name);
+        return e ? atoll(e) : dflt;
+    }
+    static int env_int(const char* name, int dflt)
+    {
+        const char* e = getenv(name);
+        return e ? atoi(e) : dflt;
+    }
+    VhSwitches()
+        : lk_force(env_int("VH_LK_FORCE", env.lk_force)), lk3_tpw(env_int("VH_LK3_TPW", env.lk3_tpw)),
+          lk3_one_level(env_int("VH_LK3_ONE_LEVEL", env.lk3_one_level)), klt_order(env_int("VH_KLT_ORDER", env.klt_order)), ransac_path(env.ransac_path),
+          pyr_rows(env.pyr_rows), ba_force_valu(env.ba_force_valu)
+    {
+        env.lko_group = env_int("VH_LKO_G", env.lko_group);
+        env.lkq_group = env_int("VH_LKQ_G", env.lkq_group);
+        env.lk3_group = env_int("VH_LK3_G", env.lk3_group);
+        env.lk_lds_pad = env_int("VH_LK_LDS_PAD", env.lk_lds_pad);
+        env.lko_min_tracks = env_ll("VH_LKO_MIN", env.lko_min_tracks);
+        env.lkh_min_tracks = env_ll("VH_LKH_MIN", env.lkh_min_tracks);
+        env.rw_xcd_bands = env_int("VH_RW_XCD", env.rw_xcd_bands);
+        env.ba_parts = env_int("VH_BA_PARTS", env.ba_parts);
+        const char* g = getenv("VH_BA_GRAPH");
+        env.ba_graph_off = g && g[0] == '0';
+    }
+};
+VhSwitches& vh_switches()
+{
+    static VhSwitches r;
+    return r;
+}
+}  // namespace
+
+VhTuning vh_tuning()
+{
+    const VhSwitches& r = vh_switches();
+    VhTuning t = r.env;
+    t.lk_force = r.lk_force.load(std::memory_order_relaxed);
+    t.lk3_tpw = r.lk3_tpw.load(std::memory_order_relaxed);
+    t.lk3_one_level = r.lk3_one_level.load(std::memory_order_relaxed);
+    t.klt_order = r.klt_order.load(std::memory_order_relaxed);
+    t.ransac_path = r.ransac_path.load(std::memory_order_relaxed);
+    t.pyr_rows = r.pyr_rows.load(std::memory_order_relaxed);
+    t.ba_force_valu = r.ba_force_valu.load(std::memory_order_relaxed);
+    return t;
+}
+
+// the setters (include/velocity_hip.h has the table of values); what a setter normalises, the plans never see otherwise
+extern "C" VH_API void vh_debug_force_generic_lk(int on) { vh_switches().lk_force.store(on, std::memory_order_relaxed); }
+extern "C" VH_API void vh_debug_lk3_tpw(int n) { vh_switches().lk3_tpw.store(n < 0 ? 0 : n, std::memory_order_relaxed); }
+extern "C" VH_API void vh_debug_lk3_one_level(int on) { vh_switches().lk3_one_level.store(on ? 1 : 0, std::memory_order_relaxed); }
+extern "C" VH_API void vh_debug_klt_order(int mode) { vh_switches().klt_order.store(mode, std::memory_order_relaxed); }
+extern "C" VH_API void vh_debug_ransac_path(int mode) { vh_switches().ransac_path.store(mode, std::memory_order_relaxed); }
+extern "C" VH_API void vh_debug_pyr_rows(int rows) { vh_switches().pyr_rows.store(rows == 2 || rows == 4 || rows == 8 ? rows : 0, std::memory_order_relaxed); }
+extern "C" VH_API void vh_debug_ba_force_valu(int on) { vh_switches().ba_force_valu.store(on, std::memory_order_relaxed); }
 
 extern "C" VH_API int vh_copy_to_host(void* dst_host, const void* src_dev, size_t bytes, void* stream)
 {
@@ -268,9 +331,6 @@ static int launch_lk_profiled(vh_ctx* c, int stage, const void* tab, size_t st, 
         vh_prof_stop((c), rec_, (stage), (s));        \
     } while (0)
 
-static std::atomic<int> g_klt_order{getenv("VH_KLT_ORDER") ? atoi(getenv("VH_KLT_ORDER")) : -1};  // PROCESS-WIDE test hook: 1 always, 0 never, -1 by load
-extern "C" VH_API void vh_debug_klt_order(int mode) { g_klt_order.store(mode, std::memory_order_relaxed); }
-
 int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_params& coarse, const vh_lk_params& fine, const SessStream* sess,
                     const uint8_t* const* frames, int n_max)
 {
@@ -278,9 +338,7 @@ int vh_run_klt_main(vh_ctx* c, int slot, int count, hipStream_t s, const vh_lk_p
     StreamWS* ws = c->d_ws + slot;
     const size_t st = sizeof(StreamWS);
     const int lvl_c = min(coarse.max_level, VH_MAX_LEVELS - 1), lvl_f = min(fine.max_level, VH_MAX_LEVELS - 1);
-    // spatial launch order of the tracks: pays from the load at which a stream's pyramids no longer sit in every L2 anyway (8 streams: no difference measured)
-    const int order_mode = g_klt_order.load(std::memory_order_relaxed);
-    const int use_order = order_mode >= 0 ? order_mode : ((long long)count * mn >= 24000 ? 1 : 0);
+    const int use_order = klt_track_order(count, mn, vh_tuning());  // spatial launch order of the tracks, by load
     hipLaunchKernelGGL(k_klt_setup, dim3(count), dim3(use_order ? KO_THREADS : 64), 0, s, ws, sess ? sess + slot : nullptr, frames, coarse, fine, use_order);
     VH_PROFILED(c, VH_PROF_RESIZE, s, vh_launch_resize_quarter(&ws->rs_src[0], &ws->rs_dst[0], st, 2, count, c->sw, c->sh, s));
     VH_PROFILED(c, VH_PROF_PYR, s, for (int l = 0; l < lvl_c; l++) vh_launch_pyr_down_ws(&ws->pb[0], st, count, l, c->sw, c->sh, s));
@@ -402,11 +460,6 @@ extern "C" VH_API int vh_profile_lk_tpw(vh_ctx* c, int* tpw_host)
     for (int k = 0; k < 3; k++) tpw_host[k] = c->lk_tpw[k];
     return 0;
 }
-
-void vh_lk3_set_tpw(int n);
-extern "C" VH_API void vh_debug_lk3_tpw(int n) { vh_lk3_set_tpw(n); }
-void vh_lk3_set_one_level(int on);
-extern "C" VH_API void vh_debug_lk3_one_level(int on) { vh_lk3_set_one_level(on); }
 
 int vh_lk3_residency(int out[4]);
 extern "C" VH_API int vh_debug_lk3_residency(int out[4])
@@ -876,14 +929,7 @@ extern "C" VH_API int vh_msv1_t(vh_ctx* c, const double* K, const float* P, cons
 // bundle adjustment entry points
 // ---------------------------------------------------------------------------------------------------------------
 // partial systems of nwin windows (ba_nparts, vh_ba_plan.hpp) under the VH_BA_PARTS experiment switch, which is read once per process
-static int ba_parts(int nt, int nc, int nwin = 1)
-{
-    static const int cap_env = [] { const char* e = getenv("VH_BA_PARTS"); return e ? atoi(e) : 0; }();
-    return ba_nparts(nt, nc, nwin, cap_env);
-}
-static std::atomic<int> g_ba_force_valu{0};  // PROCESS-WIDE test hook (include/velocity_hip.h)
-extern "C" VH_API void vh_debug_ba_force_valu(int on) { g_ba_force_valu.store(on, std::memory_order_relaxed); }
-extern "C" VH_API void vh_debug_pyr_rows(int rows) { vh_pyr_force_rows(rows == 2 || rows == 4 || rows == 8 ? rows : 0); }
+static int ba_parts(int nt, int nc, int nwin = 1) { return ba_nparts(nt, nc, nwin, vh_tuning().ba_parts); }
 
 extern "C" VH_API size_t vh_nls_batch_workspace(int nt, int nc) { return vh_ba_workspace_bytes(nt, nc, ba_parts(nt, nc)); }
 
@@ -907,7 +953,7 @@ static int ba_problem(BaProblem& P, vh_ctx* c, const char* fn, const double* K_h
     for (int k = 0; k < 9; k++) P.K[k] = (double)K_host[k];
     P.z = z; P.x = x; P.trace = trace; P.info = info; P.workspace = workspace;
     P.nt = nt; P.nc = nc; P.max_iter = max_iter; P.nparts = ba_parts(nt, nc);
-    P.force_valu = g_ba_force_valu.load(std::memory_order_relaxed);
+    P.force_valu = vh_tuning().ba_force_valu;
     P.phase = -1; P.add_identity = 1; P.count_cams = 1; P.nwin = 1;
     P.nx_total = 3.0 * nt + 6.0 * nc; P.nz_total = 2.0 * nt * (nc + 1);
     return 0;

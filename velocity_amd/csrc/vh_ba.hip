@@ -1941,8 +1941,7 @@ struct BaGraphCache {
 };
 static BaGraphCache* ba_graph_cache(void** where)
 {
-    static const bool off = [] { const char* v = getenv("VH_BA_GRAPH"); return v && v[0] == '0'; }();
-    if (!where || off) return nullptr;
+    if (!where || vh_tuning().ba_graph_off) return nullptr;
     if (!*where) {
         BaGraphCache* c = new (std::nothrow) BaGraphCache();
         if (!c) return nullptr;

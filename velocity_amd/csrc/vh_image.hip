@@ -1,8 +1,6 @@
 // Image-stage kernels of the KLT path: quarter-scale nearest decimation (K1), pyrDown (K2), shifted crop (K8) and
 // affine remap (K9).  All are HBM-bound byte kernels; descriptors are read from device memory because ROI sizes are
 // data dependent (bounding box of the tracks) and the whole frame pipeline runs without a host round trip.
-#include <atomic>
-#include <cstdlib>
 #include <algorithm>
 #include "vh_kernels.hpp"
 #include "vh_valu.hpp"
@@ -632,47 +630,21 @@ __global__ __launch_bounds__(256) void k_pyr_pad(const void* pb_tab, size_t ws_s
     }
 }
 
-static std::atomic<int> g_pyr_rows{0};  // PROCESS-WIDE test hook (include/velocity_hip.h): 2 / 4 / 8 output rows per thread whatever the launch size (0: by size)
-void vh_pyr_force_rows(int rb) { g_pyr_rows.store(rb, std::memory_order_relaxed); }
-
+// launches what pyr_plan says (vh_step_plan.hpp: rows per thread by launch size, the ring's workgroups per image)
 void vh_launch_pyr_down_ws(const void* pb_tab, size_t ws_stride, int batch, int lvl, int max_w0, int max_h0, hipStream_t s)
 {
-    // dims of level lvl+1 when level 0 is max_w0 x max_h0
-    int w = max_w0, h = max_h0;
-    for (int l = 0; l <= lvl; l++) { w = (w + 1) / 2; h = (h + 1) / 2; }
-    // 64 x 4 threads: a wavefront is ONE row of 256 output pixels.  Wavefronts of 16 x 4 or 32 x 2 threads (fewer idle lanes in the last column of
-    // workgroups: 818 output pixels are 3.2 wavefronts of 256) measured SLOWER -- 451 / 454 against 405 us for pyrDown + rings at 256 streams: a
-    // thread's 19 source rows are shared with no other row of its wavefront, and narrower row segments coalesce worse
-    const dim3 blk(64, 4);
-    // 8 output rows per thread (19 source rows in flight, 136 VGPRs) once a launch is far beyond the chip (19 rows read per 16 produced instead of
-    // 11 per 8: 271 -> 250 us for the 766 x 451 level of 256 streams; no gain below), 4 rows from ~1 Mpx, 2 for single-stream latency
-    const long long px = (long long)w * h * batch;
-    const int forced_rows = g_pyr_rows.load(std::memory_order_relaxed);
-    const int rb = forced_rows ? forced_rows : (px >= (1ll << 25) ? 8 : px >= (1ll << 20) ? 4 : 2);
-    if (rb == 8) {
-        dim3 grd((w + 4 * blk.x - 1) / (4 * blk.x), (h + 8 * blk.y - 1) / (8 * blk.y), batch * 2);
-        hipLaunchKernelGGL(k_pyr_down<8>, grd, blk, 0, s, pb_tab, ws_stride, lvl);
-    } else if (rb == 4) {
-        dim3 grd((w + 4 * blk.x - 1) / (4 * blk.x), (h + 4 * blk.y - 1) / (4 * blk.y), batch * 2);
-        hipLaunchKernelGGL(k_pyr_down<4>, grd, blk, 0, s, pb_tab, ws_stride, lvl);
-    } else {
-        dim3 grd((w + 4 * blk.x - 1) / (4 * blk.x), (h + 2 * blk.y - 1) / (2 * blk.y), batch * 2);
-        hipLaunchKernelGGL(k_pyr_down<2>, grd, blk, 0, s, pb_tab, ws_stride, lvl);
-    }
-    // border ring of the new level when it is a small one (decided per image on the device): a few workgroups per image, each loops over its share --
-    // 4 when the launch has many images (327 against 338 us for pyrDown + rings at 256 streams), 32 for a few streams (a ring of <= ~7000 dwords in one pass:
-    // with 4 a single-stream step took 6 us longer)
-    hipLaunchKernelGGL(k_pyr_pad, dim3(batch >= 16 ? 4 : 32, 1, batch * 2), dim3(256), 0, s, pb_tab, ws_stride, lvl);
+    const PyrPlan p = pyr_plan(lvl, max_w0, max_h0, batch, vh_tuning());
+    const dim3 grd(p.grid_x, p.grid_y, p.grid_z), blk(p.block_x, p.block_y);
+    if (p.rows == 8) hipLaunchKernelGGL(k_pyr_down<8>, grd, blk, 0, s, pb_tab, ws_stride, lvl);
+    else if (p.rows == 4) hipLaunchKernelGGL(k_pyr_down<4>, grd, blk, 0, s, pb_tab, ws_stride, lvl);
+    else hipLaunchKernelGGL(k_pyr_down<2>, grd, blk, 0, s, pb_tab, ws_stride, lvl);
+    hipLaunchKernelGGL(k_pyr_pad, dim3(p.ring_groups, 1, p.grid_z), dim3(256), 0, s, pb_tab, ws_stride, lvl);
 }
 
+// ... what roi_warp_plan says
 void vh_launch_roi_warp(const void* job_tab, size_t tab_stride, int batch, int max_w, int max_h, hipStream_t s)
 {
-    // 16 x 16 threads: a wavefront covers 4 consecutive ROI rows of 128 pixels, so the bottom source row of one thread row is the top source row of
-    // the next INSIDE the wavefront (one L1 fetch instead of two) and the last column of workgroups idles 28 of 1636 pixels instead of 412.  Measured at
-    // 256 streams (A/B on one box): 64 x 4 threads (one 512-pixel row per wavefront) 370 us, 32 x 8 375, 16 x 16 301, 16 x 8 292-302, 8 x 32 305
-    const dim3 blk(16, 16);
-    static const int xcd_bands = getenv("VH_RW_XCD") ? atoi(getenv("VH_RW_XCD")) : 0;  // (environment: experiments only; see the kernel)
-    const unsigned rows = (max_h + blk.y * RW_ROWS * RW_LOOP - 1) / (blk.y * RW_ROWS * RW_LOOP);
-    const dim3 grd((max_w + blk.x * RW_PX - 1) / (blk.x * RW_PX), xcd_bands ? (rows + 7u) & ~7u : rows, batch);  // (padded rows: workgroups beyond the ROI leave at once)
-    hipLaunchKernelGGL(k_roi_warp, grd, blk, 0, s, job_tab, tab_stride, xcd_bands);
+    static_assert(16 * RW_PX == RW_BLOCK_PX && 16 * RW_ROWS * RW_LOOP == RW_BLOCK_ROWS, "roi_warp_plan sizes the grid by a workgroup's pixels");
+    const RoiWarpPlan p = roi_warp_plan(max_w, max_h, batch, vh_tuning());
+    hipLaunchKernelGGL(k_roi_warp, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(p.block_x, p.block_y), 0, s, job_tab, tab_stride, p.xcd_bands);
 }

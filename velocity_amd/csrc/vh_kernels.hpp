@@ -1,6 +1,11 @@
 // Internal kernel-launcher interface of libvelocity_hip.
 #pragma once
 #include "vh_common.hpp"
+#include "vh_step_plan.hpp"
+
+// The hooks and switches of the process as the launch decisions read them (vh_step_plan.hpp): ONE record, defined in vh_api.hip beside the vh_debug_*
+// setters, built on first use.  A launcher takes one snapshot per call: a few relaxed loads, no lock, no getenv.
+VhTuning vh_tuning();
 
 // ROI warp stage of KLTregional (KLT.py:65-73)
 struct WarpJob {
@@ -54,14 +59,13 @@ struct IngestJob {
     int w, h, bgr_stride, gray_stride, dw, dh, small_stride;
 };
 void vh_launch_ingest_bgr(const IngestJob* jobs_dev, int count, int max_w, int max_h, hipStream_t s);
-void vh_pyr_force_rows(int rb);
 void vh_launch_roi_warp(const void* job_tab, size_t tab_stride, int batch, int max_w, int max_h, hipStream_t s);
 // max_level: LKJob::max_level of every job of the launch where the caller knows it (0 selects the single-level form of k_lk3), -1 = not stated
 int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, int win, hipStream_t s, int* route_out = nullptr, int* tpw_out = nullptr,
                  int max_level = -1);
 bool vh_lk_window_fits(int win);  // false: no LK kernel holds a win x win window in LDS (vh_launch_lk would return -2)
 int vh_lk_max_window();           // the largest window that fits
-int vh_lk_route(int batch, int max_n, int win);           // the kernel such a launch takes (ids of vh_debug_force_generic_lk)
+int vh_lk_route(int batch, int max_n, int win);           // the kernel such a launch takes (LkRoute, the ids of vh_debug_force_generic_lk)
 const char* vh_lk_route_name(int route, int win);
 struct StreamWS;
 // returns true when the glue that follows the call in KLTmain (glue = 1: stage 1 -> 2, 2: stage 2 -> 3; glue_ws = the streams' workspaces) ran as the

@@ -15,7 +15,7 @@
 // reduced sums (level start, 2x2 system and its gate, Newton update and stop rules, final in-level check), the loop over the levels, the
 // forward-backward gate, and a kernel's prologue (job row, launch slot -> point, start point) and epilogue (map-back, output stores, statistics)
 // exist once, in vh_lk_shared.hpp.
-#include <atomic>
+#include <algorithm>
 
 #include "vh_kernels.hpp"
 #include "vh_valu.hpp"
@@ -710,9 +710,7 @@ __device__ __forceinline__ void lk_block_xy(unsigned& bx, unsigned& by, unsigned
         bx = xq;
     }
 }
-// group argument of a launch: sets of `g` streams; pinned from 64 streams on (8+ streams share an XCD: their run times even out), rotated below (a stream's
-// workgroups visit every XCD, so a stream that carries more tracks than the others cannot hold one XCD -- and with it the in-order dispatcher -- back)
-static inline unsigned lk_group_arg(unsigned g, int batch) { return g | (batch < 64 ? LK_GRP_ROTATE : 0u); }
+static_assert(LK_GRP_ROTATE == LK_GROUP_ROTATE, "the group argument of a launch is made by lk_group_arg (vh_step_plan.hpp)");
 
 // The level functor of k_lk_strip (see lk_track) only forwards to the function above.  With the level body as the functor's own operator() --
 // the form of the other four kernels -- hipcc allocates k_lk_strip<15> differently: 472 instead of 358 v_readlane / v_writelane of parked scalar
@@ -2063,22 +2061,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
     }
 }
 
-template <int WIN>
-static int launch_lko(const void* job_tab, size_t tab_stride, int batch, int max_n, hipStream_t s)
-{
-    static const unsigned grp = getenv("VH_LKO_G") ? (unsigned)atoi(getenv("VH_LKO_G")) : 64u;  // (environment: experiments only)
-    hipLaunchKernelGGL(k_lk_o<WIN>, dim3((max_n + 7) / 8, batch), dim3(64), 0, s, job_tab, tab_stride, lk_group_arg(grp, batch));
-    return 0;
-}
-
-template <int WIN>
-static int launch_lkq(const void* job_tab, size_t tab_stride, int batch, int max_n, hipStream_t s)
-{
-    static const unsigned grp = getenv("VH_LKQ_G") ? (unsigned)atoi(getenv("VH_LKQ_G")) : 64u;  // (environment: experiments only)
-    hipLaunchKernelGGL(k_lk_q<WIN>, dim3((max_n + 3) / 4, batch), dim3(64), 0, s, job_tab, tab_stride, lk_group_arg(grp, batch));
-    return 0;
-}
-
 #ifndef VH_LKH_WAVES
 #define VH_LKH_WAVES 4  // wavefronts per SIMD k_lk_h is compiled for (profiles/lkh_lds/resources.md; 3: experiments)
 #endif
@@ -2490,14 +2472,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VH_LKH_WAVES
     }
 }
 
-template <int WIN>
-static int launch_lkh(const void* job_tab, size_t tab_stride, int batch, int max_n, hipStream_t s)
-{
-    static const unsigned grp = getenv("VH_LKO_G") ? (unsigned)atoi(getenv("VH_LKO_G")) : 64u;  // (the group argument of launch_lko)
-    hipLaunchKernelGGL(k_lk_h<WIN>, dim3((max_n + 15) / 16, batch), dim3(64), 0, s, job_tab, tab_stride, lk_group_arg(grp, batch));
-    return 0;
-}
-
 // test hook (vh_debug_lkh_residency): what the runtime makes of k_lk_h<15> -- workgroups per CU, registers, scratch bytes per lane, LDS bytes per
 // workgroup (static: the kernel is launched without dynamic LDS).  Launches nothing.
 int vh_lkh_residency(int out[4])
@@ -2513,31 +2487,13 @@ int vh_lkh_residency(int out[4])
     return 0;
 }
 
-// test hook (vh_debug_lk3_tpw): launch slots per workgroup of the one-wavefront LDS-staged kernel -- 0 = chosen by load, n > 0 = n (clamped to MAX_TPW).
-// PROCESS-WIDE atomic like the other hooks; every value gives bit-identical results (VH_LK3_TPW: experiments only, the initial value).
-static std::atomic<int> g_lk3_tpw{getenv("VH_LK3_TPW") ? atoi(getenv("VH_LK3_TPW")) : 0};
-void vh_lk3_set_tpw(int n) { g_lk3_tpw.store(n < 0 ? 0 : n, std::memory_order_relaxed); }
-// test hook (vh_debug_lk3_one_level): 1 = jobs with max_level = 0 take the single-level form of k_lk3 (the default), 0 = they take the general form, whose
-// level loop then runs once.  Bit-identical results.  PROCESS-WIDE, as the hook above.
-static std::atomic<int> g_lk3_one_level{getenv("VH_LK3_ONE_LEVEL") ? atoi(getenv("VH_LK3_ONE_LEVEL")) : 1};  // (environment: experiments only)
-void vh_lk3_set_one_level(int on) { g_lk3_one_level.store(on ? 1 : 0, std::memory_order_relaxed); }
-
-// dynamic LDS of a k_lk3 launch
-template <int WIN, int NW, int M>
-static int lk3_lds_bytes()
-{
-    // VH_LK_LDS_PAD (experiments only): extra dynamic LDS per workgroup = fewer resident wavefronts per SIMD (the occupancy sensitivity behind DESIGN.md section 9)
-    static const int pad = [] { const char* e = getenv("VH_LK_LDS_PAD"); return e ? atoi(e) : 0; }();
-    return LK3<WIN, NW, M>::LDS_BYTES + pad;
-}
-
 // test hook (vh_debug_lk3_residency): what the runtime makes of k_lk3<51, 1, 4> at the dynamic LDS size launch_lk3 passes -- workgroups per CU, registers,
 // scratch bytes per lane, LDS bytes per workgroup.  Launches nothing.  The kernel has two forms (general and single-level, see lk_track): of each figure
 // the WORSE of the two is reported (fewest workgroups, most registers, scratch and LDS).
 int vh_lk3_residency(int out[4])
 {
     const void* fns[2] = {reinterpret_cast<const void*>(k_lk3<51, 1, 4, false>), reinterpret_cast<const void*>(k_lk3<51, 1, 4, true>)};
-    const int lds = lk3_lds_bytes<51, 1, 4>();
+    const int lds = LK3<51, 1, 4>::LDS_BYTES + vh_tuning().lk_lds_pad;
     for (int f = 0; f < 2; f++) {
         int blocks = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fns[f], 64, (size_t)lds);
@@ -2552,139 +2508,65 @@ int vh_lk3_residency(int out[4])
 }
 
 template <int WIN, int NW, int M>
-static int launch_lk3(const void* job_tab, size_t tab_stride, int batch, int max_n, int max_level, hipStream_t s, int* tpw_out)
+static int launch_lk3(const LkPlan& p, const void* job_tab, size_t tab_stride, hipStream_t s)
 {
-    const int lds = lk3_lds_bytes<WIN, NW, M>();
-    static const unsigned grp = getenv("VH_LK3_G") ? (unsigned)atoi(getenv("VH_LK3_G")) : 16u;  // (environment: experiments only)
-    // Launch slots per workgroup (one-wavefront kernel): a 51 x 51 track keeps a workgroup for ~22 us, and starting one (dispatch, LDS allocation, the block
-    // remap, the first descriptor loads) is not free: 4 consecutive slots per workgroup measured 3620 -> 3520 us per launch at 512 000 tracks (2: 3580,
-    // 8: 3545; A/B on one box).  Only where the launch still has many workgroups per resident slot (256 CUs x 12): below that the tail would cost more.
-    const int tpw_env = g_lk3_tpw.load(std::memory_order_relaxed);
-    const long long tracks = (long long)max_n * batch;
-    const int tpw_auto = NW != 1 ? 1 : tracks >= 98304 ? 4 : tracks >= 49152 ? 2 : 1;
-    const unsigned tpw = (unsigned)std::min(NW == 1 && tpw_env > 0 ? tpw_env : tpw_auto, LK3<WIN, NW, M>::MAX_TPW);
-    if (tpw_out) *tpw_out = (int)tpw;
-    // max_level = 0 is one level whatever the frame size is (fill_pyramid): the single-level form of the kernel.  A caller that does not say takes the general one.
-    const dim3 grid((max_n + tpw - 1) / tpw, batch);
-    if (max_level == 0 && g_lk3_one_level.load(std::memory_order_relaxed))
-        hipLaunchKernelGGL((k_lk3<WIN, NW, M, true>), grid, dim3(64 * NW), lds, s, job_tab, tab_stride, lk_group_arg(grp, batch), tpw);
+    static_assert(LK3<WIN, NW, M>::MAX_TPW == LK3_MAX_TPW, "lk_plan clamps the slots per workgroup");
+    const int lds = LK3<WIN, NW, M>::LDS_BYTES + (int)p.lds;
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.one_level)
+        hipLaunchKernelGGL((k_lk3<WIN, NW, M, true>), grid, dim3(p.block), lds, s, job_tab, tab_stride, p.group, (unsigned)p.tpw);
     else
-        hipLaunchKernelGGL((k_lk3<WIN, NW, M, false>), grid, dim3(64 * NW), lds, s, job_tab, tab_stride, lk_group_arg(grp, batch), tpw);
+        hipLaunchKernelGGL((k_lk3<WIN, NW, M, false>), grid, dim3(p.block), lds, s, job_tab, tab_stride, p.group, (unsigned)p.tpw);
     return 0;
 }
 
-template <int WIN_T>
-static int launch_strip(const void* job_tab, size_t tab_stride, int batch, int max_n, int win, hipStream_t s)
+// k_lk and k_lk_strip: all of their dynamic LDS is the host's figure, above the default limit for the larger windows
+template <class Kernel>
+static int launch_lk_lds(Kernel kernel, const LkPlan& p, const void* job_tab, size_t tab_stride, hipStream_t s)
 {
-    const int kmax = (((win + 3) >> 2) * win + 63) / 64;
-    const size_t lds = (size_t)kmax * 64 * 24;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lk_strip<WIN_T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (p.needs_big_lds) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(k_lk_strip<WIN_T>, dim3(max_n, batch), dim3(64), lds, s, job_tab, tab_stride);
+    hipLaunchKernelGGL(kernel, dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, s, job_tab, tab_stride);
     return 0;
 }
 
-// test hook: 1 = per-sample kernel, 2 = strip kernel, 3 = LDS-staged kernel, 4 = 4-tracks-per-wave kernel (15x15), 5 / 6 / 7 = LDS-staged 51x51 kernel with
-// 1 / 2 / 4 wavefronts per track, 8 = 8-tracks-per-wave kernel (15x15), 9 = 16-tracks-per-wave kernel (15x15), 0 = default routing.
-// PROCESS-WIDE (every context of the process is re-routed; an atomic, so a flip while another thread launches is a clean switch between two
-// bit-identical implementations, never a torn value) -- a test / experiment switch, not a per-stream control.
-static std::atomic<int> g_lk_force_generic{getenv("VH_LK_FORCE") ? atoi(getenv("VH_LK_FORCE")) : 0};  // (environment: experiments only)
-void vh_lk_force_generic(int on) { g_lk_force_generic.store(on, std::memory_order_relaxed); }
-static const long long g_lko_min_tracks = getenv("VH_LKO_MIN") ? atoll(getenv("VH_LKO_MIN")) : 10000;  // (environment: experiments only)
-static const long long g_lkh_min_tracks = getenv("VH_LKH_MIN") ? atoll(getenv("VH_LKH_MIN")) : 128000;  // (environment: experiments only)
-
-// Which kernel a launch of `batch` streams x `max_n` track slots with window `win` takes (the ids of the test hook above; 2 = the strip kernel of any
-// window <= 63, 1 = the per-sample kernel).  vh_launch_lk follows exactly this decision, and the profiling records report it (vh_profile_lk_routes), so
-// nobody has to mirror the thresholds.
-//
-// Default routing, re-measured late in round 5 -- the earlier thresholds had been measured while every LK launch carried ~45 us of serialised statistics
-// atomics (StreamWS::lk_stats), which hid what the kernels themselves cost at a few thousand tracks.  51x51 fine stage: the LDS-staged kernel with ONE
-// wavefront per track from 640 tracks in flight (2000 tracks: 28.8 us against 33.2 / 43.2 with 2 / 4 wavefronts per track; 768: 37.1 / 39.7 / 41.1 for
-// the whole vh_pyr_lk call), 4 wavefronts per track below (128 tracks: 30.8 against 35.3); 2 per track is never the fastest and is kept for the tests.
-// 15x15 coarse stages: the one-wave-per-track strip kernel up to 3000 tracks (2000: 20.2 / 27.9 us against 22.2 / 29.4 for 4 tracks per wavefront; 4000:
-// 25.6 / 36.6 against 23.1 / 29.2), 4 tracks per wavefront up to 10 000, 8 per wavefront above (12 000: 33.6 / 50.2 against 35.4 / 55.9 us; 8000: a tie),
-// 16 per wavefront (k_lk_h) from 128 000.  Measured with three wavefronts per SIMD: both launches of sessions of 64 / 96 / 128 / 256 streams x 2000 tracks, routes 8 and 9 forced
-// in one call on one box (profiles/lkh/threshold.json): 147.9 / 242.5 -> 143.6 / 235.0 us at 128 000 tracks, 208.5 / 351.4 -> 202.1 / 336.3 at 192 000, 267.0 / 456.6 ->
-// 254.5 / 432.9 at 256 000, 496.8 / 927.1 -> 460.2 / 897.9 at 512 000, shorter in every run.  128 000 is the smallest load measured, not a crossover: below it the
-// route is unmeasured, and the threshold may not go below 102 401, where a test pins k_lk_o<15> as the headline's route of its time.  The protocol was
-// repeated with the build for four wavefronts per SIMD (profiles/lkh_lds/threshold.json, same loads, nothing below 128 000): the threshold stays.
-int vh_lk_route(int batch, int max_n, int win)
+// k_lk_q, k_lk_o and k_lk_h: no dynamic LDS, the group argument of the block order
+template <class Kernel>
+static int launch_lk_group(Kernel kernel, const LkPlan& p, const void* job_tab, size_t tab_stride, hipStream_t s)
 {
-    const int force = g_lk_force_generic.load(std::memory_order_relaxed);
-    const long long tracks = (long long)max_n * batch;
-    const bool force_nw = force >= 5 && force <= 7;
-    if (force == 0 || force == 3 || (force_nw && win == 51)) {
-        if (win == 15 && force == 3) return 3;
-        if (win == 51) {
-            const int nw = force_nw ? (1 << (force - 5)) : (force == 3 ? 4 : tracks >= 640 ? 1 : 4);
-            return nw == 1 ? 5 : nw == 2 ? 6 : 7;
-        }
-    }
-    if (win == 15 && (force == 9 || ((force == 0 || force_nw) && tracks >= g_lkh_min_tracks))) return 9;
-    if (win == 15 && (force == 8 || ((force == 0 || force_nw) && tracks >= g_lko_min_tracks))) return 8;
-    if (win == 15 && (force == 4 || ((force == 0 || force_nw) && tracks >= 3000))) return 4;
-    if (force != 1 && win <= 63) return 2;  // (modes 5..7 with another window than 51: default routing); int32 per-lane partial sums are exact up to 16 strips per lane
-    return 1;
+    hipLaunchKernelGGL(kernel, dim3(p.grid_x, p.grid_y), dim3(p.block), 0, s, job_tab, tab_stride, p.group);
+    return 0;
 }
 
-const char* vh_lk_route_name(int route, int win)
-{
-    switch (route) {
-    case 1: return "k_lk";
-    case 2: return win == 15 ? "k_lk_strip<15>" : win == 51 ? "k_lk_strip<51>" : "k_lk_strip<0>";
-    case 3: return "k_lk3<15, 1, 6>";
-    case 4: return "k_lk_q<15>";
-    case 5: return "k_lk3<51, 1, 4>";
-    case 6: return "k_lk3<51, 2, 4>";
-    case 7: return "k_lk3<51, 4, 4>";
-    case 8: return "k_lk_o<15>";
-    case 9: return "k_lk_h<15>";
-    default: return "none";
-    }
-}
+// one-line forms of the plan (vh_step_plan.hpp) for vh_pyr_lk, vh_profile_lk_routes and their callers
+int vh_lk_route(int batch, int max_n, int win) { return lk_route(batch, max_n, win, vh_tuning()); }
+const char* vh_lk_route_name(int route, int win) { return lk_route_name(route, win); }
+bool vh_lk_window_fits(int win) { return lk_window_fits(win); }
+int vh_lk_max_window() { return lk_max_window(); }
 
-// Dynamic LDS of the per-sample kernel (the only one for windows above 63): the packed gradient pair (int32) and the template sample (int16) of every
-// window pixel, in whole passes of the wavefront.  A workgroup has 160 KiB, so the largest window any route can solve is 165 x 165 (166 is refused).
-// vh_pyr_lk asks vh_lk_window_fits before it enqueues anything; the other callers (vh_klt_regional, vh_klt_main, the session) still learn it from
-// vh_launch_lk's -2, after their set-up kernels are queued.
-static size_t lk_per_sample_lds(int win) { return (size_t)(((long long)win * win + 63) / 64) * 64 * 6; }
-bool vh_lk_window_fits(int win) { return win >= 1 && lk_per_sample_lds(win) <= 160 * 1024; }
-int vh_lk_max_window()
-{
-    int win = 64;
-    while (vh_lk_window_fits(win + 1)) win++;
-    return win;
-}
-
+// launches what lk_plan says: one hipLaunchKernelGGL per instantiation
 int vh_launch_lk(const void* job_tab, size_t tab_stride, int batch, int max_n, int win, hipStream_t s, int* route_out, int* tpw_out, int max_level)
 {
-    if (route_out) *route_out = 0;
-    if (tpw_out) *tpw_out = 1;
-    if (max_n <= 0) return 0;
-    const int route = vh_lk_route(batch, max_n, win);
-    if (route_out) *route_out = route;
-    switch (route) {
-    case 3: return launch_lk3<15, 1, 6>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
-    case 5: return launch_lk3<51, 1, 4>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
-    case 6: return launch_lk3<51, 2, 4>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
-    case 7: return launch_lk3<51, 4, 4>(job_tab, tab_stride, batch, max_n, max_level, s, tpw_out);
-    case 8: return launch_lko<15>(job_tab, tab_stride, batch, max_n, s);
-    case 9: return launch_lkh<15>(job_tab, tab_stride, batch, max_n, s);
-    case 4: return launch_lkq<15>(job_tab, tab_stride, batch, max_n, s);
-    case 2:
-        if (win == 15) return launch_strip<15>(job_tab, tab_stride, batch, max_n, win, s);
-        if (win == 51) return launch_strip<51>(job_tab, tab_stride, batch, max_n, win, s);
-        return launch_strip<0>(job_tab, tab_stride, batch, max_n, win, s);
-    default: break;
+    const LkPlan p = lk_plan(batch, max_n, win, max_level, vh_tuning());
+    if (route_out) *route_out = p.route;
+    if (tpw_out) *tpw_out = p.tpw;
+    if (p.rc) return p.rc;
+    switch (p.route) {
+    case LK_ROUTE_NONE: return 0;
+    case LK_ROUTE_LK3_15: return launch_lk3<15, 1, 6>(p, job_tab, tab_stride, s);
+    case LK_ROUTE_LK3_51_W1: return launch_lk3<51, 1, 4>(p, job_tab, tab_stride, s);
+    case LK_ROUTE_LK3_51_W2: return launch_lk3<51, 2, 4>(p, job_tab, tab_stride, s);
+    case LK_ROUTE_LK3_51_W4: return launch_lk3<51, 4, 4>(p, job_tab, tab_stride, s);
+    case LK_ROUTE_O: return launch_lk_group(k_lk_o<15>, p, job_tab, tab_stride, s);
+    case LK_ROUTE_H: return launch_lk_group(k_lk_h<15>, p, job_tab, tab_stride, s);
+    case LK_ROUTE_Q: return launch_lk_group(k_lk_q<15>, p, job_tab, tab_stride, s);
+    case LK_ROUTE_STRIP:
+        if (p.strip_win == 15) return launch_lk_lds(k_lk_strip<15>, p, job_tab, tab_stride, s);
+        if (p.strip_win == 51) return launch_lk_lds(k_lk_strip<51>, p, job_tab, tab_stride, s);
+        return launch_lk_lds(k_lk_strip<0>, p, job_tab, tab_stride, s);
+    case LK_ROUTE_SAMPLE: break;
     }
-    if (!vh_lk_window_fits(win)) return -2;
-    const size_t lds = lk_per_sample_lds(win);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(k_lk, dim3(max_n, batch), dim3(64), lds, s, job_tab, tab_stride);
-    return 0;
+    return launch_lk_lds(k_lk, p, job_tab, tab_stride, s);
 }

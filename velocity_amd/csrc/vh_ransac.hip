@@ -711,38 +711,36 @@ __global__ __launch_bounds__(512) void k_ransac_fused(const void* tab, size_t st
     }
 }
 
-static std::atomic<int> g_ransac_force{0};  // PROCESS-WIDE test hook (include/velocity_hip.h): 1 = always the three-kernel path, 2 = the fused kernel whenever the problem fits it
-void vh_ransac_force_path(int mode) { g_ransac_force.store(mode, std::memory_order_relaxed); }
-
+// launches what ransac_plan says (vh_step_plan.hpp); the state of the kernel's dynamic-LDS attribute is runtime state and lives here
 bool vh_launch_ransac(const void* job_tab, size_t tab_stride, int batch, int max_n, hipStream_t s, StreamWS* glue_ws, int glue)
 {
-    // up to RANSAC_FUSED_MAX pairs: one fused workgroup per stream, pairs / indices / counts resident in LDS (measured faster than the three
-    // launches at every stream count, 1 .. 256: 4.53 -> 4.48 ms per step at 128 streams); more pairs: hypotheses spread over the chip
-    const int force = g_ransac_force.load(std::memory_order_relaxed);
-    if (max_n <= RANSAC_FUSED_MAX && (force == 2 || force == 0)) {
-        const size_t lds = (size_t)RANSAC_FUSED_MAX * (16 + 4) + (size_t)VH_RANSAC_ITERS * 4;
-        // 69 KB of dynamic LDS (> the 64 KB default limit): the attribute is per function AND per device; 0 = not tried, 1 = granted, -1 = refused
-        // (three-kernel path)
-        static std::atomic<signed char> attr_state[64];
+    static_assert(RANSAC_FUSED_MAX == RANSAC_FUSED_MAX_PAIRS, "ransac_plan routes by the pairs the fused kernel holds in LDS");
+    const size_t lds = (size_t)RANSAC_FUSED_MAX * (16 + 4) + (size_t)VH_RANSAC_ITERS * 4;
+    // 69 KB of dynamic LDS (> the 64 KB default limit): the attribute is per function AND per device; 0 = not tried, 1 = granted, -1 = refused
+    // (three-kernel path)
+    static std::atomic<signed char> attr_state[64];
+    const VhTuning tuning = vh_tuning();
+    RansacPlan p = ransac_plan(max_n, glue, glue_ws != nullptr, 1, tuning);  // by size and hook alone, as if granted: the device is asked only for the fused kernel
+    if (p.fused) {
         int dev = 0;
         (void)hipGetDevice(&dev);
         dev = dev < 0 || dev >= 64 ? 0 : dev;
-        signed char st = attr_state[dev].load(std::memory_order_acquire);
-        if (st == 0) {
-            st = 1;
+        p = ransac_plan(max_n, glue, glue_ws != nullptr, attr_state[dev].load(std::memory_order_acquire), tuning);
+        if (p.try_attribute) {
+            signed char st = 1;
             for (const void* f : {reinterpret_cast<const void*>(k_ransac_fused<0>), reinterpret_cast<const void*>(k_ransac_fused<1>),
                                   reinterpret_cast<const void*>(k_ransac_fused<2>)})
                 if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) st = -1;
             if (st < 0) (void)hipGetLastError();  // refused: forget the error, the three launches below serve every size
             attr_state[dev].store(st, std::memory_order_release);
+            p = ransac_plan(max_n, glue, glue_ws != nullptr, st, tuning);
         }
-        if (st > 0) {
-            const int g = glue_ws ? glue : 0;
-            if (g == 1) hipLaunchKernelGGL(k_ransac_fused<1>, dim3(batch), dim3(512), lds, s, job_tab, tab_stride, glue_ws);
-            else if (g == 2) hipLaunchKernelGGL(k_ransac_fused<2>, dim3(batch), dim3(512), lds, s, job_tab, tab_stride, glue_ws);
-            else hipLaunchKernelGGL(k_ransac_fused<0>, dim3(batch), dim3(512), lds, s, job_tab, tab_stride, glue_ws);
-            return g != 0;
-        }
+    }
+    if (p.fused) {
+        if (p.glue == 1) hipLaunchKernelGGL(k_ransac_fused<1>, dim3(batch), dim3(512), lds, s, job_tab, tab_stride, glue_ws);
+        else if (p.glue == 2) hipLaunchKernelGGL(k_ransac_fused<2>, dim3(batch), dim3(512), lds, s, job_tab, tab_stride, glue_ws);
+        else hipLaunchKernelGGL(k_ransac_fused<0>, dim3(batch), dim3(512), lds, s, job_tab, tab_stride, glue_ws);
+        return p.glue_ran != 0;
     }
     hipLaunchKernelGGL(k_ransac_compact, dim3(batch), dim3(1024), 0, s, job_tab, tab_stride);
     hipLaunchKernelGGL(k_ransac_score, dim3((VH_RANSAC_ITERS + 3) / 4, batch), dim3(256), 0, s, job_tab, tab_stride);

@@ -548,9 +548,6 @@ __global__ void k_sess_camera(SessStream* ss, SessCamera cam)
     S.w = cam.w; S.h = cam.h; S.stride = cam.w;
 }
 
-// fcnMSV1_t (vidExample.py:155-160) can fire for this session: the predicate that both sizes its scratch and gates its launch
-static inline bool sess_msv_fires(int msv_frame, int nhist) { return msv_frame >= 1 && msv_frame + 1 <= 2048 && msv_frame < nhist; }
-
 // The device side of a session as ONE walk (sizes only when base is null): the pointer fields of the host mirror h_ss and of the session itself.
 static size_t sess_carve(char* base, vh_session* s)
 {
@@ -949,7 +946,7 @@ static int session_step(vh_session* s, const uint8_t* const* frames_dev, float t
     int r = vh_run_klt_main(c, 0, nb, st, s->coarse, s->fine, s->d_ss, frames_dev, s->N0);  // the set-up kernel also fetches this frame's KltIO from the session
     if (r) return r;
     if (s->fb.on && (r = session_recover(s, frames_dev, st))) return r;
-    if (s->N0 <= 4096) {
+    if (session_frame_plan(s->N0) == 1) {
         const int rec = vh_prof_start(s->ctx, st);
         hipLaunchKernelGGL(k_sess_frame, dim3(nb), dim3(SESS_NT), 0, st, s->d_ss, frames_dev, time_s, frame_no, times_dev, frame_nos_dev);
         vh_prof_stop(s->ctx, rec, VH_PROF_SESSION, st);
