@@ -200,6 +200,21 @@ VH_API int vh_nls_batch_windows_fixed(vh_ctx* ctx, const double* K_host, const d
                                       const double* K_win_dev, const uint8_t* fixed_dev, int max_iter, double* trace, int* info, void* workspace,
                                       size_t workspace_bytes_per_window, void* stream);
 
+/* vh_nls_batch_windows_fixed with HUBER weights on the 2-D reprojection error of a measurement pair: plain least squares gives a measurement 30 pixels
+ * off the quadratic pull of one 0.1 pixels off, and one such measurement is enough to ruin a speed.  delta_px: the threshold in pixels, finite, >= 0
+ * (anything else is refused by name before a launch is queued).  Per iteration, at the state it starts from: s2 = ru^2 + rv^2; a measurement with
+ * s2 > delta_px^2 has the weight w = delta_px / sqrt(s2), every other w = 1, and its residual pair and its 18 Jacobian entries are multiplied by
+ * sqrt(w) in k_ba_jac, so every route of the BA plan solves (J^T W J + I) delta = J^T W r (iteratively reweighted least squares: the weights are
+ * recomputed every iteration).  Unchanged: the +I damping, the 0.9 gain, the stop rule, the divisors nx and nz, "no observation" (exact zeros) and
+ * the anchors, with which it composes (an anchored point's own columns are zero, its camera columns and its residual are weighted).  trace[:, 0]
+ * stays the UNWEIGHTED rms residual, so f compares with and without the weights.  nout_dev: device int32[nwin][max_iter] or NULL: the number of
+ * measurements with s2 > delta_px^2 at the start of every iteration run (0 for the iterations that did not run).  delta_px = 0 is
+ * vh_nls_batch_windows_fixed bit for bit (nout all zero); the same workspace size serves it.  Not covered: fcnNLS_batch2, the sharded phases
+ * (vh_nls_batch_phase), the per-frame pose solve, other losses (Cauchy, Tukey), an automatic choice of delta_px. */
+VH_API int vh_nls_batch_windows_robust(vh_ctx* ctx, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
+                                       const double* K_win_dev, const uint8_t* fixed_dev, double delta_px, int* nout_dev, int max_iter, double* trace,
+                                       int* info, void* workspace, size_t workspace_bytes_per_window, void* stream);
+
 /* fcnNLS_batch2(K, P, pw, cw), utils/NLS.py:253-328: the constrained sibling -- tie points, ONE joint rotation applied to the
  * points and a straight-line camera trajectory (elevation, azimuth, one range per camera 1..nc; camera 0 at the origin).
  * Same z packing, damping (+I), step (0.9) and stop rule (rms(delta) < 1e-7); the reference runs at most 20 iterations.
@@ -581,7 +596,7 @@ VH_API int vh_session_refine_windows(vh_session* s, const vh_refine_window* wins
  *      pixels in both frames; otherwise it counts as rejected.
  * Tracks ascending; starts p3[g], the anchor or the triangulated point, each + B[first, 3:6]; everything else as vh_session_refine_windows.  The rms
  * residual f is taken over all 2 nt nf entries, the zeros of the missing ones included (as the reference forms it).  With min_obs = nf and
- * start_reproj = 0 a window is exactly vh_session_refine_windows's.  What this does NOT do: starts from more than two views, robust weights, a sparse
+ * start_reproj = 0 a window is exactly vh_session_refine_windows's.  What this does NOT do: starts from more than two views, a sparse
  * layout (the solve stays dense over nt x nf: a missing measurement costs what an observed one costs), points shared between windows. */
 typedef struct {
     int min_obs;          /* 2 <= min_obs <= nf */
@@ -604,6 +619,21 @@ VH_API size_t vh_session_refine_windows_partial_workspace(const vh_session* s, i
 VH_API int vh_session_refine_windows_partial(vh_session* s, const vh_refine_window* wins_host, int nwin, int nf, int max_iter, int with_points,
                                              const vh_refine_partial_params* params_host, void* recs_dev, void* workspace, size_t workspace_bytes,
                                              void* stream);
+
+/* Huber weights for every refinement of the session (default OFF; vh_version stays: a consumer tests for the symbol).  A session setting, like the
+ * anchors and the replenishment's parameters: delta_px pixels, finite and >= 0, 0 = off; nothing is queued.  While it is non-zero,
+ * vh_session_refine, vh_session_refine_windows and vh_session_refine_windows_partial solve their windows through vh_nls_batch_windows_robust -- partial
+ * tracks, replenished rows, two-view starts and recovered motions are where a wrong measurement is most likely, and one is enough to ruin a speed -- and
+ * each of their records grows by a 16-byte tail at the offset that was its `bytes`:
+ *     int32 nout_first   measurements with s2 > delta_px^2 at iteration 0
+ *     int32 nout_last    ... at the last iteration run (both 0 for a window that was not solved)
+ *     float32 delta      the threshold
+ *     int32 0
+ * and the three *_size queries report the larger `bytes` (no offset of the layouts moves; the four counts of a partial record stay where they are,
+ * in front of the tail).  f_first, f_last and the trace stay the UNWEIGHTED rms residual.  With the setting at 0 every record is byte for byte what it
+ * is without this call.  Not covered: the per-frame pose solve, other losses (Cauchy, Tukey), an automatic choice of delta_px.  Returns -1 with
+ * vh_last_error naming the value, and the setting unchanged, for a negative or non-finite delta_px. */
+VH_API int vh_session_set_refine_robust(vh_session* s, double delta_px);
 VH_API int vh_session_ptrs(vh_session* s, int slot, vh_session_view* out_host);
 /* (vh_version >= 109) the recovery branch of KLTmain (utils/KLT.py:130-133) inside the session; default OFF: a step then queues exactly the launches it
  * always did and a stream whose coarse stage fails reports klt_flags & 1 and goes on with what the blind fine stage kept.

@@ -17,9 +17,10 @@ def _scratch(torch, shape):
     return t
 
 
-def _ba_solve(fn, K_host, z, x0, nt, nc, max_iter, nw=None, extra=()):
+def _ba_solve(fn, K_host, z, x0, nt, nc, max_iter, nw=None, extra=(), robust=None):
     """The device part of every fcnNLS_batch* shim: upload z and x0, allocate trace / info / workspace (one of each per window when nw is given), call
-    the entry point `fn` (its arguments between nc and max_iter: `extra`), read back -> info, x, trace as numpy arrays."""
+    the entry point `fn` (its arguments between nc and max_iter: `extra`), read back -> info, x, trace as numpy arrays.  robust = delta (pixels): `fn` is
+    vh_nls_batch_windows_robust, `extra` gains delta and the count table, and the counts [nw, max_iter] come back as a fourth array."""
     torch = L.torch_cuda()
     lead = () if nw is None else (nw,)
     zd = L.to_dev(z, torch.float64)
@@ -29,9 +30,25 @@ def _ba_solve(fn, K_host, z, x0, nt, nc, max_iter, nw=None, extra=()):
     ws = L.workspace()
     nbytes = int(ws.lib.vh_nls_batch_workspace(nt, nc))
     scratch = _scratch(torch, lead + (nbytes,))
+    nout = None
+    if robust is not None:
+        nout = torch.zeros(lead + (max_iter,), dtype=torch.int32, device="cuda")
+        extra = tuple(extra) + (float(robust), L.dptr(nout))
     L.check(getattr(ws.lib, fn)(ws.handle, K_host.ctypes.data_as(L.f64p), L.dptr(zd), L.dptr(xd), nt, nc, *extra, int(max_iter), L.dptr(trace), L.dptr(info),
                                 L.dptr(scratch), nbytes, L.stream_ptr()), fn)
+    if nout is not None:
+        return info.cpu().numpy(), xd.cpu().numpy(), trace.cpu().numpy(), nout.cpu().numpy()
     return info.cpu().numpy(), xd.cpu().numpy(), trace.cpu().numpy()
+
+
+def _robust_delta(robust, who):
+    """The Huber threshold of a shim: None (off) or a finite number of pixels >= 0 (0: off as well, through the robust entry point)."""
+    if robust is None:
+        return None
+    d = float(robust)
+    if not (np.isfinite(d) and d >= 0.0):
+        raise ValueError(f"{who}: robust = {robust} must be a finite number of pixels >= 0")
+    return d
 
 
 def _pose(K, p, pw, x0, R, findR, want_proj=True):
@@ -112,7 +129,7 @@ def _track_filter(P, min_obs, who):
     return seen.sum(1) >= int(min_obs), np.where(seen[None], P[0:2].astype(np.float64), np.nan)
 
 
-def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None, min_obs=None):
+def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None, min_obs=None, robust=None):
     """Dense full bundle adjustment over tie points and cameras 1..nc (utils/NLS.py:186-250) -> (cw [nc+1,3], pw [nt,3]).
 
     The track filter, the measurement ordering and the state layout are the reference's (NLS.py:190-203); the
@@ -124,6 +141,10 @@ def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None, min_o
 
     min_obs: None (the reference's filter: alive in every frame), or M with 2 <= M <= nf: the tracks observed in at least M frames take part, a missing
     measurement being no observation (the windows entry takes it; the rms residual still runs over all 2 nt nf entries, as the reference forms it).
+
+    robust: None (plain least squares, the reference's), or the Huber threshold delta in pixels: per iteration a measurement pair whose reprojection error
+    |r| exceeds delta is weighted by delta / |r| (vh_nls_batch_windows_robust; f stays the unweighted rms residual).  With return_info the counts of
+    down-weighted measurements per iteration run follow the trace.
     """
     P = np.asarray(P)
     pw = np.asarray(pw, np.float64)
@@ -136,7 +157,13 @@ def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None, min_o
     nc = nf - 1
     z = np.concatenate([uv[0].T.reshape(-1), uv[1].T.reshape(-1)])  # NLS.py:198-199
     x0 = np.concatenate((pw, cw[1:], np.zeros((nc, 3)))).reshape(-1)  # NLS.py:202-203
-    if fixed is None and min_obs is None:
+    robust = _robust_delta(robust, "fcnNLS_batch")
+    nout = None
+    if robust is not None:  # one window of the robust entry: the launches of the windows entry with the weighted k_ba_jac
+        fd = None if fixed is None else L.to_dev(fixed.astype(np.uint8), L.torch_cuda().uint8)
+        info, x, tr, nout = (a[0] for a in _ba_solve("vh_nls_batch_windows_robust", L.host_K(K), z[None], x0[None], nt, nc, max_iter, 1,
+                                                     (1, L.dptr(None), L.dptr(None), L.dptr(fd)), robust=robust))
+    elif fixed is None and min_obs is None:
         info, x, tr = _ba_solve("vh_nls_batch", L.host_K(K), z, x0, nt, nc, max_iter)
     elif fixed is None:  # one window of the windows entry, which takes missing measurements
         info, x, tr = (a[0] for a in _ba_solve("vh_nls_batch_windows", L.host_K(K), z[None], x0[None], nt, nc, max_iter, 1, (1, L.dptr(None), L.dptr(None))))
@@ -152,7 +179,7 @@ def fcnNLS_batch(K, P, pw, cw, max_iter=10, return_info=False, fixed=None, min_o
     pw_out = x[:j].reshape(nt, 3)
     cw_out = np.concatenate((np.zeros((1, 3)), x[j : j + nc * 3].reshape(nc, 3)), 0)
     if return_info:
-        return cw_out, pw_out, x, tr
+        return (cw_out, pw_out, x, tr) if nout is None else (cw_out, pw_out, x, tr, nout[: info[0]])
     return cw_out, pw_out
 
 
@@ -203,7 +230,7 @@ def pack_windows(Ps, pws, cws, fixed=None, min_obs=None):
     return z.reshape(nw, -1), x0, counts, nt, nc, fx
 
 
-def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=None, min_obs=None):
+def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=None, min_obs=None, robust=None):
     """fcnNLS_batch (utils/NLS.py:186-250) for several independent windows of the same number of frames (one finished clip or sliding window per
     video stream) in one launch sequence (grid.y = window).  Ps / pws / cws: sequences of the reference's P, pw, cw arguments.  K: one 3x3 matrix
     for all windows, or one per window ([nw, 3, 3]).  The windows may keep different numbers of full-length tracks: pack_windows lays them out for
@@ -211,7 +238,8 @@ def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=
     go through vh_nls_batch_multi unchanged.  A window without a full-length track is not solved (cw comes back as given).  Returns
     [(cw, pw), ...], pw cut to the window's own tracks (with return_info: also the padded x and the trace).  fixed: None, or a list of bool masks, one per
     window over the rows of its pw (see fcnNLS_batch; None inside the list: that window is solved free).  min_obs: None, or the least number of
-    observed frames of a kept track (see fcnNLS_batch); such windows go through vh_nls_batch_windows(_fixed)."""
+    observed frames of a kept track (see fcnNLS_batch); such windows go through vh_nls_batch_windows(_fixed).  robust: None, or the Huber threshold in
+    pixels for every window (see fcnNLS_batch; vh_nls_batch_windows_robust); with return_info each window's tuple then ends with its counts."""
     torch = L.torch_cuda()
     fx = None
     if fixed is None:
@@ -224,7 +252,13 @@ def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=
     if per_window_K and len(K64) != nw:
         raise ValueError(f"fcnNLS_batch_windows: {len(K64)} intrinsics for {nw} windows")
     K_host = L.host_K(K64[0] if per_window_K else K64)
-    if fx is not None:
+    robust = _robust_delta(robust, "fcnNLS_batch_windows")
+    nout = None
+    if robust is not None:
+        ntd, fd = L.to_dev(counts, torch.int32), (None if fx is None else L.to_dev(fx, torch.uint8))
+        Kd = L.to_dev(K64.reshape(nw, 9), torch.float64) if per_window_K else None
+        info, x, tr, nout = _ba_solve("vh_nls_batch_windows_robust", K_host, z, x0, nt, nc, max_iter, nw, (nw, L.dptr(ntd), L.dptr(Kd), L.dptr(fd)), robust=robust)
+    elif fx is not None:
         ntd, fd = L.to_dev(counts, torch.int32), L.to_dev(fx, torch.uint8)
         Kd = L.to_dev(K64.reshape(nw, 9), torch.float64) if per_window_K else None
         info, x, tr = _ba_solve("vh_nls_batch_windows_fixed", K_host, z, x0, nt, nc, max_iter, nw, (nw, L.dptr(ntd), L.dptr(Kd), L.dptr(fd)))
@@ -241,7 +275,8 @@ def fcnNLS_batch_windows(K, Ps, pws, cws, max_iter=10, return_info=False, fixed=
         j = nt * 3
         pw_out = x[w, : 3 * counts[w]].reshape(-1, 3)
         cw_out = np.concatenate((np.zeros((1, 3)), x[w, j : j + nc * 3].reshape(nc, 3)), 0)
-        out.append((cw_out, pw_out, x[w], tr[w, : info[w, 0]]) if return_info else (cw_out, pw_out))
+        rec = (cw_out, pw_out, x[w], tr[w, : info[w, 0]]) + (() if nout is None else (nout[w, : info[w, 0]],))
+        out.append(rec if return_info else (cw_out, pw_out))
     return out
 
 

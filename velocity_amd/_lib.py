@@ -144,6 +144,7 @@ _SIGS = {
     "vh_nls_batch_multi": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_nls_batch_windows": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_nls_batch_windows_fixed": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
+    "vh_nls_batch_windows_robust": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_double, vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_nls_batch2": (C.c_int, [vp, f64p, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "vh_good_features": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, vp, vp, vp]),
     "vh_corner_subpix": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp]),
@@ -169,6 +170,7 @@ _SIGS = {
     "vh_session_refine_windows_partial": (C.c_int, [vp, C.POINTER(RefineWindow), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(RefinePartialParams), vp, vp,
                                                     C.c_size_t, vp]),
     "vh_session_set_anchors": (C.c_int, [vp, C.c_int, i32p, C.c_int, f64p, vp]),
+    "vh_session_set_refine_robust": (C.c_int, [vp, C.c_double]),
     "vh_session_anchors": (C.c_int, [vp, C.c_int, i32p, f64p]),
     "vh_session_ptrs": (C.c_int, [vp, C.c_int, C.POINTER(SessionView)]),
     "vh_session_pack_state": (C.c_int, [vp, vp, vp]),

@@ -4,6 +4,7 @@
 // every image / track kernel is launched over the maximum extent and reads its extent from there.  A frame is thus a
 // fixed sequence of launches with no host round trip (hipGraph-capturable), for any number of streams per launch.
 #include <atomic>
+#include <cmath>
 #include <vector>
 #include <stdio.h>
 #include <stdlib.h>
@@ -960,7 +961,11 @@ static int ba_problem(BaProblem& P, vh_ctx* c, const char* fn, const double* K_h
 }
 static int ba_run_checked(const BaProblem& P, vh_ctx* c, void* stream)
 {
-    int r = vh_ba_run(P, vh_ctx_bind(c, stream));
+    vh_ctx_bind bound(c, stream);
+    // the per-iteration counts of a robust solve: iterations that do not run (a converged or an empty window) report 0
+    if (P.nout && hipMemset2DAsync(P.nout, sizeof(int) * P.nout_stride, 0, sizeof(int) * (size_t)P.max_iter, (size_t)P.nwin, bound) != hipSuccess)
+        return vh_fail(-1, "vh_nls_batch_windows_robust: clearing nout failed");
+    int r = vh_ba_run(P, bound);
     if (r) return vh_fail(r, "vh_ba_run failed");
     return 0;
 }
@@ -1000,10 +1005,27 @@ extern "C" VH_API int vh_nls_batch_windows_fixed(vh_ctx* c, const double* K_host
                          workspace, workspace_bytes_per_window, stream);
 }
 
+// ... with Huber weights of threshold delta_px pixels on the reprojection error of a measurement pair (vh_ba.hpp); nout_dev: int32 [nwin][max_iter], may be
+// NULL, cleared here and then filled per iteration run.  delta_px = 0 is vh_nls_batch_windows_fixed: the same launches, the same bytes
+extern "C" VH_API int vh_nls_batch_windows_robust(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
+                                                  const double* K_win_dev, const uint8_t* fixed_dev, double delta_px, int* nout_dev, int max_iter, double* trace,
+                                                  int* info, void* workspace, size_t workspace_bytes_per_window, void* stream)
+{
+    if (!(delta_px >= 0.0) || !std::isfinite(delta_px)) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "vh_nls_batch_windows_robust: delta_px = %g must be finite and >= 0 (0 = off)", delta_px);
+        return vh_fail(-1, msg);
+    }
+    return vh_ba_windows(c, K_host, z, x, nt, nc, nwin, nt_win_dev, K_win_dev, fixed_dev, max_iter, trace, (size_t)2 * (max_iter > 0 ? max_iter : 0), info, 2,
+                         workspace, workspace_bytes_per_window, stream, delta_px, nout_dev, (size_t)(max_iter > 0 ? max_iter : 0));
+}
+
+const int* vh_ba_windows_outlier_words(int nt, int nc, int nwin, void* workspace) { return vh_ba_outlier_words(nt, nc, ba_parts(nt, nc, nwin), workspace); }
+
 // ... with the windows' trace / info records trace_stride doubles / info_stride ints apart (vh_session_refine writes them straight into its records)
 int vh_ba_windows(vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev, const double* K_win_dev,
                   const uint8_t* fixed_dev, int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride, void* workspace, size_t workspace_bytes_per_window,
-                  void* stream)
+                  void* stream, double delta_px, int* nout, size_t nout_stride)
 {
     if (nwin < 1 || nwin > 65535) return vh_fail(-1, "vh_nls_batch_multi: bad arguments");
     BaProblem P;
@@ -1015,6 +1037,7 @@ int vh_ba_windows(vh_ctx* c, const double* K_host, const double* z, double* x, i
     P.nparts = ba_parts(nt, nc, nwin);
     P.nwin = nwin; P.ws_stride = workspace_bytes_per_window; P.z_stride = (size_t)2 * nt * (nc + 1); P.x_stride = (size_t)3 * nt + 6 * (size_t)nc;
     P.trace_stride = trace_stride; P.info_stride = info_stride;
+    P.delta = delta_px; P.nout = nout; P.nout_stride = nout_stride;
     return ba_run_checked(P, c, stream);
 }
 

@@ -143,13 +143,18 @@ __global__ void k_ba_cams(BaJob J)
 
 __device__ void inv3_sym(const double* U, double* Ui);
 
+// the window's count of down-weighted measurements of the running iteration (Huber weights, vh_ba.hpp): an int in the free tail of the flag block
+// (vh_ba_plan.hpp), zeroed by k_ba_init; the two ints behind it keep the counts of iteration 0 and of the last iteration run (BA_OUTLIER_WORD)
+__device__ __forceinline__ int* ba_outlier_counter(const BaJob& J) { return J.done + BA_OUTLIER_WORD; }
+
 // residual and compact forward-difference Jacobian of every measurement pair (camera c, track i).
 // A thread owns one measurement (20 doubles of output: r 2, Jp 6, Jc 12).  Written straight from the registers, a wave's store touched 64
 // separate 16 / 48 / 96-byte records per instruction; the values are transposed through LDS instead and leave as fully coalesced streams
 // (the block's measurements are contiguous in all three arrays).  A block owns WHOLE points (256 / (nc+1) of them, the last threads idle), so
 // with PREP it also finishes what the point-block Schur complement needs per point -- U_i + I, its inverse, tp_i, the Cholesky factor of the
 // inverse -- straight from the LDS copy of the rows: the separate pass re-read 8 of the 20 planes from HBM (0.8 GB per iteration at 64 C5 windows).
-template <bool PREP>
+// ROBUST: Huber weights (vh_ba.hpp) -- a measurement whose squared error exceeds delta^2 leaves scaled by sqrt(delta / |r|), and is counted.
+template <bool PREP, bool ROBUST = false>
 __global__ __launch_bounds__(BA_THREADS) void k_ba_jac(BaJob J)
 {
     ba_select_window(J, blockIdx.y);
@@ -245,6 +250,24 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_jac(BaJob J)
     if (anchored) {
 #pragma unroll
         for (int k = 2; k < 8; k++) o[k] = 0.0;
+    }
+    if constexpr (ROBUST) {
+        // ss is the measurement's own s2 here (0 for an idle lane or no observation): the sum below stays the unweighted one
+        const bool down = ss > J.delta * J.delta;
+        if (down) {
+            const double sw = sqrt(J.delta / sqrt(ss));
+#pragma unroll
+            for (int k = 0; k < 20; k++) o[k] *= sw;
+        }
+        __shared__ int s_down[BA_THREADS / 64];
+        const int nd = __popcll(__ballot(down));
+        if ((threadIdx.x & 63) == 0) s_down[threadIdx.x >> 6] = nd;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int t = 0;
+            for (int k = 0; k < BA_THREADS / 64; k++) t += s_down[k];
+            if (t) atomicAdd(ba_outlier_counter(J), t);
+        }
     }
 #pragma unroll
     for (int k = 0; k < 20; k++) s_out[k][threadIdx.x] = o[k];
@@ -1691,6 +1714,17 @@ __device__ __forceinline__ void ba_window_sizes(const BaJob& J, int w, double& n
     nx = 3.0 * n + 6.0 * J.nc; nz = 2.0 * n * (J.nc + 1);
 }
 
+// k_ba_jac<*, true> of this iteration (an earlier launch) left the window's count of down-weighted measurements in the flag block: it belongs to iteration `it`
+__device__ __forceinline__ void ba_record_outliers(const BaJob& J, int w, int it)
+{
+    int* cnt = ba_outlier_counter(J);
+    const int n = *cnt;
+    if (J.nout) J.nout[(size_t)w * J.nout_stride + it] = n;
+    if (it == 0) cnt[1] = n;
+    cnt[2] = n;
+    *cnt = 0;
+}
+
 // tail of the update kernels (all of them launched with blockIdx.y = window): block 0 moves the cameras (and builds the rotation / offset tables of the next iteration from the LDS copy of the new
 // parameters -- saves a launch per iteration); every block adds its sum of squared steps, the last one finishes the iteration record
 template <int NT>
@@ -1732,6 +1766,7 @@ __device__ __forceinline__ void ba_update_tail(BaJob& J, int it, double ss, doub
             J.trace[2 * it] = f;
             J.trace[2 * it + 1] = xr;
             J.info[0] = it + 1;
+            if (J.delta > 0.0) ba_record_outliers(J, blockIdx.y, it);
             if (xr < 1e-7) { J.info[1] = 1; *J.done = 1; }
             J.acc[0] = 0.0; J.acc[1] = 0.0;
             *J.ticket = 0u;
@@ -1884,6 +1919,7 @@ __global__ void k_ba_finalize(BaJob J, int it)
     J.trace[2 * it] = f;
     J.trace[2 * it + 1] = xr;
     J.info[0] = it + 1;
+    if (J.delta > 0.0) ba_record_outliers(J, blockIdx.y, it);
     if (xr < 1e-7) { J.info[1] = 1; *J.done = 1; }
     J.acc[0] = 0.0; J.acc[1] = 0.0;
 }
@@ -1972,8 +2008,17 @@ static void ba_layout(const BaProblem& P, BaJob& J)
     J.nx_total = P.nx_total; J.nz_total = P.nz_total;
     J.nwin = P.nwin < 1 ? 1 : P.nwin;
     J.nt_win = P.nt_win; J.K_win = P.K_win; J.fixed = P.fixed;
+    J.delta = P.delta; J.nout = P.delta > 0 ? P.nout : nullptr; J.nout_stride = P.delta > 0 ? P.nout_stride : 0;
     J.ws_stride = P.ws_stride; J.z_stride = P.z_stride; J.x_stride = P.x_stride; J.trace_stride = P.trace_stride; J.info_stride = P.info_stride;
     ba_workspace_walk(P.nt, P.nc, P.nparts, P.workspace, &J);
+}
+
+// where window 0 keeps {running count, count at iteration 0, count at the last iteration run} of a robust solve (see vh_ba.hpp)
+const int* vh_ba_outlier_words(int nt, int nc, int nparts, void* workspace)
+{
+    BaFields f;
+    ba_workspace_walk(nt, nc, nparts, workspace, &f);
+    return f.done + BA_OUTLIER_WORD;
 }
 
 // byte offset / length (in doubles) of the all-reduce span [Sfull | acc] inside the workspace
@@ -2038,8 +2083,12 @@ int vh_ba_run(const BaProblem& P, hipStream_t s)
         if (it == 0) hipLaunchKernelGGL(k_ba_cams, dim3((nc + 1 + 63) / 64, nw), dim3(64), 0, s, J);
         const int ppb = BA_THREADS / (nc + 1);  // k_ba_jac: whole points per block
         int rec = vh_prof_start(pc, s);
-        if (plan.zmode) hipLaunchKernelGGL(k_ba_jac<true>, dim3((nt + ppb - 1) / ppb, nw), dim3(BA_THREADS), 0, s, J);
-        else hipLaunchKernelGGL(k_ba_jac<false>, dim3((nt + ppb - 1) / ppb, nw), dim3(BA_THREADS), 0, s, J);
+        const dim3 jgrid((nt + ppb - 1) / ppb, nw);
+        if (J.delta > 0) {  // Huber weights: the robust instances, which the plain solves never launch
+            if (plan.zmode) hipLaunchKernelGGL((k_ba_jac<true, true>), jgrid, dim3(BA_THREADS), 0, s, J);
+            else hipLaunchKernelGGL((k_ba_jac<false, true>), jgrid, dim3(BA_THREADS), 0, s, J);
+        } else if (plan.zmode) hipLaunchKernelGGL(k_ba_jac<true>, jgrid, dim3(BA_THREADS), 0, s, J);
+        else hipLaunchKernelGGL(k_ba_jac<false>, jgrid, dim3(BA_THREADS), 0, s, J);
         vh_prof_stop(pc, rec, VH_PROF_BA_JAC, s);
         rec = vh_prof_start(pc, s);
         switch (plan.schur) {

@@ -48,6 +48,14 @@ struct BaJob {  // passed by value to every BA kernel
     // tp_i = 0, W_i = 0: it takes no step and subtracts nothing from the reduced system, while its measurements still add Jc^T Jc and Jc^T r to its
     // cameras.  It still counts as rows of x (nx, nz are unchanged).  Null = no anchors
     const uint8_t* fixed;            // [nwin][nt] non-zero = anchored
+    // Huber weights (vh_nls_batch_windows_robust): a measurement pair whose reprojection error at the start of the iteration has s2 = ru^2 + rv^2 > delta^2
+    // gets w = delta / sqrt(s2), and k_ba_jac<*, true> scales its residual pair and its 18 Jacobian entries by sqrt(w) -- after the NaN and anchor rules, before
+    // anything else reads them, so J^T W J and J^T W r follow on every route of the plan (IRLS: the weights are those of the current state).  The rms residual of
+    // the trace stays the unweighted one.  The block counts of down-weighted measurements meet in the int at double 24 of the window's flag block
+    // (ba_outlier_counter); the kernel that writes the iteration record moves the sum to nout[it] and clears it.  delta = 0: off, the plain kernels run
+    double delta;                    // pixels, >= 0
+    int* nout;                       // [nwin][nout_stride] down-weighted measurements at the start of every iteration (may be null)
+    size_t nout_stride;              // ints
 };
 
 struct BaProblem {  // every field defaults to zero / null: an entry point sets what it uses (ba_problem in vh_api.hip fills the single-window defaults)
@@ -68,15 +76,27 @@ struct BaProblem {  // every field defaults to zero / null: an entry point sets 
     const int* nt_win = nullptr;  // see BaJob (device, may be null)
     const double* K_win = nullptr;
     const uint8_t* fixed = nullptr;
+    double delta = 0;        // see BaJob (0 = plain least squares)
+    int* nout = nullptr;
+    size_t nout_stride = 0;
     struct vh_ctx* ctx = nullptr;  // may be null: per-kernel HIP-event timing when its profiling is on (vh_profile_begin)
     void** graph_cache = nullptr;  // may be null: where the owner (vh_ctx) keeps the replayable launch sequences of whole solves (vh_ba_graph_cache_free)
 };
 void vh_ba_graph_cache_free(void* cache);
 
+// A robust solve (delta > 0) leaves three ints in each window's workspace, at int BA_OUTLIER_WORD of its flag block: the running count of down-weighted
+// measurements (0 between iterations), the count at iteration 0 and the count at the last iteration run (0, 0 when none ran: k_ba_init clears the block).
+// vh_ba_outlier_words: their address in window 0's workspace (later windows: the workspace stride further)
+#define BA_OUTLIER_WORD 48
+const int* vh_ba_outlier_words(int nt, int nc, int nparts, void* workspace);
+// ... of the windows of a vh_ba_windows call (vh_api.hip: it knows the partial systems such a call uses)
+const int* vh_ba_windows_outlier_words(int nt, int nc, int nwin, void* workspace);
+
 size_t vh_ba_workspace_bytes(int nt, int nc, int nparts);
 int vh_ba_run(const BaProblem& P, hipStream_t s);
 void vh_ba_exchange_span(const BaProblem& P, size_t* offset_bytes, size_t* n_doubles);
 // vh_nls_batch_windows_fixed (include/velocity_hip.h) with the caller's own distances between the windows' trace (doubles) and info (ints) records (vh_api.hip)
+// delta_px > 0: Huber weights, and nout (device, may be null) receives the per-iteration counts, nout_stride ints between windows
 int vh_ba_windows(struct vh_ctx* c, const double* K_host, const double* z, double* x, int nt, int nc, int nwin, const int* nt_win_dev,
                   const double* K_win_dev, const uint8_t* fixed_dev, int max_iter, double* trace, size_t trace_stride, int* info, size_t info_stride,
-                  void* workspace, size_t workspace_bytes_per_window, void* stream);
+                  void* workspace, size_t workspace_bytes_per_window, void* stream, double delta_px = 0.0, int* nout = nullptr, size_t nout_stride = 0);

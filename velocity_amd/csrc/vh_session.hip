@@ -84,6 +84,7 @@ struct vh_session {
     double* d_anc_xyz;    // [batch][N0][3] its coordinates, in the frame of the clip's camera 0 (rows of unanchored ids: undefined)
     int* h_nanchor;       // per slot: anchors set (host)
     char* h_inited;       // per slot: vh_session_init has run
+    double refine_robust; // Huber threshold (pixels) of every refinement (vh_session_set_refine_robust); 0 = off: plain least squares
 };
 
 #define SESS_CHECK() VH_CHECK(hipGetLastError())
@@ -1160,6 +1161,19 @@ extern "C" VH_API int vh_session_anchors(vh_session* s, int slot, int* ids_host,
 }
 
 // ---- bundle adjustment of frame windows of the slots' clips (vidExample.py:157, NLS.py:186-250) -----------------------------------------------------------
+// Huber weights for every refinement of the session (vh_nls_batch_windows_robust): a host setting like the anchors' count -- nothing is queued
+extern "C" VH_API int vh_session_set_refine_robust(vh_session* s, double delta_px)
+{
+    if (!s) return vh_fail(-1, "vh_session_set_refine_robust: null session");
+    if (!(delta_px >= 0.0) || !std::isfinite(delta_px)) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "vh_session_set_refine_robust: delta_px = %g must be finite and >= 0 (0 = off)", delta_px);
+        return vh_fail(-1, msg);
+    }
+    s->refine_robust = delta_px;
+    return 0;
+}
+
 // ONE request path behind both entries: window (slot, first) = frames [first, first + nf) of the slot's clip; vh_session_refine asks for the window
 // first = 0 of clips that have just ended, vh_session_refine_windows for any.  pack: the window's tracks, their history, world points, per-frame
 // translations and camera -> window w of one vh_nls_batch_windows problem laid out for N0 tracks; unpack: the refined state and the speed derived from it
@@ -1192,11 +1206,13 @@ struct RefView {
     int head_words;   // int32 words from `head` on: 4 {nt, iterations, converged, nfix} | 6 {slot, first, nt, iterations, converged, nfix}
     int max_iter;
     int with_points;  // ids and pw are in the record
+    size_t tail;      // bytes behind everything else: 16 while the session refines with Huber weights (SESS_ROBUST_TAIL), else 0
 };
-// (table + workspace + view + the other arguments of the pack kernels, the partial one's parameters included: 2344 bytes of the 4 KB a launch may carry)
-static_assert(sizeof(RefReq) + sizeof(RefWs) + sizeof(RefView) + 6 * sizeof(void*) + sizeof(RefPart) == 2344, "the refinement request travels in the kernel arguments");
+// (table + workspace + view + the other arguments of the pack kernels, the partial one's parameters included: 2352 bytes of the 4 KB a launch may carry)
+static_assert(sizeof(RefReq) + sizeof(RefWs) + sizeof(RefView) + 6 * sizeof(void*) + sizeof(RefPart) == 2352, "the refinement request travels in the kernel arguments");
 
-static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_record* L)
+#define SESS_ROBUST_TAIL 16  // {int32 nout_first, int32 nout_last, float32 delta, int32 0} behind a record refined with Huber weights (robust: the threshold, 0 = none)
+static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_record* L, double robust)
 {
     size_t off = 0;
     auto put = [&](size_t bytes) { const size_t o = off; off = vh_align_up(off + bytes, 8); return o; };
@@ -1208,11 +1224,11 @@ static void refine_record_layout(int N0, int nhist, int max_iter, vh_refine_reco
     L->dr = put(sizeof(double) * (size_t)nhist); L->speed = put(sizeof(double) * (size_t)nhist);
     L->speed_mean = put(sizeof(double)); L->speed_std = put(sizeof(double)); L->f_first = put(sizeof(double)); L->f_last = put(sizeof(double));
     L->trace = put(sizeof(double) * 2 * (size_t)max_iter);
-    L->bytes = off;
+    L->bytes = off + (robust > 0 ? SESS_ROBUST_TAIL : 0);
     L->n0 = N0; L->nhist = nhist; L->max_iter = max_iter;
 }
 
-static void refine_window_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_window_record* L)
+static void refine_window_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_window_record* L, double robust)
 {
     size_t off = 0;
     auto put = [&](size_t bytes) { const size_t o = off; off = vh_align_up(off + bytes, 8); return o; };
@@ -1225,23 +1241,24 @@ static void refine_window_record_layout(int N0, int nf, int max_iter, int with_p
     L->trace = put(sizeof(double) * 2 * (size_t)max_iter);
     L->ids = with_points ? put(sizeof(int) * (size_t)N0) : 0;
     L->pw = with_points ? put(sizeof(double) * 3 * (size_t)N0) : 0;
-    L->bytes = off;
+    L->bytes = off + (robust > 0 ? SESS_ROBUST_TAIL : 0);
     L->n0 = N0; L->nf = nf; L->max_iter = max_iter; L->with_points = with_points ? 1 : 0;
 }
 
-// a partial window's record: the window record, then the four counts (the shared fields keep the window record's offsets)
-static void refine_partial_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_partial_record* L)
+// a partial window's record: the window record, then the four counts (the shared fields keep the window record's offsets), then the robust tail
+static void refine_partial_record_layout(int N0, int nf, int max_iter, int with_points, vh_refine_partial_record* L, double robust)
 {
-    refine_window_record_layout(N0, nf, max_iter, with_points, &L->win);
+    refine_window_record_layout(N0, nf, max_iter, with_points, &L->win, 0.0);
     L->nobs = L->win.bytes; L->npart = L->nobs + 4; L->ntri = L->nobs + 8; L->nrej = L->nobs + 12;
-    L->win.bytes += 4 * sizeof(int);
+    L->win.bytes += 4 * sizeof(int) + (robust > 0 ? SESS_ROBUST_TAIL : 0);
 }
 
 // the kernels' view of a public layout (the functions above stay the one source of every offset): head = the record's first header word
 template <class Layout>
-static RefView refine_view(const Layout& L, size_t head, int rows, int with_points)
+static RefView refine_view(const Layout& L, size_t head, int rows, int with_points, double robust)
 {
     RefView V;
+    V.tail = robust > 0 ? SESS_ROBUST_TAIL : 0;
     V.bytes = L.bytes; V.head = head; V.nt = L.nt; V.info = L.iterations; V.nfix = L.nfix; V.ids = L.ids; V.pw = L.pw; V.cw = L.cw; V.dr = L.dr;
     V.speed = L.speed; V.speed_mean = L.speed_mean; V.speed_std = L.speed_std; V.f_first = L.f_first; V.f_last = L.f_last; V.trace = L.trace;
     V.rows = rows; V.head_words = (int)((L.nfix - head) / sizeof(int)) + 1; V.max_iter = L.max_iter; V.with_points = with_points;
@@ -1453,7 +1470,7 @@ __global__ __launch_bounds__(256) void k_refine_pack(const SessStream* ss_all, R
 //      projection, written only while g is a pose track) is finite in some frame up to the slot's counter;
 //   C  (start_reproj > 0) neither: the start is triangulated from the first and the last observed frame of the window by sess_triangulate, origins
 //      float32(B[0, 0:3] - B[f, 0:3]) widened (MSV.py:18), and the track is admitted iff it passes that gate; the point goes to W.tri_xyz.
-// The four counts go straight into the record (V.bytes - 16 on: vh_refine_partial_record).
+// The four counts go straight into the record (the 16 bytes in front of its tail: vh_refine_partial_record).
 __global__ __launch_bounds__(256) void k_refine_pack_partial(const SessStream* ss_all, RefReq rq, int w0, int nf, RefWs W, RefView V, char* recs,
                                                              const uint8_t* anc_mask, const double* anc_xyz, const SessRepl* rp_all, RefPart Q)
 {
@@ -1513,7 +1530,7 @@ __global__ __launch_bounds__(256) void k_refine_pack_partial(const SessStream* s
     if (ntri) atomicAdd(&s_tot[2], ntri);
     if (nrej) atomicAdd(&s_tot[3], nrej);
     __syncthreads();  // (also: the ids, tm and tx written above are visible to the whole workgroup)
-    if (tid < 4) reinterpret_cast<int*>(recs + (size_t)w * V.bytes + V.bytes - 16)[tid] = s_tot[tid];
+    if (tid < 4) reinterpret_cast<int*>(recs + (size_t)w * V.bytes + V.bytes - V.tail - 16)[tid] = s_tot[tid];
     refine_pack_rest(S, sel, s_base, slot, first, w, nf, W, V, recs, anc_mask, anc_xyz, tid, tm, tx);
 }
 
@@ -1532,6 +1549,19 @@ __global__ __launch_bounds__(256) void k_refine_unpack(const SessStream* ss_all,
     o.f_first = reinterpret_cast<double*>(rec + V.f_first); o.f_last = reinterpret_cast<double*>(rec + V.f_last);
     o.trace = reinterpret_cast<const double*>(rec + V.trace); o.rows = V.rows; o.max_iter = V.max_iter;
     refine_unpack_window(S, W.ids ? W.ids + (size_t)w * S.N0 : S.ids, W.nt[w], rq.first[blockIdx.x], nf, W.x + (size_t)w * W.x_stride, o, s_speed, tid);
+}
+
+// the tail of the records of a request refined with Huber weights: the solve left {count at iteration 0, count at the last iteration run} in each window's
+// BA workspace (vh_ba.hpp; 0, 0 for a window that was not solved).  One thread per window
+__global__ __launch_bounds__(256) void k_refine_robust_tail(char* recs, size_t rec_bytes, int n, const int* words, size_t words_stride, float delta)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= n) return;
+    const int* c = reinterpret_cast<const int*>(reinterpret_cast<const char*>(words) + (size_t)w * words_stride);
+    int* t = reinterpret_cast<int*>(recs + (size_t)w * rec_bytes + rec_bytes - SESS_ROBUST_TAIL);
+    t[0] = c[1]; t[1] = c[2];
+    reinterpret_cast<float*>(t)[2] = delta;
+    t[3] = 0;
 }
 
 struct RefEntry {  // how a public entry words the refusals both share
@@ -1582,19 +1612,20 @@ static int refine_request(const RefEntry& E, vh_session* s, const void* table, i
     const bool select = E.windows || s->rp.on;  // (replenished session: survivors need not have been alive at frame 0)
     const size_t need = refine_ws_layout(s, n, nf, reinterpret_cast<char*>(workspace), &W, select, part != nullptr);
     if (workspace_bytes < need) return fail("workspace of %zu bytes, %d %s of %d frames need %zu", workspace_bytes, n, E.noun, nf, need);
+    const double robust = s->refine_robust;  // (0: every launch, table and record below is what it is without the option)
     RefView V;
     if (part) {
         vh_refine_partial_record L;
-        refine_partial_record_layout(s->N0, nf, max_iter, with_points, &L);
-        V = refine_view(L.win, L.win.slot, nf, L.win.with_points);
+        refine_partial_record_layout(s->N0, nf, max_iter, with_points, &L, robust);
+        V = refine_view(L.win, L.win.slot, nf, L.win.with_points, robust);
     } else if (E.windows) {
         vh_refine_window_record L;
-        refine_window_record_layout(s->N0, nf, max_iter, with_points, &L);
-        V = refine_view(L, L.slot, nf, L.with_points);
+        refine_window_record_layout(s->N0, nf, max_iter, with_points, &L, robust);
+        V = refine_view(L, L.slot, nf, L.with_points, robust);
     } else {
         vh_refine_record L;
-        refine_record_layout(s->N0, s->nhist, max_iter, &L);
-        V = refine_view(L, L.nt, s->nhist, 1);
+        refine_record_layout(s->N0, s->nhist, max_iter, &L, robust);
+        V = refine_view(L, L.nt, s->nhist, 1, robust);
     }
     char* recs = reinterpret_cast<char*>(recs_dev);
     bool anchored = false;  // the tables travel only when a slot of the request has anchors: otherwise the solve is queued as ever, with no table
@@ -1622,10 +1653,13 @@ static int refine_request(const RefEntry& E, vh_session* s, const void* table, i
     }
     // the windows' info = {iterations, converged} and trace go straight into the records
     int r = vh_ba_windows(s->ctx, s->h_ss[req[0].slot].K, W.z, W.x, s->N0, nf - 1, n, W.nt, W.K, anchored ? W.fixed : nullptr, max_iter, reinterpret_cast<double*>(recs + V.trace),
-                          V.bytes / sizeof(double), reinterpret_cast<int*>(recs + V.info), V.bytes / sizeof(int), W.ba, W.ba_stride, stream);
+                          V.bytes / sizeof(double), reinterpret_cast<int*>(recs + V.info), V.bytes / sizeof(int), W.ba, W.ba_stride, stream, robust);
     if (r) return r;
     VH_BIND(s->ctx, stream);
     each_chunk(k_refine_unpack, bound_.s);
+    if (robust > 0)
+        hipLaunchKernelGGL(k_refine_robust_tail, dim3((n + 255) / 256), dim3(256), 0, bound_.s, recs, V.bytes, n, vh_ba_windows_outlier_words(s->N0, nf - 1, n, W.ba),
+                           W.ba_stride, (float)robust);
     SESS_CHECK();
     return 0;
 }
@@ -1634,7 +1668,7 @@ extern "C" VH_API size_t vh_session_refine_size(const vh_session* s, int max_ite
 {
     if (!s || max_iter < 1) { vh_fail(-1, "vh_session_refine_size: bad arguments"); return 0; }
     vh_refine_record L;
-    refine_record_layout(s->N0, s->nhist, max_iter, &L);
+    refine_record_layout(s->N0, s->nhist, max_iter, &L, s->refine_robust);
     if (layout_host) *layout_host = L;
     return L.bytes;
 }
@@ -1668,7 +1702,7 @@ extern "C" VH_API size_t vh_session_refine_windows_size(const vh_session* s, int
 {
     if (!s || nf < 2 || max_iter < 1) { vh_fail(-1, "vh_session_refine_windows_size: bad arguments"); return 0; }
     vh_refine_window_record L;
-    refine_window_record_layout(s->N0, nf, max_iter, with_points, &L);
+    refine_window_record_layout(s->N0, nf, max_iter, with_points, &L, s->refine_robust);
     if (layout_host) *layout_host = L;
     return L.bytes;
 }
@@ -1711,7 +1745,7 @@ extern "C" VH_API size_t vh_session_refine_windows_partial_size(const vh_session
 {
     if (!s || nf < 2 || max_iter < 1) { vh_fail(-1, "vh_session_refine_windows_partial_size: bad arguments"); return 0; }
     vh_refine_partial_record L;
-    refine_partial_record_layout(s->N0, nf, max_iter, with_points, &L);
+    refine_partial_record_layout(s->N0, nf, max_iter, with_points, &L, s->refine_robust);
     if (layout_host) *layout_host = L;
     return L.win.bytes;
 }

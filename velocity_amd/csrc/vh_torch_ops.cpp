@@ -294,6 +294,40 @@ std::tuple<Tensor, Tensor, Tensor> ba_solve_fixed(const Tensor& K, const Tensor&
     return {x, trace, info};
 }
 
+// ba_solve_fixed with Huber weights of threshold delta pixels (vh_nls_batch_windows_robust; delta = 0: off) -> (x, trace, info, nout int32 [nwin, max_iter])
+std::tuple<Tensor, Tensor, Tensor, Tensor> ba_solve_robust(const Tensor& K, const Tensor& z, const Tensor& x0, int64_t nt, int64_t nc, double delta,
+                                                           const c10::optional<Tensor>& nt_win, const c10::optional<Tensor>& fixed, int64_t max_iter)
+{
+    TORCH_CHECK(z.is_cuda() && x0.is_cuda() && z.dim() == 2 && x0.dim() == 2, "ba_solve_robust: z and x0 must be CUDA tensors [nwin, ..]");
+    const int64_t nz = 2 * nt * (nc + 1), nx = 3 * nt + 6 * nc, nw = z.size(0);
+    TORCH_CHECK(z.size(1) == nz && x0.size(1) == nx && x0.size(0) == nw, "ba_solve_robust: z must hold [nwin, 2 nt (nc+1)] and x0 [nwin, 3 nt + 6 nc] values");
+    TORCH_CHECK(max_iter >= 1, "ba_solve_robust: max_iter must be >= 1");
+    Tensor ntw, fx;
+    if (nt_win.has_value() && nt_win->defined()) {
+        TORCH_CHECK(nt_win->is_cuda() && nt_win->numel() == nw, "ba_solve_robust: nt_win must be a CUDA tensor of nwin counts");
+        ntw = nt_win->to(at::kInt).contiguous();
+    }
+    if (fixed.has_value() && fixed->defined()) {
+        TORCH_CHECK(fixed->is_cuda() && fixed->dim() == 2 && fixed->size(0) == nw && fixed->size(1) == nt, "ba_solve_robust: fixed must be a CUDA tensor [nwin, nt]");
+        fx = fixed->ne(0).to(at::kByte).contiguous();
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(z.device());
+    void* s = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+    double Kh[9];
+    host_K(K, Kh);
+    Tensor zd = z.to(at::kDouble).contiguous(), x = x0.to(at::kDouble).contiguous().clone();
+    auto opt = z.options();
+    const size_t wsb = vh_nls_batch_workspace((int)nt, (int)nc);
+    Tensor scratch = at::empty({nw, (int64_t)wsb}, opt.dtype(at::kByte));
+    Tensor trace = at::zeros({nw, max_iter, 2}, opt.dtype(at::kDouble)), info = at::zeros({nw, 2}, opt.dtype(at::kInt));
+    Tensor nout = at::zeros({nw, max_iter}, opt.dtype(at::kInt));
+    vh_check(vh_nls_batch_windows_robust(workspace(z, 0, 0, 0, s), Kh, zd.data_ptr<double>(), x.data_ptr<double>(), (int)nt, (int)nc, (int)nw,
+                                         ntw.defined() ? ntw.data_ptr<int>() : nullptr, nullptr, fx.defined() ? fx.data_ptr<uint8_t>() : nullptr, delta,
+                                         nout.data_ptr<int>(), (int)max_iter, trace.data_ptr<double>(), info.data_ptr<int>(), scratch.data_ptr(), wsb, s),
+             "vh_nls_batch_windows_robust");
+    return {x, trace, info, nout};
+}
+
 // frame-0 initialisation of a batch of clips (vidExample.py:105-127 for each): frames CUDA uint8 [B,H,W], q [B,4,2] plate corners (host values), K, plate
 // [4,3] world points -> (p [B,cap,2] f32, p3 [B,cap,3] f64, vp [B,cap] u8, t [B,3] f32, R [B,3,3] f64, res [B] f64, n [B] i32, rois [B,8] i32 on the host),
 // cap = 4 + max_corners; row b of each holds what vh_frame0_init gives for clip b (rows beyond n[b]: p 0, p3 0, vp 0)
@@ -438,6 +472,7 @@ TORCH_LIBRARY(velocity_hip, m)
     m.def("two_view_intercept(Tensor A, Tensor U) -> Tensor");
     m.def("msv1_t(Tensor K, Tensor P, Tensor B, Tensor ids, int ii) -> (Tensor, Tensor, Tensor)");
     m.def("ba_solve(Tensor K, Tensor z, Tensor x0, int nt, int nc, int max_iter=10) -> (Tensor, Tensor, Tensor)");
+    m.def("ba_solve_robust(Tensor K, Tensor z, Tensor x0, int nt, int nc, float delta, Tensor? nt_win=None, Tensor? fixed=None, int max_iter=10) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("ba_solve_fixed(Tensor K, Tensor z, Tensor x0, int nt, int nc, Tensor? nt_win=None, Tensor? fixed=None, int max_iter=10) -> (Tensor, Tensor, Tensor)");
     m.def("frame0_init(Tensor frames, Tensor q, Tensor K, Tensor plate, int border_x=700, int border_y=500, int max_corners=1000, float quality=0.01, "
           "int block=5, float k=0.04, int subpix_win=5, int subpix_iter=100, float subpix_eps=0.001, bool use_harris=True, float min_distance=0.0) -> "
@@ -464,6 +499,7 @@ TORCH_LIBRARY_IMPL(velocity_hip, CUDA, m)
     m.impl("msv1_t", &msv1_t);
     m.impl("ba_solve", &ba_solve);
     m.impl("ba_solve_fixed", &ba_solve_fixed);
+    m.impl("ba_solve_robust", &ba_solve_robust);
     m.impl("frame0_init", &frame0_init);
     m.impl("good_features", &good_features);
     m.impl("match_affine", &match_affine);

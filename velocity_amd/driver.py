@@ -15,7 +15,7 @@ from . import _lib as L
 
 class TrackerSession:
     def __init__(self, K, width, height, n0, nhist=20, batch=1, lk_coarse=None, lk_fine=None, msv_frame=5, fallback=False, fallback_params=None,
-                 replenish=None, spare=0, replenish_settings=None):
+                 replenish=None, spare=0, replenish_settings=None, refine_robust=None):
         """width x height: the LARGEST frame a slot can hold; K: the camera a slot has until init_stream / admit gives it another (vh_session_set_camera).
         fallback=True (default off: a step queues exactly what it always did): the recovery branch of KLTmain (KLT.py:130-133) for a stream whose coarse
         stage fails -- the affine from feature matching (vh_match_affine_batch over the failed streams; `fallback_params`: _lib.MATCH_DEFAULTS keys)
@@ -25,7 +25,7 @@ class TrackerSession:
         than rows (init_stream with fewer points, admit with settings.cap below the rows).  replenish: None (default: a step queues exactly what it always
         did), or a Replenish: lost tracks are replaced by new corners in the spare rows and triangulated on the device (vh_session_set_replenish);
         replenish_settings: the Frame0Settings whose detector and sub-pixel settings the births use (default: the reference's).  state() then gains
-        born, tri and n_rows."""
+        born, tri and n_rows.  refine_robust: None, or the Huber threshold in pixels of every refinement (set_refine_robust)."""
         torch = L.torch_cuda()
         self.torch = torch
         self.spare = int(spare)
@@ -59,6 +59,18 @@ class TrackerSession:
         self._keep = [None] * batch
         self._init_keep = [None] * batch
         self._frame_i = [0] * batch  # host mirror of every slot's frame counter (refine: a clip is finished when it has had all its frames)
+        self.refine_robust = 0.0
+        if refine_robust is not None:
+            self.set_refine_robust(refine_robust)
+
+    def set_refine_robust(self, delta):
+        """Huber weights for every refinement of this session from now on (vh_session_set_refine_robust): delta pixels, finite and >= 0; 0 (the default)
+        turns them off.  refine() and refine_windows() (with or without min_obs) then weight a measurement whose reprojection error |r| exceeds delta by
+        delta / |r|, in every iteration, and their dicts gain robust, nout_first and nout_last: the threshold and how many measurements were
+        down-weighted at the first and at the last iteration run.  A host setting: nothing is queued.  The records grow by 16 bytes while it is on, so
+        the layouts are kept per setting."""
+        L.check(self.lib.vh_session_set_refine_robust(self.handle, float(delta)), "vh_session_set_refine_robust")
+        self.refine_robust = float(delta)
 
     def slot_size(self, slot):
         """(H, W) of the frames slot `slot` takes."""
@@ -345,12 +357,14 @@ class TrackerSession:
     def refine_layout(self, max_iter=10):
         """vh_refine_record of this session for max_iter iterations: byte offsets of the fields of a refined clip's record (and `bytes`, its size)."""
         lays = self.__dict__.setdefault("_refine_layouts", {})
-        if max_iter not in lays:
+        key = (int(max_iter), self.refine_robust)  # (the record has a tail while the session refines with Huber weights)
+        if key not in lays:
             lay = L.RefineRecord()
             if not self.lib.vh_session_refine_size(self.handle, int(max_iter), C.byref(lay)):
                 L.check(-1, "vh_session_refine_size")
-            lays[max_iter] = lay
-        return lays[max_iter]
+            lay.robust = self.refine_robust
+            lays[key] = lay
+        return lays[key]
 
     def _refine_request(self, call, items, lay, nf, out, chunk, need):
         """THE refinement request behind refine() and refine_windows(): `items` (slots or windows) go to the library `chunk` at a time -- call(part, recs)
@@ -401,11 +415,12 @@ class TrackerSession:
         """vh_refine_window_record of this session for windows of nf frames: byte offsets of the fields of a refined window's record (and `bytes`).
         partial: vh_refine_partial_record, the record of a refine_windows(min_obs=...) request (.win: the window record's offsets; then the counts')."""
         lays = self.__dict__.setdefault("_refine_window_layouts", {})
-        key = (int(nf), int(max_iter), bool(with_points)) + ((True,) if partial else ())
+        key = (int(nf), int(max_iter), bool(with_points), bool(partial), self.refine_robust)
         if key not in lays:
             lay, fn = (L.RefinePartialRecord(), "vh_session_refine_windows_partial_size") if partial else (L.RefineWindowRecord(), "vh_session_refine_windows_size")
             if not getattr(self.lib, fn)(self.handle, key[0], key[1], int(key[2]), C.byref(lay)):
                 L.check(-1, fn)
+            lay.robust = self.refine_robust
             lays[key] = lay
         return lays[key]
 
@@ -520,8 +535,12 @@ def _unpack_refined(raw, lay, nf=None):
     """THE reader of a refinement record of either layout (uint8 array `raw`, offsets `lay`): the header words, the first nf of the record's rows of cw, dr
     and speed, the scalars, the trace and -- where the record carries them -- ids and pw; every array is a copy."""
     counts = {}
+    if getattr(lay, "robust", 0.0):  # the 16-byte tail of a record refined with Huber weights: nout_first, nout_last, delta (float32), 0
+        nbytes = lay.win.bytes if isinstance(lay, L.RefinePartialRecord) else lay.bytes
+        first, last = np.frombuffer(raw, np.int32, 2, nbytes - 16)
+        counts = dict(robust=float(np.frombuffer(raw, np.float32, 1, nbytes - 8)[0]), nout_first=int(first), nout_last=int(last))
     if isinstance(lay, L.RefinePartialRecord):  # the window record, then the four counts
-        counts = {k: int(np.frombuffer(raw, np.int32, 1, getattr(lay, k))[0]) for k in ("nobs", "npart", "ntri", "nrej")}
+        counts.update({k: int(np.frombuffer(raw, np.int32, 1, getattr(lay, k))[0]) for k in ("nobs", "npart", "ntri", "nrej")})
         lay = lay.win
     window = isinstance(lay, L.RefineWindowRecord)
 
@@ -601,8 +620,10 @@ def merge_window_speeds(n, windows):
 
 def _merged_ba(n, wins, window, stride):
     """result["ba"] of a clip refined in windows: merge_window_speeds' dict with `window` and `stride`; windows refined with min_obs (their dicts carry
-    the counts) add the per-window arrays nobs, npart, ntri, nrej."""
-    counts = {k: np.array([w[k] for w in wins], np.int64) for k in ("nobs", "npart", "ntri", "nrej") if wins and k in wins[0]}
+    the counts) add the per-window arrays nobs, npart, ntri, nrej, and windows refined with Huber weights `robust` and the arrays nout_first, nout_last."""
+    counts = {k: np.array([w[k] for w in wins], np.int64) for k in ("nobs", "npart", "ntri", "nrej", "nout_first", "nout_last") if wins and k in wins[0]}
+    if wins and "robust" in wins[0]:  # refined with Huber weights: the threshold, and the counts per window
+        counts["robust"] = wins[0]["robust"]
     return dict(merge_window_speeds(n, wins), window=window, stride=stride, **counts)
 
 
@@ -659,20 +680,39 @@ def _refine_finished(ses, clips, win, stride, partial=None):
 def ba_line(ba):
     """The line a refined clip adds behind the reference's summary (a clip refined in windows: their count and length, the fewest and the most tracks of a
     window, the largest last rms residual among them).  A refinement that was asked to anchor (ba["anchor"], set by the drivers' refine_anchor) also says
-    how many of its tracks were anchored -- the fewest and the most of a window -- since 0 means the solve ran free; otherwise the line is what it was."""
+    how many of its tracks were anchored -- the fewest and the most of a window -- since 0 means the solve ran free; one refined with Huber weights
+    (ba["robust"]) how many of its measurements were down-weighted at the last iteration; otherwise the line is what it was."""
+    def huber(measurements):
+        if "robust" not in ba:
+            return ""
+        return f", huber {ba['robust']:g} px: {int(np.sum(ba['nout_last']))} of {int(measurements)} measurements down-weighted"
+
     if "window" in ba:
         anchors = f", {np.min(ba['nfix'])}-{np.max(ba['nfix'])} anchors" if "anchor" in ba else ""
         if "npart" in ba:  # refined with min_obs: how many of the windows' tracks live through part of their window, how many starts were triangulated
             anchors += f", {int(ba['npart'].sum())} partial of {int(ba['nt'].sum())}, {int(ba['ntri'].sum())} starts triangulated ({int(ba['nrej'].sum())} rejected)"
+        anchors += huber(ba["nobs"].sum() if "nobs" in ba else ba["nt"].sum() * ba["window"])
         return (f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({len(ba['first'])} windows of {ba['window']} frames, "
                 f"{ba['nt'].min()}-{ba['nt'].max()} tracks{anchors}, f = {np.nanmax(ba['f_last']) if np.isfinite(ba['f_last']).any() else np.nan:.3f} pixels)")
-    anchors = f", {ba['nfix']} anchors" if "anchor" in ba else ""
+    anchors = (f", {ba['nfix']} anchors" if "anchor" in ba else "") + (huber(ba["nt"] * len(ba["speed"])) if "robust" in ba else "")
     return f"BA speed = {ba['speed_mean']:.2f} +/- {ba['speed_std']:.2f} km/h ({ba['nt']:g} tracks{anchors}, f = {ba['f_last']:.3f} pixels)"
 
 
 def _tag_anchor(ba, refine_anchor):
     """A clip's refinement (either form) marked with what it was asked to anchor; None: untouched."""
     return ba if refine_anchor is None or ba is None else dict(ba, anchor=refine_anchor)
+
+
+def _check_robust(refine, refine_robust=None):
+    """-> None (no Huber weights: the option is absent or 0), or the threshold in pixels; raises ValueError by name before anything is queued."""
+    if refine_robust is None:
+        return None
+    if refine != "ba":
+        raise ValueError("refine_robust needs refine='ba'")
+    d = float(refine_robust)
+    if not (np.isfinite(d) and d >= 0.0):
+        raise ValueError(f"refine_robust = {refine_robust}: a finite number of pixels >= 0 (0 = off)")
+    return d or None
 
 
 def _check_refine(refine, refine_window=None, refine_stride=None, refine_anchor=None):
@@ -1020,7 +1060,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
                  block=5, harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, route="session", live=True,
                  out=print, clock=None, name="sequence", use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
                  refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0, refine_min_obs=None,
-                 refine_start_reproj=None):
+                 refine_start_reproj=None, refine_robust=None):
     """The packaged counterpart of vidExample.py:52-178 (minus video decode and plots) on one clip.
 
     frames  sequence of n uint8 [H, W] gray frames (numpy arrays or CUDA tensors): what `cv2.cvtColor(cap.read(), BGR2GRAY)` / `cv2.imread(.., 0)` hands
@@ -1055,6 +1095,11 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
             those whose two-view start reprojects within R (TrackerSession.refine_windows(min_obs=, start_reproj=)).  Without refine_window the clip is
             ONE window of its own length (at most 256 frames).  "ba" is then the windowed dict plus, per window, nobs, npart, ntri, nrej, and the BA
             line says how many tracks are partial and how many starts were triangulated.
+    refine_robust   None (default: plain least squares, nothing changes), or the Huber threshold D in pixels (needs refine="ba"): in every iteration a
+            measurement whose reprojection error |r| exceeds D is weighted by D / |r| (TrackerSession.set_refine_robust), so a few wrong measurements
+            no longer decide the speed.  "ba" gains `robust`, `nout_first` and `nout_last` (per window in the windowed form): how many measurements
+            were down-weighted at the first and the last iteration, and the BA line says the latter.  f stays the unweighted rms residual.  What it
+            does not do: choose D, or any loss but Huber's.
     replenish, spare   None (default: nothing new is queued), or a Replenish: the session gets `spare` rows behind the 4 + max_corners of frame 0, lost
             tracks are replaced by new corners there and triangulated on the device (TrackerSession(replenish=...); detector and sub-pixel settings: the
             frame-0 ones).  The result's track rows are then the rows used, it gains "replenish" (replenish_result) and one line follows the summary.
@@ -1066,6 +1111,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
 
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     partial = _check_partial(refine, refine_min_obs, refine_start_reproj)
+    robust = _check_robust(refine, refine_robust)
     refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     if route != "session":
         raise ValueError("route must be 'session' (the host loop on the drop-in functions is a measurement harness: tools/dropin_loop.py::run_sequence_dropin)")
@@ -1084,7 +1130,7 @@ def run_sequence(frames, q, K, fps=None, times=None, frame_numbers=None, plate="
     dev = _to_device(frames, non_blocking=True)
     H, W = dev[0].shape
     ses = _SessionSet(1, 1, max_corners).create(K, W, H, settings, n, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback,
-                                                 fallback_params=fallback_params, **_replenish_kw(replenish, spare, settings))[0]
+                                                 fallback_params=fallback_params, refine_robust=robust, **_replenish_kw(replenish, spare, settings))[0]
     f0 = ses.admit([(0, dev[0], q, times[0], frame_numbers[0])], settings, anchor=refine_anchor)[0]
     view = ses.view(0)
     proc = np.zeros(n)
@@ -1186,7 +1232,7 @@ class _SessionSet:
 def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5, harris_k=0.04, subpix=(5, 100, 0.001),
                   msv_frame=5, lk_coarse=None, lk_fine=None, out=None, sessions=0, use_harris=True, min_distance=0.0, fallback=False, fallback_params=None, refine=None,
                   refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0, refine_min_obs=None,
-                 refine_start_reproj=None):
+                 refine_start_reproj=None, refine_robust=None):
     """Many clips at once: the throughput form of run_sequence.  `clips` = list of dict(frames, q, times[, frame_numbers, name, K]) of ONE length -- the
     frame size and the intrinsics are each clip's own ("K": that clip's camera, default the K argument); the sessions are created at the elementwise
     maximum of the sizes and a frame step is sized for it, so clips of one camera type batch best.  One length stays required: a step advances every
@@ -1200,10 +1246,12 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     run_sequence; all the clips of a session are refined by ONE TrackerSession.refine after the last frame -- with refine_window=W (and clips of at least
     W frames) all the windows of all the clips of a session by ONE TrackerSession.refine_windows request.  refine_anchor="plate": as in run_sequence,
     for every clip.  refine_min_obs, refine_start_reproj: as in run_sequence (without refine_window: the clips of a session are ONE request of
-    one-window clips).  replenish, spare: as in run_sequence, for every clip (the births of all the streams of a session are one launch sequence)."""
+    one-window clips).  refine_robust: as in run_sequence, for every clip.  replenish, spare: as in run_sequence, for every clip (the births of all the
+    streams of a session are one launch sequence)."""
     import time as _time
 
     partial = _check_partial(refine, refine_min_obs, refine_start_reproj)
+    robust = _check_robust(refine, refine_robust)
     refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
@@ -1218,7 +1266,7 @@ def run_sequences(clips, K, plate="Chile", roi_border=(700, 500), max_corners=10
     for hs in group.hip_streams[1:]:
         hs.wait_stream(group.hip_streams[0])  # the frame uploads above ran on the current stream
     sess = group.create(K, W, H, settings, n, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params,
-                        **_replenish_kw(replenish, spare, settings))
+                        refine_robust=robust, **_replenish_kw(replenish, spare, settings))
     members = [list(range(a, a + size)) for a, size in zip(group.first, group.sizes)]  # session -> its clips, in slot order
     times = np.stack([np.asarray(c["times"], np.float32) for c in clips])  # [clip, frame]
     fnos = np.stack([np.asarray(c.get("frame_numbers", np.arange(n)), np.float32) for c in clips])
@@ -1319,7 +1367,7 @@ def queue_plan(lengths, streams, sessions=1):
 def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, max_size=None, plate="Chile", roi_border=(700, 500), max_corners=1000, quality=0.01, block=5,
               harris_k=0.04, subpix=(5, 100, 0.001), msv_frame=5, lk_coarse=None, lk_fine=None, out=None, use_harris=True, min_distance=0.0, fallback=False,
               fallback_params=None, refine=None, refine_window=None, refine_stride=None, refine_anchor=None, replenish=None, spare=0, refine_min_obs=None,
-                 refine_start_reproj=None):
+                 refine_start_reproj=None, refine_robust=None):
     """A queue of clips of ANY length on `streams` resident streams: what run_sequences is for clips of one length.  `clips` = any iterable of
     dict(frames, q, times[, frame_numbers, name, K]), each of >= 2 frames and with its own frame size and intrinsics ("K": default the K argument); it is consumed lazily -- a clip is pulled when a slot is free
     for it and its frames go up then, so at most `streams` clips are resident -- and may hold more clips than fit on the device at once.
@@ -1342,11 +1390,13 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
     refine_window=W (refine_stride: as in run_sequence): the clips of at least W frames that finish at a step go through ONE TrackerSession.refine_windows
     request of their session, whatever their lengths (their "ba" is the merged dict); the per-length calls remain for clips shorter than W.
     refine_anchor="plate": as in run_sequence, for every clip (a slot's anchors are set at its clip's admission and cleared by the next one).
+    refine_robust=D: as in run_sequence, for every clip (a setting of the sessions, made when they are created).
     replenish, spare: as in run_sequence, for every clip.  A finished clip's born / tri are read right behind its export (vh_session_replenish_state
     waits for the device: with the option on the loop waits once per finished clip)."""
     import time as _time
 
     partial = _check_partial(refine, refine_min_obs, refine_start_reproj)
+    robust = _check_robust(refine, refine_robust)
     refine, win, stride = _check_refine(refine, refine_window, refine_stride, refine_anchor)
     settings = Frame0Settings(plate, roi_border, max_corners, quality, block, harris_k, subpix, use_harris, min_distance)
     torch = L.torch_cuda()
@@ -1424,7 +1474,7 @@ def run_queue(clips, K, streams, max_frames=None, sessions=0, on_result=None, ma
         if not sess:  # the first clips have been pulled: the (largest) frame size is known
             H, W = size[0]
             group.create(K, W, H, settings, nhist, lk_coarse=lk_coarse, lk_fine=lk_fine, msv_frame=msv_frame, fallback=fallback, fallback_params=fallback_params,
-                         **_replenish_kw(replenish, spare, settings))
+                         refine_robust=robust, **_replenish_kw(replenish, spare, settings))
             for ses, hs in zip(sess, group.hip_streams):
                 with torch.cuda.stream(hs):  # the frame-0 scratch for a full house, so that no later admission grows it (growing waits for the stream)
                     L.check(ses.lib.vh_init_reserve_batch(ses.ws.handle, ses.batch, W, H, L.stream_ptr()), "vh_init_reserve_batch")
@@ -1541,6 +1591,8 @@ def main(argv=None):
     ap.add_argument("--refine-start-reproj", type=float, default=None, metavar="R",
                     help="with --refine-min-obs: tracks without a trusted world point start from a two-view triangulation that reprojects within R pixels")
     ap.add_argument("--refine-anchor", choices=["plate"], default=None, help="with --refine ba: hold the four plate corners fixed in the adjustment (a metric scale from the plate)")
+    ap.add_argument("--refine-robust", type=float, default=None, metavar="PX",
+                    help="with --refine ba: Huber weights, a measurement whose reprojection error exceeds PX pixels is down-weighted in every iteration")
     ap.add_argument("--replenish", type=int, nargs="?", const=5, default=None, metavar="EVERY",
                     help="replace lost tracks with new corners every EVERY frames (default 5) and triangulate them on the device")
     ap.add_argument("--spare", type=int, default=256, metavar="ROWS", help="with --replenish: rows for new tracks behind the frame-0 ones")
@@ -1552,7 +1604,7 @@ def main(argv=None):
     run_sequence(fr, d[f"{a.seq}_q"], d[f"{a.seq}_K"], times=d[f"{a.seq}_times"], roi_border=border, msv_frame=a.msv_frame,
                  name=f"{a.clip}:{a.seq}", use_harris=not a.shi_tomasi, min_distance=a.min_distance, fallback=a.fallback, refine=a.refine,
                  refine_window=a.refine_window, refine_stride=a.refine_stride, refine_anchor=a.refine_anchor,
-                 refine_min_obs=a.refine_min_obs, refine_start_reproj=a.refine_start_reproj,
+                 refine_min_obs=a.refine_min_obs, refine_start_reproj=a.refine_start_reproj, refine_robust=a.refine_robust,
                  replenish=None if a.replenish is None else Replenish(every=a.replenish), spare=a.spare if a.replenish is not None else 0)
 
 
